@@ -10,6 +10,10 @@ whole-job rate).  Other BASELINE configs are parity-test cases; `--workload` tim
 
     python bench.py --gpus 1 --steps 20 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what the headline figure does not need: further
+timed windows, the clocks under load, the device-copy ceiling, the f32-tap kernel's figure, the CPU oracle's baseline and the DFPWM
+redo counters.  `--dump-outputs DIR` writes a fixed sample of what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -188,6 +192,67 @@ def _copy_ceiling(torch, nbytes_traffic, reps=12):
     return best, how
 
 
+DUMP_SEED = 0xA0C17
+DUMP_ROWS, DUMP_ROW_ELEMS, DUMP_SAMPLE_ELEMS = 8, 4 << 20, 1 << 20   # at most 8 B x (4 Mi + 1 Mi) elements + the lengths per output
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _dump_outputs(torch, dev, ctx, wl, outdir):
+    """--dump-outputs: for every output of the step just timed (Workload.outputs), read where the library left it —
+      <name>_lengths.npy  every stream's row length (float64);
+      <name>_rows.npy     the rows of DUMP_ROWS streams picked with a fixed seed, [stream][channel][sample] back to back, each row cut to
+                          DUMP_ROW_ELEMS / (streams x channels) samples at most;
+      <name>_sample.npy   DUMP_SAMPLE_ELEMS elements drawn with a fixed seed over every row of every stream, in row order.
+    f64 rows stay float64; f32 and int8 rows, and byte outputs, are written as float32 (exact).  Nothing is computed again."""
+    from aukit_amd import batch as B
+    from aukit_amd import shard
+    import numpy as np
+    ctx.sync()
+    torch.cuda.synchronize()
+    os.makedirs(outdir, exist_ok=True)
+    written = 0
+    for name, o in wl.outputs():
+        if isinstance(o, B.AudioBatch):
+            ptr = o.device_ptr()   # (pays whatever deferred work is still owed on the rows, as a caller's read does)
+            if not ptr:
+                raise RuntimeError(f"--dump-outputs: {name}: the library returned no rows")
+            inf = o.info()
+            lens, off, stride = o.layout()
+            ch = int(inf["channels"])
+            tdt, ndt = {0: (torch.float64, np.float64), 1: (torch.float32, np.float32), 2: (torch.int8, np.float32)}[inf["dtype"]]
+            flat = shard.device_view(ptr, int(inf["total_elems"]) * torch.empty(0, dtype=tdt).element_size(), dev, keep=o).view(tdt)
+        else:
+            offs = o.offsets()
+            lens, off, stride = np.diff(offs), offs[:-1], np.zeros(len(offs) - 1, dtype=np.uint64)
+            ch, ndt = 1, np.float32
+            flat = shard.device_view(o.device_ptr(), int(offs[-1]), dev, keep=o)
+        lens, off, stride = (np.asarray(a, dtype=np.int64) for a in (lens, off, stride))
+        n = len(lens)
+        rng = np.random.default_rng(DUMP_SEED)
+        picked = np.sort(rng.choice(n, min(DUMP_ROWS, n), replace=False)) if n else np.zeros(0, dtype=np.int64)
+        keep = DUMP_ROW_ELEMS // max(len(picked) * ch, 1)
+        rows = [flat[off[s] + c * stride[s]:off[s] + c * stride[s] + min(int(lens[s]), keep)] for s in picked for c in range(ch)]
+        per = lens * ch
+        total = int(per.sum())
+        u = np.unique(rng.integers(0, total, DUMP_SAMPLE_ELEMS)) if total > DUMP_SAMPLE_ELEMS else np.arange(total, dtype=np.int64)
+        cum = np.cumsum(per)
+        s = np.searchsorted(cum, u, side="right")
+        r = u - (cum[s] - per[s])
+        c, i = r // lens[s], r % lens[s]
+        idx = off[s] + c * stride[s] + i
+        if n and (int((off + np.maximum(ch * stride, lens)).max()) > flat.numel() or (len(idx) and int(idx.max()) >= flat.numel())):
+            raise RuntimeError(f"--dump-outputs: {name}: the layout reaches past the {flat.numel()} elements of the buffer")
+        idx = torch.from_numpy(idx).to(dev)
+        arrays = {"lengths": lens.astype(np.float64),
+                  "rows": torch.cat(rows).cpu().numpy().astype(ndt) if rows else np.zeros(0, dtype=ndt),
+                  "sample": flat[idx].cpu().numpy().astype(ndt)}
+        for part, arr in arrays.items():
+            written += arr.nbytes
+            if written > DUMP_MAX_BYTES:
+                raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES} bytes")
+            np.save(os.path.join(outdir, f"{name}_{part}.npy"), arr)
+
+
 class Workload:
     """setup(torch, dev, ctx, args, rank) → self; step() runs one pass; out_samples = units per pass on this rank.
     task_bytes(): END-TO-END algorithmic bytes of one step — the input read once + the final output written once (what the roofline
@@ -227,6 +292,10 @@ class Workload:
 
     def task_bytes(self):
         return None
+
+    def outputs(self):
+        """[(name, AudioBatch or Batch)]: what a caller of the timed path holds when a step ends (--dump-outputs)"""
+        return [("out", self.out)]
 
     # ---- the distribution leg (--distribute 1, SURVEY 8e's second curve): workloads that have one define
     #   dist_whole(torch, ctx, B, args, world) -> the Batch of EVERY rank's shard, resident on rank 0 (the same synthetic content `world` times);
@@ -639,6 +708,9 @@ class DfpwmTranscode(Workload):
     def task_bytes(self):
         return int(self.x.numel()) + int(self.outb.info()[1])
 
+    def outputs(self):
+        return [("dfpwm", self.outb)]
+
     def extra(self, ctx, N):
         """the chunk-parallel decoder's redo count on this input (one more, untimed, step with the counters on)"""
         ctx.set_option(N.OPT_COLLECT_STATS, 1)
@@ -703,6 +775,9 @@ class FlacPipeline(Workload):
     def out_samples(self):
         return int(self.m.layout()[0].sum())
 
+    def outputs(self):
+        return [("mono", self.m)]
+
     def task_bytes(self):
         return int(self.x.numel()) + self.out_samples() * (4 if self.dtype == 1 else 8)
 
@@ -732,6 +807,9 @@ class SelftestNull(Workload):
 
     def out_samples(self):
         return 1000
+
+    def outputs(self):
+        return []
 
 
 WORKLOADS = {w.name: w for w in (SelftestNull, Pcm16Cubic, Pcm16Stereo, Pcm16Stream, Pcm16StereoStream, G711Cubic, G711Stream, ImaStream, ImaPipeline, MsadpcmStream, QoaStream, DfpwmTranscode, FlacPipeline)}
@@ -839,8 +917,13 @@ def main(argv=None):
     ap.add_argument("--streams", type=int, default=None, help="streams per GPU (default 4096; 16384 for dfpwm_transcode)")
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"], help="STORAGE type of the output rows")
-    ap.add_argument("--cpu-streams", type=int, default=1024, help="most streams timed on the CPU oracle (0 disables the cpu_baseline leg)")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="about how long the one-thread CPU leg runs (the all-cores leg runs about half as long again)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: --extra-windows (default 4), the clocks under load, the copy ceiling, "
+                         "the f32-tap line, the CPU oracle's baseline, the DFPWM redo counters")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed, seeded sample of what the last step computed (rank 0's) as DIR/<name>.npy")
+    ap.add_argument("--cpu-streams", type=int, default=1024, help="--full: most streams timed on the CPU oracle (0 disables the cpu_baseline leg)")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="--full: about how long the one-thread CPU leg runs (the all-cores leg runs about half as long again)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default): --streams per GPU whatever N; strong: --streams is the TOTAL, cut into N contiguous shares (aukit_partition's rule)")
     ap.add_argument("--min-seconds", type=float, default=0.0,
@@ -849,9 +932,11 @@ def main(argv=None):
     ap.add_argument("--exact-math", type=int, default=None,
                     help="arithmetic behind f32 storage: 1 = fp64 (the reference computes in doubles; default for pcm16_cubic, the driver's line), "
                          "2 = fp64 in the reference's operation order, 0 = f32 taps (default for the other workloads)")
-    ap.add_argument("--extra-windows", type=int, default=4, help="further K-step windows timed after the contractual one (spread of the measurement)")
-    ap.add_argument("--fast-line", type=int, default=1, help="pcm16_cubic: also time the f32-tap kernel and report it as roofline_fast")
-    ap.add_argument("--copy-line", type=int, default=1, help="pcm16_cubic: also time a device copy of the same traffic on this box (roofline.copy_ceiling_GBs, frac_of_copy)")
+    ap.add_argument("--extra-windows", type=int, default=None,
+                    help="further K-step windows timed after the contractual one (spread of the measurement; default 4 with --full, else 0)")
+    ap.add_argument("--fast-line", type=int, default=1, help="pcm16_cubic, --full: also time the f32-tap kernel and report it as roofline_fast")
+    ap.add_argument("--copy-line", type=int, default=1,
+                    help="pcm16_cubic, --full: also time a device copy of the same traffic on this box (roofline.copy_ceiling_GBs, frac_of_copy)")
     ap.add_argument("--distribute", type=int, default=0,
                     help="1: after the measurement, ALSO time the distribution variant (rank 0 holds every rank's input in its HBM: device-to-device "
                          "scatter over RCCL, one pass, gather of the output rows to rank 0) and report it as `distribute` — a second number, never `value`")
@@ -860,6 +945,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.streams is None:
         args.streams = {"dfpwm_transcode": 16384, "flac_pipeline": 2048, "pcm16_stereo": 2048, "pcm16_stereo_stream": 2048}.get(args.workload, 4096)
+    if args.extra_windows is None:
+        args.extra_windows = 4 if args.full else 0
     if args.exact_math is None:
         args.exact_math = 1 if args.workload in ("pcm16_cubic", "g711_cubic", "pcm16_stream") else 0   # the workloads that have an fp64-arithmetic wave kernel
     selftest = args.workload == "selftest_null"
@@ -970,8 +1057,8 @@ def main(argv=None):
             want = int(tw.item())
         args.steps = max(args.steps, want)
     def clocks_under_load():
-        """the clocks while steps are running (an idle GPU drops to its lowest level at once: sampled behind a sync they say nothing)"""
-        if selftest:
+        """the clocks while steps are running (an idle GPU drops to its lowest level at once: sampled behind a sync they say nothing); --full only"""
+        if selftest or not args.full:
             return None
         for _ in range(max(4, min(64, per_sync))):
             wl.step()
@@ -982,6 +1069,8 @@ def main(argv=None):
     dt, ev_ms, n_launch, alg_total = timed_window()  # THE measurement: exactly K steps
     out_samples = wl.out_samples()
     name = ctx.last_kernel()[0] if ctx else "none"
+    if args.dump_outputs and rank == 0 and not selftest:
+        _dump_outputs(torch, dev, ctx, wl, args.dump_outputs)   # the last timed step's outputs, before anything else runs on them
     if world > 1:
         dt, total_samples = reduce_over_ranks(dist, torch, rdev, dt, out_samples)
     else:
@@ -1015,14 +1104,14 @@ def main(argv=None):
         else:
             ranks_info = [me]
     copy_gbs, copy_how = None, None
-    if not selftest and world == 1 and args.copy_line and args.workload == "pcm16_cubic":
+    if args.full and not selftest and world == 1 and args.copy_line and args.workload == "pcm16_cubic":
         try:
             copy_gbs, copy_how = _copy_ceiling(torch, wl.task_bytes() if hasattr(wl, "task_bytes") and wl.task_bytes() else 11476992000)
         except Exception as e:
             copy_gbs, copy_how = None, f"{type(e).__name__}: {e}"
 
     fast = None
-    if not selftest and args.workload == "pcm16_cubic" and args.exact_math != 0 and args.fast_line and args.dtype == "f32":
+    if args.full and not selftest and args.workload == "pcm16_cubic" and args.exact_math != 0 and args.fast_line and args.dtype == "f32":
         ctx.set_option(N.OPT_EXACT_MATH, 0)  # the f32-tap kernel on the same batch: a secondary figure, never `value`
         for _ in range(args.warmup):
             wl.step()
@@ -1119,7 +1208,7 @@ def main(argv=None):
                 line["issue"] = {"bound": "valu", "achieved": ach, "peak": peak, "unit": "T lane-instructions/s", "frac": ach / peak, "per_unit": per, "counted": what}
             if wl.distinct:
                 line["config"]["distinct_streams"] = wl.distinct
-            if hasattr(wl, "extra"):
+            if args.full and hasattr(wl, "extra"):
                 line["config"].update(wl.extra(ctx, N))
         if fast:
             fa = fast[2] / (fast[1] * 1e-3) / 1e9
@@ -1130,7 +1219,7 @@ def main(argv=None):
             line["ranks"] = ranks_info
         if distribute:
             line["distribute"] = distribute
-        if world == 1 and args.cpu_streams > 0:
+        if args.full and world == 1 and args.cpu_streams > 0:
             cb = wl.cpu_baseline(args)
             if cb:
                 line["cpu_baseline"] = cb

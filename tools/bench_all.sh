@@ -1,14 +1,15 @@
 #!/bin/bash
-# runs every bench workload once, appends the JSON lines to gpurun_out/bench_lines.jsonl and prints a compact summary (GPU box)
-mkdir -p gpurun_out
-: > gpurun_out/bench_lines.jsonl
-python bench.py --cpu-seconds ${CPU_SECONDS:-4} 2>/dev/null | tail -1 >> gpurun_out/bench_lines.jsonl
+# runs every bench workload once with --full, appends the JSON lines to $OUT/bench_lines.jsonl (default bench_out/) and prints a compact summary (GPU box)
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
+: > "$OUT/bench_lines.jsonl"
+python bench.py --full --cpu-seconds ${CPU_SECONDS:-4} 2>/dev/null | tail -1 >> "$OUT/bench_lines.jsonl"
 for w in pcm16_stream pcm16_stereo pcm16_stereo_stream g711_cubic g711_stream ima_stream ima_pipeline msadpcm_stream qoa_stream dfpwm_transcode flac_pipeline; do
-  python bench.py --workload $w --steps ${STEPS:-5} --warmup 3 --cpu-seconds ${CPU_SECONDS:-4} 2>/dev/null | tail -1 >> gpurun_out/bench_lines.jsonl
+  python bench.py --full --workload $w --steps ${STEPS:-5} --warmup 3 --cpu-seconds ${CPU_SECONDS:-4} 2>/dev/null | tail -1 >> "$OUT/bench_lines.jsonl"
 done
-python - <<'PY'
-import json
-for l in open("gpurun_out/bench_lines.jsonl"):
+OUT="$OUT" python - <<'PY'
+import json, os
+for l in open(os.path.join(os.environ["OUT"], "bench_lines.jsonl")):
     try:
         d = json.loads(l); r = d["roofline"]
         c = d.get("cpu_baseline") or {}

@@ -13,7 +13,7 @@ n = 0
 for f in sorted(glob.glob(os.path.join(src, "r1_*.csv")) + glob.glob(os.path.join(src, "r1_*_timeline.txt"))):
     shutil.copy(f, os.path.join(dst, "r%s_%s" % (rnd, os.path.basename(f)[3:])))
     n += 1
-shutil.copy(os.path.join(root, "gpurun_out", "bench_lines.jsonl"), os.path.join(dst, "r%s_bench_lines.jsonl" % rnd))
+shutil.copy(os.path.join(root, os.environ.get("OUT", "bench_out"), "bench_lines.jsonl"), os.path.join(dst, "r%s_bench_lines.jsonl" % rnd))   # tools/bench_all.sh's lines
 
 # kernel name as bench.py reports it (ctx.last_kernel) -> (tag, substring of the rocprofv3 kernel name)
 DOMINANT = [("k_wave_f64<pcm_s16le_mono,cubic,tile640,phase_regs>", "wavef64", "k_wave_f64", 4096),
