@@ -1472,7 +1472,8 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
                     w[4 * r + 2] = (float)(-1.5L * f3 + 2.0L * f2 + 0.5L * f); w[4 * r + 3] = (float)(0.5L * f3 - 0.5L * f2);
                 }
             }
-            if ((rc = upload_table(ctx, ctx->tmp_buf3, w.data(), w.size() * 4))) { delete ck; return rc; }
+            DevBuf &S3 = ctx_scratch3(ctx);
+            if ((rc = upload_table(ctx, S3, w.data(), w.size() * 4))) { delete ck; return rc; }
             P.bps = 0;
             if (in->n) {
                 const uint64_t b1 = blk0[1] - blk0[0];
@@ -1490,7 +1491,7 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
                 const unsigned grid = (unsigned)std::min<uint64_t>((nblocks + 3) / 4, (uint64_t)ctx->num_cus * per_cu * gmul);
                 lap("tables");
                 if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
-                const float *wgp = reinterpret_cast<const float *>(ctx->tmp_buf3.p);
+                const float *wgp = reinterpret_cast<const float *>(S3.p);
                 // the phases in registers when a lane meets 3 or 5 of them (fb = 3 · 2^i or 5 · 2^i, i <= 6: 22 050 and 44 100 Hz have 5)
                 unsigned g64 = P.fb, h64 = 64;
                 while (h64) { const unsigned r = g64 % h64; g64 = h64; h64 = r; }

@@ -235,15 +235,16 @@ static int mdfpwm_rows(aukit_ctx *ctx, const aukit_batch *in, const char *badmsg
     std::vector<uint8_t> heads_pageable;
     uint8_t *heads = nullptr;
     if (in->n) {
-        int grc = ctx->tmp_buf3.ensure((size_t)in->n * HEAD + 64);
+        DevBuf &S3 = ctx_scratch3(ctx);
+        int grc = S3.ensure((size_t)in->n * HEAD + 64);
         if (grc) return grc;
         hipLaunchKernelGGL(k_gather_heads, dim3(in->n), dim3(64), 0, ctx->stream, in->data(), reinterpret_cast<const unsigned long long *>(in->d_off), in->n, HEAD,
-                           reinterpret_cast<unsigned char *>(ctx->tmp_buf3.p));
+                           reinterpret_cast<unsigned char *>(S3.p));
         AUKIT_HIP_CHECK(hipGetLastError());
         heads = static_cast<uint8_t *>(ctx_host_stage(ctx, (size_t)in->n * HEAD));
         if (!heads) { heads_pageable.resize((size_t)in->n * HEAD); heads = heads_pageable.data(); }
         lap("gather launch");
-        AUKIT_HIP_CHECK(hipMemcpyAsync(heads, ctx->tmp_buf3.p, (size_t)in->n * HEAD, hipMemcpyDeviceToHost, ctx->stream));
+        AUKIT_HIP_CHECK(hipMemcpyAsync(heads, S3.p, (size_t)in->n * HEAD, hipMemcpyDeviceToHost, ctx->stream));
         AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         lap("heads d2h+sync");
     }

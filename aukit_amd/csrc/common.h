@@ -78,7 +78,8 @@ struct aukit_ctx {
     hipEvent_t entry_ev[2] = {nullptr, nullptr};
     hipEvent_t scratch_ev = nullptr;
     bool scratch_ev_set = false;
-    bool scratch_dirty = false;   // tmp_buf3 holds a call's frames and nothing tracks who reads them (the call's own gather / stream tail on ctx->stream): the next decoder waits for all of ctx->stream
+    bool scratch_dirty = false;   // tmp_buf3 holds a call's frames and nothing tracks who reads them (the call's own gather / stream tail on ctx->stream), or a
+                                  // user on ctx->stream that is not the FLAC loader has touched it (ctx_scratch3): the next decoder waits for all of ctx->stream
     uint64_t flac_calls = 0;
     hipEvent_t side_ev[2] = {};
     int aux_enc_cus = -1;
@@ -102,8 +103,11 @@ struct aukit_ctx {
     char *tab_ring = nullptr;
     size_t tab_half = 0, tab_head = 0;
     int tab_cur = 0;
-    bool tab_used[2] = {false, false};
-    hipEvent_t tab_ev[2] = {};
+    // the streams that carried copies out of each half — ctx->stream, and the look-ahead stream while a call has ctx->stream pointing at it (flac.hip,
+    // qoa.hip) — and the event recorded on each when the half is left: the half is reused once all of them have passed
+    hipStream_t tab_on[2][4] = {};
+    hipEvent_t tab_ev[2][4] = {};
+    int tab_non[2] = {0, 0};
     // a resumable stream handle (stream_handle.hip) that has dropped the bytes of delivered iterator calls decodes the REST of its stream: what it dropped
     // — bytes, 48 kHz outputs per channel — enters the chunk positions and the length of the stream factories that support it (stream.pcm / g711 /
     // adpcm / msadpcm), so that the rest's chunks carry the whole stream's numbers.  Zero everywhere else.
@@ -257,6 +261,10 @@ int h2d_table(aukit_ctx *ctx, void *dst, const void *src, size_t bytes);
 int ctx_side_fork(aukit_ctx *ctx, hipStream_t *side);  // side stream that starts after everything queued on ctx->stream so far (runtime.hip)
 int ctx_side_join(aukit_ctx *ctx);
 int ctx_pre_stream(aukit_ctx *ctx, hipStream_t *s);   // the look-ahead stream of the FLAC loader's first stages (created on first use)                     // ctx->stream continues after everything queued on the side stream  // pinned-ring H2D on ctx->stream (runtime.hip)
+// ctx->tmp_buf3 for every user on ctx->stream that is not the FLAC loader (stream.adpcm's weights, the QOA walks and stream.qoa's scratch, the DFPWM
+// encoder's chunk tables, the MDFPWM header scan, stream.flac's tail): the decode-ahead FLAC decoder writes its frame scratch there on the look-ahead
+// stream, and scratch_dirty makes the next one wait for all of ctx->stream (flac_run_fused) instead of the last FLAC reader only (scratch_ev)
+static inline DevBuf &ctx_scratch3(aukit_ctx *ctx) { ctx->scratch_dirty = true; return ctx->tmp_buf3; }
 // q = RN(n / d) computed as fma(fma(-d, n*r, n), r, n*r) with r = RN(1/d) is exact for the integers
 // n in [0, count): verified on the host once per (d, count) and cached in ctx->div_ok.
 bool exact_div_verified(aukit_ctx *ctx, double d, uint64_t count);

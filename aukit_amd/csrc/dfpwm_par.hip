@@ -1129,8 +1129,9 @@ bool dfpwm_encode_i8_small(aukit_ctx *ctx, const signed char *in, const uint64_t
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
     const size_t o_chunks = take(b_chunks), o_sf = take(b_sf), o_cand = take(b_cand), o_dist = take(b_dist), o_dcount = take(b_cnt), o_dend = take(b_dist), o_start = take(b_cnt), o_stats = take(16);
-    if ((*rc = ctx->tmp_buf3.ensure(o + 64))) return true;
-    char *B = reinterpret_cast<char *>(ctx->tmp_buf3.p);
+    DevBuf &S3 = ctx_scratch3(ctx);
+    if ((*rc = S3.ensure(o + 64))) return true;
+    char *B = reinterpret_cast<char *>(S3.p);
     if (h2d_table(ctx, B + o_chunks, chunks.data(), b_chunks) || h2d_table(ctx, B + o_sf, sfirst.data(), b_sf) ||
         hipMemsetAsync(B + o_stats, 0, 16, ctx->stream) != hipSuccess) {
         *rc = fail(AUKIT_E_HIP, "upload of the DFPWM encoder chunk table failed");

@@ -1643,7 +1643,7 @@ static int flac_run_fused(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &D,
         // Round 6, late: the decoder and the chain walk stay on the look-ahead stream too (AUKIT_FLAC_DECODE_AHEAD=0: behind the search on ctx->stream as
         // before).  The call before's last passes — its normalize: HBM-bound, no LDS — then run BESIDE this call's decoder (VALU-bound, the CU's whole LDS)
         // instead of in front of it.  The frame scratch is the one buffer both streams touch: the decoder waits for its last reader (scratch_ev: the tile
-        // chain of the call before), or for all of ctx->stream when nothing tracked the readers.  Every nested launch goes where ctx->stream points: it
+        // chain of the call before), or for all of ctx->stream when nothing tracked the readers or a user other than this loader touched it (ctx_scratch3).  Every nested launch goes where ctx->stream points: it
         // points at the look-ahead stream until the chain has converged.
         const bool dahead = D.set && !(getenv("AUKIT_FLAC_DECODE_AHEAD") && atoi(getenv("AUKIT_FLAC_DECODE_AHEAD")) == 0);
         struct StreamSwap { aukit_ctx *c; hipStream_t saved; bool on; void back() { if (on) { c->stream = saved; on = false; } } ~StreamSwap() { back(); } } sw{ctx, ctx->stream, false};
@@ -2234,10 +2234,11 @@ int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *,
         std::vector<uint64_t> scr_off(jobs.size());
         for (size_t k = 0; k < jobs.size(); k++) { scr_off[k] = scr_elems; scr_elems += ((uint64_t)jobs[k].nout + 1) & ~1ull; max_nout = std::max<uint64_t>(max_nout, (uint64_t)jobs[k].nout); }
         if (scr_elems * 8 <= (48ull << 30) && max_nout && !getenv("AUKIT_FLAC_STREAM_ONE_PASS")) {  // two passes
-            if ((rc = ctx->tmp_buf3.ensure((size_t)scr_elems * 8 + 64))) { delete ck; return rc; }
+            DevBuf &S3 = ctx_scratch3(ctx);
+            if ((rc = S3.ensure((size_t)scr_elems * 8 + 64))) { delete ck; return rc; }
             if ((rc = upload_table(ctx, ctx->misc_buf, scr_off.data(), scr_off.size() * 8))) { delete ck; return rc; }
             const u64 *dso = reinterpret_cast<const u64 *>(ctx->misc_buf.p);
-            double *scr = reinterpret_cast<double *>(ctx->tmp_buf3.p);
+            double *scr = reinterpret_cast<double *>(S3.p);
             for (size_t first = 0; first < jobs.size(); first += 65535) {
                 const dim3 g1((unsigned)std::min<uint64_t>((max_nout + 255) / 256, 1024), (unsigned)std::min<size_t>(65535, jobs.size() - first));
 #define AUKIT_FI2(I, R) hipLaunchKernelGGL((k_flac_stream_interp<I, R>), g1, dim3(256), 0, ctx->stream, dj + first, dso + first, reinterpret_cast<const R *>(ctx->tmp_buf.p), full, scr, ratio, 1.0 / ratio, exact, ctx->sinc_w)

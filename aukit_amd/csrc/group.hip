@@ -49,6 +49,16 @@ struct aukit_group {
 
 namespace aukit {
 
+// A batch this file returns is filled asynchronously on member `r`'s stream (its offsets by h2d_table, its bytes by the copies of group_move): its
+// `ready` is recorded there after them, so that a look-ahead reader (on the member's pre_stream: FLAC, stream.qoa, stream.adpcm, stream.msadpcm)
+// waits for the bytes it reads (a null `ready` means "complete", runtime.hip).  Audios need none: every reader of an audio runs on ctx->stream.
+static int batch_mark_ready(aukit_group *g, uint32_t r, aukit_batch *b) {
+    AUKIT_HIP_CHECK(hipSetDevice(g->dev[r]));
+    if (!b->ready) AUKIT_HIP_CHECK(hipEventCreateWithFlags(&b->ready, hipEventDisableTiming));
+    AUKIT_HIP_CHECK(hipEventRecord(b->ready, g->ctx[r]->stream));
+    return AUKIT_OK;
+}
+
 // one device-to-device message: `bytes` from src (member `from`) to dst (member `to`)
 struct GroupMsg { const void *src; void *dst; size_t bytes; uint32_t from, to; };
 
@@ -330,8 +340,10 @@ int aukit_group_scatter(aukit_group *g, uint32_t root, const aukit_batch *whole,
         shards[r] = b;
         msgs.push_back(GroupMsg{whole->data() + whole->off[lo], b->data(), (size_t)bytes, root, r});
     }
-    rc = group_move(g, msgs, true, root);
-    return rc ? undo(rc) : AUKIT_OK;
+    if ((rc = group_move(g, msgs, true, root))) return undo(rc);
+    for (uint32_t r = 0; r < W; r++)
+        if (r != root && (rc = batch_mark_ready(g, r, shards[r]))) return undo(rc);
+    return AUKIT_OK;
 }
 
 // parts[r] is member r's result (same channel count, rate, dtype); *whole — on member `root` — gets every stream of every part in rank order.
@@ -399,7 +411,8 @@ int aukit_group_gather_batch(aukit_group *g, uint32_t root, aukit_batch *const *
         msgs.push_back(GroupMsg{parts[r]->data(), b->data() + at, (size_t)bytes, r, root});
         at += bytes;
     }
-    return group_move(g, msgs, false, root);
+    if ((rc = group_move(g, msgs, false, root))) return rc;   // (the root's stream waits for every sender's: join)
+    return batch_mark_ready(g, root, b);
 }
 
 }  // extern "C"

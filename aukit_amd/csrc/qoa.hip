@@ -307,7 +307,7 @@ static int qoa_walk_count(aukit_ctx *ctx, const aukit_batch *in, int mode, std::
     const uint32_t n = in->n;
     S.assign(n, QoaStreamInfo{});
     if (!n) return AUKIT_OK;
-    DevBuf &W = wb ? *wb : ctx->tmp_buf3;
+    DevBuf &W = wb ? *wb : ctx_scratch3(ctx);
     int rc = W.ensure((size_t)n * (sizeof(QoaWalkOut) + sizeof(QoaFillIn)) + 64);
     if (rc) return rc;
     QoaWalkOut *dwo = reinterpret_cast<QoaWalkOut *>(W.p);
@@ -352,7 +352,7 @@ static int qoa_walk_fill(aukit_ctx *ctx, const aukit_batch *in, int mode, const 
     const uint32_t n = in->n;
     std::vector<QoaFillIn> fin(n);
     for (uint32_t s = 0; s < n; s++) fin[s] = QoaFillIn{S[s].job_first, S[s].call_first, S[s].row_base, S[s].stride};
-    QoaFillIn *dfin = reinterpret_cast<QoaFillIn *>(reinterpret_cast<QoaWalkOut *>((wb ? *wb : ctx->tmp_buf3).p) + n);
+    QoaFillIn *dfin = reinterpret_cast<QoaFillIn *>(reinterpret_cast<QoaWalkOut *>((wb ? *wb : ctx_scratch3(ctx)).p) + n);
     { int hrc = h2d_table(ctx, dfin, fin.data(), (size_t)n * sizeof(QoaFillIn)); if (hrc) return hrc; }
     DevBuf &CB = cb ? *cb : ctx->misc_buf;
     int rc = CB.ensure((size_t)std::max<uint64_t>(ncalls, 1) * sizeof(QoaCallRec) + 64);

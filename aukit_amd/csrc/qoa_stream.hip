@@ -280,10 +280,11 @@ int stream_qoa_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_des
         // two passes whenever the scratch (one double per output) is affordable: the one-lane-per-job kernel pays four dependent table loads
         // and ~60 fp64 operations per output on a few hundred waves (1024 stereo streams of ten seconds: 94 ms against 7 ms in two passes)
         if (scr_elems * 8 <= (48ull << 30) && max_nout && !getenv("AUKIT_QOA_ONE_PASS")) {
-            if ((rc = ctx->tmp_buf3.ensure((size_t)scr_elems * 8 + 64))) { delete ck; return rc; }
+            DevBuf &S3 = ctx_scratch3(ctx);
+            if ((rc = S3.ensure((size_t)scr_elems * 8 + 64))) { delete ck; return rc; }
             if ((rc = upload_table(ctx, ctx->misc_buf, scr_off.data(), scr_off.size() * 8))) { delete ck; return rc; }
             const unsigned long long *dso = reinterpret_cast<const unsigned long long *>(ctx->misc_buf.p);
-            double *scr = reinterpret_cast<double *>(ctx->tmp_buf3.p);
+            double *scr = reinterpret_cast<double *>(S3.p);
             for (size_t first = 0; first < jobs.size(); first += 65535) {  // (grid.y holds 65535 jobs)
                 const dim3 g1((unsigned)std::min<uint64_t>((max_nout + 255) / 256, 1024), (unsigned)std::min<size_t>(65535, jobs.size() - first));
                 if (interp == 0) hipLaunchKernelGGL((k_qoa_stream_interp<0>), g1, dim3(256), 0, ctx->stream, dj + first, dso + first, rows, scr, ratio, 1.0 / ratio, exact, ctx->sinc_w);

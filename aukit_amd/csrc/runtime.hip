@@ -39,18 +39,21 @@ int h2d_table(aukit_ctx *ctx, void *dst, const void *src, size_t bytes) {
     if (!no_ring && bytes <= HALF) {   // (a table that fills most of a half just turns the ring over sooner)
         if (!ctx->tab_ring) {
             if (hipHostMalloc(reinterpret_cast<void **>(&ctx->tab_ring), 2 * HALF, hipHostMallocDefault) != hipSuccess) { ctx->tab_ring = nullptr; (void)hipGetLastError(); }
-            else if (hipEventCreateWithFlags(&ctx->tab_ev[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ctx->tab_ev[1], hipEventDisableTiming) != hipSuccess) {
-                (void)hipGetLastError(); (void)hipHostFree(ctx->tab_ring); ctx->tab_ring = nullptr;
-            } else { ctx->tab_half = HALF; ctx->tab_head = 0; ctx->tab_cur = 0; ctx->tab_used[0] = true; ctx->tab_used[1] = false; }
+            else { ctx->tab_half = HALF; ctx->tab_head = 0; ctx->tab_cur = 0; ctx->tab_non[0] = ctx->tab_non[1] = 0; }
         }
         if (ctx->tab_ring) {
-            if (ctx->tab_head + bytes > ctx->tab_half) {   // this half is full: everything copied out of it so far is ahead of this event
-                AUKIT_HIP_CHECK(hipEventRecord(ctx->tab_ev[ctx->tab_cur], ctx->stream));
+            if (ctx->tab_head + bytes > ctx->tab_half) {   // this half is full: everything copied out of it so far is ahead of these events
+                for (int i = 0; i < ctx->tab_non[ctx->tab_cur]; i++) AUKIT_HIP_CHECK(hipEventRecord(ctx->tab_ev[ctx->tab_cur][i], ctx->tab_on[ctx->tab_cur][i]));
                 ctx->tab_cur ^= 1;
                 ctx->tab_head = 0;
-                if (ctx->tab_used[ctx->tab_cur]) AUKIT_HIP_CHECK(hipEventSynchronize(ctx->tab_ev[ctx->tab_cur]));
-                ctx->tab_used[ctx->tab_cur] = true;
+                for (int i = 0; i < ctx->tab_non[ctx->tab_cur]; i++) AUKIT_HIP_CHECK(hipEventSynchronize(ctx->tab_ev[ctx->tab_cur][i]));
+                ctx->tab_non[ctx->tab_cur] = 0;
             }
+            const int h = ctx->tab_cur;
+            int i = 0;
+            while (i < ctx->tab_non[h] && ctx->tab_on[h][i] != ctx->stream) i++;
+            if (i == ctx->tab_non[h] && i < 4 && (ctx->tab_ev[h][i] || hipEventCreateWithFlags(&ctx->tab_ev[h][i], hipEventDisableTiming) == hipSuccess)) ctx->tab_on[h][ctx->tab_non[h]++] = ctx->stream;
+            if (i == ctx->tab_non[h]) { (void)hipGetLastError(); goto plain; }   // (a fifth stream, or no event: the plain copy below)
             char *st = ctx->tab_ring + (size_t)ctx->tab_cur * ctx->tab_half + ctx->tab_head;
             memcpy(st, src, bytes);
             ctx->tab_head += (bytes + 63) & ~(size_t)63;
@@ -58,6 +61,7 @@ int h2d_table(aukit_ctx *ctx, void *dst, const void *src, size_t bytes) {
             return AUKIT_OK;
         }
     }
+plain:
     AUKIT_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
     return AUKIT_OK;
 }
@@ -73,12 +77,18 @@ int ctx_side_fork(aukit_ctx *ctx, hipStream_t *side) {
     return AUKIT_OK;
 }
 int ctx_pre_stream(aukit_ctx *ctx, hipStream_t *s) {
-    if (!ctx->pre_stream) {
-        AUKIT_HIP_CHECK(hipStreamCreateWithFlags(&ctx->pre_stream, hipStreamNonBlocking));   // (a higher queue priority changes nothing: profiles/r06_flac_lookahead.txt)
-        AUKIT_HIP_CHECK(hipEventCreateWithFlags(&ctx->pre_ev, hipEventDisableTiming));
-        AUKIT_HIP_CHECK(hipEventCreateWithFlags(&ctx->entry_ev[0], hipEventDisableTiming));
-        AUKIT_HIP_CHECK(hipEventCreateWithFlags(&ctx->entry_ev[1], hipEventDisableTiming));
-        AUKIT_HIP_CHECK(hipEventCreateWithFlags(&ctx->scratch_ev, hipEventDisableTiming));
+    if (!ctx->pre_stream) {   // all or nothing: a context never holds the stream without its events
+        hipStream_t st = nullptr;
+        hipEvent_t ev[4] = {};
+        hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);   // (a higher queue priority changes nothing: profiles/r06_flac_lookahead.txt)
+        for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+        if (e != hipSuccess) {
+            for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+            if (st) (void)hipStreamDestroy(st);
+            return fail(AUKIT_E_HIP, "creating the look-ahead stream failed: %s", hipGetErrorString(e));
+        }
+        ctx->pre_ev = ev[0]; ctx->entry_ev[0] = ev[1]; ctx->entry_ev[1] = ev[2]; ctx->scratch_ev = ev[3];
+        ctx->pre_stream = st;
     }
     *s = ctx->pre_stream;
     return AUKIT_OK;
@@ -258,10 +268,12 @@ void aukit_ctx_destroy(aukit_ctx *c) {
     if (c->stream_full) { aukit_audio_free(c->stream_full); c->stream_full = nullptr; }
     delete c->spcm_ck;
     if (c->host_stage) (void)hipHostFree(c->host_stage);
-    if (c->pre_stream) { (void)hipStreamSynchronize(c->pre_stream); (void)hipStreamDestroy(c->pre_stream); (void)hipEventDestroy(c->pre_ev); (void)hipEventDestroy(c->entry_ev[0]); (void)hipEventDestroy(c->entry_ev[1]); (void)hipEventDestroy(c->scratch_ev); c->pre_stream = nullptr; }
+    if (c->pre_stream) { (void)hipStreamSynchronize(c->pre_stream); (void)hipStreamDestroy(c->pre_stream); c->pre_stream = nullptr; }
+    for (hipEvent_t *e : {&c->pre_ev, &c->entry_ev[0], &c->entry_ev[1], &c->scratch_ev}) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
     c->flac_set[0].release(); c->flac_set[1].release(); c->scan_buf.release(); for (int i = 0; i < 2; i++) for (int j = 0; j < 3; j++) c->qoa_set[i][j].release();
     if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); (void)hipEventDestroy(c->side_ev[0]); (void)hipEventDestroy(c->side_ev[1]); }
-    if (c->tab_ring) { (void)hipHostFree(c->tab_ring); (void)hipEventDestroy(c->tab_ev[0]); (void)hipEventDestroy(c->tab_ev[1]); }
+    if (c->tab_ring) (void)hipHostFree(c->tab_ring);
+    for (int h = 0; h < 2; h++) for (int i = 0; i < 4; i++) if (c->tab_ev[h][i]) (void)hipEventDestroy(c->tab_ev[h][i]);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->kev0) (void)hipEventDestroy(c->kev0);
@@ -274,6 +286,9 @@ int aukit_ctx_set_stream(aukit_ctx *c, void *s) {
     if (!c) return fail(AUKIT_E_ARG, "ctx is null");
     AUKIT_HIP_CHECK(hipSetDevice(c->device));
     AUKIT_HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (int h = 0; h < 2; h++)   // (its copies out of the table ring have landed: the ring no longer records an event on it)
+        for (int i = 0; i < c->tab_non[h]; i++)
+            if (c->tab_on[h][i] == c->stream) { const int last = --c->tab_non[h]; std::swap(c->tab_on[h][i], c->tab_on[h][last]); std::swap(c->tab_ev[h][i], c->tab_ev[h][last]); break; }
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     c->stream = (hipStream_t)s;
     c->own_stream = false;
