@@ -5,6 +5,7 @@
 // Block codecs (ADPCM, MS-ADPCM, DFPWM, QOA, FLAC) are routed to codecs.hip.
 #include <algorithm>
 #include "resample.h"
+#include "stream_pcm_sinc.h"
 
 namespace aukit {
 
@@ -12,6 +13,8 @@ int decode_block_codec(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_
                        int dtype, aukit_audio **out);
 int stream_block_codec(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d, int interp, int mono, int dtype,
                        aukit_audio **out, aukit_chunks **chunks);
+int launch_stream_pcm_sinc(aukit_ctx *ctx, const std::vector<SincCall> &calls, const SincMap &m, const aukit_batch *in, const aukit_codec_desc *d,
+                           bool table, bool mono, int dtype, aukit_audio *a, uint64_t algorithmic_bytes);   // stream_pcm_sinc.hip
 
 static int check_pcm_desc(const aukit_codec_desc *d) {
     if (d->bit_depth != 8 && d->bit_depth != 16 && d->bit_depth != 24 && d->bit_depth != 32) return fail(AUKIT_E_ARG, "bad argument #2 (invalid bit depth)");
@@ -335,7 +338,7 @@ struct ChunkPlan {
     std::vector<int> acc, req;     // per output j (1-based → [j-1]): highest index touched so far / index that must be non-nil
 };
 
-static int build_chunk_plan(double sample_rate, int interp, ChunkPlan &cp) {
+static int build_chunk_plan(double sample_rate, int interp, ChunkPlan &cp, int sinc_w = 10) {
     static const int iend[4] = {1, 2, 3, 0};
     cp.ratio = 48000 / sample_rate;  // :2364
     cp.interp = interp;
@@ -346,7 +349,7 @@ static int build_chunk_plan(double sample_rate, int interp, ChunkPlan &cp) {
         double x = ((double)(j - 1) / cp.ratio) + 1;
         double ffx = std::floor(x);
         bool isint = x == ffx;
-        int top = isint ? (int)x : (int)ffx + (interp == AUKIT_INTERP_CUBIC ? 2 : (interp == AUKIT_INTERP_LINEAR ? 1 : 0));
+        int top = isint ? (int)x : (int)ffx + (interp == AUKIT_INTERP_CUBIC ? 2 : (interp == AUKIT_INTERP_LINEAR ? 1 : (interp == AUKIT_INTERP_SINC ? sinc_w : 0)));
         if (top > mx) mx = top;
         cp.acc[j - 1] = mx;
         cp.req[j - 1] = (int)ffx;
@@ -365,7 +368,6 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
                       aukit_chunks **chunks_out, bool table = false) {
     int rc;
     if ((rc = check_pcm_desc(d))) return rc;
-    if (interp == AUKIT_INTERP_SINC) return fail(AUKIT_E_UNSUPPORTED, "stream.pcm with sinc interpolation reads its lazy table out of order (not reproduced on the GPU)");
     if (interp < 0 || interp > 3) return fail(AUKIT_E_ARG, "invalid interpolation");
     if (d->sample_rate > 48000) return fail(AUKIT_E_UNSUPPORTED, "stream.pcm above 48 kHz is ill-defined in the reference (lazy table read out of order, SURVEY Q3)");
     if (dtype != AUKIT_F64 && dtype != AUKIT_F32) return fail(AUKIT_E_ARG, "stream.pcm output must be AUKIT_F64 or AUKIT_F32");
@@ -379,24 +381,40 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     char keyb[256];
     unsigned long long oh = 1469598103934665603ull;   // FNV-1a over the stream offsets (a freed batch's address can come back with another layout)
     for (uint64_t o : in->off) { oh ^= o; oh *= 1099511628211ull; }
-    snprintf(keyb, sizeof keyb, "%p/%llu/%u/%llx/%d/%d/%d/%d/%.17g/%d/%d/%d/%llu/%llu", (const void *)in, (unsigned long long)in->version, in->n, oh,
-             d->bit_depth + (table ? 1000 : 0), d->data_type, d->big_endian, C, d->sample_rate, interp, mono, nd, (unsigned long long)ctx->sb_bytes, (unsigned long long)ctx->sb_outputs);
+    snprintf(keyb, sizeof keyb, "%p/%llu/%u/%llx/%d/%d/%d/%d/%.17g/%d/%d/%d/%llu/%llu/%d", (const void *)in, (unsigned long long)in->version, in->n, oh,
+             d->bit_depth + (table ? 1000 : 0), d->data_type, d->big_endian, C, d->sample_rate, interp, mono, nd, (unsigned long long)ctx->sb_bytes, (unsigned long long)ctx->sb_outputs,
+             ctx->sinc_w);
     std::vector<Seg> segs;
     std::vector<uint64_t> lens(in->n, 0);
     uint64_t in_bytes = 0, out_elems = 0;
     aukit_chunks *ck = new aukit_chunks();
     const bool plan_hit = ctx->spcm_ck && ctx->spcm_key == keyb && !getenv("AUKIT_NO_PLAN_CACHE");
     double cp_ratio = 48000 / d->sample_rate;
+    // sinc (stream_pcm_sinc.h): one work item per iterator call instead of segments; the cache keeps the map in front of the calls
+    const bool sinc = interp == AUKIT_INTERP_SINC;
+    SincMap sm{};
+    std::vector<SincCall> scalls;
     if (plan_hit) {
         *ck = *ctx->spcm_ck;
-        segs.resize(ctx->spcm_segs.size() / sizeof(Seg));
-        if (!segs.empty()) memcpy(segs.data(), ctx->spcm_segs.data(), ctx->spcm_segs.size());
+        if (sinc) {
+            memcpy(&sm, ctx->spcm_segs.data(), sizeof sm);
+            scalls.resize((ctx->spcm_segs.size() - sizeof sm) / sizeof(SincCall));
+            if (!scalls.empty()) memcpy(scalls.data(), ctx->spcm_segs.data() + sizeof sm, scalls.size() * sizeof(SincCall));
+        } else {
+            segs.resize(ctx->spcm_segs.size() / sizeof(Seg));
+            if (!segs.empty()) memcpy(segs.data(), ctx->spcm_segs.data(), ctx->spcm_segs.size());
+        }
         lens = ctx->spcm_lens;
         in_bytes = ctx->spcm_in_bytes; out_elems = ctx->spcm_out_elems;
     } else {
     ChunkPlan cp;
-    build_chunk_plan(d->sample_rate, interp, cp);
+    build_chunk_plan(d->sample_rate, interp, cp, ctx->sinc_w);
     cp_ratio = cp.ratio;
+    SincGrid sgrid;
+    if (sinc) {
+        sm.nd = nd;
+        if (!sinc_grid(d->sample_rate, ctx->sinc_w, sgrid, sm) || sm.K != cp.K) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "stream.pcm with sinc: the lazy tables' read order at %.17g Hz is not modelled", d->sample_rate); }
+    }
 
     ck->n = in->n;
     ck->nchunks.assign(in->n, 0);
@@ -417,6 +435,12 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         const long long nframes = (long long)(nb / ((size_t)bd * C));
         ck->length_seconds[s] = ((double)(nb + ctx->sb_bytes) / bd) / C / d->sample_rate;  // :2245, :2423 (sb_bytes: what a stream handle has dropped already)
         in_bytes += nb;
+        if (sinc) {   // units: samples, or whole frames with the mix-down (a partial frame raises where it is read)
+            const long long U = mono ? nframes : (long long)(nb / (size_t)bd);
+            const size_t first = scalls.size();
+            ck->status[s] = sinc_plan_stream(sm, sgrid, U, is_float && !mono, is_float, in->off[s], s, scalls);
+            for (size_t k = first; k < scalls.size(); k++) { clens[s].push_back(scalls[k].n_out); lens[s] += scalls[k].n_out; }
+        } else
         for (long c = 0;; c++) {
             const long long src_base = (long long)c * cp.K - istart[interp];  // frame of table index 0
             // prefill :2376-2386 reads eagerly up to index iend
@@ -457,6 +481,10 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         }
     }
     ctx->spcm_key = keyb;
+    if (sinc) {
+        ctx->spcm_segs.assign(reinterpret_cast<const unsigned char *>(&sm), reinterpret_cast<const unsigned char *>(&sm) + sizeof sm);
+        ctx->spcm_segs.insert(ctx->spcm_segs.end(), reinterpret_cast<const unsigned char *>(scalls.data()), reinterpret_cast<const unsigned char *>(scalls.data()) + scalls.size() * sizeof(SincCall));
+    } else
     ctx->spcm_segs.assign(reinterpret_cast<const unsigned char *>(segs.data()), reinterpret_cast<const unsigned char *>(segs.data()) + segs.size() * sizeof(Seg));
     ctx->spcm_lens = lens;
     ctx->spcm_in_bytes = in_bytes; ctx->spcm_out_elems = out_elems;
@@ -466,6 +494,15 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     aukit_audio *a = *out;
     if ((rc = audio_prepare(ctx, &a, in->n, nd, 48000, dtype, lens.data()))) { delete ck; return rc; }
     *out = a;
+    if (sinc) {   // every format, the table input and both storage types: one kernel (stream_pcm_sinc.hip)
+        for (SincCall &c : scalls) {
+            c.out_off += a->row_off[c.stream];
+            c.out_stride = (unsigned)a->row_stride[c.stream];
+        }
+        if ((rc = launch_stream_pcm_sinc(ctx, scalls, sm, in, d, table, mono != 0, dtype, a, in_bytes + out_elems * dtype_size(dtype)))) { delete ck; return rc; }
+        if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
+        return AUKIT_OK;
+    }
     for (Seg &g : segs) {
         g.out_off += a->row_off[g.stream];
         g.out_stride = (unsigned)a->row_stride[g.stream];

@@ -12,28 +12,7 @@
 #define AUKIT_CONST_AS_I __attribute__((address_space(4)))
 namespace aukit {
 
-// ------------------------------------------------------------------ sample decoding
-AUKIT_DEV double pcm_raw(const unsigned char *p, int bd, int dt, int be) {
-    if (dt == AUKIT_FLOAT) {
-        unsigned u = be ? ((unsigned)p[0] << 24 | (unsigned)p[1] << 16 | (unsigned)p[2] << 8 | p[3])
-                        : ((unsigned)p[3] << 24 | (unsigned)p[2] << 16 | (unsigned)p[1] << 8 | p[0]);
-        return (double)__uint_as_float(u);
-    }
-    unsigned long long u = 0;
-    if (be) for (int i = 0; i < bd; i++) u = (u << 8) | p[i];
-    else for (int i = bd - 1; i >= 0; i--) u = (u << 8) | p[i];
-    if (dt == AUKIT_SIGNED) {
-        unsigned long long sign = 1ull << (bd * 8 - 1);
-        if (u & sign) return (double)((long long)u - (long long)(1ull << (bd * 8)));
-    }
-    return (double)u;
-}
-// aukit.lua:1133 / :1152 (Q4) / :1114
-AUKIT_DEV double pcm_norm(double s, int dt, double maxv) {
-    if (dt == AUKIT_SIGNED) return s / (s < 0 ? maxv : maxv - 1);
-    if (dt == AUKIT_UNSIGNED) return (s - 128) / (s < 128 ? maxv : maxv - 1);
-    return s;
-}
+// ------------------------------------------------------------------ sample decoding (pcm_raw / pcm_norm: resample_dev.h)
 // aukit.lua:1374-1379: returns ±m as a double (sign folded in), to be scaled by 2^-13 or 2^-6
 AUKIT_DEV double g711_value(unsigned byte, int ulaw) {
     unsigned b = byte ^ (ulaw ? 0xFFu : 0x55u);

@@ -15,6 +15,29 @@ AUKIT_DEV double pos_of(const ResampleParams &P, unsigned o) {
     return q + 1.0;
 }
 
+// ------------------------------------------------------------------ PCM sample decoding (k_resample's staging, k_stream_pcm_sinc)
+AUKIT_DEV double pcm_raw(const unsigned char *p, int bd, int dt, int be) {
+    if (dt == AUKIT_FLOAT) {
+        unsigned u = be ? ((unsigned)p[0] << 24 | (unsigned)p[1] << 16 | (unsigned)p[2] << 8 | p[3])
+                        : ((unsigned)p[3] << 24 | (unsigned)p[2] << 16 | (unsigned)p[1] << 8 | p[0]);
+        return (double)__uint_as_float(u);
+    }
+    unsigned long long u = 0;
+    if (be) for (int i = 0; i < bd; i++) u = (u << 8) | p[i];
+    else for (int i = bd - 1; i >= 0; i--) u = (u << 8) | p[i];
+    if (dt == AUKIT_SIGNED) {
+        unsigned long long sign = 1ull << (bd * 8 - 1);
+        if (u & sign) return (double)((long long)u - (long long)(1ull << (bd * 8)));
+    }
+    return (double)u;
+}
+// aukit.lua:1133 / :1152 (Q4) / :1114
+AUKIT_DEV double pcm_norm(double s, int dt, double maxv) {
+    if (dt == AUKIT_SIGNED) return s / (s < 0 ? maxv : maxv - 1);
+    if (dt == AUKIT_UNSIGNED) return (s - 128) / (s < 128 ? maxv : maxv - 1);
+    return s;
+}
+
 // ------------------------------------------------------------------ one interpolated sample
 // `tab` points at the LDS slot of table index k_lo for this channel.  Returns
 // `if x % 1 == 0 then d[x] else interp(d, x)`; *isint tells the caller which branch was taken.

@@ -277,17 +277,20 @@ int aukit_pack_pcm(aukit_ctx *ctx, const aukit_audio *in, int bit_depth, int dat
 
 /* ---- aukit.stream.<codec>(data, ...) with string input, every call of the iterator at once ----
  * out audio: per stream the concatenation of all chunks (`channels` = number of chunk tables);
- * chunk metadata is read back with aukit_stream_chunks(). */
+ * chunk metadata is read back with aukit_stream_chunks().  stream.pcm takes every interpolation at or below 48 kHz (sinc included: the
+ * reference's out-of-order lazy reads are reproduced) and refuses sources above 48 kHz (AUKIT_E_UNSUPPORTED, Q3). */
 typedef struct aukit_chunks aukit_chunks;
 int aukit_stream_decode(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *desc, int interp, int mono,
                         int dtype, aukit_audio **out, aukit_chunks **chunks);
 /* aukit.stream.pcm(data, ...) with `data` a TABLE of numbers, aukit.lua:2255-2290 (`read()` hands out `data[pos]` normalised like the string's
  * samples; `len = #data / channels`): every iterator call at once, as aukit_stream_decode.  Values are taken as they are; reference-order
- * fp64 arithmetic whatever the storage type (AUKIT_F64 / AUKIT_F32); sinc and rates above 48 kHz refused like the string's (Q3). */
+ * fp64 arithmetic whatever the storage type (AUKIT_F64 / AUKIT_F32); sinc served and rates above 48 kHz refused like the string's (Q3). */
 int aukit_stream_decode_table(aukit_ctx *ctx, const double *values, const uint64_t *offsets /* n + 1, elements */, uint32_t n, const aukit_codec_desc *d, int interp,
                               int mono, int dtype, aukit_audio **out, aukit_chunks **chunks);
 /* per stream s: nchunks[s]; chunk k of stream s: length and the iterator's second return value.
- * status[s]: 0 = iterator ended with nil, AUKIT_E_LUA = the reference iterator raises after the last chunk. */
+ * status[s]: 0 = iterator ended with nil, AUKIT_E_LUA = the reference iterator raises after the last chunk, AUKIT_E_UNSUPPORTED = the
+ * reference's next chunk has different lengths per channel, which this table cannot carry: the chunks before it are delivered, it is not
+ * (stream.mdfpwm's chunk with holes; stream.pcm with sinc when data without the mix-down ends inside a later call's burst of taps). */
 int aukit_chunks_info(const aukit_chunks *c, uint32_t *n, uint32_t *max_chunks);
 int aukit_chunks_get(const aukit_chunks *c, uint32_t *nchunks /* n */, uint32_t *lens /* n*max */, double *pos /* n*max */,
                      int32_t *status /* n */, double *length_seconds /* n */);

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Throughput of every aukit.stream.* iterator (all calls of a batch at once, aukit_stream_decode) on one large batch (GPU box).
-usage: python tools/stream_rates.py [streams=1024]"""
+usage: python tools/stream_rates.py [streams=1024] [f64|f32] [only lines whose name contains this]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -12,10 +12,16 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 DT = N.F64 if (len(sys.argv) > 2 and sys.argv[2] == "f64") else N.F32
 ctx = B.Context(0, dtype=DT)
 rng = np.random.default_rng(5)
-def rate(name, bt, desc, interp, mono, dtype):
+ONLY = sys.argv[3] if len(sys.argv) > 3 else ""
+def rate(name, bt, desc, interp, mono, dtype, fn=None, fn_outs=0):
+    if ONLY not in name:
+        return
     try:
         keep = [None]
         def f():
+            if fn:   # another entry point on the same bytes, for comparison (fn_outs: the samples it writes)
+                keep[0] = fn(keep[0])
+                return None
             keep[0], ck = B.stream_decode(ctx, bt, desc, interp, mono=mono, dtype=dtype, out=keep[0])
             return ck
         for _ in range(4): ck = f(); ctx.sync()  # untimed calls: buffers, pinned staging and the runtime's own pools grow on the first ones (round 4: two were not enough —
@@ -24,7 +30,7 @@ def rate(name, bt, desc, interp, mono, dtype):
         for _ in range(5):
             t0 = time.time(); ck = f(); ctx.sync(); ts.append(time.time() - t0)
         dt = sorted(ts)[len(ts) // 2]
-        outs = float(np.sum(ck.lens)) * (1 if mono else max(1, desc.channels))
+        outs = float(np.sum(ck.lens)) * (1 if mono else max(1, desc.channels)) if ck is not None else float(fn_outs)
         print(f"{name:44s} {dt * 1e3:8.2f} ms  {outs / dt / 1e9:8.1f} G out-samples/s  ({ctx.last_kernel()[0]})", flush=True)
     except Exception as e:
         print(f"{name:44s} failed: {str(e)[:90]}", flush=True)
@@ -34,6 +40,10 @@ base_pcm = [np.stack([pcm16(44100 * sec, 44100, 8, 4 * i + c) for c in range(2)]
 bt = B.Batch.upload(ctx, [base_pcm[i % 4].astype("<i2").tobytes() for i in range(n)])
 rate("stream.pcm s16le stereo 44.1k cubic f32", bt, B.make_desc(N.CODEC_PCM, 2, 44100, 16, "signed"), "cubic", False, DT)
 rate("stream.pcm s16le stereo 44.1k cubic mono f32", bt, B.make_desc(N.CODEC_PCM, 2, 44100, 16, "signed"), "cubic", True, DT)
+# sinc (W = 10): the stream.pcm kernel beside Audio:resample's on the same bytes (the same taps per output)
+rate("stream.pcm s16le stereo 44.1k sinc", bt, B.make_desc(N.CODEC_PCM, 2, 44100, 16, "signed"), "sinc", False, DT)
+rate("decode_resample s16le stereo 44.1k sinc", bt, B.make_desc(N.CODEC_PCM, 2, 44100, 16, "signed"), "sinc", False, DT,
+     fn=lambda o: B.decode_resample(ctx, bt, B.make_desc(N.CODEC_PCM, 2, 44100, 16, "signed"), 48000, "sinc", dtype=DT, out=o), fn_outs=n * 2 * (44100 * sec * 48000 // 44100))
 del bt
 bt = B.Batch.upload(ctx, [rng.integers(0, 256, 44100 * sec * 3, dtype=np.uint8).tobytes()] * n)
 rate("stream.pcm 24-bit mono 44.1k linear f32", bt, B.make_desc(N.CODEC_PCM, 1, 44100, 24, "signed"), "linear", False, DT)
