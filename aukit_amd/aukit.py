@@ -34,6 +34,7 @@ def context():
     global _ctx
     if _ctx is None:
         _ctx = B.Context(0, dtype=N.F64)
+        _ctx.set_option(N.OPT_CHANNEL_LENS, 1)   # chunks are lists of per-channel arrays: each keeps its own length (stream.pcm's uneven last chunk)
     return _ctx
 
 
@@ -562,11 +563,12 @@ class _StreamNS:
         chans = out.download()[0]
         n = int(ck.nchunks[0])
         lens, poss, status = ck.lens[0][:n], ck.pos[0][:n], int(ck.status[0])
+        clens = ck.chan_lens[0][:n]   # every channel's own length (the rows advance by the first channel's)
 
         def it():
             off = 0
             for k in range(n):
-                yield [c[off:off + int(lens[k])] for c in chans], float(poss[k])
+                yield [c[off:off + int(clens[k][y])] for y, c in enumerate(chans)], float(poss[k])
                 off += int(lens[k])
             if status == N.E_LUA:
                 raise LuaError("the reference iterator raises a Lua error here (end of data inside the prefill / a malformed block)")

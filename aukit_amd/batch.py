@@ -378,7 +378,9 @@ class AudioBatch:
 
 
 class Chunks:
-    """Per-stream chunk metadata of a stream.* run (lengths and the iterator's position values)."""
+    """Per-stream chunk metadata of a stream.* run (lengths and the iterator's position values).  `lens[s, k]` is the length of chunk k's first
+    channel; `chan_lens[s, k, c]` every channel's (they differ only in the last chunk of a stream.pcm stream that ends inside a frame, and only
+    on a context with OPT_CHANNEL_LENS set)."""
 
     def __init__(self, handle):
         n = C.c_uint32()
@@ -394,6 +396,11 @@ class Chunks:
         N.check(N.lib().aukit_chunks_get(handle, self.nchunks.ctypes.data_as(C.POINTER(C.c_uint32)), self.lens.ctypes.data_as(C.POINTER(C.c_uint32)),
                                          self.pos.ctypes.data_as(C.POINTER(C.c_double)), self.status.ctypes.data_as(C.POINTER(C.c_int32)),
                                          self.length_seconds.ctypes.data_as(C.POINTER(C.c_double))))
+        nch = C.c_uint32()
+        N.check(N.lib().aukit_chunks_channel_lens(handle, C.byref(nch), None))
+        self.channels = nch.value
+        self.chan_lens = np.zeros((self.n, m, max(self.channels, 1)), dtype=np.uint32)
+        N.check(N.lib().aukit_chunks_channel_lens(handle, C.byref(nch), self.chan_lens.ctypes.data_as(C.POINTER(C.c_uint32))))
         N.lib().aukit_chunks_free(handle)
 
 
@@ -596,7 +603,8 @@ class StreamHandle:
         N.check(N.lib().aukit_stream_finish(self._h))
 
     def next(self):
-        """→ ("chunk", [per-channel float64 arrays], pos) | ("need_input", None, None) | ("end", None, None)"""
+        """→ ("chunk", [per-channel float64 arrays], pos) | ("need_input", None, None) | ("end", None, None); every channel's array has its own
+        length (aukit_stream_chunk_lens: they differ only in an uneven last chunk, OPT_CHANNEL_LENS)"""
         if getattr(self, "_buf", None) is None:  # one buffer per handle (a fresh zero-filled 64 MB array per chunk was most of a chunk's cost)
             self._buf_ch = 2
             self._buf = np.empty(self._cap * self._buf_ch, dtype=np.float64)
@@ -612,7 +620,10 @@ class StreamHandle:
             N.check(rc)
             break
         if st.value == N.STREAM_CHUNK:
-            return "chunk", [buf[c * self._cap: c * self._cap + ln.value].copy() for c in range(ch.value)], pos.value
+            lens = (C.c_uint32 * ch.value)()
+            N.check(N.lib().aukit_stream_chunk_lens(self._h, lens, C.c_uint32(ch.value)))
+            self.last_lens = [int(v) for v in lens]
+            return "chunk", [buf[c * self._cap: c * self._cap + lens[c]].copy() for c in range(ch.value)], pos.value
         return ("need_input" if st.value == N.STREAM_NEED_INPUT else "end"), None, None
 
     def length(self):

@@ -381,10 +381,11 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     char keyb[256];
     unsigned long long oh = 1469598103934665603ull;   // FNV-1a over the stream offsets (a freed batch's address can come back with another layout)
     for (uint64_t o : in->off) { oh ^= o; oh *= 1099511628211ull; }
-    snprintf(keyb, sizeof keyb, "%p/%llu/%u/%llx/%d/%d/%d/%d/%.17g/%d/%d/%d/%llu/%llu/%d", (const void *)in, (unsigned long long)in->version, in->n, oh,
+    snprintf(keyb, sizeof keyb, "%p/%llu/%u/%llx/%d/%d/%d/%d/%.17g/%d/%d/%d/%llu/%llu/%d/%d", (const void *)in, (unsigned long long)in->version, in->n, oh,
              d->bit_depth + (table ? 1000 : 0), d->data_type, d->big_endian, C, d->sample_rate, interp, mono, nd, (unsigned long long)ctx->sb_bytes, (unsigned long long)ctx->sb_outputs,
-             ctx->sinc_w);
+             ctx->sinc_w, ctx->chan_lens ? 1 : 0);   // (the chunk table of a stream that ends inside a frame differs between the two settings of AUKIT_OPT_CHANNEL_LENS)
     std::vector<Seg> segs;
+    std::vector<PcmTail> tails;   // the uneven last chunks (AUKIT_OPT_CHANNEL_LENS): stream_pcm_tail.hip behind the segments
     std::vector<uint64_t> lens(in->n, 0);
     uint64_t in_bytes = 0, out_elems = 0;
     aukit_chunks *ck = new aukit_chunks();
@@ -404,6 +405,8 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
             segs.resize(ctx->spcm_segs.size() / sizeof(Seg));
             if (!segs.empty()) memcpy(segs.data(), ctx->spcm_segs.data(), ctx->spcm_segs.size());
         }
+        tails.resize(ctx->spcm_tail.size() / sizeof(PcmTail));
+        if (!tails.empty()) memcpy(tails.data(), ctx->spcm_tail.data(), ctx->spcm_tail.size());
         lens = ctx->spcm_lens;
         in_bytes = ctx->spcm_in_bytes; out_elems = ctx->spcm_out_elems;
     } else {
@@ -421,16 +424,20 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     ck->status.assign(in->n, 0);
     ck->length_seconds.assign(in->n, 0);
     std::vector<std::vector<uint32_t>> clens(in->n);
+    std::vector<uint32_t> n_long_ch(in->n, 0);   // != 0: how many of the stream's channels (the first ones) are one output LONGER in its last chunk; clens holds their length
+    bool any_uneven = false;
     for (uint32_t s = 0; s < in->n; s++) {
         uint64_t nb = in->off[s + 1] - in->off[s];
         // Data that ends inside a frame (round 6).  With the mono mix-down every index is read for ALL channels (`self[i] = (rawget(self, i) or 0) + read()`,
         // :2368): the frame a channel is missing from raises where a frame missing altogether would — inside the pcall (the chunk ends there, :2389-2407) or,
         // in the prefill, as `if not c then return nil end` (:2377-2384): the partial frame counts for nothing.  WITHOUT the mix-down the channels in front
         // of the gap get one output more than the others in the last chunk (`for i ... for y`: they are written before the missing one raises) — chunk
-        // lengths per channel, which this ABI does not have: refused, as is data that ends inside a SAMPLE (`string.rep` with a fractional count is the VM's business).
+        // lengths per channel, which a host reads only if it says so (AUKIT_OPT_CHANNEL_LENS: aukit_chunks_channel_lens); refused otherwise, as is data
+        // that ends inside a SAMPLE either way (`string.rep` with a fractional count is the VM's business).
+        const int part = (int)((nb / (size_t)bd) % (size_t)C);   // channels the partial frame holds
         if (nb % ((size_t)bd * C) != 0) {
             if (nb % (size_t)bd != 0) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: data ends inside a sample (stream %u)", s); }
-            if (!mono) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: data ends inside a frame and the channels are not mixed down: the reference's last chunk is longer in its first channels (stream %u)", s); }
+            if (!mono && !ctx->chan_lens) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: data ends inside a frame and the channels are not mixed down: the reference's last chunk is longer in its first channels (stream %u)", s); }
         }
         const long long nframes = (long long)(nb / ((size_t)bd * C));
         ck->length_seconds[s] = ((double)(nb + ctx->sb_bytes) / bd) / C / d->sample_rate;  // :2245, :2423 (sb_bytes: what a stream handle has dropped already)
@@ -438,8 +445,16 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         if (sinc) {   // units: samples, or whole frames with the mix-down (a partial frame raises where it is read)
             const long long U = mono ? nframes : (long long)(nb / (size_t)bd);
             const size_t first = scalls.size();
-            ck->status[s] = sinc_plan_stream(sm, sgrid, U, is_float && !mono, is_float, in->off[s], s, scalls);
-            for (size_t k = first; k < scalls.size(); k++) { clens[s].push_back(scalls[k].n_out); lens[s] += scalls[k].n_out; }
+            ck->status[s] = sinc_plan_stream(sm, sgrid, U, is_float && !mono, is_float, in->off[s], s, scalls, ctx->chan_lens && !mono);
+            for (size_t k = first; k < scalls.size(); k++) {
+                const uint32_t n0 = scalls[k].n_out + (scalls[k].pad ? 1 : 0);   // the first table's length; tables pad .. nd-1 have one less
+                if (scalls[k].pad) {
+                    if (k + 1 != scalls.size()) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: an uneven chunk that is not the stream's last (stream %u)", s); }
+                    n_long_ch[s] = scalls[k].pad; any_uneven = true;
+                }
+                scalls[k].out_off = lens[s];
+                clens[s].push_back(n0); lens[s] += n0;
+            }
         } else
         for (long c = 0;; c++) {
             const long long src_base = (long long)c * cp.K - istart[interp];  // frame of table index 0
@@ -462,6 +477,40 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
             g.out_stride = 0;
             g.pad = 0;
             segs.push_back(g);
+            if (part && !mono && n_out < 48000) {
+                // the stream's last chunk (ok = false behind it), uneven: the partial frame is index w_avail + 1 of channels 0 .. part-1, which reach it at
+                // output n_out + 1 and are written before channel `part` raises.  An invariant, not a case: at or below 48 kHz x moves up by at most one
+                // per output and the prefill has read up to iend, so `need` rises by at most one index per output and need[n_out], the first entry above
+                // w_avail, is w_avail + 1 — the check only keeps a plan that broke it from reading past the data
+                if (need[n_out] != (int)w_avail + 1) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: the last chunk's read order at %.17g Hz is not modelled (stream %u)", d->sample_rate, s); }
+                PcmTail t;
+                t.src_base = src_base;
+                t.w_lo = g.w_lo; t.w_hi = g.w_hi;
+                t.n_short = n_out;
+                t.j_first = (unsigned)(std::upper_bound(cp.acc.begin(), cp.acc.end(), (int)w_avail) - cp.acc.begin());   // acc <= need: never behind n_out
+                t.stream = s; t.m = (unsigned)part;
+                t.out_stride = 0; t.pad = 0;
+                t.out_off = lens[s];   // patched with the row offset below
+                tails.push_back(t);
+                n_long_ch[s] = (uint32_t)part; any_uneven = true;
+                clens[s].push_back(n_out + 1);
+                lens[s] += n_out + 1;
+                break;
+            }
+            if (part && !mono && is_float && ctx->chan_lens && cp.acc[n_out - 1] > (int)w_avail) {
+                // a float string whose data runs out behind a FULL chunk's last floor index: nothing raises (the next call's prefill ends the stream), the
+                // chunk is even — but its last outputs tap index w_avail + 1, where channels 0 .. part-1 own the partial frame's sample and the others
+                // fall back on their neighbours.  The same item without the extra output (pad = 1)
+                PcmTail t;
+                t.src_base = src_base;
+                t.w_lo = g.w_lo; t.w_hi = g.w_hi;
+                t.n_short = n_out;
+                t.j_first = (unsigned)(std::upper_bound(cp.acc.begin(), cp.acc.end(), (int)w_avail) - cp.acc.begin());
+                t.stream = s; t.m = (unsigned)part;
+                t.out_stride = 0; t.pad = 1;
+                t.out_off = lens[s];
+                tails.push_back(t);
+            }
             clens[s].push_back(n_out);
             lens[s] += n_out;
             if (n_out < 48000) break;  // ok = false → next call returns nil
@@ -480,7 +529,17 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
             nacc += clens[s][k];
         }
     }
+    if (any_uneven) {   // every channel's length; only a stream's last chunk differs
+        const size_t mc = std::max<uint32_t>(ck->max_chunks, 1);
+        ck->chan_lens.assign((size_t)ck->n * mc * nd, 0);
+        for (uint32_t s = 0; s < in->n; s++)
+            for (uint32_t k = 0; k < ck->nchunks[s]; k++)
+                for (int ch = 0; ch < nd; ch++)
+                    ck->chan_lens[((size_t)s * mc + k) * nd + ch] = clens[s][k] - ((n_long_ch[s] && k + 1 == ck->nchunks[s] && ch >= (int)n_long_ch[s]) ? 1 : 0);
+    }
+    ck->channels = (uint32_t)nd;
     ctx->spcm_key = keyb;
+    ctx->spcm_tail.assign(reinterpret_cast<const unsigned char *>(tails.data()), reinterpret_cast<const unsigned char *>(tails.data()) + tails.size() * sizeof(PcmTail));
     if (sinc) {
         ctx->spcm_segs.assign(reinterpret_cast<const unsigned char *>(&sm), reinterpret_cast<const unsigned char *>(&sm) + sizeof sm);
         ctx->spcm_segs.insert(ctx->spcm_segs.end(), reinterpret_cast<const unsigned char *>(scalls.data()), reinterpret_cast<const unsigned char *>(scalls.data()) + scalls.size() * sizeof(SincCall));
@@ -514,6 +573,18 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     P.table = table ? 1 : 0;
     P.lp_alpha = 1 - std::exp(-(d->sample_rate / 96000) * 2 * M_PI);  // :2365
     P.out = a->dev;
+    for (PcmTail &t : tails) {
+        t.out_off += a->row_off[t.stream];
+        t.out_stride = (unsigned)a->row_stride[t.stream];
+    }
+    ResampleParams TP = P;   // what the tail kernel reads of it (the paths below complete P for themselves)
+    TP.ratio = cp_ratio;
+    auto finish = [&]() -> int {   // behind whichever kernel ran the segments: the long channels of the uneven last chunks
+        int trc = launch_stream_pcm_tail(ctx, tails, TP, interp, dtype);
+        if (trc) { delete ck; return trc; }
+        if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
+        return AUKIT_OK;
+    };
     int src = table ? SRC_PCM_GENERIC : pick_pcm_source(in, d, false, mono != 0);
     bool done = false;
     if (table) {   // the numbers of a table are not bytes: only the generic staging reads them (reference order, fp64)
@@ -623,8 +694,7 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         rc = launch_resample(ctx, src, interp, EPI_STREAM_PCM, dtype, P, lds, in_bytes + out_elems * dtype_size(dtype), nullptr);
         if (rc) { delete ck; return rc; }
     }
-    if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
-    return AUKIT_OK;
+    return finish();
 }
 
 // ---------------------------------------------------------------- stream.g711  aukit.lua:2850-2913
@@ -1058,9 +1128,12 @@ int aukit_stream_decode(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
                         aukit_audio **out, aukit_chunks **chunks) {
     if (!ctx || !in || !desc || !out) return fail(AUKIT_E_ARG, "null argument");
     AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
-    if (desc->codec == AUKIT_CODEC_PCM) return stream_pcm(ctx, in, desc, interp, mono, dtype, out, chunks);
-    if (desc->codec == AUKIT_CODEC_G711) return stream_g711(ctx, in, desc, interp, mono, dtype, out, chunks);
-    return stream_block_codec(ctx, in, desc, interp, mono, dtype, out, chunks);
+    int rc;
+    if (desc->codec == AUKIT_CODEC_PCM) rc = stream_pcm(ctx, in, desc, interp, mono, dtype, out, chunks);
+    else if (desc->codec == AUKIT_CODEC_G711) rc = stream_g711(ctx, in, desc, interp, mono, dtype, out, chunks);
+    else rc = stream_block_codec(ctx, in, desc, interp, mono, dtype, out, chunks);
+    if (!rc && chunks && *chunks && *out) (*chunks)->channels = (uint32_t)(*out)->channels;   // chunk tables per chunk, for aukit_chunks_channel_lens
+    return rc;
 }
 
 }  // extern "C"

@@ -48,6 +48,7 @@ struct aukit_ctx {
     int ktiming_nested = 0;     // > 0: an entry point running inside another one (dfpwm_spec.hip's hard streams): ctx_begin_kernel / ctx_end_kernel leave the outer call's events alone
     int exact_math = 0;         // AUKIT_OPT_EXACT_MATH: 1 = F32 storage is computed in fp64 (wave_f64.hip; reference-order kernels where that
                                 //   one does not apply), 2 = always the reference-order kernels; 0 = f32 taps
+    bool chan_lens = false;     // AUKIT_OPT_CHANNEL_LENS: the host reads chunk lengths per channel (stream.pcm delivers its uneven last chunk)
     bool fast_store_x4 = true;  // AUKIT_OPT_STORE_X4: LDS-transposed 16-byte stores in the fast kernels
     std::string last_kernel;
     float last_ms = 0.f;
@@ -128,6 +129,7 @@ struct aukit_ctx {
     // the same batch comes back with the same descriptor — a 4096-stream plan is 1.5 ms of host work against a 2.1 ms kernel
     std::string spcm_key;
     std::vector<unsigned char> spcm_segs;
+    std::vector<unsigned char> spcm_tail;   // ... and the work items of the uneven last chunks (stream_pcm_tail.hip), before their row offsets
     std::vector<uint64_t> spcm_lens;
     uint64_t spcm_in_bytes = 0, spcm_out_elems = 0;
     struct aukit_chunks *spcm_ck = nullptr;
@@ -209,6 +211,10 @@ struct aukit_chunks {
     // what a bounded reader-function handle cuts at (stream_handle.hip); empty where it is not known
     std::vector<uint64_t> in_end;
     std::vector<uint64_t> in_first;
+    // AUKIT_OPT_CHANNEL_LENS: chunk tables per chunk (set by aukit_stream_decode for every codec) and, only where some chunk's channels differ in
+    // length, every channel's: chan_lens[(s * max_chunks + k) * channels + ch].  Empty: every channel has lens[s * max_chunks + k]
+    uint32_t channels = 1;
+    std::vector<uint32_t> chan_lens;
 };
 
 namespace aukit {

@@ -114,6 +114,23 @@ bool fast_fmt_try(aukit_ctx *ctx, const aukit_codec_desc *d, int interp, double 
 bool fast_try(aukit_ctx *ctx, int src_kind, int interp, double old_rate, double new_rate, const std::vector<Seg> &segs, ResampleParams &P,
               uint64_t algorithmic_bytes, int *rc, int epi = 0, double alpha = 0);
 
+// stream_pcm_tail.hip: the uneven last chunk of aukit.stream.pcm (AUKIT_OPT_CHANNEL_LENS) — data that ends inside a frame without the mix-down.
+// The segment kernels have run the chunk with what the SHORT channels see (table indices up to w_hi, n_short outputs); one work item per such
+// stream then gives the channels in front of the gap (y < m), whose tables reach w_hi + 1, their outputs again where a tap lands there, and
+// the one output more they have.
+struct PcmTail {
+    long long src_base;          // source frame of table index 0 (the chunk's Seg::src_base)
+    int w_lo, w_hi;              // the short channels' valid indices; channels y < m also hold w_hi + 1 (the partial frame)
+    unsigned n_short;            // outputs of the short channels; the long ones have n_short + 1
+    unsigned j_first;            // the first output (0-based) that can reach index w_hi + 1
+    unsigned stream, m;          // source stream; channels in the partial frame (1 .. C-1)
+    unsigned out_stride;
+    unsigned pad;                // 1: a full, even chunk of a float string whose last outputs tap the partial frame — no output more, nothing to fill
+    unsigned long long out_off;  // element offset of channel 0's first output of this chunk
+};
+static_assert(sizeof(PcmTail) == 48, "PcmTail layout");
+int launch_stream_pcm_tail(aukit_ctx *ctx, const std::vector<PcmTail> &items, const ResampleParams &P, int interp, int dtype);
+
 // position of output o (0-based) exactly as the reference computes it on the host
 static inline double host_pos(uint64_t o, double ratio) { return ((double)o) / ratio + 1; }
 

@@ -316,6 +316,7 @@ int aukit_ctx_set_option(aukit_ctx *c, int option, int value) {
     else if (option == AUKIT_OPT_STORE_X4) c->fast_store_x4 = value != 0;
     else if (option == AUKIT_OPT_COLLECT_STATS) c->collect_stats = value != 0;
     else if (option == AUKIT_OPT_DFPWM_SPECULATE) c->dfx_off = value == 0;
+    else if (option == AUKIT_OPT_CHANNEL_LENS) c->chan_lens = value != 0;
     else return fail(AUKIT_E_ARG, "unknown option %d", option);
     return AUKIT_OK;
 }
@@ -576,6 +577,15 @@ int aukit_chunks_get(const aukit_chunks *c, uint32_t *nchunks, uint32_t *lens, d
     if (pos) std::copy(c->pos.begin(), c->pos.end(), pos);
     if (status) std::copy(c->status.begin(), c->status.end(), status);
     if (length_seconds) std::copy(c->length_seconds.begin(), c->length_seconds.end(), length_seconds);
+    return AUKIT_OK;
+}
+int aukit_chunks_channel_lens(const aukit_chunks *c, uint32_t *channels, uint32_t *lens) {
+    if (!c) return fail(AUKIT_E_ARG, "chunks is null");
+    const uint32_t C = c->channels ? c->channels : 1;
+    if (channels) *channels = C;
+    if (!lens) return AUKIT_OK;
+    if (!c->chan_lens.empty()) std::copy(c->chan_lens.begin(), c->chan_lens.end(), lens);
+    else for (size_t i = 0; i < c->lens.size(); i++) for (uint32_t ch = 0; ch < C; ch++) lens[i * C + ch] = c->lens[i];   // equal lengths, replicated
     return AUKIT_OK;
 }
 void aukit_chunks_free(aukit_chunks *c) { delete c; }

@@ -37,6 +37,8 @@ struct aukit_stream {
     aukit_ctx *ctx = nullptr;
     aukit_codec_desc desc{};
     int interp = 0, mono = 0, dtype = AUKIT_F64;
+    bool chan_lens = false;    // AUKIT_OPT_CHANNEL_LENS of the context when the handle was opened: every decode of this handle runs with it
+    std::vector<uint32_t> last_lens;   // every channel's length of the chunk delivered last (aukit_stream_chunk_lens)
     uint8_t *dbuf = nullptr;   // device: everything fed so far
     size_t dcap = 0, fed = 0;
     bool finished = false, dirty = true;
@@ -99,7 +101,10 @@ static int redecode(aukit_stream *h) {
     h->ctx->sb_dfpwm_on = (h->desc.codec == AUKIT_CODEC_DFPWM || h->desc.codec == AUKIT_CODEC_MDFPWM) && h->sb_bytes > 0;
     h->ctx->sb_dfpwm_n = h->desc.codec == AUKIT_CODEC_MDFPWM ? 2 : 1;
     for (int i = 0; i < 6; i++) { h->ctx->sb_dfpwm[i] = h->df_state[i]; h->ctx->sb_dfpwm2[i] = h->df_state[6 + i]; }   // the rest of a stream: the factories add what was dropped to their positions
+    const bool ctx_chan_lens = h->ctx->chan_lens;
+    h->ctx->chan_lens = h->chan_lens;
     rc = aukit_stream_decode(h->ctx, b, &h->desc, h->interp, h->mono, h->dtype, &h->spare, &ck);
+    h->ctx->chan_lens = ctx_chan_lens;
     h->ctx->sb_bytes = 0; h->ctx->sb_outputs = 0; h->ctx->sb_samples = 0; h->ctx->sb_pos = 0; h->ctx->sb_dfpwm_on = false; h->ctx->sb_dfpwm_n = 1;
     if (!rc) rc = aukit_ctx_sync(h->ctx);
     aukit_batch_free(b);
@@ -254,6 +259,7 @@ int aukit_stream_open(aukit_ctx *ctx, const aukit_codec_desc *desc, int interp, 
     if (interp < 0 || interp > 3) return fail(AUKIT_E_ARG, "invalid interpolation");
     aukit_stream *h = new aukit_stream();
     h->ctx = ctx; h->desc = *desc; h->interp = interp; h->mono = mono ? 1 : 0; h->dtype = dtype;
+    h->chan_lens = ctx->chan_lens;
     *out = h;
     return AUKIT_OK;
 }
@@ -305,7 +311,10 @@ int aukit_stream_next(aukit_stream *h, double *dst, uint64_t dst_elems, uint32_t
         const uint32_t nch = h->ck->nchunks.empty() ? 0 : h->ck->nchunks[0];
         return h->finished ? nch : (nch ? nch - 1 : 0);
     };
-    if (h->delivered >= decided() && (h->dirty || h->decoded_at != h->fed || !h->ck)) {
+    // (with AUKIT_OPT_CHANNEL_LENS the last chunk of the unfinished prefix — whole frames only — is not the finished stream's when that ends inside a
+    // frame: the complete input is decoded before anything more goes out.  A handle opened WITHOUT the option keeps what it always did: a finished
+    // input that ends inside a frame still delivers the prefix's last chunk before the string call's refusal surfaces on the call after it)
+    if ((h->delivered >= decided() || (h->chan_lens && h->finished && h->dirty)) && (h->dirty || h->decoded_at != h->fed || !h->ck)) {
         int rc = redecode(h);
         if (rc && h->finished) return rc;  // the string version's own error for these bytes
         if (rc == AUKIT_E_NOMEM || rc == AUKIT_E_HIP) return rc;  // not a verdict on the bytes: the caller must hear about it
@@ -350,9 +359,20 @@ int aukit_stream_next(aukit_stream *h, double *dst, uint64_t dst_elems, uint32_t
         }
     *len = n;
     *state = AUKIT_STREAM_CHUNK;
+    h->last_lens.assign((size_t)C, n);
+    if (!h->ck->chan_lens.empty() && h->ck->channels == (uint32_t)C)   // an uneven chunk: the rows behind a shorter channel's length hold 0
+        for (int c = 0; c < C; c++) h->last_lens[c] = h->ck->chan_lens[(size_t)k * C + c];
     h->delivered++;
     h->delivered_samples += n;
     if (!h->finished) (void)compact(h);   // (never the call's status: the chunk is out)
+    return AUKIT_OK;
+}
+
+int aukit_stream_chunk_lens(aukit_stream *h, uint32_t *lens, uint32_t n_lens) {
+    if (!h || !lens) return fail(AUKIT_E_ARG, "null argument");
+    if (h->last_lens.empty()) return fail(AUKIT_E_ARG, "aukit_stream_chunk_lens before a chunk was delivered");
+    if (n_lens < h->last_lens.size()) return fail(AUKIT_E_ARG, "%zu channels, %u lengths offered", h->last_lens.size(), n_lens);
+    std::copy(h->last_lens.begin(), h->last_lens.end(), lens);
     return AUKIT_OK;
 }
 

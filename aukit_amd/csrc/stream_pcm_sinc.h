@@ -42,9 +42,9 @@ struct SincCall {
     long long U;                    // units in the stream
     unsigned long long src;         // byte offset of the stream in the batch
     unsigned long long out_off;     // element offset of table 0's first output of this chunk (the row offset is added at launch)
-    unsigned out_stride, n_out;     // elements between the tables' rows; outputs of this chunk (the same for every table)
+    unsigned out_stride, n_out;     // elements between the tables' rows; outputs of this chunk (tables pad .. nd-1 where pad != 0, else every table)
     int first, prev_first;          // this call / the call before is the stream's first
-    unsigned stream, pad;
+    unsigned stream, pad;           // pad != 0 (AUKIT_OPT_CHANNEL_LENS, a stream's last call): tables 0 .. pad-1 have n_out + 1 outputs
 };
 static_assert(sizeof(SincCall) == 64, "SincCall layout");
 
@@ -125,7 +125,7 @@ inline SincCallOutcome sinc_call_outcome(const SincMap &m, const SincGrid &g, co
     while (ys < nd && unit(ys, xf) < U) ys++;
     r.n_out = (unsigned)(jf - 1);
     r.ragged_at = (int)ys;
-    if (nil_reads || ys > 0 || r.n_out == 0) return r;
+    if (nil_reads || (ys == 0 && r.n_out == 0)) return r;   // (no chunk at all: the iterator returns nil before the re-base)
     // #d[y] is the last index present; d[y][l-W .. l] is read again, and an absent one there calls read() past the end
     for (long long y = 0; y < nd && !r.rebase_raises; y++) {
         long long lo = 1, hi = m.K + 1;   // first t >= 1 whose unit is >= U
@@ -139,17 +139,23 @@ inline SincCallOutcome sinc_call_outcome(const SincMap &m, const SincGrid &g, co
 
 // Every call of one stream of U units: appends the calls that give a chunk (out_off relative to the stream's row, out_stride left 0) and
 // returns the stream's status — 0 (the iterator ends with nil), AUKIT_E_LUA (it raises behind the last chunk), or AUKIT_E_UNSUPPORTED: the
-// last chunk has fewer outputs in its later tables (data that ends inside a burst without the mix-down), which the ABI's one length per
-// chunk cannot carry — that chunk is withheld, the ones before it are delivered.
+// last chunk has fewer outputs in its later tables (data that ends inside a burst without the mix-down), which one length per chunk cannot
+// carry — that chunk is withheld, the ones before it are delivered.  `chan_lens` (AUKIT_OPT_CHANNEL_LENS): the host reads a length per
+// table — the chunk is delivered (SincCall::pad = the tables that are one output longer) with the status the re-base behind it decides.
 inline int sinc_plan_stream(const SincMap &m, const SincGrid &g, long long U, bool nil_reads, bool is_float, unsigned long long src,
-                            unsigned stream, std::vector<SincCall> &calls) {
+                            unsigned stream, std::vector<SincCall> &calls, bool chan_lens = false) {
     if (U < m.nd) return is_float ? 0 : AUKIT_E_LUA;   // the prefill: `if not c then return nil end` for floats, a raise for the rest
     SincCall c{};
     c.A = m.nd; c.A_prev = 0; c.U = U; c.src = src; c.first = 1; c.prev_first = 0; c.stream = stream;
     unsigned long long done = 0;
     for (;;) {
         const SincCallOutcome o = sinc_call_outcome(m, g, c, nil_reads);
-        if (o.ragged_at > 0) return AUKIT_E_UNSUPPORTED;
+        if (o.ragged_at > 0) {
+            if (!chan_lens) return AUKIT_E_UNSUPPORTED;
+            c.n_out = o.n_out; c.pad = (unsigned)o.ragged_at; c.out_off = done;   // #chunk[1] = n_out + 1 > 0: delivered; the pcall failed, so it is the last
+            calls.push_back(c);
+            return o.rebase_raises ? AUKIT_E_LUA : 0;
+        }
         if (o.n_out == 0) return 0;                      // #chunk[1] == 0: the iterator returns nil (:2407)
         c.n_out = o.n_out;
         c.out_off = done;

@@ -34,8 +34,9 @@ __global__ __launch_bounds__(256) void k_stream_pcm_sinc(const SincParams P) {
     const unsigned call = blockIdx.x / P.tiles_per_call, tin = blockIdx.x - call * P.tiles_per_call;
     const SincCall c = P.calls[call];
     const unsigned o0 = tin * SPS_TILE;
-    if (o0 >= c.n_out) return;   // (block-uniform)
-    const unsigned cnt = min((unsigned)SPS_TILE, c.n_out - o0);
+    const unsigned n_long = c.n_out + (c.pad ? 1u : 0u);   // an uneven last chunk: tables 0 .. pad-1 have one output more
+    if (o0 >= n_long) return;   // (block-uniform)
+    const unsigned cnt = min((unsigned)SPS_TILE, n_long - o0);
     const int tid = threadIdx.x, W = (int)P.m.W;
     const double pi = 3.14159265358979323846;
 
@@ -63,6 +64,8 @@ __global__ __launch_bounds__(256) void k_stream_pcm_sinc(const SincParams P) {
     const unsigned char *base = P.src + c.src;
 
     for (int y = 0; y < (int)P.m.nd; y++) {
+        const unsigned n_y = c.n_out + ((unsigned)y < c.pad ? 1u : 0u);
+        const unsigned cnt_y = n_y > o0 ? min((unsigned)SPS_TILE, n_y - o0) : 0u;   // (0: the tile holds the longer tables' extra output alone)
         __syncthreads();   // the table before is read, and so is ss
         for (int e = tid; e < n_stage; e += 256) {
             const long long p = sinc_unit(P.m, c, y, k_lo + e);
@@ -85,7 +88,7 @@ __global__ __launch_bounds__(256) void k_stream_pcm_sinc(const SincParams P) {
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < 5; r++) {
-            if (!act[r]) continue;
+            if (!act[r] || (r < 4 && (unsigned)tid + 256u * (unsigned)r >= cnt_y)) continue;
             double s;
             if (isint[r]) {
                 s = tab[min(max(kv[r] - k_lo, 0), n_stage - 1)];   // d[x]  :2396
@@ -108,7 +111,8 @@ __global__ __launch_bounds__(256) void k_stream_pcm_sinc(const SincParams P) {
         if (tid == 0 && o0 == 0) ss[0] = 0;   // ls starts at 0 in every call (chunk[y][0] is nil, :2390-2392)
         __syncthreads();
         OUT_T *row = reinterpret_cast<OUT_T *>(P.out) + c.out_off + (unsigned long long)y * c.out_stride;
-        for (unsigned i = (unsigned)tid; i < cnt; i += 256) {
+        if (cnt_y < cnt && tid == 0) row[o0 + cnt_y] = (OUT_T)0;   // a shorter table's row up to the first table's length
+        for (unsigned i = (unsigned)tid; i < cnt_y; i += 256) {
             const double prev = ss[i], s = ss[1 + i];
             const double ns = prev + P.lp_alpha * (s - prev);                                   // :2401
             row[o0 + i] = (OUT_T)lua_clamp(ns * (ns < 0 ? 128 : 127), -128, 127);             // :2402

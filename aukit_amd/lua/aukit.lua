@@ -22,6 +22,7 @@ typedef struct { int32_t codec, channels; double sample_rate; int32_t bit_depth,
 typedef struct { aukit_codec_desc desc; uint64_t payload_off, payload_len; int32_t wav_data_type, bit_depth; double length_seconds; } aukit_container;
 const char *aukit_last_error(void);
 int aukit_ctx_create(aukit_ctx **out, int device); void aukit_ctx_destroy(aukit_ctx *ctx);
+int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);
 int aukit_parse_container(const uint8_t *bytes, uint64_t n, int kind, int stream, aukit_container *out);
 int aukit_batch_upload(aukit_ctx *, aukit_batch **, const uint8_t *bytes, const uint64_t *offsets, uint32_t n);
 int aukit_batch_info(const aukit_batch *, uint32_t *n, uint64_t *total); int aukit_batch_download(aukit_ctx *, const aukit_batch *, uint8_t *dst); void aukit_batch_free(aukit_batch *);
@@ -74,10 +75,12 @@ int aukit_pack_pcm(aukit_ctx *, const aukit_audio *, int bit_depth, int data_typ
 int aukit_stream_decode(aukit_ctx *, const aukit_batch *, const aukit_codec_desc *, int interp, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks);
 int aukit_chunks_info(const aukit_chunks *, uint32_t *n, uint32_t *max_chunks);
 int aukit_chunks_get(const aukit_chunks *, uint32_t *nchunks, uint32_t *lens, double *pos, int32_t *status, double *length_seconds); void aukit_chunks_free(aukit_chunks *);
+int aukit_chunks_channel_lens(const aukit_chunks *, uint32_t *channels, uint32_t *lens);
 typedef struct aukit_stream aukit_stream;
 int aukit_stream_open(aukit_ctx *, const aukit_codec_desc *, int interp, int mono, int dtype, aukit_stream **out);
 int aukit_stream_feed(aukit_stream *, const uint8_t *bytes, uint64_t n); int aukit_stream_finish(aukit_stream *);
 int aukit_stream_next(aukit_stream *, double *dst, uint64_t dst_elems, uint32_t cap, uint32_t *len, int32_t *channels, double *pos, int32_t *state);
+int aukit_stream_chunk_lens(aukit_stream *, uint32_t *lens, uint32_t n_lens);
 int aukit_stream_length(aukit_stream *, double *seconds); void aukit_stream_close(aukit_stream *);
 ]]
 
@@ -112,7 +115,11 @@ local function u32(v) v = math.floor(v) % 4294967296 return string.char(v % 256,
 
 local ctxp = ffi.new("aukit_ctx*[1]")
 local function ctx()
-    if ctxp[0] == nil and C.aukit_ctx_create(ctxp, 0) ~= 0 then error(ffi.string(C.aukit_last_error()), 3) end
+    if ctxp[0] == nil then
+        if C.aukit_ctx_create(ctxp, 0) ~= 0 then error(ffi.string(C.aukit_last_error()), 3) end
+        -- AUKIT_OPT_CHANNEL_LENS: a chunk is a table per channel, each with its own length (stream.pcm's last chunk when data ends inside a frame)
+        if C.aukit_ctx_set_option(ctxp[0], 4, 1) ~= 0 then error(ffi.string(C.aukit_last_error()), 3) end
+    end
     return ctxp[0]
 end
 -- every native status becomes the Lua error the reference raises (AUKIT_E_ARG / AUKIT_E_LUA carry the reference's own message)
@@ -611,9 +618,11 @@ local function streamer_fn(d, fn, first, mono, dtype)
             check(rc)
             if st[0] == 0 then      -- AUKIT_STREAM_CHUNK
                 local chunk = {}
+                local clens = ffi.new("uint32_t[?]", ch[0])
+                check(C.aukit_stream_chunk_lens(h, clens, ch[0]))
                 for c = 1, ch[0] do
                     local t = {}
-                    for i = 1, len[0] do t[i] = buf[(c - 1) * CHUNK_CAP + i - 1] end
+                    for i = 1, clens[c - 1] do t[i] = buf[(c - 1) * CHUNK_CAP + i - 1] end
                     chunk[c] = t
                 end
                 return chunk, pos[0]
@@ -648,6 +657,10 @@ local function streamer(d, data, mono, dtype, first, len)
     local m = math.max(mx[0], 1)
     local nch, lens, pos, status, length = ffi.new("uint32_t[1]"), ffi.new("uint32_t[?]", m), ffi.new("double[?]", m), ffi.new("int32_t[1]"), ffi.new("double[1]")
     check(C.aukit_chunks_get(ck[0], nch, lens, pos, status, length))
+    local ncl = ffi.new("uint32_t[1]")
+    check(C.aukit_chunks_channel_lens(ck[0], ncl, nil))
+    local clens = ffi.new("uint32_t[?]", m * math.max(ncl[0], 1))   -- clens[k * ncl + c - 1]: channel c of chunk k
+    check(C.aukit_chunks_channel_lens(ck[0], ncl, clens))
     C.aukit_chunks_free(ck[0])
     local buf, ch, total = fetch(audio)
     local k, off = 0, 0
@@ -660,7 +673,7 @@ local function streamer(d, data, mono, dtype, first, len)
         local chunk = {}
         for c = 1, ch do
             local t = {}
-            for i = 1, lens[k] do t[i] = buf[(c - 1) * total + off + i - 1] end
+            for i = 1, clens[k * ncl[0] + c - 1] do t[i] = buf[(c - 1) * total + off + i - 1] end
             chunk[c] = t
         end
         off = off + lens[k]; k = k + 1

@@ -142,13 +142,18 @@ typedef enum {
     AUKIT_OPT_STORE_X4 = 1,   /* 1 (default): fast kernels transpose results through LDS and store 16 B per lane */
     AUKIT_OPT_COLLECT_STATS = 2, /* 1: calls that have counters (aukit_ctx_get_counter) read them back — one more device→host sync per call.
                                    0 (default): they do not. */
-    AUKIT_OPT_DFPWM_SPECULATE = 3 /* 1 (default): aukit_dfpwm_transcode_mono cuts every stream into time chunks that are decoded, mixed and ENCODED
+    AUKIT_OPT_DFPWM_SPECULATE = 3,/* 1 (default): aukit_dfpwm_transcode_mono cuts every stream into time chunks that are decoded, mixed and ENCODED
                                    by a lane each from a guessed encoder state, verified afterwards (dfpwm_spec.hip) — several times faster
                                    on signal (silence a stream STARTS with included), same bytes always; a few short streams (up to 16 of
                                    up to 40 stream-seconds together) stay with the exact parallel encoder either way; up to ~1.6x slower than
                                    0 where the guesses fail and the probe does not notice (noise-like streams; silence INSIDE the streams of a
                                    batch too large for a second round is noticed and declined).  0: one encoder lane per stream behind the
                                    chunk-parallel decoder. */
+    AUKIT_OPT_CHANNEL_LENS = 4 /* 1: this host reads chunk lengths per channel (aukit_chunks_channel_lens, aukit_stream_chunk_lens).  stream.pcm without the
+                                   mix-down on data that ends inside a frame — or, with sinc, inside a later call's burst of taps — then delivers the
+                                   reference's last chunk, one output longer in the channels in front of the gap, with the reference's status,
+                                   instead of refusing it.  0 (default): one length per chunk, those inputs are refused by name.  No effect on
+                                   mono streams, the mix-down or any other codec. */
 } aukit_option;
 int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);
 /* counters of the most recent call that produced them (AUKIT_OPT_COLLECT_STATS = 1) */
@@ -289,11 +294,18 @@ int aukit_stream_decode_table(aukit_ctx *ctx, const double *values, const uint64
                               int mono, int dtype, aukit_audio **out, aukit_chunks **chunks);
 /* per stream s: nchunks[s]; chunk k of stream s: length and the iterator's second return value.
  * status[s]: 0 = iterator ended with nil, AUKIT_E_LUA = the reference iterator raises after the last chunk, AUKIT_E_UNSUPPORTED = the
- * reference's next chunk has different lengths per channel, which this table cannot carry: the chunks before it are delivered, it is not
- * (stream.mdfpwm's chunk with holes; stream.pcm with sinc when data without the mix-down ends inside a later call's burst of taps). */
+ * reference's next chunk has different lengths per channel and is not delivered, the chunks before it are: stream.mdfpwm's chunk with holes
+ * always; stream.pcm with sinc when data without the mix-down ends inside a later call's burst of taps, unless AUKIT_OPT_CHANNEL_LENS is set.
+ * `lens` is the length of the chunk's FIRST channel (`#chunk[1]`, what the reference's position advances by, aukit.lua:2408, :2422): never the
+ * shorter one.  With AUKIT_OPT_CHANNEL_LENS a stream's LAST chunk may be one output shorter in its later channels (aukit.lua:2389-2407: the
+ * channels in front of the gap are written before the missing one raises): aukit_chunks_channel_lens has every channel's length.  The audio keeps
+ * its layout — a stream's rows hold the sum of the first channel's lengths; what lies behind a shorter channel's own length is 0. */
 int aukit_chunks_info(const aukit_chunks *c, uint32_t *n, uint32_t *max_chunks);
 int aukit_chunks_get(const aukit_chunks *c, uint32_t *nchunks /* n */, uint32_t *lens /* n*max */, double *pos /* n*max */,
                      int32_t *status /* n */, double *length_seconds /* n */);
+/* `*channels` = number of chunk tables; lens[(s * max + k) * channels + ch] = length of channel ch of chunk k of stream s (NULL: only the
+ * count is asked for).  Filled for every codec — equal lengths replicated — so that a host needs one code path. */
+int aukit_chunks_channel_lens(const aukit_chunks *c, uint32_t *channels, uint32_t *lens /* n*max*channels */);
 void aukit_chunks_free(aukit_chunks *c);
 
 /* ---- several GPUs of one node.  No function of the path reads another stream, so a batch shards by stream index with no
@@ -364,6 +376,10 @@ int aukit_stream_finish(aukit_stream *s);                                    /* 
  * Where the reference's iterator raises instead of ending, the call returns AUKIT_E_LUA.  A chunk never exceeds 48000 samples per channel
  * except stream.flac / stream.qoa (one coded block resampled: at most 65535 * 48000 / sampleRate). */
 int aukit_stream_next(aukit_stream *s, double *dst, uint64_t dst_elems, uint32_t cap, uint32_t *len, int32_t *channels, double *pos, int32_t *state);
+/* the length of every channel of the chunk aukit_stream_next delivered last (`n_lens` >= its channel count).  `*len` above is the first
+ * channel's; the handle takes AUKIT_OPT_CHANNEL_LENS from its context when it is opened, and only a chunk delivered after aukit_stream_finish
+ * can be shorter in its later channels (what lies behind a channel's own length at dst is 0). */
+int aukit_stream_chunk_lens(aukit_stream *s, uint32_t *lens, uint32_t n_lens);
 int aukit_stream_length(aukit_stream *s, double *seconds);                   /* the factory's second return value, for the bytes fed so far */
 /* stream bytes resident on the device, bytes dropped in front of them (stream.pcm / g711 / adpcm / msadpcm drop what delivered calls consumed:
  * austream.lua:19-64 feeds live sources for hours), and the input bytes of every decode so far, summed */
