@@ -147,7 +147,7 @@ static int decode_resample_flat(aukit_ctx *ctx, const aukit_batch *in, const auk
     aukit_audio *a = *out;
     if ((rc = audio_prepare(ctx, &a, in->n, C, do_resample ? new_rate : d->sample_rate, dtype, lens.data()))) return rc;
     *out = a;
-    if (!do_resample && d->codec == AUKIT_CODEC_PCM && !getenv("AUKIT_NO_FAST_CONVERT")) {
+    if (!do_resample && d->codec == AUKIT_CODEC_PCM) {
         std::vector<UnpackRow> ur((size_t)in->n * C);
         uint64_t longest = 0;
         for (uint32_t s = 0; s < in->n; s++)
@@ -237,7 +237,7 @@ static int decode_resample_flat(aukit_ctx *ctx, const aukit_batch *in, const auk
     // integer it interpolates and CLAMPS (:667-668) what the exact rational position copies unclamped, and that shows on samples beyond ±1:
     // unsigned 16 / 24 / 32-bit (Q4 reaches 2) and float strings keep the reference-order kernel)
     if (do_resample && dtype == AUKIT_F32 && d->codec == AUKIT_CODEC_PCM && !ctx->exact_math && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC) &&
-        (d->data_type == AUKIT_SIGNED || (d->data_type == AUKIT_UNSIGNED && d->bit_depth == 8)) && !only_if && !getenv("AUKIT_NO_FAST_CONVERT")) {
+        (d->data_type == AUKIT_SIGNED || (d->data_type == AUKIT_UNSIGNED && d->bit_depth == 8)) && !only_if) {
         // every other PCM format with a resample behind it, F32 tolerance path: unpacked to one f32 row per channel (k_pcm_unpack), then the f32
         // wave kernel on the rows — what stream.pcm does for these formats.  (k_resample moved 145-210 G samples/s on 24-bit stereo / float.)
         std::vector<UnpackRow> ur((size_t)in->n * C);
@@ -389,7 +389,7 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     std::vector<uint64_t> lens(in->n, 0);
     uint64_t in_bytes = 0, out_elems = 0;
     aukit_chunks *ck = new aukit_chunks();
-    const bool plan_hit = ctx->spcm_ck && ctx->spcm_key == keyb && !getenv("AUKIT_NO_PLAN_CACHE");
+    const bool plan_hit = ctx->spcm_ck && ctx->spcm_key == keyb;
     double cp_ratio = 48000 / d->sample_rate;
     // sinc (stream_pcm_sinc.h): one work item per iterator call instead of segments; the cache keeps the map in front of the calls
     const bool sinc = interp == AUKIT_INTERP_SINC;
@@ -608,7 +608,7 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         if (aligned4) done = fast_try(ctx, SRC_PCM_S16LE_STEREO, interp, d->sample_rate, 48000, segs, P, in_bytes + out_elems * 4, &frc, mono ? 2 : 1, P.lp_alpha);
         if (done && frc) { delete ck; return frc; }
     }
-    if (!done && dtype == AUKIT_F32 && C == 1 && bd == 1 && d->data_type != AUKIT_FLOAT && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC) && !getenv("AUKIT_NO_FAST_CONVERT")) {
+    if (!done && dtype == AUKIT_F32 && C == 1 && bd == 1 && d->data_type != AUKIT_FLOAT && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {
         int frc = AUKIT_OK;  // 8-bit mono: the wave kernel reads the bytes themselves (fast_stream_u8.hip)
         done = fast_try(ctx, SRC_PCM8_MONO, interp, d->sample_rate, 48000, segs, P, in_bytes + out_elems * 4, &frc, 1, P.lp_alpha);
         if (done && frc) { delete ck; return frc; }
@@ -620,7 +620,7 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         done = fast_fmt_try(ctx, d, interp, 48000, segs, P, in_bytes + out_elems * 4, &frc, &unused, (mono && C > 1) ? 2 : 1, P.lp_alpha);
         if (done && frc) { delete ck; return frc; }
     }
-    if (!done && dtype == AUKIT_F32 && !ctx->exact_math && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC) && !getenv("AUKIT_NO_FAST_CONVERT")) {
+    if (!done && dtype == AUKIT_F32 && !ctx->exact_math && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {
         // every other PCM format (8-bit unsigned at 48 kHz is what most ComputerCraft audio is kept in), f32 tolerance path: the string is
         // unpacked to one f32 row per output channel (k_pcm_unpack; the `mono` mix is made there, in the reference's order) and the stream.pcm
         // wave kernel runs on the rows (fast_stream_f32.hip).  The reference-order kernel below moved 190 G samples/s on these.
@@ -935,7 +935,7 @@ int audio_from_int_rows(aukit_ctx *ctx, int src_kind, const void *rows_dev, cons
     int rc;
     if ((rc = audio_prepare(ctx, &a, n, channels, do_resample ? new_rate : rate, dtype, lens.data()))) return rc;
     *out = a;
-    if (!do_resample && (src_kind == SRC_I8 || src_kind == SRC_I16 || src_kind == SRC_I32) && !getenv("AUKIT_NO_FAST_CONVERT")) {
+    if (!do_resample && (src_kind == SRC_I8 || src_kind == SRC_I16 || src_kind == SRC_I32)) {
         std::vector<ConvRow> cr((size_t)n * channels);
         uint64_t longest = 0;
         for (uint32_t s = 0; s < n; s++)

@@ -9,7 +9,6 @@
 //   The stream.adpcm path keeps the decoded block in LDS and resamples it in the same kernel (fp64, reference order).
 #include <algorithm>
 #include <type_traits>
-#include <chrono>
 #include <map>
 #include "resample.h"
 #include "resample_dev.h"
@@ -929,7 +928,7 @@ struct CvImaF32 {
 //   2. (about one output in 500) the polynomial in fp64 on exact doubles and the exact rational position, FMA Horner form, taken
 //      when more than 1e-6 away from an integer (the reference's x carries < 1024 · 2^-53 of rounding, times a slope below 1600).
 //   3. otherwise, and where the nil fall-backs of the block's ends apply: the reference-order code on the same table.
-// Same-box A/B against the fp64-only short-cut of k_ima_stream (AUKIT_IMA_F64=1) in DESIGN.md §3.
+// Same-box A/B against the fp64-only short-cut of k_ima_stream in DESIGN.md §3.
 // PH > 0 (round 3): the phases in registers.  A block's outputs start at phase 0 and rows R and R + PH (PH = fb / gcd(fb, 64): 5 at 22 050 and 44 100 Hz)
 // share their phases, so a lane keeps the weights and the first-tap offsets of its PH phases for the whole launch; the clean rows of a block then run
 // in groups of PH rows without position arithmetic, the guard's turn-downs noted in a bit each and redone behind the group by one copy of tiers 2-3.
@@ -1227,7 +1226,7 @@ static int ima_decode_audio(aukit_ctx *ctx, const aukit_batch *in, const aukit_c
         if ((rc = ctx_begin_kernel(ctx))) return rc;
         uint64_t max_blocks = 0;
         if (wav) for (uint32_t s = 0; s < in->n; s++) max_blocks = std::max<uint64_t>(max_blocks, (in->off[s + 1] - in->off[s] + (uint64_t)d->block_align - 1) / (uint64_t)d->block_align);
-        if (wav && C == 1 && max_blocks >= 1 && !getenv("AUKIT_IMA_ROWS_WAVE") && !getenv("AUKIT_IMA_ROWS_SERIAL")) {   // a lane per block (round 6)
+        if (wav && C == 1 && max_blocks >= 1 && !getenv("AUKIT_IMA_ROWS_WAVE")) {   // a lane per block (round 6)
             std::vector<uint64_t> blk0(jobs.size() + 1, 0);
             for (size_t j = 0; j < jobs.size(); j++) blk0[j + 1] = blk0[j] + (jobs[j].nbytes + (uint64_t)d->block_align - 1) / (uint64_t)d->block_align;
             const size_t nwaves = (size_t)((blk0.back() + 63) / 64);
@@ -1242,7 +1241,7 @@ static int ima_decode_audio(aukit_ctx *ctx, const aukit_batch *in, const aukit_c
             Q.block_align = d->block_align; Q.mask_mono_index = P.mask_mono_index; Q.out = P.out; Q.err = P.err;
             if (Q.nblocks) hipLaunchKernelGGL(k_ima_lanes, dim3((unsigned)((Q.nblocks + 63) / 64)), dim3(64), 0, ctx->stream, Q);
         } else
-        if (wav && max_blocks > 1 && (uint64_t)jobs.size() * max_blocks < (1ull << 31) && !getenv("AUKIT_IMA_ROWS_SERIAL"))
+        if (wav && max_blocks > 1 && (uint64_t)jobs.size() * max_blocks < (1ull << 31))
             hipLaunchKernelGGL(k_ima_rows_blocks, dim3((unsigned)(jobs.size() * (C == 1 ? (max_blocks + AUKIT_IMA_BPW - 1) / AUKIT_IMA_BPW : max_blocks))), dim3(64), 0, ctx->stream, P, (unsigned)max_blocks);
         else hipLaunchKernelGGL(k_ima_rows, dim3((unsigned)jobs.size()), dim3(64), 0, ctx->stream, P);
         AUKIT_HIP_CHECK(hipGetLastError());
@@ -1314,9 +1313,6 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     const uint32_t newlen_full = (uint32_t)std::floor(spb * ratio);                // :2768
     const uint64_t ips = (uint64_t)iterPerSecond;
     const int nd = mono ? 1 : C;
-    static const bool TT = getenv("AUKIT_HOST_TIMING") != nullptr;
-    auto T0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char *w) { if (TT) { auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[ima host] %-12s %7.1f us\n", w, std::chrono::duration<double, std::micro>(t - T0).count()); T0 = t; } };
     aukit_chunks *ck = new aukit_chunks();
     ck->n = in->n;
     ck->nchunks.assign(in->n, 0);
@@ -1327,13 +1323,11 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     hipStream_t scan_stream = ctx->stream;
     if (in->n) {  // which streams die on a header index above 88, and where (the answer is awaited after the plans below were made)
         // (round 6, late: on the look-ahead stream — the scan reads the input batch and nothing else, and its host wait was a wait for everything the call
-        // BEFORE had left on ctx->stream: back-to-back calls now plan while the kernel of the call before runs.  AUKIT_IMA_SCAN_MAIN=1: as before)
-        if (!getenv("AUKIT_IMA_SCAN_MAIN")) {
-            int prc = ctx_pre_stream(ctx, &scan_stream);
-            if (prc) { delete ck; return prc; }
-            if (in->ready && hipStreamWaitEvent(scan_stream, in->ready, 0) != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "hipStreamWaitEvent failed"); }
-        }
-        DevBuf &sb = scan_stream == ctx->stream ? ctx->misc_buf : ctx->scan_buf;
+        // BEFORE had left on ctx->stream: back-to-back calls now plan while the kernel of the call before runs)
+        int prc = ctx_pre_stream(ctx, &scan_stream);
+        if (prc) { delete ck; return prc; }
+        if (in->ready && hipStreamWaitEvent(scan_stream, in->ready, 0) != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "hipStreamWaitEvent failed"); }
+        DevBuf &sb = ctx->scan_buf;
         int rc0 = sb.ensure((size_t)in->n * 4 + 16);
         if (rc0) { delete ck; return rc0; }
         unsigned *dfb = reinterpret_cast<unsigned *>(sb.p);
@@ -1392,7 +1386,6 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         plan_of[s] = last;
     }
     if (in->n && hipStreamSynchronize(scan_stream) != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "stream.adpcm header scan failed"); }
-    lap("scan+plans");
     for (uint32_t s = 0; s < in->n; s++) {
         const uint64_t nb = in->off[s + 1] - in->off[s];
         ck->length_seconds[s] = (double)(nb + ctx->sb_bytes) / (double)ba * spb / d->sample_rate;   // :2834
@@ -1421,11 +1414,9 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         }
     }
     int rc;
-    lap("plan");
     aukit_audio *a = *out;
     if ((rc = audio_prepare(ctx, &a, in->n, nd, 48000, dtype, lens.data()))) { delete ck; return rc; }
     *out = a;
-    lap("prepare");
     const uint64_t nblocks = blk0[in->n];
     if (nblocks) {
         std::vector<uint64_t> tab(blk0);
@@ -1461,7 +1452,7 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
             }
         }
         // one channel, at most 512 phases: the three-tier kernel on an f32 table (k_ima_stream_f32)
-        if (P.fast && P.fb <= 512 && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC) && !getenv("AUKIT_IMA_F64")) {
+        if (P.fast && P.fb <= 512 && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {
             const int wf = interp == AUKIT_INTERP_CUBIC ? 4 : 1;
             std::vector<float> w((size_t)P.fb * wf);
             for (unsigned r = 0; r < P.fb; r++) {
@@ -1486,18 +1477,15 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
             if (lds <= 64 * 1024) {
                 P.cap = capf;
                 const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));
-                unsigned gmul = 8;   // 1 / 2 / 4 / 8 / 16 / 32 measured 2.98 / 2.83 / 2.74 / 2.71 / 2.72 / 2.74 ms on config 3a
-                if (const char *e = getenv("AUKIT_IMA_GRID_MUL")) { const int v = atoi(e); if (v >= 1) gmul = (unsigned)v; }   // tuning knob
+                const unsigned gmul = 8;   // 1 / 2 / 4 / 8 / 16 / 32 measured 2.98 / 2.83 / 2.74 / 2.71 / 2.72 / 2.74 ms on config 3a
                 const unsigned grid = (unsigned)std::min<uint64_t>((nblocks + 3) / 4, (uint64_t)ctx->num_cus * per_cu * gmul);
-                lap("tables");
                 if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
                 const float *wgp = reinterpret_cast<const float *>(S3.p);
                 // the phases in registers when a lane meets 3 or 5 of them (fb = 3 · 2^i or 5 · 2^i, i <= 6: 22 050 and 44 100 Hz have 5)
                 unsigned g64 = P.fb, h64 = 64;
                 while (h64) { const unsigned r = g64 % h64; g64 = h64; h64 = r; }
                 unsigned ph = P.fb / g64;
-                const char *er = getenv("AUKIT_IMA_REGS");
-                if ((ph != 3 && ph != 5) || (er && atoi(er) == 0)) ph = 0;
+                if (ph != 3 && ph != 5) ph = 0;
                 P.audit = nullptr;
                 if (ctx->collect_stats) {   // the audited instantiation (floor_wave.hip): tier 1's values against tier 2's, every output
                     if ((rc = ctx->fmt_flag.ensure(64))) { delete ck; return rc; }
@@ -1518,14 +1506,11 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
                 for (uint64_t l : lens) out_elems += l * nd;
                 if ((rc = ctx_end_kernel(ctx, "k_ima_stream_f32", in->total() + out_elems * dtype_size(dtype)))) { delete ck; return rc; }
                 // (the plans end in front of the first block whose header index is above 88 — k_ima_scan_headers —: the kernel's own flag for such a block cannot
-                // be raised by a planned block.  Waiting for it kept the host behind every call's kernel; AUKIT_IMA_ASSERT=1 waits and looks, as do the audited runs)
+                // be raised by a planned block.  Waiting for it kept the host behind every call's kernel; the audited runs wait and look)
                 int herr = 0;
-                if (P.audit || getenv("AUKIT_IMA_ASSERT")) {
+                if (P.audit) {
                     AUKIT_HIP_CHECK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, ctx->stream));
                     AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                }
-                lap("kernel+sync");
-                if (P.audit) {
                     unsigned h[2] = {0, 0};
                     AUKIT_HIP_CHECK(hipMemcpy(h, P.audit, 8, hipMemcpyDeviceToHost));
                     float e; memcpy(&e, &h[0], 4);
@@ -1534,7 +1519,6 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
                 }
                 if (herr) { delete ck; return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (field '?')"); }  // ima_step_table[idx > 88]
                 if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
-                lap("chunks out");
                 return AUKIT_OK;
             }
         }
@@ -1734,7 +1718,7 @@ int aukit_dfpwm_transcode_mono(aukit_ctx *ctx, const aukit_batch *in, int channe
     if (rc) return rc;
     bool aligned = (reinterpret_cast<uintptr_t>(in->data()) & 15) == 0;
     for (uint32_t s = 0; s < in->n && aligned; s++) aligned = (in->off[s] & 15) == 0;
-    const bool stereo = channels == 2 && aligned && !getenv("AUKIT_DFPWM_GENERIC");
+    const bool stereo = channels == 2 && aligned;
     if (channels == 2) {
         // every lane decodes, mixes and encodes its own time chunk of a stream; verified and patched afterwards (dfpwm_spec.hip)
         bool spec = false;
@@ -1760,11 +1744,10 @@ int aukit_dfpwm_transcode_mono(aukit_ctx *ctx, const aukit_batch *in, int channe
         uint64_t max_bytes = 0;
         for (uint32_t s = 0; s < in->n; s++) max_bytes = std::max<uint64_t>(max_bytes, in->off[s + 1] - in->off[s]);
         const uint64_t want = std::max<uint64_t>(1, lanes_full / in->n);
-        int slices = in->n >= 2048 ? (int)std::min<uint64_t>(8, max_bytes / 1920 / want) : 1;  // measured on config 4: 1 / 4 / 8 slices = 27.0 / 25.7 / 24.4 ms per step
-        if (const char *e = getenv("AUKIT_DFPWM_SLICES")) slices = atoi(e);
+        const int slices = in->n >= 2048 ? (int)std::min<uint64_t>(8, max_bytes / 1920 / want) : 1;  // measured on config 4: 1 / 4 / 8 slices = 27.0 / 25.7 / 24.4 ms per step
         // batches of up to one 64-stream group per CU: decoder and encoder in one persistent launch (AUKIT_DFPWM_FUSED=1: whatever the size, 0: never)
         const char *fe = getenv("AUKIT_DFPWM_FUSED");
-        if (fe ? atoi(fe) != 0 : (in->n >= 2048 && !getenv("AUKIT_DFPWM_SLICES"))) {
+        if (fe ? atoi(fe) != 0 : in->n >= 2048) {
             bool taken = false;
             rc = dfpwm_transcode_fused(ctx, in, reinterpret_cast<signed char *>(ctx->tmp_buf.p), t, t + in->n, b->data(), reinterpret_cast<const unsigned long long *>(b->d_off), off.data(), &taken);
             if (rc) return rc;

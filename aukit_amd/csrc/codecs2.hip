@@ -3,7 +3,6 @@
 // The QOA LMS (aukit.lua:1686-1701) has a wrap inside the recurrence, so frames are sequential: one lane per (frame, channel);
 // parallelism comes from frames × streams.  (MS-ADPCM lives in msadpcm.hip.)
 #include <algorithm>
-#include <chrono>
 #include "resample.h"
 #include "dfpwm_dev.h"
 
@@ -229,9 +228,6 @@ __global__ __launch_bounds__(64) void k_gather_heads(const unsigned char *src, c
 static int mdfpwm_rows(aukit_ctx *ctx, const aukit_batch *in, const char *badmsg, std::vector<MdHeader> &hdrs, std::vector<uint64_t> &row_off,
                        std::vector<uint64_t> &row_len) {
     constexpr unsigned HEAD = 300;
-    static const bool TT = getenv("AUKIT_HOST_TIMING") != nullptr;
-    auto T0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char *w) { if (TT) { auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[mdfpwm_rows host] %-14s %8.1f us\n", w, std::chrono::duration<double, std::micro>(t - T0).count()); T0 = t; } };
     std::vector<uint8_t> heads_pageable;
     uint8_t *heads = nullptr;
     if (in->n) {
@@ -243,10 +239,8 @@ static int mdfpwm_rows(aukit_ctx *ctx, const aukit_batch *in, const char *badmsg
         AUKIT_HIP_CHECK(hipGetLastError());
         heads = static_cast<uint8_t *>(ctx_host_stage(ctx, (size_t)in->n * HEAD));
         if (!heads) { heads_pageable.resize((size_t)in->n * HEAD); heads = heads_pageable.data(); }
-        lap("gather launch");
         AUKIT_HIP_CHECK(hipMemcpyAsync(heads, S3.p, (size_t)in->n * HEAD, hipMemcpyDeviceToHost, ctx->stream));
         AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        lap("heads d2h+sync");
     }
     hdrs.resize(in->n);
     row_off.assign((size_t)in->n * 2, 0);
@@ -275,11 +269,9 @@ static int mdfpwm_rows(aukit_ctx *ctx, const aukit_batch *in, const char *badmsg
         tab[2 * (size_t)in->n + 2 * s] = tot; tab[2 * (size_t)in->n + 2 * s + 1] = tot + stride;
         tot += 2 * stride;
     }
-    lap("host headers");
     int rc = ctx->tmp_buf.ensure((size_t)tot + 64);
     if (rc) return rc;
     if ((rc = upload_table(ctx, ctx->misc_buf, tab.data(), tab.size() * 8))) return rc;  // tmp_buf2 is the parallel decoder's scratch
-    lap("ensure+upload");
     if (in->n) {
         const unsigned long long *t = reinterpret_cast<const unsigned long long *>(ctx->misc_buf.p);
         if ((rc = ctx_begin_kernel(ctx))) return rc;
@@ -292,7 +284,6 @@ static int mdfpwm_rows(aukit_ctx *ctx, const aukit_batch *in, const char *badmsg
         if (dfpwm_decode_parallel_feed(ctx, in->data(), p_off, p_fed, 6000, 12000, 0, 1, reinterpret_cast<signed char *>(ctx->tmp_buf.p), t + 2 * (size_t)in->n, nullptr, 0,
                                        &prc)) {
             if (prc) return prc;
-            lap("par decode");
             return ctx_end_kernel(ctx, "k_df_chunks", in->total() + tot);
         }
         DfInit2 I2{};
@@ -497,7 +488,7 @@ static int stream_dfpwm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
                            in->n, (unsigned long long)adv, reinterpret_cast<signed char *>(ctx->tmp_buf.p), reinterpret_cast<const unsigned long long *>(ctx->misc_buf.p), I);
         }
         AUKIT_HIP_CHECK(hipGetLastError());
-        if (d->sample_rate == 48000 && !getenv("AUKIT_NO_FAST_CONVERT")) {  // ratio 1: a strided copy (k_dfpwm_stream_copy)
+        if (d->sample_rate == 48000) {  // ratio 1: a strided copy (k_dfpwm_stream_copy)
             if ((rc = upload_table(ctx, ctx->seg_buf, segs.data(), segs.size() * sizeof(Seg)))) { delete ck; return rc; }
             ctx->plan_key.clear();  // (seg_buf no longer holds a resample plan)
             if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
@@ -595,14 +586,10 @@ __global__ __launch_bounds__(256) void k_mdfpwm_chunks(const signed char *rows, 
 
 static int stream_mdfpwm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks_out) {
     if (dtype != AUKIT_I8) return fail(AUKIT_E_ARG, "stream.mdfpwm output must be AUKIT_I8");
-    static const bool TT = getenv("AUKIT_HOST_TIMING") != nullptr;
-    auto T0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char *w) { if (TT) { auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[stream.mdfpwm host] %-12s %8.1f us\n", w, std::chrono::duration<double, std::micro>(t - T0).count()); T0 = t; } };
     std::vector<MdHeader> hdrs;
     std::vector<uint64_t> row_off, row_len;
     int rc = mdfpwm_rows(ctx, in, "bad argument #1 (invalid MDFPWM data)", hdrs, row_off, row_len);
     if (rc) return rc;
-    lap("rows");
     aukit_chunks *ck = new aukit_chunks();
     ck->n = in->n;
     ck->nchunks.assign(in->n, 0); ck->status.assign(in->n, 0); ck->length_seconds.assign(in->n, 0);
@@ -627,11 +614,9 @@ static int stream_mdfpwm(aukit_ctx *ctx, const aukit_batch *in, const aukit_code
     ck->pos.assign((size_t)ck->n * mc, 0);
     for (uint32_t s = 0; s < in->n; s++)
         for (uint32_t k = 0; k < ck->nchunks[s]; k++) { ck->lens[(size_t)s * mc + k] = 48000; ck->pos[(size_t)s * mc + k] = (double)(ctx->sb_bytes + 12000ull * k + 1) / 12000; }
-    lap("chunk plan");
     aukit_audio *a = *out;
     if ((rc = audio_prepare(ctx, &a, in->n, mono ? 1 : 2, 48000, AUKIT_I8, lens.data()))) { delete ck; return rc; }
     *out = a;
-    lap("prepare");
     if (in->n) {
         std::vector<uint64_t> tab(row_off);
         tab.insert(tab.end(), lens.begin(), lens.end());
@@ -643,7 +628,6 @@ static int stream_mdfpwm(aukit_ctx *ctx, const aukit_batch *in, const aukit_code
         AUKIT_HIP_CHECK(hipGetLastError());
         ctx->last_kernel = "k_mdfpwm_chunks";
     }
-    lap("launch");
     if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
     return AUKIT_OK;
 }

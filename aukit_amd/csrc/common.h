@@ -58,12 +58,12 @@ struct aukit_ctx {
     // scratch tables (segment/tile/stream descriptors); plan_key caches the last uploaded plan
     aukit::DevBuf seg_buf, tile_buf, misc_buf, tmp_buf, tmp_buf2, tmp_buf3;
     aukit::DevBuf enc_state_buf;  // DFPWM encoder states between the time slices of a transcode (dfpwm_par.hip)
-    hipStream_t aux_stream = nullptr, dec_stream = nullptr;  // aux_stream: the sliced transcode's encoder runs here (dec_stream: unused, kept for the CU-mask experiment)
-    hipEvent_t aux_ev[10] = {};
+    hipStream_t aux_stream = nullptr;  // the sliced transcode's encoder runs here
+    hipEvent_t aux_ev[9] = {};
     hipStream_t side_stream = nullptr;   // independent kernels of one call run next to each other (FLAC's order classes): ctx_side_stream()
     // round 6: the FLAC loader's first stages (stream headers, the sync search) read nothing but the input batch: they run on a stream of their own, into one of
     // two alternating sets of tables, so that call k + 1's search overlaps what call k still has queued on ctx->stream (its filter and normalize passes);
-    // the decoder waits for them by event.  AUKIT_FLAC_NO_LOOKAHEAD=1: everything on ctx->stream as before
+    // the decoder waits for them by event.  AUKIT_FLAC_LOOKAHEAD=0: everything on ctx->stream as before
     hipStream_t pre_stream = nullptr;
     hipEvent_t pre_ev = nullptr;
     aukit::DevBuf flac_set[2];
@@ -83,7 +83,6 @@ struct aukit_ctx {
                                   // user on ctx->stream that is not the FLAC loader has touched it (ctx_scratch3): the next decoder waits for all of ctx->stream
     uint64_t flac_calls = 0;
     hipEvent_t side_ev[2] = {};
-    int aux_enc_cus = -1;
     bool fused_attr_set = false;
     aukit::DevBuf dfx_lut;        // the 64 KiB stereo → mono mix table of the chunk-speculative transcoder (dfpwm_spec.hip), built once
     bool dfx_attr_set = false;
@@ -246,7 +245,7 @@ int lazy_materialize(aukit_ctx *ctx, aukit_audio *a);
 struct LazyFrames {   // the fused FLAC decoder's frames (flac_dev.h), for a deferred resample that reads them in place
     const void *d_frames; uint64_t nfr; const unsigned long long *d_fbase, *d_rowoff; const std::vector<int> *bs0; bool uniform; uint64_t tot_elems;
     const std::vector<unsigned> *nframes;
-    bool scratch16 = false;   // the frames hold int16 finals (k_flac_decode<..., O16>): [channel 0][channel 1] from twice the record's offset
+    bool scratch16 = false;   // the frames hold int16 finals (k_flac_stream / k_flac_pq <O16>): [channel 0][channel 1] from twice the record's offset
 };
 bool lazy_resample_try(aukit_ctx *ctx, const std::vector<uint64_t> &row_off, const std::vector<uint64_t> &row_len, uint32_t n, int C, double rate, double new_rate, int interp,
                        double full, aukit_audio **out, int *rc, const LazyFrames *frames = nullptr, int src_kind = 8 /* SRC_I32 */, double norm_pos = 0, double norm_neg = 0);

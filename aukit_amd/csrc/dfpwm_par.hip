@@ -14,7 +14,7 @@
 //                       true one in practice — records the state it reached, decodes its chunk, records the end state;
 //   4. k_df_verify      wave per stream: where a chunk's recorded start state differs from the true end state of the chunk
 //                       before it, that chunk is decoded again serially from the true state.  Exactness therefore never rests
-//                       on the convergence argument; only the speed does (AUKIT_DFPWM_STATS=1 prints the redo count).
+//                       on the convergence argument; only the speed does (AUKIT_COUNTER_DFPWM_CHUNKS_REDONE is the redo count).
 // Output: de-interleaved int8 rows (the loader), or the stereo → mono mix of aukit.pcm ∘ Audio:mono ∘ encodePCM as int8 (transcode).
 #include <algorithm>
 #include "common.h"
@@ -482,7 +482,7 @@ bool dfpwm_decode_parallel_feed(aukit_ctx *ctx, const unsigned char *src, const 
     // ... for a batch that fills the chip.  A few streams leave most SIMDs idle and the launch takes the time of ONE lane: short chunks then,
     // whatever their warm-up share (one stream of ten seconds: 40 lanes of 7 blocks, 1.24 ms; 235 lanes of 2 blocks, a third of it) — the
     // shortest that keeps the lanes under 3/4 of a wave per SIMD
-    if (!getenv("AUKIT_DFPWM_CHUNKS") && !getenv("AUKIT_DFPWM_BPC_MIN6"))
+    if (!getenv("AUKIT_DFPWM_CHUNKS"))
         for (unsigned b = std::max<unsigned>(nblk ? (nblk + want - 1) / want : 1, 1); b < 6; b++)
             if ((uint64_t)n * ((nblk + b - 1) / b) * 4 <= (uint64_t)ctx->num_cus * 4 * 64 * 3) { bpc = b; break; }
     const unsigned nchunk = nblk ? (nblk + bpc - 1) / bpc : 0;
@@ -521,12 +521,11 @@ bool dfpwm_decode_parallel_feed(aukit_ctx *ctx, const unsigned char *src, const 
         if (hipGetLastError() != hipSuccess) { *rc = fail(AUKIT_E_HIP, "parallel DFPWM decode launch failed"); return true; }
         if (sliced && (*rc = hook->after_slice(k, nsl, (u64)P.c_lo * bpc * W, (u64)P.c_hi * bpc * W))) return true;  // fed bytes [lo, hi) of every stream are final
     }
-    if (getenv("AUKIT_DFPWM_STATS") || ctx->collect_stats) {
+    if (ctx->collect_stats) {
         unsigned h[2] = {0, 0};
         (void)hipMemcpyAsync(h, P.stats, 8, hipMemcpyDeviceToHost, ctx->stream);
         (void)hipStreamSynchronize(ctx->stream);
         ctx->counters[AUKIT_COUNTER_DFPWM_CHUNKS] = h[1]; ctx->counters[AUKIT_COUNTER_DFPWM_CHUNKS_REDONE] = h[0];
-        if (getenv("AUKIT_DFPWM_STATS")) fprintf(stderr, "[dfpwm] %u streams x %u chunks of %u blocks of %llu fed bytes: %u of %u chunks redone serially\n", n, nchunk, bpc, (unsigned long long)W, h[0], h[1]);
     }
     *rc = AUKIT_OK;
     return true;
@@ -551,36 +550,16 @@ bool dfpwm_decode_parallel(aukit_ctx *ctx, const aukit_batch *in, int mode, int 
 int dfpwm_transcode_sliced(aukit_ctx *ctx, const aukit_batch *in, signed char *mono, const u64 *d_moff, const u64 *d_mcount, unsigned char *out, const u64 *d_ooff,
                            const uint64_t *h_ooff, int slices, bool *taken) {
     *taken = false;
-    int enc_cus = 0;  // CUs reserved for the encoder; 0 (default): decoder and encoder share every CU — see below, reserving lost
-    if (const char *e = getenv("AUKIT_DFPWM_ENC_CUS")) enc_cus = std::max(0, std::min(atoi(e), ctx->num_cus - 8));
-    if (!ctx->aux_stream || ctx->aux_enc_cus != enc_cus) {
-        // Sharing every CU (the default): an encoder wave beside two decoder waves on one SIMD slows both by ~40 % (traced, profiles/),
+    if (!ctx->aux_stream) {
+        // Decoder and encoder share every CU: an encoder wave beside two decoder waves on one SIMD slows both by ~40 % (traced, profiles/),
         // and as one encoder wave lands on every CU every decoder workgroup has a slowed wave; with s_setprio 3 in the encoder it keeps
-        // its speed and the decoder runs 1.8x longer (27 ms per step: no gain).  Disjoint CU masks (AUKIT_DFPWM_ENC_CUS = 32 / 48 / 64;
-        // the masks do what they say: tools/micro/cumask_probe.hip) lose outright — 41 / 39 / 34 ms per step: 256 encoder waves packed
+        // its speed and the decoder runs 1.8x longer (27 ms per step: no gain).  Disjoint CU masks (32 / 48 / 64 CUs for the encoder;
+        // the masks do what they say: tools/micro/cumask_probe.hip) lost outright — 41 / 39 / 34 ms per step: 256 encoder waves packed
         // on few CUs run several times slower than one per CU, whatever their store width.
-        if (ctx->aux_stream) { (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); ctx->aux_stream = nullptr; }
-        if (ctx->dec_stream) { (void)hipStreamSynchronize(ctx->dec_stream); (void)hipStreamDestroy(ctx->dec_stream); ctx->dec_stream = nullptr; }
-        if (enc_cus > 0) {
-            const int words = (ctx->num_cus + 31) / 32;
-            std::vector<uint32_t> m_enc(words, 0), m_dec(words, 0);
-            for (int cu = 0; cu < ctx->num_cus; cu++) (cu < enc_cus ? m_enc : m_dec)[cu >> 5] |= 1u << (cu & 31);
-            AUKIT_HIP_CHECK(hipExtStreamCreateWithCUMask(&ctx->aux_stream, (uint32_t)words, m_enc.data()));
-            AUKIT_HIP_CHECK(hipExtStreamCreateWithCUMask(&ctx->dec_stream, (uint32_t)words, m_dec.data()));
-        } else {
-            int lo = 0, hi = 0;
-            (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-            AUKIT_HIP_CHECK(hipStreamCreateWithPriority(&ctx->aux_stream, hipStreamNonBlocking, hi));
-        }
-        for (int i = 0; i < 10; i++) if (!ctx->aux_ev[i]) AUKIT_HIP_CHECK(hipEventCreateWithFlags(&ctx->aux_ev[i], hipEventDisableTiming));
-        ctx->aux_enc_cus = enc_cus;
-    }
-    hipStream_t const user_stream = ctx->stream;
-    struct Restore { aukit_ctx *c; hipStream_t s; ~Restore() { c->stream = s; } } restore{ctx, user_stream};
-    if (ctx->dec_stream) {  // the decoder's launches go to the masked stream: ctx->stream is swapped for the duration of this call
-        AUKIT_HIP_CHECK(hipEventRecord(ctx->aux_ev[9], user_stream));
-        AUKIT_HIP_CHECK(hipStreamWaitEvent(ctx->dec_stream, ctx->aux_ev[9], 0));
-        ctx->stream = ctx->dec_stream;
+        int lo = 0, hi = 0;
+        (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
+        AUKIT_HIP_CHECK(hipStreamCreateWithPriority(&ctx->aux_stream, hipStreamNonBlocking, hi));
+        for (int i = 0; i < 9; i++) if (!ctx->aux_ev[i]) AUKIT_HIP_CHECK(hipEventCreateWithFlags(&ctx->aux_ev[i], hipEventDisableTiming));
     }
     const uint32_t n = in->n;
     uint64_t max_out = 0;
@@ -592,7 +571,6 @@ int dfpwm_transcode_sliced(aukit_ctx *ctx, const aukit_batch *in, signed char *m
     unsigned char *stage = reinterpret_cast<unsigned char *>(ctx->enc_state_buf.p) + round_up((size_t)n * 24 + 16, 64);
     DfSliceHook hook;
     hook.slices = std::min(slices, 8);
-    // (the table of mono offsets `d_moff` was uploaded on the caller's stream: ordered by the event above)
     hook.after_slice = [&](unsigned k, unsigned nsl, u64 fed_lo, u64 fed_hi) -> int {
         AUKIT_HIP_CHECK(hipEventRecord(ctx->aux_ev[k], ctx->stream));
         AUKIT_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_ev[k], 0));
@@ -603,16 +581,12 @@ int dfpwm_transcode_sliced(aukit_ctx *ctx, const aukit_batch *in, signed char *m
             hipLaunchKernelGGL(k_dfpwm_compact, dim3((unsigned)std::min<u64>((max_out / 4 + 256) / 256, 4), n), dim3(256), 0, ctx->aux_stream, stage, sstride, out, d_ooff, n);
             AUKIT_HIP_CHECK(hipGetLastError());
             AUKIT_HIP_CHECK(hipEventRecord(ctx->aux_ev[8], ctx->aux_stream));
-            AUKIT_HIP_CHECK(hipStreamWaitEvent(user_stream, ctx->aux_ev[8], 0));  // the encoder's last slice ends the call (it waited for the decoder's)
+            AUKIT_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->aux_ev[8], 0));  // the encoder's last slice ends the call (it waited for the decoder's)
         }
         return AUKIT_OK;
     };
     int prc = AUKIT_OK;
     const bool ran = dfpwm_decode_parallel(ctx, in, 1, 2, mono, d_moff, nullptr, &prc, 6000, 0, &hook);
-    if (ctx->dec_stream) {  // whatever was enqueued on the masked stream is ordered before the caller's next work
-        AUKIT_HIP_CHECK(hipEventRecord(ctx->aux_ev[9], ctx->dec_stream));
-        AUKIT_HIP_CHECK(hipStreamWaitEvent(user_stream, ctx->aux_ev[9], 0));
-    }
     if (!ran) return AUKIT_OK;  // not taken: the caller runs the plain sequence
     *taken = true;
     return prc;
@@ -637,7 +611,7 @@ struct DfFusedParams {
     int *fst;             // [nchunk][10][npad]: start state (5 ints) and end state (5 ints) of every chunk lane, stream index fastest
     unsigned *flags;      // [nchunk][G] unit done;  flags[nchunk * G] = the ticket counter, [nchunk * G + 1] = workgroups whose encoder sat alone
     unsigned G, npad, total;
-    unsigned dbg;         // AUKIT_DFPWM_FUSED_DBG, A/B only: 1 = the encoder waves never take decoder tickets (same bytes)
+    unsigned dbg;         // always 0 from the host (it was an A/B switch): 1 = the encoder waves never take decoder tickets (same bytes)
     const u64 *mcount;    // mono samples per stream
     unsigned char *enc_out;  // the packed result
     const u64 *ooff;         // [n + 1] byte offset of every stream's bytes in it
@@ -867,7 +841,7 @@ __global__ __launch_bounds__(448) void k_df_fused(const DfFusedParams F) {
     if (wave == enc && blockIdx.x < F.G) {
         const unsigned long long t0 = wall_clock64();
         dff_encoder(F, blockIdx.x, lut, lane);
-        if (lane == 0) atomicMax(&F.flags[(size_t)F.P.nchunk * F.G + 2], (unsigned)(wall_clock64() - t0));  // (AUKIT_DFPWM_STATS: the slowest encoder, 100 MHz ticks)
+        if (lane == 0) atomicMax(&F.flags[(size_t)F.P.nchunk * F.G + 2], (unsigned)(wall_clock64() - t0));  // (timing statistics: the slowest encoder, 100 MHz ticks)
         return;
     }
     const unsigned long long td0 = wall_clock64();
@@ -876,7 +850,7 @@ __global__ __launch_bounds__(448) void k_df_fused(const DfFusedParams F) {
         dff_decode_unit(F, t / F.G, t % F.G, lut, lane);
         t = dff_take(F, lane);
     }
-    if (lane == 0) {  // (AUKIT_DFPWM_STATS) the slowest and the mean decoder wave
+    if (lane == 0) {  // (timing statistics) the slowest and the mean decoder wave
         atomicMax(&F.flags[(size_t)F.P.nchunk * F.G + 5], (unsigned)(wall_clock64() - td0));
         atomicAdd(&F.flags[(size_t)F.P.nchunk * F.G + 6], (unsigned)((wall_clock64() - td0) >> 8));
     }
@@ -934,7 +908,6 @@ int dfpwm_transcode_fused(aukit_ctx *ctx, const aukit_batch *in, signed char *mo
         F.flags = reinterpret_cast<unsigned *>(B + b_tab + b_maps + b_ss + b_st);
         P.stats = reinterpret_cast<unsigned *>(B + b_tab + b_maps + b_ss + b_st + b_fl);
         P.mode = 1; P.C = 2; P.out = mono; P.out_off = d_moff + s0; P.out_stride = nullptr; P.lead = 0;
-        if (const char *e = getenv("AUKIT_DFPWM_FUSED_DBG")) F.dbg = (unsigned)atoi(e);
         F.G = G; F.npad = npad; F.total = nchunk * G; F.mcount = d_mcount + s0;
         F.enc_out = out; F.ooff = d_ooff + s0;
         if (hipMemsetAsync(F.flags, 0, b_fl + 8, ctx->stream) != hipSuccess) return fail(AUKIT_E_HIP, "hipMemsetAsync failed");
@@ -942,15 +915,12 @@ int dfpwm_transcode_fused(aukit_ctx *ctx, const aukit_batch *in, signed char *mo
         hipLaunchKernelGGL(k_df_blockscan, dim3((ns + 63) / 64), dim3(64), 0, ctx->stream, P);
         hipLaunchKernelGGL(k_df_fused, dim3((unsigned)std::max<int>(ctx->num_cus, (int)G)), dim3(448), lds, ctx->stream, F);
         AUKIT_HIP_CHECK(hipGetLastError());
-        if (getenv("AUKIT_DFPWM_STATS") || ctx->collect_stats) {
-            unsigned h[2] = {0, 0}, al[6] = {0, 0, 0, 0, 0, 0};
+        if (ctx->collect_stats) {
+            unsigned h[2] = {0, 0};
             (void)hipMemcpyAsync(h, P.stats, 8, hipMemcpyDeviceToHost, ctx->stream);
-            (void)hipMemcpyAsync(al, F.flags + (size_t)nchunk * G + 1, 24, hipMemcpyDeviceToHost, ctx->stream);
             (void)hipStreamSynchronize(ctx->stream);
             if (s0 == 0) { ctx->counters[AUKIT_COUNTER_DFPWM_CHUNKS] = 0; ctx->counters[AUKIT_COUNTER_DFPWM_CHUNKS_REDONE] = 0; }
             ctx->counters[AUKIT_COUNTER_DFPWM_CHUNKS] += h[1]; ctx->counters[AUKIT_COUNTER_DFPWM_CHUNKS_REDONE] += h[0];
-            if (getenv("AUKIT_DFPWM_STATS")) fprintf(stderr, "[dfpwm fused] %u streams x %u chunks of %u blocks of %llu fed bytes: %u of %u chunks redone by their encoder lane; encoder alone on its SIMD in %u of %d workgroups, slowest encoder %.2f ms (mean over encoders: waiting %.2f ms, verify + encode %.2f ms); decoder waves: slowest %.2f ms, mean %.2f ms\n",
-                    ns, nchunk, bpc, (unsigned long long)W, h[0], h[1], al[0], std::max<int>(ctx->num_cus, (int)G), al[1] * 1e-5, al[2] * 16e-5 / G, al[3] * 16e-5 / G, al[4] * 1e-5, al[5] * 256e-5 / (6.0 * std::max<int>(ctx->num_cus, (int)G)));
         }
     }
     *taken = true;
@@ -1103,7 +1073,7 @@ bool dfpwm_encode_i8_small(aukit_ctx *ctx, const signed char *in, const uint64_t
                            int *rc) {
     // measured on the transcode of random bytes (a noise-like mix: the worst case, many starts are not among the candidates):
     // 1 stream 2.5 vs 15.1 ms, 16 streams 8.7 vs 15.0 ms, 64 streams 14.6 vs 13.1 ms — so up to 16 streams
-    if (n == 0 || n > 16 || getenv("AUKIT_DFPWM_SERIAL") || getenv("AUKIT_DFPWM_ENC_SERIAL")) return false;
+    if (n == 0 || n > 16 || getenv("AUKIT_DFPWM_SERIAL")) return false;
     uint64_t maxc = 0;
     for (uint32_t s = 0; s < n; s++) maxc = std::max(maxc, h_count[s]);
     if (maxc < 65536 || maxc > 0xF0000000ull) return false;
@@ -1146,12 +1116,6 @@ bool dfpwm_encode_i8_small(aukit_ctx *ctx, const signed char *in, const uint64_t
     hipLaunchKernelGGL(k_dfe_resolve, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, in, dch, reinterpret_cast<const unsigned *>(B + o_sf), n, dist, dcount, dend, start, stats);
     hipLaunchKernelGGL(k_dfe_emit, dim3((unsigned)((nch + 63) / 64)), dim3(64), 0, ctx->stream, in, dch, (unsigned)nch, start, out);
     if (hipGetLastError() != hipSuccess) { *rc = fail(AUKIT_E_HIP, "parallel DFPWM encode launch failed"); return true; }
-    if (getenv("AUKIT_DFPWM_STATS")) {
-        unsigned h[2] = {0, 0};
-        (void)hipMemcpyAsync(h, stats, 8, hipMemcpyDeviceToHost, ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream);
-        fprintf(stderr, "[dfpwm] encoder: %u streams in %zu chunks, %u chunk starts not among the candidates (run serially)\n", n, nch, h[0]);
-    }
     *rc = AUKIT_OK;
     return true;
 }

@@ -785,8 +785,8 @@ static int dfx_run(aukit_ctx *ctx, const DfxJob &J, unsigned char *out, const u6
     const uint32_t n = (uint32_t)J.off.size();
     if (ctx->dfx_disable || ctx->dfx_off) return AUKIT_OK;
     // (the environment switches of the older schedules — tests and A/B runs — name those schedules: not this one)
-    if (n == 0 || getenv("AUKIT_DFPWM_SERIAL") || getenv("AUKIT_DFPWM_NOSPEC") || getenv("AUKIT_DFPWM_FUSED") || getenv("AUKIT_DFPWM_SLICES") || getenv("AUKIT_DFPWM_BLOCK") ||
-        getenv("AUKIT_DFPWM_CHUNKS") || getenv("AUKIT_DFPWM_ENC_SERIAL"))
+    if (n == 0 || getenv("AUKIT_DFPWM_SERIAL") || getenv("AUKIT_DFPWM_NOSPEC") || getenv("AUKIT_DFPWM_FUSED") || getenv("AUKIT_DFPWM_BLOCK") ||
+        getenv("AUKIT_DFPWM_CHUNKS"))
         return AUKIT_OK;
     const std::vector<uint64_t> &h_off = J.off, &h_fed = J.fed;
     uint64_t fed_max = 0, fed_sum = 0;
@@ -799,9 +799,9 @@ static int dfx_run(aukit_ctx *ctx, const DfxJob &J, unsigned char *out, const u6
     uint64_t few = 500000;   // fed bytes of the batch (stereo transcode; units of four samples for Audio:dfpwm): four ten-second streams
     if (const char *e = getenv("AUKIT_DFX_FEW")) few = strtoull(e, nullptr, 10);
     if (n <= 16 && fed_sum <= few) return AUKIT_OK;
-    unsigned We = 640, Wd = 64;  // fed bytes: 2560 mono samples of encoder warm-up behind 64 bytes of decoder-only warm-up
+    unsigned We = 640;
+    const unsigned Wd = 64;  // fed bytes: 2560 mono samples of encoder warm-up behind 64 bytes of decoder-only warm-up
     if (const char *e = getenv("AUKIT_DFX_WE")) We = (unsigned)std::max(64, atoi(e)) & ~63u;
-    if (const char *e = getenv("AUKIT_DFX_WD")) Wd = (unsigned)std::max(64, atoi(e)) & ~63u;
     // chunks per stream: enough lanes for `wps` waves on every SIMD, at least three blocks each (the warm-up block is then 1/4 of a lane's work)
     unsigned wps = 2;
     if (const char *e = getenv("AUKIT_DFX_WPS")) wps = (unsigned)std::max(1, atoi(e));
@@ -845,7 +845,6 @@ static int dfx_run(aukit_ctx *ctx, const DfxJob &J, unsigned char *out, const u6
     // the strength scan's lanes: a map block (the bytes between two chunks' warm-up starts) cut into pieces until four waves per SIMD walk them
     unsigned msub = 1;
     while (msub < 16 && (uint64_t)n * nchunk * msub < (uint64_t)ctx->num_cus * 4 * 64 * 4 && (uint64_t)bpc * W / (2 * msub) >= 1024) msub *= 2;
-    if (const char *e = getenv("AUKIT_DFX_MSUB")) msub = (unsigned)std::max(1, std::min(atoi(e), 64));
     const size_t o_tab = take((size_t)n * 24), o_maps = take((size_t)n * nchunk * msub * sizeof(SatMap)), o_ss = take((size_t)n * (nchunk + 1) * 4),
                  o_st = take((size_t)nchunk * 12 * npad * 4), o_ck = take((size_t)nchunk * nck * 6 * npad * 4 + 4), o_fx = take((size_t)nchunk * 13 * npad * 4),
                  o_ctl = take((size_t)9 * npad * 4), o_pst = take((size_t)8 * npad * 4), o_on = take((size_t)2 * npad * 4), o_hard = take((size_t)npad * 4), o_fl = take(64 + (size_t)npad);
@@ -882,9 +881,8 @@ static int dfx_run(aukit_ctx *ctx, const DfxJob &J, unsigned char *out, const u6
     // per stream, a whole step for a gain of a quarter).  What the probe cannot see — silence or noise later in the streams — costs rounds.
     // windows of the probe per stream: one.  (More of them — 64 guesses per batch whatever its size — were tried for small batches, round 6: eight
     // windows are 1.5 ms of a lone lane in front of the host's first look, 8 streams of signal 1.0 -> 2.6 ms; what tells noise from signal at
-    // any batch size is round 0 itself: k_dfx_verify below counts the chunk boundaries where the guesses missed.  AUKIT_DFX_PROBE_WINDOWS for the A/B)
+    // any batch size is round 0 itself: k_dfx_verify below counts the chunk boundaries where the guesses missed)
     X.probe = getenv("AUKIT_DFX_NOPROBE") ? 0u : 1u;
-    if (const char *e = getenv("AUKIT_DFX_PROBE_WINDOWS")) X.probe = (unsigned)std::max(1, std::min(atoi(e), 16));
     // (the prologue's 256 lone waves run on the side stream, beside the strength scan: the probe hides behind k_df_blockmaps)
     if (!ctx->dfx_attr_set) {
         AUKIT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dfx_chunks<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
@@ -933,17 +931,6 @@ static int dfx_run(aukit_ctx *ctx, const DfxJob &J, unsigned char *out, const u6
                 hipLaunchKernelGGL(k_dfx_fix<1>, grid, dim3(256), 0, ctx->stream, X);
             }
             hipLaunchKernelGGL(k_dfx_verify, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, X);
-            if (getenv("AUKIT_DFX_TRACE")) {  // (debugging: where the first streams stand after every round)
-                int hc[16] = {};
-                (void)hipStreamSynchronize(ctx->stream);
-                (void)hipMemcpy(hc, X.ctl, sizeof(int) * std::min<unsigned>(8, npad), hipMemcpyDeviceToHost);
-                (void)hipMemcpy(hc + 8, X.ctl + npad, sizeof(int) * std::min<unsigned>(8, npad), hipMemcpyDeviceToHost);
-                unsigned fl[16] = {};
-                (void)hipMemcpy(fl, X.flags, 64, hipMemcpyDeviceToHost);
-                fprintf(stderr, "[dfpwm spec] round %u: %u hard streams so far, %u re-speculations so far, %u chunks run again by k_dfx_fix\n", r, fl[13], fl[10], fl[11]);
-                fprintf(stderr, "[dfpwm spec] round %u: first not-final chunk of streams 0..7: %d %d %d %d %d %d %d %d; reference states %d %d %d %d %d %d %d %d\n", r, hc[0], hc[1], hc[2], hc[3], hc[4], hc[5], hc[6], hc[7],
-                        hc[8], hc[9], hc[10], hc[11], hc[12], hc[13], hc[14], hc[15]);
-            }
         }
         AUKIT_HIP_CHECK(hipGetLastError());
         if (aside && r0 == 0 && (rc = ctx_side_join(ctx))) return rc;
@@ -954,11 +941,6 @@ static int dfx_run(aukit_ctx *ctx, const DfxJob &J, unsigned char *out, const u6
     }
     ctx->counters[AUKIT_COUNTER_DFPWM_CHUNKS] = h[8]; ctx->counters[AUKIT_COUNTER_DFPWM_CHUNKS_REDONE] = h[11]; ctx->counters[AUKIT_COUNTER_DFPWM_RESPECULATED] = h[10];
     ctx->counters[AUKIT_COUNTER_DFPWM_HARD] = h[13];
-    if (getenv("AUKIT_DFPWM_STATS"))
-        fprintf(stderr, "[dfpwm spec] probe: of %u streams, %u guesses missed, %u silent where the probe ends, %u with silence behind the one they start with%s\n", n, h[14], h[15], h[12], h[6] ? ": declined" : "");
-    if (getenv("AUKIT_DFPWM_STATS") && !h[6])
-        fprintf(stderr, "[dfpwm spec] %u streams x %u chunks of %u blocks of %llu fed bytes (decoder-only warm-up %u, checkpoints every %u, %u rounds): %u chunks verified; %u chunks run again by k_dfx_fix (%u checkpoint intervals); %u stream rounds re-speculated (flags %u %u %u %u %u %u); %u hard streams\n",
-                n, nchunk, bpc, (unsigned long long)W, Wd, G, rounds, h[8], h[11], h[9], h[10], h[0], h[1], h[2], h[3], h[4], h[5], h[13]);
     if (h[6]) return AUKIT_OK;   // declined by the probe (nothing was written): not taken, the caller runs the older schedule
     std::vector<unsigned> hs;
     if (h[13] || h[10]) {   // something was given up on or speculated again: who is not done?

@@ -634,7 +634,7 @@ static int fx_reverb(aukit_ctx *ctx, aukit_audio *a, double delay, double decay,
     for (uint64_t l : a->len)
         if ((long long)l < S + 1 || S < 20) return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (field '?')");
     int rc;
-    if (a->dtype == AUKIT_F32 && !getenv("AUKIT_NO_FUSED_REVERB")) {  // one pass, state in LDS (k_reverb_f32)
+    if (a->dtype == AUKIT_F32) {  // one pass, state in LDS (k_reverb_f32)
         const long long minlag = std::min(std::min(std::min(lag[0], lag[1]), std::min(lag[2], lag[3])), S - 20);
         const size_t lds = (((size_t)S + 1) & ~(size_t)1) * 8 + (size_t)(lag[0] + lag[1] + lag[2] + lag[3]) * 4;
         if (minlag >= 1024 && lds <= 150 * 1024 && S < 0x7FFFFFFFll) {

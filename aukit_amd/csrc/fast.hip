@@ -215,7 +215,6 @@ bool fast_eligible(int src_kind, int interp, double old_rate, double new_rate, F
     // division magic fits 32 bits
     if (b < 2) { a *= 2; b *= 2; }
     F.tile_out = 4096;
-    if (const char *e = getenv("AUKIT_FAST_TILE")) { int v = atoi(e); if (v >= 1024 && v % 1024 == 0) F.tile_out = v; }  // tuning knob
     while (F.tile_out > 1024 && ((double)F.tile_out * (double)a / (double)b + 64) * 4 > 40 * 1024) F.tile_out -= 1024;
     if (((double)F.tile_out * (double)a / (double)b + 64) * 4 > 60 * 1024) return false;
     if (((double)b + (double)F.tile_out * (double)a) * (double)b >= 4294967296.0) return false;  // magic division exactness
@@ -249,7 +248,6 @@ int launch_fast(aukit_ctx *ctx, int src_kind, int interp, const std::vector<Seg>
     const bool x4 = ctx->fast_store_x4;
     size_t lds = (size_t)F.cap * 4 + (x4 ? 4 * 256 * 4 : 0);
     unsigned per_cu = 16 * (unsigned)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));   // 16 x the resident count (8 / 32 / 128 per CU measured 1.53 / 1.44 / 1.41 ms on Audio:resample 44.1k linear)
-    if (const char *e = getenv("AUKIT_FAST_BLOCKS_PER_CU")) { int v = atoi(e); if (v >= 1) per_cu = (unsigned)v; }  // tuning knob
     unsigned grid = std::min<unsigned>(P.n_tiles, (unsigned)ctx->num_cus * std::max(per_cu, 1u));
     if ((rc = ctx_begin_kernel(ctx))) return rc;
 #define AUKIT_FAST_CASE(S)                                                                                   \
@@ -305,11 +303,9 @@ bool fast_try(aukit_ctx *ctx, int src_kind, int interp, double old_rate, double 
         if (taken) *rc = r2;
         return taken;
     }
-    if (!getenv("AUKIT_FAST_V1")) {  // wave-private pipelined kernel (fast2.hip); v1 kept for A/B and odd ratios
-        bool taken = false;
-        int r2 = launch_fast_wave(ctx, src_kind, interp, segs, P, F, algorithmic_bytes, &taken);
-        if (taken) { *rc = r2; return true; }
-    }
+    bool taken = false;  // wave-private pipelined kernel (fast2.hip); v1 for the ratios it declines
+    int r2 = launch_fast_wave(ctx, src_kind, interp, segs, P, F, algorithmic_bytes, &taken);
+    if (taken) { *rc = r2; return true; }
     *rc = launch_fast(ctx, src_kind, interp, segs, P, F, algorithmic_bytes);
     return true;
 }

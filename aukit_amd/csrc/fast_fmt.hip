@@ -362,7 +362,7 @@ bool fast_eligible(int src_kind, int interp, double old_rate, double new_rate, F
 bool fast_fmt_try(aukit_ctx *ctx, const aukit_codec_desc *d, int interp, double new_rate, const std::vector<Seg> &segs, ResampleParams &P,
                   uint64_t algorithmic_bytes, int *rc, const int **only_if, int epi, double alpha) {
     *only_if = nullptr;
-    if (ctx->exact_math > 1 || getenv("AUKIT_NO_FAST_FMT")) return false;
+    if (ctx->exact_math > 1) return false;
     const bool f64 = ctx->exact_math == 1;   // fp64 arithmetic, f32 store
     if (epi && f64) return false;            // the stream epilogue exists in f32 arithmetic only
     if (epi == 2 && d->channels != 2) return false;
@@ -422,7 +422,6 @@ bool fast_fmt_try(aukit_ctx *ctx, const aukit_codec_desc *d, int interp, double 
     *rc = AUKIT_OK;
     if (P.n_tiles == 0) return true;
     unsigned per_cu = 64;   // measured 4 / 8 / 16 / 32 / 64 on 1024 ten-second streams: float mono 497 / 549 / 555 / 569 / 600 G out-samples/s, 24-bit stereo 629 / 651 / 660 / 649 / 667
-    if (const char *e = getenv("AUKIT_FMT_PER_CU")) { const int v = atoi(e); if (v >= 1) per_cu = (unsigned)v; }   // tuning knob
     const unsigned grid = std::min<unsigned>((P.n_tiles + 3) / 4, (unsigned)ctx->num_cus * per_cu);
     if ((*rc = ctx_begin_kernel(ctx))) return true;
     if (M.flag && hipMemsetAsync(M.flag, 0, 4, ctx->stream) != hipSuccess) { *rc = fail(AUKIT_E_HIP, "hipMemsetAsync failed"); return true; }

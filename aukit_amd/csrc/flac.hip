@@ -20,7 +20,6 @@
 // Rows are int32 when the bit depth is ≤ 24 and no value overflows (checked everywhere; a flagged batch is redone with
 // double rows and the Lua's own floating-point prediction, so even absurd values round the way the reference rounds them).  The division by 2^depth (:505) happens in the consumer.
 #include <algorithm>
-#include <chrono>
 #include <type_traits>
 #include "resample.h"
 #include "stream_tail.h"
@@ -812,7 +811,7 @@ __global__ __launch_bounds__(64) void k_flac_chain(const FlacGlobals G, unsigned
                 ci[k].sample_off = sp;
                 ci[k].seq = nf;
                 ci[k].used = 1;
-                if (!sd) {}   // (the fused decoder, flac_fused.hip: no prediction jobs to count)
+                if (!sd) {}   // (the fused decoder: no prediction jobs to count)
                 else if (C == 2) kc[4 * max(sd[(size_t)k * 2].kind & 3, sd[(size_t)k * 2 + 1].kind & 3) + (f.chan_asgn >= 8 ? f.chan_asgn - 7 : 0)] += 2;  // a stereo frame's two jobs share a wave (k_flac_jobs)
                 else for (int c = 0; c < f.nsub; c++) kc[4 * (sd[(size_t)k * C + c].kind & 3)]++;
                 if (nf == 0) bs0 = f.blocksize;
@@ -1347,7 +1346,7 @@ struct FlacDecoded {
     std::vector<uint64_t> fbase;
     std::vector<unsigned> nframes;
     uint64_t nfr = 0;
-    // the fused decoder (flac_fused.hip) leaves every frame's final integers where it decoded them — ctx->tmp_buf3, at FrameRec::scratch — and
+    // the fused decoder (k_flac_stream / k_flac_pq) leaves every frame's final integers where it decoded them — ctx->tmp_buf3, at FrameRec::scratch — and
     // the consumers that can follow the frame records read them there (the loader's conversion, the deferred resample + one-pole pass,
     // stream.flac's tail jobs); flac_rows_materialize() gathers contiguous rows into ctx->tmp_buf for the others
     bool in_scratch = false;
@@ -1448,17 +1447,6 @@ static int flac_run(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &D, bool 
             AUKIT_HIP_CHECK(hipMemcpyAsync(&hc, d_cnt, sizeof hc, hipMemcpyDeviceToHost, ctx->stream));
             AUKIT_HIP_CHECK(hipMemcpyAsync(chain.data(), d_chain, (size_t)n * sizeof(ChainOut), hipMemcpyDeviceToHost, ctx->stream));
             AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            if (getenv("AUKIT_FLAC_STATS"))
-                fprintf(stderr, "[flac stats] rounds %llu outer %llu turns %llu values|singles %llu lane_turns %llu live|single_turns %llu\n", hc.stats[0], hc.stats[1], hc.stats[2], hc.stats[3], hc.stats[4], hc.stats[5]);
-            if (getenv("AUKIT_FLAC_DEBUG")) {
-                std::vector<CandInfo> hci(ncand);
-                (void)hipMemcpy(hci.data(), d_ci, ncand * sizeof(CandInfo), hipMemcpyDeviceToHost);
-                fprintf(stderr, "[flac] pass %d ncand %u cursor %llu scap %llu flags %u\n", pass, ncand, (u64)hc.scratch_cursor, (u64)scap, hc.flags);
-                for (unsigned k = 0; k < ncand && k < 16; k++)
-                    fprintf(stderr, "  cand %u end %llu bs %d asgn %d status %d nsub %d used %u seq %u\n", k, hci[k].end_byte, hci[k].blocksize, hci[k].chan_asgn, hci[k].status, hci[k].nsub, hci[k].used, hci[k].seq);
-                for (uint32_t s = 0; s < n && s < 4; s++)
-                    fprintf(stderr, "  chain %u L %llu nfr %u status %d miss %d at %llu ci %u\n", s, chain[s].L, chain[s].nframes, chain[s].status, chain[s].miss_kind, chain[s].miss_at, chain[s].miss_ci);
-            }
             if (hc.scratch_cursor > scap) {  // some frames had no room for their values: grow and extract everything again
                 scap = hc.scratch_cursor + hc.scratch_cursor / 16 + 65536;
                 pass = -1;
@@ -1582,13 +1570,13 @@ __global__ __launch_bounds__(256) void k_flac_frames_brief(const FrameRec *frame
     if (i < nfr) out[i] = make_uint2((unsigned)frames[i].bs, frames[i].end_rel);
 }
 
-// The fused decoder (flac_fused.hip): find → k_flac_decode (final integers into the scratch) → chain → k_flac_gather (scratch → rows).
-// Returns AUKIT_OK, an error, or 2 = "the chain needs a frame k_flac_decode declined": the caller runs the first design (flac_run).
+// The fused decoder: find → k_flac_stream / k_flac_pq (final integers into the scratch) → chain → k_flac_gather (scratch → rows).
+// Returns AUKIT_OK, an error, or 2 = "the chain needs a frame the decoder declined": the caller runs the first design (flac_run).
 static int flac_run_fused(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &D, bool want_frames) {
     const uint32_t n = in->n;
     const int C = D.channels;
     int rc;
-    const bool o16 = D.want16 && D.depth <= 16 && !getenv("AUKIT_FLAC_NO_I16");   // finals as int16 (flac_fused.hip, O16)
+    const bool o16 = D.want16 && D.depth <= 16;   // finals as int16 (FusedArgs::out16)
     const uintptr_t dptr = reinterpret_cast<uintptr_t>(in->data());
     FlacGlobals G;
     G.src = in->data();
@@ -1637,21 +1625,19 @@ static int flac_run_fused(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &D,
         AUKIT_HIP_CHECK(hipGetLastError());
         Counters hc;
         AUKIT_HIP_CHECK(hipMemcpyAsync(&hc, d_cnt, sizeof hc, hipMemcpyDeviceToHost, pre));
-        if (D.set) AUKIT_HIP_CHECK(hipEventRecord(ctx->pre_ev, pre));
         AUKIT_HIP_CHECK(hipStreamSynchronize(pre));
         if (hc.ncand > cand_room) { capc = hc.ncand + hc.ncand / 8 + n + 4096; continue; }
-        // Round 6, late: the decoder and the chain walk stay on the look-ahead stream too (AUKIT_FLAC_DECODE_AHEAD=0: behind the search on ctx->stream as
-        // before).  The call before's last passes — its normalize: HBM-bound, no LDS — then run BESIDE this call's decoder (VALU-bound, the CU's whole LDS)
+        // Round 6, late: the decoder and the chain walk stay on the look-ahead stream too.  The call before's last passes — its normalize: HBM-bound, no LDS — then run BESIDE this call's decoder (VALU-bound, the CU's whole LDS)
         // instead of in front of it.  The frame scratch is the one buffer both streams touch: the decoder waits for its last reader (scratch_ev: the tile
         // chain of the call before), or for all of ctx->stream when nothing tracked the readers or a user other than this loader touched it (ctx_scratch3).  Every nested launch goes where ctx->stream points: it
         // points at the look-ahead stream until the chain has converged.
-        const bool dahead = D.set && !(getenv("AUKIT_FLAC_DECODE_AHEAD") && atoi(getenv("AUKIT_FLAC_DECODE_AHEAD")) == 0);
+        const bool dahead = D.set != nullptr;
         struct StreamSwap { aukit_ctx *c; hipStream_t saved; bool on; void back() { if (on) { c->stream = saved; on = false; } } ~StreamSwap() { back(); } } sw{ctx, ctx->stream, false};
         if (dahead) {
             if (ctx->scratch_dirty && D.entry) AUKIT_HIP_CHECK(hipStreamWaitEvent(pre, D.entry, 0));
             else if (ctx->scratch_ev_set) AUKIT_HIP_CHECK(hipStreamWaitEvent(pre, ctx->scratch_ev, 0));
             ctx->stream = pre; sw.on = true;
-        } else if (D.set) AUKIT_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->pre_ev, 0));   // the decoder (ctx->stream) behind the search
+        }
         unsigned ncand = (unsigned)hc.ncand;
         auto decode = [&](unsigned first, unsigned count, int limit_factor) -> int {
             FusedArgs A;
@@ -1659,12 +1645,10 @@ static int flac_run_fused(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &D,
             A.scratch = reinterpret_cast<int *>(ctx->tmp_buf3.p); A.scratch_cap = scap; A.scratch_cursor = &d_cnt->scratch_cursor; A.flags = &d_cnt->flags;
             A.limit_factor = limit_factor; A.ticket = &d_cnt->ticket; A.stats = d_cnt->stats;
             A.out16 = o16 ? 1 : 0;
-            A.dbg = getenv("AUKIT_FLAC_FUSED_DBG") ? atoi(getenv("AUKIT_FLAC_FUSED_DBG")) : 0;
+            A.dbg = 0;   // always 0 from the host: k_flac_stream still reads the field
             // k_flac_stream (a wave per 64 frames) when the batch fills the chip; k_flac_pq (a parser and a predictor wave per 64 frames: the lane's chain
-            // cut in two) when it does not — fewer frames than three of its workgroups per CU hold at once.  AUKIT_FLAC_DECODER = stream | pq | fused for the A/B
-            // (fused: k_flac_decode, flac_fused.hip, round 4)
+            // cut in two) when it does not — fewer frames than three of its workgroups per CU hold at once.  AUKIT_FLAC_DECODER = stream | pq for the A/B
             const char *which = getenv("AUKIT_FLAC_DECODER");
-            if (which && !strcmp(which, "fused")) return flac_fused_launch(ctx, A);
             const bool pq = which ? !strcmp(which, "pq") : (uint64_t)A.count <= (uint64_t)ctx->num_cus * 3ull * 64ull;
             return pq ? flac_pq_launch(ctx, A) : flac_stream_launch(ctx, A);
         };
@@ -1676,28 +1660,14 @@ static int flac_run_fused(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &D,
                 AUKIT_HIP_CHECK(hipMemsetAsync(&d_cnt->scratch_cursor, 0, 8, ctx->stream));
                 if ((rc = ctx_begin_kernel(ctx))) return rc;
                 if ((rc = decode(0, ncand, 5))) return rc;
-                if ((rc = ctx_end_kernel(ctx, "k_flac_decode", in->total() + guess * 4))) return rc;
+                if ((rc = ctx_end_kernel(ctx, "k_flac_decode", in->total() + guess * 4))) return rc;   // (the label aukit_ctx_last_kernel has always reported for this stage, kept on purpose: k_flac_stream or k_flac_pq ran)
             }
-            if (getenv("AUKIT_FLAC_CHAIN_OLD")) hipLaunchKernelGGL(k_flac_chain, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, G, n, H, d_ci, (const SubDesc *)nullptr, C, d_chain, d_cnt->kind_count);
-            else {
-                hipLaunchKernelGGL(k_flac_links, dim3((ncand + 255) / 256), dim3(256), 0, ctx->stream, G, d_cand, d_ci, ncand, H, d_links);
-                hipLaunchKernelGGL(k_flac_chain_links, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, G, n, H, d_ci, d_links, d_chain);
-            }
+            hipLaunchKernelGGL(k_flac_links, dim3((ncand + 255) / 256), dim3(256), 0, ctx->stream, G, d_cand, d_ci, ncand, H, d_links);
+            hipLaunchKernelGGL(k_flac_chain_links, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, G, n, H, d_ci, d_links, d_chain);
             AUKIT_HIP_CHECK(hipGetLastError());
             AUKIT_HIP_CHECK(hipMemcpyAsync(&hc, d_cnt, sizeof hc, hipMemcpyDeviceToHost, ctx->stream));
             AUKIT_HIP_CHECK(hipMemcpyAsync(chain.data(), d_chain, (size_t)n * sizeof(ChainOut), hipMemcpyDeviceToHost, ctx->stream));
             AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            if (getenv("AUKIT_FLAC_STATS"))
-                fprintf(stderr, "[flac stats] rounds %llu outer %llu turns %llu values|singles %llu lane_turns %llu live|single_turns %llu\n", hc.stats[0], hc.stats[1], hc.stats[2], hc.stats[3], hc.stats[4], hc.stats[5]);
-            if (getenv("AUKIT_FLAC_DEBUG")) {
-                std::vector<CandInfo> hci(ncand);
-                (void)hipMemcpy(hci.data(), d_ci, ncand * sizeof(CandInfo), hipMemcpyDeviceToHost);
-                fprintf(stderr, "[flac fused] pass %d ncand %u cursor %llu scap %llu\n", pass, ncand, (u64)hc.scratch_cursor, (u64)scap);
-                for (unsigned k = 0; k < ncand && k < 16; k++)
-                    fprintf(stderr, "  cand %u end %llu bs %d asgn %d status %d nsub %d used %u seq %u\n", k, hci[k].end_byte, hci[k].blocksize, hci[k].chan_asgn, hci[k].status, hci[k].nsub, hci[k].used, hci[k].seq);
-                for (uint32_t s = 0; s < n && s < 4; s++)
-                    fprintf(stderr, "  chain %u L %llu nfr %u status %d miss %d at %llu ci %u\n", s, chain[s].L, chain[s].nframes, chain[s].status, chain[s].miss_kind, chain[s].miss_at, chain[s].miss_ci);
-            }
             if (hc.scratch_cursor > scap) { scap = hc.scratch_cursor + hc.scratch_cursor / 16 + 65536; pass = -1; continue; }
             std::vector<Cand> extra;
             std::vector<unsigned> redo;
@@ -1812,7 +1782,6 @@ static int flac_decode_rows(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &
     // there and 11.5 with everything on ctx->stream, one box)
     bool ahead = true;
     if (const char *e = getenv("AUKIT_FLAC_LOOKAHEAD")) ahead = atoi(e) != 0;
-    if (getenv("AUKIT_FLAC_NO_LOOKAHEAD")) ahead = false;
     if (ahead) {
         if ((rc = ctx_pre_stream(ctx, &pre))) return rc;
         if (in->ready) AUKIT_HIP_CHECK(hipStreamWaitEvent(pre, in->ready, 0));
@@ -1850,13 +1819,11 @@ static int flac_decode_rows(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &
         else if (D.info[s].channels != D.channels || D.info[s].depth != D.depth || D.info[s].rate != D.rate)
             return fail(AUKIT_E_ARG, "all FLAC streams of a batch must share channel count, bit depth and sample rate");
     }
-    const bool no_fused = getenv("AUKIT_FLAC_NO_FUSED") != nullptr;   // A/B and the tests: the first design for every batch
-    if (D.depth <= 24 && !g_flac_force_wide() && !no_fused && !getenv("AUKIT_FLAC_SLOW_RESTORE")) {
+    if (D.depth <= 24 && !g_flac_force_wide() && !getenv("AUKIT_FLAC_SLOW_RESTORE")) {
         rc = flac_run_fused(ctx, in, D, want_frames);
         if (rc == 3) { D.want16 = false; rc = flac_run_fused(ctx, in, D, want_frames); }
         ctx->counters[AUKIT_COUNTER_FLAC_FUSED] = rc == AUKIT_OK ? 1 : 0;
         if (rc != 2) return rc;
-        if (getenv("AUKIT_FLAC_DEBUG")) fprintf(stderr, "[flac] the fused decoder declined a frame of the chain: two-kernel decoder\n");
     } else ctx->counters[AUKIT_COUNTER_FLAC_FUSED] = 0;
     if (D.depth <= 24 && !g_flac_force_wide()) {
         rc = flac_run<int>(ctx, in, D, want_frames);
@@ -2083,12 +2050,8 @@ int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *,
     if (interp < 0 || interp > 3) return fail(AUKIT_E_ARG, "stream.flac: bad interpolation");   // (sinc: the reference-order kernels below — aukit.defaultInterpolation = "sinc" is legal at :3156)
     if (dtype != AUKIT_F64 && dtype != AUKIT_F32) return fail(AUKIT_E_ARG, "stream.flac output must be AUKIT_F64 or AUKIT_F32");
     FlacDecoded D;
-    static const bool TT = getenv("AUKIT_HOST_TIMING") != nullptr;
-    auto T0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char *w) { if (TT) { auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[stream.flac host] %-12s %8.1f us\n", w, std::chrono::duration<double, std::micro>(t - T0).count()); T0 = t; } };
     int rc = flac_decode_rows(ctx, in, D, true);
     if (rc) return rc;
-    lap("decode rows");
     const int C = D.channels;
     const double ratio = 48000 / D.rate;                                      // :3154
     const double lp_alpha = 1 - std::exp(-(D.rate / 96000) * 2 * M_PI);       // :3155
@@ -2110,7 +2073,6 @@ int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *,
         lens[s] = l;
         sum_nout += l * (uint64_t)C; njobs += (uint64_t)C * nf;
     }
-    lap("lens");
     // the chunk table (which frames an iterator call returns) is host work nothing on the device waits for: it is built AFTER the tail kernel has been
     // launched (round 4: 0.3 ms of an 8.2 ms call on 1024 streams during which the GPU stood idle)
     auto build_chunks = [&]() {
@@ -2158,7 +2120,6 @@ int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *,
     aukit_audio *a = *out;
     if ((rc = audio_prepare(ctx, &a, in->n, C, 48000, dtype, lens.data()))) { delete ck; return rc; }
     *out = a;
-    lap("audio_prepare");
     {   // round 3: jobs written on the device from the decoder's frame records, one launch from the decoded rows (k_iir_tail, stream_tail.hip)
         const int rk = D.wide ? TAIL_ROWS_F64 : TAIL_ROWS_I32;
         const double fullv = std::ldexp(1.0, D.depth);
@@ -2170,26 +2131,21 @@ int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *,
             hipLaunchKernelGGL(k_flac_tail_jobs, dim3((in->n + 63) / 64), dim3(64), 0, ctx->stream, D.d_frames, D.d_fbase, dnf, D.d_rowoff, reinterpret_cast<const u64 *>(a->d_meta), in->n, C,
                                ratio, dj, D.in_scratch ? 1 : 0);
             if (hipGetLastError() != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "k_flac_tail_jobs launch failed"); }
-            lap("plan + jobs");
             int trc = AUKIT_OK;
             if (rk == TAIL_ROWS_I32 && dtype == AUKIT_F32 &&
                 rs_onepole_jobs_try_dev(ctx, D.in_scratch ? ctx->tmp_buf3.p : ctx->tmp_buf.p, fullv, dj, njobs, D.rate, interp, lp_alpha, reinterpret_cast<float *>(a->dev),
                                         in->total() + sum_nout * dtype_size(dtype), "k_rs_onepole<flac>", &trc)) {   // the tile chain of flac_tail.hip (state carried from tile to tile, a workgroup takes frame after frame)
                 if (trc) { delete ck; return trc; }
-                lap("tail launch");
                 if (brief) frames_from_brief(D);
                 build_chunks();
-                lap("chunk table");
                 if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
                 return AUKIT_OK;
             }
             if (iir_tail_try_dev(ctx, TAIL_FLAC, rk, D.in_scratch ? ctx->tmp_buf3.p : ctx->tmp_buf.p, fullv, dj, njobs, max_nout, sum_nout, 1, D.rate, interp, dtype, a->dev, in->total() + sum_nout * dtype_size(dtype),
                                  "k_iir_tail<flac>", &trc)) {
                 if (trc) { delete ck; return trc; }
-                lap("tail launch");
                 if (brief) frames_from_brief(D);
                 build_chunks();
-                lap("chunk table");
                 if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
                 return AUKIT_OK;
             }
@@ -2233,7 +2189,7 @@ int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *,
         uint64_t scr_elems = 0, max_nout = 0;
         std::vector<uint64_t> scr_off(jobs.size());
         for (size_t k = 0; k < jobs.size(); k++) { scr_off[k] = scr_elems; scr_elems += ((uint64_t)jobs[k].nout + 1) & ~1ull; max_nout = std::max<uint64_t>(max_nout, (uint64_t)jobs[k].nout); }
-        if (scr_elems * 8 <= (48ull << 30) && max_nout && !getenv("AUKIT_FLAC_STREAM_ONE_PASS")) {  // two passes
+        if (scr_elems * 8 <= (48ull << 30) && max_nout) {  // two passes
             DevBuf &S3 = ctx_scratch3(ctx);
             if ((rc = S3.ensure((size_t)scr_elems * 8 + 64))) { delete ck; return rc; }
             if ((rc = upload_table(ctx, ctx->misc_buf, scr_off.data(), scr_off.size() * 8))) { delete ck; return rc; }

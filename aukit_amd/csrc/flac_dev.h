@@ -1,4 +1,4 @@
-// flac_dev.h — what the two FLAC decoders (flac.hip: extract → chain → restore; flac_fused.hip: decode → chain → gather) share: stream / candidate /
+// flac_dev.h — what the two FLAC decoders (flac.hip: extract → chain → restore; flac_stream.hip / flac_pq.hip: decode → chain → gather) share: stream / candidate /
 // frame records, the byte-position hash table, the error codes of decodeFrame (aukit.lua:510-567).
 #pragma once
 #include "resample.h"
@@ -10,7 +10,7 @@ typedef unsigned long long u64;
 enum FlacErr { FE_OK = 0, FE_EOF_START = 1 /* readByte() == nil at a frame start: clean end */, FE_NIL = 2, FE_SYNC = 3, FE_BLOCKSIZE = 4,
                FE_CHAN = 5, FE_SUBTYPE = 6, FE_RESMETHOD = 7, FE_PARTITION = 8,
                FE_LIMIT = 9 /* the candidate ran past its bit budget; extracted again without a budget if the chain needs it */,
-               FE_DECLINE = 10 /* k_flac_decode (flac_fused.hip) does not serve this frame's shape: the batch goes through k_flac_extract + k_flac_restore */ };
+               FE_DECLINE = 10 /* the fused decoder (k_flac_stream / k_flac_pq) does not serve this frame's shape: the batch goes through k_flac_extract + k_flac_restore */ };
 static const char *flac_err_msg(int e) {
     switch (e) {
     case FE_NIL: return "attempt to perform arithmetic on a nil value";
@@ -67,15 +67,15 @@ struct CandInfo {
 struct SubDesc { int order, lshift, wasted, kind; short coef[32]; };  // kind: 0 = no prediction, 1/2/3 = order <= 4/12/32
 struct ChainOut { u64 L, miss_at; unsigned nframes; int status; int miss_kind; unsigned miss_ci; int bs0, uniform; };   // bs0: the first frame's block size; uniform: every frame but the last has it, the last is no longer  // miss_kind: 1 = no candidate at miss_at, 2 = candidate miss_ci hit its bit budget
 struct SubJob { u64 src, dst; unsigned desc; int bs; int asgn, pad; };  // asgn: the frame's channel assignment when it decorrelates (8..10), else 0
-struct FrameRec { u64 sample_off; u64 scratch; int bs, chan_asgn; unsigned stream, end_rel; };   // end_rel: the byte behind the frame, relative to its stream's start (streams below 4 GiB; 0: not recorded)   // scratch: where k_flac_decode left the frame's final values (channel c at + c * bs); 0 for the first design
+struct FrameRec { u64 sample_off; u64 scratch; int bs, chan_asgn; unsigned stream, end_rel; };   // end_rel: the byte behind the frame, relative to its stream's start (streams below 4 GiB; 0: not recorded)   // scratch: where k_flac_stream / k_flac_pq left the frame's final values (channel c at + c * bs); 0 for the first design
 struct Carve {
     size_t at = 0;
     size_t take(size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; }
 };
-struct Counters { u64 ncand, scratch_cursor, kind_count[16], kind_fill[16]; unsigned flags, ticket; u64 stats[8]; };   // stats: -DAUKIT_FLAC_STATS builds of k_flac_decode count their rounds and turns here (tools/r06_flac_stats.sh)
+struct Counters { u64 ncand, scratch_cursor, kind_count[16], kind_fill[16]; unsigned flags, ticket; u64 stats[8]; };   // stats: -DAUKIT_FLAC_STATS builds of k_flac_stream count their rounds and turns here; the host does not read them
 
-// ---- flac_fused.hip: decodeFrame (:510-567) with the prediction (:411-419), the wasted-bits shift (:467-469), the stereo decorrelation and the
-// wrap (:482-507) done by the lane that reads the frame's bits — final integers leave the kernel once (k_flac_decode)
+// ---- the fused decoders (flac_stream.hip, flac_pq.hip): decodeFrame (:510-567) with the prediction (:411-419), the wasted-bits shift (:467-469), the stereo decorrelation and the
+// wrap (:482-507) done by the lane that reads the frame's bits — final integers leave the kernel once
 struct FusedArgs {
     FlacGlobals G;
     const Cand *cands;
@@ -88,16 +88,15 @@ struct FusedArgs {
     unsigned *flags;
     int limit_factor;
     unsigned *ticket;
-    int out16;               // finals as int16 (k_flac_decode<..., O16>; depths <= 16)
+    int out16;               // finals as int16 (k_flac_stream / k_flac_pq <O16>; depths <= 16)
     u64 *stats;              // Counters::stats
-    int dbg;                 // ablation switches (AUKIT_FLAC_FUSED_DBG; wrong results): 1 no prediction, 2 no stores, 4 no read-back of parked values
+    int dbg;                 // always 0 from the host (they were ablation switches with wrong results: 1 no prediction, 2 no stores, 4 no read-back); k_flac_stream still reads it
 };
-int flac_fused_launch(aukit_ctx *ctx, const FusedArgs &A);
-// flac_stream.hip (round 6): the same contract, values in registers from the bit stream to the store
+// flac_stream.hip (round 6): values in registers from the bit stream to the store
 int flac_stream_launch(aukit_ctx *ctx, const FusedArgs &A);
 // flac_pq.hip (round 6): the same contract, a parser wave and a predictor wave per 64 frames — small batches
 int flac_pq_launch(aukit_ctx *ctx, const FusedArgs &A);
-// the chained frames' records in stream order (one lane per candidate)
+// flac_gather.hip: the chained frames' records in stream order (one lane per candidate)
 int flac_frames_launch(aukit_ctx *ctx, const Cand *cands, const CandInfo *ci, unsigned ncand, const u64 *frame_base, FrameRec *frames, const u64 *stream_off);
 // chained frames: scratch → contiguous int32 rows (one workgroup per frame record)
 int flac_gather_launch(aukit_ctx *ctx, const FrameRec *frames, u64 nfr, int C, const u64 *row_off, const int *scratch, int *rows, bool scratch16 = false);   // scratch16: the frames hold int16 finals (FusedArgs::out16)

@@ -9,7 +9,7 @@
 //     (:482-497), wraps (:501-507), packs, and flushes the output rows exactly as k_flac_stream does.
 // Two buffers (rows, parameter blocks, counts), one workgroup barrier per round: P fills buffer r while Q works on buffer r - 1.  What Q finds
 // beyond its ranges (the multiply-add bound of a subframe, an int16 final) it says in s_bad / its own flag; a frame is reported two rounds behind
-// its last value, when Q has seen everything of it.  Same arguments, same outputs as k_flac_stream and k_flac_decode; the host takes this
+// its last value, when Q has seen everything of it.  Same arguments, same outputs as k_flac_stream; the host takes this
 // kernel when the batch has fewer frames than three workgroups per CU hold at once (flac_pq_launch: its 53 KB of LDS per workgroup and the
 // second wave cost a full chip 1.5 x what they win a small batch).
 #include "flac_stream_dev.h"

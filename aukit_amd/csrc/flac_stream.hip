@@ -1,7 +1,7 @@
 // flac_stream.hip — FLAC frames decoded to FINAL integers in the registers of the lane that reads their bits (round 6).
 //
-// k_flac_decode (flac_fused.hip, round 4) works in rounds of 32 values: parse them into the lane's LDS row, predict over the row, flush the row
-// through a cooperative store phase.  Its census (tools/r06_flac_stats.sh, profiles/r06_flac_phase.txt) says the hot loop is ideal — 28.2 M wave
+// Its predecessor (round 4's k_flac_decode, since removed) worked in rounds of 32 values: parse them into the lane's LDS row, predict over the row, flush the row
+// through a cooperative store phase.  Its census (profiles/r06_flac_phase.txt) said the hot loop was ideal — 28.2 M wave
 // turns for 1.806 G values, 64 lanes each — and that two thirds of its 99 VALU instructions per value are NOT in that loop: the cooperative
 // window slide (three passes of shuffles and 64-bit line arithmetic: ≈ 400 per round), the row's way through LDS (write, read, write, read), the
 // flush's per-row metadata, the prefetch registers of both (80 VGPRs: two waves per SIMD).
@@ -21,9 +21,9 @@
 //   * everything that is not such a group — frame / subframe / partition headers, warm-up samples, the one to three values that align a run to
 //     a multiple of four, codes longer than 32 bits, the last bytes of a stream, CONSTANT subframes — is generic single-value code (64-bit
 //     sums, every check), entered a few times per subframe.
-// What the kernel does not serve it DECLINES (FE_DECLINE), exactly as k_flac_decode does: predictor orders above 12, values beyond the ranges
-// checked below, the :400 quirk, sample depths of a subframe outside 1..31.  Outputs (CandInfo, the scratch layout) are k_flac_decode's: nothing
-// downstream knows which of the two ran (AUKIT_FLAC_DECODER=fused brings the round-4 kernel back for the A/B).
+// What the kernel does not serve it DECLINES (FE_DECLINE): predictor orders above 12, values beyond the ranges
+// checked below, the :400 quirk, sample depths of a subframe outside 1..31.  Outputs (CandInfo, the scratch layout) are the same as k_flac_pq's: nothing
+// downstream knows which of the two ran (AUKIT_FLAC_DECODER = stream | pq forces one).
 #include "flac_stream_dev.h"
 
 namespace aukit {
@@ -699,8 +699,8 @@ __global__ __launch_bounds__(64, AUKIT_FS_LB) void k_flac_stream(const FusedArgs
 int flac_stream_launch(aukit_ctx *ctx, const FusedArgs &A) {
     if (!A.count) return AUKIT_OK;
     AUKIT_HIP_CHECK(hipMemsetAsync(A.ticket, 0, 4, ctx->stream));
-    static const int wgs = getenv("AUKIT_FLAC_STREAM_WGS") ? atoi(getenv("AUKIT_FLAC_STREAM_WGS")) : 4 * AUKIT_FS_LB;   // waves per CU (three per SIMD)
-    const unsigned grid = std::min<unsigned>((A.count + 63) / 64, (unsigned)ctx->num_cus * (unsigned)std::max(wgs, 1));
+    const unsigned wgs = 4 * AUKIT_FS_LB;   // waves per CU (three per SIMD)
+    const unsigned grid = std::min<unsigned>((A.count + 63) / 64, (unsigned)ctx->num_cus * wgs);
     if (A.out16) hipLaunchKernelGGL((k_flac_stream<true>), dim3(grid), dim3(64), 0, ctx->stream, A);
     else hipLaunchKernelGGL((k_flac_stream<false>), dim3(grid), dim3(64), 0, ctx->stream, A);
     AUKIT_HIP_CHECK(hipGetLastError());

@@ -75,7 +75,7 @@ AUKIT_DEV int srd_rice(SRd &b, int k, int &v) {
     return FE_OK;
 }
 
-// the finals' stores.  Non-temporal by default as in k_flac_decode; -DAUKIT_FS_PLAIN: ordinary (cached, write-back) stores
+// the finals' stores.  Non-temporal by default; -DAUKIT_FS_PLAIN: ordinary (cached, write-back) stores
 template <typename V>
 __device__ __forceinline__ void sstore(V v, V *p) {
 #ifdef AUKIT_FS_PLAIN

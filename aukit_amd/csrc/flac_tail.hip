@@ -611,7 +611,7 @@ bool lazy_onepole_try(aukit_ctx *ctx, aukit_audio *a, double coef, bool highpass
     constexpr int T = 512;
     if (((double)F.b + (double)T * (double)F.a) * (double)F.b >= 4294967296.0) return false;   // exact (q, rem) inside a tile
     const int cap = std::max(512, ((int)(((unsigned long long)T * F.a) / F.b) + 16 + 3) & ~3) + 32;   // (+ 32: the slack around the window that whole vectors may spill into)
-    const bool tabw = a->lazy_interp == AUKIT_INTERP_CUBIC && F.b <= 512 && !getenv("AUKIT_RS_HORNER");
+    const bool tabw = a->lazy_interp == AUKIT_INTERP_CUBIC && F.b <= 512;
     const int NWh = mono_out ? 2 : 1;
     const size_t wave_lds = (size_t)cap + T + T / 8 + 8;
     const size_t lds = ((size_t)NWh * wave_lds + (tabw ? ((4 * (size_t)F.b + 3) & ~(size_t)3) : 0) + (mono_out ? (size_t)NWh * (T + T / 8 + 8) : 0)) * 4;
@@ -662,21 +662,21 @@ bool lazy_onepole_try(aukit_ctx *ctx, aukit_audio *a, double coef, bool highpass
         uint64_t min_tiles = ~0ull;
         for (uint64_t l : a->len) min_tiles = std::min<uint64_t>(min_tiles, (l + T - 1) / T);
         int warm = 0, segs = 1;
-        if (m > 0 && m < 1 && !getenv("AUKIT_RS_ONE_CHAIN")) {
+        if (m > 0 && m < 1) {
             warm = (int)std::ceil(40.0 * M_LN2 / -std::log(m) / T);
             const uint64_t by_rows = std::max<uint64_t>(1, 4096 / std::max<size_t>(rows, 1))   /* (what the chip holds at once: more runs than that only add warm-up) */, by_len = min_tiles / (8ull * (uint64_t)std::max(warm, 1));
             segs = (int)std::max<uint64_t>(1, std::min<uint64_t>(std::min(by_rows, by_len), 16));
         }
         if (getenv("AUKIT_RS_SEGS")) segs = std::max(1, atoi(getenv("AUKIT_RS_SEGS")));
         P.segs = segs; P.warm = segs > 1 ? warm : 0;
-        P.novec = getenv("AUKIT_RS_NOVEC") ? 1 : 0;
+        P.novec = 0;
         if (hipMemsetAsync(a->d_rowmax, 0, rows * 8, ctx->stream) != hipSuccess) { *rc = fail(AUKIT_E_HIP, "hipMemsetAsync failed"); return true; }
         if (mono_out && hipMemsetAsync(mono_out->d_rowmax, 0, (size_t)a->n * 8, ctx->stream) != hipSuccess) { *rc = fail(AUKIT_E_HIP, "hipMemsetAsync failed"); return true; }
     }
     if ((*rc = ctx_begin_kernel(ctx))) return true;
     const size_t ldsb = lds;
  const dim3 grid((unsigned)((rows / (size_t)NWh) * (size_t)P.segs));
-    const bool r32 = !highpass && (1.0 - coef) <= 0.5 && (1.0 - coef) >= 0 && !getenv("AUKIT_RS_F64");   // the recurrence in f32 (k_rs_onepole<..., R32>)
+    const bool r32 = !highpass && (1.0 - coef) <= 0.5 && (1.0 - coef) >= 0;   // the recurrence in f32 (k_rs_onepole<..., R32>)
     ctx->counters[AUKIT_COUNTER_RECURRENCE_F32] = r32 ? 1 : 0;
 #define AUKIT_RSO1(I, H, Tb, S)                                                                                                                            \
     do {                                                                                                                                                     \
@@ -737,7 +737,7 @@ static bool rs_onepole_jobs_launch(aukit_ctx *ctx, const void *rows, bool rows_i
     if (((double)F.b + (double)T * (double)F.a) * (double)F.b >= 4294967296.0) return false;
     if (!(lp_alpha > 0 && lp_alpha < 1)) return false;
     const int cap = std::max(512, ((int)(((unsigned long long)T * F.a) / F.b) + 16 + 3) & ~3) + 32;
-    const bool tabw = interp == AUKIT_INTERP_CUBIC && F.b <= 512 && !getenv("AUKIT_RS_HORNER");
+    const bool tabw = interp == AUKIT_INTERP_CUBIC && F.b <= 512;
     const int NWh = mix_channels;
     const size_t wave_lds = (size_t)cap + T + T / 8 + 8;
     const size_t lds = ((size_t)NWh * wave_lds + (tabw ? ((4 * (size_t)F.b + 3) & ~(size_t)3) : 0) + (NWh > 1 ? (size_t)NWh * (T + T / 8 + 8) : 0)) * 4;
@@ -753,7 +753,7 @@ static bool rs_onepole_jobs_launch(aukit_ctx *ctx, const void *rows, bool rows_i
     P.dq256 = (unsigned)((64ull * F.a) / F.b); P.dr256 = (unsigned)((64ull * F.a) % F.b);
     P.scale = P.scale_neg = rows_i32 ? (float)(1.0 / full) : 1.0f;
     P.coef = lp_alpha;
-    P.segs = 1; P.warm = 0; P.novec = getenv("AUKIT_RS_NOVEC") ? 1 : 0; P.fr_mul = 1;
+    P.segs = 1; P.warm = 0; P.novec = 0; P.fr_mul = 1;
     P.wave_lds = (int)wave_lds;
     P.epi = epi;
     P.clo = epi ? -3.0e38f : -128.0f; P.chi = epi ? 3.0e38f : 127.0f;   // (stream.flac does not clamp the interpolated sample, :3177-3178)
@@ -771,7 +771,7 @@ static bool rs_onepole_jobs_launch(aukit_ctx *ctx, const void *rows, bool rows_i
     // long jobs (an iterator call of stream.qoa: ~ 100 tiles): a workgroup each — measured 6.8 ms against 7.6 for workgroups that take five in turn;
     // short ones (a FLAC frame: nine tiles): a workgroup takes several in turn and pays the set-up in front of its tile loop once
     const dim3 grid((unsigned)((long_jobs || NWh > 1) ? njobs : std::min<size_t>(njobs, (size_t)ctx->num_cus * 64)));
-    const bool r32 = (1.0 - lp_alpha) <= 0.5 && (1.0 - lp_alpha) >= 0 && !getenv("AUKIT_RS_F64");   // the recurrence in f32 (k_rs_onepole<..., R32>)
+    const bool r32 = (1.0 - lp_alpha) <= 0.5 && (1.0 - lp_alpha) >= 0;   // the recurrence in f32 (k_rs_onepole<..., R32>)
     ctx->counters[AUKIT_COUNTER_RECURRENCE_F32] = r32 ? 1 : 0;
 #define AUKIT_RSJ(I, Tb, S)                                                                                                                           \
     do {                                                                                                                                              \

@@ -838,9 +838,7 @@ __global__ __launch_bounds__(64) void k_ms_wave(const MsWaveParams P) {
 // ----------------------------------------------------------------- host side of the wave kernel
 // bytes of a block per round: 32 for the rows kernels, 16 for the stream kernels (same-box A/B, 1024 × 10 s mono: rows 0.99 / 1.26 / 1.30 ms
 // for 32 / 16 / 64, stream 3.16 / 2.53 / 4.88 ms — the stream kernel is bound by how many waves a CU holds, i.e. by its LDS tables).
-// AUKIT_MS_RB=16|32 overrides both (A/B knob).
-static const int MS_RB_ENV = getenv("AUKIT_MS_RB") ? atoi(getenv("AUKIT_MS_RB")) : 0;
-static const int MS_RB_ROWS = MS_RB_ENV == 16 ? 16 : 32, MS_RB_STREAM = MS_RB_ENV == 32 ? 32 : 16;
+constexpr int MS_RB_ROWS = 32, MS_RB_STREAM = 16;
 
 // fills the coefficient table; false when a product sum could leave 32 bits (|s1 c1 + s2 c2| <= 32768 (|c1| + |c2|))
 static bool ms_fill_coefs(const aukit_codec_desc *d, MsWaveParams &P) {
@@ -909,7 +907,7 @@ int decode_msadpcm_audio(aukit_ctx *ctx, const aukit_batch *in, const aukit_code
     static const bool magic_ok = ms_magic_ok();
     MsWaveParams P{};
     const int C = d->channels;
-    const bool wave = magic_ok && ms_fill_coefs(d, P) && (dtype == AUKIT_F64 || dtype == AUKIT_F32) && !getenv("AUKIT_MS_GENERIC") && (C == 1 || C == 2);
+    const bool wave = magic_ok && ms_fill_coefs(d, P) && (dtype == AUKIT_F64 || dtype == AUKIT_F32) && (C == 1 || C == 2);
     if (wave) {
         MsBlocks B;
         int rc = ms_count_blocks(in, d, B);
@@ -965,8 +963,7 @@ int decode_msadpcm_audio(aukit_ctx *ctx, const aukit_batch *in, const aukit_code
                 else if (mode == MS_ROWS_F32) ms_launch_rows<CC, RBB, MS_ROWS_F32>(P, grid, lds, ctx->stream);          \
                 else ms_launch_rows<CC, RBB, MS_ROWS_I16>(P, grid, lds, ctx->stream);                                   \
             } while (0)
-            if (C == 1) { if (MS_RB_ROWS == 16) AUKIT_MS_ROWS(1, 16); else AUKIT_MS_ROWS(1, 32); }
-            else { if (MS_RB_ROWS == 16) AUKIT_MS_ROWS(2, 16); else AUKIT_MS_ROWS(2, 32); }
+            if (C == 1) AUKIT_MS_ROWS(1, MS_RB_ROWS); else AUKIT_MS_ROWS(2, MS_RB_ROWS);
 #undef AUKIT_MS_ROWS
             AUKIT_HIP_CHECK(hipGetLastError());
             uint64_t out_elems = 0;
@@ -1061,7 +1058,7 @@ int stream_msadpcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc
     // ---- the wave kernel: integer sample rates whose positions have at most 512 phases
     static const bool magic_ok = ms_magic_ok();
     MsWaveParams P{};
-    bool wave = magic_ok && ms_fill_coefs(d, P) && interp != AUKIT_INTERP_SINC && !ctx->exact_math && !getenv("AUKIT_MS_GENERIC") &&
+    bool wave = magic_ok && ms_fill_coefs(d, P) && interp != AUKIT_INTERP_SINC && !ctx->exact_math &&
                 d->sample_rate == std::floor(d->sample_rate) && d->sample_rate <= 4e9;
     unsigned long long fa = 0, fb = 0;
     if (wave) {
@@ -1072,23 +1069,20 @@ int stream_msadpcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc
         wave = fb <= 512 && ((double)newlen * (double)fa + (double)fb) * (double)fb < 4294967296.0;
     }
     const int wf = interp == AUKIT_INTERP_CUBIC ? 4 : 1;
-    const int MS_RB = MS_RB_STREAM;
+    constexpr int MS_RB = MS_RB_STREAM;
     // int8 chunks: the round's outputs of every block wait in an LDS row (sst bytes, an odd number of dwords) before they leave
     unsigned sst = 0;
     // (stereo only.  Same-box A/B, 1024 ten-second streams, pairs / lanes: stereo 2.98 / 2.81 ms, stereo mixed to mono 2.40 / 2.11, mono 2.55 / 3.26 —
     // PMC for mono: 828 M / 963 M VALU instructions, LDS bank conflicts 78 M / 0: the copy loop that brings the staged bytes out costs a
-    // mono round more than the bookkeeping it saves, AUKIT_MS_LANES=1 forces it)
-    if (wave && dtype == AUKIT_I8 && !getenv("AUKIT_MS_PAIRS") && (C == 2 || getenv("AUKIT_MS_LANES"))) {
+    // mono round more than the bookkeeping it saves)
+    if (wave && dtype == AUKIT_I8 && C == 2) {
         const unsigned long long Rr = (unsigned long long)(MS_RB * 2 / C);
         const unsigned long long njmax = (Rr * fb + fa - 1) / fa + 2;   // outputs whose floor(x) falls into one round's samples
         sst = (unsigned)((((njmax + 3) / 4) | 1) * 4);
         if ((size_t)nd * 64 * sst > 24 * 1024) sst = 0;                // strong up-sampling: the pair-mapped loop
     }
     wave = wave && spb_dec < (1u << 17) && newlen < (1u << 26);   // (the deferred-line records of k_ms_wave pack q0 and j into 17 and 26 bits)
-    size_t lds = wave ? ms_lds_bytes(C, MS_RB, (unsigned)fb * wf, MS_FB_STREAM, (((size_t)nd * 64 * sst + 7) & ~(size_t)7) + ((MS_RB == 16 && MS_FB_STREAM == 128) ? 0 : (size_t)MS_DL_CAP * 8)) : 0;
-    // (A/B only: what a per-block staging row for whole output lines would cost in resident waves — unused bytes of LDS per workgroup,
-    // profiles/r05_msadpcm_lds_ab.txt)
-    if (const char *e = getenv("AUKIT_MS_EXTRA_LDS")) lds += (size_t)std::max(0, atoi(e));
+    const size_t lds = wave ? ms_lds_bytes(C, MS_RB, (unsigned)fb * wf, MS_FB_STREAM, (((size_t)nd * 64 * sst + 7) & ~(size_t)7) + ((MS_RB == 16 && MS_FB_STREAM == 128) ? 0 : (size_t)MS_DL_CAP * 8)) : 0;
     if (wave && lds <= 64 * 1024) {
         const int R = MS_RB * 2 / C, ndata = d->block_align - 7 * C, nr = (ndata + MS_RB - 1) / MS_RB;
         // tables: blk0 (n + 1) | out_off (n) | out_stride (n) | err | rounds (nr) | weights (fb * wf, f32)
@@ -1141,7 +1135,7 @@ int stream_msadpcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc
         P.unit = d->sample_rate == 48000 ? 1 : 0;
         P.sst = sst;
         P.audit = nullptr;
-        if (ctx->collect_stats && dtype == AUKIT_I8 && MS_RB == 16 && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {
+        if (ctx->collect_stats && dtype == AUKIT_I8 && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {
             if ((rc = ctx->fmt_flag.ensure(64))) { delete ck; return rc; }
             P.audit = reinterpret_cast<unsigned *>(ctx->fmt_flag.p) + 8;
             if (hipMemsetAsync(P.audit, 0, 8, ctx->stream) != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "hipMemsetAsync failed"); }
@@ -1159,15 +1153,15 @@ int stream_msadpcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc
             if (dtype == AUKIT_I8) ms_launch_stream<CC, RBB, MIXX, signed char>(interp, P, grid, lds, ctx->stream);                    \
             else ms_launch_stream<CC, RBB, MIXX, double>(interp, P, grid, lds, ctx->stream);                                           \
         } while (0)
-        if (C == 1) { if (MS_RB == 16) AUKIT_MS_STREAM(1, 16, false); else AUKIT_MS_STREAM(1, 32, false); }
-        else if (mono) { if (MS_RB == 16) AUKIT_MS_STREAM(2, 16, true); else AUKIT_MS_STREAM(2, 32, true); }
-        else { if (MS_RB == 16) AUKIT_MS_STREAM(2, 16, false); else AUKIT_MS_STREAM(2, 32, false); }
+        if (C == 1) AUKIT_MS_STREAM(1, MS_RB, false);
+        else if (mono) AUKIT_MS_STREAM(2, MS_RB, true);
+        else AUKIT_MS_STREAM(2, MS_RB, false);
 #undef AUKIT_MS_STREAM
         if (hipGetLastError() != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "k_ms_wave launch failed"); }
         if ((rc = ctx_end_kernel(ctx, "k_ms_wave", in->total() + out_elems * dtype_size(dtype)))) { delete ck; return rc; }
         int herr = 0;
-        // (scanned: no planned block can raise the kernel's flag — the host looked at every index it will meet; AUKIT_MS_ASSERT=1 waits and looks all the same)
-        if (!scanned || P.audit || getenv("AUKIT_MS_ASSERT"))
+        // (scanned: no planned block can raise the kernel's flag — the host looked at every index it will meet)
+        if (!scanned || P.audit)
         if (hipMemcpyAsync(&herr, P.err, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "k_ms_wave failed"); }
         if (P.audit) {
             unsigned h[2] = {0, 0};

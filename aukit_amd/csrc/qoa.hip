@@ -13,7 +13,6 @@
 //   * stream.qoa stores `math_floor(reconstructed / 256)` (:3299) as int8 rows (one byte per sample of intermediate) and runs its
 //     resample + recursive low-pass (+ channel mean) tail in ONE launch from them (k_iir_tail, stream_tail.hip).
 #include <algorithm>
-#include <chrono>
 #include "resample.h"
 #include "stream_tail.h"
 
@@ -294,11 +293,6 @@ __global__ __launch_bounds__(64) void k_qoa_wave(const unsigned char *src, const
 }
 
 // ================================================================= host side
-struct QoaLaps {   // AUKIT_HOST_TIMING=1: host laps on stderr
-    bool on = getenv("AUKIT_HOST_TIMING") != nullptr;
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    void lap(const char *w) { if (on) { auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[qoa host] %-14s %8.1f us\n", w, std::chrono::duration<double, std::micro>(t - t0).count()); t0 = t; } }
-};
 struct QoaStreamInfo { int channels; double rate, file_samples; bool raised, big; unsigned ncalls; uint64_t njobs, rows_total, L, job_first, call_first, row_base, stride; };
 
 // pass 1 of the device walk; validates the file headers like the reference (errors with its strings)
@@ -385,13 +379,10 @@ static int qoa_decode_launch(aukit_ctx *ctx, const aukit_batch *in, const QoaJob
 
 // aukit.qoa(data)  aukit.lua:1706-1777
 int decode_qoa_audio(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d, double new_rate, int interp, bool do_resample, int dtype, aukit_audio **out) {
-    if (getenv("AUKIT_QOA_HOST")) return decode_qoa_audio_host(ctx, in, d, new_rate, interp, do_resample, dtype, out);
     if (in->n == 0) return fail(AUKIT_E_ARG, "empty batch");
-    QoaLaps laps;
     std::vector<QoaStreamInfo> S;
     int rc = qoa_walk_count(ctx, in, 0, S);
     if (rc) return rc;
-    laps.lap("walk 1");
     const int C = S[0].channels;
     const double rate = S[0].rate;
     std::vector<uint64_t> row_off, row_len;
@@ -408,41 +399,31 @@ int decode_qoa_audio(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_de
     QoaJob *djobs = reinterpret_cast<QoaJob *>(ctx->tmp_buf2.p);
     if ((rc = qoa_walk_fill(ctx, in, 0, S, djobs, in->n, nullptr))) return rc;
     if ((rc = qoa_decode_launch<false>(ctx, in, djobs, njobs, ctx->tmp_buf.p, tot * 2))) return rc;
-    laps.lap("walk 2 + decode");
-    struct AtExit { QoaLaps &l; ~AtExit() { l.lap("rows -> audio"); } } at_exit{laps};
     return audio_from_int_rows(ctx, SRC_I16, ctx->tmp_buf.p, row_off, row_len, in->n, C, rate, new_rate, interp, do_resample, dtype, 32767, 32768, out);
 }
 
 // aukit.stream.qoa(data, mono)  aukit.lua:3202-3337
 int stream_qoa(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d, int interp, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks_out) {
-    if (getenv("AUKIT_QOA_HOST")) return stream_qoa_host(ctx, in, d, interp, mono, dtype, out, chunks_out);
     if (interp == AUKIT_INTERP_SINC) return stream_qoa_host(ctx, in, d, interp, mono, dtype, out, chunks_out);   // aukit.defaultInterpolation = "sinc" (:3252): the reference-order kernels
     if (interp < 0 || interp > 2) return fail(AUKIT_E_ARG, "stream.qoa: bad interpolation");
     if (dtype != AUKIT_F64 && dtype != AUKIT_F32) return fail(AUKIT_E_ARG, "stream.qoa output must be AUKIT_F64 or AUKIT_F32");
     if (in->n == 0) return fail(AUKIT_E_ARG, "empty batch");
-    QoaLaps laps;
     std::vector<QoaStreamInfo> S;
     // Round 6, late: the two walks (they read the input batch and nothing else) run on the look-ahead stream, into words of their own (ctx->qoa_set, alternating):
     // their host waits were waits for everything the call BEFORE had left on ctx->stream — a host that issues call after call now counts, plans and
     // builds the tail's job table while that call's decoder and tail still run.  entry_ev orders a set's next writer behind its last readers (common.h).
-    // AUKIT_QOA_WALK_MAIN=1: everything on ctx->stream, as before.
     struct StreamSwap { aukit_ctx *c; hipStream_t saved; bool on; void back() { if (on) { c->stream = saved; on = false; } } ~StreamSwap() { back(); } } sw{ctx, ctx->stream, false};
-    DevBuf *qs = nullptr;   // the call's set: [0] walk words, [1] call records, [2] decode jobs
     hipStream_t pre = nullptr;
-    if (!getenv("AUKIT_QOA_WALK_MAIN")) {
-        int prc = ctx_pre_stream(ctx, &pre);
-        if (prc) return prc;
-        if (in->ready) AUKIT_HIP_CHECK(hipStreamWaitEvent(pre, in->ready, 0));
-        const uint64_t k = ctx->flac_calls++;
-        AUKIT_HIP_CHECK(hipEventRecord(ctx->entry_ev[k & 1], ctx->stream));
-        if (k >= 1) AUKIT_HIP_CHECK(hipStreamWaitEvent(pre, ctx->entry_ev[(k - 1) & 1], 0));
-        ctx->qoa_par ^= 1;
-        qs = ctx->qoa_set[ctx->qoa_par];
-        ctx->stream = pre; sw.on = true;
-    }
-    int rc = qoa_walk_count(ctx, in, 1, S, qs ? &qs[0] : nullptr);
+    int rc = ctx_pre_stream(ctx, &pre);
     if (rc) return rc;
-    laps.lap("walk 1");
+    if (in->ready) AUKIT_HIP_CHECK(hipStreamWaitEvent(pre, in->ready, 0));
+    const uint64_t call = ctx->flac_calls++;
+    AUKIT_HIP_CHECK(hipEventRecord(ctx->entry_ev[call & 1], ctx->stream));
+    if (call >= 1) AUKIT_HIP_CHECK(hipStreamWaitEvent(pre, ctx->entry_ev[(call - 1) & 1], 0));
+    ctx->qoa_par ^= 1;
+    DevBuf *qs = ctx->qoa_set[ctx->qoa_par];   // the call's set: [0] walk words, [1] call records, [2] decode jobs
+    ctx->stream = pre; sw.on = true;
+    if ((rc = qoa_walk_count(ctx, in, 1, S, &qs[0]))) return rc;
     const int C = S[0].channels;
     const double rate = S[0].rate;
     if (!(rate > 0)) { sw.back(); return stream_qoa_host(ctx, in, d, interp, mono, dtype, out, chunks_out); }
@@ -455,16 +436,13 @@ int stream_qoa(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d,
     }
     std::vector<QoaCallRec> calls;
     if ((rc = ctx->tmp_buf.ensure((size_t)tot + 64))) return rc;
-    DevBuf &JB = qs ? qs[2] : ctx->tmp_buf2;
+    DevBuf &JB = qs[2];
     if ((rc = JB.ensure((size_t)std::max<uint64_t>(njobs, 1) * sizeof(QoaJob) + 64))) return rc;
     QoaJob *djobs = reinterpret_cast<QoaJob *>(JB.p);
-    if ((rc = qoa_walk_fill(ctx, in, 1, S, djobs, ncalls, &calls, qs ? &qs[0] : nullptr, qs ? &qs[1] : nullptr))) return rc;
-    if (sw.on) {   // ctx->stream behind the walks (the decoder reads their jobs)
-        sw.back();
-        AUKIT_HIP_CHECK(hipEventRecord(ctx->pre_ev, pre));
-        AUKIT_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->pre_ev, 0));
-    }
-    laps.lap("walk 2");
+    if ((rc = qoa_walk_fill(ctx, in, 1, S, djobs, ncalls, &calls, &qs[0], &qs[1]))) return rc;
+    sw.back();   // ctx->stream behind the walks (the decoder reads their jobs)
+    AUKIT_HIP_CHECK(hipEventRecord(ctx->pre_ev, pre));
+    AUKIT_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->pre_ev, 0));
     aukit_chunks *ck = new aukit_chunks();
     ck->n = in->n;
     ck->nchunks.assign(in->n, 0); ck->status.assign(in->n, 0); ck->length_seconds.assign(in->n, 0);
@@ -499,7 +477,6 @@ int stream_qoa(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d,
     aukit_audio *a = *out;
     if ((rc = audio_prepare(ctx, &a, in->n, mix ? 1 : C, 48000, dtype, lens.data()))) { delete ck; return rc; }
     *out = a;
-    laps.lap("plan");
     if (ncalls) {
         if ((rc = qoa_decode_launch<true>(ctx, in, djobs, njobs, ctx->tmp_buf.p, tot))) { delete ck; return rc; }
         std::vector<TailJob> jobs;
@@ -541,7 +518,6 @@ int stream_qoa(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d,
             return stream_qoa_host(ctx, in, d, interp, mono, dtype, out, chunks_out);   // very low sample rates: the filter's memory outlasts a tile's warm-up
         }
         if (trc) { delete ck; return trc; }
-        laps.lap("decode + tail");
     }
     if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
     return AUKIT_OK;

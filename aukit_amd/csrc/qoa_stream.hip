@@ -279,7 +279,7 @@ int stream_qoa_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_des
         for (size_t k = 0; k < jobs.size(); k++) { scr_off[k] = scr_elems; scr_elems += ((uint64_t)jobs[k].nout + 1) & ~1ull; max_nout = std::max<uint64_t>(max_nout, (uint64_t)jobs[k].nout); }
         // two passes whenever the scratch (one double per output) is affordable: the one-lane-per-job kernel pays four dependent table loads
         // and ~60 fp64 operations per output on a few hundred waves (1024 stereo streams of ten seconds: 94 ms against 7 ms in two passes)
-        if (scr_elems * 8 <= (48ull << 30) && max_nout && !getenv("AUKIT_QOA_ONE_PASS")) {
+        if (scr_elems * 8 <= (48ull << 30) && max_nout) {
             DevBuf &S3 = ctx_scratch3(ctx);
             if ((rc = S3.ensure((size_t)scr_elems * 8 + 64))) { delete ck; return rc; }
             if ((rc = upload_table(ctx, ctx->misc_buf, scr_off.data(), scr_off.size() * 8))) { delete ck; return rc; }

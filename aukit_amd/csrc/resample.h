@@ -66,7 +66,7 @@ struct ResampleParams {
     int mix_mono;      // EPI_STREAM_FLOOR: 1 = mean over channels after interpolation (:2905-2908), 2 = l + r/2 (:2672)
     int pos_mul;       // x = ((i-1) * pos_mul) / ratio + 1 (stream.dfpwm steps i by `channels`); 0 means 1
     int out_channels;  // EPI_STREAM_DFPWM: rows written per output
-    int nt_store;      // fast kernels: non-temporal output stores (tuning knob AUKIT_NT_STORE)
+    int nt_store;      // fast kernels: non-temporal output stores; always 0 from the host (it was a tuning knob), k_fast_wave still reads it
     int table;         // SRC_PCM_GENERIC: the "string" is a Lua TABLE of numbers (doubles, 8 bytes each: aukit.lua:2255-2290), read as they are
                        // (last members: the offsets of everything the wave kernels read stay what they were)
     const int *only_if;// k_resample: non-null → the launch does nothing unless *only_if != 0 (fast_fmt.hip's flag: a float string with samples beyond ±1)

@@ -302,7 +302,6 @@ int launch_resample(aukit_ctx *ctx, int src_kind, int interp, int epi, int out_d
     unsigned per_cu = (unsigned)std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds_bytes, 1));
     if (per_cu < 1) per_cu = 1;
     per_cu *= 16;   // a finer hand-out than the resident count: 8 / 16 / 32 / 64 / 128 workgroups per CU measured 7.37 / 6.57 / 6.28 / 6.11 / 6.02 ms on stream.g711 through this kernel
-    if (const char *e = getenv("AUKIT_RESAMPLE_PER_CU")) { const int v = atoi(e); if (v >= 1) per_cu = (unsigned)v; }   // tuning knob
     unsigned grid = std::min<unsigned>(P.n_tiles, (unsigned)ctx->num_cus * per_cu);
     int rc = ctx_begin_kernel(ctx);
     if (rc) return rc;
@@ -359,7 +358,7 @@ int plan_tiles_sized(aukit_ctx *ctx, const std::vector<Seg> &segs, int tile_out,
     // stream.pcm on 4096 ten-second streams they are 1.6 MB of segments and 7.7 MB of tile -> segment entries per call.
     const size_t seg_bytes = segs.size() * sizeof(Seg);
     if (!ctx->plan_key.empty() && ctx->plan_tile_out == tile_out && ctx->plan_segs.size() == seg_bytes && seg_bytes &&
-        memcmp(ctx->plan_segs.data(), segs.data(), seg_bytes) == 0 && !getenv("AUKIT_NO_PLAN_CACHE")) {
+        memcmp(ctx->plan_segs.data(), segs.data(), seg_bytes) == 0) {
         P.n_tiles = ctx->plan_n_tiles;
         P.segs = reinterpret_cast<const Seg *>(ctx->seg_buf.p);
         P.tiles_per_seg = ctx->plan_tiles_per_seg;

@@ -29,8 +29,8 @@ struct RsOnepoleParams {
     // recurrence forgets its state at m per output (m^(512 warm) < 2^-40), so the run's own outputs are those of the whole row's chain to far
     // below an f32 ulp — and a row is no longer ONE serial chain of 938 tiles on a chip that can run four times as many chains as config 5 has rows
     int segs, warm;
-    int novec;   // AUKIT_RS_NOVEC=1: every window element by element (the first cut; A/B)
-    int fr_mul;  // frame-by-frame rows: a record's offset counts int32 slots — 2 when the frames hold int16 finals (k_flac_decode<..., O16>), else 1
+    int novec;   // always 0 from the host (it was an A/B switch): 1 = every window element by element (the first cut); k_rs_onepole and k_rsp still read it
+    int fr_mul;  // frame-by-frame rows: a record's offset counts int32 slots — 2 when the frames hold int16 finals (k_flac_stream / k_flac_pq <O16>), else 1
     // NW = 2 (round 4, late): a workgroup = the two channels of one stream, a wave each; what leaves is their MEAN (`Audio:mono` :682-687 behind
     // the filter), `out` / `a_meta` describe the MONO audio, rowmax2[stream] receives the larger of the two channels' maxima (what a
     // non-independent effects.normalize in between divides by, :3439-3444); wave_lds = floats of LDS per wave

@@ -18,7 +18,7 @@
 // The window of 640 outputs is staged at once (16 int16 = 32 bytes per lane: 38 of 64 lanes at 44.1 kHz — a window of 320 would use 19 — and the
 // conversion costs what the wave costs, not what the busy lanes cost), then two sub-tiles of 320 run from it.
 // Everything else is k_rs_onepole's: the window requested a tile ahead by an asm load the compiler does not see (tests/test_isa_schedule.py walks
-// this file's code too), first / last tiles and `AUKIT_RS_NOVEC` element by element, frame-by-frame rows (FLAC's int16 finals), runs of tiles with
+// this file's code too), first / last tiles and `RsOnepoleParams::novec` element by element, frame-by-frame rows (FLAC's int16 finals), runs of tiles with
 // a warm-up (segs / warm), the two-channel mean (NW = 2), the row maxima for effects.normalize.
 #include <algorithm>
 #include <cmath>
@@ -449,7 +449,7 @@ bool rsp_try(aukit_ctx *ctx, RsOnepoleParams &P, bool highpass, bool r32, int NW
     {   // runs of tiles per row: lazy_onepole_try's rule on this kernel's tile
         const double m = highpass ? P.coef : 1.0 - P.coef;
         int warm = 0, segs = 1;
-        if (m > 0 && m < 1 && !getenv("AUKIT_RS_ONE_CHAIN")) {
+        if (m > 0 && m < 1) {
             warm = (int)std::ceil(40.0 * M_LN2 / -std::log(m) / TT);
             const uint64_t min_tiles = (min_out_len + TT - 1) / TT;
             const uint64_t by_rows = std::max<uint64_t>(1, 4096 / std::max<size_t>(rows, 1)), by_len = min_tiles / (8ull * (uint64_t)std::max(warm, 1));

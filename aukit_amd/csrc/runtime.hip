@@ -34,9 +34,8 @@ void DevBuf::release() {
 // Host -> device copy of a descriptor table on the context's stream that never blocks the host on the stream's earlier work.
 int h2d_table(aukit_ctx *ctx, void *dst, const void *src, size_t bytes) {
     if (!bytes) return AUKIT_OK;
-    static const bool no_ring = getenv("AUKIT_NO_TABLE_RING") != nullptr;
     const size_t HALF = (size_t)16 << 20;
-    if (!no_ring && bytes <= HALF) {   // (a table that fills most of a half just turns the ring over sooner)
+    if (bytes <= HALF) {   // (a table that fills most of a half just turns the ring over sooner)
         if (!ctx->tab_ring) {
             if (hipHostMalloc(reinterpret_cast<void **>(&ctx->tab_ring), 2 * HALF, hipHostMallocDefault) != hipSuccess) { ctx->tab_ring = nullptr; (void)hipGetLastError(); }
             else { ctx->tab_half = HALF; ctx->tab_head = 0; ctx->tab_cur = 0; ctx->tab_non[0] = ctx->tab_non[1] = 0; }
@@ -261,8 +260,7 @@ void aukit_ctx_destroy(aukit_ctx *c) {
     c->seg_buf.release(); c->tile_buf.release(); c->misc_buf.release(); c->tmp_buf.release(); c->tmp_buf2.release(); c->tmp_buf3.release(); c->wt_buf.release(); c->enc_state_buf.release(); c->dfx_lut.release(); c->dfx_gather.release(); if (c->dfx_sub_out) { aukit_batch_free(c->dfx_sub_out); c->dfx_sub_out = nullptr; }
     if (c->aux_stream) {
         (void)hipStreamSynchronize(c->aux_stream);
-        if (c->dec_stream) { (void)hipStreamSynchronize(c->dec_stream); (void)hipStreamDestroy(c->dec_stream); }
-        for (int i = 0; i < 10; i++) if (c->aux_ev[i]) (void)hipEventDestroy(c->aux_ev[i]);
+        for (int i = 0; i < 9; i++) if (c->aux_ev[i]) (void)hipEventDestroy(c->aux_ev[i]);
         (void)hipStreamDestroy(c->aux_stream);
     }
     if (c->stream_full) { aukit_audio_free(c->stream_full); c->stream_full = nullptr; }

@@ -331,7 +331,7 @@ static void tail_launch_out(int interp, int dtype, const TailParams &P, unsigned
 struct TailShape { bool ok = false, fast = false; int C = 1, E = 4, T = 1024, W = 0, cap = 0, xbn = 0, wf = 1; unsigned long long fa = 0, fb = 0; size_t lds = 0; double ratio = 1, lp_alpha = 0; };
 static TailShape tail_shape(aukit_ctx *ctx, int kind, int rows_kind, int mix_channels, double rate, double full, int interp, int dtype, uint64_t max_nout, uint64_t avg_nout) {
     TailShape S;
-    if (interp < 0 || interp > 2 || (dtype != AUKIT_F64 && dtype != AUKIT_F32) || getenv("AUKIT_NO_IIR_TAIL")) return S;
+    if (interp < 0 || interp > 2 || (dtype != AUKIT_F64 && dtype != AUKIT_F32)) return S;
     if (ctx->exact_math == 2) return S;   // "always the reference-order kernels": the carried two-pass recurrence, not the warm-up tiles
     if (kind == TAIL_QOA && rows_kind != TAIL_ROWS_I8) return S;
     if (kind == TAIL_FLAC && (rows_kind == TAIL_ROWS_I8 || mix_channels > 1)) return S;
@@ -346,7 +346,7 @@ static TailShape tail_shape(aukit_ctx *ctx, int kind, int rows_kind, int mix_cha
     const double mag = rows_kind == TAIL_ROWS_I8 ? 128.0 : std::max(1.0, std::ldexp(1.0, 31) / full);
     const double wd = std::ceil((37.0 + std::log(mag)) / decay);
     // F32 storage: the f32 interpolation (k_iir_tail_fast, wave-private tiles) — integer sample rates with at most 512 output phases
-    S.fast = dtype == AUKIT_F32 && !ctx->exact_math && !getenv("AUKIT_NO_TAIL_FAST") && rate == std::floor(rate) && rate <= 4e9;
+    S.fast = dtype == AUKIT_F32 && !ctx->exact_math && rate == std::floor(rate) && rate <= 4e9;
     if (S.fast) {
         unsigned long long x = 48000, y = (unsigned long long)rate;
         while (y) { const unsigned long long tq = x % y; x = y; y = tq; }
@@ -355,7 +355,7 @@ static TailShape tail_shape(aukit_ctx *ctx, int kind, int rows_kind, int mix_cha
         S.fast = S.fb <= 512 && ((double)max_nout * (double)S.fa + (double)S.fb) * (double)S.fb < 4294967296.0 && wd <= 192;
     }
     S.E = ((avg_nout >= 6144 && kind == TAIL_QOA) || (S.fast && avg_nout >= 2048)) ? 8 : 4;
-    if (S.fast && S.C == 1 && avg_nout >= 4096 && !getenv("AUKIT_TAIL_E8")) S.E = 16;   // a thread's warm-up (W steps) is paid once per E outputs: stream.flac's tail 4.6 / 3.3 / 3.1 ms for E = 4 / 8 / 16, stream.qoa's 2.8 -> 2.5   // long jobs (QOA calls): 2048-output tiles; FLAC blocks: 1024; the fast kernel's wave tiles: 512 outputs from 2048 per job on
+    if (S.fast && S.C == 1 && avg_nout >= 4096) S.E = 16;   // a thread's warm-up (W steps) is paid once per E outputs: stream.flac's tail 4.6 / 3.3 / 3.1 ms for E = 4 / 8 / 16, stream.qoa's 2.8 -> 2.5   // long jobs (QOA calls): 2048-output tiles; FLAC blocks: 1024; the fast kernel's wave tiles: 512 outputs from 2048 per job on
     S.T = (S.fast ? 64 : 256) * S.E;
     if (wd > (double)S.T) return S;
     S.W = (int)wd;
@@ -405,7 +405,6 @@ bool iir_tail_try_dev(aukit_ctx *ctx, int kind, int rows_kind, const void *rows,
         P.dq256 = (unsigned)((64ull * S.fa) / S.fb); P.dr256 = (unsigned)((64ull * S.fa) % S.fb);   // the step of one row of a wave tile (64 outputs)
     }
     unsigned per_cu = 64;   // workgroups per CU in the grid (what the LDS lets stay resident is fewer: a finer hand-out of the tiles): 8 / 16 / 32 / 64 / 128 / 256 measured 3.51 / 3.42 / 3.40 / 3.37 / 3.46 / 3.55 ms on stream.qoa
-    if (const char *e = getenv("AUKIT_TAIL_PER_CU")) { const int v = atoi(e); if (v >= 1) per_cu = (unsigned)v; }   // tuning knob
     const unsigned grid = (unsigned)std::min<uint64_t>(S.fast ? (P.n_tiles + 3) / 4 : P.n_tiles, (uint64_t)ctx->num_cus * per_cu);
     if ((*rc = ctx_begin_kernel(ctx))) return true;
     const size_t lds = S.lds;

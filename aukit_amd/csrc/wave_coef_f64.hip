@@ -255,11 +255,9 @@ bool wave_coef_f64_try(aukit_ctx *ctx, int src_kind, int interp, double old_rate
     unsigned g64 = F.b, h64 = 64;
     while (h64) { const unsigned r = g64 % h64; g64 = h64; h64 = r; }
     unsigned ph = F.b / g64;
-    const char *er = getenv("AUKIT_COEF_REGS");
-    if (F.wd != 0 || (ph != 1 && ph != 3 && ph != 5) || (WT / 64) % (int)ph != 0 || (er && atoi(er) == 0)) ph = 0;
+    if (F.wd != 0 || (ph != 1 && ph != 3 && ph != 5) || (WT / 64) % (int)ph != 0) ph = 0;
     const unsigned qstep = ph ? (unsigned)((64ull * ph * F.a) / F.b) : 0u;
     unsigned per_cu = 512;   // workgroups per CU in the grid (six are resident): 64 / 128 / 256 / 512 / 1024 / 2048 measured 1.573 / 1.550 / 1.541 / 1.473 / 1.581 / 1.771 ms on config 2a (a wave then takes 3-4 tiles: the hardware's dispatcher balances better than the static tile stride)
-    if (const char *e = getenv("AUKIT_FAST_BLOCKS_PER_CU")) { int v = atoi(e); if (v >= 1) per_cu = (unsigned)v; }
     const unsigned grid = std::min<unsigned>((P.n_tiles + 3) / 4, (unsigned)ctx->num_cus * per_cu);
     if ((*rc = ctx_begin_kernel(ctx))) return true;
     const double inv_b = 1.0 / (double)F.b;

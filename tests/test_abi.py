@@ -119,3 +119,27 @@ def test_container_struct_layout():
     from aukit_amd import _native as N
     assert C.sizeof(N.GroupCall) == 160 and N.GroupCall.new_rate.offset == 64 and N.GroupCall.args.offset == 80   # static_assert in group.hip
     assert C.sizeof(N.Container) == 688 + 8 + 8 + 4 + 4 + 8 and N.Container.payload_off.offset == 688 and N.Container.length_seconds.offset == 712
+
+
+def test_every_env_switch_is_set_by_a_test_and_documented():
+    """the library's behaviour may depend on an AUKIT_* environment variable only where a test sets it: every name a getenv() under aukit_amd/csrc/
+    reads is set in a test file other than this one — the first argument of a setenv(...) or a key of a dict of variables (a delenv or a mention
+    in a docstring sets nothing) — and stands in INTEGRATION.md's table of switches (this test lists no name itself)"""
+    csrc = os.path.join(ROOT, "aukit_amd", "csrc")
+    names = set()
+    for f in sorted(os.listdir(csrc)):
+        names |= set(re.findall(r'getenv\("(AUKIT_[A-Z0-9_]+)"\)', open(os.path.join(csrc, f), errors="replace").read()))
+    assert names, "no getenv(\"AUKIT_...\") found: the search is broken"
+    tests = os.path.join(ROOT, "tests")
+    text = ""
+    for dirpath, _, files in os.walk(tests):
+        for f in files:
+            p = os.path.join(dirpath, f)
+            if f.endswith(".py") and not os.path.samefile(p, __file__):
+                text += open(p, errors="replace").read() + "\n"
+    unset = sorted(n for n in names if not re.search(r"setenv\(\s*[\"']" + n + r"[\"']|[\"']" + n + r"[\"']\s*:", text))
+    assert not unset, f"read by the library, set by no test: {unset}"
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    rows = set(re.findall(r"^\|\s*`(AUKIT_[A-Z0-9_]+)`\s*\|", doc, flags=re.M))
+    assert sorted(names - rows) == [], f"missing from INTEGRATION.md's table: {sorted(names - rows)}"
+    assert sorted(rows - names) == [], f"in INTEGRATION.md's table but read nowhere: {sorted(rows - names)}"

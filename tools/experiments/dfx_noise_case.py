@@ -1,4 +1,4 @@
-"""One cell of tools/r06_dfx_grid.py with the engine's own account of it (AUKIT_DFPWM_STATS): python3 tools/experiments/dfx_noise_case.py [streams] [class] [entry]"""
+"""One cell of tools/r06_dfx_grid.py timed with and without the speculative schedule: python3 tools/experiments/dfx_noise_case.py [streams] [class] [entry]"""
 import ctypes, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 sys.argv, args = sys.argv[:1], sys.argv[1:]
@@ -23,9 +23,6 @@ else:
     mono = B.mono(ctx, B.decode(ctx, bt, d, dtype=N.F32))
     f = lambda: B.dfpwm_encode(ctx, mono, True, out=out)
 f(); ctx.sync()
-os.environ["AUKIT_DFPWM_STATS"] = "1"
-f(); ctx.sync()
-del os.environ["AUKIT_DFPWM_STATS"]
 print(f"{n} x {kind} {entry}: default {ns['timed'](f, n):.2f} ms", flush=True)
 os.environ["AUKIT_DFPWM_NOSPEC"] = "1"
 print(f"{n} x {kind} {entry}: NOSPEC  {ns['timed'](f, n):.2f} ms", flush=True)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""stream.flac on 1024 copies... of 4 encoder-made stereo files: wall time per call and (AUKIT_HOST_TIMING=1) the host laps (GPU box)"""
+"""stream.flac on 1024 copies... of 4 encoder-made stereo files: wall time per call (GPU box)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
