@@ -457,6 +457,93 @@ def au(data):  # aukit.lua:1639
     return Audio(_load(d, p), {}, info)
 
 
+# ---- a mixed library in one call: every file its own container, rate, format and channel count (aukit_decode_resample_mixed) ----
+_MAGIC_KIND = {"wav": N.CONTAINER_WAV, "aiff": N.CONTAINER_AIFF, "au": N.CONTAINER_AU}
+
+
+def _sniff_many(files):
+    """load_many's host half, up to the device call: every file sniffed by magic as `detect` does and walked by aukit_parse_container
+    -> ([descriptor per file], [(first payload byte, byte count) per file], [info table per file]).  A file that is no WAV / AIFF / AU, or whose
+    payload is neither PCM nor G.711, raises LuaError naming the file's index (0-based, the position in `files`)."""
+    _expect(1, files, "table")
+    descs, ranges, infos = [], [], []
+    for i, f in enumerate(files):
+        if not isinstance(f, (bytes, bytearray, memoryview)):
+            raise LuaError(f"bad argument #1 (file {i}: expected string)")
+        kind = detect(bytes(f[:12]))[0]
+        if kind not in _MAGIC_KIND:
+            raise LuaError(f"file {i}: not a WAV, AIFF or AU file")
+        try:
+            c, _ = _parse(f, _MAGIC_KIND[kind])
+        except LuaError as e:
+            raise LuaError(f"file {i}: {e}") from None
+        d = _desc_copy(c)
+        if d.codec not in (N.CODEC_PCM, N.CODEC_G711):
+            what = N.WAVDT[c.wav_data_type] if kind == "wav" else f"codec {d.codec}"
+            raise LuaError(f"file {i}: {what} payload: load_many takes PCM and G.711 (the block codecs keep their own loaders)")
+        descs.append(d)
+        ranges.append((int(c.payload_off), int(c.payload_len)))
+        if kind == "wav":
+            infos.append({"dataType": N.WAVDT[c.wav_data_type], "bitDepth": c.bit_depth})
+        else:
+            infos.append({"bitDepth": d.bit_depth, "dataType": ("signed", "unsigned", "float")[d.data_type]} if d.codec == N.CODEC_PCM else {"bitDepth": 8, "dataType": "signed"})
+    return descs, ranges, infos
+
+
+class _RowView(B.AudioBatch):
+    """One stream of an AudioBatch seen as an AudioBatch of its own (what an Audio wraps): geometry and samples come from the parent's rows; a
+    handle of its own exists only once a method hands the audio on to the library (then the row is uploaded as a one-stream audio, once)."""
+
+    def __init__(self, parent, s, shared):
+        self.ctx = parent.ctx
+        self._parent, self._s, self._shared = parent, s, shared
+        self._own = None
+
+    def info(self):
+        inf = dict(self._parent.info())
+        inf["n"] = 1
+        return inf
+
+    def layout(self):
+        lens, off, stride = self._parent.layout()
+        s = self._s
+        return lens[s:s + 1], off[s:s + 1], stride[s:s + 1]
+
+    def download(self):
+        if "rows" not in self._shared:
+            self._shared["rows"] = self._parent.download()
+        return [[c.copy() for c in self._shared["rows"][self._s]]]
+
+    @property
+    def _h(self):
+        if self._own is None:
+            inf = self._parent.info()
+            self._own = B.AudioBatch.upload(self.ctx, self.download(), inf["sample_rate"], dtype=inf["dtype"])
+        return self._own._h
+
+    def free(self):
+        if self._own is not None:
+            self._own.free()
+            self._own = None
+
+
+def load_many(files, sampleRate=None, interpolation=None, mono=None):
+    """aukit.wav / aukit.aiff / aukit.au (file):resample(sampleRate, interpolation) [:mono()] for a LIST of whole files of any mix of containers,
+    rates, PCM formats / G.711 and channel counts: the payload ranges go up as one batch, one aukit_decode_resample_mixed call resamples (and,
+    by default, mixes down) all of them, and one Audio per file comes back, in input order, each a view of its row of the result.  Without
+    `mono` the files must agree in channel count."""
+    sampleRate = 48000 if sampleRate is None else _expect(2, sampleRate, "number")
+    interpolation = interpolation if interpolation is not None else defaultInterpolation
+    ip = _interp(interpolation, 3)
+    mono = True if mono is None else _expect(4, mono, "boolean")
+    descs, ranges, infos = _sniff_many(files)
+    ctx = context()
+    bt = _wrap(B.Batch.upload, ctx, [bytes(f[o:o + n]) for f, (o, n) in zip(files, ranges)])
+    out = _wrap(B.decode_resample_mixed, ctx, bt, descs, float(sampleRate), ip, mono, ctx.dtype)
+    shared = {}
+    return [Audio(_RowView(out, s, shared), {}, infos[s]) for s in range(len(files))]
+
+
 # aukit.lua:2134-2146: (string.unpack format, bit depth, data type) in table order; every format reads 8 values
 _DETECT_FMTS = (("<8b", 8, "signed"), ("<8B", 8, "unsigned"), ("<8h", 16, "signed"), ("<8i", 32, "signed"),
                 ("<8f", 32, "float"), (None, 24, "signed"), ("<8I", 32, "unsigned"), (None, 24, "unsigned"),

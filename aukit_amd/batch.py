@@ -464,6 +464,18 @@ def decode_resample(ctx, batch, desc, new_rate, interp, dtype=None, out=None):
     return out
 
 
+def decode_resample_mixed(ctx, batch, descs, new_rate, interp, mono=False, dtype=None, out=None):
+    """aukit_decode_resample_mixed: stream s is decoded with descs[s] (PCM of any format or G.711, any rate), resampled to `new_rate` and, with
+    `mono`, mixed down — one call, one launch, one AudioBatch at `new_rate` in the batch's order.  `descs`: one CodecDesc per stream."""
+    out = out if out is not None else AudioBatch(ctx)
+    arr = (N.CodecDesc * max(len(descs), 1))()
+    for i, d in enumerate(descs):
+        C.memmove(C.byref(arr[i]), C.byref(d), C.sizeof(N.CodecDesc))
+    N.check(N.lib().aukit_decode_resample_mixed(ctx._h, batch._h, arr, C.c_uint32(len(descs)), C.c_double(new_rate), _interp(interp), int(bool(mono)),
+                                                ctx.dtype if dtype is None else dtype, C.byref(out._h)))
+    return out
+
+
 def resample(ctx, audio, new_rate, interp, out=None):
     out = out if out is not None else AudioBatch(ctx)
     N.check(N.lib().aukit_resample(ctx._h, audio._h, C.c_double(new_rate), _interp(interp), C.byref(out._h)))

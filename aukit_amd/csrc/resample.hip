@@ -12,18 +12,7 @@
 #define AUKIT_CONST_AS_I __attribute__((address_space(4)))
 namespace aukit {
 
-// ------------------------------------------------------------------ sample decoding (pcm_raw / pcm_norm: resample_dev.h)
-// aukit.lua:1374-1379: returns ±m as a double (sign folded in), to be scaled by 2^-13 or 2^-6
-AUKIT_DEV double g711_value(unsigned byte, int ulaw) {
-    unsigned b = byte ^ (ulaw ? 0xFFu : 0x55u);
-    int m = b & 15, e = (b >> 4) & 7;
-    if (!ulaw && e == 0) m = m * 4 + 2;
-    else m = (m * 2 + 33) << e;
-    if (ulaw) m -= 33;
-    bool neg = ((b & 0x80) != 0) == (ulaw != 0);
-    return (double)(neg ? -m : m);  // m / -D == -(m / D) exactly, D a power of two
-}
-
+// ------------------------------------------------------------------ sample decoding: pcm_raw / pcm_norm / g711_value (resample_dev.h)
 // ------------------------------------------------------------------ staging (returns LDS index of table index k_lo)
 template <int SRC>
 AUKIT_DEV int stage(const ResampleParams &P, const Seg &sg, int k_lo, int n_stage, double *sm) {

@@ -38,6 +38,17 @@ AUKIT_DEV double pcm_norm(double s, int dt, double maxv) {
     return s;
 }
 
+// aukit.lua:1374-1379: returns ±m as a double (sign folded in), to be scaled by 2^-13 or 2^-6
+AUKIT_DEV double g711_value(unsigned byte, int ulaw) {
+    unsigned b = byte ^ (ulaw ? 0xFFu : 0x55u);
+    int m = b & 15, e = (b >> 4) & 7;
+    if (!ulaw && e == 0) m = m * 4 + 2;
+    else m = (m * 2 + 33) << e;
+    if (ulaw) m -= 33;
+    bool neg = ((b & 0x80) != 0) == (ulaw != 0);
+    return (double)(neg ? -m : m);  // m / -D == -(m / D) exactly, D a power of two
+}
+
 // ------------------------------------------------------------------ one interpolated sample
 // `tab` points at the LDS slot of table index k_lo for this channel.  Returns
 // `if x % 1 == 0 then d[x] else interp(d, x)`; *isint tells the caller which branch was taken.

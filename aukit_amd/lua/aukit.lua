@@ -31,6 +31,7 @@ int aukit_audio_info(const aukit_audio *, uint32_t *n, int *channels, double *ra
 int aukit_audio_layout(const aukit_audio *, uint64_t *lens, uint64_t *row_off, uint64_t *row_stride);
 int aukit_audio_download(aukit_ctx *, const aukit_audio *, double *dst); void aukit_audio_free(aukit_audio *);
 int aukit_decode(aukit_ctx *, const aukit_batch *, const aukit_codec_desc *, int dtype, aukit_audio **out);
+int aukit_decode_resample_mixed(aukit_ctx *, const aukit_batch *, const aukit_codec_desc *descs, uint32_t n_descs, double new_rate, int interp, int mono, int dtype, aukit_audio **out);
 int aukit_resample(aukit_ctx *, const aukit_audio *, double new_rate, int interp, aukit_audio **out);
 int aukit_mono(aukit_ctx *, const aukit_audio *, aukit_audio **out);
 int aukit_mix(aukit_ctx *, const aukit_audio *const *audios, int count, double amplifier, aukit_audio **out);
@@ -562,6 +563,58 @@ function aukit.au(data)                                                -- :1639
     expect(1, data, "string")
     local c = container(data, 2, false)
     return loader(c.desc, data, pcm_info(c.desc), tonumber(c.payload_off), tonumber(c.payload_len))
+end
+
+-- a mixed library in one call (aukit_decode_resample_mixed): `files` = whole WAV / AIFF / AU files of any mix of rates, PCM formats / G.711 and
+-- channel counts -> one Audio per file at `sampleRate`, mixed down unless `mono == false`; one upload, one launch.  Each Audio is its row of the
+-- result, handed on as a one-stream audio of its own.
+local MAGIC = {{"^RIFF....WAVE", 0}, {"^FORM....AIF[FC]", 1}, {"^%.snd", 2}}
+function aukit.load_many(files, sampleRate, interpolation, mono)
+    expect(1, files, "table")
+    sampleRate = expect(2, sampleRate, "number", "nil") or 48000
+    interpolation = expect(3, interpolation, "string", "nil") or aukit.defaultInterpolation
+    if INTERP[interpolation] == nil then error("bad argument #3 (invalid interpolation type)", 2) end
+    if expect(4, mono, "boolean", "nil") == nil then mono = true end
+    local n = #files
+    local descs = ffi.new("aukit_codec_desc[?]", math.max(n, 1))
+    local offs = ffi.new("uint64_t[?]", n + 1)
+    local parts, infos = {}, {}
+    for i = 1, n do
+        local f = files[i]
+        if type(f) ~= "string" then error("bad argument #1 (file " .. (i - 1) .. ": expected string)", 2) end
+        local kind
+        for _, m in ipairs(MAGIC) do if f:find(m[1]) then kind = m[2] break end end
+        if not kind then error("file " .. (i - 1) .. ": not a WAV, AIFF or AU file", 2) end
+        local c = ffi.new("aukit_container")
+        if C.aukit_parse_container(ffi.cast("const uint8_t*", f), #f, kind, 0, c) ~= 0 then error("file " .. (i - 1) .. ": " .. ffi.string(C.aukit_last_error()), 2) end
+        if c.desc.codec > 1 then error("file " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: load_many takes PCM and G.711 (the block codecs keep their own loaders)", 2) end
+        descs[i - 1] = c.desc
+        parts[i] = f:sub(tonumber(c.payload_off) + 1, tonumber(c.payload_off + c.payload_len))
+        offs[i] = offs[i - 1] + #parts[i]
+        infos[i] = kind == 0 and {dataType = WAVDT[c.wav_data_type], bitDepth = c.bit_depth} or pcm_info(c.desc)
+    end
+    local b = ffi.new("aukit_batch*[1]")
+    check(C.aukit_batch_upload(ctx(), b, ffi.cast("const uint8_t*", table.concat(parts)), offs, n))
+    local batch = ffi.gc(b[0], C.aukit_batch_free)
+    local o = ffi.new("aukit_audio*[1]")
+    check(C.aukit_decode_resample_mixed(ctx(), batch, descs, n, sampleRate, INTERP[interpolation], mono and 1 or 0, F64, o))
+    local whole = ffi.gc(o[0], C.aukit_audio_free)
+    local cnt, ch, rate, dt, tot = ffi.new("uint32_t[1]"), ffi.new("int[1]"), ffi.new("double[1]"), ffi.new("int[1]"), ffi.new("uint64_t[1]")
+    check(C.aukit_audio_info(whole, cnt, ch, rate, dt, tot))
+    local lens = ffi.new("uint64_t[?]", math.max(n, 1))
+    check(C.aukit_audio_layout(whole, lens, nil, nil))
+    local total = 0
+    for i = 0, n - 1 do total = total + tonumber(lens[i]) * ch[0] end
+    local buf = ffi.new("double[?]", math.max(total, 1))
+    check(C.aukit_audio_download(ctx(), whole, buf))
+    local res, at = {}, 0
+    for i = 1, n do  -- packed [s][c][len_s]: row i starts where the rows before it end
+        local one = ffi.new("aukit_audio*[1]")
+        check(C.aukit_audio_upload(ctx(), one, buf + at, lens + (i - 1), 1, ch[0], rate[0], F64))
+        res[i] = wrap(one[0], {}, infos[i])
+        at = at + tonumber(lens[i - 1]) * ch[0]
+    end
+    return res
 end
 
 -- ---------------------------------------------------------------- effects (in place, return the same object: :3356-3618)
