@@ -461,10 +461,12 @@ def au(data):  # aukit.lua:1639
 _MAGIC_KIND = {"wav": N.CONTAINER_WAV, "aiff": N.CONTAINER_AIFF, "au": N.CONTAINER_AU}
 
 
-def _sniff_many(files):
+def _sniff_many(files, stream=False):
     """load_many's host half, up to the device call: every file sniffed by magic as `detect` does and walked by aukit_parse_container
     -> ([descriptor per file], [(first payload byte, byte count) per file], [info table per file]).  A file that is no WAV / AIFF / AU, or whose
-    payload is neither PCM nor G.711, raises LuaError naming the file's index (0-based, the position in `files`)."""
+    payload is neither PCM nor G.711, raises LuaError naming the file's index (0-based, the position in `files`).
+    `stream`: the walk follows aukit.stream.wav / aiff / au's rules instead of the loaders' (`sowt`, AU's offset) — stream.many's host half; the
+    third list then holds what the container says the length is, in seconds (NaN where the stream factory's own figure stands)."""
     _expect(1, files, "table")
     descs, ranges, infos = [], [], []
     for i, f in enumerate(files):
@@ -474,16 +476,18 @@ def _sniff_many(files):
         if kind not in _MAGIC_KIND:
             raise LuaError(f"file {i}: not a WAV, AIFF or AU file")
         try:
-            c, _ = _parse(f, _MAGIC_KIND[kind])
+            c, _ = _parse(f, _MAGIC_KIND[kind], stream=bool(stream))
         except LuaError as e:
             raise LuaError(f"file {i}: {e}") from None
         d = _desc_copy(c)
         if d.codec not in (N.CODEC_PCM, N.CODEC_G711):
             what = N.WAVDT[c.wav_data_type] if kind == "wav" else f"codec {d.codec}"
-            raise LuaError(f"file {i}: {what} payload: load_many takes PCM and G.711 (the block codecs keep their own loaders)")
+            raise LuaError(f"file {i}: {what} payload: {'stream.many' if stream else 'load_many'} takes PCM and G.711 (the block codecs keep their own {'streams' if stream else 'loaders'})")
         descs.append(d)
         ranges.append((int(c.payload_off), int(c.payload_len)))
-        if kind == "wav":
+        if stream:
+            infos.append(float(c.length_seconds))
+        elif kind == "wav":
             infos.append({"dataType": N.WAVDT[c.wav_data_type], "bitDepth": c.bit_depth})
         else:
             infos.append({"bitDepth": d.bit_depth, "dataType": ("signed", "unsigned", "float")[d.data_type]} if d.codec == N.CODEC_PCM else {"bitDepth": 8, "dataType": "signed"})
@@ -646,11 +650,12 @@ class _StreamNS:
         return _StreamNS._chunk_iter(out, ck, length_override, endless_empty)
 
     @staticmethod
-    def _chunk_iter(out, ck, length_override=None, endless_empty=False):
-        chans = out.download()[0]
-        n = int(ck.nchunks[0])
-        lens, poss, status = ck.lens[0][:n], ck.pos[0][:n], int(ck.status[0])
-        clens = ck.chan_lens[0][:n]   # every channel's own length (the rows advance by the first channel's)
+    def _chunk_iter(out, ck, length_override=None, endless_empty=False, s=0, rows=None):
+        """stream `s` of a stream_decode result as the reference's iterator; `rows`: out.download(), where several iterators share one result"""
+        chans = (out.download() if rows is None else rows)[s]
+        n = int(ck.nchunks[s])
+        lens, poss, status = ck.lens[s][:n], ck.pos[s][:n], int(ck.status[s])
+        clens = ck.chan_lens[s][:n]   # every channel's own length (the rows advance by the first channel's)
 
         def it():
             off = 0
@@ -661,7 +666,7 @@ class _StreamNS:
                 raise LuaError("the reference iterator raises a Lua error here (end of data inside the prefill / a malformed block)")
             while endless_empty:  # stream.g711 never returns nil with string input (Q13)
                 yield [np.zeros(0) for _ in chans], float("nan")
-        return it(), (float(ck.length_seconds[0]) if length_override is None else length_override)
+        return it(), (float(ck.length_seconds[s]) if length_override is None else length_override)
 
     def pcm(self, data, bitDepth=None, dataType=None, channels=None, sampleRate=None, bigEndian=None, mono=None):
         if not isinstance(data, (list, tuple)):
@@ -762,6 +767,19 @@ class _StreamNS:
         else:
             it, length = self._run(d, p, mono, dtype, endless_empty=d.codec == N.CODEC_G711)
         return it, (length if math.isnan(c.length_seconds) else c.length_seconds)
+
+    def many(self, files, mono=None):
+        """aukit.stream.wav / aiff / au (file, mono) for a LIST of whole files of any mix of containers, rates, PCM formats / G.711 and channel
+        counts: the payload ranges go up as one batch, one aukit_stream_decode_mixed call computes every iterator call of every file, and a list
+        of (iterator, length) pairs comes back in input order, each what the file's own factory returns (stream.g711's endless empty chunks
+        and the raise behind a stream that ends inside the prefill included).  Without `mono` the files must agree in channel count."""
+        _expect(2, mono, "boolean", "nil")
+        descs, ranges, lengths = _sniff_many(files, stream=True)
+        ctx = context()
+        bt = _wrap(B.Batch.upload, ctx, [bytes(f[o:o + n]) for f, (o, n) in zip(files, ranges)])
+        out, ck = _wrap(B.stream_decode_mixed, ctx, bt, descs, _interp(defaultInterpolation, 0), bool(mono), N.F64)
+        rows = out.download()
+        return [self._chunk_iter(out, ck, None if math.isnan(lengths[i]) else lengths[i], d.codec == N.CODEC_G711, i, rows) for i, d in enumerate(descs)]
 
     def wav(self, data, mono=None, ignoreHeader=None):  # :2927: header walk (library) + dispatch (:2992-2996)
         _expect_src(1, data)

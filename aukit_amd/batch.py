@@ -597,6 +597,25 @@ def stream_decode(ctx, batch, desc, interp, mono=False, dtype=None, out=None):
     return out, Chunks(ch)
 
 
+def stream_decode_mixed(ctx, batch, descs, interp, mono=False, dtype=None, out=None, chunks=None):
+    """aukit_stream_decode_mixed: aukit.stream.pcm / aukit.stream.g711 of stream s with descs[s] (PCM of any format at or below 48 kHz, G.711 at
+    integer rates), every iterator call at once — one call, one launch -> (AudioBatch at 48 kHz in the batch's order, Chunks).  `descs`: one
+    CodecDesc per stream.  `out` / `chunks`: what an earlier call returned — the audio's buffers are reused, the chunk table is replaced (after
+    a refusal both keep what they held)."""
+    out = out if out is not None else AudioBatch(ctx)
+    arr = (N.CodecDesc * max(len(descs), 1))()
+    for i, d in enumerate(descs):
+        C.memmove(C.byref(arr[i]), C.byref(d), C.sizeof(N.CodecDesc))
+    ch = C.c_void_p()
+    N.check(N.lib().aukit_stream_decode_mixed(ctx._h, batch._h, arr, C.c_uint32(len(descs)), _interp(interp), int(bool(mono)),
+                                              ctx.dtype if dtype is None else dtype, C.byref(out._h), C.byref(ch)))
+    ck = Chunks(ch)
+    if chunks is not None:  # the caller's table object takes the new call's numbers
+        chunks.__dict__.update(ck.__dict__)
+        ck = chunks
+    return out, ck
+
+
 class StreamHandle:
     """aukit.stream.<codec> fed piece by piece (aukit_stream_open / feed / finish / next): the chunks are those of the string version for the
     concatenation of everything fed, whatever the feeding pattern (include/aukit_hip.h)."""

@@ -331,14 +331,7 @@ static int decode_resample_flat(aukit_ctx *ctx, const aukit_batch *in, const auk
 }
 
 // ---------------------------------------------------------------- stream.pcm  aukit.lua:2228-2424
-struct ChunkPlan {
-    double ratio;
-    int interp;
-    long K;                        // table re-base per full chunk (Q1)
-    std::vector<int> acc, req;     // per output j (1-based → [j-1]): highest index touched so far / index that must be non-nil
-};
-
-static int build_chunk_plan(double sample_rate, int interp, ChunkPlan &cp, int sinc_w = 10) {
+int build_chunk_plan(double sample_rate, int interp, ChunkPlan &cp, int sinc_w) {   // (ChunkPlan: resample.h)
     static const int iend[4] = {1, 2, 3, 0};
     cp.ratio = 48000 / sample_rate;  // :2364
     cp.interp = interp;
@@ -358,6 +351,33 @@ static int build_chunk_plan(double sample_rate, int interp, ChunkPlan &cp, int s
     return AUKIT_OK;
 }
 
+// iterator call `c` (0-based) of aukit.stream.pcm on a stream of `nframes` whole frames: the call's segment (source window and output count;
+// stream, out_off and out_stride are the caller's) -> its outputs, 0 where the iterator ends instead — *status is written only where the prefill
+// runs out of data, with what that means for the format.  Shared with aukit_stream_decode_mixed (stream_mixed.hip).
+uint32_t stream_pcm_call(const ChunkPlan &cp, long c, long long nframes, bool is_float, bool mono, Seg *g, int32_t *status) {
+    static const int istart[4] = {1, 1, 0, 0}, iend[4] = {1, 2, 3, 0};  // :283-284
+    const int interp = cp.interp;
+    const long long src_base = (long long)c * cp.K - istart[interp];  // frame of table index 0
+    // prefill :2376-2386 reads eagerly up to index iend
+    if (src_base + iend[interp] > nframes - 1) { *status = is_float ? 0 : AUKIT_E_LUA; return 0; }
+    const long long w_avail = nframes - 1 - src_base;
+    // float strings: read() hands out nil past the end (:2291-2311) and interpolate falls back on its neighbours, so only the
+    // floor index must exist; with a mono mix-down of several channels the lazy __index adds that nil (:2368) and raises
+    // like the integer readers do on their first read past the end
+    const std::vector<int> &need = (is_float && !mono) ? cp.req : cp.acc;
+    const uint32_t n_out = (uint32_t)(std::upper_bound(need.begin(), need.end(), (int)std::min<long long>(w_avail, 0x7FFFFFFF)) - need.begin());
+    if (n_out == 0) return 0;  // :2407
+    g->src_base = src_base;
+    g->w_lo = c == 0 ? istart[interp] : -1;
+    g->w_hi = (int)std::min<long long>(w_avail, 0x7FFFFFF0);
+    g->n_out = n_out;
+    g->stream = 0;
+    g->out_off = 0;
+    g->out_stride = 0;
+    g->pad = 0;
+    return n_out;
+}
+
 long stream_pcm_call_frames(double sample_rate, int interp) {
     ChunkPlan cp;
     build_chunk_plan(sample_rate, interp, cp);
@@ -375,7 +395,6 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     if (C == 1) mono = 0;  // :2243
     const int nd = mono ? 1 : C;
     const int bd = table ? 8 : d->bit_depth / 8;   // a table entry is one number (`len = #data / channels`, :2245)
-    static const int istart[4] = {1, 1, 0, 0}, iend[4] = {1, 2, 3, 0};  // :283-284
     const bool is_float = d->data_type == AUKIT_FLOAT;
     // the plan depends on the batch's layout and the descriptor alone: the same batch coming back (austream's loop, bench.py's steps) reuses it
     char keyb[256];
@@ -457,25 +476,13 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
             }
         } else
         for (long c = 0;; c++) {
-            const long long src_base = (long long)c * cp.K - istart[interp];  // frame of table index 0
-            // prefill :2376-2386 reads eagerly up to index iend
-            if (src_base + iend[interp] > nframes - 1) { ck->status[s] = is_float ? 0 : AUKIT_E_LUA; break; }
-            const long long w_avail = nframes - 1 - src_base;
-            // float strings: read() hands out nil past the end (:2291-2311) and interpolate falls back on its neighbours, so only the
-            // floor index must exist; with a mono mix-down of several channels the lazy __index adds that nil (:2368) and raises
-            // like the integer readers do on their first read past the end
-            const std::vector<int> &need = (is_float && !mono) ? cp.req : cp.acc;
-            uint32_t n_out = (uint32_t)(std::upper_bound(need.begin(), need.end(), (int)std::min<long long>(w_avail, 0x7FFFFFFF)) - need.begin());
-            if (n_out == 0) break;  // :2407
             Seg g;
-            g.src_base = src_base;
-            g.w_lo = c == 0 ? istart[interp] : -1;
-            g.w_hi = (int)std::min<long long>(w_avail, 0x7FFFFFF0);
-            g.n_out = n_out;
+            const uint32_t n_out = stream_pcm_call(cp, c, nframes, is_float, mono != 0, &g, &ck->status[s]);
+            if (n_out == 0) break;
+            const long long src_base = g.src_base, w_avail = nframes - 1 - src_base;
+            const std::vector<int> &need = (is_float && !mono) ? cp.req : cp.acc;
             g.stream = s;
             g.out_off = lens[s];  // patched with the row offset below
-            g.out_stride = 0;
-            g.pad = 0;
             segs.push_back(g);
             if (part && !mono && n_out < 48000) {
                 // the stream's last chunk (ok = false behind it), uneven: the partial frame is index w_avail + 1 of channels 0 .. part-1, which reach it at

@@ -131,6 +131,16 @@ struct PcmTail {
 static_assert(sizeof(PcmTail) == 48, "PcmTail layout");
 int launch_stream_pcm_tail(aukit_ctx *ctx, const std::vector<PcmTail> &items, const ResampleParams &P, int interp, int dtype);
 
+// aukit.stream.pcm's host plan (api_resample.hip): what one iterator call reads and delivers depends on the rate and the interpolation alone
+struct ChunkPlan {
+    double ratio;
+    int interp;
+    long K;                        // table re-base per full chunk (Q1)
+    std::vector<int> acc, req;     // per output j (1-based → [j-1]): highest index touched so far / index that must be non-nil
+};
+int build_chunk_plan(double sample_rate, int interp, ChunkPlan &cp, int sinc_w = 10);
+uint32_t stream_pcm_call(const ChunkPlan &cp, long c, long long nframes, bool is_float, bool mono, Seg *g, int32_t *status);
+
 // position of output o (0-based) exactly as the reference computes it on the host
 static inline double host_pos(uint64_t o, double ratio) { return ((double)o) / ratio + 1; }
 

@@ -1,0 +1,494 @@
+// stream_mixed.hip — aukit_stream_decode_mixed: aukit.stream.pcm / aukit.stream.g711 (data_s, <descs[s]>), every iterator call at once, for a batch
+// whose streams each carry their OWN descriptor (aukit.lua:2228-2424, :2850-2913), in one launch.
+//
+// k_resample (resample.hip) runs the stream epilogues with format, channel count, ratio and low-pass weight taken from the launch-uniform
+// ResampleParams; k_stream_mixed is k_resample_mixed's sibling for them and takes all of that per tile.  The host plans
+//   - a class table: one record per distinct (codec, format, byte order, channel count, law, rate) — ratio, reciprocal and the exact_div_verified
+//     verdict, the low-pass weight, the G.711 scale, how many channels are staged (1 where stream.pcm mixes down at read time), the epilogue,
+//     the LDS doubles per staged channel;
+//   - a segment table: one record per (stream, iterator call) — the call's table window (src_base, w_lo, w_hi: api_resample.hip's stream_pcm_call
+//     for PCM, one independent table per call for G.711, Q13), its outputs and where they go;
+//   - a tile table: one record per tile (segment, first output, count) — the tile height is the class's, so the staged window stays within the
+//     LDS budget.
+// A 256-thread workgroup walks tiles (grid-stride).  Per tile the class record is block-uniform, so every format branch is uniform:
+//   (1) the window is decoded into LDS as fp64: every channel, or ((0 + read()) + read() ...) / channels (:2368); a PCM tile's window starts one
+//       output early (the low-pass reads s(o0 - 1)); 16-bit little-endian mono at even addresses takes 16-byte loads;
+//   (2) a lane per output evaluates `if x % 1 == 0 then d[x] else interp(d, x)` in the reference's order, nil fall-backs at w_lo / w_hi;
+//   (3) stream.pcm: ns = ls + alpha * (s - ls) with ls the RAW previous sample — the neighbouring lane's, a wave walks consecutive rows of 64
+//       outputs and evaluates once more only where its run starts — then ns * (ns < 0 and 128 or 127), clamped (:2401-2402);
+//       stream.g711: clamp(floor(s)) per channel or clamp(floor(acc / channels)) (:2905-2909).  Coalesced stores.
+// fp64 in the reference's operation order whatever the storage type; F32 rounds once, at the store.
+#include <algorithm>
+#include <string>
+#include <tuple>
+#include "resample.h"
+#include "resample_dev.h"
+
+namespace aukit {
+
+enum { SMIX_EPI_PCM = 0, SMIX_EPI_FLOOR = 1 };
+
+struct SMixClass {
+    double ratio, rcp;     // x = (i - 1) / ratio + 1
+    double lp_alpha;       // 1 - exp(-(rate / 96000) * 2 pi)  :2365
+    double g711_scale;     // 1 / 0x40  :2891
+    int codec;             // AUKIT_CODEC_PCM / AUKIT_CODEC_G711
+    int bytes;             // per sample
+    int data_type, big_endian, ulaw;
+    int channels;          // in the data
+    int stage;             // channels staged: 1 where stream.pcm mixes down at read time
+    int mix;               // PCM: the staged channel is the channels' mean; G.711: the mean is taken after interpolation
+    int epi;               // SMIX_EPI_*
+    int exact_rcp;         // 1: RN((i-1)/ratio) via rcp + two fmas is verified exact for 48 001 outputs
+    int cap;               // LDS doubles per staged channel
+    int s16le_mono;        // 16-byte vector staging where the stream's bytes start at an even address
+};
+static_assert(sizeof(SMixClass) == 80, "SMixClass layout");
+struct SMixSeg {
+    unsigned long long src_off;  // the stream's first byte, relative to the batch's data
+    long long src_base;          // source frame (within the stream) of table index 0
+    unsigned long long out_off;  // element offset of output channel 0, output index 0 of this call
+    int w_lo, w_hi;              // valid table indices (anything else reads as nil)
+    unsigned n_out;
+    unsigned out_stride;         // elements between output channels
+    unsigned cls;
+    unsigned pad;
+};
+static_assert(sizeof(SMixSeg) == 48, "SMixSeg layout");
+struct SMixTile { unsigned seg, o0, cnt; };
+
+struct SMixParams {
+    const SMixTile *tiles;
+    const SMixSeg *segs;
+    const SMixClass *classes;
+    unsigned n_tiles;
+    const unsigned char *src;
+    const unsigned char *safe_lo, *safe_hi;  // the allocation: a 16-byte vector load at p needs safe_lo <= p and p + 16 <= safe_hi
+    void *out;
+};
+
+AUKIT_DEV double smix_pos(const SMixClass &K, unsigned o) {  // pos_of with the class's numbers
+    const double n = (double)o;
+    return (K.exact_rcp ? div_rcp(n, K.ratio, K.rcp) : n / K.ratio) + 1.0;
+}
+
+// where output o reads the staged window: slot of floor(x) and of its neighbours with the nil fall-backs applied, every slot inside [0, last]
+struct SMixAt { int i0, i1, i2, i3; double fx; bool isint; };
+template <int INTERP>
+AUKIT_DEV SMixAt smix_at(const SMixClass &K, const SMixSeg &sg, int k_lo, int last, unsigned o) {
+    SMixAt a;
+    const double x = smix_pos(K, o);
+    const double ffx = floor(x);
+    int k = (int)ffx;
+    k = k < sg.w_lo ? sg.w_lo : (k > sg.w_hi ? sg.w_hi : k);  // the host guarantees w_lo <= k <= w_hi
+    a.isint = (x == ffx);  // x % 1 == 0
+    a.fx = x - ffx;
+    const int idx = min(max(k - k_lo, 0), last);
+    a.i0 = a.i1 = a.i2 = a.i3 = idx;
+    if constexpr (INTERP == AUKIT_INTERP_LINEAR) {
+        a.i2 = (k + 1 <= sg.w_hi) ? idx + 1 : idx;          // data[ffx + 1] or data[ffx]
+    } else if constexpr (INTERP == AUKIT_INTERP_CUBIC) {
+        a.i0 = (k - 1 >= sg.w_lo) ? idx - 1 : idx;          // p0 or p1
+        a.i2 = (k + 1 <= sg.w_hi) ? idx + 1 : idx;          // p2 or p1
+        a.i3 = (k + 2 <= sg.w_hi) ? idx + 2 : a.i2;         // p3 or p2 or p1
+    }
+    a.i0 = max(a.i0, 0); a.i2 = min(a.i2, last); a.i3 = min(a.i3, last);  // (no-ops on a window the host sized: they keep every LDS read inside it)
+    return a;
+}
+template <int INTERP>
+AUKIT_DEV double smix_tap(const double *tab, const SMixAt &a) {
+    const double p1 = tab[a.i1];
+    if (a.isint || INTERP == AUKIT_INTERP_NONE) return p1;  // d[x] / data[math.floor(x)]  :254-256
+    if constexpr (INTERP == AUKIT_INTERP_LINEAR) return linear_exact(p1, tab[a.i2], a.fx);
+    else return cubic_exact(tab[a.i0], p1, tab[a.i2], tab[a.i3], a.fx);
+}
+
+template <typename T> AUKIT_DEV void smix_store(T *p, double v) { *p = (T)v; }
+
+template <int INTERP, typename OUT_T>
+__global__ __launch_bounds__(256) void k_stream_mixed(const SMixParams P) {
+    extern __shared__ double sm[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int HL = HaloOf<INTERP>::L, HR = HaloOf<INTERP>::R;
+    OUT_T *const out = reinterpret_cast<OUT_T *>(P.out);
+
+    for (unsigned t = blockIdx.x; t < P.n_tiles; t += gridDim.x) {
+        const SMixTile tl = P.tiles[t];
+        const SMixSeg sg = P.segs[tl.seg];
+        const SMixClass K = P.classes[sg.cls];
+        const unsigned o0 = tl.o0, cnt = tl.cnt;
+        const int C = K.channels, SC = K.stage, cap = K.cap;
+
+        // window of the table this tile touches
+        const unsigned o_first = (K.epi == SMIX_EPI_PCM && o0 > 0) ? o0 - 1 : o0;  // the FIR needs s(o0 - 1)
+        int k_lo = (int)floor(smix_pos(K, o_first)) - HL;
+        int k_hi = (int)floor(smix_pos(K, o0 + cnt - 1)) + HR;
+        k_lo = max(k_lo, sg.w_lo);
+        k_hi = min(k_hi, sg.w_hi);
+        int n_stage = k_hi - k_lo + 1;
+        n_stage = min(n_stage, cap - 16);  // the host sized cap for the window plus the vector path's head and tail; never past the class's LDS
+
+        __syncthreads();  // the tile before: its LDS reads are done
+        int shift = 0;
+        if (n_stage > 0) {
+            const long long g0 = sg.src_base + k_lo;  // source frame of table index k_lo (>= 0: w_lo is the stream's or the call's first frame)
+            const unsigned char *base = P.src + sg.src_off;
+            if (K.s16le_mono && (((uintptr_t)base) & 1) == 0) {
+                const unsigned char *a0 = base + 2 * g0;
+                const unsigned char *al = (const unsigned char *)((uintptr_t)a0 & ~(uintptr_t)15);
+                const int head = (int)(a0 - al) >> 1;
+                const int nvec = (head + n_stage + 7) >> 3;
+                const double r32767 = 1.0 / 32767.0;
+                for (int v = tid; v < nvec; v += 256) {
+                    const unsigned char *p = al + 16 * (size_t)v;
+                    short s[8];
+                    if (p >= P.safe_lo && p + 16 <= P.safe_hi) {
+                        uint4 u = *reinterpret_cast<const uint4 *>(p);
+                        s[0] = (short)(u.x & 0xFFFF); s[1] = (short)(u.x >> 16); s[2] = (short)(u.y & 0xFFFF); s[3] = (short)(u.y >> 16);
+                        s[4] = (short)(u.z & 0xFFFF); s[5] = (short)(u.z >> 16); s[6] = (short)(u.w & 0xFFFF); s[7] = (short)(u.w >> 16);
+                    } else {
+                        for (int e = 0; e < 8; e++) {
+                            const unsigned char *q = p + 2 * e;
+                            s[e] = (q >= P.safe_lo && q + 2 <= P.safe_hi) ? (short)(q[0] | q[1] << 8) : (short)0;
+                        }
+                    }
+                    double d[8];
+#pragma unroll
+                    for (int e = 0; e < 8; e++) {
+                        double x = (double)s[e];
+                        d[e] = s[e] < 0 ? x * (1.0 / 32768.0) : div_rcp(x, 32767.0, r32767);  // s / (s < 0 and 32768 or 32767)  :2274
+                    }
+                    double2 *o = reinterpret_cast<double2 *>(sm + 8 * v);
+                    o[0] = make_double2(d[0], d[1]); o[1] = make_double2(d[2], d[3]); o[2] = make_double2(d[4], d[5]); o[3] = make_double2(d[6], d[7]);
+                }
+                shift = head;
+            } else if (K.codec == AUKIT_CODEC_G711) {
+                const int total = n_stage * C;
+                for (int idx = tid; idx < total; idx += 256) {
+                    const int rel = idx / C, c = idx - rel * C;
+                    sm[c * cap + rel] = g711_value(base[(size_t)(g0 + rel) * C + c], K.ulaw) * K.g711_scale;
+                }
+            } else {
+                const int bd = K.bytes;
+                const double maxv = (double)(1ull << (8 * bd - 1));
+                const int total = n_stage * SC;
+                for (int idx = tid; idx < total; idx += 256) {
+                    const int rel = idx / SC, c = idx - rel * SC;
+                    const size_t g = (size_t)(g0 + rel);
+                    double v;
+                    if (K.mix) {  // self[i] = ((0 + read()) + read() ...) / channels   :2368
+                        double acc = 0;
+                        for (int cc = 0; cc < C; cc++) acc = acc + pcm_norm(pcm_raw(base + (g * C + cc) * bd, bd, K.data_type, K.big_endian), K.data_type, maxv);
+                        v = acc / C;
+                    } else {
+                        v = pcm_norm(pcm_raw(base + (g * C + c) * bd, bd, K.data_type, K.big_endian), K.data_type, maxv);
+                    }
+                    sm[c * cap + rel] = v;
+                }
+            }
+        }
+        __syncthreads();
+        if (n_stage <= 0) continue;  // (block-uniform; a tile always has outputs, and outputs always have a window: kept for safety)
+
+        const double *tab0 = sm + shift;  // slot of table index k_lo, channel 0
+        const int last = n_stage - 1;
+        if (K.epi == SMIX_EPI_FLOOR) {
+            for (unsigned j = tid; j < cnt; j += 256) {
+                const unsigned o = o0 + j;
+                const SMixAt a = smix_at<INTERP>(K, sg, k_lo, last, o);
+                double acc = 0;
+                for (int c = 0; c < SC; c++) {
+                    const double s = smix_tap<INTERP>(tab0 + c * cap, a);
+                    if (K.mix) acc = acc + s;                                                                                    // :2905-2907
+                    else smix_store<OUT_T>(out + sg.out_off + (size_t)c * sg.out_stride + o, lua_clamp(floor(s), -128, 127));    // :2909
+                }
+                if (K.mix) smix_store<OUT_T>(out + sg.out_off + o, lua_clamp(floor(acc / SC), -128, 127));                       // :2908
+            }
+        } else {
+            // a wave takes consecutive rows of 64 outputs: the raw sample of a row's last lane is the next row's carry
+            const unsigned rows = (cnt + 63u) >> 6, rpw = (rows + 3u) >> 2;
+            const unsigned wbase = (unsigned)wave * rpw * 64u;
+            for (int c = 0; c < SC; c++) {
+                const double *tab = tab0 + c * cap;
+                OUT_T *orow = out + sg.out_off + (size_t)c * sg.out_stride;
+                double carry = 0;  // ls, the RAW previous sample (Q2); 0 at the start of every chunk
+                if (wbase < cnt && o0 + wbase > 0) carry = smix_tap<INTERP>(tab, smix_at<INTERP>(K, sg, k_lo, last, o0 + wbase - 1));
+                for (unsigned r = 0; r < rpw; r++) {
+                    const unsigned rb = wbase + r * 64u;
+                    if (rb >= cnt) break;  // wave-uniform
+                    const unsigned j = rb + lane;
+                    const bool active = j < cnt;
+                    const unsigned o = o0 + (active ? j : cnt - 1);
+                    const double s = smix_tap<INTERP>(tab, smix_at<INTERP>(K, sg, k_lo, last, o));
+                    double prev = __shfl_up(s, 1);
+                    if (lane == 0) prev = carry;
+                    carry = __shfl(s, 63);
+                    const double ns = prev + K.lp_alpha * (s - prev);                                              // :2401
+                    if (active) smix_store<OUT_T>(orow + o, lua_clamp(ns * (ns < 0 ? 128 : 127), -128, 127));      // :2402
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------ host
+static int check_smix_pcm(const aukit_codec_desc *d) {  // what check_pcm_desc (api_resample.hip) refuses, with its words
+    if (d->bit_depth != 8 && d->bit_depth != 16 && d->bit_depth != 24 && d->bit_depth != 32) return fail(AUKIT_E_ARG, "bad argument #2 (invalid bit depth)");
+    if (d->data_type < 0 || d->data_type > 2) return fail(AUKIT_E_ARG, "bad argument #3 (invalid data type)");
+    if (d->data_type == AUKIT_FLOAT && d->bit_depth != 32) return fail(AUKIT_E_ARG, "bad argument #2 (float audio must have 32-bit depth)");
+    if (d->channels < 1) return fail(AUKIT_E_ARG, "bad argument #4 (number outside of range)");
+    if (d->sample_rate < 1) return fail(AUKIT_E_ARG, "bad argument #5 (number outside of range)");
+    if (d->channels > AUKIT_MAX_PLANAR_CHANNELS) return fail(AUKIT_E_UNSUPPORTED, "at most %d channels are supported", AUKIT_MAX_PLANAR_CHANNELS);
+    return AUKIT_OK;
+}
+
+// everything the stream's own aukit_stream_decode call refuses (stream_pcm / stream_g711, api_resample.hip), with its words; and the one thing that
+// call serves and this one does not: the uneven last chunk
+static int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) {
+    if (d->codec == AUKIT_CODEC_PCM) {
+        int rc;
+        if ((rc = check_smix_pcm(d))) return rc;
+        if (d->sample_rate > 48000) return fail(AUKIT_E_UNSUPPORTED, "stream.pcm above 48 kHz is ill-defined in the reference (lazy table read out of order, SURVEY Q3)");
+        const size_t bd = (size_t)d->bit_depth / 8;
+        if (nb % (bd * d->channels) != 0) {
+            if (nb % bd != 0) return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: data ends inside a sample");
+            if (!mono || d->channels == 1)
+                return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: data ends inside a frame and the channels are not mixed down: the uneven last chunk stays with aukit_stream_decode");
+        }
+        if (nb / (bd * d->channels) > 0x7FFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "stream too long");
+        return AUKIT_OK;
+    }
+    if (d->channels < 1 || d->channels > AUKIT_MAX_PLANAR_CHANNELS) return fail(AUKIT_E_ARG, "channels out of range");
+    if (d->sample_rate != std::floor(d->sample_rate) || d->sample_rate < 1) return fail(AUKIT_E_UNSUPPORTED, "stream.g711 needs an integer sample rate");
+    if (nb % (uint64_t)d->channels != 0 && 48000 / d->sample_rate < 1)
+        return fail(AUKIT_E_UNSUPPORTED, "G.711 data length is not a multiple of the channel count at a rate above 48 kHz");
+    const uint64_t per_call = (uint64_t)d->sample_rate * (uint64_t)d->channels;
+    if ((nb + per_call - 1) / per_call > 0x7FFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "stream too long");
+    return AUKIT_OK;
+}
+
+template <typename OUT_T>
+static int launch_smix(aukit_ctx *ctx, int interp, const SMixParams &P, size_t lds, unsigned grid) {
+    switch (interp) {
+    case AUKIT_INTERP_NONE: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_NONE, OUT_T>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
+    case AUKIT_INTERP_LINEAR: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_LINEAR, OUT_T>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
+    default: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_CUBIC, OUT_T>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
+    }
+    AUKIT_HIP_CHECK(hipGetLastError());
+    return AUKIT_OK;
+}
+
+}  // namespace aukit
+
+using namespace aukit;
+
+extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype,
+                                         aukit_audio **out, aukit_chunks **chunks) {
+    if (!ctx || !in || !out || (!descs && n_descs)) return fail(AUKIT_E_ARG, "null argument");
+    if (dtype != AUKIT_F64 && dtype != AUKIT_F32) return fail(AUKIT_E_ARG, "dtype must be AUKIT_F64 or AUKIT_F32");
+    if (interp < 0 || interp > 3) return fail(AUKIT_E_ARG, "invalid interpolation");
+    if (interp == AUKIT_INTERP_SINC) return fail(AUKIT_E_UNSUPPORTED, "sinc interpolation is not served for per-stream descriptors: stream each class with aukit_stream_decode");
+    if (n_descs != in->n) return fail(AUKIT_E_ARG, "%u descriptors for a batch of %u streams", n_descs, in->n);
+    const uint32_t n = in->n;
+    for (uint32_t s = 0; s < n; s++)
+        if (descs[s].codec != AUKIT_CODEC_PCM && descs[s].codec != AUKIT_CODEC_G711)
+            return fail(AUKIT_E_UNSUPPORTED, "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM and AUKIT_CODEC_G711)", s, descs[s].codec);
+    if (!mono)
+        for (uint32_t s = 1; s < n; s++)
+            if (descs[s].channels != descs[0].channels) return fail(AUKIT_E_ARG, "streams differ in channel count: mix down or split the batch");
+    for (uint32_t s = 0; s < n; s++) {
+        const int rc = check_smix_stream(&descs[s], in->off[s + 1] - in->off[s], mono != 0);
+        if (rc) {  // the stream's own call would fail: its status and words, and which stream it is
+            const std::string m = aukit_last_error();
+            return fail(rc, "%s (stream %u)", m.c_str(), s);
+        }
+    }
+
+    // classes: one per distinct descriptor, in order of first appearance; the tile height is the class's
+    int hl = 0, hr = 0;
+    if (interp == AUKIT_INTERP_LINEAR) { hr = 1; }
+    else if (interp == AUKIT_INTERP_CUBIC) { hl = 1; hr = 2; }
+    typedef std::tuple<int, int, int, int, int, int, double> ClassKey;
+    std::map<ClassKey, unsigned> index;
+    std::vector<SMixClass> classes;
+    std::vector<int> tile_out;  // per class
+    std::vector<unsigned> cls_of(n);
+    size_t lds = 0;
+    for (uint32_t s = 0; s < n; s++) {
+        const aukit_codec_desc &d = descs[s];
+        const bool pcm = d.codec == AUKIT_CODEC_PCM;
+        const ClassKey key(d.codec, pcm ? d.bit_depth : 8, pcm ? d.data_type : 0, pcm ? (d.big_endian ? 1 : 0) : 0, d.channels, pcm ? 0 : (d.ulaw ? 1 : 0), d.sample_rate);
+        auto it = index.find(key);
+        if (it == index.end()) {
+            SMixClass K;
+            memset(&K, 0, sizeof K);
+            K.ratio = 48000 / d.sample_rate;  // :2364, :2896
+            K.rcp = 1.0 / K.ratio;
+            K.lp_alpha = 1 - std::exp(-(d.sample_rate / 96000) * 2 * M_PI);  // :2365
+            K.g711_scale = 1.0 / 64.0;  // m / 0x40  :2891
+            K.codec = d.codec;
+            K.bytes = pcm ? d.bit_depth / 8 : 1;
+            K.data_type = pcm ? d.data_type : 0;
+            K.big_endian = pcm && d.big_endian ? 1 : 0;
+            K.ulaw = d.ulaw ? 1 : 0;
+            K.channels = d.channels;
+            if (pcm) {
+                K.mix = (mono && d.channels > 1) ? 1 : 0;  // with one channel `mono` is ignored  :2243
+                K.stage = K.mix ? 1 : d.channels;
+                K.epi = SMIX_EPI_PCM;
+            } else {
+                K.mix = mono ? 1 : 0;
+                K.stage = d.channels;
+                K.epi = SMIX_EPI_FLOOR;
+            }
+            K.s16le_mono = (pcm && d.bit_depth == 16 && d.data_type == AUKIT_SIGNED && !d.big_endian && d.channels == 1) ? 1 : 0;
+            // tile height: the staged window (tile_out / ratio + halo) x staged channels x 8 B within plan_tiles' budget; 64 KiB at the most
+            const int slack = hl + hr + 2 + 32;  // +32: the vector path's alignment head and tail, the FIR's look-back, the kernel's own margin of 16
+            auto cap_for = [&](int to) { return (int)std::ceil((double)to / K.ratio) + slack; };
+            const size_t budget = 24 * 1024, hard = 64 * 1024;
+            int to = 2048;
+            while (to > 256 && (size_t)cap_for(to) * 8 * K.stage > budget) to -= 256;
+            while (to > 64 && (size_t)cap_for(to) * 8 * K.stage > hard) to -= 64;
+            if ((size_t)cap_for(to) * 8 * K.stage > hard)
+                return fail(AUKIT_E_UNSUPPORTED, "resampling ratio %g with %d channels needs more than 64 KiB of LDS per tile (stream %u)", K.ratio, K.stage, s);
+            K.cap = (cap_for(to) + 1) & ~1;
+            lds = std::max(lds, (size_t)K.cap * 8 * K.stage);
+            it = index.emplace(key, (unsigned)classes.size()).first;
+            classes.push_back(K);
+            tile_out.push_back(to);
+        }
+        cls_of[s] = it->second;
+    }
+    AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
+    for (SMixClass &K : classes) K.exact_rcp = exact_div_verified(ctx, K.ratio, 48001) ? 1 : 0;  // a segment has at most 48 000 outputs
+
+    // segments: one per (stream, iterator call); the chunk table beside them.  stream.pcm's plan is made once per distinct rate
+    std::map<double, ChunkPlan> plans;
+    std::vector<SMixSeg> segs;
+    std::vector<std::vector<uint32_t>> clens(n);
+    std::vector<std::vector<double>> cpos(n);
+    std::vector<uint64_t> lens(n, 0);
+    aukit_chunks *ck = new aukit_chunks();
+    ck->n = n;
+    ck->nchunks.assign(n, 0);
+    ck->status.assign(n, 0);
+    ck->length_seconds.assign(n, 0);
+    uint64_t in_bytes = 0, out_elems = 0;
+    for (uint32_t s = 0; s < n; s++) {
+        const aukit_codec_desc &d = descs[s];
+        const uint64_t nb = in->off[s + 1] - in->off[s];
+        const int C = d.channels;
+        in_bytes += nb;
+        SMixSeg g;
+        memset(&g, 0, sizeof g);
+        g.src_off = in->off[s];
+        g.cls = cls_of[s];
+        if (d.codec == AUKIT_CODEC_PCM) {
+            const int bd = d.bit_depth / 8;
+            const bool is_float = d.data_type == AUKIT_FLOAT, mix = mono && C > 1;
+            auto pit = plans.find(d.sample_rate);
+            if (pit == plans.end()) {
+                pit = plans.emplace(d.sample_rate, ChunkPlan()).first;
+                build_chunk_plan(d.sample_rate, interp, pit->second);
+            }
+            const ChunkPlan &cp = pit->second;
+            const long long nframes = (long long)(nb / ((size_t)bd * C));  // with the mix-down a partial frame counts for nothing
+            ck->length_seconds[s] = ((double)nb / bd) / C / d.sample_rate;  // :2245, :2423
+            for (long c = 0;; c++) {
+                Seg q;
+                const uint32_t n_out = stream_pcm_call(cp, c, nframes, is_float, mix, &q, &ck->status[s]);
+                if (n_out == 0) break;
+                g.src_base = q.src_base; g.w_lo = q.w_lo; g.w_hi = q.w_hi; g.n_out = n_out;
+                g.out_off = lens[s];  // patched with the row offset below
+                segs.push_back(g);
+                clens[s].push_back(n_out);
+                cpos[s].push_back((double)lens[s] / 48000);  // (n - #chunk[1]) / 48000  :2422
+                lens[s] += n_out;
+                if (n_out < 48000) break;  // ok = false → the next call returns nil
+            }
+        } else {
+            // every call is independent (Q13): its own table, indices 1 .. m.  A byte count that is no multiple of the channel count: the last call
+            // raises (stream_g711, api_resample.hip), the calls before it deliver their chunks
+            const double ratio = 48000 / d.sample_rate;
+            const uint64_t per_call = (uint64_t)d.sample_rate * (uint64_t)C;
+            ck->length_seconds[s] = (double)nb / d.sample_rate / C;
+            uint32_t calls = (uint32_t)((nb + per_call - 1) / per_call);  // calls that see data; the reference then returns {{}} forever
+            if (nb % (uint64_t)C != 0) { calls--; ck->status[s] = AUKIT_E_LUA; }
+            for (uint32_t k = 0; k < calls; k++) {
+                const uint64_t pos = (uint64_t)k * per_call;
+                const uint64_t m = std::min<uint64_t>(per_call, nb - pos) / C;    // #retval[1]
+                const uint32_t n_out = (uint32_t)std::floor((double)m * ratio);   // :2897
+                g.src_base = (long long)(pos / C) - 1;
+                g.w_lo = 1; g.w_hi = (int)m; g.n_out = n_out;
+                g.out_off = lens[s];
+                segs.push_back(g);
+                clens[s].push_back(n_out);
+                cpos[s].push_back(((double)(pos + 1) - 1) / d.sample_rate / C);  // (lp - 1) / sampleRate / channels
+                lens[s] += n_out;
+            }
+        }
+        ck->nchunks[s] = (uint32_t)clens[s].size();
+        ck->max_chunks = std::max<uint32_t>(ck->max_chunks, ck->nchunks[s]);
+    }
+    const size_t mc = std::max<uint32_t>(ck->max_chunks, 1);
+    ck->lens.assign((size_t)n * mc, 0);
+    ck->pos.assign((size_t)n * mc, 0);
+    for (uint32_t s = 0; s < n; s++)
+        for (uint32_t k = 0; k < ck->nchunks[s]; k++) {
+            ck->lens[(size_t)s * mc + k] = clens[s][k];
+            ck->pos[(size_t)s * mc + k] = cpos[s][k];
+        }
+    const int C_out = mono ? 1 : (n ? descs[0].channels : 1);
+    ck->channels = (uint32_t)C_out;
+    for (uint32_t s = 0; s < n; s++) out_elems += lens[s] * (uint64_t)C_out;
+    uint64_t nt = 0;
+    for (const SMixSeg &g : segs) nt += (g.n_out + (unsigned)tile_out[g.cls] - 1) / (unsigned)tile_out[g.cls];
+    if (nt > 0xFFFFFFF0ull) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "too many tiles"); }
+
+    aukit_audio *a = *out;
+    int rc;
+    if ((rc = audio_prepare(ctx, &a, n, C_out, 48000, dtype, lens.data()))) { delete ck; return rc; }
+    *out = a;
+    auto deliver = [&]() { if (chunks) { if (*chunks) aukit_chunks_free(*chunks); *chunks = ck; } else delete ck; };
+    if (nt == 0) { deliver(); return AUKIT_OK; }
+
+    std::vector<SMixTile> tiles;
+    tiles.reserve((size_t)nt);
+    {
+        size_t i = 0;
+        for (uint32_t s = 0; s < n; s++)
+            for (uint32_t k = 0; k < ck->nchunks[s]; k++, i++) {
+                SMixSeg &g = segs[i];
+                g.out_off += a->row_off[s];
+                g.out_stride = (unsigned)a->row_stride[s];
+                const unsigned to = (unsigned)tile_out[g.cls];
+                for (unsigned o0 = 0; o0 < g.n_out; o0 += to) tiles.push_back(SMixTile{(unsigned)i, o0, std::min(to, g.n_out - o0)});
+            }
+    }
+    if ((rc = upload_table(ctx, ctx->misc_buf, classes.data(), classes.size() * sizeof(SMixClass))) ||
+        (rc = upload_table(ctx, ctx->seg_buf, segs.data(), segs.size() * sizeof(SMixSeg))) ||
+        (rc = upload_table(ctx, ctx->tile_buf, tiles.data(), tiles.size() * sizeof(SMixTile)))) { delete ck; return rc; }
+
+    SMixParams P;
+    memset(&P, 0, sizeof P);
+    P.tiles = reinterpret_cast<const SMixTile *>(ctx->tile_buf.p);
+    P.segs = reinterpret_cast<const SMixSeg *>(ctx->seg_buf.p);
+    P.classes = reinterpret_cast<const SMixClass *>(ctx->misc_buf.p);
+    P.n_tiles = (unsigned)tiles.size();
+    P.src = in->data();
+    P.safe_lo = in->base;
+    P.safe_hi = in->base + in->cap;
+    P.out = a->dev;
+    unsigned per_cu = (unsigned)std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1));
+    if (per_cu < 1) per_cu = 1;
+    per_cu *= 16;  // a finer hand-out than the resident count, as launch_resample: the tiles of a mixed batch differ in cost
+    const unsigned grid = std::min<unsigned>(P.n_tiles, (unsigned)ctx->num_cus * per_cu);
+    if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
+    if (dtype == AUKIT_F64) rc = launch_smix<double>(ctx, interp, P, lds, grid);
+    else rc = launch_smix<float>(ctx, interp, P, lds, grid);
+    if (rc) { delete ck; return rc; }
+    static const char *names[] = {"k_stream_mixed<none>", "k_stream_mixed<linear>", "k_stream_mixed<cubic>"};
+    if ((rc = ctx_end_kernel(ctx, names[interp], in_bytes + out_elems * dtype_size(dtype)))) { delete ck; return rc; }
+    deliver();
+    return AUKIT_OK;
+}

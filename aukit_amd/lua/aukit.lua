@@ -74,6 +74,7 @@ int aukit_tone(aukit_ctx *, uint32_t n, double frequency, double duration, doubl
 int aukit_noise(aukit_ctx *, uint32_t n, double duration, double amplitude, int channels, double sample_rate, uint64_t seed, int dtype, aukit_audio **out);
 int aukit_pack_pcm(aukit_ctx *, const aukit_audio *, int bit_depth, int data_type, int big_endian, int interleaved, int int_mode, aukit_batch **out);
 int aukit_stream_decode(aukit_ctx *, const aukit_batch *, const aukit_codec_desc *, int interp, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks);
+int aukit_stream_decode_mixed(aukit_ctx *, const aukit_batch *, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks);
 int aukit_chunks_info(const aukit_chunks *, uint32_t *n, uint32_t *max_chunks);
 int aukit_chunks_get(const aukit_chunks *, uint32_t *nchunks, uint32_t *lens, double *pos, int32_t *status, double *length_seconds); void aukit_chunks_free(aukit_chunks *);
 int aukit_chunks_channel_lens(const aukit_chunks *, uint32_t *channels, uint32_t *lens);
@@ -796,6 +797,73 @@ local function stream_container(data, kind, mono, ignoreHeader)
     local it, length = streamer(c.desc, data, mono, dtype, tonumber(c.payload_off), tonumber(c.payload_len))
     if c.length_seconds == c.length_seconds then length = c.length_seconds end  -- not NaN: the container factory computes its own (:2994-2996, :3064-3069, :3107-3113)
     return it, length
+end
+-- a mixed library streamed in one call (aukit_stream_decode_mixed): `files` = whole WAV / AIFF / AU files of any mix of rates, PCM formats / G.711
+-- and channel counts -> a list of {iterator, length} pairs in input order, each what aukit.stream.wav / aiff / au(file, mono) returns; one
+-- upload, one launch.  Without `mono` the files must agree in channel count.
+function aukit.stream.many(files, mono)
+    expect(1, files, "table") expect(2, mono, "boolean", "nil")
+    local n = #files
+    local descs = ffi.new("aukit_codec_desc[?]", math.max(n, 1))
+    local offs = ffi.new("uint64_t[?]", n + 1)
+    local parts, lengths = {}, {}
+    for i = 1, n do
+        local f = files[i]
+        if type(f) ~= "string" then error("bad argument #1 (file " .. (i - 1) .. ": expected string)", 2) end
+        local kind
+        for _, m in ipairs(MAGIC) do if f:find(m[1]) then kind = m[2] break end end
+        if not kind then error("file " .. (i - 1) .. ": not a WAV, AIFF or AU file", 2) end
+        local c = ffi.new("aukit_container")
+        if C.aukit_parse_container(ffi.cast("const uint8_t*", f), #f, kind, 1, c) ~= 0 then error("file " .. (i - 1) .. ": " .. ffi.string(C.aukit_last_error()), 2) end
+        if c.desc.codec > 1 then error("file " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: stream.many takes PCM and G.711 (the block codecs keep their own streams)", 2) end
+        descs[i - 1] = c.desc
+        parts[i] = f:sub(tonumber(c.payload_off) + 1, tonumber(c.payload_off + c.payload_len))
+        offs[i] = offs[i - 1] + #parts[i]
+        lengths[i] = c.length_seconds   -- NaN: the stream factory's own figure stands
+    end
+    local b = ffi.new("aukit_batch*[1]")
+    check(C.aukit_batch_upload(ctx(), b, ffi.cast("const uint8_t*", table.concat(parts)), offs, n))
+    local batch = ffi.gc(b[0], C.aukit_batch_free)
+    local o, ck = ffi.new("aukit_audio*[1]"), ffi.new("aukit_chunks*[1]")
+    check(C.aukit_stream_decode_mixed(ctx(), batch, descs, n, INTERP[aukit.defaultInterpolation], mono and 1 or 0, F64, o, ck))
+    local whole = ffi.gc(o[0], C.aukit_audio_free)
+    local cnt, mx = ffi.new("uint32_t[1]"), ffi.new("uint32_t[1]")
+    check(C.aukit_chunks_info(ck[0], cnt, mx))
+    local m = math.max(mx[0], 1)
+    local nch, lens, pos = ffi.new("uint32_t[?]", math.max(n, 1)), ffi.new("uint32_t[?]", math.max(n, 1) * m), ffi.new("double[?]", math.max(n, 1) * m)
+    local status, length = ffi.new("int32_t[?]", math.max(n, 1)), ffi.new("double[?]", math.max(n, 1))
+    check(C.aukit_chunks_get(ck[0], nch, lens, pos, status, length))
+    C.aukit_chunks_free(ck[0])
+    local acnt, ch, rate, dt, tot = ffi.new("uint32_t[1]"), ffi.new("int[1]"), ffi.new("double[1]"), ffi.new("int[1]"), ffi.new("uint64_t[1]")
+    check(C.aukit_audio_info(whole, acnt, ch, rate, dt, tot))
+    local rows = ffi.new("uint64_t[?]", math.max(n, 1))
+    check(C.aukit_audio_layout(whole, rows, nil, nil))
+    local total = 0
+    for i = 0, n - 1 do total = total + tonumber(rows[i]) * ch[0] end
+    local buf = ffi.new("double[?]", math.max(total, 1))   -- packed [s][c][len_s]
+    check(C.aukit_audio_download(ctx(), whole, buf))
+    local res, at = {}, 0
+    for i = 1, n do
+        local s, base, row = i - 1, at, tonumber(rows[i - 1])
+        local k, off = 0, 0
+        local it = function()
+            if k >= nch[s] then
+                if status[s] == -2 then error("attempt to perform arithmetic on a nil value (field '?')", 2) end
+                return nil
+            end
+            local chunk = {}
+            for c = 1, ch[0] do
+                local t = {}
+                for j = 1, lens[s * m + k] do t[j] = buf[base + (c - 1) * row + off + j - 1] end
+                chunk[c] = t
+            end
+            off = off + lens[s * m + k]; k = k + 1
+            return chunk, pos[s * m + k - 1]
+        end
+        res[i] = {it, lengths[i] == lengths[i] and lengths[i] or length[s]}
+        at = at + row * ch[0]
+    end
+    return res
 end
 function aukit.stream.wav(data, mono, ignoreHeader) return stream_container(data, 0, mono, ignoreHeader) end    -- :2927
 function aukit.stream.aiff(data, mono, ignoreHeader) expect(2, mono, "boolean", "nil") return stream_container(data, 1, mono, ignoreHeader) end  -- :3016
