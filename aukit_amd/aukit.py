@@ -464,12 +464,27 @@ _MAGIC_KIND = {"wav": N.CONTAINER_WAV, "aiff": N.CONTAINER_AIFF, "au": N.CONTAIN
 def _sniff_many(files, stream=False):
     """load_many's host half, up to the device call: every file sniffed by magic as `detect` does and walked by aukit_parse_container
     -> ([descriptor per file], [(first payload byte, byte count) per file], [info table per file]).  A file that is no WAV / AIFF / AU, or whose
-    payload is neither PCM nor G.711, raises LuaError naming the file's index (0-based, the position in `files`).
+    payload is none of PCM, G.711 and DFPWM, raises LuaError naming the file's index (0-based, the position in `files`).
+    An entry may also be a sequence (data, "dfpwm"[, channels[, sampleRate]]) — aukit.dfpwm's arguments, for raw .dfpwm files, which carry no
+    header: the whole of `data` is the payload and the info table is aukit.dfpwm's.
     `stream`: the walk follows aukit.stream.wav / aiff / au's rules instead of the loaders' (`sowt`, AU's offset) — stream.many's host half; the
     third list then holds what the container says the length is, in seconds (NaN where the stream factory's own figure stands)."""
     _expect(1, files, "table")
     descs, ranges, infos = [], [], []
     for i, f in enumerate(files):
+        if isinstance(f, (list, tuple)):
+            if not 2 <= len(f) <= 4 or not isinstance(f[0], (bytes, bytearray, memoryview)) or f[1] != "dfpwm":
+                raise LuaError(f"bad argument #1 (file {i}: expected (string, \"dfpwm\"[, channels[, sampleRate]]))")
+            ch, rate = (f[2] if len(f) > 2 else None), (f[3] if len(f) > 3 else None)
+            for v, integral in ((ch, True), (rate, False)):
+                if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or (integral and v != int(v))):
+                    raise LuaError(f"bad argument #1 (file {i}: expected number for channels and sampleRate)")
+            if stream:
+                raise LuaError(f"file {i}: dfpwm payload: stream.many takes PCM and G.711 (the block codecs keep their own streams)")
+            descs.append(B.make_desc(N.CODEC_DFPWM, 1 if ch is None else int(ch), 48000 if rate is None else rate))
+            ranges.append((0, len(f[0])))
+            infos.append({"bitDepth": 8, "dataType": "signed"})   # what aukit.dfpwm sets
+            continue
         if not isinstance(f, (bytes, bytearray, memoryview)):
             raise LuaError(f"bad argument #1 (file {i}: expected string)")
         kind = detect(bytes(f[:12]))[0]
@@ -480,9 +495,11 @@ def _sniff_many(files, stream=False):
         except LuaError as e:
             raise LuaError(f"file {i}: {e}") from None
         d = _desc_copy(c)
-        if d.codec not in (N.CODEC_PCM, N.CODEC_G711):
+        if d.codec not in ((N.CODEC_PCM, N.CODEC_G711) if stream else (N.CODEC_PCM, N.CODEC_G711, N.CODEC_DFPWM)):
             what = N.WAVDT[c.wav_data_type] if kind == "wav" else f"codec {d.codec}"
-            raise LuaError(f"file {i}: {what} payload: {'stream.many' if stream else 'load_many'} takes PCM and G.711 (the block codecs keep their own {'streams' if stream else 'loaders'})")
+            if stream:
+                raise LuaError(f"file {i}: {what} payload: stream.many takes PCM and G.711 (the block codecs keep their own streams)")
+            raise LuaError(f"file {i}: {what} payload: load_many takes PCM, G.711 and DFPWM (the block codecs keep their own loaders)")
         descs.append(d)
         ranges.append((int(c.payload_off), int(c.payload_len)))
         if stream:
@@ -533,16 +550,17 @@ class _RowView(B.AudioBatch):
 
 def load_many(files, sampleRate=None, interpolation=None, mono=None):
     """aukit.wav / aukit.aiff / aukit.au (file):resample(sampleRate, interpolation) [:mono()] for a LIST of whole files of any mix of containers,
-    rates, PCM formats / G.711 and channel counts: the payload ranges go up as one batch, one aukit_decode_resample_mixed call resamples (and,
-    by default, mixes down) all of them, and one Audio per file comes back, in input order, each a view of its row of the result.  Without
-    `mono` the files must agree in channel count."""
+    rates, PCM formats / G.711 / DFPWM and channel counts: the payload ranges go up as one batch, one aukit_decode_resample_mixed call resamples
+    (and, by default, mixes down) all of them, and one Audio per file comes back, in input order, each a view of its row of the result.  Without
+    `mono` the files must agree in channel count.  A raw .dfpwm file, which has no header, is given as (data, "dfpwm"[, channels[, sampleRate]]):
+    aukit.dfpwm's arguments."""
     sampleRate = 48000 if sampleRate is None else _expect(2, sampleRate, "number")
     interpolation = interpolation if interpolation is not None else defaultInterpolation
     ip = _interp(interpolation, 3)
     mono = True if mono is None else _expect(4, mono, "boolean")
     descs, ranges, infos = _sniff_many(files)
     ctx = context()
-    bt = _wrap(B.Batch.upload, ctx, [bytes(f[o:o + n]) for f, (o, n) in zip(files, ranges)])
+    bt = _wrap(B.Batch.upload, ctx, [bytes((f[0] if isinstance(f, (list, tuple)) else f)[o:o + n]) for f, (o, n) in zip(files, ranges)])
     out = _wrap(B.decode_resample_mixed, ctx, bt, descs, float(sampleRate), ip, mono, ctx.dtype)
     shared = {}
     return [Audio(_RowView(out, s, shared), {}, infos[s]) for s in range(len(files))]

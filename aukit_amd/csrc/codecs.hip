@@ -48,6 +48,42 @@ __global__ __launch_bounds__(64) void k_dfpwm_decode(const unsigned char *src, c
     }
 }
 
+// The same slices for a LIST of streams that are a subset of a batch (the DFPWM streams of aukit_decode_resample_mixed, resample_mixed.hip): a lane
+// per entry (first byte, byte count, row offset), the samples left flat in decode order — the interleaved order, whatever the channel count — in
+// rows that start at multiples of 16 bytes: the eight samples of a fed byte are one 8-byte store.
+struct DfListItem { unsigned long long src_off, nb, row_off; };
+__global__ __launch_bounds__(64) void k_dfpwm_decode_list(const unsigned char *src, const DfListItem *list, unsigned n, signed char *rows) {
+    const unsigned s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= n) return;
+    const DfListItem it = list[s];
+    const unsigned char *p = src + it.src_off;
+    signed char *o = rows + it.row_off;
+    DfDec d{};
+    unsigned long long i = 0;
+    for (unsigned long long pos = 0; pos < it.nb; pos += 6000) {
+        const unsigned long long cnt = it.nb - pos < 6001 ? it.nb - pos : 6001;
+        for (unsigned long long b = 0; b < cnt; b++) {
+            unsigned byte = p[pos + b];
+            unsigned w[2] = {0, 0};
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                w[k >> 2] |= ((unsigned)(unsigned char)df_decode_bit(d, byte & 1)) << (8 * (k & 3));
+                byte >>= 1;
+            }
+            *reinterpret_cast<uint2 *>(o + i) = make_uint2(w[0], w[1]);
+            i += 8;
+        }
+    }
+}
+
+// host: `n` entries of three u64 each at `d_list` (device), as DfListItem
+int dfpwm_decode_list(aukit_ctx *ctx, const unsigned char *src, const unsigned long long *d_list, uint32_t n, signed char *rows) {
+    if (!n) return AUKIT_OK;
+    hipLaunchKernelGGL(k_dfpwm_decode_list, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, src, reinterpret_cast<const DfListItem *>(d_list), n, rows);
+    AUKIT_HIP_CHECK(hipGetLastError());
+    return AUKIT_OK;
+}
+
 // Audio:dfpwm  aukit.lua:1005-1018 + encodePCM :874, in two steps: every sample is quantised to floor(d * (d < 0 and 128 or 127)) in
 // parallel (range-checked: the encoder raises outside [-128, 127]) into an int8 row in ENCODING order — interleaved, or channel
 // after channel (:1011-1014) — and the serial encoder (k_dfpwm_encode_i8, dfpwm_par.hip) then runs on bytes.  With the fp64 work

@@ -566,9 +566,10 @@ function aukit.au(data)                                                -- :1639
     return loader(c.desc, data, pcm_info(c.desc), tonumber(c.payload_off), tonumber(c.payload_len))
 end
 
--- a mixed library in one call (aukit_decode_resample_mixed): `files` = whole WAV / AIFF / AU files of any mix of rates, PCM formats / G.711 and
--- channel counts -> one Audio per file at `sampleRate`, mixed down unless `mono == false`; one upload, one launch.  Each Audio is its row of the
--- result, handed on as a one-stream audio of its own.
+-- a mixed library in one call (aukit_decode_resample_mixed): `files` = whole WAV / AIFF / AU files of any mix of rates, PCM formats / G.711 /
+-- DFPWM and channel counts -> one Audio per file at `sampleRate`, mixed down unless `mono == false`; one upload, one launch.  Each Audio is its
+-- row of the result, handed on as a one-stream audio of its own.  A raw .dfpwm file, which has no header, is given as a table
+-- {data, "dfpwm"[, channels[, sampleRate]]}: aukit.dfpwm's arguments.
 local MAGIC = {{"^RIFF....WAVE", 0}, {"^FORM....AIF[FC]", 1}, {"^%.snd", 2}}
 function aukit.load_many(files, sampleRate, interpolation, mono)
     expect(1, files, "table")
@@ -582,17 +583,28 @@ function aukit.load_many(files, sampleRate, interpolation, mono)
     local parts, infos = {}, {}
     for i = 1, n do
         local f = files[i]
+        if type(f) == "table" then
+            if type(f[1]) ~= "string" or f[2] ~= "dfpwm" or #f > 4 then error("bad argument #1 (file " .. (i - 1) .. ": expected {string, \"dfpwm\"[, channels[, sampleRate]]})", 2) end
+            if (f[3] ~= nil and (type(f[3]) ~= "number" or f[3] % 1 ~= 0)) or (f[4] ~= nil and type(f[4]) ~= "number") then
+                error("bad argument #1 (file " .. (i - 1) .. ": expected number for channels and sampleRate)", 2)
+            end
+            descs[i - 1] = desc {codec = "dfpwm", channels = f[3] or 1, sampleRate = f[4] or 48000}
+            parts[i] = f[1]
+            offs[i] = offs[i - 1] + #parts[i]
+            infos[i] = {bitDepth = 8, dataType = "signed"}   -- what aukit.dfpwm sets
+        else
         if type(f) ~= "string" then error("bad argument #1 (file " .. (i - 1) .. ": expected string)", 2) end
         local kind
         for _, m in ipairs(MAGIC) do if f:find(m[1]) then kind = m[2] break end end
         if not kind then error("file " .. (i - 1) .. ": not a WAV, AIFF or AU file", 2) end
         local c = ffi.new("aukit_container")
         if C.aukit_parse_container(ffi.cast("const uint8_t*", f), #f, kind, 0, c) ~= 0 then error("file " .. (i - 1) .. ": " .. ffi.string(C.aukit_last_error()), 2) end
-        if c.desc.codec > 1 then error("file " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: load_many takes PCM and G.711 (the block codecs keep their own loaders)", 2) end
+        if c.desc.codec > 1 and c.desc.codec ~= CODEC.dfpwm then error("file " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: load_many takes PCM, G.711 and DFPWM (the block codecs keep their own loaders)", 2) end
         descs[i - 1] = c.desc
         parts[i] = f:sub(tonumber(c.payload_off) + 1, tonumber(c.payload_off + c.payload_len))
         offs[i] = offs[i - 1] + #parts[i]
         infos[i] = kind == 0 and {dataType = WAVDT[c.wav_data_type], bitDepth = c.bit_depth} or pcm_info(c.desc)
+        end
     end
     local b = ffi.new("aukit_batch*[1]")
     check(C.aukit_batch_upload(ctx(), b, ffi.cast("const uint8_t*", table.concat(parts)), offs, n))
