@@ -763,6 +763,7 @@ int aukit_mix(aukit_ctx *ctx, const aukit_audio *const *audios, int count, doubl
 int aukit_encode_pcm(aukit_ctx *ctx, const aukit_audio *in, int bit_depth, int data_type, int interleaved, aukit_audio **out) {
     if (!ctx || !in || !out) return fail(AUKIT_E_ARG, "null argument");
     AUKIT_FLOAT_ONLY(in);
+    if (*out == in) return fail(AUKIT_E_ARG, "Audio:pcm cannot run in place");  // (audio_prepare would rewrite the input's layout before the kernel reads it)
     AUKIT_FLUSH(ctx, in);
     if (bit_depth != 8 && bit_depth != 16 && bit_depth != 24 && bit_depth != 32) return fail(AUKIT_E_ARG, "bad argument #2 (invalid bit depth)");
     if (data_type < 0 || data_type > 2) return fail(AUKIT_E_ARG, "bad argument #3 (invalid data type)");

@@ -543,6 +543,7 @@ int aukit_audio_upload(aukit_ctx *ctx, aukit_audio **out, const double *samples,
 
 int aukit_audio_clone(aukit_ctx *ctx, const aukit_audio *a, aukit_audio **out) {
     if (!ctx || !a || !out) return fail(AUKIT_E_ARG, "null argument");
+    if (*out == a) return fail(AUKIT_E_ARG, "clone cannot run in place");  // (audio_prepare would assign the audio's lengths from themselves)
     AUKIT_FLUSH(ctx, a);
     aukit_audio *b = *out;
     int rc = audio_prepare(ctx, &b, a->n, a->channels, a->rate, a->dtype, a->len.data());
