@@ -463,8 +463,10 @@ _MAGIC_KIND = {"wav": N.CONTAINER_WAV, "aiff": N.CONTAINER_AIFF, "au": N.CONTAIN
 
 def _sniff_many(files, stream=False):
     """load_many's host half, up to the device call: every file sniffed by magic as `detect` does and walked by aukit_parse_container
-    -> ([descriptor per file], [(first payload byte, byte count) per file], [info table per file]).  A file that is no WAV / AIFF / AU, or whose
-    payload is none of PCM, G.711 and DFPWM, raises LuaError naming the file's index (0-based, the position in `files`).
+    -> ([descriptor per file], [(first payload byte, byte count) per file], [info table per file]).  A file that is no WAV / AIFF / AU / QOA, or
+    whose payload is none of PCM, G.711 and DFPWM, raises LuaError naming the file's index (0-based, the position in `files`).
+    A QOA file (magic "qoaf") carries its channel count and sample rate in its own header: its payload is the whole file, its descriptor names the
+    codec only, and its info table is aukit.qoa's.  (IMA-ADPCM WAV files stay refused here; aukit_decode_resample_mixed itself takes their blocks.)
     An entry may also be a sequence (data, "dfpwm"[, channels[, sampleRate]]) — aukit.dfpwm's arguments, for raw .dfpwm files, which carry no
     header: the whole of `data` is the payload and the info table is aukit.dfpwm's.
     `stream`: the walk follows aukit.stream.wav / aiff / au's rules instead of the loaders' (`sowt`, AU's offset) — stream.many's host half; the
@@ -488,6 +490,13 @@ def _sniff_many(files, stream=False):
         if not isinstance(f, (bytes, bytearray, memoryview)):
             raise LuaError(f"bad argument #1 (file {i}: expected string)")
         kind = detect(bytes(f[:12]))[0]
+        if kind == "qoa":
+            if stream:
+                raise LuaError(f"file {i}: qoa payload: stream.many takes PCM and G.711 (the block codecs keep their own streams)")
+            descs.append(B.make_desc(N.CODEC_QOA))
+            ranges.append((0, len(f)))
+            infos.append({"bitDepth": 16, "dataType": "signed"})   # what aukit.qoa sets
+            continue
         if kind not in _MAGIC_KIND:
             raise LuaError(f"file {i}: not a WAV, AIFF or AU file")
         try:
@@ -499,7 +508,7 @@ def _sniff_many(files, stream=False):
             what = N.WAVDT[c.wav_data_type] if kind == "wav" else f"codec {d.codec}"
             if stream:
                 raise LuaError(f"file {i}: {what} payload: stream.many takes PCM and G.711 (the block codecs keep their own streams)")
-            raise LuaError(f"file {i}: {what} payload: load_many takes PCM, G.711 and DFPWM (the block codecs keep their own loaders)")
+            raise LuaError(f"file {i}: {what} payload: load_many takes PCM, G.711, DFPWM and QOA files (the block codecs keep their own loaders; the batch API takes IMA blocks)")
         descs.append(d)
         ranges.append((int(c.payload_off), int(c.payload_len)))
         if stream:
@@ -549,11 +558,11 @@ class _RowView(B.AudioBatch):
 
 
 def load_many(files, sampleRate=None, interpolation=None, mono=None):
-    """aukit.wav / aukit.aiff / aukit.au (file):resample(sampleRate, interpolation) [:mono()] for a LIST of whole files of any mix of containers,
-    rates, PCM formats / G.711 / DFPWM and channel counts: the payload ranges go up as one batch, one aukit_decode_resample_mixed call resamples
-    (and, by default, mixes down) all of them, and one Audio per file comes back, in input order, each a view of its row of the result.  Without
-    `mono` the files must agree in channel count.  A raw .dfpwm file, which has no header, is given as (data, "dfpwm"[, channels[, sampleRate]]):
-    aukit.dfpwm's arguments."""
+    """aukit.wav / aukit.aiff / aukit.au / aukit.qoa (file):resample(sampleRate, interpolation) [:mono()] for a LIST of whole files of any mix of
+    containers, rates, PCM formats / G.711 / DFPWM / QOA and channel counts: the payload ranges go up as one batch, one aukit_decode_resample_mixed
+    call resamples (and, by default, mixes down) all of them, and one Audio per file comes back, in input order, each a view of its row of the
+    result.  Without `mono` the files must agree in channel count.  A raw .dfpwm file, which has no header, is given as
+    (data, "dfpwm"[, channels[, sampleRate]]): aukit.dfpwm's arguments.  A .qoa file goes up whole."""
     sampleRate = 48000 if sampleRate is None else _expect(2, sampleRate, "number")
     interpolation = interpolation if interpolation is not None else defaultInterpolation
     ip = _interp(interpolation, 3)

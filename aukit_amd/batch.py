@@ -465,9 +465,11 @@ def decode_resample(ctx, batch, desc, new_rate, interp, dtype=None, out=None):
 
 
 def decode_resample_mixed(ctx, batch, descs, new_rate, interp, mono=False, dtype=None, out=None):
-    """aukit_decode_resample_mixed: stream s is decoded with descs[s] (PCM of any format, G.711 or DFPWM, any rate), resampled to `new_rate` and,
-    with `mono`, mixed down — one call, one resample launch (behind a decode pre-pass when the batch holds DFPWM streams), one AudioBatch at
-    `new_rate` in the batch's order.  `descs`: one CodecDesc per stream."""
+    """aukit_decode_resample_mixed: stream s is decoded with descs[s] (PCM of any format, G.711, DFPWM, a whole QOA file or the IMA-ADPCM blocks of
+    a WAV file, any rate), resampled to `new_rate` and, with `mono`, mixed down — one call, one resample launch (behind decode pre-passes when the
+    batch holds DFPWM, QOA or IMA-ADPCM streams), one AudioBatch at `new_rate` in the batch's order.  `descs`: one CodecDesc per stream —
+    make_desc(N.CODEC_QOA) for a QOA file (channel count and rate are its header's), make_desc(N.CODEC_ADPCM_WAV, channels, rate, block_align=...)
+    for IMA blocks.  Every refusal, those only the device can detect included, comes before `out` is touched."""
     out = out if out is not None else AudioBatch(ctx)
     arr = (N.CodecDesc * max(len(descs), 1))()
     for i, d in enumerate(descs):

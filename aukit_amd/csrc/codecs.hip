@@ -815,6 +815,79 @@ __global__ __launch_bounds__(64, 3) void k_ima_lanes(const ImaLaneParams P) {
     }
 }
 
+// aukit.wav's IMA blocks for aukit_decode_resample_mixed (resample_mixed.hip): one LANE per (stream, channel, block) again, but every job carries its
+// own geometry — the streams of a mixed library differ in blockAlign and channel count, so neighbouring lanes of a wave may walk blocks of different
+// sizes and nothing but the tables is uniform across the launch.  The inner loop is k_ima_lanes' (the 89 x 8 diff table in LDS, the index delta from a
+// constant's bit-field, clampi); a word's eight predictors leave as one ordinary 16-byte store (rows, and a block's samples within them, start at
+// multiples of eight samples: (blockAlign - 4 C) * 2 / C is one for every blockAlign the host admits).  The line staging of k_ima_lanes is not here.
+//   one channel : the header's step index is masked with 0x0F (:1544) and cannot leave the table; a stream's last block may be short (:1545);
+//   two channels: words alternate, left then right, behind an 8-byte header (:1513-1540); a step index beyond 88 (expect.range(step_index, 0, 88)) puts the
+//     stream's index into *flag by an atomic minimum — the lowest offending stream is the one the host names — and the lane writes nothing.
+struct ImaMixJob {
+    unsigned long long src_off;   // the block's first byte, relative to the batch's data
+    unsigned long long row_off;   // the block's first sample of this channel, int16 elements from `rows`
+    unsigned nbytes;              // bytes in the block (blockAlign; less for a one-channel stream's last block)
+    unsigned stream;
+    int c, channels;
+};
+static_assert(sizeof(ImaMixJob) == 32, "ImaMixJob layout");
+__global__ __launch_bounds__(64) void k_ima_mixed(const unsigned char *src, const ImaMixJob *jobs, unsigned long long njobs, short *rows, unsigned *flag) {
+    __shared__ int lut[89 * 8];
+    const int lane = threadIdx.x;
+    for (int i = lane; i < 89 * 8; i += 64) { const int st = c_ima_step[i >> 3]; lut[i] = (int)(((unsigned)(i & 7) * (unsigned)st) >> 2) + (st >> 3); }   // :2809 (Q5)
+    __syncthreads();
+    const unsigned long long g = (unsigned long long)blockIdx.x * 64 + (unsigned)lane;
+    if (g >= njobs) return;
+    const ImaMixJob job = jobs[g];
+    const unsigned C = (unsigned)job.channels, hdr = 4u * C;
+    if (job.nbytes < 3u) return;   // (the host refuses such a block: kept so that no header byte is read that is not there)
+    const unsigned char *blk = src + job.src_off;
+    int pred = (short)((unsigned)blk[4 * job.c] | (unsigned)blk[4 * job.c + 1] << 8);
+    int idx = blk[4 * job.c + 2];
+    if (C == 1u) idx &= 0x0F;                                             // :1544
+    else if (idx > 88) { atomicMin(flag, job.stream); return; }           // expect.range(step_index, 0, 88)
+    int idx32 = idx * 32;
+    const unsigned nb = job.nbytes > hdr ? (job.nbytes - hdr) * 2u / C : 0u;   // samples of this channel: str_sub is simply shorter (:1545)
+    const unsigned nwf = nb >> 3, rag = nb & 7u;
+    typedef unsigned u32u __attribute__((aligned(1)));
+    typedef unsigned v4ua __attribute__((ext_vector_type(4)));
+    const unsigned char *wp = blk + hdr + 4 * job.c;   // this channel's words: 4 C bytes apart, which is `hdr` too
+    const char *const lutb = reinterpret_cast<const char *>(lut);
+    short *const o = rows + job.row_off;
+    auto word = [&](unsigned w) -> v4ua {   // eight nibbles, low nibble first (:1546 / :2803-2806) -> eight predictors
+        int pv[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const unsigned sh = __builtin_amdgcn_ubfe(w, 4 * k, 3) << 2;                                   // 4 (n & 7)
+            const int diff = *reinterpret_cast<const int *>(lutb + (unsigned)idx32 + sh);                  // :2807, :2809
+            const int sg = __builtin_amdgcn_sbfe((int)w, 4 * k + 3, 1);                                    // n & 8: all ones
+            pred = clampi(pred + ((diff ^ sg) - sg), -32768, 32767);                                       // :2810-2811
+            const int dd = (int)__builtin_amdgcn_ubfe(0x97530000u, sh, 4);                                 // index delta + 1: {0,0,0,0,3,5,7,9}
+            idx32 = clampi(idx32 + (dd << 5) - 32, 0, 88 * 32);                                            // :2808
+            pv[k] = pred;
+        }
+        return v4ua{__builtin_amdgcn_perm((unsigned)pv[1], (unsigned)pv[0], 0x05040100u), __builtin_amdgcn_perm((unsigned)pv[3], (unsigned)pv[2], 0x05040100u),
+                    __builtin_amdgcn_perm((unsigned)pv[5], (unsigned)pv[4], 0x05040100u), __builtin_amdgcn_perm((unsigned)pv[7], (unsigned)pv[6], 0x05040100u)};
+    };
+    for (unsigned w = 0; w < nwf; w++) *reinterpret_cast<v4ua *>(o + 8u * w) = word(*reinterpret_cast<const u32u *>(wp + (size_t)w * hdr));
+    if (rag) {   // a one-channel stream's short last block: rag / 2 bytes of a part word
+        const unsigned char *q = wp + (size_t)nwf * hdr;
+        unsigned pw = 0;
+        for (unsigned i = 0; i < rag / 2; i++) pw |= (unsigned)q[i] << (8 * i);
+        const v4ua v = word(pw);
+        const unsigned e[4] = {v.x, v.y, v.z, v.w};
+        for (unsigned k = 0; k < rag; k++) o[8u * nwf + k] = (short)(e[k >> 1] >> (16 * (k & 1)));
+    }
+}
+int ima_mixed_decode(aukit_ctx *ctx, const unsigned char *src, const void *d_jobs, uint64_t njobs, short *rows, unsigned *flag, uint64_t bytes) {
+    if (!njobs) return AUKIT_OK;
+    int rc = ctx_begin_kernel(ctx);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_ima_mixed, dim3((unsigned)((njobs + 63) / 64)), dim3(64), 0, ctx->stream, src, reinterpret_cast<const ImaMixJob *>(d_jobs), (unsigned long long)njobs, rows, flag);
+    AUKIT_HIP_CHECK(hipGetLastError());
+    return ctx_end_kernel(ctx, "k_ima_mixed", bytes);
+}
+
 // stream.adpcm  aukit.lua:2788-2831: wave per block, decoded block kept in LDS as the reference's doubles, resampled in place
 struct ImaStreamParams {
     const unsigned char *src;

@@ -100,13 +100,16 @@ static AUKIT_DEV QoaCallWalk qoa_walk_call(const unsigned char *h, unsigned long
     return w;
 }
 
-template <bool FILL>
+// IDX: the walk's streams are a LIST of the batch's (`list[s]`: the mixed-library call, whose other streams are not QOA and are not walked); the words
+// of both passes are per list entry, the jobs' frame offsets the batch's.
+template <bool FILL, bool IDX = false>
 __global__ __launch_bounds__(64) void k_qoa_walk(const unsigned char *src, const unsigned long long *off, unsigned n, int mode, QoaWalkOut *wo,
-                                                const QoaFillIn *fin, QoaJob *jobs, QoaCallRec *calls) {
+                                                const QoaFillIn *fin, QoaJob *jobs, QoaCallRec *calls, const unsigned *list) {
     const unsigned s = blockIdx.x * 64 + threadIdx.x;
     if (s >= n) return;
-    const unsigned char *h = src + off[s];
-    const unsigned long long nb = off[s + 1] - off[s];
+    const unsigned g = IDX ? list[s] : s;   // the stream of the batch
+    const unsigned char *h = src + off[g];
+    const unsigned long long nb = off[g + 1] - off[g];
     QoaWalkOut o;
     for (int i = 0; i < 12; i++) o.head[i] = (unsigned long long)i < nb ? h[i] : 0;
     o.ncalls = 0; o.raised = 0; o.big = 0; o.pad = 0; o.njobs = 0; o.rows_total = 0; o.L = 0;
@@ -130,7 +133,7 @@ __global__ __launch_bounds__(64) void k_qoa_walk(const unsigned char *src, const
                         const bool lastf = ++k == nfr;
                         for (int c = 0; c < fc; c++) {
                             QoaJob j;
-                            j.frame_off = off[s] + fpos; j.out_off = rat + (unsigned long long)c * stride + sp;
+                            j.frame_off = off[g] + fpos; j.out_off = rat + (unsigned long long)c * stride + sp;
                             j.c = c; j.channels = fc; j.samples = samples;
                             j.emit = lastf ? ((samples + 19) / 20) * 20 : samples;   // Q15: the ≤19-sample tail survives only after the last frame of a table
                             jobs[jat++] = j;
@@ -297,17 +300,26 @@ struct QoaStreamInfo { int channels; double rate, file_samples; bool raised, big
 
 // pass 1 of the device walk; validates the file headers like the reference (errors with its strings)
 // (wb: where the walks keep their words — tmp_buf3, or the call's set of ctx->qoa_set when they run on the look-ahead stream: stream_qoa)
-static int qoa_walk_count(aukit_ctx *ctx, const aukit_batch *in, int mode, std::vector<QoaStreamInfo> &S, DevBuf *wb = nullptr) {
-    const uint32_t n = in->n;
+// (list: the streams to walk, where they are not the whole batch — its device copy goes behind the walks' words and serves the fill pass too; a
+// refusal then leaves the refused entry's position in *bad)
+static int qoa_walk_count(aukit_ctx *ctx, const aukit_batch *in, int mode, std::vector<QoaStreamInfo> &S, DevBuf *wb = nullptr, const std::vector<uint32_t> *list = nullptr,
+                          uint32_t *bad = nullptr) {
+    const uint32_t n = list ? (uint32_t)list->size() : in->n;
     S.assign(n, QoaStreamInfo{});
     if (!n) return AUKIT_OK;
     DevBuf &W = wb ? *wb : ctx_scratch3(ctx);
-    int rc = W.ensure((size_t)n * (sizeof(QoaWalkOut) + sizeof(QoaFillIn)) + 64);
+    int rc = W.ensure((size_t)n * (sizeof(QoaWalkOut) + sizeof(QoaFillIn) + (list ? sizeof(unsigned) : 0)) + 64);
     if (rc) return rc;
     QoaWalkOut *dwo = reinterpret_cast<QoaWalkOut *>(W.p);
     const unsigned long long *doff = reinterpret_cast<const unsigned long long *>(in->d_off);
+    if (list) {
+        unsigned *dlist = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(W.p) + (size_t)n * (sizeof(QoaWalkOut) + sizeof(QoaFillIn)));
+        if ((rc = h2d_table(ctx, dlist, list->data(), (size_t)n * sizeof(unsigned)))) return rc;
+        hipLaunchKernelGGL((k_qoa_walk<false, true>), dim3((n + 63) / 64), dim3(64), 0, ctx->stream, in->data(), doff, n, mode, dwo, static_cast<const QoaFillIn *>(nullptr),
+                           static_cast<QoaJob *>(nullptr), static_cast<QoaCallRec *>(nullptr), dlist);
+    } else
     hipLaunchKernelGGL((k_qoa_walk<false>), dim3((n + 63) / 64), dim3(64), 0, ctx->stream, in->data(), doff, n, mode, dwo, static_cast<const QoaFillIn *>(nullptr),
-                       static_cast<QoaJob *>(nullptr), static_cast<QoaCallRec *>(nullptr));
+                       static_cast<QoaJob *>(nullptr), static_cast<QoaCallRec *>(nullptr), static_cast<const unsigned *>(nullptr));
     AUKIT_HIP_CHECK(hipGetLastError());
     // (read-backs go through the context's pinned staging buffer: a pageable destination makes the runtime pin it on the fly — 26 ms per
     // call for a megabyte, measured, against 0.4 ms)
@@ -320,8 +332,10 @@ static int qoa_walk_count(aukit_ctx *ctx, const aukit_batch *in, int mode, std::
     }
     uint64_t jat = 0, cat = 0, rat = 0;
     for (uint32_t s = 0; s < n; s++) {
-        const uint64_t nb = in->off[s + 1] - in->off[s];
+        const uint32_t g = list ? (*list)[s] : s;
+        const uint64_t nb = in->off[g + 1] - in->off[g];
         const unsigned char *h = wo[s].head;
+        if (bad) *bad = s;
         // aukit.qoa: (">c4I4"):unpack / (">BI3"):unpack on a short string raise; stream.qoa: assert(read(8), ...) / assert(peek(4), ...)
         if (nb < 8) return fail(AUKIT_E_LUA, mode == 0 ? "data string too short" : "Not a QOA file");
         if (memcmp(h, "qoaf", 4) != 0) return fail(AUKIT_E_ARG, "Not a QOA file");
@@ -342,8 +356,9 @@ static int qoa_walk_count(aukit_ctx *ctx, const aukit_batch *in, int mode, std::
 }
 
 // pass 2: the decode jobs into `djobs` (device), the call records to the host (stream mode: want_calls)
-static int qoa_walk_fill(aukit_ctx *ctx, const aukit_batch *in, int mode, const std::vector<QoaStreamInfo> &S, QoaJob *djobs, uint64_t ncalls, std::vector<QoaCallRec> *calls, DevBuf *wb = nullptr, DevBuf *cb = nullptr) {
-    const uint32_t n = in->n;
+static int qoa_walk_fill(aukit_ctx *ctx, const aukit_batch *in, int mode, const std::vector<QoaStreamInfo> &S, QoaJob *djobs, uint64_t ncalls, std::vector<QoaCallRec> *calls, DevBuf *wb = nullptr, DevBuf *cb = nullptr,
+                         bool listed = false) {
+    const uint32_t n = (uint32_t)S.size();   // (the batch's streams, or the list qoa_walk_count left behind the words)
     std::vector<QoaFillIn> fin(n);
     for (uint32_t s = 0; s < n; s++) fin[s] = QoaFillIn{S[s].job_first, S[s].call_first, S[s].row_base, S[s].stride};
     QoaFillIn *dfin = reinterpret_cast<QoaFillIn *>(reinterpret_cast<QoaWalkOut *>((wb ? *wb : ctx_scratch3(ctx)).p) + n);
@@ -352,8 +367,12 @@ static int qoa_walk_fill(aukit_ctx *ctx, const aukit_batch *in, int mode, const 
     int rc = CB.ensure((size_t)std::max<uint64_t>(ncalls, 1) * sizeof(QoaCallRec) + 64);
     if (rc) return rc;
     QoaCallRec *dcalls = reinterpret_cast<QoaCallRec *>(CB.p);
+    if (listed)
+        hipLaunchKernelGGL((k_qoa_walk<true, true>), dim3((n + 63) / 64), dim3(64), 0, ctx->stream, in->data(), reinterpret_cast<const unsigned long long *>(in->d_off), n, mode,
+                           static_cast<QoaWalkOut *>(nullptr), dfin, djobs, dcalls, reinterpret_cast<const unsigned *>(dfin + n));
+    else
     hipLaunchKernelGGL((k_qoa_walk<true>), dim3((n + 63) / 64), dim3(64), 0, ctx->stream, in->data(), reinterpret_cast<const unsigned long long *>(in->d_off), n, mode,
-                       static_cast<QoaWalkOut *>(nullptr), dfin, djobs, dcalls);
+                       static_cast<QoaWalkOut *>(nullptr), dfin, djobs, dcalls, static_cast<const unsigned *>(nullptr));
     AUKIT_HIP_CHECK(hipGetLastError());
     if (calls) {
         calls->resize(ncalls);
@@ -401,6 +420,41 @@ int decode_qoa_audio(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_de
     if ((rc = qoa_decode_launch<false>(ctx, in, djobs, njobs, ctx->tmp_buf.p, tot * 2))) return rc;
     return audio_from_int_rows(ctx, SRC_I16, ctx->tmp_buf.p, row_off, row_len, in->n, C, rate, new_rate, interp, do_resample, dtype, 32767, 32768, out);
 }
+
+// The QOA pre-pass of aukit_decode_resample_mixed (resample_mixed.hip): aukit.qoa's walks and decoder on the streams `list` names and on no other
+// stream of the batch.  Two halves, because the call sizes its scratch between them:
+//   qoa_mixed_count: the count pass and the header read-back; refuses what decode_qoa_audio refuses of a header, with its words (*bad: which entry);
+//   qoa_mixed_decode: the fill pass with the caller's row bases (int16 elements from `rows`; a stream's channel c at row_base + c * stride, stride =
+//     round_up(max(L, 1), 8), as decode_qoa_audio lays its rows out), then k_qoa_wave<false>.  `djobs`: room for the jobs the count pass reported.
+// What no job writes is what decode_qoa_audio leaves there too: the jobs are the same (Q15: emit beyond `samples` only for a table's last frame).
+struct QoaMixedStream { int channels; double rate; uint64_t L, njobs; bool raised, big; };
+int qoa_mixed_count(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<QoaMixedStream> &Q, uint32_t *bad) {
+    std::vector<QoaStreamInfo> S;
+    const int rc = qoa_walk_count(ctx, in, 0, S, nullptr, &list, bad);
+    if (rc) return rc;
+    Q.resize(S.size());
+    for (size_t s = 0; s < S.size(); s++) Q[s] = QoaMixedStream{S[s].channels, S[s].rate, S[s].L, S[s].njobs, S[s].raised, S[s].big};
+    return AUKIT_OK;
+}
+int qoa_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<QoaMixedStream> &Q, const uint64_t *row_base, short *rows, void *djobs, uint64_t src_bytes) {
+    std::vector<QoaStreamInfo> S(Q.size());
+    uint64_t jat = 0, row_elems = 0;
+    for (size_t s = 0; s < Q.size(); s++) {
+        QoaStreamInfo &q = S[s];
+        q.channels = Q[s].channels; q.rate = Q[s].rate; q.L = Q[s].L; q.njobs = Q[s].njobs; q.ncalls = 1;
+        q.stride = round_up(std::max<uint64_t>(q.L, 1), 8);
+        q.rows_total = q.stride * (uint64_t)q.channels;
+        q.job_first = jat; q.call_first = s; q.row_base = row_base[s];
+        jat += q.njobs; row_elems += q.rows_total;
+    }
+    int rc = qoa_walk_fill(ctx, in, 0, S, reinterpret_cast<QoaJob *>(djobs), S.size(), nullptr, nullptr, nullptr, true);
+    if (rc || !jat) return rc;
+    if ((rc = ctx_begin_kernel(ctx))) return rc;
+    hipLaunchKernelGGL((k_qoa_wave<false>), dim3((unsigned)((jat + 63) / 64)), dim3(64), 0, ctx->stream, in->data(), reinterpret_cast<const QoaJob *>(djobs), (unsigned long long)jat, rows);
+    AUKIT_HIP_CHECK(hipGetLastError());
+    return ctx_end_kernel(ctx, "k_qoa_wave", src_bytes + row_elems * 2);
+}
+size_t qoa_mixed_job_bytes(uint64_t njobs) { return (size_t)std::max<uint64_t>(njobs, 1) * sizeof(QoaJob) + 64; }
 
 // aukit.stream.qoa(data, mono)  aukit.lua:3202-3337
 int stream_qoa(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d, int interp, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks_out) {

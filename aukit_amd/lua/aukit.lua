@@ -566,10 +566,11 @@ function aukit.au(data)                                                -- :1639
     return loader(c.desc, data, pcm_info(c.desc), tonumber(c.payload_off), tonumber(c.payload_len))
 end
 
--- a mixed library in one call (aukit_decode_resample_mixed): `files` = whole WAV / AIFF / AU files of any mix of rates, PCM formats / G.711 /
--- DFPWM and channel counts -> one Audio per file at `sampleRate`, mixed down unless `mono == false`; one upload, one launch.  Each Audio is its
+-- a mixed library in one call (aukit_decode_resample_mixed): `files` = whole WAV / AIFF / AU / QOA files of any mix of rates, PCM formats / G.711 /
+-- DFPWM / QOA and channel counts -> one Audio per file at `sampleRate`, mixed down unless `mono == false`; one upload, one launch.  Each Audio is its
 -- row of the result, handed on as a one-stream audio of its own.  A raw .dfpwm file, which has no header, is given as a table
--- {data, "dfpwm"[, channels[, sampleRate]]}: aukit.dfpwm's arguments.
+-- {data, "dfpwm"[, channels[, sampleRate]]}: aukit.dfpwm's arguments.  A .qoa file (magic "qoaf") goes up whole: its header carries its channel
+-- count and sample rate.  IMA-ADPCM WAV files stay refused here (the batch API, aukit_decode_resample_mixed with AUKIT_CODEC_ADPCM_WAV, takes them).
 local MAGIC = {{"^RIFF....WAVE", 0}, {"^FORM....AIF[FC]", 1}, {"^%.snd", 2}}
 function aukit.load_many(files, sampleRate, interpolation, mono)
     expect(1, files, "table")
@@ -594,16 +595,23 @@ function aukit.load_many(files, sampleRate, interpolation, mono)
             infos[i] = {bitDepth = 8, dataType = "signed"}   -- what aukit.dfpwm sets
         else
         if type(f) ~= "string" then error("bad argument #1 (file " .. (i - 1) .. ": expected string)", 2) end
+        if f:sub(1, 4) == "qoaf" then   -- the whole file is the payload; the info table is aukit.qoa's
+            descs[i - 1] = desc {codec = "qoa"}
+            parts[i] = f
+            offs[i] = offs[i - 1] + #f
+            infos[i] = {bitDepth = 16, dataType = "signed"}
+        else
         local kind
         for _, m in ipairs(MAGIC) do if f:find(m[1]) then kind = m[2] break end end
         if not kind then error("file " .. (i - 1) .. ": not a WAV, AIFF or AU file", 2) end
         local c = ffi.new("aukit_container")
         if C.aukit_parse_container(ffi.cast("const uint8_t*", f), #f, kind, 0, c) ~= 0 then error("file " .. (i - 1) .. ": " .. ffi.string(C.aukit_last_error()), 2) end
-        if c.desc.codec > 1 and c.desc.codec ~= CODEC.dfpwm then error("file " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: load_many takes PCM, G.711 and DFPWM (the block codecs keep their own loaders)", 2) end
+        if c.desc.codec > 1 and c.desc.codec ~= CODEC.dfpwm then error("file " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: load_many takes PCM, G.711, DFPWM and QOA files (the block codecs keep their own loaders; the batch API takes IMA blocks)", 2) end
         descs[i - 1] = c.desc
         parts[i] = f:sub(tonumber(c.payload_off) + 1, tonumber(c.payload_off + c.payload_len))
         offs[i] = offs[i - 1] + #parts[i]
         infos[i] = kind == 0 and {dataType = WAVDT[c.wav_data_type], bitDepth = c.bit_depth} or pcm_info(c.desc)
+        end
         end
     end
     local b = ffi.new("aukit_batch*[1]")

@@ -222,16 +222,28 @@ int aukit_decode(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *
  * aukit_decode followed by aukit_resample. */
 int aukit_decode_resample(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *desc, double new_rate, int interp,
                           int dtype, aukit_audio **out);
-/* aukit.pcm / aukit.g711 / aukit.dfpwm (data_s, <descs[s]>):resample(new_rate, interp) [:mono()] for every stream s, each with its OWN descriptor
- * (aukit.lua:1049-1171, :1361-1390, :1399-1413, :653-673, :677-689).  One audio out: `new_rate`, one channel if `mono`, else the common channel
- * count.  Stream s of the result is what aukit_decode_resample gives for a one-stream batch of its bytes with descs[s] (followed by aukit_mono when
- * `mono` is set: ((0 + ch1) + ch2 ...) / cn on the clamped, resampled values) — fp64 in the reference's order whatever the storage type,
- * AUKIT_F32 rounds once, at the store.  AUKIT_CODEC_PCM (every format aukit_decode takes, planar and big-endian included), AUKIT_CODEC_G711 and
- * AUKIT_CODEC_DFPWM (`channels`, `sample_rate`; the reference's 6001-byte slices advanced by 6000 included: a pre-pass decodes these streams to
- * int8 rows in the context's scratch, which the one resample launch reads) only, interpolation none / linear / cubic; anything else is
- * AUKIT_E_UNSUPPORTED by name.  n_descs must be the batch's stream count; without `mono` the descriptors must agree in channel count
- * (AUKIT_E_ARG).  A stream whose own call would fail fails the whole call with that status and message, the stream's index appended, before
- * anything is allocated or launched. */
+/* aukit.pcm / aukit.g711 / aukit.dfpwm / aukit.qoa / aukit.wav's IMA-ADPCM blocks (data_s, <descs[s]>):resample(new_rate, interp) [:mono()] for every
+ * stream s, each with its OWN descriptor (aukit.lua:1049-1171, :1361-1390, :1399-1413, :1706-1777, :1509-1548, :653-673, :677-689).  One audio out:
+ * `new_rate`, one channel if `mono`, else the common channel count.  Stream s of the result is what aukit_decode_resample gives for a one-stream batch
+ * of its bytes with descs[s] (followed by aukit_mono when `mono` is set: ((0 + ch1) + ch2 ...) / cn on the clamped, resampled values) — fp64 in the
+ * reference's order whatever the storage type, AUKIT_F32 rounds once, at the store.  Five codecs are served:
+ *   AUKIT_CODEC_PCM       every format aukit_decode takes, planar and big-endian included;
+ *   AUKIT_CODEC_G711      `channels`, `sample_rate`, `ulaw`;
+ *   AUKIT_CODEC_DFPWM     `channels`, `sample_rate`; the reference's 6001-byte slices advanced by 6000 included: a pre-pass decodes these streams to
+ *                         int8 rows in the context's scratch, which the one resample launch reads;
+ *   AUKIT_CODEC_QOA       only `codec` is read: the stream is a whole .qoa file, and its channel count and sample rate are its header's (without
+ *                         `mono` it is the header's channel count that must agree with the other streams').  A pre-pass walks and decodes the QOA
+ *                         streams — and no other stream's bytes — to int16 rows in the context's scratch.  One exception to "what the stream's own
+ *                         call gives": a file with a frame of more than 8192 samples, which aukit_decode_resample decodes on the host, is
+ *                         AUKIT_E_UNSUPPORTED here;
+ *   AUKIT_CODEC_ADPCM_WAV the `data` chunk of an IMA-ADPCM WAV file: `channels` (1 or 2), `sample_rate` and `block_align`, each the stream's own.  A
+ *                         pre-pass decodes every block, a lane each, to int16 rows beside the QOA streams'.
+ * Interpolation none / linear / cubic; any other codec or interpolation is AUKIT_E_UNSUPPORTED by name.  n_descs must be the batch's stream count;
+ * without `mono` the streams must agree in channel count (AUKIT_E_ARG).  A stream whose own call would fail fails the whole call with that status
+ * and message, the stream's index appended.  Ordering: everything that can refuse does so before `*out` is touched — the descriptor and length
+ * checks of the host, and what only the device can tell (a QOA walk's verdict, a two-channel IMA block whose step index is beyond 88): the QOA and
+ * IMA pre-passes write context scratch only, and they run, and their verdicts are read back, first.  A refused call leaves `*out` and its samples as
+ * they were. */
 int aukit_decode_resample_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs /* n */, uint32_t n_descs,
                                 double new_rate, int interp, int mono, int dtype, aukit_audio **out);
 
