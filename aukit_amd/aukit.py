@@ -461,7 +461,7 @@ def au(data):  # aukit.lua:1639
 _MAGIC_KIND = {"wav": N.CONTAINER_WAV, "aiff": N.CONTAINER_AIFF, "au": N.CONTAINER_AU}
 
 
-def _sniff_many(files, stream=False):
+def _sniff_many(files, stream=False, stream_dfpwm=False):
     """load_many's host half, up to the device call: every file sniffed by magic as `detect` does and walked by aukit_parse_container
     -> ([descriptor per file], [(first payload byte, byte count) per file], [info table per file]).  A file that is no WAV / AIFF / AU / QOA, or
     whose payload is none of PCM, G.711 and DFPWM, raises LuaError naming the file's index (0-based, the position in `files`).
@@ -470,8 +470,12 @@ def _sniff_many(files, stream=False):
     An entry may also be a sequence (data, "dfpwm"[, channels[, sampleRate]]) — aukit.dfpwm's arguments, for raw .dfpwm files, which carry no
     header: the whole of `data` is the payload and the info table is aukit.dfpwm's.
     `stream`: the walk follows aukit.stream.wav / aiff / au's rules instead of the loaders' (`sowt`, AU's offset) — stream.many's host half; the
-    third list then holds what the container says the length is, in seconds (NaN where the stream factory's own figure stands)."""
+    third list then holds what the container says the length is, in seconds (NaN where the stream factory's own figure stands).
+    `stream_dfpwm` (with `stream`): DFPWM WAV files and raw (data, "dfpwm", ...) entries are taken too, as aukit.stream.many takes them — a WAV's
+    length is the container's, a raw entry's is NaN (aukit.stream.dfpwm's own figure, #data * 8 / sampleRate / channels, stands).  Without it they
+    are refused by index, as before aukit_stream_decode_mixed took the codec."""
     _expect(1, files, "table")
+    takes = "PCM, G.711 and DFPWM" if stream_dfpwm else "PCM and G.711"
     descs, ranges, infos = [], [], []
     for i, f in enumerate(files):
         if isinstance(f, (list, tuple)):
@@ -481,18 +485,18 @@ def _sniff_many(files, stream=False):
             for v, integral in ((ch, True), (rate, False)):
                 if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or (integral and v != int(v))):
                     raise LuaError(f"bad argument #1 (file {i}: expected number for channels and sampleRate)")
-            if stream:
+            if stream and not stream_dfpwm:
                 raise LuaError(f"file {i}: dfpwm payload: stream.many takes PCM and G.711 (the block codecs keep their own streams)")
             descs.append(B.make_desc(N.CODEC_DFPWM, 1 if ch is None else int(ch), 48000 if rate is None else rate))
             ranges.append((0, len(f[0])))
-            infos.append({"bitDepth": 8, "dataType": "signed"})   # what aukit.dfpwm sets
+            infos.append(float("nan") if stream else {"bitDepth": 8, "dataType": "signed"})   # what aukit.dfpwm sets
             continue
         if not isinstance(f, (bytes, bytearray, memoryview)):
             raise LuaError(f"bad argument #1 (file {i}: expected string)")
         kind = detect(bytes(f[:12]))[0]
         if kind == "qoa":
             if stream:
-                raise LuaError(f"file {i}: qoa payload: stream.many takes PCM and G.711 (the block codecs keep their own streams)")
+                raise LuaError(f"file {i}: qoa payload: stream.many takes {takes} (the block codecs keep their own streams)")
             descs.append(B.make_desc(N.CODEC_QOA))
             ranges.append((0, len(f)))
             infos.append({"bitDepth": 16, "dataType": "signed"})   # what aukit.qoa sets
@@ -504,10 +508,10 @@ def _sniff_many(files, stream=False):
         except LuaError as e:
             raise LuaError(f"file {i}: {e}") from None
         d = _desc_copy(c)
-        if d.codec not in ((N.CODEC_PCM, N.CODEC_G711) if stream else (N.CODEC_PCM, N.CODEC_G711, N.CODEC_DFPWM)):
+        if d.codec not in ((N.CODEC_PCM, N.CODEC_G711) if stream and not stream_dfpwm else (N.CODEC_PCM, N.CODEC_G711, N.CODEC_DFPWM)):
             what = N.WAVDT[c.wav_data_type] if kind == "wav" else f"codec {d.codec}"
             if stream:
-                raise LuaError(f"file {i}: {what} payload: stream.many takes PCM and G.711 (the block codecs keep their own streams)")
+                raise LuaError(f"file {i}: {what} payload: stream.many takes {takes} (the block codecs keep their own streams)")
             raise LuaError(f"file {i}: {what} payload: load_many takes PCM, G.711, DFPWM and QOA files (the block codecs keep their own loaders; the batch API takes IMA blocks)")
         descs.append(d)
         ranges.append((int(c.payload_off), int(c.payload_len)))
@@ -796,14 +800,16 @@ class _StreamNS:
         return it, (length if math.isnan(c.length_seconds) else c.length_seconds)
 
     def many(self, files, mono=None):
-        """aukit.stream.wav / aiff / au (file, mono) for a LIST of whole files of any mix of containers, rates, PCM formats / G.711 and channel
-        counts: the payload ranges go up as one batch, one aukit_stream_decode_mixed call computes every iterator call of every file, and a list
-        of (iterator, length) pairs comes back in input order, each what the file's own factory returns (stream.g711's endless empty chunks
-        and the raise behind a stream that ends inside the prefill included).  Without `mono` the files must agree in channel count."""
+        """aukit.stream.wav / aiff / au (file, mono) for a LIST of whole files of any mix of containers, rates, PCM formats / G.711 / DFPWM and
+        channel counts: the payload ranges go up as one batch, one aukit_stream_decode_mixed call computes every iterator call of every file, and
+        a list of (iterator, length) pairs comes back in input order, each what the file's own factory returns (stream.g711's endless empty
+        chunks and the raise behind a stream that ends inside the prefill included).  Without `mono` the files must agree in channel count.
+        A raw .dfpwm file, which has no header, is given as (data, "dfpwm"[, channels[, sampleRate]]) — load_many's tuple, channels first — and
+        its pair is aukit.stream.dfpwm(data, sampleRate, channels, mono)'s."""
         _expect(2, mono, "boolean", "nil")
-        descs, ranges, lengths = _sniff_many(files, stream=True)
+        descs, ranges, lengths = _sniff_many(files, stream=True, stream_dfpwm=True)
         ctx = context()
-        bt = _wrap(B.Batch.upload, ctx, [bytes(f[o:o + n]) for f, (o, n) in zip(files, ranges)])
+        bt = _wrap(B.Batch.upload, ctx, [bytes((f[0] if isinstance(f, (list, tuple)) else f)[o:o + n]) for f, (o, n) in zip(files, ranges)])
         out, ck = _wrap(B.stream_decode_mixed, ctx, bt, descs, _interp(defaultInterpolation, 0), bool(mono), N.F64)
         rows = out.download()
         return [self._chunk_iter(out, ck, None if math.isnan(lengths[i]) else lengths[i], d.codec == N.CODEC_G711, i, rows) for i, d in enumerate(descs)]

@@ -18,34 +18,47 @@
 //       outputs and evaluates once more only where its run starts — then ns * (ns < 0 and 128 or 127), clamped (:2401-2402);
 //       stream.g711: clamp(floor(s)) per channel or clamp(floor(acc / channels)) (:2905-2909).  Coalesced stores.
 // fp64 in the reference's operation order whatever the storage type; F32 rounds once, at the store.
+//
+// aukit.stream.dfpwm (data_s, rate, channels, mono) (:2439-2496) is one more kind of class, in instantiations of their own (DF = true, launched
+// only for a batch that has one; DF = false is the kernel of before).  A pre-pass decodes every DFPWM stream of the batch to a flat int8 row in
+// ctx->tmp_buf — element 0 the leading 0, then the samples in feed order: slices of 6000 C + 1 bytes advanced by 6000 C, the decoder's state
+// carried (Q10) — with the chunk engine (dfpwm_par.hip; one call per distinct channel count) or, where it declines, a lane per stream
+// (k_smix_dfpwm_rows).  Iterator call k's table is the row from element 8 * (bytes fed before it) on: audio[0] is the call before's last sample.
+// A tile stages its window of raw int8 values as doubles (16-byte loads; one flat "channel"), a lane per output reads x = (o C) / ratio + 1,
+// v = isint ? audio[x] : clamp(interp(audio, x), -128, 127), and v goes to all C rows or, mixed down, ((0 + v) + v ...) / C to one (Q11).
 #include <algorithm>
 #include <string>
 #include <tuple>
 #include "resample.h"
 #include "resample_dev.h"
+#include "dfpwm_dev.h"
 
 namespace aukit {
 
-enum { SMIX_EPI_PCM = 0, SMIX_EPI_FLOOR = 1 };
+bool dfpwm_decode_parallel_feed(aukit_ctx *ctx, const unsigned char *src, const std::vector<uint64_t> &h_off, const std::vector<uint64_t> &h_fed, uint64_t run,
+                                uint64_t stride, int mode, int C, signed char *out, const unsigned long long *d_out_off, const unsigned long long *d_out_stride,
+                                uint64_t lead, int *rc, const DfSliceHook *hook = nullptr);  // dfpwm_par.hip
+
+enum { SMIX_EPI_PCM = 0, SMIX_EPI_FLOOR = 1, SMIX_EPI_DFPWM = 2 };
 
 struct SMixClass {
     double ratio, rcp;     // x = (i - 1) / ratio + 1
     double lp_alpha;       // 1 - exp(-(rate / 96000) * 2 pi)  :2365
     double g711_scale;     // 1 / 0x40  :2891
-    int codec;             // AUKIT_CODEC_PCM / AUKIT_CODEC_G711
+    int codec;             // AUKIT_CODEC_PCM / AUKIT_CODEC_G711 / AUKIT_CODEC_DFPWM
     int bytes;             // per sample
     int data_type, big_endian, ulaw;
-    int channels;          // in the data
-    int stage;             // channels staged: 1 where stream.pcm mixes down at read time
-    int mix;               // PCM: the staged channel is the channels' mean; G.711: the mean is taken after interpolation
+    int channels;          // in the data; DFPWM: rows written per output, and the step of i (x = (o * channels) / ratio + 1)
+    int stage;             // channels staged: 1 where stream.pcm mixes down at read time, and for DFPWM (the row is flat)
+    int mix;               // PCM: the staged channel is the channels' mean; G.711: the mean is taken after interpolation; DFPWM: ((0 + v) + v ...) / channels
     int epi;               // SMIX_EPI_*
-    int exact_rcp;         // 1: RN((i-1)/ratio) via rcp + two fmas is verified exact for 48 001 outputs
+    int exact_rcp;         // 1: RN((i-1)/ratio) via rcp + two fmas is verified exact for 48 001 outputs (DFPWM: for every (i - 1) its longest call reaches)
     int cap;               // LDS doubles per staged channel
     int s16le_mono;        // 16-byte vector staging where the stream's bytes start at an even address
 };
 static_assert(sizeof(SMixClass) == 80, "SMixClass layout");
 struct SMixSeg {
-    unsigned long long src_off;  // the stream's first byte, relative to the batch's data
+    unsigned long long src_off;  // the stream's first byte, relative to the batch's data (DFPWM: its row's, relative to SMixParams::rows)
     long long src_base;          // source frame (within the stream) of table index 0
     unsigned long long out_off;  // element offset of output channel 0, output index 0 of this call
     int w_lo, w_hi;              // valid table indices (anything else reads as nil)
@@ -65,19 +78,22 @@ struct SMixParams {
     const unsigned char *src;
     const unsigned char *safe_lo, *safe_hi;  // the allocation: a 16-byte vector load at p needs safe_lo <= p and p + 16 <= safe_hi
     void *out;
+    const signed char *rows;  // DF: the pre-pass's int8 rows (ctx->tmp_buf): 16-byte aligned, 64 bytes to spare behind the last
 };
 
+template <bool DF = false>
 AUKIT_DEV double smix_pos(const SMixClass &K, unsigned o) {  // pos_of with the class's numbers
-    const double n = (double)o;
+    double n = (double)o;
+    if constexpr (DF) { if (K.epi == SMIX_EPI_DFPWM) n = (double)((unsigned long long)o * (unsigned)K.channels); }  // for i = 1, newlen, channels  :2478
     return (K.exact_rcp ? div_rcp(n, K.ratio, K.rcp) : n / K.ratio) + 1.0;
 }
 
 // where output o reads the staged window: slot of floor(x) and of its neighbours with the nil fall-backs applied, every slot inside [0, last]
 struct SMixAt { int i0, i1, i2, i3; double fx; bool isint; };
-template <int INTERP>
+template <int INTERP, bool DF = false>
 AUKIT_DEV SMixAt smix_at(const SMixClass &K, const SMixSeg &sg, int k_lo, int last, unsigned o) {
     SMixAt a;
-    const double x = smix_pos(K, o);
+    const double x = smix_pos<DF>(K, o);
     const double ffx = floor(x);
     int k = (int)ffx;
     k = k < sg.w_lo ? sg.w_lo : (k > sg.w_hi ? sg.w_hi : k);  // the host guarantees w_lo <= k <= w_hi
@@ -105,7 +121,29 @@ AUKIT_DEV double smix_tap(const double *tab, const SMixAt &a) {
 
 template <typename T> AUKIT_DEV void smix_store(T *p, double v) { *p = (T)v; }
 
-template <int INTERP, typename OUT_T>
+// DF: `n_stage` raw int8 values from row element g0 on become doubles (exact: no table, no normalisation) — 16 bytes per lane from the aligned address
+// at or below the window; what lies outside it lands in slots no output indexes.  No safe_lo / safe_hi test: rows start at multiples of 16 bytes and
+// the buffer has 64 bytes to spare, and the caller keeps head + n_stage + 15 <= cap.  -> the window's first slot
+AUKIT_DEV int smix_stage_i8(const signed char *row, long long g0, int n_stage, double *sm, int tid) {
+    const signed char *a0 = row + g0;
+    const signed char *al = (const signed char *)((uintptr_t)a0 & ~(uintptr_t)15);
+    const int head = (int)(a0 - al);
+    const int nvec = (head + n_stage + 15) >> 4;
+    for (int v = tid; v < nvec; v += 256) {
+        const uint4 u = *reinterpret_cast<const uint4 *>(al + 16 * (size_t)v);
+        const unsigned w[4] = {u.x, u.y, u.z, u.w};
+        double2 *o = reinterpret_cast<double2 *>(sm + 16 * v);
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const int x = (int)w[e];
+            o[2 * e] = make_double2((double)((x << 24) >> 24), (double)((x << 16) >> 24));
+            o[2 * e + 1] = make_double2((double)((x << 8) >> 24), (double)(x >> 24));
+        }
+    }
+    return head;
+}
+
+template <int INTERP, typename OUT_T, bool DF>
 __global__ __launch_bounds__(256) void k_stream_mixed(const SMixParams P) {
     extern __shared__ double sm[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -121,19 +159,22 @@ __global__ __launch_bounds__(256) void k_stream_mixed(const SMixParams P) {
 
         // window of the table this tile touches
         const unsigned o_first = (K.epi == SMIX_EPI_PCM && o0 > 0) ? o0 - 1 : o0;  // the FIR needs s(o0 - 1)
-        int k_lo = (int)floor(smix_pos(K, o_first)) - HL;
-        int k_hi = (int)floor(smix_pos(K, o0 + cnt - 1)) + HR;
+        int k_lo = (int)floor(smix_pos<DF>(K, o_first)) - HL;
+        int k_hi = (int)floor(smix_pos<DF>(K, o0 + cnt - 1)) + HR;
         k_lo = max(k_lo, sg.w_lo);
         k_hi = min(k_hi, sg.w_hi);
         int n_stage = k_hi - k_lo + 1;
         n_stage = min(n_stage, cap - 16);  // the host sized cap for the window plus the vector path's head and tail; never past the class's LDS
+        if constexpr (DF) { if (K.codec == AUKIT_CODEC_DFPWM) n_stage = min(n_stage, cap - 32); }  // (a head of up to 15 slots, and as many behind)
 
         __syncthreads();  // the tile before: its LDS reads are done
         int shift = 0;
         if (n_stage > 0) {
             const long long g0 = sg.src_base + k_lo;  // source frame of table index k_lo (>= 0: w_lo is the stream's or the call's first frame)
             const unsigned char *base = P.src + sg.src_off;
-            if (K.s16le_mono && (((uintptr_t)base) & 1) == 0) {
+            if (DF && K.codec == AUKIT_CODEC_DFPWM) {
+                if constexpr (DF) shift = smix_stage_i8(P.rows + sg.src_off, g0, n_stage, sm, tid);
+            } else if (K.s16le_mono && (((uintptr_t)base) & 1) == 0) {
                 const unsigned char *a0 = base + 2 * g0;
                 const unsigned char *al = (const unsigned char *)((uintptr_t)a0 & ~(uintptr_t)15);
                 const int head = (int)(a0 - al) >> 1;
@@ -192,7 +233,23 @@ __global__ __launch_bounds__(256) void k_stream_mixed(const SMixParams P) {
 
         const double *tab0 = sm + shift;  // slot of table index k_lo, channel 0
         const int last = n_stage - 1;
-        if (K.epi == SMIX_EPI_FLOOR) {
+        if (DF && K.epi == SMIX_EPI_DFPWM) {
+            if constexpr (DF) {
+                for (unsigned j = tid; j < cnt; j += 256) {
+                    const unsigned o = o0 + j;
+                    const SMixAt a = smix_at<INTERP, true>(K, sg, k_lo, last, o);
+                    const double s = smix_tap<INTERP>(tab0, a);
+                    const double v = a.isint ? s : lua_clamp(s, -128, 127);                                                      // :2483-2484
+                    if (K.mix) {
+                        double acc = 0;
+                        for (int c = 0; c < C; c++) acc = acc + v;
+                        smix_store<OUT_T>(out + sg.out_off + o, acc / C);                                                        // :2485, :2488
+                    } else {
+                        for (int c = 0; c < C; c++) smix_store<OUT_T>(out + sg.out_off + (size_t)c * sg.out_stride + o, v);      // :2486
+                    }
+                }
+            }
+        } else if (K.epi == SMIX_EPI_FLOOR) {
             for (unsigned j = tid; j < cnt; j += 256) {
                 const unsigned o = o0 + j;
                 const SMixAt a = smix_at<INTERP>(K, sg, k_lo, last, o);
@@ -231,6 +288,35 @@ __global__ __launch_bounds__(256) void k_stream_mixed(const SMixParams P) {
     }
 }
 
+// The pre-pass where the chunk engine declines (every DFPWM stream short): a lane per entry (first byte, byte count, row offset, advance) decodes
+// slices of adv + 1 bytes advanced by adv with one decoder into its row — element 0 the leading 0, the eight samples of a fed byte one 8-byte store
+// behind it (codecs.hip's k_dfpwm_decode_list is this for aukit.dfpwm's 6001 / 6000, without the leading element)
+struct SMixDfItem { unsigned long long src_off, nb, row_off, adv; };
+__global__ __launch_bounds__(64) void k_smix_dfpwm_rows(const unsigned char *src, const SMixDfItem *list, unsigned n, signed char *rows) {
+    const unsigned s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= n) return;
+    const SMixDfItem it = list[s];
+    const unsigned char *p = src + it.src_off;
+    signed char *o = rows + it.row_off;
+    DfDec d{};
+    o[0] = 0;  // audio[0] of the first call: `last` = 0  :2448
+    unsigned long long i = 1;
+    for (unsigned long long pos = 0; pos < it.nb; pos += it.adv) {
+        const unsigned long long cnt = it.nb - pos < it.adv + 1 ? it.nb - pos : it.adv + 1;  // str_sub(data, pos, pos + 6000 * channels)  :2455
+        for (unsigned long long b = 0; b < cnt; b++) {
+            unsigned byte = p[pos + b];
+#pragma unroll
+            for (int k = 0; k < 8; k++) { o[i + k] = (signed char)df_decode_bit(d, byte & 1); byte >>= 1; }
+            i += 8;
+        }
+    }
+}
+// behind the chunk engine, which writes a row from element 1 on: the leading 0 of every row
+__global__ __launch_bounds__(256) void k_smix_row_heads(signed char *rows, const unsigned long long *row_off, unsigned n) {
+    const unsigned s = blockIdx.x * 256 + threadIdx.x;
+    if (s < n) rows[row_off[s]] = 0;
+}
+
 // ------------------------------------------------------------------ host
 static int check_smix_pcm(const aukit_codec_desc *d) {  // what check_pcm_desc (api_resample.hip) refuses, with its words
     if (d->bit_depth != 8 && d->bit_depth != 16 && d->bit_depth != 24 && d->bit_depth != 32) return fail(AUKIT_E_ARG, "bad argument #2 (invalid bit depth)");
@@ -245,6 +331,13 @@ static int check_smix_pcm(const aukit_codec_desc *d) {  // what check_pcm_desc (
 // everything the stream's own aukit_stream_decode call refuses (stream_pcm / stream_g711, api_resample.hip), with its words; and the one thing that
 // call serves and this one does not: the uneven last chunk
 static int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) {
+    if (d->codec == AUKIT_CODEC_DFPWM) {  // stream_dfpwm's (codecs2.hip); rates above 48 kHz are served there, and here
+        if (d->sample_rate < 1) return fail(AUKIT_E_ARG, "bad argument #2 (number outside of range)");
+        if (d->channels < 1 || d->channels > AUKIT_MAX_PLANAR_CHANNELS) return fail(AUKIT_E_ARG, "bad argument #3 (number outside of range)");
+        // (a call's outputs are counted in 32 bits there and here: a call of 48 008 C samples at a rate below 1.08 Hz would not fit)
+        if ((double)(8 * (6000ull * d->channels + 1)) * (48000 / d->sample_rate) / d->channels > 2147483632.0) return fail(AUKIT_E_UNSUPPORTED, "stream too long");
+        return AUKIT_OK;
+    }
     if (d->codec == AUKIT_CODEC_PCM) {
         int rc;
         if ((rc = check_smix_pcm(d))) return rc;
@@ -267,12 +360,12 @@ static int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) 
     return AUKIT_OK;
 }
 
-template <typename OUT_T>
+template <typename OUT_T, bool DF>
 static int launch_smix(aukit_ctx *ctx, int interp, const SMixParams &P, size_t lds, unsigned grid) {
     switch (interp) {
-    case AUKIT_INTERP_NONE: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_NONE, OUT_T>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
-    case AUKIT_INTERP_LINEAR: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_LINEAR, OUT_T>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
-    default: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_CUBIC, OUT_T>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
+    case AUKIT_INTERP_NONE: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_NONE, OUT_T, DF>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
+    case AUKIT_INTERP_LINEAR: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_LINEAR, OUT_T, DF>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
+    default: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_CUBIC, OUT_T, DF>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
     }
     AUKIT_HIP_CHECK(hipGetLastError());
     return AUKIT_OK;
@@ -290,9 +383,13 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
     if (interp == AUKIT_INTERP_SINC) return fail(AUKIT_E_UNSUPPORTED, "sinc interpolation is not served for per-stream descriptors: stream each class with aukit_stream_decode");
     if (n_descs != in->n) return fail(AUKIT_E_ARG, "%u descriptors for a batch of %u streams", n_descs, in->n);
     const uint32_t n = in->n;
-    for (uint32_t s = 0; s < n; s++)
-        if (descs[s].codec != AUKIT_CODEC_PCM && descs[s].codec != AUKIT_CODEC_G711)
-            return fail(AUKIT_E_UNSUPPORTED, "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM and AUKIT_CODEC_G711)", s, descs[s].codec);
+    bool has_df = false;
+    for (uint32_t s = 0; s < n; s++) {
+        if (descs[s].codec != AUKIT_CODEC_PCM && descs[s].codec != AUKIT_CODEC_G711 && descs[s].codec != AUKIT_CODEC_DFPWM)
+            return fail(AUKIT_E_UNSUPPORTED, "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711 and AUKIT_CODEC_DFPWM)", s,
+                        descs[s].codec);
+        has_df = has_df || descs[s].codec == AUKIT_CODEC_DFPWM;
+    }
     if (!mono)
         for (uint32_t s = 1; s < n; s++)
             if (descs[s].channels != descs[0].channels) return fail(AUKIT_E_ARG, "streams differ in channel count: mix down or split the batch");
@@ -316,8 +413,8 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
     size_t lds = 0;
     for (uint32_t s = 0; s < n; s++) {
         const aukit_codec_desc &d = descs[s];
-        const bool pcm = d.codec == AUKIT_CODEC_PCM;
-        const ClassKey key(d.codec, pcm ? d.bit_depth : 8, pcm ? d.data_type : 0, pcm ? (d.big_endian ? 1 : 0) : 0, d.channels, pcm ? 0 : (d.ulaw ? 1 : 0), d.sample_rate);
+        const bool pcm = d.codec == AUKIT_CODEC_PCM, df = d.codec == AUKIT_CODEC_DFPWM;
+        const ClassKey key(d.codec, pcm ? d.bit_depth : 8, pcm ? d.data_type : 0, pcm ? (d.big_endian ? 1 : 0) : 0, d.channels, pcm || df ? 0 : (d.ulaw ? 1 : 0), d.sample_rate);
         auto it = index.find(key);
         if (it == index.end()) {
             SMixClass K;
@@ -336,6 +433,10 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
                 K.mix = (mono && d.channels > 1) ? 1 : 0;  // with one channel `mono` is ignored  :2243
                 K.stage = K.mix ? 1 : d.channels;
                 K.epi = SMIX_EPI_PCM;
+            } else if (df) {
+                K.mix = (mono && d.channels > 1) ? 1 : 0;  // if channels == 1 then mono = false end  :2445
+                K.stage = 1;                               // the row is flat: the step of `channels` is in the position
+                K.epi = SMIX_EPI_DFPWM;
             } else {
                 K.mix = mono ? 1 : 0;
                 K.stage = d.channels;
@@ -343,8 +444,11 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
             }
             K.s16le_mono = (pcm && d.bit_depth == 16 && d.data_type == AUKIT_SIGNED && !d.big_endian && d.channels == 1) ? 1 : 0;
             // tile height: the staged window (tile_out / ratio + halo) x staged channels x 8 B within plan_tiles' budget; 64 KiB at the most
-            const int slack = hl + hr + 2 + 32;  // +32: the vector path's alignment head and tail, the FIR's look-back, the kernel's own margin of 16
-            auto cap_for = [&](int to) { return (int)std::ceil((double)to / K.ratio) + slack; };
+            // DFPWM: outputs advance `channels` table steps at a time (rates above 48 kHz widen the window further); 16-byte loads of int8: +64, the
+            // kernel's margin is 32
+            const int slack = hl + hr + 2 + (df ? 64 : 32);  // +32: the vector path's alignment head and tail, the FIR's look-back, the kernel's own margin of 16
+            const double eff = df ? K.ratio / d.channels : K.ratio;
+            auto cap_for = [&](int to) { return (int)std::ceil((double)to / eff) + slack; };
             const size_t budget = 24 * 1024, hard = 64 * 1024;
             int to = 2048;
             while (to > 256 && (size_t)cap_for(to) * 8 * K.stage > budget) to -= 256;
@@ -360,7 +464,12 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
         cls_of[s] = it->second;
     }
     AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
-    for (SMixClass &K : classes) K.exact_rcp = exact_div_verified(ctx, K.ratio, 48001) ? 1 : 0;  // a segment has at most 48 000 outputs
+    for (SMixClass &K : classes) {
+        if (K.epi != SMIX_EPI_DFPWM) { K.exact_rcp = exact_div_verified(ctx, K.ratio, 48001) ? 1 : 0; continue; }  // a segment has at most 48 000 outputs
+        // a DFPWM call reads (i - 1) = o * channels up to 8 (6000 C + 1) ratio: the verdict covers all of it (288 048 at 8 kHz), or the kernel divides
+        const double top = (double)(8 * (6000ull * K.channels + 1)) * K.ratio + K.channels + 1;
+        K.exact_rcp = (top <= 4e6 && exact_div_verified(ctx, K.ratio, (uint64_t)top)) ? 1 : 0;
+    }
 
     // segments: one per (stream, iterator call); the chunk table beside them.  stream.pcm's plan is made once per distinct rate
     std::map<double, ChunkPlan> plans;
@@ -374,6 +483,11 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
     ck->status.assign(n, 0);
     ck->length_seconds.assign(n, 0);
     uint64_t in_bytes = 0, out_elems = 0;
+    // the DFPWM streams that have bytes, by channel count (the engine's run and stride are per call): first byte, fed bytes, row offset
+    struct DfGroup { std::vector<uint64_t> off, fed, row; std::vector<SMixDfItem> items; };
+    std::map<int, DfGroup> df_groups;
+    uint64_t df_tot = 0, df_src = 0;
+    uint32_t df_n = 0;
     for (uint32_t s = 0; s < n; s++) {
         const aukit_codec_desc &d = descs[s];
         const uint64_t nb = in->off[s + 1] - in->off[s];
@@ -383,7 +497,35 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
         memset(&g, 0, sizeof g);
         g.src_off = in->off[s];
         g.cls = cls_of[s];
-        if (d.codec == AUKIT_CODEC_PCM) {
+        if (d.codec == AUKIT_CODEC_DFPWM) {
+            // stream_dfpwm's plan (codecs2.hip) from byte 0: slices of adv + 1 bytes advanced by adv; a call's table starts at the row element that holds
+            // the call before's last sample (element 0: the leading 0)
+            const uint64_t adv = 6000ull * C, slice = adv + 1;
+            const double ratio = 48000 / d.sample_rate;  // :2473
+            ck->length_seconds[s] = (double)nb * 8 / d.sample_rate / C;  // :2495
+            uint64_t fed8 = 0, k = 0;
+            for (uint64_t pos = 0; pos < nb; pos += adv, k++) {
+                const uint64_t cnt = std::min<uint64_t>(slice, nb - pos), na = cnt * 8;
+                const double newlen = (double)na * ratio;                                                          // :2474
+                const uint32_t m = newlen >= 1 ? (uint32_t)(std::floor((newlen - 1) / C) + 1) : 0;                 // for i = 1, newlen, channels
+                g.src_off = df_tot;  // the row; where it lies is settled here, before anything is allocated
+                g.src_base = (long long)fed8; g.w_lo = 0; g.w_hi = (int)na; g.n_out = m;
+                g.out_off = lens[s];
+                segs.push_back(g);
+                clens[s].push_back(m);
+                cpos[s].push_back((double)(k * adv + 1) * 8 / d.sample_rate / C);  // p * 8 / sampleRate / channels  :2494
+                lens[s] += m;
+                fed8 += na;
+            }
+            if (nb) {
+                DfGroup &G = df_groups[C];
+                G.off.push_back(in->off[s]); G.fed.push_back(fed8 / 8); G.row.push_back(df_tot);
+                G.items.push_back(SMixDfItem{in->off[s], nb, df_tot, adv});
+                df_tot += round_up(fed8 + 1, 16);
+                df_src += nb;
+                df_n++;
+            }
+        } else if (d.codec == AUKIT_CODEC_PCM) {
             const int bd = d.bit_depth / 8;
             const bool is_float = d.data_type == AUKIT_FLOAT, mix = mono && C > 1;
             auto pit = plans.find(d.sample_rate);
@@ -447,10 +589,54 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
 
     aukit_audio *a = *out;
     int rc;
+    // the pre-pass's scratch: the int8 rows (each at a multiple of 16 bytes, 64 bytes to spare behind the last) and behind them its tables, in
+    // ctx->tmp_buf — sized before `*out` is touched.  audio_prepare may swap ctx->tmp_buf for the larger buffer of an `*out` that owes a resample
+    // (lazy_drop): the scratch is asked to be at least that large, so it stays, and the pointer is read after it all the same
+    const size_t df_tab_at = (size_t)round_up(df_tot + 64, 256);
+    if (df_n) {
+        size_t need = df_tab_at + (size_t)df_n * (8 + sizeof(SMixDfItem)) + 64;
+        if (*out && (*out)->lazy_rows.p && !(*out)->lazy_indirect) need = std::max(need, (*out)->lazy_rows.cap);
+        if ((rc = ctx->tmp_buf.ensure(need))) { delete ck; return rc; }
+    }
     if ((rc = audio_prepare(ctx, &a, n, C_out, 48000, dtype, lens.data()))) { delete ck; return rc; }
     *out = a;
     auto deliver = [&]() { if (chunks) { if (*chunks) aukit_chunks_free(*chunks); *chunks = ck; } else delete ck; };
     if (nt == 0) { deliver(); return AUKIT_OK; }
+
+    if (df_n) {  // pre-pass, timed under its own name in front of the resample launch
+        char *const T = reinterpret_cast<char *>(ctx->tmp_buf.p) + df_tab_at;
+        signed char *const rows = reinterpret_cast<signed char *>(ctx->tmp_buf.p);
+        if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
+        const bool sb_on = ctx->sb_dfpwm_on;  // a stream handle's carried decoder state is not this call's: every stream starts from reset, at byte 0
+        ctx->sb_dfpwm_on = false;
+        std::vector<SMixDfItem> lanes;  // the groups the engine declines (dfpwm_par.hip: nchunk < 2, every stream short)
+        bool engine = false;
+        size_t at = 0;
+        for (auto &kv : df_groups) {
+            const DfGroup &G = kv.second;
+            const uint64_t adv = 6000ull * (uint64_t)kv.first;
+            const uint32_t m = (uint32_t)G.off.size();
+            unsigned long long *d_row = reinterpret_cast<unsigned long long *>(T + at);
+            at += (size_t)m * 8;
+            int prc = AUKIT_OK;
+            if ((rc = h2d_table(ctx, d_row, G.row.data(), (size_t)m * 8))) break;
+            if (dfpwm_decode_parallel_feed(ctx, in->data(), G.off, G.fed, adv + 1, adv, 0 /* rows */, 1 /* one "channel": flat */, rows, d_row, nullptr, 1 /* behind the leading 0 */,
+                                           &prc)) {
+                if ((rc = prc)) break;
+                hipLaunchKernelGGL(k_smix_row_heads, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, rows, d_row, m);
+                engine = true;
+            } else lanes.insert(lanes.end(), G.items.begin(), G.items.end());
+        }
+        ctx->sb_dfpwm_on = sb_on;
+        if (rc) { delete ck; return rc; }
+        if (!lanes.empty()) {
+            SMixDfItem *d_items = reinterpret_cast<SMixDfItem *>(T + (size_t)df_n * 8);
+            if ((rc = h2d_table(ctx, d_items, lanes.data(), lanes.size() * sizeof(SMixDfItem)))) { delete ck; return rc; }
+            hipLaunchKernelGGL(k_smix_dfpwm_rows, dim3(((unsigned)lanes.size() + 63) / 64), dim3(64), 0, ctx->stream, in->data(), d_items, (unsigned)lanes.size(), rows);
+        }
+        if (hipGetLastError() != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "DFPWM pre-pass launch failed"); }
+        if ((rc = ctx_end_kernel(ctx, engine ? "k_df_chunks(parallel dfpwm decode)" : "k_smix_dfpwm_rows", df_src + df_tot))) { delete ck; return rc; }
+    }
 
     std::vector<SMixTile> tiles;
     tiles.reserve((size_t)nt);
@@ -479,13 +665,15 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
     P.safe_lo = in->base;
     P.safe_hi = in->base + in->cap;
     P.out = a->dev;
+    P.rows = reinterpret_cast<const signed char *>(ctx->tmp_buf.p);
     unsigned per_cu = (unsigned)std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1));
     if (per_cu < 1) per_cu = 1;
     per_cu *= 16;  // a finer hand-out than the resident count, as launch_resample: the tiles of a mixed batch differ in cost
     const unsigned grid = std::min<unsigned>(P.n_tiles, (unsigned)ctx->num_cus * per_cu);
     if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
-    if (dtype == AUKIT_F64) rc = launch_smix<double>(ctx, interp, P, lds, grid);
-    else rc = launch_smix<float>(ctx, interp, P, lds, grid);
+    // (the DFPWM class lives in instantiations of its own: a batch without one launches the kernels it always did)
+    if (has_df) rc = dtype == AUKIT_F64 ? launch_smix<double, true>(ctx, interp, P, lds, grid) : launch_smix<float, true>(ctx, interp, P, lds, grid);
+    else rc = dtype == AUKIT_F64 ? launch_smix<double, false>(ctx, interp, P, lds, grid) : launch_smix<float, false>(ctx, interp, P, lds, grid);
     if (rc) { delete ck; return rc; }
     static const char *names[] = {"k_stream_mixed<none>", "k_stream_mixed<linear>", "k_stream_mixed<cubic>"};
     if ((rc = ctx_end_kernel(ctx, names[interp], in_bytes + out_elems * dtype_size(dtype)))) { delete ck; return rc; }

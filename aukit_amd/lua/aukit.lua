@@ -818,9 +818,10 @@ local function stream_container(data, kind, mono, ignoreHeader)
     if c.length_seconds == c.length_seconds then length = c.length_seconds end  -- not NaN: the container factory computes its own (:2994-2996, :3064-3069, :3107-3113)
     return it, length
 end
--- a mixed library streamed in one call (aukit_stream_decode_mixed): `files` = whole WAV / AIFF / AU files of any mix of rates, PCM formats / G.711
--- and channel counts -> a list of {iterator, length} pairs in input order, each what aukit.stream.wav / aiff / au(file, mono) returns; one
--- upload, one launch.  Without `mono` the files must agree in channel count.
+-- a mixed library streamed in one call (aukit_stream_decode_mixed): `files` = whole WAV / AIFF / AU files of any mix of rates, PCM formats / G.711 /
+-- DFPWM and channel counts -> a list of {iterator, length} pairs in input order, each what aukit.stream.wav / aiff / au(file, mono) returns; one
+-- upload, one launch.  Without `mono` the files must agree in channel count.  A raw .dfpwm file, which has no header, is given as
+-- {data, "dfpwm"[, channels[, sampleRate]]} (load_many's entry: channels first): its pair is aukit.stream.dfpwm(data, sampleRate, channels, mono)'s.
 function aukit.stream.many(files, mono)
     expect(1, files, "table") expect(2, mono, "boolean", "nil")
     local n = #files
@@ -829,17 +830,29 @@ function aukit.stream.many(files, mono)
     local parts, lengths = {}, {}
     for i = 1, n do
         local f = files[i]
-        if type(f) ~= "string" then error("bad argument #1 (file " .. (i - 1) .. ": expected string)", 2) end
-        local kind
-        for _, m in ipairs(MAGIC) do if f:find(m[1]) then kind = m[2] break end end
-        if not kind then error("file " .. (i - 1) .. ": not a WAV, AIFF or AU file", 2) end
-        local c = ffi.new("aukit_container")
-        if C.aukit_parse_container(ffi.cast("const uint8_t*", f), #f, kind, 1, c) ~= 0 then error("file " .. (i - 1) .. ": " .. ffi.string(C.aukit_last_error()), 2) end
-        if c.desc.codec > 1 then error("file " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: stream.many takes PCM and G.711 (the block codecs keep their own streams)", 2) end
-        descs[i - 1] = c.desc
-        parts[i] = f:sub(tonumber(c.payload_off) + 1, tonumber(c.payload_off + c.payload_len))
+        if type(f) == "table" then
+            if type(f[1]) ~= "string" or f[2] ~= "dfpwm" or #f > 4 then error("bad argument #1 (file " .. (i - 1) .. ": expected {string, \"dfpwm\"[, channels[, sampleRate]]})", 2) end
+            if (f[3] ~= nil and (type(f[3]) ~= "number" or f[3] % 1 ~= 0)) or (f[4] ~= nil and type(f[4]) ~= "number") then
+                error("bad argument #1 (file " .. (i - 1) .. ": expected number for channels and sampleRate)", 2)
+            end
+            descs[i - 1] = desc {codec = "dfpwm", channels = f[3] or 1, sampleRate = f[4] or 48000}
+            parts[i] = f[1]
+            lengths[i] = 0 / 0   -- NaN: aukit.stream.dfpwm's own figure stands (#data * 8 / sampleRate / channels)
+        else
+            if type(f) ~= "string" then error("bad argument #1 (file " .. (i - 1) .. ": expected string)", 2) end
+            local kind
+            for _, m in ipairs(MAGIC) do if f:find(m[1]) then kind = m[2] break end end
+            if not kind then error("file " .. (i - 1) .. ": not a WAV, AIFF or AU file", 2) end
+            local c = ffi.new("aukit_container")
+            if C.aukit_parse_container(ffi.cast("const uint8_t*", f), #f, kind, 1, c) ~= 0 then error("file " .. (i - 1) .. ": " .. ffi.string(C.aukit_last_error()), 2) end
+            if c.desc.codec > 1 and c.desc.codec ~= 5 then  -- 5: AUKIT_CODEC_DFPWM (a WAV with the DFPWM GUID)
+                error("file " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: stream.many takes PCM, G.711 and DFPWM (the block codecs keep their own streams)", 2)
+            end
+            descs[i - 1] = c.desc
+            parts[i] = f:sub(tonumber(c.payload_off) + 1, tonumber(c.payload_off + c.payload_len))
+            lengths[i] = c.length_seconds   -- NaN: the stream factory's own figure stands
+        end
         offs[i] = offs[i - 1] + #parts[i]
-        lengths[i] = c.length_seconds   -- NaN: the stream factory's own figure stands
     end
     local b = ffi.new("aukit_batch*[1]")
     check(C.aukit_batch_upload(ctx(), b, ffi.cast("const uint8_t*", table.concat(parts)), offs, n))

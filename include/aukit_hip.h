@@ -316,14 +316,20 @@ int aukit_stream_decode(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
  * fp64 arithmetic whatever the storage type (AUKIT_F64 / AUKIT_F32); sinc served and rates above 48 kHz refused like the string's (Q3). */
 int aukit_stream_decode_table(aukit_ctx *ctx, const double *values, const uint64_t *offsets /* n + 1, elements */, uint32_t n, const aukit_codec_desc *d, int interp,
                               int mono, int dtype, aukit_audio **out, aukit_chunks **chunks);
-/* aukit.stream.pcm / aukit.stream.g711 (data_s, <descs[s]>) for every stream s, each with its OWN descriptor, string input, every iterator call at
- * once (aukit.lua:2228-2424, :2850-2913).  The result has aukit_stream_decode's shape: one audio at 48 kHz (per stream the concatenation of its
+/* aukit.stream.pcm / aukit.stream.g711 / aukit.stream.dfpwm (data_s, <descs[s]>) for every stream s, each with its OWN descriptor, string input,
+ * every iterator call at once (aukit.lua:2228-2424, :2850-2913, :2439-2496).  The result has aukit_stream_decode's shape: one audio at 48 kHz (per stream the concatenation of its
  * chunks; one channel if `mono`, else the common channel count) and one aukit_chunks.  Stream s of both — samples, nchunks, lens, pos, status,
  * length_seconds — is what aukit_stream_decode gives for a one-stream batch of its bytes with descs[s]; every chunk's channels are equally long.
  * fp64 in the reference's order whatever the storage type: AUKIT_F64, or AUKIT_F32 rounded once, at the store (stream.g711's floored integers
  * are exact in both).  `mono` has each codec's own meaning: stream.pcm mixes at read time (:2368), stream.g711 after interpolation (:2908); with
- * one channel it is ignored.  AUKIT_CODEC_PCM (every format stream.pcm takes, rates at or below 48 kHz) and AUKIT_CODEC_G711 (integer rates)
- * only, interpolation none / linear / cubic; anything else is AUKIT_E_UNSUPPORTED by name.  n_descs must be the batch's stream count; without
+ * one channel it is ignored.  AUKIT_CODEC_PCM (every format stream.pcm takes, rates at or below 48 kHz), AUKIT_CODEC_G711 (integer rates) and
+ * AUKIT_CODEC_DFPWM (the descriptor's `channels` and `sample_rate`, rates above 48 kHz included; positions count from byte 0 whatever a stream
+ * handle on the context carries; the same sample goes to every channel, and `mono` is ((0 + v) + v ...) / channels, :2485-2488) only,
+ * interpolation none / linear / cubic; anything else is AUKIT_E_UNSUPPORTED by name.  A batch with a DFPWM stream pays a pre-pass in front of the
+ * one resample launch: every DFPWM stream is decoded to a flat int8 row in the context's scratch (the chunk-parallel decoder, one run per distinct
+ * channel count, or a lane per stream where every stream is short) — element 0 a leading 0, then the samples in feed order (slices of
+ * 6000 * channels + 1 bytes advanced by 6000 * channels, the slice's last byte decoded again as the next one's first), rows at multiples of 16
+ * bytes — and iterator call k's table is the row from the call before's last sample on.  n_descs must be the batch's stream count; without
  * `mono` the descriptors must agree in channel count (AUKIT_E_ARG).  A stream whose own call would fail fails the whole call with that status
  * and message, the stream's index appended.  PCM data that ends inside a frame is served with the mix-down (the partial frame counts for
  * nothing) and refused without it whatever AUKIT_OPT_CHANNEL_LENS says: the uneven last chunk stays with aukit_stream_decode.  Every refusal

@@ -13,7 +13,9 @@ device synchronisations (the grouping's cost is host work and launches as much a
 reported, one line per library.
 
 Libraries: mixed64 (64 streams over 24 classes), mixed1024 (1024 streams over 24 classes), ten seconds each give or take 5 %; homog4096 (4096
-streams, 16-bit little-endian mono at 44.1 kHz, 10 s each: the headline benchmark's shape).
+streams, 16-bit little-endian mono at 44.1 kHz, 10 s each: the headline benchmark's shape); mixeddf64 and mixeddf1024 (64 / 1024 streams: every
+other one a ten-second DFPWM stream of one of six classes, 1 or 2 channels x 48000 / 44100 / 24000 Hz — the oracle's encoding of a tone plus noise,
+one payload per class — the others from the 24 PCM classes; (b) streams the DFPWM classes through aukit_stream_decode's own DFPWM path).
 
 Without --one the tool is a driver: every library runs in a fresh child process under its own `timeout -k 10`; after a child that faults, aborts
 or runs into its limit nothing more is started.  The lines go to --out (profiles/stream_mixed_rates.txt)."""
@@ -26,7 +28,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-LIBRARIES = {"mixed64": 300, "mixed1024": 420, "homog4096": 420}   # name -> time limit of its child, seconds
+LIBRARIES = {"mixed64": 300, "mixed1024": 420, "homog4096": 420, "mixeddf64": 300, "mixeddf1024": 420}   # name -> time limit of its child, seconds
 
 RATES = [8000, 11025, 22050, 32000, 44100, 48000, 37800, 16000]   # stream.pcm serves rates at or below 48 kHz
 FORMATS = [(8, "unsigned", False), (16, "signed", False), (24, "signed", False), (32, "float", False), (16, "signed", True), (32, "signed", False)]
@@ -58,20 +60,40 @@ def build_library(name, dev):
             noise = (torch.rand((256, frames), generator=g, device=dev, dtype=torch.float32) - 0.5) * 0.5
             x[s0 * frames:(s0 + 256) * frames] = torch.round((sine[None, :] + noise) * 32767.0).to(torch.int16).reshape(-1)
         return x.view(torch.uint8), [i * frames * 2 for i in range(n + 1)], [0] * n, [dict(rate=44100, bits=16, dtype="signed", be=False, ch=1)]
-    n = {"mixed64": 64, "mixed1024": 1024}[name]
+    n = {"mixed64": 64, "mixed1024": 1024, "mixeddf64": 64, "mixeddf1024": 1024}[name]
+    with_df = name.startswith("mixeddf")
     cl = classes24()
     rng = np.random.Generator(np.random.PCG64(0xA0C17 + n))
-    cls_of = [int(i % 24) if i < 24 else int(rng.integers(0, 24)) for i in range(n)]   # every class occurs
+    if with_df:   # even places: the six DFPWM classes in turn; odd places: the PCM classes, every one occurring
+        cl = cl + [dict(codec="dfpwm", rate=r, ch=c) for c in (1, 2) for r in (48000, 44100, 24000)]
+        cls_of = [24 + (i // 2) % 6 if i % 2 == 0 else (int((i // 2) % 24) if i // 2 < 24 else int(rng.integers(0, 24))) for i in range(n)]
+    else:
+        cls_of = [int(i % 24) if i < 24 else int(rng.integers(0, 24)) for i in range(n)]   # every class occurs
+    payload = {}
+    if with_df:   # ten seconds each: rate x channels x 10 samples, one bit per sample
+        from oracle import oracle as O
+        for c in range(24, 30):
+            k = cl[c]["rate"] * cl[c]["ch"] * 10
+            t = np.arange(k) / float(cl[c]["rate"] * cl[c]["ch"])
+            sig = 0.5 * np.sin(2 * np.pi * 440.0 * t) + rng.uniform(-0.25, 0.25, k)
+            payload[c] = np.frombuffer(O.dfpwm_encode(sig), dtype=np.uint8)
     offs, total = [0], 0
     for c in cls_of:
-        frames = int(cl[c]["rate"] * rng.uniform(9.5, 10.5))   # 9.5 .. 10.5 s
-        total += frames * cl[c]["ch"] * (cl[c]["bits"] // 8)
+        if c >= 24:
+            total += len(payload[c])
+        else:
+            frames = int(cl[c]["rate"] * rng.uniform(9.5, 10.5))   # 9.5 .. 10.5 s
+            total += frames * cl[c]["ch"] * (cl[c]["bits"] // 8)
         offs.append(total)
     g = torch.Generator(device=dev)
     g.manual_seed(0xA0C17 + n)
     x = torch.randint(0, 256, (max(total, 1),), generator=g, device=dev, dtype=torch.uint8)
+    dev_payload = {c: torch.from_numpy(p.copy()).to(dev) for c, p in payload.items()}
+    for s, c in enumerate(cls_of):
+        if c >= 24:
+            x[offs[s]:offs[s + 1]] = dev_payload[c]
     for s, c in enumerate(cls_of):   # float streams: numbers within +-1 instead of random bit patterns (NaN, huge values)
-        if cl[c]["dtype"] == "float":
+        if cl[c].get("dtype") == "float":
             k = (offs[s + 1] - offs[s]) // 4
             v = (torch.rand(k, generator=g, device=dev, dtype=torch.float32) * 2 - 1)
             x[offs[s]:offs[s + 1]] = v.view(torch.uint8) if not cl[c]["be"] else v.view(torch.uint8).reshape(-1, 4).flip(1).reshape(-1)
@@ -94,7 +116,8 @@ def run_one(name, pairs, dtype_name, exact):
     x, offs, cls_of, cl = build_library(name, dev)
     n = len(cls_of)
     print(f"{name}: {n} streams, {int(offs[-1]) / 1e6:.1f} MB of input built", flush=True)
-    descs_c = [B.make_desc(N.CODEC_PCM, c["ch"], c["rate"], c["bits"], c["dtype"], big_endian=c["be"]) for c in cl]
+    descs_c = [B.make_desc(N.CODEC_DFPWM, c["ch"], c["rate"]) if c.get("codec") == "dfpwm" else B.make_desc(N.CODEC_PCM, c["ch"], c["rate"], c["bits"], c["dtype"], big_endian=c["be"])
+               for c in cl]
     whole = B.Batch.wrap(ctx, x.data_ptr(), offs, keep=x)
     descs = [descs_c[c] for c in cls_of]
     # (b)'s inputs: one batch per class, views of the same bytes (a host that groups its files uploads them grouped: not timed on either side)
@@ -169,7 +192,7 @@ def run_one(name, pairs, dtype_name, exact):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--one", choices=sorted(LIBRARIES), help="run this library in this process (what the driver starts)")
-    ap.add_argument("--libraries", default="mixed64,mixed1024,homog4096")
+    ap.add_argument("--libraries", default="mixed64,mixed1024,homog4096,mixeddf64,mixeddf1024")
     ap.add_argument("--pairs", type=int, default=7)
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"], help="storage type of the rows on both sides")
     ap.add_argument("--exact-math", type=int, default=2, choices=[0, 1, 2], help="AUKIT_OPT_EXACT_MATH of the context both sides run on")
