@@ -171,6 +171,19 @@ __global__ __launch_bounds__(64) void k_flac_header(const unsigned char *src, co
             r.nsamples = (double)((unsigned)q[14] << 24 | (unsigned)q[15] << 16 | (unsigned)q[16] << 8 | q[17]) + (double)(q[13] & 15) * 4294967296.0;
             pos += 34;
             have = true;
+        } else if (type == 4) {
+            // :592-600: a VORBIS_COMMENT is walked by its content (string.unpack "<s4I4", then one "<s4" per comment), never by the declared length
+            u64 ncomments = 0;
+            for (u64 i = 0; i <= ncomments; i++) {   // i == 0: the vendor string, with the comment count behind it
+                for (int field = 0; field < (i == 0 ? 2 : 1); field++) {
+                    if (pos + 4 > nb) { r.status = 5; out[s] = r; return; }                              // "data string too short"
+                    const u64 v = (u64)p[pos] | (u64)p[pos + 1] << 8 | (u64)p[pos + 2] << 16 | (u64)p[pos + 3] << 24;
+                    pos += 4;
+                    if (field == 1) { ncomments = v; break; }
+                    if (v > nb - pos) { r.status = 5; out[s] = r; return; }
+                    pos += v;
+                }
+            }
         } else pos += length;
     }
     if (!have) r.status = 3;                    // "Stream info metadata block absent"
@@ -1662,7 +1675,8 @@ static int flac_run_fused(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &D,
                 if ((rc = decode(0, ncand, 5))) return rc;
                 if ((rc = ctx_end_kernel(ctx, "k_flac_decode", in->total() + guess * 4))) return rc;   // (the label aukit_ctx_last_kernel has always reported for this stage, kept on purpose: k_flac_stream or k_flac_pq ran)
             }
-            hipLaunchKernelGGL(k_flac_links, dim3((ncand + 255) / 256), dim3(256), 0, ctx->stream, G, d_cand, d_ci, ncand, H, d_links);
+            // (no candidate at all — a file whose metadata walk ends at or beyond its last byte: an audio of no samples, not a launch of no workgroups)
+            if (ncand) hipLaunchKernelGGL(k_flac_links, dim3((ncand + 255) / 256), dim3(256), 0, ctx->stream, G, d_cand, d_ci, ncand, H, d_links);
             hipLaunchKernelGGL(k_flac_chain_links, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, G, n, H, d_ci, d_links, d_chain);
             AUKIT_HIP_CHECK(hipGetLastError());
             AUKIT_HIP_CHECK(hipMemcpyAsync(&hc, d_cnt, sizeof hc, hipMemcpyDeviceToHost, ctx->stream));
@@ -1813,6 +1827,7 @@ static int flac_decode_rows(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &
         case 2: return fail(AUKIT_E_LUA, "Invalid magic string");
         case 3: return fail(AUKIT_E_LUA, "Stream info metadata block absent");
         case 4: return fail(AUKIT_E_LUA, "Sample depth not supported");
+        case 5: return fail(AUKIT_E_LUA, "data string too short");
         default: return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value");
         }
         if (s == 0) { D.channels = D.info[0].channels; D.depth = D.info[0].depth; D.rate = D.info[0].rate; }
@@ -1904,9 +1919,20 @@ template <typename R> AUKIT_DEV double flac_row_value(const R *rows, u64 at, dou
     if constexpr (sizeof(R) == 4) return (double)rows[at] / full;
     else return rows[at];
 }
+// interpolate.cubic (:261-266) with fx^3 handed in: cubic_exact's operations in cubic_exact's order.  The reference takes fx^3 with Lua's `^`, the
+// host C library's pow(), which is not correctly rounded everywhere (glibc's: one ulp off at 4 of the 160 phases of 44.1 -> 48 kHz); pow3_rn is.
+// With AUKIT_OPT_EXACT_MATH = 2 ("the reference's operations") stream.flac's positions are a function of the output index alone, so the host
+// hands the kernels its own pow(fx, 3) per output index (f3tab) and the samples are the ones the reference computes on this host, to the bit.
+AUKIT_DEV double cubic_with_f3(double p0, double p1, double p2, double p3, double fx, double f3) {
+    double f2 = fx * fx;
+    double c3 = -0.5 * p0 + 1.5 * p1 - 1.5 * p2 + 0.5 * p3;
+    double c2 = p0 - 2.5 * p1 + 2 * p2 - 0.5 * p3;
+    double c1 = -0.5 * p0 + 0.5 * p2;
+    return c3 * f3 + c2 * f2 + c1 * fx + p1;
+}
 template <int INTERP, typename OUT_T, typename R>
 __global__ __launch_bounds__(64) void k_flac_stream(const FsJob *jobs, u64 njobs, const R *rows, double full, OUT_T *out, double ratio, double rcp, int exact,
-                                                   double lp_alpha, int sinc_w) {
+                                                   double lp_alpha, int sinc_w, const double *f3tab) {
     const u64 j = (u64)blockIdx.x * 64 + threadIdx.x;
     if (j >= njobs) return;
     const FsJob job = jobs[j];
@@ -1930,7 +1956,7 @@ __global__ __launch_bounds__(64) void k_flac_stream(const FsJob *jobs, u64 njobs
             else if constexpr (INTERP == AUKIT_INTERP_SINC) s = sinc_at(tap, k, -1, n, fx, sinc_w);
             else {
                 const double p1 = tap(k), p0 = (k - 1 >= -1) ? tap(k - 1) : p1, p2 = (k + 1 <= n) ? tap(k + 1) : p1, p3 = (k + 2 <= n) ? tap(k + 2) : p2;
-                s = cubic_exact(p0, p1, p2, p3, fx);
+                s = f3tab ? cubic_with_f3(p0, p1, p2, p3, fx, f3tab[i]) : cubic_exact(p0, p1, p2, p3, fx);
             }
         }
         s = ls + lp_alpha * (s - ls);  // :3179 (recursive: ls = filtered s, Q14)
@@ -1944,7 +1970,7 @@ __global__ __launch_bounds__(64) void k_flac_stream(const FsJob *jobs, u64 njobs
 // every output, all outputs in parallel, into a scratch of doubles; pass 2: the recursive low-pass (:3179) and the scaling, serially per job
 // over contiguous doubles, 32 per round with the next 32 in flight, 16-byte stores.  Same operations in the same order: same values.
 template <int INTERP, typename R>
-__global__ __launch_bounds__(256) void k_flac_stream_interp(const FsJob *jobs, const u64 *scr_off, const R *rows, double full, double *scr, double ratio, double rcp, int exact, int sinc_w) {
+__global__ __launch_bounds__(256) void k_flac_stream_interp(const FsJob *jobs, const u64 *scr_off, const R *rows, double full, double *scr, double ratio, double rcp, int exact, int sinc_w, const double *f3tab) {
     const FsJob job = jobs[blockIdx.y];
     double m1 = 0, z0 = 0;
     if (job.last_off != ~0ull) z0 = flac_row_value(rows, job.last_off, full);
@@ -1966,7 +1992,7 @@ __global__ __launch_bounds__(256) void k_flac_stream_interp(const FsJob *jobs, c
             else if constexpr (INTERP == AUKIT_INTERP_SINC) s = sinc_at(tap, k, -1, n, fx, sinc_w);
             else {
                 const double p1 = tap(k), p0 = (k - 1 >= -1) ? tap(k - 1) : p1, p2 = (k + 1 <= n) ? tap(k + 1) : p1, p3 = (k + 2 <= n) ? tap(k + 2) : p2;
-                s = cubic_exact(p0, p1, p2, p3, fx);
+                s = f3tab ? cubic_with_f3(p0, p1, p2, p3, fx, f3tab[i]) : cubic_exact(p0, p1, p2, p3, fx);
             }
         }
         o[i] = s;
@@ -2185,10 +2211,17 @@ int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *,
         const unsigned grid = (unsigned)((jobs.size() + 63) / 64);
         const FsJob *dj = reinterpret_cast<const FsJob *>(ctx->seg_buf.p);
         const double full = std::ldexp(1.0, D.depth);
-        if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
         uint64_t scr_elems = 0, max_nout = 0;
         std::vector<uint64_t> scr_off(jobs.size());
         for (size_t k = 0; k < jobs.size(); k++) { scr_off[k] = scr_elems; scr_elems += ((uint64_t)jobs[k].nout + 1) & ~1ull; max_nout = std::max<uint64_t>(max_nout, (uint64_t)jobs[k].nout); }
+        const double *f3tab = nullptr;   // cubic_with_f3: the host's pow(fx, 3) of every output index of a block (outputs the division is verified for)
+        if (ctx->exact_math == 2 && interp == AUKIT_INTERP_CUBIC && max_nout && max_nout <= maxn) {
+            std::vector<double> f3(max_nout);
+            for (uint64_t i = 0; i < max_nout; i++) { const double x = (double)i / ratio + 1.0; f3[i] = std::pow(x - std::floor(x), 3); }   // :263, :265
+            if ((rc = upload_table(ctx, ctx->tile_buf, f3.data(), f3.size() * 8))) { delete ck; return rc; }
+            f3tab = reinterpret_cast<const double *>(ctx->tile_buf.p);
+        }
+        if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
         if (scr_elems * 8 <= (48ull << 30) && max_nout) {  // two passes
             DevBuf &S3 = ctx_scratch3(ctx);
             if ((rc = S3.ensure((size_t)scr_elems * 8 + 64))) { delete ck; return rc; }
@@ -2197,7 +2230,7 @@ int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *,
             double *scr = reinterpret_cast<double *>(S3.p);
             for (size_t first = 0; first < jobs.size(); first += 65535) {
                 const dim3 g1((unsigned)std::min<uint64_t>((max_nout + 255) / 256, 1024), (unsigned)std::min<size_t>(65535, jobs.size() - first));
-#define AUKIT_FI2(I, R) hipLaunchKernelGGL((k_flac_stream_interp<I, R>), g1, dim3(256), 0, ctx->stream, dj + first, dso + first, reinterpret_cast<const R *>(ctx->tmp_buf.p), full, scr, ratio, 1.0 / ratio, exact, ctx->sinc_w)
+#define AUKIT_FI2(I, R) hipLaunchKernelGGL((k_flac_stream_interp<I, R>), g1, dim3(256), 0, ctx->stream, dj + first, dso + first, reinterpret_cast<const R *>(ctx->tmp_buf.p), full, scr, ratio, 1.0 / ratio, exact, ctx->sinc_w, f3tab)
 #define AUKIT_FI(I) do { if (D.wide) AUKIT_FI2(I, double); else AUKIT_FI2(I, int); } while (0)
                 if (interp == 0) AUKIT_FI(0); else if (interp == 1) AUKIT_FI(1); else if (interp == 2) AUKIT_FI(2); else AUKIT_FI(3);
 #undef AUKIT_FI
@@ -2208,7 +2241,7 @@ int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *,
             else { if (D.wide) AUKIT_FR(float, double); else AUKIT_FR(float, int); }
 #undef AUKIT_FR
         } else {
-#define AUKIT_FS2(I, T, R) hipLaunchKernelGGL((k_flac_stream<I, T, R>), dim3(grid), dim3(64), 0, ctx->stream, dj, (u64)jobs.size(), reinterpret_cast<const R *>(ctx->tmp_buf.p), full, reinterpret_cast<T *>(a->dev), ratio, 1.0 / ratio, exact, lp_alpha, ctx->sinc_w)
+#define AUKIT_FS2(I, T, R) hipLaunchKernelGGL((k_flac_stream<I, T, R>), dim3(grid), dim3(64), 0, ctx->stream, dj, (u64)jobs.size(), reinterpret_cast<const R *>(ctx->tmp_buf.p), full, reinterpret_cast<T *>(a->dev), ratio, 1.0 / ratio, exact, lp_alpha, ctx->sinc_w, f3tab)
 #define AUKIT_FS(I, T) do { if (D.wide) AUKIT_FS2(I, T, double); else AUKIT_FS2(I, T, int); } while (0)
         if (dtype == AUKIT_F64) { if (interp == 0) AUKIT_FS(0, double); else if (interp == 1) AUKIT_FS(1, double); else if (interp == 2) AUKIT_FS(2, double); else AUKIT_FS(3, double); }
         else { if (interp == 0) AUKIT_FS(0, float); else if (interp == 1) AUKIT_FS(1, float); else if (interp == 2) AUKIT_FS(2, float); else AUKIT_FS(3, float); }

@@ -138,7 +138,8 @@ typedef enum {
                                  kernel (16-bit mono PCM, stream.pcm on it), the fp64 coefficient kernel (G.711 mono), fp64 tables with a
                                  Horner form on the exact rational position (every other interleaved PCM format of one or two channels,
                                  G.711 stereo); anything else runs the reference-order kernels.  Results may differ from value 2 by one
-                                 f32 ulp.  2: always the reference-order fp64 kernels (stream tails included). */
+                                 f32 ulp.  2: always the reference-order fp64 kernels (stream tails included; stream.flac's cubic interpolation takes
+                                 fx^3 from the host's pow(), as the reference's `^` does, not correctly rounded as the kernels do otherwise). */
     AUKIT_OPT_STORE_X4 = 1,   /* 1 (default): fast kernels transpose results through LDS and store 16 B per lane */
     AUKIT_OPT_COLLECT_STATS = 2, /* 1: calls that have counters (aukit_ctx_get_counter) read them back — one more device→host sync per call.
                                    0 (default): they do not. */

@@ -705,8 +705,23 @@ int ork__flac_open(const uint8_t *data, size_t n, ork_flac_dec **dd, double *sam
             ns = (double)rd_be32(p + 14) + (double)(p[13] & 15) * 4294967296.0;
             pos += 34;
             have = 1;
+        } else if (type == 4) {
+            /* :592-600: a VORBIS_COMMENT is walked by its CONTENT — string.unpack "<s4I4" (vendor string, comment count), then one "<s4" per
+               comment — and the declared length is never looked at: the walk goes on behind the last comment, wherever the header says the block
+               ends.  string.unpack raises when a length or a string reaches past the end of the file. */
+            uint64_t ncomments = 0;
+            for (uint64_t i = 0; i <= ncomments; i++) { /* i == 0: the vendor string, with the count behind it */
+                for (int field = 0; field < (i == 0 ? 2 : 1); field++) {
+                    if (pos + 4 > n) return ork__fail(ORK_E_LUA, "data string too short");
+                    uint32_t v = data[pos] | data[pos + 1] << 8 | data[pos + 2] << 16 | (uint32_t)data[pos + 3] << 24;
+                    pos += 4;
+                    if (field == 1) { ncomments = v; break; }
+                    if (v > n - pos) return ork__fail(ORK_E_LUA, "data string too short");
+                    pos += v;
+                }
+            }
         } else {
-            pos += length; /* type 4 is parsed for metadata in the reference; it ends at the same offset */
+            pos += length;
         }
     }
     if (!have) return ork__fail(ORK_E_LUA, "Stream info metadata block absent");

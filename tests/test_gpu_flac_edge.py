@@ -4,6 +4,7 @@ hand-assembled frames whose predictor order exceeds the block / the Rice partiti
 import numpy as np
 import pytest
 
+from tests.flac_write_util import BitWriter, crc8, fixed_subframe, frame, lpc_subframe, streaminfo  # noqa: F401
 from tests.util import pcm16
 
 pytestmark = pytest.mark.gpu
@@ -26,111 +27,6 @@ def _B():
 def _N():
     from aukit_amd import _native as N
     return N
-
-
-class BitWriter:
-    def __init__(self):
-        self.bits = []
-
-    def u(self, v, n):
-        for i in range(n - 1, -1, -1):
-            self.bits.append((v >> i) & 1)
-
-    def s(self, v, n):
-        self.u(v & ((1 << n) - 1), n)
-
-    def rice(self, v, k):
-        u = 2 * v if v >= 0 else -2 * v - 1
-        self.bits.extend([0] * (u >> k))
-        self.bits.append(1)
-        if k:
-            self.u(u & ((1 << k) - 1), k)
-
-    def align(self):
-        while len(self.bits) % 8:
-            self.bits.append(0)
-
-    def bytes(self):
-        self.align()
-        a = np.array(self.bits, dtype=np.uint8).reshape(-1, 8)
-        return bytes(np.packbits(a, axis=1).ravel())
-
-
-def crc8(data):
-    c = 0
-    for b in data:
-        c ^= b
-        for _ in range(8):
-            c = ((c << 1) ^ 0x07) & 0xFF if c & 0x80 else (c << 1) & 0xFF
-    return c
-
-
-def streaminfo(rate, channels, depth, nsamples):
-    w = BitWriter()
-    w.u(16, 16); w.u(65535, 16); w.u(0, 24); w.u(0, 24)
-    w.u(rate, 20); w.u(channels - 1, 3); w.u(depth - 1, 5); w.u(nsamples, 36)
-    body = w.bytes() + bytes(16)
-    assert len(body) == 34
-    return b"fLaC" + bytes([0x80, 0, 0, 34]) + body
-
-
-def frame(bs, subframes, chan_asgn=0, good_crc=True, number=0):
-    """subframes: list of callables(BitWriter) writing one subframe each."""
-    w = BitWriter()
-    w.u(0x3FFE, 14); w.u(0, 2)
-    w.u(6, 4)            # block size: 8-bit (blocksize - 1) follows
-    w.u(9, 4)            # 44.1 kHz
-    w.u(chan_asgn, 4); w.u(4, 3); w.u(0, 1)
-    w.u(number, 8)       # "UTF-8" frame number, one byte
-    w.u(bs - 1, 8)
-    hdr = w.bytes()
-    w.u(crc8(hdr) if good_crc else crc8(hdr) ^ 0x5A, 8)
-    for sf in subframes:
-        sf(w)
-    w.align()
-    w.u(0xBEEF, 16)      # CRC-16: ignored by the reference (:557)
-    return w.bytes()
-
-
-def lpc_subframe(order, depth, warm, precision, shift, coefs, porder, bs, params, residuals, escape_bits=None):
-    def write(w):
-        w.u(0, 1); w.u(31 + order, 6); w.u(0, 1)
-        for v in warm:
-            w.s(int(v), depth)
-        w.u(precision - 1, 4); w.s(shift, 5)
-        for c in coefs:
-            w.s(int(c), precision)
-        w.u(0, 2); w.u(porder, 4)
-        nparts, psize = 1 << porder, bs >> porder
-        it = iter(residuals)
-        for p in range(nparts):
-            start = p * psize + (order if p == 0 else 0)
-            cnt = max(0, (p + 1) * psize - start)
-            if escape_bits is not None and p % 2 == 1:
-                w.u(15, 4); w.u(escape_bits, 5)
-                for _ in range(cnt):
-                    w.s(int(next(it)), escape_bits)
-            else:
-                w.u(params[p % len(params)], 4)
-                for _ in range(cnt):
-                    w.rice(int(next(it)), params[p % len(params)])
-    return write
-
-
-def fixed_subframe(order, depth, warm, porder, bs, param, residuals):
-    def write(w):
-        w.u(0, 1); w.u(8 + order, 6); w.u(0, 1)
-        for v in warm:
-            w.s(int(v), depth)
-        w.u(0, 2); w.u(porder, 4)
-        nparts, psize = 1 << porder, bs >> porder
-        it = iter(residuals)
-        for p in range(nparts):
-            start = p * psize + (order if p == 0 else 0)
-            w.u(param, 4)
-            for _ in range(max(0, (p + 1) * psize - start)):
-                w.rice(int(next(it)), param)
-    return write
 
 
 def _odd_stream(seed):
