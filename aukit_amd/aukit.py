@@ -461,7 +461,7 @@ def au(data):  # aukit.lua:1639
 _MAGIC_KIND = {"wav": N.CONTAINER_WAV, "aiff": N.CONTAINER_AIFF, "au": N.CONTAINER_AU}
 
 
-def _sniff_many(files, stream=False, stream_dfpwm=False):
+def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False):
     """load_many's host half, up to the device call: every file sniffed by magic as `detect` does and walked by aukit_parse_container
     -> ([descriptor per file], [(first payload byte, byte count) per file], [info table per file]).  A file that is no WAV / AIFF / AU / QOA, or
     whose payload is none of PCM, G.711 and DFPWM, raises LuaError naming the file's index (0-based, the position in `files`).
@@ -473,9 +473,18 @@ def _sniff_many(files, stream=False, stream_dfpwm=False):
     third list then holds what the container says the length is, in seconds (NaN where the stream factory's own figure stands).
     `stream_dfpwm` (with `stream`): DFPWM WAV files and raw (data, "dfpwm", ...) entries are taken too, as aukit.stream.many takes them — a WAV's
     length is the container's, a raw entry's is NaN (aukit.stream.dfpwm's own figure, #data * 8 / sampleRate / channels, stands).  Without it they
-    are refused by index, as before aukit_stream_decode_mixed took the codec."""
+    are refused by index, as before aukit_stream_decode_mixed took the codec.
+    `stream_ima` (with `stream`): an IMA-ADPCM WAV file (format 0x11, or extensible with the ADPCM GUID) is taken too — the descriptor is the
+    container walk's, blockAlign included, the payload the `data` chunk, the length NaN (aukit.stream.adpcm's own figure stands, :2992).  Without
+    it such a file is refused by index in the words of before."""
     _expect(1, files, "table")
     takes = "PCM, G.711 and DFPWM" if stream_dfpwm else "PCM and G.711"
+    if stream_ima:
+        takes += " payloads and IMA-ADPCM blocks"
+    served = (N.CODEC_PCM, N.CODEC_G711) if stream and not stream_dfpwm else (N.CODEC_PCM, N.CODEC_G711, N.CODEC_DFPWM)
+    if stream and stream_ima:
+        served += (N.CODEC_ADPCM_WAV,)
+    others = "the other block codecs" if stream_ima else "the block codecs"
     descs, ranges, infos = [], [], []
     for i, f in enumerate(files):
         if isinstance(f, (list, tuple)):
@@ -496,7 +505,7 @@ def _sniff_many(files, stream=False, stream_dfpwm=False):
         kind = detect(bytes(f[:12]))[0]
         if kind == "qoa":
             if stream:
-                raise LuaError(f"file {i}: qoa payload: stream.many takes {takes} (the block codecs keep their own streams)")
+                raise LuaError(f"file {i}: qoa payload: stream.many takes {takes} ({others} keep their own streams)")
             descs.append(B.make_desc(N.CODEC_QOA))
             ranges.append((0, len(f)))
             infos.append({"bitDepth": 16, "dataType": "signed"})   # what aukit.qoa sets
@@ -508,10 +517,10 @@ def _sniff_many(files, stream=False, stream_dfpwm=False):
         except LuaError as e:
             raise LuaError(f"file {i}: {e}") from None
         d = _desc_copy(c)
-        if d.codec not in ((N.CODEC_PCM, N.CODEC_G711) if stream and not stream_dfpwm else (N.CODEC_PCM, N.CODEC_G711, N.CODEC_DFPWM)):
+        if d.codec not in served:
             what = N.WAVDT[c.wav_data_type] if kind == "wav" else f"codec {d.codec}"
             if stream:
-                raise LuaError(f"file {i}: {what} payload: stream.many takes {takes} (the block codecs keep their own streams)")
+                raise LuaError(f"file {i}: {what} payload: stream.many takes {takes} ({others} keep their own streams)")
             raise LuaError(f"file {i}: {what} payload: load_many takes PCM, G.711, DFPWM and QOA files (the block codecs keep their own loaders; the batch API takes IMA blocks)")
         descs.append(d)
         ranges.append((int(c.payload_off), int(c.payload_len)))
@@ -799,15 +808,23 @@ class _StreamNS:
             it, length = self._run(d, p, mono, dtype, endless_empty=d.codec == N.CODEC_G711)
         return it, (length if math.isnan(c.length_seconds) else c.length_seconds)
 
-    def many(self, files, mono=None):
-        """aukit.stream.wav / aiff / au (file, mono) for a LIST of whole files of any mix of containers, rates, PCM formats / G.711 / DFPWM and
+    def many(self, files, mono=None, adpcm=None):
+        """aukit.stream.wav / aiff / au (file, mono) for a LIST of whole files of any mix of containers, rates, PCM formats / G.711 / DFPWM /
+        IMA-ADPCM WAV blocks (each file its own blockAlign; the raise behind a block whose header step index is above 88 included) and
         channel counts: the payload ranges go up as one batch, one aukit_stream_decode_mixed call computes every iterator call of every file, and
         a list of (iterator, length) pairs comes back in input order, each what the file's own factory returns (stream.g711's endless empty
         chunks and the raise behind a stream that ends inside the prefill included).  Without `mono` the files must agree in channel count.
         A raw .dfpwm file, which has no header, is given as (data, "dfpwm"[, channels[, sampleRate]]) — load_many's tuple, channels first — and
-        its pair is aukit.stream.dfpwm(data, sampleRate, channels, mono)'s."""
+        its pair is aukit.stream.dfpwm(data, sampleRate, channels, mono)'s.
+        IMA-ADPCM WAV files are taken on request only — `adpcm=True`, or `mono` given as the options table of the LuaJIT shim,
+        {"mono": ..., "adpcm": True} —: without it such a file is refused by index, as before aukit_stream_decode_mixed took the codec."""
+        if isinstance(mono, dict):
+            if set(mono) - {"mono", "adpcm"}:
+                raise LuaError("bad argument #2 (unknown option " + sorted(set(mono) - {"mono", "adpcm"})[0] + ")")
+            mono, adpcm = mono.get("mono"), mono.get("adpcm", adpcm)
         _expect(2, mono, "boolean", "nil")
-        descs, ranges, lengths = _sniff_many(files, stream=True, stream_dfpwm=True)
+        _expect(3, adpcm, "boolean", "nil")
+        descs, ranges, lengths = _sniff_many(files, stream=True, stream_dfpwm=True, stream_ima=bool(adpcm))
         ctx = context()
         bt = _wrap(B.Batch.upload, ctx, [bytes((f[0] if isinstance(f, (list, tuple)) else f)[o:o + n]) for f, (o, n) in zip(files, ranges)])
         out, ck = _wrap(B.stream_decode_mixed, ctx, bt, descs, _interp(defaultInterpolation, 0), bool(mono), N.F64)

@@ -602,7 +602,8 @@ def stream_decode(ctx, batch, desc, interp, mono=False, dtype=None, out=None):
 
 def stream_decode_mixed(ctx, batch, descs, interp, mono=False, dtype=None, out=None, chunks=None):
     """aukit_stream_decode_mixed: aukit.stream.pcm / aukit.stream.g711 / aukit.stream.dfpwm of stream s with descs[s] (PCM of any format at or below
-    48 kHz, G.711 at integer rates, DFPWM with the descriptor's channels and rate: a pre-pass decodes those streams to int8 rows first), every
+    48 kHz, G.711 at integer rates, DFPWM with the descriptor's channels and rate: a pre-pass decodes those streams to int8 rows first;
+    aukit.stream.adpcm for CODEC_ADPCM_WAV with the descriptor's channels, rate and block_align: a header scan, then a pre-pass to int16 rows), every
     iterator call at once — one call, one resample launch -> (AudioBatch at 48 kHz in the batch's order, Chunks).  `descs`: one
     CodecDesc per stream.  `out` / `chunks`: what an earlier call returned — the audio's buffers are reused, the chunk table is replaced (after
     a refusal both keep what they held)."""

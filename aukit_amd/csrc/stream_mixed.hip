@@ -26,6 +26,16 @@
 // (k_smix_dfpwm_rows).  Iterator call k's table is the row from element 8 * (bytes fed before it) on: audio[0] is the call before's last sample.
 // A tile stages its window of raw int8 values as doubles (16-byte loads; one flat "channel"), a lane per output reads x = (o C) / ratio + 1,
 // v = isint ? audio[x] : clamp(interp(audio, x), -128, 127), and v goes to all C rows or, mixed down, ((0 + v) + v ...) / C to one (Q11).
+//
+// aukit.stream.adpcm (data_s, blockAlign, channels, rate, mono) (:2753-2835) is the third kind (IM = true, launched only for a batch that has an
+// AUKIT_CODEC_ADPCM_WAV stream).  k_smix_ima_scan finds, per stream, the first block that decodes a word under a header step index above 88 — the
+// iterator call that reaches it raises, so the plan ends in front of that call; the host reads the verdict back before anything is sized.  Then
+// k_smix_ima_rows, a lane per (block, channel), decodes every planned block to int16 predictors in ctx->tmp_buf behind the DFPWM scratch: a block's
+// row holds samplesPerBlock + 8 entries per channel, the last eight the junk word's (the next block's header bytes read as nibbles with the running
+// state, Q6).  A segment is a (stream, iterator call); a tile lies within one block — block kb = o0 / floor(samplesPerBlock ratio) of the call — whose
+// table is indices 1 .. 8 * words with the nil fall-backs at both ends, as a G.711 call's.  The tile stages its window of every channel as
+// p / (p < 0 and 128 or 127) (:2812; 16-byte loads), runs the position, fall-back and interpolation code of the other kinds and ends in the G.711
+// epilogue: clamp(floor(c_j)) per channel or clamp(floor(((0 + c_1) + c_2 ...) / channels)) (:2818-2828).
 #include <algorithm>
 #include <string>
 #include <tuple>
@@ -55,17 +65,20 @@ struct SMixClass {
     int exact_rcp;         // 1: RN((i-1)/ratio) via rcp + two fmas is verified exact for 48 001 outputs (DFPWM: for every (i - 1) its longest call reaches)
     int cap;               // LDS doubles per staged channel
     int s16le_mono;        // 16-byte vector staging where the stream's bytes start at an even address
+    unsigned nl_full;      // IMA: floor(samplesPerBlock * ratio), the outputs of a full block  :2768
+    int row_len;           // IMA: int16 entries per (block, channel) in the pre-pass's rows: samplesPerBlock + 8
 };
-static_assert(sizeof(SMixClass) == 80, "SMixClass layout");
+static_assert(sizeof(SMixClass) == 88, "SMixClass layout");
 struct SMixSeg {
-    unsigned long long src_off;  // the stream's first byte, relative to the batch's data (DFPWM: its row's, relative to SMixParams::rows)
-    long long src_base;          // source frame (within the stream) of table index 0
+    unsigned long long src_off;  // the stream's first byte, relative to the batch's data (DFPWM: its row's, relative to SMixParams::rows; IMA: its first row's
+                                 // first int16 entry, relative to SMixParams::rows16)
+    long long src_base;          // source frame (within the stream) of table index 0 (IMA: the call's first block within the stream)
     unsigned long long out_off;  // element offset of output channel 0, output index 0 of this call
-    int w_lo, w_hi;              // valid table indices (anything else reads as nil)
+    int w_lo, w_hi;              // valid table indices (anything else reads as nil) (IMA: of the call's LAST block; a block before it has row_len entries)
     unsigned n_out;
     unsigned out_stride;         // elements between output channels
     unsigned cls;
-    unsigned pad;
+    unsigned nblk;               // IMA: blocks of the call
 };
 static_assert(sizeof(SMixSeg) == 48, "SMixSeg layout");
 struct SMixTile { unsigned seg, o0, cnt; };
@@ -79,6 +92,7 @@ struct SMixParams {
     const unsigned char *safe_lo, *safe_hi;  // the allocation: a 16-byte vector load at p needs safe_lo <= p and p + 16 <= safe_hi
     void *out;
     const signed char *rows;  // DF: the pre-pass's int8 rows (ctx->tmp_buf): 16-byte aligned, 64 bytes to spare behind the last
+    const short *rows16;      // IM: the pre-pass's int16 rows (ctx->tmp_buf, behind the DFPWM scratch): every (block, channel) row at a multiple of 16 bytes
 };
 
 template <bool DF = false>
@@ -143,7 +157,30 @@ AUKIT_DEV int smix_stage_i8(const signed char *row, long long g0, int n_stage, d
     return head;
 }
 
-template <int INTERP, typename OUT_T, bool DF>
+// IM: table indices e0 + 1 .. e0 + n_stage of every channel of one block become the reference's doubles p / (p < 0 and 128 or 127) (:2812) — 16 bytes
+// (eight predictors) per lane from the aligned entry at or below the window.  A (block, channel) row starts at a multiple of 16 bytes and holds
+// row_len entries, a multiple of eight, and the window ends inside it: no load leaves the row; the entries of a short last block that the pre-pass
+// did not write land in slots no output indexes.  The caller keeps head + n_stage + 7 <= cap.  -> the window's first slot
+AUKIT_DEV int smix_stage_i16(const short *row, int e0, int n_stage, int C, int row_len, int cap, double *sm, int tid) {
+    const int head = e0 & 7;
+    const int nvec = (head + n_stage + 7) >> 3;
+    const int total = nvec * C;
+    const double r127 = 1.0 / 127.0;
+    for (int i = tid; i < total; i += 256) {
+        const int c = i / nvec, v = i - c * nvec;
+        const uint4 u = *reinterpret_cast<const uint4 *>(row + (size_t)c * row_len + (e0 - head) + 8 * v);
+        const unsigned w[4] = {u.x, u.y, u.z, u.w};
+        double2 *o = reinterpret_cast<double2 *>(sm + (size_t)c * cap + 8 * v);
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const int lo = ((int)w[e] << 16) >> 16, hi = (int)w[e] >> 16;
+            o[e] = make_double2(lo < 0 ? (double)lo * (1.0 / 128) : div_rcp((double)lo, 127.0, r127), hi < 0 ? (double)hi * (1.0 / 128) : div_rcp((double)hi, 127.0, r127));
+        }
+    }
+    return head;
+}
+
+template <int INTERP, typename OUT_T, bool DF, bool IM>
 __global__ __launch_bounds__(256) void k_stream_mixed(const SMixParams P) {
     extern __shared__ double sm[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -152,10 +189,21 @@ __global__ __launch_bounds__(256) void k_stream_mixed(const SMixParams P) {
 
     for (unsigned t = blockIdx.x; t < P.n_tiles; t += gridDim.x) {
         const SMixTile tl = P.tiles[t];
-        const SMixSeg sg = P.segs[tl.seg];
+        SMixSeg sg = P.segs[tl.seg];
         const SMixClass K = P.classes[sg.cls];
-        const unsigned o0 = tl.o0, cnt = tl.cnt;
+        unsigned o0 = tl.o0;
+        const unsigned cnt = tl.cnt;
         const int C = K.channels, SC = K.stage, cap = K.cap;
+        unsigned long long ima_row = 0;  // IM: the tile's block, channel 0: first int16 entry
+        if constexpr (IM) {
+            if (K.codec == AUKIT_CODEC_ADPCM_WAV) {  // the tile lies within block kb of the call: the block's own table, outputs counted from its first
+                const unsigned kb = o0 / K.nl_full;  // (a short block is the stream's last: every block before it yields nl_full outputs)
+                o0 -= kb * K.nl_full;
+                sg.out_off += (unsigned long long)kb * K.nl_full;
+                if (kb + 1 != sg.nblk) sg.w_hi = K.row_len;  // all its words and the junk word
+                ima_row = sg.src_off + (unsigned long long)(sg.src_base + kb) * (unsigned)C * (unsigned)K.row_len;
+            }
+        }
 
         // window of the table this tile touches
         const unsigned o_first = (K.epi == SMIX_EPI_PCM && o0 > 0) ? o0 - 1 : o0;  // the FIR needs s(o0 - 1)
@@ -174,6 +222,8 @@ __global__ __launch_bounds__(256) void k_stream_mixed(const SMixParams P) {
             const unsigned char *base = P.src + sg.src_off;
             if (DF && K.codec == AUKIT_CODEC_DFPWM) {
                 if constexpr (DF) shift = smix_stage_i8(P.rows + sg.src_off, g0, n_stage, sm, tid);
+            } else if (IM && K.codec == AUKIT_CODEC_ADPCM_WAV) {
+                if constexpr (IM) shift = smix_stage_i16(P.rows16 + ima_row, k_lo - 1, n_stage, C, K.row_len, cap, sm, tid);  // table index 1 is entry 0
             } else if (K.s16le_mono && (((uintptr_t)base) & 1) == 0) {
                 const unsigned char *a0 = base + 2 * g0;
                 const unsigned char *al = (const unsigned char *)((uintptr_t)a0 & ~(uintptr_t)15);
@@ -317,6 +367,91 @@ __global__ __launch_bounds__(256) void k_smix_row_heads(signed char *rows, const
     if (s < n) rows[row_off[s]] = 0;
 }
 
+// ---- aukit.stream.adpcm's pre-pass: codecs.hip's k_ima_scan_headers and k_ima_mixed with the channel count and blockAlign taken per stream
+__constant__ int c_smix_ima_step[89] = {
+    7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 19, 21, 23, 25, 28, 31, 34, 37, 41, 45,
+    50, 55, 60, 66, 73, 80, 88, 97, 107, 118, 130, 143, 157, 173, 190, 209, 230, 253, 279, 307,
+    337, 371, 408, 449, 494, 544, 598, 658, 724, 796, 876, 963, 1060, 1166, 1282, 1411, 1552, 1707, 1878, 2066,
+    2272, 2499, 2749, 3024, 3327, 3660, 4026, 4428, 4871, 5358, 5894, 6484, 7132, 7845, 8630, 9493, 10442, 11487, 12635, 13899,
+    15289, 16818, 18500, 20350, 22385, 24623, 27086, 29794, 32767};  // aukit.lua:161-171
+struct SMixImaStream {
+    unsigned long long src_off;  // the stream's first byte, relative to the batch's data
+    unsigned long long nbytes;
+    unsigned long long row_off;  // rows: the stream's first int16 entry, relative to the IMA rows (a multiple of eight)
+    unsigned long long job0;     // rows: index of its first (block, channel) job
+    int channels, block_align;
+};
+static_assert(sizeof(SMixImaStream) == 40, "SMixImaStream layout");
+
+// word groups block `bi` decodes per channel: i = 4C .. blockAlign inclusive — the junk word (Q6) — while #data >= n + i + 4C  :2800-2802.
+// The caller names a processed block: nbytes - bi * ba >= 4C + 1  :2794
+AUKIT_DEV long long smix_ima_groups(unsigned long long nbytes, unsigned long long bi, unsigned long long ba, unsigned long long hdr) {
+    const unsigned long long rem = nbytes - bi * ba;
+    const long long nwr = (long long)((ba - hdr) / hdr);
+    long long ng = (long long)((rem - 1) / hdr) - 1;
+    ng = ng > nwr + 1 ? nwr + 1 : ng;
+    return ng < 0 ? 0 : ng;
+}
+
+// first block of every stream whose header carries a step index above 88 and that decodes at least one word (0xFFFFFFFF: none): the reference
+// indexes ima_step_table with it unmasked (:2799, :2807).  One wave per stream; writes first_bad only
+__global__ __launch_bounds__(64) void k_smix_ima_scan(const unsigned char *src, const SMixImaStream *st, unsigned n, unsigned *first_bad) {
+    const unsigned s = blockIdx.x;
+    if (s >= n) return;
+    const SMixImaStream S = st[s];
+    const unsigned long long hdr = 4ull * (unsigned)S.channels, ba = (unsigned long long)S.block_align;
+    const unsigned long long nblk = S.nbytes >= hdr + 1 ? (S.nbytes - hdr - 1) / ba + 1 : 0;
+    unsigned best = 0xFFFFFFFFu;
+    for (unsigned long long bi = threadIdx.x; bi < nblk && bi < 0xFFFFFFFFull; bi += 64) {
+        if (smix_ima_groups(S.nbytes, bi, ba, hdr) <= 0) continue;
+        const unsigned char *blk = src + S.src_off + bi * ba;  // (the block has at least 4C + 1 bytes: every header byte read is the stream's)
+        bool bad = false;
+        for (int c = 0; c < S.channels; c++) bad = bad || blk[4 * c + 2] > 88;
+        if (bad) best = min(best, (unsigned)bi);
+    }
+    for (int o = 32; o > 0; o >>= 1) best = min(best, (unsigned)__shfl_xor((int)best, o));
+    if (threadIdx.x == 0) first_bad[s] = best;
+}
+
+// a lane per (block, channel) of every planned block: the header's predictor and step index (unmasked, :2798-2799), then word after word of the
+// channel, eight predictors per word as one 16-byte store (:2803-2812 without the division, which the resample tile does)
+__global__ __launch_bounds__(64) void k_smix_ima_rows(const unsigned char *src, const SMixImaStream *st, unsigned n, unsigned long long njobs, short *rows) {
+    __shared__ int lut[89 * 8];
+    const int lane = threadIdx.x;
+    for (int i = lane; i < 89 * 8; i += 64) { const int sp = c_smix_ima_step[i >> 3]; lut[i] = (int)(((unsigned)(i & 7) * (unsigned)sp) >> 2) + (sp >> 3); }  // :2809 (Q5)
+    __syncthreads();
+    const unsigned long long g = (unsigned long long)blockIdx.x * 64 + (unsigned)lane;
+    if (g >= njobs) return;
+    unsigned lo = 0, hi = n;
+    while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (st[mid].job0 <= g) lo = mid; else hi = mid; }
+    const SMixImaStream S = st[lo];
+    const unsigned C = (unsigned)S.channels;
+    const unsigned long long hdr = 4ull * C, ba = (unsigned long long)S.block_align, j = g - S.job0, bi = j / C;
+    const unsigned c = (unsigned)(j - bi * C);
+    const long long ng = smix_ima_groups(S.nbytes, bi, ba, hdr);
+    const unsigned char *blk = src + S.src_off + bi * ba;
+    int pred = (short)((unsigned)blk[4 * c] | (unsigned)blk[4 * c + 1] << 8);
+    int idx = blk[4 * c + 2];
+    if (ng <= 0 || idx > 88) return;  // (no word; the host plans no block with such an index: kept so that the table is never left)
+    const unsigned long long row_len = (ba - hdr) * 2 / C + 8;
+    short *const o = rows + S.row_off + (bi * C + c) * row_len;
+    typedef unsigned u32u __attribute__((aligned(1)));
+    const unsigned char *wp = blk + hdr + 4 * c;  // this channel's words, 4C bytes apart; the last byte read is blk[4C (ng + 1) - 1], inside the stream
+    for (long long w = 0; w < ng; w++) {
+        const unsigned x = *reinterpret_cast<const u32u *>(wp + (size_t)w * hdr);
+        unsigned pv[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {  // low nibble first  :2803-2806
+            const unsigned nib = (x >> (4 * k)) & 15u;
+            const int diff = lut[idx * 8 + (int)(nib & 7u)];                          // :2807, :2809
+            pred = min(max(pred + ((nib & 8u) ? -diff : diff), -32768), 32767);       // :2810-2811
+            idx = min(max(idx + ((nib & 4u) ? (int)((nib & 3u) + 1) * 2 : -1), 0), 88);  // :2808
+            pv[k] = (unsigned)pred & 0xFFFFu;
+        }
+        *reinterpret_cast<uint4 *>(o + 8 * (size_t)w) = make_uint4(pv[0] | pv[1] << 16, pv[2] | pv[3] << 16, pv[4] | pv[5] << 16, pv[6] | pv[7] << 16);
+    }
+}
+
 // ------------------------------------------------------------------ host
 static int check_smix_pcm(const aukit_codec_desc *d) {  // what check_pcm_desc (api_resample.hip) refuses, with its words
     if (d->bit_depth != 8 && d->bit_depth != 16 && d->bit_depth != 24 && d->bit_depth != 32) return fail(AUKIT_E_ARG, "bad argument #2 (invalid bit depth)");
@@ -328,6 +463,30 @@ static int check_smix_pcm(const aukit_codec_desc *d) {  // what check_pcm_desc (
     return AUKIT_OK;
 }
 
+// aukit.stream.adpcm's derived quantities for one descriptor (:2761, :2765-2768), as ima_stream (codecs.hip) computes them
+struct SMixImaGeom {
+    uint64_t ba, hdr, nwr, ips, row_len;
+    double ratio, spb, iter_per_second, bytes_per_second, newlen_full;
+    explicit SMixImaGeom(const aukit_codec_desc *d) {
+        const int C = d->channels;
+        ba = (uint64_t)d->block_align; hdr = 4ull * C; nwr = (ba - hdr) / hdr;
+        ratio = 48000 / d->sample_rate;                       // :2761
+        spb = (double)(ba - hdr) * 2 / C;                     // samplesPerBlock  :2765
+        iter_per_second = std::ceil(d->sample_rate / spb);    // :2766
+        bytes_per_second = (double)ba * iter_per_second;      // :2767
+        newlen_full = std::floor(spb * ratio);                // :2768
+        ips = iter_per_second < 9e18 ? (uint64_t)iter_per_second : 0;
+        row_len = 8 * (nwr + 1);                              // samplesPerBlock + 8: the junk word's entries behind the block's
+    }
+    uint64_t blocks(uint64_t nb) const { return nb >= hdr + 1 ? (nb - hdr - 1) / ba + 1 : 0; }  // processed: while n + 4C <= #data (1-based n)  :2794
+    uint64_t entries(uint64_t nb, uint64_t bi) const {  // #d[1] of block bi: eight per word group decoded  :2800-2802
+        const uint64_t rem = nb - bi * ba;
+        long long ng = (long long)((rem - 1) / hdr) - 1;
+        if (ng > (long long)nwr + 1) ng = (long long)nwr + 1;
+        return ng < 0 ? 0 : (uint64_t)ng * 8;
+    }
+};
+
 // everything the stream's own aukit_stream_decode call refuses (stream_pcm / stream_g711, api_resample.hip), with its words; and the one thing that
 // call serves and this one does not: the uneven last chunk
 static int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) {
@@ -336,6 +495,18 @@ static int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) 
         if (d->channels < 1 || d->channels > AUKIT_MAX_PLANAR_CHANNELS) return fail(AUKIT_E_ARG, "bad argument #3 (number outside of range)");
         // (a call's outputs are counted in 32 bits there and here: a call of 48 008 C samples at a rate below 1.08 Hz would not fit)
         if ((double)(8 * (6000ull * d->channels + 1)) * (48000 / d->sample_rate) / d->channels > 2147483632.0) return fail(AUKIT_E_UNSUPPORTED, "stream too long");
+        return AUKIT_OK;
+    }
+    if (d->codec == AUKIT_CODEC_ADPCM_WAV) {  // ima_stream's (codecs.hip)
+        const int C = d->channels;
+        if (d->sample_rate < 1) return fail(AUKIT_E_ARG, "bad argument #4 (number outside of range)");
+        if (C < 1 || C > AUKIT_MAX_PLANAR_CHANNELS) return fail(AUKIT_E_ARG, "channels out of range");
+        if (d->block_align <= 4 * C || (d->block_align - 4 * C) % (4 * C) != 0) return fail(AUKIT_E_UNSUPPORTED, "blockAlign must be 4*channels*(k+1)");
+        // blocks are counted, and a call's outputs are, in 32 bits here (one block at 1 Hz yields 48 000 outputs per sample)
+        const SMixImaGeom G(d);
+        const uint64_t nblk = G.blocks(nb);
+        if (nblk > 0x7FFFFFF0ull || G.row_len > 0x7FFFFFF0ull || !(G.iter_per_second < 9e18) || G.newlen_full * (double)std::max<uint64_t>(std::min<uint64_t>(nblk, G.ips), 1) > 2147483632.0)
+            return fail(AUKIT_E_UNSUPPORTED, "stream too long");
         return AUKIT_OK;
     }
     if (d->codec == AUKIT_CODEC_PCM) {
@@ -360,12 +531,12 @@ static int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) 
     return AUKIT_OK;
 }
 
-template <typename OUT_T, bool DF>
+template <typename OUT_T, bool DF, bool IM>
 static int launch_smix(aukit_ctx *ctx, int interp, const SMixParams &P, size_t lds, unsigned grid) {
     switch (interp) {
-    case AUKIT_INTERP_NONE: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_NONE, OUT_T, DF>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
-    case AUKIT_INTERP_LINEAR: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_LINEAR, OUT_T, DF>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
-    default: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_CUBIC, OUT_T, DF>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
+    case AUKIT_INTERP_NONE: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_NONE, OUT_T, DF, IM>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
+    case AUKIT_INTERP_LINEAR: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_LINEAR, OUT_T, DF, IM>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
+    default: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_CUBIC, OUT_T, DF, IM>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
     }
     AUKIT_HIP_CHECK(hipGetLastError());
     return AUKIT_OK;
@@ -383,12 +554,14 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
     if (interp == AUKIT_INTERP_SINC) return fail(AUKIT_E_UNSUPPORTED, "sinc interpolation is not served for per-stream descriptors: stream each class with aukit_stream_decode");
     if (n_descs != in->n) return fail(AUKIT_E_ARG, "%u descriptors for a batch of %u streams", n_descs, in->n);
     const uint32_t n = in->n;
-    bool has_df = false;
+    bool has_df = false, has_ima = false;
     for (uint32_t s = 0; s < n; s++) {
-        if (descs[s].codec != AUKIT_CODEC_PCM && descs[s].codec != AUKIT_CODEC_G711 && descs[s].codec != AUKIT_CODEC_DFPWM)
-            return fail(AUKIT_E_UNSUPPORTED, "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711 and AUKIT_CODEC_DFPWM)", s,
+        if (descs[s].codec != AUKIT_CODEC_PCM && descs[s].codec != AUKIT_CODEC_G711 && descs[s].codec != AUKIT_CODEC_DFPWM && descs[s].codec != AUKIT_CODEC_ADPCM_WAV)
+            return fail(AUKIT_E_UNSUPPORTED,
+                        "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM and AUKIT_CODEC_ADPCM_WAV)", s,
                         descs[s].codec);
         has_df = has_df || descs[s].codec == AUKIT_CODEC_DFPWM;
+        has_ima = has_ima || descs[s].codec == AUKIT_CODEC_ADPCM_WAV;
     }
     if (!mono)
         for (uint32_t s = 1; s < n; s++)
@@ -405,7 +578,7 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
     int hl = 0, hr = 0;
     if (interp == AUKIT_INTERP_LINEAR) { hr = 1; }
     else if (interp == AUKIT_INTERP_CUBIC) { hl = 1; hr = 2; }
-    typedef std::tuple<int, int, int, int, int, int, double> ClassKey;
+    typedef std::tuple<int, int, int, int, int, int, int, double> ClassKey;
     std::map<ClassKey, unsigned> index;
     std::vector<SMixClass> classes;
     std::vector<int> tile_out;  // per class
@@ -413,8 +586,9 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
     size_t lds = 0;
     for (uint32_t s = 0; s < n; s++) {
         const aukit_codec_desc &d = descs[s];
-        const bool pcm = d.codec == AUKIT_CODEC_PCM, df = d.codec == AUKIT_CODEC_DFPWM;
-        const ClassKey key(d.codec, pcm ? d.bit_depth : 8, pcm ? d.data_type : 0, pcm ? (d.big_endian ? 1 : 0) : 0, d.channels, pcm || df ? 0 : (d.ulaw ? 1 : 0), d.sample_rate);
+        const bool pcm = d.codec == AUKIT_CODEC_PCM, df = d.codec == AUKIT_CODEC_DFPWM, ima = d.codec == AUKIT_CODEC_ADPCM_WAV;
+        const ClassKey key(d.codec, pcm ? d.bit_depth : 8, pcm ? d.data_type : 0, pcm ? (d.big_endian ? 1 : 0) : 0, d.channels, pcm || df || ima ? 0 : (d.ulaw ? 1 : 0),
+                           ima ? d.block_align : 0, d.sample_rate);
         auto it = index.find(key);
         if (it == index.end()) {
             SMixClass K;
@@ -456,6 +630,12 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
             if ((size_t)cap_for(to) * 8 * K.stage > hard)
                 return fail(AUKIT_E_UNSUPPORTED, "resampling ratio %g with %d channels needs more than 64 KiB of LDS per tile (stream %u)", K.ratio, K.stage, s);
             K.cap = (cap_for(to) + 1) & ~1;
+            if (ima) {  // stream.adpcm's epilogue is stream.g711's (above); a tile's window never leaves its block's table
+                const SMixImaGeom G(&d);
+                K.nl_full = (unsigned)G.newlen_full;
+                K.row_len = (int)G.row_len;
+                K.cap = (int)std::min<uint64_t>((uint64_t)K.cap, (G.row_len + (uint64_t)slack + 1) & ~1ull);
+            }
             lds = std::max(lds, (size_t)K.cap * 8 * K.stage);
             it = index.emplace(key, (unsigned)classes.size()).first;
             classes.push_back(K);
@@ -465,10 +645,34 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
     }
     AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
     for (SMixClass &K : classes) {
+        if (K.codec == AUKIT_CODEC_ADPCM_WAV) {  // outputs are counted within a block: the verdict covers a full block's, or the kernel divides
+            K.exact_rcp = (K.nl_full <= 4000000u && exact_div_verified(ctx, K.ratio, (uint64_t)K.nl_full + 2)) ? 1 : 0;
+            continue;
+        }
         if (K.epi != SMIX_EPI_DFPWM) { K.exact_rcp = exact_div_verified(ctx, K.ratio, 48001) ? 1 : 0; continue; }  // a segment has at most 48 000 outputs
         // a DFPWM call reads (i - 1) = o * channels up to 8 (6000 C + 1) ratio: the verdict covers all of it (288 048 at 8 kHz), or the kernel divides
         const double top = (double)(8 * (6000ull * K.channels + 1)) * K.ratio + K.channels + 1;
         K.exact_rcp = (top <= 4e6 && exact_div_verified(ctx, K.ratio, (uint64_t)top)) ? 1 : 0;
+    }
+
+    // stream.adpcm: which streams die on a header step index above 88, and in which block — only the device knows, and the rows' lengths depend on it.
+    // The scan writes ctx->scan_buf (the verdicts, the stream table behind them) and nothing else; its answer is awaited here
+    std::vector<SMixImaStream> ima_tab;   // per IMA stream, in batch order
+    std::vector<unsigned> ima_bad;
+    if (has_ima) {
+        for (uint32_t s = 0; s < n; s++)
+            if (descs[s].codec == AUKIT_CODEC_ADPCM_WAV) ima_tab.push_back(SMixImaStream{in->off[s], in->off[s + 1] - in->off[s], 0, 0, descs[s].channels, descs[s].block_align});
+        const size_t m = ima_tab.size(), tab_at = (size_t)round_up(m * 4, 16);
+        ima_bad.assign(m, 0xFFFFFFFFu);
+        int rc0 = ctx->scan_buf.ensure(tab_at + m * sizeof(SMixImaStream) + 16);
+        if (rc0) return rc0;
+        unsigned *d_bad = reinterpret_cast<unsigned *>(ctx->scan_buf.p);
+        SMixImaStream *d_tab = reinterpret_cast<SMixImaStream *>(reinterpret_cast<char *>(ctx->scan_buf.p) + tab_at);
+        if ((rc0 = h2d_table(ctx, d_tab, ima_tab.data(), m * sizeof(SMixImaStream)))) return rc0;
+        hipLaunchKernelGGL(k_smix_ima_scan, dim3((unsigned)m), dim3(64), 0, ctx->stream, in->data(), d_tab, (unsigned)m, d_bad);
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(ima_bad.data(), d_bad, m * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess)
+            return fail(AUKIT_E_HIP, "stream.adpcm header scan failed");
     }
 
     // segments: one per (stream, iterator call); the chunk table beside them.  stream.pcm's plan is made once per distinct rate
@@ -488,6 +692,10 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
     std::map<int, DfGroup> df_groups;
     uint64_t df_tot = 0, df_src = 0;
     uint32_t df_n = 0;
+    // the IMA streams: int16 entries of the rows so far, (block, channel) jobs so far, bytes read; the streams that have a planned block
+    uint64_t ima_elems = 0, ima_jobs = 0, ima_src = 0;
+    size_t ima_i = 0;
+    std::vector<SMixImaStream> ima_rows;
     for (uint32_t s = 0; s < n; s++) {
         const aukit_codec_desc &d = descs[s];
         const uint64_t nb = in->off[s + 1] - in->off[s];
@@ -524,6 +732,44 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
                 df_tot += round_up(fed8 + 1, 16);
                 df_src += nb;
                 df_n++;
+            }
+        } else if (d.codec == AUKIT_CODEC_ADPCM_WAV) {
+            // ima_stream's plan (codecs.hip) from byte 0: an iterator call takes up to iterPerSecond blocks; every block but the stream's last sees at
+            // least blockAlign + 4C more bytes — all its word groups plus the junk word (Q6) — and yields newlen_full outputs, so block k of a call
+            // starts at output k * newlen_full of its chunk; a header index above 88 kills the call that reaches it and everything behind it
+            const SMixImaGeom G(&d);
+            const uint64_t nblk = G.blocks(nb), nl_full = (uint64_t)G.newlen_full;
+            const unsigned bad = ima_bad[ima_i];
+            SMixImaStream &S = ima_tab[ima_i++];
+            ck->length_seconds[s] = (double)nb / (double)G.ba * G.spb / d.sample_rate;  // :2834
+            uint64_t calls_ok = ~0ull, done = 0, planned = 0;
+            if (bad != 0xFFFFFFFFu) { calls_ok = (uint64_t)bad / std::max<uint64_t>(G.ips, 1); ck->status[s] = AUKIT_E_LUA; }  // "attempt to perform arithmetic on a nil value (field '?')"
+            for (uint64_t call = 0; call != calls_ok; call++) {
+                const uint64_t take = std::min<uint64_t>(G.ips, nblk - done);
+                uint64_t full = take, produced = 0, m_last = G.row_len;
+                if (take && done + take == nblk) {  // the stream's last block: the arithmetic of :2800-2802 / :2817
+                    full = take - 1;
+                    m_last = G.entries(nb, nblk - 1);
+                    produced = (double)m_last < G.spb ? (uint64_t)std::floor((double)m_last * G.ratio) : nl_full;
+                }
+                produced += full * nl_full;
+                if (produced == 0) break;  // #retval[1] == 0 -> nil  :2832
+                g.src_off = ima_elems; g.src_base = (long long)done; g.w_lo = 1; g.w_hi = (int)m_last; g.nblk = (unsigned)take; g.n_out = (uint32_t)produced;
+                g.out_off = lens[s];
+                segs.push_back(g);
+                clens[s].push_back((uint32_t)produced);
+                done += take;
+                cpos[s].push_back((double)(done * G.ba + 1) / G.bytes_per_second);  // (n + pos) / bytesPerSecond  :2833
+                lens[s] += produced;
+                planned = done;
+                if (done >= nblk) break;  // the next call sees n + 4C > #data and returns nil
+            }
+            if (planned) {
+                S.row_off = ima_elems; S.job0 = ima_jobs;
+                ima_rows.push_back(S);
+                ima_elems += planned * (uint64_t)C * G.row_len;
+                ima_jobs += planned * (uint64_t)C;
+                ima_src += std::min<uint64_t>(nb, planned * G.ba + G.hdr);
             }
         } else if (d.codec == AUKIT_CODEC_PCM) {
             const int bd = d.bit_depth / 8;
@@ -584,17 +830,27 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
     ck->channels = (uint32_t)C_out;
     for (uint32_t s = 0; s < n; s++) out_elems += lens[s] * (uint64_t)C_out;
     uint64_t nt = 0;
-    for (const SMixSeg &g : segs) nt += (g.n_out + (unsigned)tile_out[g.cls] - 1) / (unsigned)tile_out[g.cls];
-    if (nt > 0xFFFFFFF0ull) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "too many tiles"); }
+    for (const SMixSeg &g : segs) {
+        const uint64_t to = (uint64_t)tile_out[g.cls];
+        if (classes[g.cls].codec == AUKIT_CODEC_ADPCM_WAV) {  // no tile straddles a block: the full blocks' tiles, and the last block's
+            const uint64_t nlf = classes[g.cls].nl_full, last = g.n_out - (uint64_t)(g.nblk - 1) * nlf;
+            nt += (uint64_t)(g.nblk - 1) * ((nlf + to - 1) / to) + (last + to - 1) / to;
+        } else nt += (g.n_out + to - 1) / to;
+    }
+    if (nt > 0xFFFFFFF0ull || ima_jobs > 0x7FFFFFF0ull * 64) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "too many tiles"); }
 
     aukit_audio *a = *out;
     int rc;
     // the pre-pass's scratch: the int8 rows (each at a multiple of 16 bytes, 64 bytes to spare behind the last) and behind them its tables, in
     // ctx->tmp_buf — sized before `*out` is touched.  audio_prepare may swap ctx->tmp_buf for the larger buffer of an `*out` that owes a resample
     // (lazy_drop): the scratch is asked to be at least that large, so it stays, and the pointer is read after it all the same
+    // Behind the DFPWM scratch, at a multiple of 256 bytes: the IMA pre-pass's int16 rows (planned blocks x channels x (samplesPerBlock + 8) entries:
+    // every row at a multiple of 16 bytes) and its stream table.
     const size_t df_tab_at = (size_t)round_up(df_tot + 64, 256);
-    if (df_n) {
-        size_t need = df_tab_at + (size_t)df_n * (8 + sizeof(SMixDfItem)) + 64;
+    const size_t ima_at = df_n ? (size_t)round_up(df_tab_at + (size_t)df_n * (8 + sizeof(SMixDfItem)) + 64, 256) : 0;
+    const size_t ima_tab_at = (size_t)round_up(ima_at + ima_elems * 2 + 64, 256);
+    if (df_n || ima_jobs) {
+        size_t need = ima_jobs ? ima_tab_at + ima_rows.size() * sizeof(SMixImaStream) + 64 : df_tab_at + (size_t)df_n * (8 + sizeof(SMixDfItem)) + 64;
         if (*out && (*out)->lazy_rows.p && !(*out)->lazy_indirect) need = std::max(need, (*out)->lazy_rows.cap);
         if ((rc = ctx->tmp_buf.ensure(need))) { delete ck; return rc; }
     }
@@ -638,6 +894,16 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
         if ((rc = ctx_end_kernel(ctx, engine ? "k_df_chunks(parallel dfpwm decode)" : "k_smix_dfpwm_rows", df_src + df_tot))) { delete ck; return rc; }
     }
 
+    if (ima_jobs) {  // the IMA pre-pass, under its own name
+        short *const rows16 = reinterpret_cast<short *>(reinterpret_cast<char *>(ctx->tmp_buf.p) + ima_at);
+        SMixImaStream *const d_tab = reinterpret_cast<SMixImaStream *>(reinterpret_cast<char *>(ctx->tmp_buf.p) + ima_tab_at);
+        if ((rc = ctx_begin_kernel(ctx)) || (rc = h2d_table(ctx, d_tab, ima_rows.data(), ima_rows.size() * sizeof(SMixImaStream)))) { delete ck; return rc; }
+        hipLaunchKernelGGL(k_smix_ima_rows, dim3((unsigned)((ima_jobs + 63) / 64)), dim3(64), 0, ctx->stream, in->data(), d_tab, (unsigned)ima_rows.size(),
+                           (unsigned long long)ima_jobs, rows16);
+        if (hipGetLastError() != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "IMA pre-pass launch failed"); }
+        if ((rc = ctx_end_kernel(ctx, "k_smix_ima_rows", ima_src + ima_elems * 2))) { delete ck; return rc; }
+    }
+
     std::vector<SMixTile> tiles;
     tiles.reserve((size_t)nt);
     {
@@ -648,6 +914,20 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
                 g.out_off += a->row_off[s];
                 g.out_stride = (unsigned)a->row_stride[s];
                 const unsigned to = (unsigned)tile_out[g.cls];
+                if (classes[g.cls].codec == AUKIT_CODEC_ADPCM_WAV) {
+                    // a block's outputs in equal parts of at most the tile height (12 240 outputs under a height of 2048: six tiles of 2040, no sliver)
+                    const unsigned nlf = classes[g.cls].nl_full;
+                    for (unsigned kb = 0; kb < g.nblk; kb++) {
+                        const unsigned nout = kb + 1 < g.nblk ? nlf : g.n_out - (g.nblk - 1) * nlf;
+                        const unsigned parts = (nout + to - 1) / to, each = parts ? nout / parts : 0, extra = parts ? nout % parts : 0;
+                        for (unsigned p = 0, o0 = kb * nlf; p < parts; p++) {
+                            const unsigned cnt = each + (p < extra ? 1u : 0u);
+                            tiles.push_back(SMixTile{(unsigned)i, o0, cnt});
+                            o0 += cnt;
+                        }
+                    }
+                    continue;
+                }
                 for (unsigned o0 = 0; o0 < g.n_out; o0 += to) tiles.push_back(SMixTile{(unsigned)i, o0, std::min(to, g.n_out - o0)});
             }
     }
@@ -666,14 +946,17 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
     P.safe_hi = in->base + in->cap;
     P.out = a->dev;
     P.rows = reinterpret_cast<const signed char *>(ctx->tmp_buf.p);
+    P.rows16 = reinterpret_cast<const short *>(reinterpret_cast<const char *>(ctx->tmp_buf.p) + ima_at);
     unsigned per_cu = (unsigned)std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1));
     if (per_cu < 1) per_cu = 1;
     per_cu *= 16;  // a finer hand-out than the resident count, as launch_resample: the tiles of a mixed batch differ in cost
     const unsigned grid = std::min<unsigned>(P.n_tiles, (unsigned)ctx->num_cus * per_cu);
     if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
-    // (the DFPWM class lives in instantiations of its own: a batch without one launches the kernels it always did)
-    if (has_df) rc = dtype == AUKIT_F64 ? launch_smix<double, true>(ctx, interp, P, lds, grid) : launch_smix<float, true>(ctx, interp, P, lds, grid);
-    else rc = dtype == AUKIT_F64 ? launch_smix<double, false>(ctx, interp, P, lds, grid) : launch_smix<float, false>(ctx, interp, P, lds, grid);
+    // (the DFPWM and the IMA class live in instantiations of their own: a batch without one launches the kernels it always did)
+    if (has_ima && has_df) rc = dtype == AUKIT_F64 ? launch_smix<double, true, true>(ctx, interp, P, lds, grid) : launch_smix<float, true, true>(ctx, interp, P, lds, grid);
+    else if (has_ima) rc = dtype == AUKIT_F64 ? launch_smix<double, false, true>(ctx, interp, P, lds, grid) : launch_smix<float, false, true>(ctx, interp, P, lds, grid);
+    else if (has_df) rc = dtype == AUKIT_F64 ? launch_smix<double, true, false>(ctx, interp, P, lds, grid) : launch_smix<float, true, false>(ctx, interp, P, lds, grid);
+    else rc = dtype == AUKIT_F64 ? launch_smix<double, false, false>(ctx, interp, P, lds, grid) : launch_smix<float, false, false>(ctx, interp, P, lds, grid);
     if (rc) { delete ck; return rc; }
     static const char *names[] = {"k_stream_mixed<none>", "k_stream_mixed<linear>", "k_stream_mixed<cubic>"};
     if ((rc = ctx_end_kernel(ctx, names[interp], in_bytes + out_elems * dtype_size(dtype)))) { delete ck; return rc; }

@@ -819,11 +819,19 @@ local function stream_container(data, kind, mono, ignoreHeader)
     return it, length
 end
 -- a mixed library streamed in one call (aukit_stream_decode_mixed): `files` = whole WAV / AIFF / AU files of any mix of rates, PCM formats / G.711 /
--- DFPWM and channel counts -> a list of {iterator, length} pairs in input order, each what aukit.stream.wav / aiff / au(file, mono) returns; one
--- upload, one launch.  Without `mono` the files must agree in channel count.  A raw .dfpwm file, which has no header, is given as
+-- DFPWM / IMA-ADPCM WAV blocks and channel counts -> a list of {iterator, length} pairs in input order, each what aukit.stream.wav / aiff / au(file, mono)
+-- returns (aukit.stream.adpcm's raise behind a header step index above 88 included); one upload, one launch.  Without `mono` the files must agree in channel count.  A raw .dfpwm file, which has no header, is given as
 -- {data, "dfpwm"[, channels[, sampleRate]]} (load_many's entry: channels first): its pair is aukit.stream.dfpwm(data, sampleRate, channels, mono)'s.
+-- IMA-ADPCM WAV files are taken on request only: `mono` given as an options table, {mono = ..., adpcm = true}.  Without it such a file is refused by index, as before
+-- aukit_stream_decode_mixed took the codec.
 function aukit.stream.many(files, mono)
-    expect(1, files, "table") expect(2, mono, "boolean", "nil")
+    expect(1, files, "table") expect(2, mono, "boolean", "table", "nil")
+    local adpcm = false
+    if type(mono) == "table" then
+        for k in pairs(mono) do if k ~= "mono" and k ~= "adpcm" then error("bad argument #2 (unknown option " .. tostring(k) .. ")", 2) end end
+        if (mono.mono ~= nil and type(mono.mono) ~= "boolean") or (mono.adpcm ~= nil and type(mono.adpcm) ~= "boolean") then error("bad argument #2 (expected boolean options)", 2) end
+        mono, adpcm = mono.mono, mono.adpcm or false
+    end
     local n = #files
     local descs = ffi.new("aukit_codec_desc[?]", math.max(n, 1))
     local offs = ffi.new("uint64_t[?]", n + 1)
@@ -845,8 +853,11 @@ function aukit.stream.many(files, mono)
             if not kind then error("file " .. (i - 1) .. ": not a WAV, AIFF or AU file", 2) end
             local c = ffi.new("aukit_container")
             if C.aukit_parse_container(ffi.cast("const uint8_t*", f), #f, kind, 1, c) ~= 0 then error("file " .. (i - 1) .. ": " .. ffi.string(C.aukit_last_error()), 2) end
-            if c.desc.codec > 1 and c.desc.codec ~= 5 then  -- 5: AUKIT_CODEC_DFPWM (a WAV with the DFPWM GUID)
-                error("file " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: stream.many takes PCM, G.711 and DFPWM (the block codecs keep their own streams)", 2)
+            -- 5: AUKIT_CODEC_DFPWM (a WAV with the DFPWM GUID); 3: AUKIT_CODEC_ADPCM_WAV (format 0x11 or the ADPCM GUID: the walk's descriptor carries block_align)
+            if c.desc.codec > 1 and c.desc.codec ~= 5 and (c.desc.codec ~= 3 or not adpcm) then
+                error("file " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: " .. (adpcm and
+                      "stream.many takes PCM, G.711 and DFPWM payloads and IMA-ADPCM blocks (the other block codecs keep their own streams)" or
+                      "stream.many takes PCM, G.711 and DFPWM (the block codecs keep their own streams)"), 2)
             end
             descs[i - 1] = c.desc
             parts[i] = f:sub(tonumber(c.payload_off) + 1, tonumber(c.payload_off + c.payload_len))

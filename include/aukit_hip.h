@@ -323,18 +323,28 @@ int aukit_stream_decode_table(aukit_ctx *ctx, const double *values, const uint64
  * length_seconds — is what aukit_stream_decode gives for a one-stream batch of its bytes with descs[s]; every chunk's channels are equally long.
  * fp64 in the reference's order whatever the storage type: AUKIT_F64, or AUKIT_F32 rounded once, at the store (stream.g711's floored integers
  * are exact in both).  `mono` has each codec's own meaning: stream.pcm mixes at read time (:2368), stream.g711 after interpolation (:2908); with
- * one channel it is ignored.  AUKIT_CODEC_PCM (every format stream.pcm takes, rates at or below 48 kHz), AUKIT_CODEC_G711 (integer rates) and
+ * one channel it is ignored.  AUKIT_CODEC_PCM (every format stream.pcm takes, rates at or below 48 kHz), AUKIT_CODEC_G711 (integer rates),
  * AUKIT_CODEC_DFPWM (the descriptor's `channels` and `sample_rate`, rates above 48 kHz included; positions count from byte 0 whatever a stream
- * handle on the context carries; the same sample goes to every channel, and `mono` is ((0 + v) + v ...) / channels, :2485-2488) only,
- * interpolation none / linear / cubic; anything else is AUKIT_E_UNSUPPORTED by name.  A batch with a DFPWM stream pays a pre-pass in front of the
+ * handle on the context carries; the same sample goes to every channel, and `mono` is ((0 + v) + v ...) / channels, :2485-2488) and
+ * AUKIT_CODEC_ADPCM_WAV (IMA-ADPCM WAV blocks, below) only, interpolation none / linear / cubic; anything else is AUKIT_E_UNSUPPORTED by name.  A batch with a DFPWM stream pays a pre-pass in front of the
  * one resample launch: every DFPWM stream is decoded to a flat int8 row in the context's scratch (the chunk-parallel decoder, one run per distinct
  * channel count, or a lane per stream where every stream is short) — element 0 a leading 0, then the samples in feed order (slices of
  * 6000 * channels + 1 bytes advanced by 6000 * channels, the slice's last byte decoded again as the next one's first), rows at multiples of 16
- * bytes — and iterator call k's table is the row from the call before's last sample on.  n_descs must be the batch's stream count; without
+ * bytes — and iterator call k's table is the row from the call before's last sample on.
+ * AUKIT_CODEC_ADPCM_WAV is aukit.stream.adpcm (data_s, block_align, channels, sample_rate, mono) (:2753-2835): the descriptor's `channels`
+ * (1 .. 64), `sample_rate` (>= 1, any rate) and `block_align` (4 * channels * (k + 1)) are the stream's own; positions count from byte 0; the
+ * samples are clamp(floor(v)) per channel, or clamp(floor(((0 + c1) + c2 ...) / channels)) with `mono` (for one channel too), exact in both
+ * storage types.  A batch with such a stream pays a header scan and a second pre-pass: the scan (per stream the first block that decodes a word
+ * under a header step index above 88; it writes context scratch only) is read back before anything is sized, because the iterator call that
+ * reaches such a block raises — status[s] = AUKIT_E_LUA, the chunks of the calls before it are delivered, that call's and everything behind it
+ * are not —; then a lane per (block, channel) decodes every planned block to an int16 row of predictors in the context's scratch, behind the
+ * int8 rows and 16-byte aligned: up to samplesPerBlock + 8 entries per channel, the last eight those of the junk word (the next block's header
+ * bytes read as nibbles, Q6).  A block is one independent table, indices 1 .. 8 * words, and block k of a call writes its outputs at
+ * k * floor(samplesPerBlock * ratio) of the call's chunk.  n_descs must be the batch's stream count; without
  * `mono` the descriptors must agree in channel count (AUKIT_E_ARG).  A stream whose own call would fail fails the whole call with that status
  * and message, the stream's index appended.  PCM data that ends inside a frame is served with the mix-down (the partial frame counts for
  * nothing) and refused without it whatever AUKIT_OPT_CHANNEL_LENS says: the uneven last chunk stays with aukit_stream_decode.  Every refusal
- * happens before anything is allocated or launched and leaves `*out` and `*chunks` as they were. */
+ * happens before anything is allocated or launched (the header scan and its scratch excepted) and leaves `*out` and `*chunks` as they were. */
 int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs /* n */, uint32_t n_descs,
                               int interp, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks);
 /* per stream s: nchunks[s]; chunk k of stream s: length and the iterator's second return value.

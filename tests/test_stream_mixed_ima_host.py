@@ -1,0 +1,138 @@
+"""CPU: Library I (tests/stream_mixed_ima_util.py) holds the shapes AUKIT_CODEC_ADPCM_WAV in aukit_stream_decode_mixed can go wrong at and every
+stream of it runs on the oracle; aukit.stream.many's host half with IMA-ADPCM WAV files taken (the `stream_ima` keyword of aukit._sniff_many:
+descriptor with block_align, payload range, NaN length — everything up to the device call); and what the header and the LuaJIT shim say about
+the codec."""
+import math
+import os
+import struct
+
+import pytest
+
+import aukit_amd.aukit as aukit
+from tests import mixed_dfpwm_util as D
+from tests import mixed_util as M
+from tests import stream_mixed_ima_util as I
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def lib(oracle):
+    return I.library_i(oracle, "linear")
+
+
+def test_library_holds_the_shapes(lib):
+    ima = [s for s in lib if s["kind"] == "ima"]
+    assert len(ima) == 26 and len(lib) == 38 and {s["kind"] for s in lib} == {"ima", "pcm", "g711", "dfpwm"}
+    assert lib[0]["kind"] == lib[-1]["kind"] == "ima"
+    assert {(s["ch"], s["block_align"]) for s in ima} == set(I.SHAPES) and {s["rate"] for s in ima} == set(I.RATES)
+    assert sum(len(s["bytes"]) for s in lib) < 2_000_000
+    ev = lambda e, s: int(eval(e, {}, dict(C=s["ch"], ips=I.geometry(s["ch"], s["block_align"], s["rate"])[1])))
+    for e in I.BLOCKS:
+        assert any(s["blocks"] == ev(e, s) for s in ima), e
+    for e in I.TAILS:
+        assert any(s["tail"] == ev(e, s) and s["blocks"] > 0 for s in ima), e
+    # (1, 8) at 22050 Hz: 2757 and 2758 blocks; one block of (1, 8) with nothing behind it
+    assert {s["blocks"] for s in ima if (s["ch"], s["block_align"], s["rate"]) == (1, 8, 22050)} == {2757, 2758}
+    assert any((s["ch"], s["block_align"], s["blocks"], s["tail"]) == (1, 8, 1, 0) for s in ima)
+    pairs = list(zip(lib, lib[1:]))
+    assert any(a["kind"] == b["kind"] == "ima" and (a["ch"], a["rate"]) == (b["ch"], b["rate"]) and a["block_align"] != b["block_align"] for a, b in pairs)
+    keys = [(s["ch"], s["rate"], s["block_align"]) for s in ima]
+    assert any(keys.count(k) >= 2 and len({len(s["bytes"]) for s in ima if (s["ch"], s["rate"], s["block_align"]) == k}) >= 2 for k in keys)
+    assert sorted(s["bad"] for s in ima if s["bad"] is not None) == [0, 345]
+
+
+def test_every_stream_runs_on_the_oracle(oracle, lib):
+    for mono in (True, False):
+        for s in lib:
+            if s["kind"] != "ima":
+                continue
+            ref = I.oracle_stream(oracle, s, "linear", mono)
+            what = (s["ch"], s["block_align"], s["rate"], s["spec"], s["bad"])
+            assert ref.channels == (1 if mono else s["ch"]), what
+            spb, ips, full = I.geometry(s["ch"], s["block_align"], s["rate"])
+            assert ref.length_seconds == len(s["bytes"]) / s["block_align"] * spb / s["rate"], what
+            if s["bad"] is None:
+                assert ref.final_status == 0, what
+            elif s["bad"] == 0:
+                assert ref.final_status == -2 and ref.nchunks == 0, what
+            else:
+                assert ref.final_status == -2 and ref.nchunks == 1 and int(ref.chunk_len[0, 0]) == 47955 == ips * full, what
+            if (s["ch"], s["block_align"], s["rate"]) == (1, 8, 22050):   # the second call, of one block without a word, is empty and ends the stream
+                assert ips == 2757 and ref.nchunks == 1 and int(ref.chunk_len[0, 0]) == (s["blocks"] - 1) * full, what   # (the stream's last block has no word)
+            if (s["block_align"], s["blocks"], s["tail"]) == (8, 1, 0):
+                assert ref.nchunks == 0, what
+            if s["rate"] == 11025.5 and s["blocks"] > 1:
+                assert int(ref.chunk_len[0, 0]) == 48094 and ref.nchunks == 2, what
+            if (s["block_align"], s["rate"]) == (1024, 8000):
+                assert full == 12240, what
+
+
+def _ima_files(oracle):
+    import numpy as np
+    rng = np.random.Generator(np.random.PCG64(0x1AF1))
+    a = I.ima_stream(oracle, rng, 1, 256, 22050, 3, "4 * C + 1", True)
+    b = I.ima_stream(oracle, rng, 2, 72, 44100, 5, 0, False)
+    return [(a, I.ima_wav(a)), (b, I.ima_wav(b, extensible=True))]
+
+
+def test_stream_many_sniffs_ima_wav_files(oracle):
+    from aukit_amd import _native as N
+    entries, _ = D.four_entries()
+    ima = _ima_files(oracle)
+    files = [entries[0], ima[0][1], entries[1], ima[1][1]]
+    descs, ranges, lengths = aukit._sniff_many(files, stream=True, stream_dfpwm=True, stream_ima=True)
+    assert [d.codec for d in descs] == [N.CODEC_PCM, N.CODEC_ADPCM_WAV, N.CODEC_DFPWM, N.CODEC_ADPCM_WAV]
+    for i, (s, f) in ((1, ima[0]), (3, ima[1])):
+        d = descs[i]
+        assert (d.channels, d.sample_rate, d.block_align) == (s["ch"], s["rate"], s["block_align"]), i
+        c, p = aukit._parse(f, N.CONTAINER_WAV, stream=True)   # what aukit.stream.wav hands to aukit.stream.adpcm
+        assert ranges[i] == (c.payload_off, c.payload_len) and p == s["bytes"] and f[ranges[i][0]:ranges[i][0] + ranges[i][1]] == s["bytes"], i
+        assert math.isnan(lengths[i]), i
+    assert lengths[0] == 1200 / 44100 and not math.isnan(lengths[2])
+
+
+def test_the_keyword_means_nothing_without_stream_and_the_old_words_stand(oracle):
+    ima = _ima_files(oracle)
+    files, _ = M.six_files()
+    with pytest.raises(aukit.LuaError, match=r"file 0: adpcm payload: stream\.many takes PCM, G\.711 and DFPWM \(the block codecs keep their own streams\)"):
+        aukit._sniff_many([ima[0][1]], stream=True, stream_dfpwm=True)
+    with pytest.raises(aukit.LuaError, match=r"file 1: adpcm payload: load_many takes .*the batch API takes IMA blocks"):
+        aukit._sniff_many([files[0], ima[0][1]], stream_ima=True)
+    a, b = aukit._sniff_many(files[:5]), aukit._sniff_many(files[:5], stream_ima=True)
+    assert a[1] == b[1] and a[2] == b[2] and [bytes(d) for d in a[0]] == [bytes(d) for d in b[0]]
+    # aukit.stream.many takes IMA files on request only: by default the refusal of before, raised ahead of any device work
+    for args in ((True,), (True, False), ({"mono": True},)):
+        with pytest.raises(aukit.LuaError, match=r"file 1: adpcm payload: stream\.many takes PCM, G\.711 and DFPWM \(the block codecs keep their own streams\)"):
+            aukit.stream.many([files[0], ima[0][1]], *args)
+    with pytest.raises(aukit.LuaError, match=r"bad argument #3"):
+        aukit.stream.many([files[0]], True, "yes")
+    with pytest.raises(aukit.LuaError, match=r"bad argument #2 \(unknown option stereo\)"):
+        aukit.stream.many([files[0]], {"stereo": True})
+
+
+def test_stream_many_still_refuses_msadpcm_and_qoa_by_index(oracle):
+    ima = _ima_files(oracle)
+    ms = M._wav(struct.pack("<HHIIHH", 2, 1, 22050, 11100, 256, 4) + struct.pack("<HHH", 4, 500, 0), bytes(512))
+    words = r"stream\.many takes PCM, G\.711 and DFPWM payloads and IMA-ADPCM blocks \(the other block codecs keep their own streams\)"
+    with pytest.raises(aukit.LuaError, match=r"file 1: msadpcm payload: " + words):
+        aukit._sniff_many([ima[0][1], ms], stream=True, stream_dfpwm=True, stream_ima=True)
+    with pytest.raises(aukit.LuaError, match=r"file 2: qoa payload: " + words):
+        aukit._sniff_many([ima[0][1], ima[1][1], b"qoaf" + bytes(60)], stream=True, stream_dfpwm=True, stream_ima=True)
+
+
+def test_header_and_shim_name_the_codec():
+    text = open(os.path.join(ROOT, "include", "aukit_hip.h")).read()
+    at = text.index("int aukit_stream_decode_mixed(")
+    comment = text[text.rindex("/*", 0, at):at]
+    for w in ("AUKIT_CODEC_ADPCM_WAV", "aukit.stream.adpcm", "block_align", "int16 row", "header scan", "AUKIT_E_LUA", "above 88"):
+        assert w in comment, w
+    assert "#define AUKIT_ABI_VERSION 2" in text
+    lua = open(os.path.join(ROOT, "aukit_amd", "lua", "aukit.lua")).read()
+    at = lua.index("function aukit.stream.many(files, mono)")
+    body = lua[at:lua.index("\nend\n", at)]
+    assert "AUKIT_CODEC_ADPCM_WAV" in body and "c.desc.codec ~= 3" in body and "descs[i - 1] = c.desc" in body   # the walk's descriptor, block_align included
+    assert "stream.many takes PCM, G.711 and DFPWM payloads and IMA-ADPCM blocks (the other block codecs keep their own streams)" in body
+    assert "mono.adpcm" in body and "(c.desc.codec ~= 3 or not adpcm)" in body   # on request only: {mono = ..., adpcm = true} in place of `mono`
+    src = open(os.path.join(ROOT, "aukit_amd", "csrc", "stream_mixed.hip")).read()
+    assert "AUKIT_CODEC_DFPWM and AUKIT_CODEC_ADPCM_WAV)" in src   # the "has its own stream" refusal names the codec among those served
