@@ -16,16 +16,6 @@ int stream_block_codec(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_
 int launch_stream_pcm_sinc(aukit_ctx *ctx, const std::vector<SincCall> &calls, const SincMap &m, const aukit_batch *in, const aukit_codec_desc *d,
                            bool table, bool mono, int dtype, aukit_audio *a, uint64_t algorithmic_bytes);   // stream_pcm_sinc.hip
 
-static int check_pcm_desc(const aukit_codec_desc *d) {
-    if (d->bit_depth != 8 && d->bit_depth != 16 && d->bit_depth != 24 && d->bit_depth != 32) return fail(AUKIT_E_ARG, "bad argument #2 (invalid bit depth)");
-    if (d->data_type < 0 || d->data_type > 2) return fail(AUKIT_E_ARG, "bad argument #3 (invalid data type)");
-    if (d->data_type == AUKIT_FLOAT && d->bit_depth != 32) return fail(AUKIT_E_ARG, "bad argument #2 (float audio must have 32-bit depth)");
-    if (d->channels < 1) return fail(AUKIT_E_ARG, "bad argument #4 (number outside of range)");
-    if (d->sample_rate < 1) return fail(AUKIT_E_ARG, "bad argument #5 (number outside of range)");
-    if (d->channels > AUKIT_MAX_PLANAR_CHANNELS) return fail(AUKIT_E_UNSUPPORTED, "at most %d channels are supported", AUKIT_MAX_PLANAR_CHANNELS);
-    return AUKIT_OK;
-}
-
 static void fill_source(ResampleParams &P, const aukit_batch *in, const aukit_codec_desc *d) {
     P.src = in->data();
     P.src_off = reinterpret_cast<const unsigned long long *>(in->d_off);

@@ -11,6 +11,7 @@
 #include <type_traits>
 #include <map>
 #include "resample.h"
+#include "ima_geom.h"
 #include "resample_dev.h"
 #include "dfpwm_dev.h"
 
@@ -306,13 +307,7 @@ static int dfpwm_decode_audio(aukit_ctx *ctx, const aukit_batch *in, const aukit
 }
 
 // ================================================================= IMA ADPCM
-__constant__ int c_ima_step[89] = {
-    7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 19, 21, 23, 25, 28, 31, 34, 37, 41, 45,
-    50, 55, 60, 66, 73, 80, 88, 97, 107, 118, 130, 143, 157, 173, 190, 209, 230, 253, 279, 307,
-    337, 371, 408, 449, 494, 544, 598, 658, 724, 796, 876, 963, 1060, 1166, 1282, 1411, 1552, 1707, 1878, 2066,
-    2272, 2499, 2749, 3024, 3327, 3660, 4026, 4428, 4871, 5358, 5894, 6484, 7132, 7845, 8630, 9493, 10442, 11487, 12635, 13899,
-    15289, 16818, 18500, 20350, 22385, 24623, 27086, 29794, 32767};  // aukit.lua:161-171
-
+// (the step table, c_ima_step: ima_geom.h)
 struct Sat { int a, lo, hi; };  // x -> clamp(x + a, lo, hi)
 // clamp(v, lo, hi) for lo <= hi as ONE v_med3_i32 (left to itself hipcc builds part of these out of compares and selects; the IMA kernels are bound
 // by their VALU instructions)
@@ -1414,13 +1409,10 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     if (d->block_align <= 4 * C || (d->block_align - 4 * C) % (4 * C) != 0) return fail(AUKIT_E_UNSUPPORTED, "blockAlign must be 4*channels*(k+1)");
     if (interp < 0 || interp > 3) return fail(AUKIT_E_ARG, "invalid interpolation");
     if (dtype != AUKIT_I8 && dtype != AUKIT_F64) return fail(AUKIT_E_ARG, "stream.adpcm output must be AUKIT_I8 or AUKIT_F64");
-    const uint64_t ba = (uint64_t)d->block_align;
-    const double ratio = 48000 / d->sample_rate;                                   // :2761
-    const double spb = (double)(ba - 4ull * C) * 2 / C;                            // :2765
-    const double iterPerSecond = std::ceil(d->sample_rate / spb);                  // :2766
-    const double bytesPerSecond = (double)ba * iterPerSecond;                      // :2767
-    const uint32_t newlen_full = (uint32_t)std::floor(spb * ratio);                // :2768
-    const uint64_t ips = (uint64_t)iterPerSecond;
+    const ImaGeom G(C, d->block_align, d->sample_rate);  // :2761, :2765-2768
+    const uint64_t ba = G.ba, ips = G.ips;
+    const double ratio = G.ratio, spb = G.spb;
+    const uint32_t newlen_full = (uint32_t)G.newlen_full;
     const int nd = mono ? 1 : C;
     aukit_chunks *ck = new aukit_chunks();
     ck->n = in->n;
@@ -1450,33 +1442,16 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     struct Plan { uint64_t blocks = 0, total = 0; std::vector<uint32_t> len; std::vector<double> pos; };
     auto make_plan = [&](uint64_t nb, uint64_t calls_ok) {
         Plan pl;
-        // blocks processed: while n + 4C <= #data (1-based n)  :2794
-        const uint64_t nblk = nb >= 4ull * C + 1 ? (nb - 4ull * C - 1) / ba + 1 : 0;
+        const uint64_t nblk = G.blocks(nb);
         pl.blocks = calls_ok == ~0ull ? nblk : std::min<uint64_t>(nblk, calls_ok * ips);
         uint64_t done = 0;
-        for (uint64_t call = 0;; call++) {  // one iterator call = up to iterPerSecond blocks
-            if (call == calls_ok) break;
-            const uint64_t take = std::min<uint64_t>(ips, nblk - done);
-            // every block but the stream's last sees at least blockAlign + 4C more bytes — all its word groups plus the junk word (Q6) —
-            // and yields newlen_full outputs; only the last block needs the arithmetic of :2800-2802 / :2817
-            uint64_t full = take, produced = 0;
-            if (take && done + take == nblk) {
-                full = take - 1;
-                const uint64_t rem = nb - (nblk - 1) * ba;
-                long long ng = (long long)((rem - 1) / (4ull * C)) - 1;
-                const long long nwr = (long long)((ba - 4ull * C) / (4ull * C));
-                if (ng > nwr + 1) ng = nwr + 1;
-                if (ng < 0) ng = 0;
-                const uint64_t nbn = (uint64_t)ng * 8;
-                produced += ((double)nbn < spb) ? (uint64_t)std::floor((double)nbn * ratio) : newlen_full;
-            }
-            produced += full * newlen_full;
-            // a short block is always the last one (n advances past #data), so block b's outputs start at b * newlen_full
-            done += take;
-            if (produced == 0) break;  // #retval[1] == 0 → nil
-            pl.len.push_back((uint32_t)produced);
-            pl.pos.push_back(((double)(done * ba + ctx->sb_bytes + 1)) / bytesPerSecond);  // (n + pos) / bytesPerSecond :2833 (sb_bytes: what a stream handle dropped)
-            pl.total += produced;
+        for (uint64_t call = 0; call != calls_ok; call++) {  // one iterator call = up to iterPerSecond blocks (ima_call, ima_geom.h)
+            const ImaCall c = ima_call(G, nb, nblk, done);
+            done += c.take;
+            if (c.produced == 0) break;  // #retval[1] == 0 → nil
+            pl.len.push_back((uint32_t)c.produced);
+            pl.pos.push_back(((double)(done * ba + ctx->sb_bytes + 1)) / G.bytes_per_second);  // (n + pos) / bytesPerSecond :2833 (sb_bytes: what a stream handle dropped)
+            pl.total += c.produced;
             if (done >= nblk) break;   // the next call sees n + 4C > #data and returns nil
         }
         return pl;

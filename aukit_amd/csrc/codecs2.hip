@@ -196,9 +196,6 @@ __global__ __launch_bounds__(64) void k_mdfpwm_decode(const unsigned char *src, 
     }
 }
 
-bool dfpwm_decode_parallel_feed(aukit_ctx *ctx, const unsigned char *src, const std::vector<uint64_t> &h_off, const std::vector<uint64_t> &h_fed, uint64_t run,
-                                uint64_t stride, int mode, int C, signed char *out, const unsigned long long *d_out_off, const unsigned long long *d_out_stride,
-                                uint64_t lead, int *rc, const DfSliceHook *hook = nullptr);
 struct MdHeader { uint64_t payload, length; };
 static int mdfpwm_header(const uint8_t *h, uint64_t nb, MdHeader *out, const char *badmsg) {
     if (nb < 7 || memcmp(h, "MDFPWM\3", 7) != 0) return fail(AUKIT_E_ARG, "%s", badmsg);

@@ -1,0 +1,172 @@
+// mixed_plan.h — what the two per-stream-descriptor calls share on the host (aukit_decode_resample_mixed, resample_mixed.hip;
+// aukit_stream_decode_mixed, stream_mixed.hip): the checks of the call's own arguments, the class index, the tile-height search, the grid, the
+// launcher of a kernel template instantiated over <INTERP, OUT_T, flags...>, the driver of the DFPWM row pre-pass, and the layout of the
+// pre-passes' scratch in ctx->tmp_buf.  Host only: no kernel lives here.
+#pragma once
+#include <algorithm>
+#include <type_traits>
+#include "resample.h"
+
+namespace aukit {
+
+// the call's own arguments.  The two calls word the interpolation refusal differently and name different calls for sinc: `bad_interp`, `sinc_hint`
+static inline int mixed_check_call(const aukit_ctx *ctx, const aukit_batch *in, const void *out, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int dtype,
+                                   const char *bad_interp, const char *sinc_hint) {
+    if (!ctx || !in || !out || (!descs && n_descs)) return fail(AUKIT_E_ARG, "null argument");
+    if (dtype != AUKIT_F64 && dtype != AUKIT_F32) return fail(AUKIT_E_ARG, "dtype must be AUKIT_F64 or AUKIT_F32");
+    if (interp < 0 || interp > 3) return fail(AUKIT_E_ARG, "%s", bad_interp);
+    if (interp == AUKIT_INTERP_SINC) return fail(AUKIT_E_UNSUPPORTED, "sinc interpolation is not served for per-stream descriptors: %s", sinc_hint);
+    if (n_descs != in->n) return fail(AUKIT_E_ARG, "%u descriptors for a batch of %u streams", n_descs, in->n);
+    return AUKIT_OK;
+}
+
+// every codec must be one of `served`.  `words`: the call's refusal, a format of the stream's index (%u) and its codec (%d), which names what the
+// call serves
+static inline int mixed_check_codecs(const aukit_codec_desc *descs, uint32_t n, std::initializer_list<int> served, const char *words) {
+    for (uint32_t s = 0; s < n; s++)
+        if (std::find(served.begin(), served.end(), descs[s].codec) == served.end()) return fail(AUKIT_E_UNSUPPORTED, words, s, descs[s].codec);
+    return AUKIT_OK;
+}
+
+// without the mix-down every stream has the channel count of the first.  channels_of(s): the descriptor's, or (QOA) the file header's
+template <class ChannelsOf>
+static inline int mixed_check_channels(uint32_t n, int mono, ChannelsOf channels_of) {
+    if (!mono)
+        for (uint32_t s = 1; s < n; s++)
+            if (channels_of(s) != channels_of(0)) return fail(AUKIT_E_ARG, "streams differ in channel count: mix down or split the batch");
+    return AUKIT_OK;
+}
+
+// the stream's own call would fail: its status and words, and which stream it is
+static inline int fail_for_stream(int rc, unsigned s) {
+    const std::string m = aukit_last_error();
+    return fail(rc, "%s (stream %u)", m.c_str(), s);
+}
+
+// taps below / above floor(x)
+static inline void mixed_halos(int interp, int *hl, int *hr) {
+    *hl = interp == AUKIT_INTERP_CUBIC ? 1 : 0;
+    *hr = interp == AUKIT_INTERP_CUBIC ? 2 : interp == AUKIT_INTERP_LINEAR ? 1 : 0;
+}
+
+// key -> class number, in order of first appearance
+template <class Key>
+struct ClassIndex {
+    std::map<Key, unsigned> index;
+    unsigned of(const Key &key, bool *fresh) { const auto r = index.emplace(key, (unsigned)index.size()); *fresh = r.second; return r.first->second; }
+};
+
+// The launch both calls end in: the class, segment and tile tables go to the context's buffers, P gets them and the source, the output and the
+// pre-passes' rows, launch(grid) enqueues the kernel for a grid-stride walk of the tiles — 16 workgroups per resident one, a finer hand-out than the
+// resident count, as launch_resample: the tiles of a mixed batch differ in cost — and the timed region is closed under names[interp]
+template <class Params, class Class, class Seg, class Tile, class Launch>
+static inline int mixed_launch(aukit_ctx *ctx, const aukit_batch *in, const aukit_audio *a, const std::vector<Class> &classes, const std::vector<Seg> &segs,
+                               const std::vector<Tile> &tiles, Params &P, size_t lds, const char *name, uint64_t algorithmic_bytes, Launch launch) {
+    int rc;
+    if ((rc = upload_table(ctx, ctx->misc_buf, classes.data(), classes.size() * sizeof(Class))) || (rc = upload_table(ctx, ctx->seg_buf, segs.data(), segs.size() * sizeof(Seg))) ||
+        (rc = upload_table(ctx, ctx->tile_buf, tiles.data(), tiles.size() * sizeof(Tile))))
+        return rc;
+    P.tiles = reinterpret_cast<const Tile *>(ctx->tile_buf.p);
+    P.segs = reinterpret_cast<const Seg *>(ctx->seg_buf.p);
+    P.classes = reinterpret_cast<const Class *>(ctx->misc_buf.p);
+    P.n_tiles = (unsigned)tiles.size();
+    P.src = in->data();
+    P.safe_lo = in->base;
+    P.safe_hi = in->base + in->cap;
+    P.out = a->dev;
+    P.rows = reinterpret_cast<const signed char *>(ctx->tmp_buf.p);
+    unsigned per_cu = (unsigned)std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1));
+    if (per_cu < 1) per_cu = 1;
+    if ((rc = ctx_begin_kernel(ctx))) return rc;
+    launch(std::min<unsigned>(P.n_tiles, (unsigned)ctx->num_cus * per_cu * 16));
+    AUKIT_HIP_CHECK(hipGetLastError());
+    return ctx_end_kernel(ctx, name, algorithmic_bytes);
+}
+
+// Tile height of a class: the staged window (tile_out / eff_ratio + slack doubles) x staged channels x 8 B within plan_tiles' budget of 24 KiB, where
+// that leaves at least 256 outputs; `hard` bytes at the most (what a launch may ask for).  slack: the halos, the vector paths' alignment head and
+// tail and the kernel's own margin.  -> *tile_out, and *cap: LDS doubles per staged channel (even).  `ratio`, `s`: for the words of the refusal
+static inline int mixed_tile_height(double ratio, double eff_ratio, int staged, int slack, size_t hard, unsigned s, int *tile_out, int *cap) {
+    auto cap_for = [&](int to) { return (int)std::ceil((double)to / eff_ratio) + slack; };
+    const size_t budget = 24 * 1024;
+    int to = 2048;
+    while (to > 256 && (size_t)cap_for(to) * 8 * staged > budget) to -= 256;
+    while (to > 64 && (size_t)cap_for(to) * 8 * staged > hard) to -= 64;
+    if ((size_t)cap_for(to) * 8 * staged > hard)
+        return fail(AUKIT_E_UNSUPPORTED, "resampling ratio %g with %d channels needs more than 64 KiB of LDS per tile (stream %u)", ratio, staged, s);
+    *tile_out = to;
+    *cap = (cap_for(to) + 1) & ~1;
+    return AUKIT_OK;
+}
+
+// f(std::integral_constant<int, INTERP>, OUT_T()) for the run-time interpolation (none, linear, cubic) and output type (AUKIT_F64, AUKIT_F32)
+template <class F>
+static inline void mixed_dispatch(int interp, int dtype, F &&f) {
+    auto typed = [&](auto t) {
+        switch (interp) {
+        case AUKIT_INTERP_NONE: f(std::integral_constant<int, AUKIT_INTERP_NONE>(), t); break;
+        case AUKIT_INTERP_LINEAR: f(std::integral_constant<int, AUKIT_INTERP_LINEAR>(), t); break;
+        default: f(std::integral_constant<int, AUKIT_INTERP_CUBIC>(), t); break;
+        }
+    };
+    if (dtype == AUKIT_F64) typed(double()); else typed(float());
+}
+// launches KERNEL<INTERP, OUT_T, flags...> (256 threads) on ctx->stream; the flags are compile-time, so every flag combination is a statement of its own
+#define AUKIT_MIXED_LAUNCH(ctx, KERNEL, interp, dtype, grid, lds, P, ...)                                                                             \
+    mixed_dispatch(interp, dtype, [&](auto ip_, auto t_) {                                                                                            \
+        hipLaunchKernelGGL((KERNEL<decltype(ip_)::value, decltype(t_), __VA_ARGS__>), dim3(grid), dim3(256), lds, (ctx)->stream, P);                  \
+    })
+
+// ---- the DFPWM row pre-pass: streams decoded to flat int8 rows by the chunk engine (dfpwm_par.hip)
+// the streams of one engine call: first byte, fed bytes and row offset of each; slices of `run` bytes advanced by `stride`
+struct DfRowGroup { std::vector<uint64_t> off, fed, row; uint64_t run = 0, stride = 0; };
+// a stream handle's carried decoder state is not a mixed call's: every stream starts from reset.  Off for a scope, whatever way it is left
+struct DfCarriedStateOff {
+    aukit_ctx *ctx;
+    bool was;
+    explicit DfCarriedStateOff(aukit_ctx *c) : ctx(c), was(c->sb_dfpwm_on) { c->sb_dfpwm_on = false; }
+    ~DfCarriedStateOff() { ctx->sb_dfpwm_on = was; }
+};
+// Opens the pre-pass's timed region and runs the engine on group after group: the group's row offsets go to `table` (the groups' tables lie one behind
+// the other), its samples to rows + row offset + lead.  Behind a group the engine took, taken(d_row, streams) may enqueue more; a group it declined
+// (dfpwm_par.hip: nchunk < 2, every stream short) is listed in `declined` — the caller runs its lane-per-stream kernel on those and closes the region
+template <class Taken>
+static inline int mixed_dfpwm_rows(aukit_ctx *ctx, const aukit_batch *in, const std::vector<const DfRowGroup *> &groups, uint64_t lead, signed char *rows, char *table,
+                                   std::vector<size_t> *declined, Taken taken) {
+    int rc;
+    if ((rc = ctx_begin_kernel(ctx))) return rc;
+    const DfCarriedStateOff from_reset(ctx);
+    for (size_t g = 0; g < groups.size(); g++) {
+        const DfRowGroup &G = *groups[g];
+        const size_t m = G.off.size();
+        unsigned long long *d_row = reinterpret_cast<unsigned long long *>(table);
+        table += m * 8;
+        int prc = AUKIT_OK;
+        if ((rc = h2d_table(ctx, d_row, G.row.data(), m * 8))) return rc;
+        if (dfpwm_decode_parallel_feed(ctx, in->data(), G.off, G.fed, G.run, G.stride, 0 /* rows */, 1 /* one "channel": flat */, rows, d_row, nullptr, lead, &prc)) {
+            if (prc) return prc;
+            taken(d_row, (uint32_t)m);
+        } else declined->push_back(g);
+    }
+    return AUKIT_OK;
+}
+
+// ---- the pre-passes' scratch: regions of ctx->tmp_buf, one behind the other, each at a multiple of 256 bytes with `tail` bytes to spare behind it
+// (64 behind rows: the kernels' 16-byte loads rely on them)
+struct Carve {
+    size_t end = 0;
+    size_t take(size_t bytes, size_t tail = 64) {
+        const size_t at = (size_t)round_up(end, 256);
+        end = at + bytes + tail;
+        return at;
+    }
+};
+// Sizes ctx->tmp_buf for scratch that is written, or whose place is settled, before audio_prepare touches `out`.  Where `out` owes a resample whose
+// rows it took out of ctx->tmp_buf, lazy_drop hands that buffer back if it is the larger one: the scratch is asked to be at least as large, so
+// it stays and lazy_drop frees the audio's instead.  (The pointer is read after audio_prepare all the same.)
+static inline int mixed_scratch_ensure(aukit_ctx *ctx, const aukit_audio *out, size_t need) {
+    if (out && out->lazy_rows.p && !out->lazy_indirect) need = std::max(need, out->lazy_rows.cap);
+    return ctx->tmp_buf.ensure(need);
+}
+
+}  // namespace aukit

@@ -141,6 +141,23 @@ struct ChunkPlan {
 int build_chunk_plan(double sample_rate, int interp, ChunkPlan &cp, int sinc_w = 10);
 uint32_t stream_pcm_call(const ChunkPlan &cp, long c, long long nframes, bool is_float, bool mono, Seg *g, int32_t *status);
 
+// what aukit.pcm / aukit.stream.pcm refuse of a descriptor (:1049-1063, :2228-2242): the single-descriptor calls and, per stream, the mixed-library ones
+static inline int check_pcm_desc(const aukit_codec_desc *d) {
+    if (d->bit_depth != 8 && d->bit_depth != 16 && d->bit_depth != 24 && d->bit_depth != 32) return fail(AUKIT_E_ARG, "bad argument #2 (invalid bit depth)");
+    if (d->data_type < 0 || d->data_type > 2) return fail(AUKIT_E_ARG, "bad argument #3 (invalid data type)");
+    if (d->data_type == AUKIT_FLOAT && d->bit_depth != 32) return fail(AUKIT_E_ARG, "bad argument #2 (float audio must have 32-bit depth)");
+    if (d->channels < 1) return fail(AUKIT_E_ARG, "bad argument #4 (number outside of range)");
+    if (d->sample_rate < 1) return fail(AUKIT_E_ARG, "bad argument #5 (number outside of range)");
+    if (d->channels > AUKIT_MAX_PLANAR_CHANNELS) return fail(AUKIT_E_UNSUPPORTED, "at most %d channels are supported", AUKIT_MAX_PLANAR_CHANNELS);
+    return AUKIT_OK;
+}
+
+// the DFPWM decoders the mixed-library calls run as pre-passes
+bool dfpwm_decode_parallel_feed(aukit_ctx *ctx, const unsigned char *src, const std::vector<uint64_t> &h_off, const std::vector<uint64_t> &h_fed, uint64_t run,
+                                uint64_t stride, int mode, int C, signed char *out, const unsigned long long *d_out_off, const unsigned long long *d_out_stride,
+                                uint64_t lead, int *rc, const DfSliceHook *hook = nullptr);  // dfpwm_par.hip
+int dfpwm_decode_list(aukit_ctx *ctx, const unsigned char *src, const unsigned long long *d_list, uint32_t n, signed char *rows);  // codecs.hip
+
 // position of output o (0-based) exactly as the reference computes it on the host
 static inline double host_pos(uint64_t o, double ratio) { return ((double)o) / ratio + 1; }
 

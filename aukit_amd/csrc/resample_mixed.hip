@@ -18,18 +18,17 @@
 //   (2) a lane per output: the position and the index clamps once, then the taps of every channel (consecutive lanes read consecutive LDS doubles);
 //   (3) either every channel goes to its row, or ((0 + ch1) + ch2 ...) / cn goes to row 0 (Audio:mono on the clamped values) — coalesced stores.
 // fp64 in the reference's operation order whatever the storage type; F32 rounds once, at the store.
+//
+// The host half reads as the call's phases: mix_validate (the QOA header read-back inside it), mix_classes, the scratch layout, the int16-row
+// pre-passes (QOA and IMA jobs, and the stereo-IMA flag read-back), the DFPWM row pre-pass, segments and tiles, the launch.  What the call shares
+// with aukit_stream_decode_mixed is in mixed_plan.h.
 #include <algorithm>
-#include <string>
 #include <tuple>
-#include "resample.h"
+#include "mixed_plan.h"
 #include "resample_dev.h"
 
 namespace aukit {
 
-bool dfpwm_decode_parallel_feed(aukit_ctx *ctx, const unsigned char *src, const std::vector<uint64_t> &h_off, const std::vector<uint64_t> &h_fed, uint64_t run,
-                                uint64_t stride, int mode, int C, signed char *out, const unsigned long long *d_out_off, const unsigned long long *d_out_stride,
-                                uint64_t lead, int *rc, const DfSliceHook *hook = nullptr);  // dfpwm_par.hip
-int dfpwm_decode_list(aukit_ctx *ctx, const unsigned char *src, const unsigned long long *d_list, uint32_t n, signed char *rows);  // codecs.hip
 // the pre-passes of the int16-row streams
 struct QoaMixedStream { int channels; double rate; uint64_t L, njobs; bool raised, big; };  // qoa.hip
 int qoa_mixed_count(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<QoaMixedStream> &Q, uint32_t *bad);
@@ -155,16 +154,6 @@ AUKIT_DEV int mixed_stage_i16(const short *row, long long g0, int n_stage, doubl
 #undef AUKIT_MIXED_I16
 
 // ------------------------------------------------------------------ host
-static int check_mixed_pcm(const aukit_codec_desc *d) {  // what check_pcm_desc (api_resample.hip) refuses, with its words
-    if (d->bit_depth != 8 && d->bit_depth != 16 && d->bit_depth != 24 && d->bit_depth != 32) return fail(AUKIT_E_ARG, "bad argument #2 (invalid bit depth)");
-    if (d->data_type < 0 || d->data_type > 2) return fail(AUKIT_E_ARG, "bad argument #3 (invalid data type)");
-    if (d->data_type == AUKIT_FLOAT && d->bit_depth != 32) return fail(AUKIT_E_ARG, "bad argument #2 (float audio must have 32-bit depth)");
-    if (d->channels < 1) return fail(AUKIT_E_ARG, "bad argument #4 (number outside of range)");
-    if (d->sample_rate < 1) return fail(AUKIT_E_ARG, "bad argument #5 (number outside of range)");
-    if (d->channels > AUKIT_MAX_PLANAR_CHANNELS) return fail(AUKIT_E_UNSUPPORTED, "at most %d channels are supported", AUKIT_MAX_PLANAR_CHANNELS);
-    return AUKIT_OK;
-}
-
 static inline uint64_t mixed_count(uint64_t n_in, double ratio) {  // `for i = 1, #data * ratio`  :659-664
     double newlen = (double)n_in * ratio;
     return newlen >= 1 ? (uint64_t)std::floor(newlen) : 0;
@@ -173,11 +162,21 @@ static inline uint64_t mixed_count(uint64_t n_in, double ratio) {  // `for i = 1
 // fed bytes of aukit.dfpwm's slice loop, 6001 bytes advanced by 6000 (:1405-1411): every slice but the last feeds one byte twice
 static inline uint64_t mixed_dfpwm_fed(uint64_t nb) { return nb ? nb + (nb + 5999) / 6000 - 1 : 0; }
 
+// what Audio:resample (audio_from_int_rows, api_resample.hip) refuses of a decoded stream's rate and length, with its words; fills the outputs
+static int check_mixed_rows(double rate, double new_rate, uint64_t frames, uint64_t *n_out) {
+    const double ratio = new_rate / rate;
+    if (!(ratio > 0) || std::isinf(ratio)) return fail(AUKIT_E_ARG, "bad sample rate");
+    *n_out = mixed_count(frames, ratio);
+    if (frames > 0x7FFFFFF0ull || *n_out > 0xFFFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "stream too long");
+    if (*n_out && std::floor(host_pos(*n_out - 1, ratio)) > (double)frames) return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (field '?')");
+    return AUKIT_OK;
+}
+
 // everything the stream's own single-descriptor call would refuse; fills frames / outputs
 static int check_mixed_stream(const aukit_codec_desc *d, uint64_t nb, double new_rate, uint64_t *frames, uint64_t *n_out) {
     int rc;
     if (d->codec == AUKIT_CODEC_PCM) {
-        if ((rc = check_mixed_pcm(d))) return rc;
+        if ((rc = check_pcm_desc(d))) return rc;
     } else if (d->codec == AUKIT_CODEC_DFPWM) {  // what dfpwm_decode_audio (codecs.hip) refuses, with its words
         if (d->channels < 1) return fail(AUKIT_E_ARG, "bad argument #2 (number outside of range)");
         if (d->sample_rate < 1) return fail(AUKIT_E_ARG, "bad argument #3 (number outside of range)");
@@ -198,10 +197,7 @@ static int check_mixed_stream(const aukit_codec_desc *d, uint64_t nb, double new
         }
         *frames = nb / frame_bytes;
     }
-    *n_out = mixed_count(*frames, ratio);
-    if (*frames > 0x7FFFFFF0ull || *n_out > 0xFFFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "stream too long");
-    if (*n_out && std::floor(host_pos(*n_out - 1, ratio)) > (double)*frames) return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (field '?')");
-    return AUKIT_OK;
+    return check_mixed_rows(d->sample_rate, new_rate, *frames, n_out);
 }
 
 // what ima_decode_audio (codecs.hip) refuses of one aukit.wav IMA-ADPCM stream, with its words; fills the samples per channel (:1509-1548)
@@ -224,134 +220,98 @@ static int check_mixed_ima(const aukit_codec_desc *d, uint64_t nb, uint64_t *fra
     return AUKIT_OK;
 }
 
-// what audio_from_int_rows (api_resample.hip) refuses of a decoded stream's rate and length, with its words; fills the outputs
-static int check_mixed_rows(double rate, double new_rate, uint64_t frames, uint64_t *n_out) {
-    const double ratio = new_rate / rate;
-    if (!(ratio > 0) || std::isinf(ratio)) return fail(AUKIT_E_ARG, "bad sample rate");
-    *n_out = mixed_count(frames, ratio);
-    if (frames > 0x7FFFFFF0ull || *n_out > 0xFFFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "stream too long");
-    if (*n_out && std::floor(host_pos(*n_out - 1, ratio)) > (double)frames) return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (field '?')");
-    return AUKIT_OK;
-}
+// ---- phase 1: validation.  What the batch is, per stream, once nothing is left to refuse from descriptors, byte counts and QOA headers
+struct MixStreams {
+    std::vector<int> ch;           // channel count and sample rate of every stream: the descriptor's, or (QOA) the file header's  :1708-1711
+    std::vector<double> rate;
+    std::vector<uint32_t> q_list;  // the QOA streams, in batch order
+    std::vector<QoaMixedStream> Q;
+    std::vector<uint64_t> frames, lens;
+    uint64_t in_bytes = 0, out_elems = 0;  // in_bytes: what the resample launch reads — a DFPWM stream's int8 row, not its source bytes
+    bool has_df = false, has_i16 = false;
+};
 
-template <typename OUT_T, bool DF>
-static int launch_mixed_i16(aukit_ctx *ctx, int interp, const MixParams &P, size_t lds, unsigned grid) {
-    switch (interp) {
-    case AUKIT_INTERP_NONE: hipLaunchKernelGGL((k_resample_mixed_i16<AUKIT_INTERP_NONE, OUT_T, DF>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
-    case AUKIT_INTERP_LINEAR: hipLaunchKernelGGL((k_resample_mixed_i16<AUKIT_INTERP_LINEAR, OUT_T, DF>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
-    default: hipLaunchKernelGGL((k_resample_mixed_i16<AUKIT_INTERP_CUBIC, OUT_T, DF>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
-    }
-    AUKIT_HIP_CHECK(hipGetLastError());
-    return AUKIT_OK;
-}
-
-template <typename OUT_T, bool DF>
-static int launch_mixed(aukit_ctx *ctx, int interp, const MixParams &P, size_t lds, unsigned grid) {
-    switch (interp) {
-    case AUKIT_INTERP_NONE: hipLaunchKernelGGL((k_resample_mixed<AUKIT_INTERP_NONE, OUT_T, DF>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
-    case AUKIT_INTERP_LINEAR: hipLaunchKernelGGL((k_resample_mixed<AUKIT_INTERP_LINEAR, OUT_T, DF>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
-    default: hipLaunchKernelGGL((k_resample_mixed<AUKIT_INTERP_CUBIC, OUT_T, DF>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
-    }
-    AUKIT_HIP_CHECK(hipGetLastError());
-    return AUKIT_OK;
-}
-
-}  // namespace aukit
-
-using namespace aukit;
-
-extern "C" int aukit_decode_resample_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, double new_rate, int interp,
-                                           int mono, int dtype, aukit_audio **out) {
-    if (!ctx || !in || !out || (!descs && n_descs)) return fail(AUKIT_E_ARG, "null argument");
-    if (dtype != AUKIT_F64 && dtype != AUKIT_F32) return fail(AUKIT_E_ARG, "dtype must be AUKIT_F64 or AUKIT_F32");
-    if (interp < 0 || interp > 3) return fail(AUKIT_E_ARG, "bad argument #2 (invalid interpolation type)");
-    if (interp == AUKIT_INTERP_SINC) return fail(AUKIT_E_UNSUPPORTED, "sinc interpolation is not served for per-stream descriptors: resample each class with aukit_decode_resample");
-    if (n_descs != in->n) return fail(AUKIT_E_ARG, "%u descriptors for a batch of %u streams", n_descs, in->n);
+static int mix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, double new_rate, int interp, int mono, int dtype,
+                        aukit_audio **out, MixStreams &S) {
+    int rc;
+    if ((rc = mixed_check_call(ctx, in, out, descs, n_descs, interp, dtype, "bad argument #2 (invalid interpolation type)", "resample each class with aukit_decode_resample")))
+        return rc;
     if (!(new_rate > 0)) return fail(AUKIT_E_ARG, "bad sample rate");
     const uint32_t n = in->n;
-    std::vector<int> ch(n);        // channel count and sample rate of every stream: the descriptor's, or (QOA) the file header's  :1708-1711
-    std::vector<double> rate(n);
-    std::vector<uint32_t> q_list;  // the QOA streams, in batch order
-    bool has_i16 = false;
+    if ((rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV},
+                                 "stream %u: codec %d has its own loader (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, "
+                                 "AUKIT_CODEC_QOA and AUKIT_CODEC_ADPCM_WAV)")))
+        return rc;
+    S.ch.resize(n);
+    S.rate.resize(n);
     for (uint32_t s = 0; s < n; s++) {
         const int codec = descs[s].codec;
-        if (codec != AUKIT_CODEC_PCM && codec != AUKIT_CODEC_G711 && codec != AUKIT_CODEC_DFPWM && codec != AUKIT_CODEC_QOA && codec != AUKIT_CODEC_ADPCM_WAV)
-            return fail(AUKIT_E_UNSUPPORTED,
-                        "stream %u: codec %d has its own loader (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_QOA and "
-                        "AUKIT_CODEC_ADPCM_WAV)", s, codec);
-        ch[s] = descs[s].channels;
-        rate[s] = descs[s].sample_rate;
-        if (codec == AUKIT_CODEC_QOA) q_list.push_back(s);
-        if (codec == AUKIT_CODEC_QOA || codec == AUKIT_CODEC_ADPCM_WAV) has_i16 = true;
+        S.ch[s] = descs[s].channels;
+        S.rate[s] = descs[s].sample_rate;
+        if (codec == AUKIT_CODEC_QOA) S.q_list.push_back(s);
+        if (codec == AUKIT_CODEC_QOA || codec == AUKIT_CODEC_ADPCM_WAV) S.has_i16 = true;
     }
     // QOA: the count pass of the device walk on these streams only, and the header read-back — what a header is refused for comes first, with
     // aukit.qoa's words.  It writes ctx->tmp_buf3 and nothing of `*out`.
-    std::vector<QoaMixedStream> Q;
-    if (!q_list.empty()) {
+    if (!S.q_list.empty()) {
         AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
         uint32_t bad = 0;
-        const int rc = qoa_mixed_count(ctx, in, q_list, Q, &bad);
-        if (rc) {
-            const std::string m = aukit_last_error();
-            return fail(rc, "%s (stream %u)", m.c_str(), q_list[bad]);
-        }
-        for (size_t k = 0; k < q_list.size(); k++) { ch[q_list[k]] = Q[k].channels; rate[q_list[k]] = Q[k].rate; }
+        if ((rc = qoa_mixed_count(ctx, in, S.q_list, S.Q, &bad))) return fail_for_stream(rc, S.q_list[bad]);
+        for (size_t k = 0; k < S.q_list.size(); k++) { S.ch[S.q_list[k]] = S.Q[k].channels; S.rate[S.q_list[k]] = S.Q[k].rate; }
     }
-    if (!mono)
-        for (uint32_t s = 1; s < n; s++)
-            if (ch[s] != ch[0]) return fail(AUKIT_E_ARG, "streams differ in channel count: mix down or split the batch");
-    std::vector<uint64_t> frames(n), lens(n);
-    uint64_t in_bytes = 0, out_elems = 0;  // in_bytes: what the resample launch reads — a DFPWM stream's int8 row, not its source bytes
-    bool has_df = false;
+    if ((rc = mixed_check_channels(n, mono, [&](uint32_t s) { return S.ch[s]; }))) return rc;
+    S.frames.resize(n);
+    S.lens.resize(n);
     for (uint32_t s = 0, qk = 0; s < n; s++) {
         const uint64_t nb = in->off[s + 1] - in->off[s];
         const int codec = descs[s].codec;
-        int rc;
         if (codec == AUKIT_CODEC_QOA) {  // what decode_qoa_audio (qoa.hip) refuses of a walk
-            const QoaMixedStream &q = Q[qk++];
-            frames[s] = q.L;
+            const QoaMixedStream &q = S.Q[qk++];
+            S.frames[s] = q.L;
             if (q.raised) rc = fail(AUKIT_E_LUA, "data string too short");
             else if (q.big)  // (weights could leave 24 bits: the single call decodes such a file on the host)
                 rc = fail(AUKIT_E_UNSUPPORTED, "QOA frame of more than 8192 samples: aukit_decode_resample takes this file");
-            else rc = check_mixed_rows(rate[s], new_rate, frames[s], &lens[s]);
+            else rc = check_mixed_rows(S.rate[s], new_rate, S.frames[s], &S.lens[s]);
         } else if (codec == AUKIT_CODEC_ADPCM_WAV) {
-            if (!(rc = check_mixed_ima(&descs[s], nb, &frames[s]))) rc = check_mixed_rows(rate[s], new_rate, frames[s], &lens[s]);
-        } else rc = check_mixed_stream(&descs[s], nb, new_rate, &frames[s], &lens[s]);
-        if (rc) {  // the stream's own call would fail: its status and words, and which stream it is
-            const std::string m = aukit_last_error();
-            return fail(rc, "%s (stream %u)", m.c_str(), s);
-        }
-        if (codec == AUKIT_CODEC_DFPWM) { has_df = true; in_bytes += mixed_dfpwm_fed(nb) * 8; }
-        else if (codec == AUKIT_CODEC_QOA || codec == AUKIT_CODEC_ADPCM_WAV) in_bytes += frames[s] * (uint64_t)ch[s] * 2;
-        else in_bytes += nb;
-        out_elems += lens[s] * (uint64_t)(mono ? 1 : ch[s]);
+            if (!(rc = check_mixed_ima(&descs[s], nb, &S.frames[s]))) rc = check_mixed_rows(S.rate[s], new_rate, S.frames[s], &S.lens[s]);
+        } else rc = check_mixed_stream(&descs[s], nb, new_rate, &S.frames[s], &S.lens[s]);
+        if (rc) return fail_for_stream(rc, s);
+        if (codec == AUKIT_CODEC_DFPWM) { S.has_df = true; S.in_bytes += mixed_dfpwm_fed(nb) * 8; }
+        else if (codec == AUKIT_CODEC_QOA || codec == AUKIT_CODEC_ADPCM_WAV) S.in_bytes += S.frames[s] * (uint64_t)S.ch[s] * 2;
+        else S.in_bytes += nb;
+        S.out_elems += S.lens[s] * (uint64_t)(mono ? 1 : S.ch[s]);
     }
-    AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
+    return AUKIT_OK;
+}
 
-    // classes: one per distinct descriptor, in order of first appearance
-    int hl = 0, hr = 0;
-    if (interp == AUKIT_INTERP_LINEAR) { hr = 1; }
-    else if (interp == AUKIT_INTERP_CUBIC) { hl = 1; hr = 2; }
-    typedef std::tuple<int, int, int, int, int, int, int, double> ClassKey;
-    std::map<ClassKey, unsigned> index;
+// ---- phase 2: the class table — one class per distinct descriptor, in order of first appearance; the tile height is the class's
+struct MixClasses {
     std::vector<MixClass> classes;
-    std::vector<int> tile_out;          // per class
-    std::vector<uint64_t> class_max;    // per class: the largest output count
-    std::vector<unsigned> cls_of(n);
-    size_t lds = 0;
+    std::vector<int> tile_out;     // per class
+    std::vector<unsigned> cls_of;  // per stream
+    size_t lds = 0;                // the largest class's
+};
+
+static int mix_classes(aukit_ctx *ctx, const aukit_codec_desc *descs, uint32_t n, const MixStreams &S, double new_rate, int interp, MixClasses &T) {
+    int hl, hr;
+    mixed_halos(interp, &hl, &hr);
+    ClassIndex<std::tuple<int, int, int, int, int, int, int, double>> index;
+    std::vector<uint64_t> class_max;  // per class: the largest output count
+    T.cls_of.resize(n);
     for (uint32_t s = 0; s < n; s++) {
         const aukit_codec_desc &d = descs[s];
         const bool pcm = d.codec == AUKIT_CODEC_PCM;
         const int planar = (pcm && d.channels > 1 && !d.interleaved) ? 1 : 0;  // aukit.lua:1156-1169
         const bool g711 = d.codec == AUKIT_CODEC_G711;  // (a DFPWM class is keyed by codec, channels and sample rate)
         const bool i16 = d.codec == AUKIT_CODEC_QOA || d.codec == AUKIT_CODEC_ADPCM_WAV;  // (one kind of class for both: keyed by channels and sample rate)
-        const int kcodec = i16 ? MIX_SRC_I16 : d.codec, kch = ch[s];
-        const ClassKey key(kcodec, pcm ? d.bit_depth : i16 ? 16 : 8, pcm ? d.data_type : 0, pcm ? (d.big_endian ? 1 : 0) : 0, planar, kch, g711 ? (d.ulaw ? 1 : 0) : 0, rate[s]);
-        auto it = index.find(key);
-        if (it == index.end()) {
+        const int kcodec = i16 ? MIX_SRC_I16 : d.codec, kch = S.ch[s];
+        bool fresh;
+        const unsigned c = T.cls_of[s] = index.of({kcodec, pcm ? d.bit_depth : i16 ? 16 : 8, pcm ? d.data_type : 0, pcm ? (d.big_endian ? 1 : 0) : 0, planar, kch,
+                                                   g711 ? (d.ulaw ? 1 : 0) : 0, S.rate[s]}, &fresh);
+        if (fresh) {
             MixClass K;
             memset(&K, 0, sizeof K);
-            K.ratio = new_rate / rate[s];
+            K.ratio = new_rate / S.rate[s];
             K.rcp = 1.0 / K.ratio;
             K.g711_scale = 1.0 / 8192.0;  // m / 0x2000  :1379
             K.codec = kcodec;
@@ -362,187 +322,207 @@ extern "C" int aukit_decode_resample_mixed(aukit_ctx *ctx, const aukit_batch *in
             K.ulaw = d.ulaw ? 1 : 0;
             K.channels = kch;
             K.s16le_mono = (pcm && d.bit_depth == 16 && d.data_type == AUKIT_SIGNED && !d.big_endian && d.channels == 1) ? 1 : 0;
-            // tile height: the staged window (tile_out / ratio + halo) x channels x 8 B within plan_tiles' budget; 64 KiB at the most
-            const int slack = hl + hr + 2 + 32;  // +32: the vector path's alignment head and tail, the kernel's own margin of 16
-            auto cap_for = [&](int to) { return (int)std::ceil((double)to / K.ratio) + slack; };
-            // (the 2 KiB int8 table of a batch with a DFPWM class comes out of the 64 KiB a launch may ask for)
-            const size_t budget = 24 * 1024, hard = 64 * 1024 - (has_df ? 2048 : 0);
-            int to = 2048;
-            while (to > 256 && (size_t)cap_for(to) * 8 * kch > budget) to -= 256;
-            while (to > 64 && (size_t)cap_for(to) * 8 * kch > hard) to -= 64;
-            if ((size_t)cap_for(to) * 8 * kch > hard)
-                return fail(AUKIT_E_UNSUPPORTED, "resampling ratio %g with %d channels needs more than 64 KiB of LDS per tile (stream %u)", K.ratio, kch, s);
-            K.cap = (cap_for(to) + 1) & ~1;
-            lds = std::max(lds, (size_t)K.cap * 8 * kch);
-            it = index.emplace(key, (unsigned)classes.size()).first;
-            classes.push_back(K);
-            tile_out.push_back(to);
+            // slack + 32: the vector path's alignment head and tail, the kernel's own margin of 16.  The 2 KiB int8 table of a batch with a DFPWM class
+            // comes out of the 64 KiB a launch may ask for
+            int to, rc;
+            if ((rc = mixed_tile_height(K.ratio, K.ratio, kch, hl + hr + 2 + 32, 64 * 1024 - (S.has_df ? 2048 : 0), s, &to, &K.cap))) return rc;
+            T.lds = std::max(T.lds, (size_t)K.cap * 8 * kch);
+            T.classes.push_back(K);
+            T.tile_out.push_back(to);
             class_max.push_back(0);
         }
-        cls_of[s] = it->second;
-        class_max[it->second] = std::max(class_max[it->second], lens[s]);
+        class_max[c] = std::max(class_max[c], S.lens[s]);
     }
-    for (size_t c = 0; c < classes.size(); c++) classes[c].exact_rcp = exact_div_verified(ctx, classes[c].ratio, class_max[c] + 1) ? 1 : 0;
+    for (size_t c = 0; c < T.classes.size(); c++) T.classes[c].exact_rcp = exact_div_verified(ctx, T.classes[c].ratio, class_max[c] + 1) ? 1 : 0;
+    return AUKIT_OK;
+}
 
-    const int C_out = mono ? 1 : (n ? ch[0] : 1);
-    // pre-pass: the DFPWM streams that have outputs, as flat int8 rows in ctx->tmp_buf — fed x 8 samples each in decode order (the interleaved order),
-    // every row at a multiple of 16 bytes, 64 bytes to spare behind the last (mixed_stage_i8's 16-byte loads).  The decoders' tables live behind the
-    // rows in the same buffer: ctx->misc_buf, where the class table goes below, and ctx->tmp_buf2, which the chunk engine carves, stay free of them.
-    // Planned, and the scratch sized, before `*out` is touched: a failure to allocate leaves it as it was.  (audio_prepare may hand a larger buffer back
-    // to ctx->tmp_buf, lazy_drop, never a smaller one: the pointer is read after it.)
-    std::vector<uint64_t> df_row(n, 0), h_off, h_fed, h_row, h_list;
-    uint64_t tot = 0, df_src = 0;
-    size_t tab_at = 0;
-    uint32_t nd = 0;
+// ---- phase 3: what the pre-passes decode, and where in ctx->tmp_buf.  Planned, and the scratch sized, before `*out` is touched: a failure to
+// allocate leaves it as it was.
+// The DFPWM streams that have outputs, as flat int8 rows — fed x 8 samples each in decode order (the interleaved order), every row at a multiple of
+// 16 bytes (mixed_stage_i8's 16-byte loads)
+struct MixDfRows {
+    DfRowGroup group;            // one engine call: aukit.dfpwm's 6001 / 6000
+    std::vector<uint64_t> list;  // the same streams for the lane-per-stream kernel: (first byte, bytes, row offset) each
+    std::vector<uint64_t> row;   // per stream of the batch: its row's offset
+    uint64_t tot = 0, src = 0;   // bytes of all rows; source bytes
+    uint32_t n = 0;
+};
+static MixDfRows mix_dfpwm_plan(const aukit_batch *in, const aukit_codec_desc *descs, const MixStreams &S) {
+    MixDfRows D;
+    D.group.run = 6001; D.group.stride = 6000;
+    D.row.assign(in->n, 0);
+    for (uint32_t s = 0; s < in->n; s++) {
+        if (descs[s].codec != AUKIT_CODEC_DFPWM || !S.lens[s]) continue;
+        const uint64_t nb = in->off[s + 1] - in->off[s], fed = mixed_dfpwm_fed(nb);
+        D.row[s] = D.tot;
+        D.group.off.push_back(in->off[s]); D.group.fed.push_back(fed); D.group.row.push_back(D.tot);
+        D.list.push_back(in->off[s]); D.list.push_back(nb); D.list.push_back(D.tot);
+        D.tot += round_up(fed * 8, 16);
+        D.src += nb;
+    }
+    D.n = (uint32_t)D.group.off.size();
+    return D;
+}
+
+// The QOA and IMA-ADPCM streams' samples as int16 rows: every row at a multiple of 16 bytes, channel c of a stream c * round_up(max(frames, 1), 8)
+// elements behind channel 0 (the single-descriptor loaders' layout; mixed_stage_i16's 16-byte loads)
+struct MixI16Rows {
+    std::vector<uint64_t> row;      // per stream of the batch: first element of its channel 0's row
+    std::vector<uint64_t> q_rows;   // the same, per QOA stream
+    std::vector<ImaMixJob> ijobs;   // one job per (IMA block, channel): where the block is, how long, where its samples go
+    uint64_t el = 0, q_jobs = 0, q_src = 0, i_src = 0;  // elements of all rows; QOA jobs; source bytes of the QOA / the IMA streams
+    bool stereo_ima = false;
+};
+static MixI16Rows mix_i16_plan(const aukit_batch *in, const aukit_codec_desc *descs, const MixStreams &S) {
+    MixI16Rows R;
+    R.row.assign(in->n, 0);
+    for (uint32_t s = 0, qk = 0; s < in->n; s++) {
+        const int codec = descs[s].codec;
+        if (codec != AUKIT_CODEC_QOA && codec != AUKIT_CODEC_ADPCM_WAV) continue;
+        const uint64_t stride = round_up(std::max<uint64_t>(S.frames[s], 1), 8), nb = in->off[s + 1] - in->off[s];
+        R.row[s] = R.el;
+        if (codec == AUKIT_CODEC_QOA) { R.q_rows.push_back(R.el); R.q_jobs += S.Q[qk++].njobs; R.q_src += nb; }
+        else {
+            const uint64_t ba = (uint64_t)descs[s].block_align, C = (uint64_t)S.ch[s], spb = (ba - 4 * C) * 2 / C;
+            if (C == 2) R.stereo_ima = true;
+            R.i_src += nb;
+            for (uint64_t b = 0; b * ba < nb; b++)
+                for (uint64_t c = 0; c < C; c++)
+                    R.ijobs.push_back(ImaMixJob{in->off[s] + b * ba, R.el + c * stride + b * spb, (unsigned)std::min<uint64_t>(ba, nb - b * ba), s, (int)c, (int)C});
+        }
+        R.el += stride * (uint64_t)S.ch[s];
+    }
+    return R;
+}
+
+// The int8 rows first; the DFPWM decoders' tables behind them in the same buffer (ctx->misc_buf, where the class table goes, and ctx->tmp_buf2,
+// which the chunk engine carves, stay free of them); then the int16 rows, the QOA and the IMA job tables and the IMA flag
+struct MixScratch { size_t df_tab_at = 0, i16_at = 0, qj_at = 0, ij_at = 0, flag_at = 0, size = 0; };
+static MixScratch mix_scratch(const MixStreams &S, const MixDfRows &D, const MixI16Rows &R) {
+    Carve carve;
+    MixScratch L;
+    if (S.has_df) { carve.take((size_t)D.tot); L.df_tab_at = carve.take((size_t)D.n * 32); }  // (the rows are at 0)
+    if (S.has_i16) {
+        L.i16_at = carve.take((size_t)R.el * 2);
+        L.qj_at = carve.take(S.q_list.empty() ? 0 : qoa_mixed_job_bytes(R.q_jobs), 0);
+        L.ij_at = carve.take(R.ijobs.size() * sizeof(ImaMixJob), 0);
+        L.flag_at = carve.take(4, 60);
+    }
+    L.size = carve.end;
+    return L;
+}
+
+// ---- phase 4: the int16-row pre-passes.  They can still refuse (a stereo IMA block's step index), and they write nothing but the scratch: so they
+// run, and their flag is read back, BEFORE `*out` is touched
+static int mix_i16_prepass(aukit_ctx *ctx, const aukit_batch *in, const MixStreams &S, const MixI16Rows &R, const MixScratch &L) {
     int rc;
-    if (has_df) {
-        for (uint32_t s = 0; s < n; s++) {
-            if (descs[s].codec != AUKIT_CODEC_DFPWM || !lens[s]) continue;
-            const uint64_t nb = in->off[s + 1] - in->off[s], fed = mixed_dfpwm_fed(nb);
-            df_row[s] = tot;
-            h_off.push_back(in->off[s]); h_fed.push_back(fed); h_row.push_back(tot);
-            h_list.push_back(in->off[s]); h_list.push_back(nb); h_list.push_back(tot);
-            tot += round_up(fed * 8, 16);
-            df_src += nb;
-        }
-        nd = (uint32_t)h_off.size();
-        tab_at = (size_t)round_up(tot + 64, 256);
-        if (!has_i16 && (rc = ctx->tmp_buf.ensure(tab_at + (size_t)nd * 32 + 64))) return rc;
+    char *const T = reinterpret_cast<char *>(ctx->tmp_buf.p);
+    short *const rows16 = reinterpret_cast<short *>(T + L.i16_at);
+    if (!S.q_list.empty() && (rc = qoa_mixed_decode(ctx, in, S.Q, R.q_rows.data(), rows16, T + L.qj_at, R.q_src))) return rc;
+    if (R.ijobs.empty()) return AUKIT_OK;
+    unsigned *flag = reinterpret_cast<unsigned *>(T + L.flag_at);
+    if ((rc = h2d_table(ctx, T + L.ij_at, R.ijobs.data(), R.ijobs.size() * sizeof(ImaMixJob)))) return rc;
+    AUKIT_HIP_CHECK(hipMemsetAsync(flag, 0xFF, 4, ctx->stream));
+    if ((rc = ima_mixed_decode(ctx, in->data(), T + L.ij_at, R.ijobs.size(), rows16, flag, R.i_src + R.el * 2))) return rc;
+    if (R.stereo_ima) {  // (a one-channel block's masked index cannot leave 0 .. 88: no flag to wait for)
+        unsigned hflag = 0xFFFFFFFFu;
+        AUKIT_HIP_CHECK(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+        AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (hflag != 0xFFFFFFFFu) return fail(AUKIT_E_ARG, "bad argument #7 (number outside of range) (stream %u)", hflag);
     }
-    // pre-passes of the int16-row streams: QOA and IMA-ADPCM samples as int16 rows behind the int8 rows and the DFPWM tables, in the same buffer — every
-    // row at a multiple of 16 bytes, channel c of a stream c * round_up(max(frames, 1), 8) elements behind channel 0 (the single-descriptor loaders'
-    // layout), 64 bytes to spare behind the last (mixed_stage_i16's 16-byte loads) — and behind them the decoders' job tables and the IMA flag.  The
-    // buffer is sized ONCE for all of it.  These passes can still refuse (a stereo IMA block's step index), and they write nothing but this scratch: so
-    // they run, and their flag is read back, BEFORE `*out` is touched.  audio_prepare must then leave the buffer alone: where `*out` owes a resample
-    // whose rows it took out of ctx->tmp_buf, lazy_drop hands that buffer back if it is the larger one — so the scratch is asked to be at least as
-    // large, and lazy_drop frees the audio's instead.
-    std::vector<uint64_t> row16(n, 0);
-    size_t i16_at = 0;
-    if (has_i16) {
-        i16_at = has_df ? (size_t)round_up(tab_at + (size_t)nd * 32 + 64, 256) : 0;
-        uint64_t el = 0, q_jobs = 0, q_src = 0, i_src = 0;
-        std::vector<uint64_t> q_rows;
-        std::vector<ImaMixJob> ijobs;
-        bool stereo_ima = false;
-        for (uint32_t s = 0, qk = 0; s < n; s++) {
-            const int codec = descs[s].codec;
-            if (codec != AUKIT_CODEC_QOA && codec != AUKIT_CODEC_ADPCM_WAV) continue;
-            const uint64_t stride = round_up(std::max<uint64_t>(frames[s], 1), 8), nb = in->off[s + 1] - in->off[s];
-            row16[s] = el;
-            if (codec == AUKIT_CODEC_QOA) { q_rows.push_back(el); q_jobs += Q[qk++].njobs; q_src += nb; }
-            else {  // one job per (block, channel): where the block is, how long, where its samples go
-                const uint64_t ba = (uint64_t)descs[s].block_align, C = (uint64_t)ch[s], spb = (ba - 4 * C) * 2 / C;
-                if (C == 2) stereo_ima = true;
-                i_src += nb;
-                for (uint64_t b = 0; b * ba < nb; b++)
-                    for (uint64_t c = 0; c < C; c++)
-                        ijobs.push_back(ImaMixJob{in->off[s] + b * ba, el + c * stride + b * spb, (unsigned)std::min<uint64_t>(ba, nb - b * ba), s, (int)c, (int)C});
-            }
-            el += stride * (uint64_t)ch[s];
-        }
-        const size_t qj_at = (size_t)round_up(i16_at + el * 2 + 64, 256);
-        const size_t ij_at = (size_t)round_up(qj_at + (q_list.empty() ? 0 : qoa_mixed_job_bytes(q_jobs)), 256);
-        const size_t flag_at = (size_t)round_up(ij_at + ijobs.size() * sizeof(ImaMixJob), 256);
-        size_t need = flag_at + 64;
-        if (*out && (*out)->lazy_rows.p && !(*out)->lazy_indirect) need = std::max(need, (*out)->lazy_rows.cap);
-        if ((rc = ctx->tmp_buf.ensure(need))) return rc;
-        char *const T = reinterpret_cast<char *>(ctx->tmp_buf.p);
-        short *const rows16 = reinterpret_cast<short *>(T + i16_at);
-        if (!q_list.empty() && (rc = qoa_mixed_decode(ctx, in, Q, q_rows.data(), rows16, T + qj_at, q_src))) return rc;
-        if (!ijobs.empty()) {
-            unsigned *flag = reinterpret_cast<unsigned *>(T + flag_at);
-            if ((rc = h2d_table(ctx, T + ij_at, ijobs.data(), ijobs.size() * sizeof(ImaMixJob)))) return rc;
-            AUKIT_HIP_CHECK(hipMemsetAsync(flag, 0xFF, 4, ctx->stream));
-            if ((rc = ima_mixed_decode(ctx, in->data(), T + ij_at, ijobs.size(), rows16, flag, i_src + el * 2))) return rc;
-            if (stereo_ima) {  // (a one-channel block's masked index cannot leave 0 .. 88: no flag to wait for)
-                unsigned hflag = 0xFFFFFFFFu;
-                AUKIT_HIP_CHECK(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-                AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                if (hflag != 0xFFFFFFFFu) return fail(AUKIT_E_ARG, "bad argument #7 (number outside of range) (stream %u)", hflag);
-            }
-        }
-    }
+    return AUKIT_OK;
+}
 
-    aukit_audio *a = *out;
-    if ((rc = audio_prepare(ctx, &a, n, C_out, new_rate, dtype, lens.data()))) return rc;
-    *out = a;
+// ---- phase 5: the DFPWM row pre-pass, timed under its own name: the chunk engine or, where every stream is shorter than two of its chunks, a lane
+// per stream
+static int mix_dfpwm_prepass(aukit_ctx *ctx, const aukit_batch *in, const MixDfRows &D, const MixScratch &L) {
+    char *const T = reinterpret_cast<char *>(ctx->tmp_buf.p) + L.df_tab_at;
+    signed char *const rows = reinterpret_cast<signed char *>(ctx->tmp_buf.p);
+    std::vector<size_t> declined;
+    int rc = mixed_dfpwm_rows(ctx, in, {&D.group}, 0, rows, T, &declined, [](const unsigned long long *, uint32_t) {});
+    if (rc) return rc;
+    if (declined.empty()) return ctx_end_kernel(ctx, "k_df_chunks(parallel dfpwm decode)", D.src + D.tot);
+    unsigned long long *list = reinterpret_cast<unsigned long long *>(T + (size_t)D.n * 8);
+    if ((rc = h2d_table(ctx, list, D.list.data(), (size_t)D.n * 24))) return rc;
+    if ((rc = dfpwm_decode_list(ctx, in->data(), list, D.n, rows))) return rc;
+    return ctx_end_kernel(ctx, "k_dfpwm_decode_list", D.src + D.tot);
+}
 
-    std::vector<MixSeg> segs(n);
+// ---- phase 6: segments (one per stream) and tiles
+static uint64_t mix_count_tiles(const MixStreams &S, const MixClasses &T) {
     uint64_t nt = 0;
-    for (uint32_t s = 0; s < n; s++) nt += (lens[s] + tile_out[cls_of[s]] - 1) / tile_out[cls_of[s]];
+    for (size_t s = 0; s < S.lens.size(); s++) nt += (S.lens[s] + T.tile_out[T.cls_of[s]] - 1) / T.tile_out[T.cls_of[s]];
+    return nt;
+}
+static void mix_tiles(const aukit_batch *in, const aukit_codec_desc *descs, const MixStreams &S, const MixClasses &T, const MixDfRows &D, const MixI16Rows &R,
+                      const MixScratch &L, const aukit_audio *a, std::vector<MixSeg> &segs, std::vector<MixTile> &tiles) {
+    for (uint32_t s = 0; s < in->n; s++) {
+        MixSeg &g = segs[s];
+        const bool i16 = descs[s].codec == AUKIT_CODEC_QOA || descs[s].codec == AUKIT_CODEC_ADPCM_WAV;
+        g.src_off = descs[s].codec == AUKIT_CODEC_DFPWM ? D.row[s] : i16 ? L.i16_at + 2 * R.row[s] : in->off[s];
+        g.out_off = a->row_off[s];
+        g.frames = (unsigned)S.frames[s];
+        g.n_out = (unsigned)S.lens[s];
+        g.out_stride = (unsigned)a->row_stride[s];
+        g.cls = T.cls_of[s];
+        const unsigned to = (unsigned)T.tile_out[g.cls];
+        for (uint64_t o0 = 0; o0 < g.n_out; o0 += to) tiles.push_back(MixTile{s, (unsigned)o0, (unsigned)std::min<uint64_t>(to, g.n_out - o0)});
+    }
+}
+
+// ---- phase 7: the launch.  The DFPWM and the int16-row staging live in instantiations of their own: every other batch launches the kernels it
+// always did
+static int mix_launch(aukit_ctx *ctx, const aukit_batch *in, const MixStreams &S, const MixClasses &T, const std::vector<MixSeg> &segs, const std::vector<MixTile> &tiles,
+                      const aukit_audio *a, int interp, int mono, int dtype) {
+    MixParams P;
+    memset(&P, 0, sizeof P);
+    P.mono = mono ? 1 : 0;
+    const size_t lds = T.lds + (S.has_df ? 2048 : 0);  // counted only then: a PCM / G.711 batch keeps its LDS size, its residency and its grid
+    static const char *names[] = {"k_resample_mixed<none>", "k_resample_mixed<linear>", "k_resample_mixed<cubic>"};
+    return mixed_launch(ctx, in, a, T.classes, segs, tiles, P, lds, names[interp], S.in_bytes + S.out_elems * dtype_size(dtype), [&](unsigned grid) {
+        if (S.has_i16 && S.has_df) AUKIT_MIXED_LAUNCH(ctx, k_resample_mixed_i16, interp, dtype, grid, lds, P, true);
+        else if (S.has_i16) AUKIT_MIXED_LAUNCH(ctx, k_resample_mixed_i16, interp, dtype, grid, lds, P, false);
+        else if (S.has_df) AUKIT_MIXED_LAUNCH(ctx, k_resample_mixed, interp, dtype, grid, lds, P, true);
+        else AUKIT_MIXED_LAUNCH(ctx, k_resample_mixed, interp, dtype, grid, lds, P, false);
+    });
+}
+
+}  // namespace aukit
+
+using namespace aukit;
+
+extern "C" int aukit_decode_resample_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, double new_rate, int interp,
+                                           int mono, int dtype, aukit_audio **out) {
+    int rc;
+    MixStreams S;
+    if ((rc = mix_validate(ctx, in, descs, n_descs, new_rate, interp, mono, dtype, out, S))) return rc;
+    const uint32_t n = in->n;
+    AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
+    MixClasses T;
+    if ((rc = mix_classes(ctx, descs, n, S, new_rate, interp, T))) return rc;
+
+    // the pre-passes' rows and the scratch that holds them: sized ONCE for all of it, before `*out` is touched.  The int16-row passes run before it
+    // too, so audio_prepare must then leave the buffer alone (mixed_scratch_ensure); the DFPWM pass runs behind it and reads the pointer there
+    const MixDfRows D = S.has_df ? mix_dfpwm_plan(in, descs, S) : MixDfRows();
+    const MixI16Rows R = S.has_i16 ? mix_i16_plan(in, descs, S) : MixI16Rows();
+    const MixScratch L = mix_scratch(S, D, R);
+    if (S.has_i16) {
+        if ((rc = mixed_scratch_ensure(ctx, *out, L.size)) || (rc = mix_i16_prepass(ctx, in, S, R, L))) return rc;
+    } else if (S.has_df && (rc = ctx->tmp_buf.ensure(L.size))) return rc;
+
+    const int C_out = mono ? 1 : (n ? S.ch[0] : 1);
+    aukit_audio *a = *out;
+    if ((rc = audio_prepare(ctx, &a, n, C_out, new_rate, dtype, S.lens.data()))) return rc;
+    *out = a;
+    const uint64_t nt = mix_count_tiles(S, T);
     if (nt > 0xFFFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
     if (nt == 0) return AUKIT_OK;
 
-    if (has_df) {
-        if (nd) {
-            char *T = reinterpret_cast<char *>(ctx->tmp_buf.p) + tab_at;
-            signed char *rows = reinterpret_cast<signed char *>(ctx->tmp_buf.p);
-            if ((rc = ctx_begin_kernel(ctx))) return rc;
-            const bool sb_on = ctx->sb_dfpwm_on;  // a stream handle's carried decoder state is not this call's: every stream starts from reset, as aukit.dfpwm's
-            ctx->sb_dfpwm_on = false;
-            int prc = AUKIT_OK;
-            bool taken = false;
-            if (!(rc = h2d_table(ctx, T, h_row.data(), (size_t)nd * 8)))
-                taken = dfpwm_decode_parallel_feed(ctx, in->data(), h_off, h_fed, 6001, 6000, 0 /* rows */, 1 /* one "channel": flat */, rows,
-                                                   reinterpret_cast<const unsigned long long *>(T), nullptr, 0, &prc);
-            ctx->sb_dfpwm_on = sb_on;
-            if (rc) return rc;
-            if (taken) {
-                if (prc) return prc;
-                if ((rc = ctx_end_kernel(ctx, "k_df_chunks(parallel dfpwm decode)", df_src + tot))) return rc;
-            } else {  // every stream shorter than two chunks of the engine (dfpwm_par.hip: nchunk < 2): a lane per stream
-                unsigned long long *L = reinterpret_cast<unsigned long long *>(T + (size_t)nd * 8);
-                if ((rc = h2d_table(ctx, L, h_list.data(), (size_t)nd * 24))) return rc;
-                if ((rc = dfpwm_decode_list(ctx, in->data(), L, nd, rows))) return rc;
-                if ((rc = ctx_end_kernel(ctx, "k_dfpwm_decode_list", df_src + tot))) return rc;
-            }
-        }
-    }
-
+    if (D.n && (rc = mix_dfpwm_prepass(ctx, in, D, L))) return rc;
+    std::vector<MixSeg> segs(n);
     std::vector<MixTile> tiles;
     tiles.reserve((size_t)nt);
-    for (uint32_t s = 0; s < n; s++) {
-        MixSeg &g = segs[s];
-        const bool i16 = descs[s].codec == AUKIT_CODEC_QOA || descs[s].codec == AUKIT_CODEC_ADPCM_WAV;
-        g.src_off = descs[s].codec == AUKIT_CODEC_DFPWM ? df_row[s] : i16 ? i16_at + 2 * row16[s] : in->off[s];
-        g.out_off = a->row_off[s];
-        g.frames = (unsigned)frames[s];
-        g.n_out = (unsigned)lens[s];
-        g.out_stride = (unsigned)a->row_stride[s];
-        g.cls = cls_of[s];
-        const unsigned to = (unsigned)tile_out[g.cls];
-        for (uint64_t o0 = 0; o0 < g.n_out; o0 += to) tiles.push_back(MixTile{s, (unsigned)o0, (unsigned)std::min<uint64_t>(to, g.n_out - o0)});
-    }
-    if ((rc = upload_table(ctx, ctx->misc_buf, classes.data(), classes.size() * sizeof(MixClass)))) return rc;
-    if ((rc = upload_table(ctx, ctx->seg_buf, segs.data(), segs.size() * sizeof(MixSeg)))) return rc;
-    if ((rc = upload_table(ctx, ctx->tile_buf, tiles.data(), tiles.size() * sizeof(MixTile)))) return rc;
-
-    MixParams P;
-    memset(&P, 0, sizeof P);
-    P.tiles = reinterpret_cast<const MixTile *>(ctx->tile_buf.p);
-    P.segs = reinterpret_cast<const MixSeg *>(ctx->seg_buf.p);
-    P.classes = reinterpret_cast<const MixClass *>(ctx->misc_buf.p);
-    P.n_tiles = (unsigned)tiles.size();
-    P.mono = mono ? 1 : 0;
-    P.src = in->data();
-    P.safe_lo = in->base;
-    P.safe_hi = in->base + in->cap;
-    P.out = a->dev;
-    P.rows = reinterpret_cast<const signed char *>(ctx->tmp_buf.p);
-    if (has_df) lds += 2048;  // counted only then: a PCM / G.711 batch keeps its LDS size, its residency and its grid
-    unsigned per_cu = (unsigned)std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1));
-    if (per_cu < 1) per_cu = 1;
-    per_cu *= 16;  // a finer hand-out than the resident count, as launch_resample: the tiles of a mixed batch differ in cost
-    const unsigned grid = std::min<unsigned>(P.n_tiles, (unsigned)ctx->num_cus * per_cu);
-    if ((rc = ctx_begin_kernel(ctx))) return rc;
-    if (has_i16) {  // (the int16-row staging lives in instantiations of its own: every other batch launches the kernels it always did)
-        if (has_df) rc = dtype == AUKIT_F64 ? launch_mixed_i16<double, true>(ctx, interp, P, lds, grid) : launch_mixed_i16<float, true>(ctx, interp, P, lds, grid);
-        else rc = dtype == AUKIT_F64 ? launch_mixed_i16<double, false>(ctx, interp, P, lds, grid) : launch_mixed_i16<float, false>(ctx, interp, P, lds, grid);
-    } else
-    if (has_df) rc = dtype == AUKIT_F64 ? launch_mixed<double, true>(ctx, interp, P, lds, grid) : launch_mixed<float, true>(ctx, interp, P, lds, grid);
-    else if (dtype == AUKIT_F64) rc = launch_mixed<double, false>(ctx, interp, P, lds, grid);
-    else rc = launch_mixed<float, false>(ctx, interp, P, lds, grid);
-    if (rc) return rc;
-    static const char *names[] = {"k_resample_mixed<none>", "k_resample_mixed<linear>", "k_resample_mixed<cubic>"};
-    return ctx_end_kernel(ctx, names[interp], in_bytes + out_elems * dtype_size(dtype));
+    mix_tiles(in, descs, S, T, D, R, L, a, segs, tiles);
+    return mix_launch(ctx, in, S, T, segs, tiles, a, interp, mono, dtype);
 }

@@ -36,18 +36,19 @@
 // table is indices 1 .. 8 * words with the nil fall-backs at both ends, as a G.711 call's.  The tile stages its window of every channel as
 // p / (p < 0 and 128 or 127) (:2812; 16-byte loads), runs the position, fall-back and interpolation code of the other kinds and ends in the G.711
 // epilogue: clamp(floor(c_j)) per channel or clamp(floor(((0 + c_1) + c_2 ...) / channels)) (:2818-2828).
+//
+// The host half reads as the call's phases: smix_validate, smix_classes, the IMA header scan, one planner per codec (plan_pcm, plan_g711, plan_dfpwm,
+// plan_ima: they fill an SMixPlan and touch neither the context nor HIP), the scratch layout, the two pre-passes, smix_tiles, the launch.  What the
+// call shares with aukit_decode_resample_mixed is in mixed_plan.h, stream.adpcm's arithmetic in ima_geom.h.
 #include <algorithm>
-#include <string>
+#include <memory>
 #include <tuple>
-#include "resample.h"
+#include "mixed_plan.h"
+#include "ima_geom.h"
 #include "resample_dev.h"
 #include "dfpwm_dev.h"
 
 namespace aukit {
-
-bool dfpwm_decode_parallel_feed(aukit_ctx *ctx, const unsigned char *src, const std::vector<uint64_t> &h_off, const std::vector<uint64_t> &h_fed, uint64_t run,
-                                uint64_t stride, int mode, int C, signed char *out, const unsigned long long *d_out_off, const unsigned long long *d_out_stride,
-                                uint64_t lead, int *rc, const DfSliceHook *hook = nullptr);  // dfpwm_par.hip
 
 enum { SMIX_EPI_PCM = 0, SMIX_EPI_FLOOR = 1, SMIX_EPI_DFPWM = 2 };
 
@@ -368,12 +369,7 @@ __global__ __launch_bounds__(256) void k_smix_row_heads(signed char *rows, const
 }
 
 // ---- aukit.stream.adpcm's pre-pass: codecs.hip's k_ima_scan_headers and k_ima_mixed with the channel count and blockAlign taken per stream
-__constant__ int c_smix_ima_step[89] = {
-    7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 19, 21, 23, 25, 28, 31, 34, 37, 41, 45,
-    50, 55, 60, 66, 73, 80, 88, 97, 107, 118, 130, 143, 157, 173, 190, 209, 230, 253, 279, 307,
-    337, 371, 408, 449, 494, 544, 598, 658, 724, 796, 876, 963, 1060, 1166, 1282, 1411, 1552, 1707, 1878, 2066,
-    2272, 2499, 2749, 3024, 3327, 3660, 4026, 4428, 4871, 5358, 5894, 6484, 7132, 7845, 8630, 9493, 10442, 11487, 12635, 13899,
-    15289, 16818, 18500, 20350, 22385, 24623, 27086, 29794, 32767};  // aukit.lua:161-171
+// (the step table, c_ima_step, and the word groups of a block, ima_word_groups: ima_geom.h)
 struct SMixImaStream {
     unsigned long long src_off;  // the stream's first byte, relative to the batch's data
     unsigned long long nbytes;
@@ -382,16 +378,6 @@ struct SMixImaStream {
     int channels, block_align;
 };
 static_assert(sizeof(SMixImaStream) == 40, "SMixImaStream layout");
-
-// word groups block `bi` decodes per channel: i = 4C .. blockAlign inclusive — the junk word (Q6) — while #data >= n + i + 4C  :2800-2802.
-// The caller names a processed block: nbytes - bi * ba >= 4C + 1  :2794
-AUKIT_DEV long long smix_ima_groups(unsigned long long nbytes, unsigned long long bi, unsigned long long ba, unsigned long long hdr) {
-    const unsigned long long rem = nbytes - bi * ba;
-    const long long nwr = (long long)((ba - hdr) / hdr);
-    long long ng = (long long)((rem - 1) / hdr) - 1;
-    ng = ng > nwr + 1 ? nwr + 1 : ng;
-    return ng < 0 ? 0 : ng;
-}
 
 // first block of every stream whose header carries a step index above 88 and that decodes at least one word (0xFFFFFFFF: none): the reference
 // indexes ima_step_table with it unmasked (:2799, :2807).  One wave per stream; writes first_bad only
@@ -403,7 +389,7 @@ __global__ __launch_bounds__(64) void k_smix_ima_scan(const unsigned char *src, 
     const unsigned long long nblk = S.nbytes >= hdr + 1 ? (S.nbytes - hdr - 1) / ba + 1 : 0;
     unsigned best = 0xFFFFFFFFu;
     for (unsigned long long bi = threadIdx.x; bi < nblk && bi < 0xFFFFFFFFull; bi += 64) {
-        if (smix_ima_groups(S.nbytes, bi, ba, hdr) <= 0) continue;
+        if (ima_word_groups(S.nbytes, bi, ba, hdr) <= 0) continue;
         const unsigned char *blk = src + S.src_off + bi * ba;  // (the block has at least 4C + 1 bytes: every header byte read is the stream's)
         bool bad = false;
         for (int c = 0; c < S.channels; c++) bad = bad || blk[4 * c + 2] > 88;
@@ -418,7 +404,7 @@ __global__ __launch_bounds__(64) void k_smix_ima_scan(const unsigned char *src, 
 __global__ __launch_bounds__(64) void k_smix_ima_rows(const unsigned char *src, const SMixImaStream *st, unsigned n, unsigned long long njobs, short *rows) {
     __shared__ int lut[89 * 8];
     const int lane = threadIdx.x;
-    for (int i = lane; i < 89 * 8; i += 64) { const int sp = c_smix_ima_step[i >> 3]; lut[i] = (int)(((unsigned)(i & 7) * (unsigned)sp) >> 2) + (sp >> 3); }  // :2809 (Q5)
+    for (int i = lane; i < 89 * 8; i += 64) { const int sp = c_ima_step[i >> 3]; lut[i] = (int)(((unsigned)(i & 7) * (unsigned)sp) >> 2) + (sp >> 3); }  // :2809 (Q5)
     __syncthreads();
     const unsigned long long g = (unsigned long long)blockIdx.x * 64 + (unsigned)lane;
     if (g >= njobs) return;
@@ -428,7 +414,7 @@ __global__ __launch_bounds__(64) void k_smix_ima_rows(const unsigned char *src, 
     const unsigned C = (unsigned)S.channels;
     const unsigned long long hdr = 4ull * C, ba = (unsigned long long)S.block_align, j = g - S.job0, bi = j / C;
     const unsigned c = (unsigned)(j - bi * C);
-    const long long ng = smix_ima_groups(S.nbytes, bi, ba, hdr);
+    const long long ng = ima_word_groups(S.nbytes, bi, ba, hdr);
     const unsigned char *blk = src + S.src_off + bi * ba;
     int pred = (short)((unsigned)blk[4 * c] | (unsigned)blk[4 * c + 1] << 8);
     int idx = blk[4 * c + 2];
@@ -453,40 +439,6 @@ __global__ __launch_bounds__(64) void k_smix_ima_rows(const unsigned char *src, 
 }
 
 // ------------------------------------------------------------------ host
-static int check_smix_pcm(const aukit_codec_desc *d) {  // what check_pcm_desc (api_resample.hip) refuses, with its words
-    if (d->bit_depth != 8 && d->bit_depth != 16 && d->bit_depth != 24 && d->bit_depth != 32) return fail(AUKIT_E_ARG, "bad argument #2 (invalid bit depth)");
-    if (d->data_type < 0 || d->data_type > 2) return fail(AUKIT_E_ARG, "bad argument #3 (invalid data type)");
-    if (d->data_type == AUKIT_FLOAT && d->bit_depth != 32) return fail(AUKIT_E_ARG, "bad argument #2 (float audio must have 32-bit depth)");
-    if (d->channels < 1) return fail(AUKIT_E_ARG, "bad argument #4 (number outside of range)");
-    if (d->sample_rate < 1) return fail(AUKIT_E_ARG, "bad argument #5 (number outside of range)");
-    if (d->channels > AUKIT_MAX_PLANAR_CHANNELS) return fail(AUKIT_E_UNSUPPORTED, "at most %d channels are supported", AUKIT_MAX_PLANAR_CHANNELS);
-    return AUKIT_OK;
-}
-
-// aukit.stream.adpcm's derived quantities for one descriptor (:2761, :2765-2768), as ima_stream (codecs.hip) computes them
-struct SMixImaGeom {
-    uint64_t ba, hdr, nwr, ips, row_len;
-    double ratio, spb, iter_per_second, bytes_per_second, newlen_full;
-    explicit SMixImaGeom(const aukit_codec_desc *d) {
-        const int C = d->channels;
-        ba = (uint64_t)d->block_align; hdr = 4ull * C; nwr = (ba - hdr) / hdr;
-        ratio = 48000 / d->sample_rate;                       // :2761
-        spb = (double)(ba - hdr) * 2 / C;                     // samplesPerBlock  :2765
-        iter_per_second = std::ceil(d->sample_rate / spb);    // :2766
-        bytes_per_second = (double)ba * iter_per_second;      // :2767
-        newlen_full = std::floor(spb * ratio);                // :2768
-        ips = iter_per_second < 9e18 ? (uint64_t)iter_per_second : 0;
-        row_len = 8 * (nwr + 1);                              // samplesPerBlock + 8: the junk word's entries behind the block's
-    }
-    uint64_t blocks(uint64_t nb) const { return nb >= hdr + 1 ? (nb - hdr - 1) / ba + 1 : 0; }  // processed: while n + 4C <= #data (1-based n)  :2794
-    uint64_t entries(uint64_t nb, uint64_t bi) const {  // #d[1] of block bi: eight per word group decoded  :2800-2802
-        const uint64_t rem = nb - bi * ba;
-        long long ng = (long long)((rem - 1) / hdr) - 1;
-        if (ng > (long long)nwr + 1) ng = (long long)nwr + 1;
-        return ng < 0 ? 0 : (uint64_t)ng * 8;
-    }
-};
-
 // everything the stream's own aukit_stream_decode call refuses (stream_pcm / stream_g711, api_resample.hip), with its words; and the one thing that
 // call serves and this one does not: the uneven last chunk
 static int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) {
@@ -503,7 +455,7 @@ static int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) 
         if (C < 1 || C > AUKIT_MAX_PLANAR_CHANNELS) return fail(AUKIT_E_ARG, "channels out of range");
         if (d->block_align <= 4 * C || (d->block_align - 4 * C) % (4 * C) != 0) return fail(AUKIT_E_UNSUPPORTED, "blockAlign must be 4*channels*(k+1)");
         // blocks are counted, and a call's outputs are, in 32 bits here (one block at 1 Hz yields 48 000 outputs per sample)
-        const SMixImaGeom G(d);
+        const ImaGeom G(C, d->block_align, d->sample_rate);
         const uint64_t nblk = G.blocks(nb);
         if (nblk > 0x7FFFFFF0ull || G.row_len > 0x7FFFFFF0ull || !(G.iter_per_second < 9e18) || G.newlen_full * (double)std::max<uint64_t>(std::min<uint64_t>(nblk, G.ips), 1) > 2147483632.0)
             return fail(AUKIT_E_UNSUPPORTED, "stream too long");
@@ -511,7 +463,7 @@ static int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) 
     }
     if (d->codec == AUKIT_CODEC_PCM) {
         int rc;
-        if ((rc = check_smix_pcm(d))) return rc;
+        if ((rc = check_pcm_desc(d))) return rc;
         if (d->sample_rate > 48000) return fail(AUKIT_E_UNSUPPORTED, "stream.pcm above 48 kHz is ill-defined in the reference (lazy table read out of order, SURVEY Q3)");
         const size_t bd = (size_t)d->bit_depth / 8;
         if (nb % (bd * d->channels) != 0) {
@@ -531,119 +483,89 @@ static int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) 
     return AUKIT_OK;
 }
 
-template <typename OUT_T, bool DF, bool IM>
-static int launch_smix(aukit_ctx *ctx, int interp, const SMixParams &P, size_t lds, unsigned grid) {
-    switch (interp) {
-    case AUKIT_INTERP_NONE: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_NONE, OUT_T, DF, IM>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
-    case AUKIT_INTERP_LINEAR: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_LINEAR, OUT_T, DF, IM>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
-    default: hipLaunchKernelGGL((k_stream_mixed<AUKIT_INTERP_CUBIC, OUT_T, DF, IM>), dim3(grid), dim3(256), lds, ctx->stream, P); break;
-    }
-    AUKIT_HIP_CHECK(hipGetLastError());
+// ---- phase 1: everything that can refuse from the arguments, the descriptors and the byte counts alone
+static int smix_validate(const aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out) {
+    int rc;
+    if ((rc = mixed_check_call(ctx, in, out, descs, n_descs, interp, dtype, "invalid interpolation", "stream each class with aukit_stream_decode"))) return rc;
+    if ((rc = mixed_check_codecs(descs, in->n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV},
+                                 "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, "
+                                 "AUKIT_CODEC_DFPWM and AUKIT_CODEC_ADPCM_WAV)")))
+        return rc;
+    if ((rc = mixed_check_channels(in->n, mono, [&](uint32_t s) { return descs[s].channels; }))) return rc;
+    for (uint32_t s = 0; s < in->n; s++)
+        if ((rc = check_smix_stream(&descs[s], in->off[s + 1] - in->off[s], mono != 0))) return fail_for_stream(rc, s);
     return AUKIT_OK;
 }
 
-}  // namespace aukit
-
-using namespace aukit;
-
-extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype,
-                                         aukit_audio **out, aukit_chunks **chunks) {
-    if (!ctx || !in || !out || (!descs && n_descs)) return fail(AUKIT_E_ARG, "null argument");
-    if (dtype != AUKIT_F64 && dtype != AUKIT_F32) return fail(AUKIT_E_ARG, "dtype must be AUKIT_F64 or AUKIT_F32");
-    if (interp < 0 || interp > 3) return fail(AUKIT_E_ARG, "invalid interpolation");
-    if (interp == AUKIT_INTERP_SINC) return fail(AUKIT_E_UNSUPPORTED, "sinc interpolation is not served for per-stream descriptors: stream each class with aukit_stream_decode");
-    if (n_descs != in->n) return fail(AUKIT_E_ARG, "%u descriptors for a batch of %u streams", n_descs, in->n);
-    const uint32_t n = in->n;
-    bool has_df = false, has_ima = false;
-    for (uint32_t s = 0; s < n; s++) {
-        if (descs[s].codec != AUKIT_CODEC_PCM && descs[s].codec != AUKIT_CODEC_G711 && descs[s].codec != AUKIT_CODEC_DFPWM && descs[s].codec != AUKIT_CODEC_ADPCM_WAV)
-            return fail(AUKIT_E_UNSUPPORTED,
-                        "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM and AUKIT_CODEC_ADPCM_WAV)", s,
-                        descs[s].codec);
-        has_df = has_df || descs[s].codec == AUKIT_CODEC_DFPWM;
-        has_ima = has_ima || descs[s].codec == AUKIT_CODEC_ADPCM_WAV;
-    }
-    if (!mono)
-        for (uint32_t s = 1; s < n; s++)
-            if (descs[s].channels != descs[0].channels) return fail(AUKIT_E_ARG, "streams differ in channel count: mix down or split the batch");
-    for (uint32_t s = 0; s < n; s++) {
-        const int rc = check_smix_stream(&descs[s], in->off[s + 1] - in->off[s], mono != 0);
-        if (rc) {  // the stream's own call would fail: its status and words, and which stream it is
-            const std::string m = aukit_last_error();
-            return fail(rc, "%s (stream %u)", m.c_str(), s);
-        }
-    }
-
-    // classes: one per distinct descriptor, in order of first appearance; the tile height is the class's
-    int hl = 0, hr = 0;
-    if (interp == AUKIT_INTERP_LINEAR) { hr = 1; }
-    else if (interp == AUKIT_INTERP_CUBIC) { hl = 1; hr = 2; }
-    typedef std::tuple<int, int, int, int, int, int, int, double> ClassKey;
-    std::map<ClassKey, unsigned> index;
+// ---- phase 2: the class table — one class per distinct descriptor, in order of first appearance; the tile height is the class's
+struct SMixClasses {
     std::vector<SMixClass> classes;
-    std::vector<int> tile_out;  // per class
-    std::vector<unsigned> cls_of(n);
-    size_t lds = 0;
+    std::vector<int> tile_out;     // per class
+    std::vector<unsigned> cls_of;  // per stream
+    size_t lds = 0;                // the largest class's
+    bool has_df = false, has_ima = false;
+};
+
+static int smix_classes(const aukit_codec_desc *descs, uint32_t n, int interp, int mono, SMixClasses &T) {
+    int hl, hr;
+    mixed_halos(interp, &hl, &hr);
+    ClassIndex<std::tuple<int, int, int, int, int, int, int, double>> index;
+    T.cls_of.resize(n);
     for (uint32_t s = 0; s < n; s++) {
         const aukit_codec_desc &d = descs[s];
         const bool pcm = d.codec == AUKIT_CODEC_PCM, df = d.codec == AUKIT_CODEC_DFPWM, ima = d.codec == AUKIT_CODEC_ADPCM_WAV;
-        const ClassKey key(d.codec, pcm ? d.bit_depth : 8, pcm ? d.data_type : 0, pcm ? (d.big_endian ? 1 : 0) : 0, d.channels, pcm || df || ima ? 0 : (d.ulaw ? 1 : 0),
-                           ima ? d.block_align : 0, d.sample_rate);
-        auto it = index.find(key);
-        if (it == index.end()) {
-            SMixClass K;
-            memset(&K, 0, sizeof K);
-            K.ratio = 48000 / d.sample_rate;  // :2364, :2896
-            K.rcp = 1.0 / K.ratio;
-            K.lp_alpha = 1 - std::exp(-(d.sample_rate / 96000) * 2 * M_PI);  // :2365
-            K.g711_scale = 1.0 / 64.0;  // m / 0x40  :2891
-            K.codec = d.codec;
-            K.bytes = pcm ? d.bit_depth / 8 : 1;
-            K.data_type = pcm ? d.data_type : 0;
-            K.big_endian = pcm && d.big_endian ? 1 : 0;
-            K.ulaw = d.ulaw ? 1 : 0;
-            K.channels = d.channels;
-            if (pcm) {
-                K.mix = (mono && d.channels > 1) ? 1 : 0;  // with one channel `mono` is ignored  :2243
-                K.stage = K.mix ? 1 : d.channels;
-                K.epi = SMIX_EPI_PCM;
-            } else if (df) {
-                K.mix = (mono && d.channels > 1) ? 1 : 0;  // if channels == 1 then mono = false end  :2445
-                K.stage = 1;                               // the row is flat: the step of `channels` is in the position
-                K.epi = SMIX_EPI_DFPWM;
-            } else {
-                K.mix = mono ? 1 : 0;
-                K.stage = d.channels;
-                K.epi = SMIX_EPI_FLOOR;
-            }
-            K.s16le_mono = (pcm && d.bit_depth == 16 && d.data_type == AUKIT_SIGNED && !d.big_endian && d.channels == 1) ? 1 : 0;
-            // tile height: the staged window (tile_out / ratio + halo) x staged channels x 8 B within plan_tiles' budget; 64 KiB at the most
-            // DFPWM: outputs advance `channels` table steps at a time (rates above 48 kHz widen the window further); 16-byte loads of int8: +64, the
-            // kernel's margin is 32
-            const int slack = hl + hr + 2 + (df ? 64 : 32);  // +32: the vector path's alignment head and tail, the FIR's look-back, the kernel's own margin of 16
-            const double eff = df ? K.ratio / d.channels : K.ratio;
-            auto cap_for = [&](int to) { return (int)std::ceil((double)to / eff) + slack; };
-            const size_t budget = 24 * 1024, hard = 64 * 1024;
-            int to = 2048;
-            while (to > 256 && (size_t)cap_for(to) * 8 * K.stage > budget) to -= 256;
-            while (to > 64 && (size_t)cap_for(to) * 8 * K.stage > hard) to -= 64;
-            if ((size_t)cap_for(to) * 8 * K.stage > hard)
-                return fail(AUKIT_E_UNSUPPORTED, "resampling ratio %g with %d channels needs more than 64 KiB of LDS per tile (stream %u)", K.ratio, K.stage, s);
-            K.cap = (cap_for(to) + 1) & ~1;
-            if (ima) {  // stream.adpcm's epilogue is stream.g711's (above); a tile's window never leaves its block's table
-                const SMixImaGeom G(&d);
-                K.nl_full = (unsigned)G.newlen_full;
-                K.row_len = (int)G.row_len;
-                K.cap = (int)std::min<uint64_t>((uint64_t)K.cap, (G.row_len + (uint64_t)slack + 1) & ~1ull);
-            }
-            lds = std::max(lds, (size_t)K.cap * 8 * K.stage);
-            it = index.emplace(key, (unsigned)classes.size()).first;
-            classes.push_back(K);
-            tile_out.push_back(to);
+        T.has_df = T.has_df || df;
+        T.has_ima = T.has_ima || ima;
+        bool fresh;
+        T.cls_of[s] = index.of({d.codec, pcm ? d.bit_depth : 8, pcm ? d.data_type : 0, pcm ? (d.big_endian ? 1 : 0) : 0, d.channels, pcm || df || ima ? 0 : (d.ulaw ? 1 : 0),
+                                ima ? d.block_align : 0, d.sample_rate}, &fresh);
+        if (!fresh) continue;
+        SMixClass K;
+        memset(&K, 0, sizeof K);
+        K.ratio = 48000 / d.sample_rate;  // :2364, :2896
+        K.rcp = 1.0 / K.ratio;
+        K.lp_alpha = 1 - std::exp(-(d.sample_rate / 96000) * 2 * M_PI);  // :2365
+        K.g711_scale = 1.0 / 64.0;  // m / 0x40  :2891
+        K.codec = d.codec;
+        K.bytes = pcm ? d.bit_depth / 8 : 1;
+        K.data_type = pcm ? d.data_type : 0;
+        K.big_endian = pcm && d.big_endian ? 1 : 0;
+        K.ulaw = d.ulaw ? 1 : 0;
+        K.channels = d.channels;
+        if (pcm) {
+            K.mix = (mono && d.channels > 1) ? 1 : 0;  // with one channel `mono` is ignored  :2243
+            K.stage = K.mix ? 1 : d.channels;
+            K.epi = SMIX_EPI_PCM;
+        } else if (df) {
+            K.mix = (mono && d.channels > 1) ? 1 : 0;  // if channels == 1 then mono = false end  :2445
+            K.stage = 1;                               // the row is flat: the step of `channels` is in the position
+            K.epi = SMIX_EPI_DFPWM;
+        } else {
+            K.mix = mono ? 1 : 0;
+            K.stage = d.channels;
+            K.epi = SMIX_EPI_FLOOR;
         }
-        cls_of[s] = it->second;
+        K.s16le_mono = (pcm && d.bit_depth == 16 && d.data_type == AUKIT_SIGNED && !d.big_endian && d.channels == 1) ? 1 : 0;
+        // DFPWM: outputs advance `channels` table steps at a time (rates above 48 kHz widen the window further); 16-byte loads of int8: +64, the
+        // kernel's margin is 32.  +32 otherwise: the vector path's alignment head and tail, the FIR's look-back, the kernel's own margin of 16
+        const int slack = hl + hr + 2 + (df ? 64 : 32);
+        int to, rc;
+        if ((rc = mixed_tile_height(K.ratio, df ? K.ratio / d.channels : K.ratio, K.stage, slack, 64 * 1024, s, &to, &K.cap))) return rc;
+        if (ima) {  // stream.adpcm's epilogue is stream.g711's (above); a tile's window never leaves its block's table
+            const ImaGeom G(d.channels, d.block_align, d.sample_rate);
+            K.nl_full = (unsigned)G.newlen_full;
+            K.row_len = (int)G.row_len;
+            K.cap = (int)std::min<uint64_t>((uint64_t)K.cap, (G.row_len + (uint64_t)slack + 1) & ~1ull);
+        }
+        T.lds = std::max(T.lds, (size_t)K.cap * 8 * K.stage);
+        T.classes.push_back(K);
+        T.tile_out.push_back(to);
     }
-    AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
+    return AUKIT_OK;
+}
+
+// the exact_div_verified verdict of every class, for as many positions as one of its segments (an IMA class: one of its blocks) can ask for
+static void smix_exact_division(aukit_ctx *ctx, std::vector<SMixClass> &classes) {
     for (SMixClass &K : classes) {
         if (K.codec == AUKIT_CODEC_ADPCM_WAV) {  // outputs are counted within a block: the verdict covers a full block's, or the kernel divides
             K.exact_rcp = (K.nl_full <= 4000000u && exact_div_verified(ctx, K.ratio, (uint64_t)K.nl_full + 2)) ? 1 : 0;
@@ -654,312 +576,340 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
         const double top = (double)(8 * (6000ull * K.channels + 1)) * K.ratio + K.channels + 1;
         K.exact_rcp = (top <= 4e6 && exact_div_verified(ctx, K.ratio, (uint64_t)top)) ? 1 : 0;
     }
+}
 
-    // stream.adpcm: which streams die on a header step index above 88, and in which block — only the device knows, and the rows' lengths depend on it.
-    // The scan writes ctx->scan_buf (the verdicts, the stream table behind them) and nothing else; its answer is awaited here
-    std::vector<SMixImaStream> ima_tab;   // per IMA stream, in batch order
-    std::vector<unsigned> ima_bad;
-    if (has_ima) {
-        for (uint32_t s = 0; s < n; s++)
-            if (descs[s].codec == AUKIT_CODEC_ADPCM_WAV) ima_tab.push_back(SMixImaStream{in->off[s], in->off[s + 1] - in->off[s], 0, 0, descs[s].channels, descs[s].block_align});
-        const size_t m = ima_tab.size(), tab_at = (size_t)round_up(m * 4, 16);
-        ima_bad.assign(m, 0xFFFFFFFFu);
-        int rc0 = ctx->scan_buf.ensure(tab_at + m * sizeof(SMixImaStream) + 16);
-        if (rc0) return rc0;
-        unsigned *d_bad = reinterpret_cast<unsigned *>(ctx->scan_buf.p);
-        SMixImaStream *d_tab = reinterpret_cast<SMixImaStream *>(reinterpret_cast<char *>(ctx->scan_buf.p) + tab_at);
-        if ((rc0 = h2d_table(ctx, d_tab, ima_tab.data(), m * sizeof(SMixImaStream)))) return rc0;
-        hipLaunchKernelGGL(k_smix_ima_scan, dim3((unsigned)m), dim3(64), 0, ctx->stream, in->data(), d_tab, (unsigned)m, d_bad);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(ima_bad.data(), d_bad, m * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess)
-            return fail(AUKIT_E_HIP, "stream.adpcm header scan failed");
-    }
+// ---- phase 3: stream.adpcm — which streams die on a header step index above 88, and in which block: only the device knows, and the rows' lengths
+// depend on it.  The scan writes ctx->scan_buf (the verdicts, the stream table behind them) and nothing else; its answer is awaited here.
+// -> bad: per IMA stream, in batch order, the first such block (0xFFFFFFFF: none)
+static int smix_ima_scan(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, std::vector<unsigned> &bad) {
+    std::vector<SMixImaStream> tab;
+    for (uint32_t s = 0; s < in->n; s++)
+        if (descs[s].codec == AUKIT_CODEC_ADPCM_WAV) tab.push_back(SMixImaStream{in->off[s], in->off[s + 1] - in->off[s], 0, 0, descs[s].channels, descs[s].block_align});
+    const size_t m = tab.size(), tab_at = (size_t)round_up(m * 4, 16);
+    bad.assign(m, 0xFFFFFFFFu);
+    int rc = ctx->scan_buf.ensure(tab_at + m * sizeof(SMixImaStream) + 16);
+    if (rc) return rc;
+    unsigned *d_bad = reinterpret_cast<unsigned *>(ctx->scan_buf.p);
+    SMixImaStream *d_tab = reinterpret_cast<SMixImaStream *>(reinterpret_cast<char *>(ctx->scan_buf.p) + tab_at);
+    if ((rc = h2d_table(ctx, d_tab, tab.data(), m * sizeof(SMixImaStream)))) return rc;
+    hipLaunchKernelGGL(k_smix_ima_scan, dim3((unsigned)m), dim3(64), 0, ctx->stream, in->data(), d_tab, (unsigned)m, d_bad);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(bad.data(), d_bad, m * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess)
+        return fail(AUKIT_E_HIP, "stream.adpcm header scan failed");
+    return AUKIT_OK;
+}
 
-    // segments: one per (stream, iterator call); the chunk table beside them.  stream.pcm's plan is made once per distinct rate
-    std::map<double, ChunkPlan> plans;
-    std::vector<SMixSeg> segs;
-    std::vector<std::vector<uint32_t>> clens(n);
-    std::vector<std::vector<double>> cpos(n);
-    std::vector<uint64_t> lens(n, 0);
-    aukit_chunks *ck = new aukit_chunks();
-    ck->n = n;
-    ck->nchunks.assign(n, 0);
-    ck->status.assign(n, 0);
-    ck->length_seconds.assign(n, 0);
-    uint64_t in_bytes = 0, out_elems = 0;
-    // the DFPWM streams that have bytes, by channel count (the engine's run and stride are per call): first byte, fed bytes, row offset
-    struct DfGroup { std::vector<uint64_t> off, fed, row; std::vector<SMixDfItem> items; };
-    std::map<int, DfGroup> df_groups;
+// ---- phase 4: the plan — one segment per (stream, iterator call) with the chunk table beside it, and what the pre-passes have to decode.  The
+// planners below fill it from a descriptor and a byte count; they touch neither the context nor HIP
+struct SMixDfGroup : DfRowGroup { std::vector<SMixDfItem> items; };  // (and, for the lane-per-stream kernel, the same streams as items)
+struct SMixPlan {
+    std::vector<SMixSeg> segs;                // stream after stream, call after call
+    std::vector<double> cpos;                 // per segment: the position its iterator call returns
+    std::vector<uint64_t> lens;               // per stream: outputs of all its calls
+    std::unique_ptr<aukit_chunks> ck;         // held here until the call delivers it
+    std::map<double, ChunkPlan> pcm_plans;    // stream.pcm's plan is made once per distinct rate
+    // the DFPWM streams that have bytes, by channel count (the engine's run and stride are per call); bytes of all rows, source bytes, streams
+    std::map<int, SMixDfGroup> df_groups;
     uint64_t df_tot = 0, df_src = 0;
     uint32_t df_n = 0;
-    // the IMA streams: int16 entries of the rows so far, (block, channel) jobs so far, bytes read; the streams that have a planned block
-    uint64_t ima_elems = 0, ima_jobs = 0, ima_src = 0;
-    size_t ima_i = 0;
+    // the IMA streams that have a planned block; int16 entries of their rows, (block, channel) jobs, bytes read
     std::vector<SMixImaStream> ima_rows;
-    for (uint32_t s = 0; s < n; s++) {
+    uint64_t ima_elems = 0, ima_jobs = 0, ima_src = 0;
+    uint64_t in_bytes = 0;
+
+    explicit SMixPlan(uint32_t n) : lens(n, 0), ck(new aukit_chunks()) {
+        ck->n = n;
+        ck->nchunks.assign(n, 0);
+        ck->status.assign(n, 0);
+        ck->length_seconds.assign(n, 0);
+    }
+    // one iterator call of stream s: g.n_out outputs behind the stream's earlier ones (the row's offset is added once the audio is laid out)
+    void add_call(uint32_t s, SMixSeg &g, double pos) {
+        g.out_off = lens[s];
+        segs.push_back(g);
+        cpos.push_back(pos);
+        lens[s] += g.n_out;
+        ck->nchunks[s]++;
+    }
+};
+// (the planners take `g` with src_off — the stream's first byte in the batch — and cls filled in)
+
+static void plan_pcm(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc &d, uint64_t nb, int interp, bool mono) {
+    const int C = d.channels, bd = d.bit_depth / 8;
+    const bool is_float = d.data_type == AUKIT_FLOAT, mix = mono && C > 1;
+    auto pit = pl.pcm_plans.find(d.sample_rate);
+    if (pit == pl.pcm_plans.end()) {
+        pit = pl.pcm_plans.emplace(d.sample_rate, ChunkPlan()).first;
+        build_chunk_plan(d.sample_rate, interp, pit->second);
+    }
+    const ChunkPlan &cp = pit->second;
+    const long long nframes = (long long)(nb / ((size_t)bd * C));  // with the mix-down a partial frame counts for nothing
+    pl.ck->length_seconds[s] = ((double)nb / bd) / C / d.sample_rate;  // :2245, :2423
+    for (long c = 0;; c++) {
+        Seg q;
+        g.n_out = stream_pcm_call(cp, c, nframes, is_float, mix, &q, &pl.ck->status[s]);
+        if (g.n_out == 0) break;
+        g.src_base = q.src_base; g.w_lo = q.w_lo; g.w_hi = q.w_hi;
+        pl.add_call(s, g, (double)pl.lens[s] / 48000);  // (n - #chunk[1]) / 48000  :2422
+        if (g.n_out < 48000) break;  // ok = false → the next call returns nil
+    }
+}
+
+// every call is independent (Q13): its own table, indices 1 .. m.  A byte count that is no multiple of the channel count: the last call raises
+// (stream_g711, api_resample.hip), the calls before it deliver their chunks
+static void plan_g711(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc &d, uint64_t nb) {
+    const int C = d.channels;
+    const double ratio = 48000 / d.sample_rate;
+    const uint64_t per_call = (uint64_t)d.sample_rate * (uint64_t)C;
+    pl.ck->length_seconds[s] = (double)nb / d.sample_rate / C;
+    uint32_t calls = (uint32_t)((nb + per_call - 1) / per_call);  // calls that see data; the reference then returns {{}} forever
+    if (nb % (uint64_t)C != 0) { calls--; pl.ck->status[s] = AUKIT_E_LUA; }
+    for (uint32_t k = 0; k < calls; k++) {
+        const uint64_t pos = (uint64_t)k * per_call;
+        const uint64_t m = std::min<uint64_t>(per_call, nb - pos) / C;  // #retval[1]
+        g.src_base = (long long)(pos / C) - 1;
+        g.w_lo = 1; g.w_hi = (int)m;
+        g.n_out = (uint32_t)std::floor((double)m * ratio);  // :2897
+        pl.add_call(s, g, ((double)(pos + 1) - 1) / d.sample_rate / C);  // (lp - 1) / sampleRate / channels
+    }
+}
+
+// stream_dfpwm's plan (codecs2.hip) from byte 0: slices of adv + 1 bytes advanced by adv; a call's table starts at the row element that holds the
+// call before's last sample (element 0: the leading 0)
+static void plan_dfpwm(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc &d, uint64_t nb) {
+    const int C = d.channels;
+    const uint64_t adv = 6000ull * C, slice = adv + 1, src_off = g.src_off;
+    const double ratio = 48000 / d.sample_rate;  // :2473
+    pl.ck->length_seconds[s] = (double)nb * 8 / d.sample_rate / C;  // :2495
+    uint64_t fed8 = 0, k = 0;
+    g.src_off = pl.df_tot;  // the row; where it lies is settled here, before anything is allocated
+    g.w_lo = 0;
+    for (uint64_t pos = 0; pos < nb; pos += adv, k++) {
+        const uint64_t na = std::min<uint64_t>(slice, nb - pos) * 8;
+        const double newlen = (double)na * ratio;                                              // :2474
+        g.n_out = newlen >= 1 ? (uint32_t)(std::floor((newlen - 1) / C) + 1) : 0;              // for i = 1, newlen, channels
+        g.src_base = (long long)fed8; g.w_hi = (int)na;
+        pl.add_call(s, g, (double)(k * adv + 1) * 8 / d.sample_rate / C);  // p * 8 / sampleRate / channels  :2494
+        fed8 += na;
+    }
+    if (!nb) return;
+    SMixDfGroup &G = pl.df_groups[C];
+    G.run = slice; G.stride = adv;
+    G.off.push_back(src_off); G.fed.push_back(fed8 / 8); G.row.push_back(pl.df_tot);
+    G.items.push_back(SMixDfItem{src_off, nb, pl.df_tot, adv});
+    pl.df_tot += round_up(fed8 + 1, 16);
+    pl.df_src += nb;
+    pl.df_n++;
+}
+
+// ima_stream's plan (codecs.hip) from byte 0, call after call (ima_call, ima_geom.h); a header index above 88, in block `bad`, kills the call that
+// reaches it and everything behind it
+static void plan_ima(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc &d, uint64_t nb, unsigned bad) {
+    const int C = d.channels;
+    const ImaGeom G(C, d.block_align, d.sample_rate);
+    const uint64_t nblk = G.blocks(nb), src_off = g.src_off;
+    pl.ck->length_seconds[s] = (double)nb / (double)G.ba * G.spb / d.sample_rate;  // :2834
+    uint64_t calls_ok = ~0ull, done = 0;
+    if (bad != 0xFFFFFFFFu) { calls_ok = (uint64_t)bad / std::max<uint64_t>(G.ips, 1); pl.ck->status[s] = AUKIT_E_LUA; }  // "attempt to perform arithmetic on a nil value (field '?')"
+    g.src_off = pl.ima_elems;
+    g.w_lo = 1;
+    for (uint64_t call = 0; call != calls_ok; call++) {
+        const ImaCall c = ima_call(G, nb, nblk, done);
+        if (c.produced == 0) break;  // #retval[1] == 0 -> nil  :2832
+        g.src_base = (long long)done; g.w_hi = (int)c.m_last; g.nblk = (unsigned)c.take; g.n_out = (uint32_t)c.produced;
+        done += c.take;
+        pl.add_call(s, g, (double)(done * G.ba + 1) / G.bytes_per_second);  // (n + pos) / bytesPerSecond  :2833
+        if (done >= nblk) break;  // the next call sees n + 4C > #data and returns nil
+    }
+    if (!done) return;  // `done` blocks are planned: the pre-pass decodes those
+    pl.ima_rows.push_back(SMixImaStream{src_off, nb, pl.ima_elems, pl.ima_jobs, C, d.block_align});
+    pl.ima_elems += done * (uint64_t)C * G.row_len;
+    pl.ima_jobs += done * (uint64_t)C;
+    pl.ima_src += std::min<uint64_t>(nb, done * G.ba + G.hdr);
+}
+
+static void smix_plan(const aukit_batch *in, const aukit_codec_desc *descs, const std::vector<unsigned> &cls_of, int interp, bool mono, const std::vector<unsigned> &ima_bad,
+                      SMixPlan &pl) {
+    size_t ima_i = 0;
+    for (uint32_t s = 0; s < in->n; s++) {
         const aukit_codec_desc &d = descs[s];
         const uint64_t nb = in->off[s + 1] - in->off[s];
-        const int C = d.channels;
-        in_bytes += nb;
+        pl.in_bytes += nb;
         SMixSeg g;
         memset(&g, 0, sizeof g);
         g.src_off = in->off[s];
         g.cls = cls_of[s];
-        if (d.codec == AUKIT_CODEC_DFPWM) {
-            // stream_dfpwm's plan (codecs2.hip) from byte 0: slices of adv + 1 bytes advanced by adv; a call's table starts at the row element that holds
-            // the call before's last sample (element 0: the leading 0)
-            const uint64_t adv = 6000ull * C, slice = adv + 1;
-            const double ratio = 48000 / d.sample_rate;  // :2473
-            ck->length_seconds[s] = (double)nb * 8 / d.sample_rate / C;  // :2495
-            uint64_t fed8 = 0, k = 0;
-            for (uint64_t pos = 0; pos < nb; pos += adv, k++) {
-                const uint64_t cnt = std::min<uint64_t>(slice, nb - pos), na = cnt * 8;
-                const double newlen = (double)na * ratio;                                                          // :2474
-                const uint32_t m = newlen >= 1 ? (uint32_t)(std::floor((newlen - 1) / C) + 1) : 0;                 // for i = 1, newlen, channels
-                g.src_off = df_tot;  // the row; where it lies is settled here, before anything is allocated
-                g.src_base = (long long)fed8; g.w_lo = 0; g.w_hi = (int)na; g.n_out = m;
-                g.out_off = lens[s];
-                segs.push_back(g);
-                clens[s].push_back(m);
-                cpos[s].push_back((double)(k * adv + 1) * 8 / d.sample_rate / C);  // p * 8 / sampleRate / channels  :2494
-                lens[s] += m;
-                fed8 += na;
-            }
-            if (nb) {
-                DfGroup &G = df_groups[C];
-                G.off.push_back(in->off[s]); G.fed.push_back(fed8 / 8); G.row.push_back(df_tot);
-                G.items.push_back(SMixDfItem{in->off[s], nb, df_tot, adv});
-                df_tot += round_up(fed8 + 1, 16);
-                df_src += nb;
-                df_n++;
-            }
-        } else if (d.codec == AUKIT_CODEC_ADPCM_WAV) {
-            // ima_stream's plan (codecs.hip) from byte 0: an iterator call takes up to iterPerSecond blocks; every block but the stream's last sees at
-            // least blockAlign + 4C more bytes — all its word groups plus the junk word (Q6) — and yields newlen_full outputs, so block k of a call
-            // starts at output k * newlen_full of its chunk; a header index above 88 kills the call that reaches it and everything behind it
-            const SMixImaGeom G(&d);
-            const uint64_t nblk = G.blocks(nb), nl_full = (uint64_t)G.newlen_full;
-            const unsigned bad = ima_bad[ima_i];
-            SMixImaStream &S = ima_tab[ima_i++];
-            ck->length_seconds[s] = (double)nb / (double)G.ba * G.spb / d.sample_rate;  // :2834
-            uint64_t calls_ok = ~0ull, done = 0, planned = 0;
-            if (bad != 0xFFFFFFFFu) { calls_ok = (uint64_t)bad / std::max<uint64_t>(G.ips, 1); ck->status[s] = AUKIT_E_LUA; }  // "attempt to perform arithmetic on a nil value (field '?')"
-            for (uint64_t call = 0; call != calls_ok; call++) {
-                const uint64_t take = std::min<uint64_t>(G.ips, nblk - done);
-                uint64_t full = take, produced = 0, m_last = G.row_len;
-                if (take && done + take == nblk) {  // the stream's last block: the arithmetic of :2800-2802 / :2817
-                    full = take - 1;
-                    m_last = G.entries(nb, nblk - 1);
-                    produced = (double)m_last < G.spb ? (uint64_t)std::floor((double)m_last * G.ratio) : nl_full;
-                }
-                produced += full * nl_full;
-                if (produced == 0) break;  // #retval[1] == 0 -> nil  :2832
-                g.src_off = ima_elems; g.src_base = (long long)done; g.w_lo = 1; g.w_hi = (int)m_last; g.nblk = (unsigned)take; g.n_out = (uint32_t)produced;
-                g.out_off = lens[s];
-                segs.push_back(g);
-                clens[s].push_back((uint32_t)produced);
-                done += take;
-                cpos[s].push_back((double)(done * G.ba + 1) / G.bytes_per_second);  // (n + pos) / bytesPerSecond  :2833
-                lens[s] += produced;
-                planned = done;
-                if (done >= nblk) break;  // the next call sees n + 4C > #data and returns nil
-            }
-            if (planned) {
-                S.row_off = ima_elems; S.job0 = ima_jobs;
-                ima_rows.push_back(S);
-                ima_elems += planned * (uint64_t)C * G.row_len;
-                ima_jobs += planned * (uint64_t)C;
-                ima_src += std::min<uint64_t>(nb, planned * G.ba + G.hdr);
-            }
-        } else if (d.codec == AUKIT_CODEC_PCM) {
-            const int bd = d.bit_depth / 8;
-            const bool is_float = d.data_type == AUKIT_FLOAT, mix = mono && C > 1;
-            auto pit = plans.find(d.sample_rate);
-            if (pit == plans.end()) {
-                pit = plans.emplace(d.sample_rate, ChunkPlan()).first;
-                build_chunk_plan(d.sample_rate, interp, pit->second);
-            }
-            const ChunkPlan &cp = pit->second;
-            const long long nframes = (long long)(nb / ((size_t)bd * C));  // with the mix-down a partial frame counts for nothing
-            ck->length_seconds[s] = ((double)nb / bd) / C / d.sample_rate;  // :2245, :2423
-            for (long c = 0;; c++) {
-                Seg q;
-                const uint32_t n_out = stream_pcm_call(cp, c, nframes, is_float, mix, &q, &ck->status[s]);
-                if (n_out == 0) break;
-                g.src_base = q.src_base; g.w_lo = q.w_lo; g.w_hi = q.w_hi; g.n_out = n_out;
-                g.out_off = lens[s];  // patched with the row offset below
-                segs.push_back(g);
-                clens[s].push_back(n_out);
-                cpos[s].push_back((double)lens[s] / 48000);  // (n - #chunk[1]) / 48000  :2422
-                lens[s] += n_out;
-                if (n_out < 48000) break;  // ok = false → the next call returns nil
-            }
-        } else {
-            // every call is independent (Q13): its own table, indices 1 .. m.  A byte count that is no multiple of the channel count: the last call
-            // raises (stream_g711, api_resample.hip), the calls before it deliver their chunks
-            const double ratio = 48000 / d.sample_rate;
-            const uint64_t per_call = (uint64_t)d.sample_rate * (uint64_t)C;
-            ck->length_seconds[s] = (double)nb / d.sample_rate / C;
-            uint32_t calls = (uint32_t)((nb + per_call - 1) / per_call);  // calls that see data; the reference then returns {{}} forever
-            if (nb % (uint64_t)C != 0) { calls--; ck->status[s] = AUKIT_E_LUA; }
-            for (uint32_t k = 0; k < calls; k++) {
-                const uint64_t pos = (uint64_t)k * per_call;
-                const uint64_t m = std::min<uint64_t>(per_call, nb - pos) / C;    // #retval[1]
-                const uint32_t n_out = (uint32_t)std::floor((double)m * ratio);   // :2897
-                g.src_base = (long long)(pos / C) - 1;
-                g.w_lo = 1; g.w_hi = (int)m; g.n_out = n_out;
-                g.out_off = lens[s];
-                segs.push_back(g);
-                clens[s].push_back(n_out);
-                cpos[s].push_back(((double)(pos + 1) - 1) / d.sample_rate / C);  // (lp - 1) / sampleRate / channels
-                lens[s] += n_out;
-            }
-        }
-        ck->nchunks[s] = (uint32_t)clens[s].size();
-        ck->max_chunks = std::max<uint32_t>(ck->max_chunks, ck->nchunks[s]);
+        if (d.codec == AUKIT_CODEC_DFPWM) plan_dfpwm(pl, s, g, d, nb);
+        else if (d.codec == AUKIT_CODEC_ADPCM_WAV) plan_ima(pl, s, g, d, nb, ima_bad[ima_i++]);
+        else if (d.codec == AUKIT_CODEC_PCM) plan_pcm(pl, s, g, d, nb, interp, mono);
+        else plan_g711(pl, s, g, d, nb);
     }
-    const size_t mc = std::max<uint32_t>(ck->max_chunks, 1);
-    ck->lens.assign((size_t)n * mc, 0);
-    ck->pos.assign((size_t)n * mc, 0);
-    for (uint32_t s = 0; s < n; s++)
-        for (uint32_t k = 0; k < ck->nchunks[s]; k++) {
-            ck->lens[(size_t)s * mc + k] = clens[s][k];
-            ck->pos[(size_t)s * mc + k] = cpos[s][k];
-        }
-    const int C_out = mono ? 1 : (n ? descs[0].channels : 1);
-    ck->channels = (uint32_t)C_out;
-    for (uint32_t s = 0; s < n; s++) out_elems += lens[s] * (uint64_t)C_out;
-    uint64_t nt = 0;
-    for (const SMixSeg &g : segs) {
-        const uint64_t to = (uint64_t)tile_out[g.cls];
-        if (classes[g.cls].codec == AUKIT_CODEC_ADPCM_WAV) {  // no tile straddles a block: the full blocks' tiles, and the last block's
-            const uint64_t nlf = classes[g.cls].nl_full, last = g.n_out - (uint64_t)(g.nblk - 1) * nlf;
-            nt += (uint64_t)(g.nblk - 1) * ((nlf + to - 1) / to) + (last + to - 1) / to;
-        } else nt += (g.n_out + to - 1) / to;
-    }
-    if (nt > 0xFFFFFFF0ull || ima_jobs > 0x7FFFFFF0ull * 64) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "too many tiles"); }
+}
 
-    aukit_audio *a = *out;
+// the chunk table of the plan: lengths and positions of every stream's calls, max_chunks apart
+static void smix_chunk_table(SMixPlan &pl, int C_out) {
+    aukit_chunks &ck = *pl.ck;
+    for (uint32_t s = 0; s < ck.n; s++) ck.max_chunks = std::max<uint32_t>(ck.max_chunks, ck.nchunks[s]);
+    const size_t mc = std::max<uint32_t>(ck.max_chunks, 1);
+    ck.lens.assign((size_t)ck.n * mc, 0);
+    ck.pos.assign((size_t)ck.n * mc, 0);
+    size_t i = 0;
+    for (uint32_t s = 0; s < ck.n; s++)
+        for (uint32_t k = 0; k < ck.nchunks[s]; k++, i++) {
+            ck.lens[(size_t)s * mc + k] = pl.segs[i].n_out;
+            ck.pos[(size_t)s * mc + k] = pl.cpos[i];
+        }
+    ck.channels = (uint32_t)C_out;
+}
+
+// ---- phase 5: the pre-passes' scratch in ctx->tmp_buf: the DFPWM streams' int8 rows (each at a multiple of 16 bytes) and behind them the pre-pass's
+// tables (a row offset per stream, then a lane-per-stream item per stream); behind the DFPWM scratch the IMA pre-pass's int16 rows (planned blocks x
+// channels x (samplesPerBlock + 8) entries: every row at a multiple of 16 bytes) and its stream table
+struct SMixScratch { size_t df_tab_at = 0, ima_at = 0, ima_tab_at = 0, size = 0; };
+static SMixScratch smix_scratch(const SMixPlan &pl) {
+    Carve carve;
+    SMixScratch L;
+    if (pl.df_n) { carve.take((size_t)pl.df_tot); L.df_tab_at = carve.take((size_t)pl.df_n * (8 + sizeof(SMixDfItem))); }  // (the rows are at 0)
+    if (pl.ima_jobs) { L.ima_at = carve.take((size_t)pl.ima_elems * 2); L.ima_tab_at = carve.take(pl.ima_rows.size() * sizeof(SMixImaStream)); }
+    L.size = carve.end;
+    return L;
+}
+
+// ---- phase 6: the pre-passes, each timed under its own name in front of the resample launch
+static int smix_dfpwm_prepass(aukit_ctx *ctx, const aukit_batch *in, const SMixPlan &pl, const SMixScratch &L) {
+    char *const T = reinterpret_cast<char *>(ctx->tmp_buf.p) + L.df_tab_at;
+    signed char *const rows = reinterpret_cast<signed char *>(ctx->tmp_buf.p);
+    std::vector<const DfRowGroup *> groups;
+    for (const auto &kv : pl.df_groups) groups.push_back(&kv.second);
+    std::vector<size_t> declined;
+    int rc = mixed_dfpwm_rows(ctx, in, groups, 1 /* behind the leading 0 */, rows, T, &declined, [&](const unsigned long long *d_row, uint32_t m) {
+        hipLaunchKernelGGL(k_smix_row_heads, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, rows, d_row, m);
+    });
+    if (rc) return rc;
+    std::vector<SMixDfItem> lanes;  // the streams of the groups the engine declined
+    for (size_t g : declined) {
+        const std::vector<SMixDfItem> &items = static_cast<const SMixDfGroup *>(groups[g])->items;
+        lanes.insert(lanes.end(), items.begin(), items.end());
+    }
+    if (!lanes.empty()) {
+        SMixDfItem *d_items = reinterpret_cast<SMixDfItem *>(T + (size_t)pl.df_n * 8);
+        if ((rc = h2d_table(ctx, d_items, lanes.data(), lanes.size() * sizeof(SMixDfItem)))) return rc;
+        hipLaunchKernelGGL(k_smix_dfpwm_rows, dim3(((unsigned)lanes.size() + 63) / 64), dim3(64), 0, ctx->stream, in->data(), d_items, (unsigned)lanes.size(), rows);
+    }
+    if (hipGetLastError() != hipSuccess) return fail(AUKIT_E_HIP, "DFPWM pre-pass launch failed");
+    return ctx_end_kernel(ctx, declined.size() < groups.size() ? "k_df_chunks(parallel dfpwm decode)" : "k_smix_dfpwm_rows", pl.df_src + pl.df_tot);
+}
+
+static int smix_ima_prepass(aukit_ctx *ctx, const aukit_batch *in, const SMixPlan &pl, const SMixScratch &L) {
+    short *const rows16 = reinterpret_cast<short *>(reinterpret_cast<char *>(ctx->tmp_buf.p) + L.ima_at);
+    SMixImaStream *const d_tab = reinterpret_cast<SMixImaStream *>(reinterpret_cast<char *>(ctx->tmp_buf.p) + L.ima_tab_at);
     int rc;
-    // the pre-pass's scratch: the int8 rows (each at a multiple of 16 bytes, 64 bytes to spare behind the last) and behind them its tables, in
-    // ctx->tmp_buf — sized before `*out` is touched.  audio_prepare may swap ctx->tmp_buf for the larger buffer of an `*out` that owes a resample
-    // (lazy_drop): the scratch is asked to be at least that large, so it stays, and the pointer is read after it all the same
-    // Behind the DFPWM scratch, at a multiple of 256 bytes: the IMA pre-pass's int16 rows (planned blocks x channels x (samplesPerBlock + 8) entries:
-    // every row at a multiple of 16 bytes) and its stream table.
-    const size_t df_tab_at = (size_t)round_up(df_tot + 64, 256);
-    const size_t ima_at = df_n ? (size_t)round_up(df_tab_at + (size_t)df_n * (8 + sizeof(SMixDfItem)) + 64, 256) : 0;
-    const size_t ima_tab_at = (size_t)round_up(ima_at + ima_elems * 2 + 64, 256);
-    if (df_n || ima_jobs) {
-        size_t need = ima_jobs ? ima_tab_at + ima_rows.size() * sizeof(SMixImaStream) + 64 : df_tab_at + (size_t)df_n * (8 + sizeof(SMixDfItem)) + 64;
-        if (*out && (*out)->lazy_rows.p && !(*out)->lazy_indirect) need = std::max(need, (*out)->lazy_rows.cap);
-        if ((rc = ctx->tmp_buf.ensure(need))) { delete ck; return rc; }
-    }
-    if ((rc = audio_prepare(ctx, &a, n, C_out, 48000, dtype, lens.data()))) { delete ck; return rc; }
-    *out = a;
-    auto deliver = [&]() { if (chunks) { if (*chunks) aukit_chunks_free(*chunks); *chunks = ck; } else delete ck; };
-    if (nt == 0) { deliver(); return AUKIT_OK; }
+    if ((rc = ctx_begin_kernel(ctx)) || (rc = h2d_table(ctx, d_tab, pl.ima_rows.data(), pl.ima_rows.size() * sizeof(SMixImaStream)))) return rc;
+    hipLaunchKernelGGL(k_smix_ima_rows, dim3((unsigned)((pl.ima_jobs + 63) / 64)), dim3(64), 0, ctx->stream, in->data(), d_tab, (unsigned)pl.ima_rows.size(),
+                       (unsigned long long)pl.ima_jobs, rows16);
+    if (hipGetLastError() != hipSuccess) return fail(AUKIT_E_HIP, "IMA pre-pass launch failed");
+    return ctx_end_kernel(ctx, "k_smix_ima_rows", pl.ima_src + pl.ima_elems * 2);
+}
 
-    if (df_n) {  // pre-pass, timed under its own name in front of the resample launch
-        char *const T = reinterpret_cast<char *>(ctx->tmp_buf.p) + df_tab_at;
-        signed char *const rows = reinterpret_cast<signed char *>(ctx->tmp_buf.p);
-        if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
-        const bool sb_on = ctx->sb_dfpwm_on;  // a stream handle's carried decoder state is not this call's: every stream starts from reset, at byte 0
-        ctx->sb_dfpwm_on = false;
-        std::vector<SMixDfItem> lanes;  // the groups the engine declines (dfpwm_par.hip: nchunk < 2, every stream short)
-        bool engine = false;
-        size_t at = 0;
-        for (auto &kv : df_groups) {
-            const DfGroup &G = kv.second;
-            const uint64_t adv = 6000ull * (uint64_t)kv.first;
-            const uint32_t m = (uint32_t)G.off.size();
-            unsigned long long *d_row = reinterpret_cast<unsigned long long *>(T + at);
-            at += (size_t)m * 8;
-            int prc = AUKIT_OK;
-            if ((rc = h2d_table(ctx, d_row, G.row.data(), (size_t)m * 8))) break;
-            if (dfpwm_decode_parallel_feed(ctx, in->data(), G.off, G.fed, adv + 1, adv, 0 /* rows */, 1 /* one "channel": flat */, rows, d_row, nullptr, 1 /* behind the leading 0 */,
-                                           &prc)) {
-                if ((rc = prc)) break;
-                hipLaunchKernelGGL(k_smix_row_heads, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, rows, d_row, m);
-                engine = true;
-            } else lanes.insert(lanes.end(), G.items.begin(), G.items.end());
+// ---- phase 7: tiles.  A segment is cut into tiles of the class's height.  An IMA segment: no tile straddles a block, and a block's outputs are cut
+// in equal parts of at most the tile height (12 240 outputs under a height of 2048: six tiles of 2040, no sliver).
+// -> the segment's tiles, appended to `tiles` where it is given
+static uint64_t smix_cut(const SMixClass &K, unsigned to, const SMixSeg &g, unsigned seg, std::vector<SMixTile> *tiles) {
+    if (K.codec != AUKIT_CODEC_ADPCM_WAV) {
+        if (tiles)
+            for (unsigned o0 = 0; o0 < g.n_out; o0 += to) tiles->push_back(SMixTile{seg, o0, std::min(to, g.n_out - o0)});
+        return ((uint64_t)g.n_out + to - 1) / to;
+    }
+    const unsigned nlf = K.nl_full, last = g.n_out - (g.nblk - 1) * nlf;  // the full blocks' outputs, and the last block's
+    if (tiles)
+        for (unsigned kb = 0; kb < g.nblk; kb++) {
+            const unsigned nout = kb + 1 < g.nblk ? nlf : last;
+            const unsigned parts = (nout + to - 1) / to, each = parts ? nout / parts : 0, extra = parts ? nout % parts : 0;
+            for (unsigned p = 0, o0 = kb * nlf; p < parts; p++) {
+                const unsigned cnt = each + (p < extra ? 1u : 0u);
+                tiles->push_back(SMixTile{seg, o0, cnt});
+                o0 += cnt;
+            }
         }
-        ctx->sb_dfpwm_on = sb_on;
-        if (rc) { delete ck; return rc; }
-        if (!lanes.empty()) {
-            SMixDfItem *d_items = reinterpret_cast<SMixDfItem *>(T + (size_t)df_n * 8);
-            if ((rc = h2d_table(ctx, d_items, lanes.data(), lanes.size() * sizeof(SMixDfItem)))) { delete ck; return rc; }
-            hipLaunchKernelGGL(k_smix_dfpwm_rows, dim3(((unsigned)lanes.size() + 63) / 64), dim3(64), 0, ctx->stream, in->data(), d_items, (unsigned)lanes.size(), rows);
-        }
-        if (hipGetLastError() != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "DFPWM pre-pass launch failed"); }
-        if ((rc = ctx_end_kernel(ctx, engine ? "k_df_chunks(parallel dfpwm decode)" : "k_smix_dfpwm_rows", df_src + df_tot))) { delete ck; return rc; }
-    }
-
-    if (ima_jobs) {  // the IMA pre-pass, under its own name
-        short *const rows16 = reinterpret_cast<short *>(reinterpret_cast<char *>(ctx->tmp_buf.p) + ima_at);
-        SMixImaStream *const d_tab = reinterpret_cast<SMixImaStream *>(reinterpret_cast<char *>(ctx->tmp_buf.p) + ima_tab_at);
-        if ((rc = ctx_begin_kernel(ctx)) || (rc = h2d_table(ctx, d_tab, ima_rows.data(), ima_rows.size() * sizeof(SMixImaStream)))) { delete ck; return rc; }
-        hipLaunchKernelGGL(k_smix_ima_rows, dim3((unsigned)((ima_jobs + 63) / 64)), dim3(64), 0, ctx->stream, in->data(), d_tab, (unsigned)ima_rows.size(),
-                           (unsigned long long)ima_jobs, rows16);
-        if (hipGetLastError() != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "IMA pre-pass launch failed"); }
-        if ((rc = ctx_end_kernel(ctx, "k_smix_ima_rows", ima_src + ima_elems * 2))) { delete ck; return rc; }
-    }
-
+    return (uint64_t)(g.nblk - 1) * (((uint64_t)nlf + to - 1) / to) + ((uint64_t)last + to - 1) / to;
+}
+static uint64_t smix_count_tiles(const SMixClasses &T, const SMixPlan &pl) {
+    uint64_t nt = 0;
+    for (const SMixSeg &g : pl.segs) nt += smix_cut(T.classes[g.cls], (unsigned)T.tile_out[g.cls], g, 0, nullptr);
+    return nt;
+}
+// the segments get their place in the audio's rows on the way
+static std::vector<SMixTile> smix_tiles(const SMixClasses &T, SMixPlan &pl, const aukit_audio *a, uint64_t nt) {
     std::vector<SMixTile> tiles;
     tiles.reserve((size_t)nt);
-    {
-        size_t i = 0;
-        for (uint32_t s = 0; s < n; s++)
-            for (uint32_t k = 0; k < ck->nchunks[s]; k++, i++) {
-                SMixSeg &g = segs[i];
-                g.out_off += a->row_off[s];
-                g.out_stride = (unsigned)a->row_stride[s];
-                const unsigned to = (unsigned)tile_out[g.cls];
-                if (classes[g.cls].codec == AUKIT_CODEC_ADPCM_WAV) {
-                    // a block's outputs in equal parts of at most the tile height (12 240 outputs under a height of 2048: six tiles of 2040, no sliver)
-                    const unsigned nlf = classes[g.cls].nl_full;
-                    for (unsigned kb = 0; kb < g.nblk; kb++) {
-                        const unsigned nout = kb + 1 < g.nblk ? nlf : g.n_out - (g.nblk - 1) * nlf;
-                        const unsigned parts = (nout + to - 1) / to, each = parts ? nout / parts : 0, extra = parts ? nout % parts : 0;
-                        for (unsigned p = 0, o0 = kb * nlf; p < parts; p++) {
-                            const unsigned cnt = each + (p < extra ? 1u : 0u);
-                            tiles.push_back(SMixTile{(unsigned)i, o0, cnt});
-                            o0 += cnt;
-                        }
-                    }
-                    continue;
-                }
-                for (unsigned o0 = 0; o0 < g.n_out; o0 += to) tiles.push_back(SMixTile{(unsigned)i, o0, std::min(to, g.n_out - o0)});
-            }
-    }
-    if ((rc = upload_table(ctx, ctx->misc_buf, classes.data(), classes.size() * sizeof(SMixClass))) ||
-        (rc = upload_table(ctx, ctx->seg_buf, segs.data(), segs.size() * sizeof(SMixSeg))) ||
-        (rc = upload_table(ctx, ctx->tile_buf, tiles.data(), tiles.size() * sizeof(SMixTile)))) { delete ck; return rc; }
+    size_t i = 0;
+    for (uint32_t s = 0; s < pl.ck->n; s++)
+        for (uint32_t k = 0; k < pl.ck->nchunks[s]; k++, i++) {
+            SMixSeg &g = pl.segs[i];
+            g.out_off += a->row_off[s];
+            g.out_stride = (unsigned)a->row_stride[s];
+            smix_cut(T.classes[g.cls], (unsigned)T.tile_out[g.cls], g, (unsigned)i, &tiles);
+        }
+    return tiles;
+}
 
+// ---- phase 8: the launch.  The DFPWM and the IMA class live in instantiations of their own: a batch without one launches the kernels it always did
+static int smix_launch(aukit_ctx *ctx, const aukit_batch *in, const SMixClasses &T, const SMixPlan &pl, const std::vector<SMixTile> &tiles, const SMixScratch &L,
+                       const aukit_audio *a, int interp, int dtype) {
     SMixParams P;
     memset(&P, 0, sizeof P);
-    P.tiles = reinterpret_cast<const SMixTile *>(ctx->tile_buf.p);
-    P.segs = reinterpret_cast<const SMixSeg *>(ctx->seg_buf.p);
-    P.classes = reinterpret_cast<const SMixClass *>(ctx->misc_buf.p);
-    P.n_tiles = (unsigned)tiles.size();
-    P.src = in->data();
-    P.safe_lo = in->base;
-    P.safe_hi = in->base + in->cap;
-    P.out = a->dev;
-    P.rows = reinterpret_cast<const signed char *>(ctx->tmp_buf.p);
-    P.rows16 = reinterpret_cast<const short *>(reinterpret_cast<const char *>(ctx->tmp_buf.p) + ima_at);
-    unsigned per_cu = (unsigned)std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1));
-    if (per_cu < 1) per_cu = 1;
-    per_cu *= 16;  // a finer hand-out than the resident count, as launch_resample: the tiles of a mixed batch differ in cost
-    const unsigned grid = std::min<unsigned>(P.n_tiles, (unsigned)ctx->num_cus * per_cu);
-    if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
-    // (the DFPWM and the IMA class live in instantiations of their own: a batch without one launches the kernels it always did)
-    if (has_ima && has_df) rc = dtype == AUKIT_F64 ? launch_smix<double, true, true>(ctx, interp, P, lds, grid) : launch_smix<float, true, true>(ctx, interp, P, lds, grid);
-    else if (has_ima) rc = dtype == AUKIT_F64 ? launch_smix<double, false, true>(ctx, interp, P, lds, grid) : launch_smix<float, false, true>(ctx, interp, P, lds, grid);
-    else if (has_df) rc = dtype == AUKIT_F64 ? launch_smix<double, true, false>(ctx, interp, P, lds, grid) : launch_smix<float, true, false>(ctx, interp, P, lds, grid);
-    else rc = dtype == AUKIT_F64 ? launch_smix<double, false, false>(ctx, interp, P, lds, grid) : launch_smix<float, false, false>(ctx, interp, P, lds, grid);
-    if (rc) { delete ck; return rc; }
+    P.rows16 = reinterpret_cast<const short *>(reinterpret_cast<const char *>(ctx->tmp_buf.p) + L.ima_at);
     static const char *names[] = {"k_stream_mixed<none>", "k_stream_mixed<linear>", "k_stream_mixed<cubic>"};
-    if ((rc = ctx_end_kernel(ctx, names[interp], in_bytes + out_elems * dtype_size(dtype)))) { delete ck; return rc; }
-    deliver();
+    uint64_t out_elems = 0;
+    for (uint64_t len : pl.lens) out_elems += len * pl.ck->channels;
+    const size_t lds = T.lds;
+    return mixed_launch(ctx, in, a, T.classes, pl.segs, tiles, P, lds, names[interp], pl.in_bytes + out_elems * dtype_size(dtype), [&](unsigned grid) {
+        if (T.has_ima && T.has_df) AUKIT_MIXED_LAUNCH(ctx, k_stream_mixed, interp, dtype, grid, lds, P, true, true);
+        else if (T.has_ima) AUKIT_MIXED_LAUNCH(ctx, k_stream_mixed, interp, dtype, grid, lds, P, false, true);
+        else if (T.has_df) AUKIT_MIXED_LAUNCH(ctx, k_stream_mixed, interp, dtype, grid, lds, P, true, false);
+        else AUKIT_MIXED_LAUNCH(ctx, k_stream_mixed, interp, dtype, grid, lds, P, false, false);
+    });
+}
+
+}  // namespace aukit
+
+using namespace aukit;
+
+extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype,
+                                         aukit_audio **out, aukit_chunks **chunks) {
+    // what can be refused is refused before the device is touched; `*out` and `*chunks` keep what they held
+    int rc;
+    if ((rc = smix_validate(ctx, in, descs, n_descs, interp, mono, dtype, out))) return rc;
+    const uint32_t n = in->n;
+    SMixClasses T;
+    if ((rc = smix_classes(descs, n, interp, mono, T))) return rc;
+    AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
+    smix_exact_division(ctx, T.classes);
+    std::vector<unsigned> ima_bad;
+    if (T.has_ima && (rc = smix_ima_scan(ctx, in, descs, ima_bad))) return rc;
+
+    const int C_out = mono ? 1 : (n ? descs[0].channels : 1);
+    SMixPlan pl(n);
+    smix_plan(in, descs, T.cls_of, interp, mono != 0, ima_bad, pl);
+    smix_chunk_table(pl, C_out);
+    const uint64_t nt = smix_count_tiles(T, pl);
+    if (nt > 0xFFFFFFF0ull || pl.ima_jobs > 0x7FFFFFF0ull * 64) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
+
+    // the scratch is sized before `*out` is touched, and its pointer is read after
+    const SMixScratch L = smix_scratch(pl);
+    if ((pl.df_n || pl.ima_jobs) && (rc = mixed_scratch_ensure(ctx, *out, L.size))) return rc;
+    aukit_audio *a = *out;
+    if ((rc = audio_prepare(ctx, &a, n, C_out, 48000, dtype, pl.lens.data()))) return rc;
+    *out = a;
+    if (nt) {
+        if (pl.df_n && (rc = smix_dfpwm_prepass(ctx, in, pl, L))) return rc;
+        if (pl.ima_jobs && (rc = smix_ima_prepass(ctx, in, pl, L))) return rc;
+        const std::vector<SMixTile> tiles = smix_tiles(T, pl, a, nt);
+        if ((rc = smix_launch(ctx, in, T, pl, tiles, L, a, interp, dtype))) return rc;
+    }
+    if (chunks) {  // delivery: the caller's table is replaced
+        if (*chunks) aukit_chunks_free(*chunks);
+        *chunks = pl.ck.release();
+    }
     return AUKIT_OK;
 }

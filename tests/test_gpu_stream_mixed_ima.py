@@ -158,6 +158,25 @@ def test_ima_only_batches_with_reused_handles(ctx, oracle):
     assert all(np.array_equal(a[0], b[0]) for a, b in zip(rows1, again))
 
 
+def test_reuses_a_handle_that_owes_a_resample(ctx, oracle):
+    """`out` comes from an AUKIT_F32 single-descriptor QOA call, whose resample may be left owed on rows taken out of the context's scratch: the
+    scratch of both pre-passes, sized before `out` is prepared, must survive that hand-back (tests/test_gpu_mixed_i16.py has the decode call's twin).
+    Mixed down, AUKIT_F64: the DFPWM and the IMA pre-pass and all four kinds of segment run"""
+    from tests import mixed_i16_util as Q
+    from tests import stream_mixed_dfpwm_util as S
+    B, N = _B(), _N()
+    interp = "linear"
+    big = [s for s in Q.library_q(oracle) if s["kind"] == "qoa" and s["frames"] == 10241][0]
+    owed = B.decode_resample(ctx, B.Batch.upload(ctx, [big["bytes"]] * 8), Q.desc_of(big), 48000, "cubic", dtype=N.F32)
+    rng = np.random.Generator(np.random.PCG64(0x1A0E))
+    lib = [I.ima_stream(oracle, rng, 1, 36, 22050, "2", "8 * C + 1", True), I.ima_stream(oracle, rng, 2, 72, 48000, "1", "4 * C", False),
+           S.df_stream(oracle, rng, 513, 2, 24000, tone=True), S.df_stream(oracle, rng, 6001, 1, 44100, tone=True),
+           U._pcm(rng, 1, "65", interp), U._g711(rng, 0, 3001, 1)]
+    out, ck = B.stream_decode_mixed(ctx, B.Batch.upload(ctx, [s["bytes"] for s in lib]), I.descs_of(lib), interp, mono=True, dtype=N.F64, out=owed)
+    assert out is owed and out.info()["dtype"] == N.F64 and out.info()["n"] == len(lib) and ctx.last_kernel()[0] == f"k_stream_mixed<{interp}>"
+    I.compare(lib, out.download(), ck, [I.oracle_stream(oracle, s, interp, True) for s in lib], interp)
+
+
 def test_refusals(oracle):
     """ima_stream's argument checks with the stream's index, and the codecs that keep their own streams; `*out`, its samples and `*chunks` keep
     what the call before left"""
