@@ -533,6 +533,41 @@ def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False):
     return descs, ranges, infos
 
 
+def _sniff_set(readers):
+    """aukit.stream.set's host half, up to the device: every reader is called once; its first piece, which holds the whole header (:2918), is
+    sniffed by magic and walked by aukit_parse_container in its first-piece mode
+    -> ([descriptor per reader], [the payload bytes behind the header per reader], [the container's length in seconds, NaN where the stream
+    factory's own figure stands]).  A reader whose stream is no WAV / AIFF / AU, or whose payload is none of PCM, G.711 and IMA-ADPCM blocks,
+    raises LuaError naming the reader's index (0-based)."""
+    _expect(1, readers, "table")
+    takes = "stream.set takes PCM and G.711 payloads and IMA-ADPCM blocks (the other codecs keep their own streams)"
+    descs, firsts, lengths = [], [], []
+    for i, fn in enumerate(readers):
+        if not callable(fn):
+            raise LuaError(f"bad argument #1 (reader {i}: expected function)")
+        first = fn()
+        if not isinstance(first, (bytes, bytearray, memoryview)):
+            raise LuaError(f"bad argument #1 (reader {i}: expected string from the first call)")
+        first = bytes(first)
+        kind = detect(first[:12])[0]
+        if kind == "qoa":
+            raise LuaError(f"reader {i}: qoa payload: {takes}")
+        if kind not in _MAGIC_KIND:
+            raise LuaError(f"reader {i}: not a WAV, AIFF or AU stream")
+        try:
+            c, p = _parse_first_piece(first, _MAGIC_KIND[kind])
+        except LuaError as e:
+            raise LuaError(f"reader {i}: {e}") from None
+        d = _desc_copy(c)
+        if d.codec not in (N.CODEC_PCM, N.CODEC_G711, N.CODEC_ADPCM_WAV):
+            what = N.WAVDT[c.wav_data_type] if kind == "wav" else f"codec {d.codec}"
+            raise LuaError(f"reader {i}: {what} payload: {takes}")
+        descs.append(d)
+        firsts.append(p)
+        lengths.append(float(c.length_seconds))
+    return descs, firsts, lengths
+
+
 class _RowView(B.AudioBatch):
     """One stream of an AudioBatch seen as an AudioBatch of its own (what an Audio wraps): geometry and samples come from the parent's rows; a
     handle of its own exists only once a method hands the audio on to the library (then the row is uploaded as a one-stream audio, once)."""
@@ -830,6 +865,47 @@ class _StreamNS:
         out, ck = _wrap(B.stream_decode_mixed, ctx, bt, descs, _interp(defaultInterpolation, 0), bool(mono), N.F64)
         rows = out.download()
         return [self._chunk_iter(out, ck, None if math.isnan(lengths[i]) else lengths[i], d.codec == N.CODEC_G711, i, rows) for i, d in enumerate(descs)]
+
+    def set(self, readers, mono=None):
+        """aukit.stream.wav / aiff / au (fn, mono) for a LIST of reader functions — live sources, each a WAV / AIFF / AU stream of PCM, G.711 or
+        IMA-ADPCM blocks with its own rate, format and channel count — served by ONE aukit_streamset: a list of (iterator, length) pairs in
+        input order, each iterator handing out what the reader's own factory hands out.  Every reader's first piece holds the whole header
+        (the reference's rule for function input, :2918).  A round starts when any iterator has nothing decided: the set pulls one piece from
+        every unfinished reader and pumps once — the device work of all listeners is one upload, three launches and one download per round.
+        Without `mono` the streams must agree in channel count.  A payload the set does not take is refused by the reader's index."""
+        _expect(2, mono, "boolean", "nil")
+        descs, firsts, lengths = _sniff_set(readers)
+        ctx = context()
+        st = _wrap(B.StreamSet, ctx, descs, _interp(defaultInterpolation, 0), bool(mono), N.F64)
+        n = len(readers)
+        done = [False] * n
+
+        def a_round(pieces=None):
+            for s in range(n):
+                if done[s]:
+                    continue
+                piece = readers[s]() if pieces is None else pieces[s]
+                if piece is None:
+                    done[s] = True
+                    _wrap(st.finish, s)
+                else:
+                    _wrap(st.feed, s, _expect(1, piece, "string"))
+            _wrap(st.pump)
+
+        a_round(firsts)
+
+        def it(s):
+            while True:
+                kind, chans, pos = _wrap(st.next, s)
+                if kind == "chunk":
+                    yield chans, pos
+                elif kind == "end":
+                    return
+                elif all(done):
+                    raise LuaError("stream.set: every reader has ended and nothing is decided")   # (cannot happen: a finished member ends)
+                else:
+                    a_round()
+        return [(it(s), (_wrap(st.length, s) if math.isnan(lengths[s]) else lengths[s])) for s in range(n)]
 
     def wav(self, data, mono=None, ignoreHeader=None):  # :2927: header walk (library) + dispatch (:2992-2996)
         _expect_src(1, data)

@@ -685,4 +685,77 @@ class StreamHandle:
             pass
 
 
+class StreamSet:
+    """Many live streams fed and pumped as one batch (aukit_streamset_*): member s is StreamHandle(ctx, descs[s], interp, mono, dtype) fed the
+    same bytes — the same chunks, positions, length and end — but `feed` only copies on the host, `pump` does the device work of a tick for all
+    members at once (one upload, a repack launch, one mixed stream decode, a gather launch, one download, one wait) and `next` reads the host
+    cache the last pump filled.  CODEC_PCM at or below 48 kHz, CODEC_G711, CODEC_ADPCM_WAV; none / linear / cubic; F64 or F32
+    (include/aukit_hip.h)."""
+
+    def __init__(self, ctx, descs, interp, mono=False, dtype=None, cap=48000):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        self._cap = int(cap)
+        self.n = len(descs)
+        arr = (N.CodecDesc * max(len(descs), 1))()
+        for i, d in enumerate(descs):
+            C.memmove(C.byref(arr[i]), C.byref(d), C.sizeof(N.CodecDesc))
+        N.check(N.lib().aukit_streamset_open(ctx._h, arr, C.c_uint32(len(descs)), _interp(interp), int(bool(mono)), ctx.dtype if dtype is None else dtype,
+                                             C.byref(self._h)))
+        self._buf_ch = 2
+        self._buf = np.empty(self._cap * self._buf_ch, dtype=np.float64)
+
+    def feed(self, s, data):
+        b = bytes(data)
+        N.check(N.lib().aukit_streamset_feed(self._h, C.c_uint32(s), b, C.c_uint64(len(b))))
+
+    def finish(self, s):
+        N.check(N.lib().aukit_streamset_finish(self._h, C.c_uint32(s)))
+
+    def pump(self):
+        """all device work of a tick → the number of members with a chunk waiting"""
+        r = C.c_uint32()
+        N.check(N.lib().aukit_streamset_pump(self._h, C.byref(r)))
+        return r.value
+
+    def next(self, s):
+        """member s → ("chunk", [per-channel float64 arrays], pos) | ("need_input", None, None) | ("end", None, None), as StreamHandle.next"""
+        ln, ch, st, pos = C.c_uint32(), C.c_int32(), C.c_int32(), C.c_double()
+        while True:
+            buf = self._buf
+            rc = N.lib().aukit_streamset_next(self._h, C.c_uint32(s), buf.ctypes.data_as(C.POINTER(C.c_double)), C.c_uint64(buf.size), C.c_uint32(self._cap), C.byref(ln),
+                                              C.byref(ch), C.byref(pos), C.byref(st))
+            if rc == N.E_ARG and ch.value > self._buf_ch and ln.value <= self._cap:  # more channels than the buffer was sized for: the chunk is still there
+                self._buf_ch = ch.value
+                self._buf = np.empty(self._cap * self._buf_ch, dtype=np.float64)
+                continue
+            N.check(rc)
+            break
+        if st.value == N.STREAM_CHUNK:
+            return "chunk", [buf[c * self._cap: c * self._cap + ln.value].copy() for c in range(ch.value)], pos.value
+        return ("need_input" if st.value == N.STREAM_NEED_INPUT else "end"), None, None
+
+    def length(self, s):
+        v = C.c_double()
+        N.check(N.lib().aukit_streamset_length(self._h, C.c_uint32(s), C.byref(v)))
+        return v.value
+
+    def resident(self, s):
+        """member s → (bytes in the device arena, bytes dropped in front of them, input bytes of all its decodes so far)"""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        N.check(N.lib().aukit_streamset_resident(self._h, C.c_uint32(s), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def close(self):
+        if self._h:
+            N.lib().aukit_streamset_close(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 AUKIT_MAX_CH = N.MAX_CH

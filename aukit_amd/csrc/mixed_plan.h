@@ -43,6 +43,15 @@ static inline int fail_for_stream(int rc, unsigned s) {
     return fail(rc, "%s (stream %u)", m.c_str(), s);
 }
 
+// aukit_stream_decode_mixed for a stream set (stream_mixed.hip, streamset.hip): stream s is the REST of a longer stream.  bytes_dropped / outputs_dropped
+// are what was dropped in front of it (the chunk positions and the length are the whole stream's: what aukit_ctx::sb_bytes / sb_outputs are to the
+// single-descriptor calls); nbytes is how many of the bytes from the batch's offset on are the stream's (the batch's next offset is only an upper bound)
+struct SMixCarry { uint64_t bytes_dropped, outputs_dropped, nbytes; };
+int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
+                              aukit_chunks **chunks, const SMixCarry *carry /* n_descs, or null */);
+// what the stream's own aukit_stream_decode call refuses of a descriptor and a byte count, and the uneven last chunk (stream_mixed.hip)
+int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono);
+
 // taps below / above floor(x)
 static inline void mixed_halos(int interp, int *hl, int *hr) {
     *hl = interp == AUKIT_INTERP_CUBIC ? 1 : 0;

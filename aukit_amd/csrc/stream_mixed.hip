@@ -440,8 +440,8 @@ __global__ __launch_bounds__(64) void k_smix_ima_rows(const unsigned char *src, 
 
 // ------------------------------------------------------------------ host
 // everything the stream's own aukit_stream_decode call refuses (stream_pcm / stream_g711, api_resample.hip), with its words; and the one thing that
-// call serves and this one does not: the uneven last chunk
-static int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) {
+// call serves and this one does not: the uneven last chunk.  (Not static: a stream set asks member by member, streamset.hip)
+int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) {
     if (d->codec == AUKIT_CODEC_DFPWM) {  // stream_dfpwm's (codecs2.hip); rates above 48 kHz are served there, and here
         if (d->sample_rate < 1) return fail(AUKIT_E_ARG, "bad argument #2 (number outside of range)");
         if (d->channels < 1 || d->channels > AUKIT_MAX_PLANAR_CHANNELS) return fail(AUKIT_E_ARG, "bad argument #3 (number outside of range)");
@@ -484,7 +484,12 @@ static int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) 
 }
 
 // ---- phase 1: everything that can refuse from the arguments, the descriptors and the byte counts alone
-static int smix_validate(const aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out) {
+// the bytes of stream s: what the batch's offsets span, or — a stream set's member, whose slot is padded and whose unfinished prefix ends at a whole
+// frame — what its carry says
+static inline uint64_t smix_nbytes(const aukit_batch *in, const SMixCarry *carry, uint32_t s) { return carry ? carry[s].nbytes : in->off[s + 1] - in->off[s]; }
+
+static int smix_validate(const aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
+                         const SMixCarry *carry) {
     int rc;
     if ((rc = mixed_check_call(ctx, in, out, descs, n_descs, interp, dtype, "invalid interpolation", "stream each class with aukit_stream_decode"))) return rc;
     if ((rc = mixed_check_codecs(descs, in->n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV},
@@ -492,8 +497,10 @@ static int smix_validate(const aukit_ctx *ctx, const aukit_batch *in, const auki
                                  "AUKIT_CODEC_DFPWM and AUKIT_CODEC_ADPCM_WAV)")))
         return rc;
     if ((rc = mixed_check_channels(in->n, mono, [&](uint32_t s) { return descs[s].channels; }))) return rc;
-    for (uint32_t s = 0; s < in->n; s++)
-        if ((rc = check_smix_stream(&descs[s], in->off[s + 1] - in->off[s], mono != 0))) return fail_for_stream(rc, s);
+    for (uint32_t s = 0; s < in->n; s++) {
+        if (carry && carry[s].nbytes > in->off[s + 1] - in->off[s]) return fail(AUKIT_E_ARG, "stream %u: the carry names more bytes than the batch holds", s);
+        if ((rc = check_smix_stream(&descs[s], smix_nbytes(in, carry, s), mono != 0))) return fail_for_stream(rc, s);
+    }
     return AUKIT_OK;
 }
 
@@ -581,10 +588,10 @@ static void smix_exact_division(aukit_ctx *ctx, std::vector<SMixClass> &classes)
 // ---- phase 3: stream.adpcm — which streams die on a header step index above 88, and in which block: only the device knows, and the rows' lengths
 // depend on it.  The scan writes ctx->scan_buf (the verdicts, the stream table behind them) and nothing else; its answer is awaited here.
 // -> bad: per IMA stream, in batch order, the first such block (0xFFFFFFFF: none)
-static int smix_ima_scan(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, std::vector<unsigned> &bad) {
+static int smix_ima_scan(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, const SMixCarry *carry, std::vector<unsigned> &bad) {
     std::vector<SMixImaStream> tab;
     for (uint32_t s = 0; s < in->n; s++)
-        if (descs[s].codec == AUKIT_CODEC_ADPCM_WAV) tab.push_back(SMixImaStream{in->off[s], in->off[s + 1] - in->off[s], 0, 0, descs[s].channels, descs[s].block_align});
+        if (descs[s].codec == AUKIT_CODEC_ADPCM_WAV) tab.push_back(SMixImaStream{in->off[s], smix_nbytes(in, carry, s), 0, 0, descs[s].channels, descs[s].block_align});
     const size_t m = tab.size(), tab_at = (size_t)round_up(m * 4, 16);
     bad.assign(m, 0xFFFFFFFFu);
     int rc = ctx->scan_buf.ensure(tab_at + m * sizeof(SMixImaStream) + 16);
@@ -634,7 +641,9 @@ struct SMixPlan {
 };
 // (the planners take `g` with src_off — the stream's first byte in the batch — and cls filled in)
 
-static void plan_pcm(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc &d, uint64_t nb, int interp, bool mono) {
+// `cy`: what a stream set has dropped in front of these bytes (zeros in the public call) — it enters the positions and the length exactly where
+// the single-descriptor calls add ctx->sb_bytes / sb_outputs for a stream handle (api_resample.hip, codecs.hip)
+static void plan_pcm(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc &d, uint64_t nb, int interp, bool mono, const SMixCarry &cy) {
     const int C = d.channels, bd = d.bit_depth / 8;
     const bool is_float = d.data_type == AUKIT_FLOAT, mix = mono && C > 1;
     auto pit = pl.pcm_plans.find(d.sample_rate);
@@ -644,24 +653,24 @@ static void plan_pcm(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc
     }
     const ChunkPlan &cp = pit->second;
     const long long nframes = (long long)(nb / ((size_t)bd * C));  // with the mix-down a partial frame counts for nothing
-    pl.ck->length_seconds[s] = ((double)nb / bd) / C / d.sample_rate;  // :2245, :2423
+    pl.ck->length_seconds[s] = ((double)(nb + cy.bytes_dropped) / bd) / C / d.sample_rate;  // :2245, :2423
     for (long c = 0;; c++) {
         Seg q;
         g.n_out = stream_pcm_call(cp, c, nframes, is_float, mix, &q, &pl.ck->status[s]);
         if (g.n_out == 0) break;
         g.src_base = q.src_base; g.w_lo = q.w_lo; g.w_hi = q.w_hi;
-        pl.add_call(s, g, (double)pl.lens[s] / 48000);  // (n - #chunk[1]) / 48000  :2422
+        pl.add_call(s, g, (double)(cy.outputs_dropped + pl.lens[s]) / 48000);  // (n - #chunk[1]) / 48000  :2422
         if (g.n_out < 48000) break;  // ok = false → the next call returns nil
     }
 }
 
 // every call is independent (Q13): its own table, indices 1 .. m.  A byte count that is no multiple of the channel count: the last call raises
 // (stream_g711, api_resample.hip), the calls before it deliver their chunks
-static void plan_g711(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc &d, uint64_t nb) {
+static void plan_g711(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc &d, uint64_t nb, const SMixCarry &cy) {
     const int C = d.channels;
     const double ratio = 48000 / d.sample_rate;
     const uint64_t per_call = (uint64_t)d.sample_rate * (uint64_t)C;
-    pl.ck->length_seconds[s] = (double)nb / d.sample_rate / C;
+    pl.ck->length_seconds[s] = (double)(nb + cy.bytes_dropped) / d.sample_rate / C;
     uint32_t calls = (uint32_t)((nb + per_call - 1) / per_call);  // calls that see data; the reference then returns {{}} forever
     if (nb % (uint64_t)C != 0) { calls--; pl.ck->status[s] = AUKIT_E_LUA; }
     for (uint32_t k = 0; k < calls; k++) {
@@ -670,7 +679,7 @@ static void plan_g711(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_des
         g.src_base = (long long)(pos / C) - 1;
         g.w_lo = 1; g.w_hi = (int)m;
         g.n_out = (uint32_t)std::floor((double)m * ratio);  // :2897
-        pl.add_call(s, g, ((double)(pos + 1) - 1) / d.sample_rate / C);  // (lp - 1) / sampleRate / channels
+        pl.add_call(s, g, ((double)(pos + cy.bytes_dropped + 1) - 1) / d.sample_rate / C);  // (lp - 1) / sampleRate / channels
     }
 }
 
@@ -704,11 +713,11 @@ static void plan_dfpwm(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_de
 
 // ima_stream's plan (codecs.hip) from byte 0, call after call (ima_call, ima_geom.h); a header index above 88, in block `bad`, kills the call that
 // reaches it and everything behind it
-static void plan_ima(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc &d, uint64_t nb, unsigned bad) {
+static void plan_ima(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc &d, uint64_t nb, unsigned bad, const SMixCarry &cy) {
     const int C = d.channels;
     const ImaGeom G(C, d.block_align, d.sample_rate);
     const uint64_t nblk = G.blocks(nb), src_off = g.src_off;
-    pl.ck->length_seconds[s] = (double)nb / (double)G.ba * G.spb / d.sample_rate;  // :2834
+    pl.ck->length_seconds[s] = (double)(nb + cy.bytes_dropped) / (double)G.ba * G.spb / d.sample_rate;  // :2834
     uint64_t calls_ok = ~0ull, done = 0;
     if (bad != 0xFFFFFFFFu) { calls_ok = (uint64_t)bad / std::max<uint64_t>(G.ips, 1); pl.ck->status[s] = AUKIT_E_LUA; }  // "attempt to perform arithmetic on a nil value (field '?')"
     g.src_off = pl.ima_elems;
@@ -718,7 +727,7 @@ static void plan_ima(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc
         if (c.produced == 0) break;  // #retval[1] == 0 -> nil  :2832
         g.src_base = (long long)done; g.w_hi = (int)c.m_last; g.nblk = (unsigned)c.take; g.n_out = (uint32_t)c.produced;
         done += c.take;
-        pl.add_call(s, g, (double)(done * G.ba + 1) / G.bytes_per_second);  // (n + pos) / bytesPerSecond  :2833
+        pl.add_call(s, g, (double)(done * G.ba + cy.bytes_dropped + 1) / G.bytes_per_second);  // (n + pos) / bytesPerSecond  :2833
         if (done >= nblk) break;  // the next call sees n + 4C > #data and returns nil
     }
     if (!done) return;  // `done` blocks are planned: the pre-pass decodes those
@@ -728,21 +737,22 @@ static void plan_ima(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc
     pl.ima_src += std::min<uint64_t>(nb, done * G.ba + G.hdr);
 }
 
-static void smix_plan(const aukit_batch *in, const aukit_codec_desc *descs, const std::vector<unsigned> &cls_of, int interp, bool mono, const std::vector<unsigned> &ima_bad,
-                      SMixPlan &pl) {
+static void smix_plan(const aukit_batch *in, const aukit_codec_desc *descs, const SMixCarry *carry, const std::vector<unsigned> &cls_of, int interp, bool mono,
+                      const std::vector<unsigned> &ima_bad, SMixPlan &pl) {
     size_t ima_i = 0;
     for (uint32_t s = 0; s < in->n; s++) {
         const aukit_codec_desc &d = descs[s];
-        const uint64_t nb = in->off[s + 1] - in->off[s];
+        const uint64_t nb = smix_nbytes(in, carry, s);
+        const SMixCarry cy = carry ? carry[s] : SMixCarry{0, 0, nb};
         pl.in_bytes += nb;
         SMixSeg g;
         memset(&g, 0, sizeof g);
         g.src_off = in->off[s];
         g.cls = cls_of[s];
         if (d.codec == AUKIT_CODEC_DFPWM) plan_dfpwm(pl, s, g, d, nb);
-        else if (d.codec == AUKIT_CODEC_ADPCM_WAV) plan_ima(pl, s, g, d, nb, ima_bad[ima_i++]);
-        else if (d.codec == AUKIT_CODEC_PCM) plan_pcm(pl, s, g, d, nb, interp, mono);
-        else plan_g711(pl, s, g, d, nb);
+        else if (d.codec == AUKIT_CODEC_ADPCM_WAV) plan_ima(pl, s, g, d, nb, ima_bad[ima_i++], cy);
+        else if (d.codec == AUKIT_CODEC_PCM) plan_pcm(pl, s, g, d, nb, interp, mono, cy);
+        else plan_g711(pl, s, g, d, nb, cy);
     }
 }
 
@@ -871,26 +881,24 @@ static int smix_launch(aukit_ctx *ctx, const aukit_batch *in, const SMixClasses 
     });
 }
 
-}  // namespace aukit
-
-using namespace aukit;
-
-extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype,
-                                         aukit_audio **out, aukit_chunks **chunks) {
+// the call itself.  `carry` (null: the public call, every stream counted from byte 0): per stream, what a stream set has dropped in front of the
+// bytes and how many of the slot's bytes are the stream's (mixed_plan.h).  A DFPWM stream's decoder state is not carried: a set has none
+int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
+                              aukit_chunks **chunks, const SMixCarry *carry) {
     // what can be refused is refused before the device is touched; `*out` and `*chunks` keep what they held
     int rc;
-    if ((rc = smix_validate(ctx, in, descs, n_descs, interp, mono, dtype, out))) return rc;
+    if ((rc = smix_validate(ctx, in, descs, n_descs, interp, mono, dtype, out, carry))) return rc;
     const uint32_t n = in->n;
     SMixClasses T;
     if ((rc = smix_classes(descs, n, interp, mono, T))) return rc;
     AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
     smix_exact_division(ctx, T.classes);
     std::vector<unsigned> ima_bad;
-    if (T.has_ima && (rc = smix_ima_scan(ctx, in, descs, ima_bad))) return rc;
+    if (T.has_ima && (rc = smix_ima_scan(ctx, in, descs, carry, ima_bad))) return rc;
 
     const int C_out = mono ? 1 : (n ? descs[0].channels : 1);
     SMixPlan pl(n);
-    smix_plan(in, descs, T.cls_of, interp, mono != 0, ima_bad, pl);
+    smix_plan(in, descs, carry, T.cls_of, interp, mono != 0, ima_bad, pl);
     smix_chunk_table(pl, C_out);
     const uint64_t nt = smix_count_tiles(T, pl);
     if (nt > 0xFFFFFFF0ull || pl.ima_jobs > 0x7FFFFFF0ull * 64) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
@@ -912,4 +920,13 @@ extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, 
         *chunks = pl.ck.release();
     }
     return AUKIT_OK;
+}
+
+}  // namespace aukit
+
+using namespace aukit;
+
+extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype,
+                                         aukit_audio **out, aukit_chunks **chunks) {
+    return stream_decode_mixed_carry(ctx, in, descs, n_descs, interp, mono, dtype, out, chunks, nullptr);
 }

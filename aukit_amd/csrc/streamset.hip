@@ -1,0 +1,520 @@
+// streamset.hip — aukit_streamset: many live reader-function streams (stream_handle.hip: one stream per handle) fed and pumped as ONE batch.
+//
+// A handle pays per stream and tick: a synchronous upload per feed, a launch chain per `next`, a download per channel and chunk, an allocation per
+// compaction.  A set pays per tick, whatever its member count:
+//   feed    the bytes go to a pinned host staging buffer (no device call, no wait); a piece starts at the residue modulo 16 it will have in the
+//           arena, so that the repack below moves it with 16-byte loads and stores;
+//   pump    (1) host: which members have news (bytes, or a finish, since their last decode); the new arena's layout — every live member's rest
+//               followed by its new bytes, slots at multiples of 16, 64 bytes to spare behind the last (k_stream_mixed's vector staging reads up to
+//               safe_hi);
+//           (2) one upload of the staging buffer, one launch of k_sset_repack: a segment table {old arena | staging, src_off, dst_off, n} builds
+//               the OTHER of two device arenas (no copy overlaps itself); a workgroup takes a 16 KiB piece of a segment;
+//           (3) aukit_stream_decode_mixed's engine (stream_decode_mixed_carry, stream_mixed.hip) over the members that have news, straight from the
+//               arena, each with what it has dropped so far (SMixCarry): positions and lengths are the whole stream's;
+//           (4) one launch of k_sset_gather: the newly decided chunks of all members, as doubles, [item][channel][len]; one download into the
+//               pinned host cache; one wait — the pump's only one (a set with stream.adpcm members adds the mixed call's header-scan read-back);
+//           (5) host: the compaction plan for the next repack (restart_rule's PCM / G.711 / IMA cases, stream_handle.hip: stream.pcm keeps the call
+//               in front of the next one and skips its chunk, stream.g711 / stream.adpcm calls stand alone).  No 64 KiB threshold: the repack runs
+//               anyway, so a member is compacted whenever a call of its became droppable;
+//   next    reads the host cache.
+// The contract is the handle's: member s hands out aukit_stream_decode's chunk list for its concatenated bytes.  A chunk is decided once a later
+// chunk of the same decode exists, or the member is finished.  One bad member ends alone: whatever would refuse the whole mixed call is asked of
+// every member on the host first (check_smix_stream), and such a member never enters a batch.
+#include <algorithm>
+#include <deque>
+#include "mixed_plan.h"
+
+namespace aukit {
+
+enum { SSET_PIECE = 16384 };            // bytes of a segment one workgroup of k_sset_repack moves
+enum { SSET_GATHER_PIECE = 4096 };      // elements of a chunk's channel one workgroup of k_sset_gather moves
+
+struct SSetSeg { unsigned long long src_off, dst_off; unsigned n, from_staging; };
+static_assert(sizeof(SSetSeg) == 24, "SSetSeg layout");
+struct SSetPiece { unsigned seg, off; };
+
+typedef unsigned sset_u32u __attribute__((aligned(1)));
+
+// A piece of a segment: bytes [off, off + min(SSET_PIECE, n - off)) of it, from the old arena or the staging buffer to the new arena.  The head up to
+// the destination's next multiple of 16 and the tail behind its last go byte by byte; the middle goes in 16-byte stores — from 16-byte loads where
+// source and destination agree modulo 16, from four dword loads of any alignment where they do not.  Every load lies inside the segment's source
+// bytes and every store inside its destination bytes: the host sized both.  Plain vector loads and stores only
+__global__ __launch_bounds__(256) void k_sset_repack(const unsigned char *__restrict__ old_arena, const unsigned char *__restrict__ staging, unsigned char *__restrict__ arena,
+                                                     const SSetSeg *__restrict__ segs, const SSetPiece *__restrict__ pieces, unsigned n_pieces) {
+    const unsigned b = blockIdx.x;
+    if (b >= n_pieces) return;
+    const SSetPiece pc = pieces[b];
+    const SSetSeg sg = segs[pc.seg];
+    if (pc.off >= sg.n) return;
+    const unsigned n = min((unsigned)SSET_PIECE, sg.n - pc.off);
+    const unsigned char *src = (sg.from_staging ? staging : old_arena) + sg.src_off + pc.off;
+    unsigned char *dst = arena + sg.dst_off + pc.off;
+    const unsigned head = min(n, (unsigned)((16u - (unsigned)((uintptr_t)dst & 15u)) & 15u));
+    const unsigned nvec = (n - head) >> 4;
+    const unsigned tail0 = head + (nvec << 4);
+    const unsigned tid = threadIdx.x;
+    if (tid < head) dst[tid] = src[tid];
+    if (tid < n - tail0) dst[tail0 + tid] = src[tail0 + tid];
+    if ((((uintptr_t)src ^ (uintptr_t)dst) & 15u) == 0) {
+        const uint4 *s4 = reinterpret_cast<const uint4 *>(src + head);
+        uint4 *d4 = reinterpret_cast<uint4 *>(dst + head);
+        for (unsigned v = tid; v < nvec; v += 256) d4[v] = s4[v];
+    } else {
+        uint4 *d4 = reinterpret_cast<uint4 *>(dst + head);
+        for (unsigned v = tid; v < nvec; v += 256) {
+            const sset_u32u *s1 = reinterpret_cast<const sset_u32u *>(src + head + 16 * (size_t)v);
+            d4[v] = make_uint4(s1[0], s1[1], s1[2], s1[3]);
+        }
+    }
+}
+
+// one newly decided chunk: `len` samples of each of `channels` rows of the decode's audio, `src_stride` elements apart from element `src` on, become
+// doubles [channel][len] from element `dst` of the gather buffer on
+struct SSetItem { unsigned long long src, dst; unsigned src_stride, len; };
+static_assert(sizeof(SSetItem) == 24, "SSetItem layout");
+struct SSetGPiece { unsigned item, chan, off, pad; };
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_sset_gather(const T *__restrict__ audio, double *__restrict__ out, const SSetItem *__restrict__ items, const SSetGPiece *__restrict__ pieces,
+                                                     unsigned n_pieces) {
+    const unsigned b = blockIdx.x;
+    if (b >= n_pieces) return;
+    const SSetGPiece pc = pieces[b];
+    const SSetItem it = items[pc.item];
+    if (pc.off >= it.len) return;
+    const unsigned n = min((unsigned)SSET_GATHER_PIECE, it.len - pc.off);
+    const T *src = audio + it.src + (size_t)pc.chan * it.src_stride + pc.off;
+    double *dst = out + it.dst + (size_t)pc.chan * it.len + pc.off;
+    for (unsigned i = threadIdx.x; i < n; i += 256) dst[i] = (double)src[i];   // (F32 widened at the read)
+}
+
+// ------------------------------------------------------------------ host
+struct SSetChunk { uint64_t at; uint32_t len; int32_t channels; double pos; };   // at: first double in the host cache
+struct SSetFeed { uint32_t s; uint64_t at, n; };                                 // at: first byte in the staging buffer
+
+struct SSetMember {
+    aukit_codec_desc desc{};
+    uint64_t slot = 0;          // the rest's first byte in the current arena ...
+    uint64_t drop = 0;          // ... behind the bytes of dropped calls that the next repack leaves where they are
+    uint64_t resident = 0;      // bytes of the rest in the arena (the dropped ones not counted)
+    uint64_t pending = 0;       // bytes in the staging buffer
+    uint64_t sb_bytes = 0, sb_outputs = 0, decoded_total = 0;   // as aukit_stream's
+    uint64_t decoded_usable = ~0ull;   // the byte count of the last decode, in terms of the current rest
+    uint32_t skip = 0;          // chunks at the front of the next decode that are out already
+    uint32_t lead = 0;          // restart_rule's: 1 for stream.pcm
+    uint64_t call_bytes = 0;    // ... and the bytes of a whole iterator call (0: the member is never compacted)
+    bool finished = false;      // aukit_streamset_finish was called
+    bool over = false;          // no pump decodes this member any more: `end_status` is what follows its queued chunks
+    bool fed_any = false;
+    int end_status = 0;
+    std::string end_msg;
+    double length = 0;
+    std::deque<SSetChunk> q;
+};
+
+}  // namespace aukit
+
+struct aukit_streamset {
+    aukit_ctx *ctx = nullptr;
+    int interp = 0, mono = 0, dtype = AUKIT_F64;
+    std::vector<aukit::SSetMember> m;
+    // pinned host staging of what was fed since the last pump, and its device copy
+    unsigned char *stage = nullptr;
+    size_t stage_cap = 0, stage_used = 0;
+    std::vector<aukit::SSetFeed> feeds;
+    aukit::DevBuf d_stage, d_tab, d_gather;
+    // the two arenas
+    unsigned char *arena[2] = {nullptr, nullptr};
+    size_t arena_cap[2] = {0, 0};
+    int cur = 0;
+    uint64_t arena_used = 0;
+    // the decode's own audio and chunk table, reused from pump to pump
+    aukit_audio *out = nullptr;
+    aukit_chunks *ck = nullptr;
+    // pinned host cache of decided chunks: appended to by every pump, rewound once every chunk in it has been handed out
+    double *cache = nullptr;
+    size_t cache_cap = 0, cache_used = 0, cache_live = 0;
+};
+
+namespace aukit {
+
+static int pinned_grow(void **p, size_t *cap, size_t used, size_t need, size_t elem) {
+    if (need <= *cap) return AUKIT_OK;
+    const size_t ncap = std::max<size_t>(need + need / 2, 1 << 16);
+    void *np = nullptr;
+    hipError_t e = hipHostMalloc(&np, ncap * elem, hipHostMallocDefault);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(AUKIT_E_NOMEM, "hipHostMalloc(%zu) failed: %s", ncap * elem, hipGetErrorString(e)); }
+    if (used) memcpy(np, *p, used * elem);
+    if (*p) (void)hipHostFree(*p);
+    *p = np; *cap = ncap;
+    return AUKIT_OK;
+}
+
+// restart_rule's PCM / G.711 / IMA cases (stream_handle.hip): the bytes of a whole iterator call, and whether the rest starts one call early
+static void sset_restart(SSetMember &M, int interp) {
+    const aukit_codec_desc &d = M.desc;
+    const uint64_t C = (uint64_t)std::max(d.channels, 1);
+    if (d.codec == AUKIT_CODEC_PCM) {
+        M.lead = 1;
+        M.call_bytes = (uint64_t)stream_pcm_call_frames(d.sample_rate, interp) * C * (uint64_t)std::max(d.bit_depth / 8, 1);
+    } else if (d.codec == AUKIT_CODEC_G711) {
+        M.call_bytes = (uint64_t)d.sample_rate * C;
+    } else {
+        const double spb = (double)((uint64_t)d.block_align - 4 * C) * 2 / (double)C;   // :2765
+        M.call_bytes = (uint64_t)std::ceil(d.sample_rate / spb) * (uint64_t)d.block_align;   // :2766-2767
+    }
+}
+
+// the bytes of the rest an UNFINISHED member is decoded with: redecode()'s whole-frame trimming (stream_handle.hip)
+static uint64_t sset_whole_frames(const SSetMember &M, uint64_t nb) {
+    const uint64_t C = (uint64_t)std::max(M.desc.channels, 1);
+    if (M.desc.codec == AUKIT_CODEC_PCM) return nb - nb % (C * (uint64_t)std::max(M.desc.bit_depth / 8, 1));
+    if (M.desc.codec == AUKIT_CODEC_G711) return nb - nb % C;
+    return nb;
+}
+
+// What aukit_stream_decode says of a finished stream of `nb` bytes that the mixed call would refuse — the handle's words, a one-stream batch's index
+// included.  -> 0: served
+static int sset_finished_refusal(const SSetMember &M, uint64_t nb, bool mono) {
+    const aukit_codec_desc &d = M.desc;
+    if (d.codec == AUKIT_CODEC_PCM) {
+        const uint64_t bd = (uint64_t)std::max(d.bit_depth / 8, 1), C = (uint64_t)std::max(d.channels, 1);
+        if (nb % (bd * C) != 0) {
+            if (nb % bd != 0) return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: data ends inside a sample (stream %u)", 0u);
+            if (!mono || C == 1)
+                return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: data ends inside a frame and the channels are not mixed down: the reference's last chunk is longer in its first channels (stream %u)", 0u);
+        }
+    }
+    return check_smix_stream(&d, nb, mono);
+}
+
+struct SSetJob { uint32_t s; uint64_t usable; bool all_decided, ends; int end_status; std::string end_msg; };
+
+static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
+    aukit_ctx *ctx = S->ctx;
+    const uint32_t n = (uint32_t)S->m.size();
+    auto ready = [&]() { uint32_t r = 0; for (const SSetMember &M : S->m) r += M.q.empty() ? 0 : 1; if (n_ready) *n_ready = r; };
+    bool news = !S->feeds.empty();
+    for (const SSetMember &M : S->m) news = news || (!M.over && M.finished);
+    if (!news) { ready(); return AUKIT_OK; }   // nothing is launched
+    AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
+    if (S->cache_live == 0) S->cache_used = 0;
+    int rc;
+
+    // (1) the other arena's layout, the segments that build it
+    std::vector<SSetSeg> segs;
+    std::vector<uint64_t> slot(n, 0), filled(n, 0);
+    uint64_t cursor = 0;
+    for (uint32_t s = 0; s < n; s++) {
+        SSetMember &M = S->m[s];
+        slot[s] = cursor;
+        if (M.resident) {
+            for (uint64_t at = 0; at < M.resident; at += 0x40000000ull)   // (a segment's length is 32 bits)
+                segs.push_back(SSetSeg{M.slot + M.drop + at, cursor + at, (unsigned)std::min<uint64_t>(M.resident - at, 0x40000000ull), 0u});
+        }
+        filled[s] = M.resident;
+        cursor = round_up(cursor + M.resident + M.pending, 16);
+    }
+    for (const SSetFeed &f : S->feeds) {
+        for (uint64_t at = 0; at < f.n; at += 0x40000000ull)
+            segs.push_back(SSetSeg{f.at + at, slot[f.s] + filled[f.s] + at, (unsigned)std::min<uint64_t>(f.n - at, 0x40000000ull), 1u});
+        filled[f.s] += f.n;
+    }
+    const int nxt = S->cur ^ 1;
+    if (cursor + 64 > S->arena_cap[nxt]) {   // (outside the steady state; what the arena held is two pumps old)
+        const size_t cap = std::max<size_t>((size_t)(cursor + cursor / 2) + 64, 1 << 16);
+        if (S->arena[nxt]) (void)hipFree(S->arena[nxt]);
+        S->arena[nxt] = nullptr; S->arena_cap[nxt] = 0;
+        hipError_t e = hipMalloc((void **)&S->arena[nxt], cap);
+        if (e != hipSuccess) return fail(AUKIT_E_NOMEM, "hipMalloc(%zu) failed: %s", cap, hipGetErrorString(e));
+        S->arena_cap[nxt] = cap;
+    }
+    std::vector<SSetPiece> pieces;
+    uint64_t moved = 0;
+    for (size_t i = 0; i < segs.size(); i++) {
+        moved += segs[i].n;
+        for (unsigned off = 0; off < segs[i].n; off += SSET_PIECE) pieces.push_back(SSetPiece{(unsigned)i, off});
+    }
+    if (pieces.size() > 0x7FFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many pieces");
+
+    // (2) one upload, one repack
+    if (!pieces.empty()) {
+        const size_t seg_bytes = (size_t)round_up(segs.size() * sizeof(SSetSeg), 64);
+        if ((rc = S->d_tab.ensure(seg_bytes + pieces.size() * sizeof(SSetPiece))) || (rc = S->d_stage.ensure(std::max<size_t>(S->stage_used, 16)))) return rc;
+        if (S->stage_used) AUKIT_HIP_CHECK(hipMemcpyAsync(S->d_stage.p, S->stage, S->stage_used, hipMemcpyHostToDevice, ctx->stream));
+        char *T = reinterpret_cast<char *>(S->d_tab.p);
+        if ((rc = h2d_table(ctx, T, segs.data(), segs.size() * sizeof(SSetSeg))) || (rc = h2d_table(ctx, T + seg_bytes, pieces.data(), pieces.size() * sizeof(SSetPiece)))) return rc;
+        if ((rc = ctx_begin_kernel(ctx))) return rc;
+        hipLaunchKernelGGL(k_sset_repack, dim3((unsigned)pieces.size()), dim3(256), 0, ctx->stream, S->arena[S->cur], reinterpret_cast<const unsigned char *>(S->d_stage.p), S->arena[nxt],
+                           reinterpret_cast<const SSetSeg *>(T), reinterpret_cast<const SSetPiece *>(T + seg_bytes), (unsigned)pieces.size());
+        AUKIT_HIP_CHECK(hipGetLastError());
+        if ((rc = ctx_end_kernel(ctx, "k_sset_repack", 2 * moved))) return rc;
+    }
+    std::vector<bool> fed(n, false);
+    for (const SSetFeed &f : S->feeds) fed[f.s] = true;
+    for (uint32_t s = 0; s < n; s++) {
+        SSetMember &M = S->m[s];
+        M.slot = slot[s]; M.drop = 0;
+        M.resident += M.pending; M.pending = 0;
+    }
+    S->cur = nxt;
+    S->arena_used = cursor;
+    S->feeds.clear();
+    S->stage_used = 0;   // (the upload reads the buffer until this pump's wait: nothing is fed in between)
+
+    // (3) the members that have news, each asked on the host what would refuse the whole batch
+    std::vector<SSetJob> jobs;
+    for (uint32_t s = 0; s < n; s++) {
+        SSetMember &M = S->m[s];
+        if (M.over || !(fed[s] || M.finished)) continue;
+        SSetJob J{s, M.finished ? M.resident : sset_whole_frames(M, M.resident), M.finished, M.finished, 0, std::string()};
+        if (M.finished && (rc = sset_finished_refusal(M, M.resident, S->mono != 0))) {
+            // the string call refuses these bytes: as the handle, the member hands out the chunks of its whole frames, then that status
+            J.end_status = rc; J.end_msg = aukit_last_error();
+            J.usable = sset_whole_frames(M, M.resident);
+        }
+        if ((rc = check_smix_stream(&M.desc, J.usable, S->mono != 0))) {   // (not a verdict the trimming changes: the member ends here)
+            M.over = true; M.end_status = rc; M.end_msg = aukit_last_error();
+            M.sb_bytes += M.resident; M.resident = 0;
+            continue;
+        }
+        if (!M.finished && J.usable == M.decoded_usable) continue;   // a piece that ends inside the same frame: nothing new to decide
+        jobs.push_back(J);
+    }
+
+    std::vector<SSetItem> items;
+    std::vector<SSetGPiece> gpieces;
+    std::vector<std::pair<uint32_t, SSetChunk>> fresh;   // (member, chunk), `at` relative to this pump's part of the cache
+    uint64_t gather_elems = 0;
+    if (!jobs.empty()) {
+        const uint32_t nj = (uint32_t)jobs.size();
+        std::vector<aukit_codec_desc> descs(nj);
+        std::vector<SMixCarry> carry(nj);
+        // the batch aukit_batch_wrap_device makes of the arena, without the device copy of the offsets (nothing on this path reads it): stream i
+        // starts at its member's slot; how many of the bytes from there on are its own is the carry's word
+        aukit_batch B;
+        B.n = nj; B.base = S->arena[S->cur]; B.front_pad = 0; B.cap = (size_t)S->arena_used; B.own = false;
+        B.off.resize((size_t)nj + 1);
+        for (uint32_t i = 0; i < nj; i++) {
+            const SSetMember &M = S->m[jobs[i].s];
+            descs[i] = M.desc;
+            carry[i] = SMixCarry{M.sb_bytes, M.sb_outputs, jobs[i].usable};
+            B.off[i] = M.slot;
+        }
+        B.off[nj] = S->arena_used;
+        if ((rc = stream_decode_mixed_carry(ctx, &B, descs.data(), nj, S->interp, S->mono, S->dtype, &S->out, &S->ck, carry.data()))) return rc;
+        const aukit_chunks &ck = *S->ck;
+        const aukit_audio &a = *S->out;
+        const size_t mc = std::max<uint32_t>(ck.max_chunks, 1);
+        for (uint32_t i = 0; i < nj; i++) {
+            const SSetJob &J = jobs[i];
+            SSetMember &M = S->m[J.s];
+            const uint32_t nch = ck.nchunks[i];
+            const uint32_t decided = J.all_decided ? nch : (nch ? nch - 1 : 0);
+            M.length = ck.length_seconds[i];
+            M.decoded_total += J.usable;
+            M.decoded_usable = J.usable;
+            uint64_t before = 0;
+            for (uint32_t k = 0; k < decided; k++) {
+                const uint32_t len = ck.lens[(size_t)i * mc + k];
+                if (k >= M.skip) {
+                    fresh.push_back({J.s, SSetChunk{gather_elems, len, a.channels, ck.pos[(size_t)i * mc + k]}});
+                    if (len) {
+                        for (int c = 0; c < a.channels; c++)
+                            for (unsigned off = 0; off < len; off += SSET_GATHER_PIECE) gpieces.push_back(SSetGPiece{(unsigned)items.size(), (unsigned)c, off, 0u});
+                        items.push_back(SSetItem{a.row_off[i] + before, gather_elems, (unsigned)a.row_stride[i], len});
+                    }
+                    gather_elems += (uint64_t)len * a.channels;
+                }
+                before += len;
+            }
+            M.skip = std::max(M.skip, decided);
+            if (J.ends) {   // what follows the queued chunks is settled: the member leaves the arena
+                M.over = true;
+                M.end_status = J.end_status ? J.end_status : ck.status[i];
+                M.end_msg = J.end_status ? J.end_msg : (ck.status[i] == AUKIT_E_LUA ? "attempt to perform arithmetic on a nil value (field '?')" : "");
+                M.sb_bytes += M.resident; M.resident = 0;
+                continue;
+            }
+            // (5) the compaction plan: the whole calls whose chunks are out and that no later chunk depends on stay behind at the next repack
+            const uint64_t shift = M.lead ? (M.skip ? M.skip - 1 : 0) : M.skip;   // the fresh decode's chunk 0 is this one's chunk `shift`
+            if (shift && M.call_bytes && shift * M.call_bytes <= M.resident) {
+                const uint64_t drop = shift * M.call_bytes;
+                for (uint32_t k = 0; k < shift; k++) M.sb_outputs += ck.lens[(size_t)i * mc + k];
+                M.sb_bytes += drop;
+                M.drop += drop; M.resident -= drop;
+                M.decoded_usable -= drop;
+                M.skip -= (uint32_t)shift;
+            }
+        }
+    }
+
+    // (4) one gather, one download, one wait
+    if (!gpieces.empty()) {
+        if (gpieces.size() > 0x7FFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many pieces");
+        void *cp = S->cache;
+        if ((rc = pinned_grow(&cp, &S->cache_cap, S->cache_used, S->cache_used + (size_t)gather_elems, sizeof(double)))) return rc;
+        S->cache = reinterpret_cast<double *>(cp);
+        const size_t item_bytes = (size_t)round_up(items.size() * sizeof(SSetItem), 64);
+        if ((rc = S->d_gather.ensure((size_t)gather_elems * 8)) || (rc = S->d_tab.ensure(item_bytes + gpieces.size() * sizeof(SSetGPiece)))) return rc;
+        char *T = reinterpret_cast<char *>(S->d_tab.p);   // (the repack's tables: read by a kernel in front of these copies on the same stream)
+        if ((rc = h2d_table(ctx, T, items.data(), items.size() * sizeof(SSetItem))) || (rc = h2d_table(ctx, T + item_bytes, gpieces.data(), gpieces.size() * sizeof(SSetGPiece)))) return rc;
+        if ((rc = ctx_begin_kernel(ctx))) return rc;
+        if (S->dtype == AUKIT_F64)
+            hipLaunchKernelGGL(k_sset_gather<double>, dim3((unsigned)gpieces.size()), dim3(256), 0, ctx->stream, reinterpret_cast<const double *>(S->out->dev),
+                               reinterpret_cast<double *>(S->d_gather.p), reinterpret_cast<const SSetItem *>(T), reinterpret_cast<const SSetGPiece *>(T + item_bytes), (unsigned)gpieces.size());
+        else
+            hipLaunchKernelGGL(k_sset_gather<float>, dim3((unsigned)gpieces.size()), dim3(256), 0, ctx->stream, reinterpret_cast<const float *>(S->out->dev),
+                               reinterpret_cast<double *>(S->d_gather.p), reinterpret_cast<const SSetItem *>(T), reinterpret_cast<const SSetGPiece *>(T + item_bytes), (unsigned)gpieces.size());
+        AUKIT_HIP_CHECK(hipGetLastError());
+        if ((rc = ctx_end_kernel(ctx, "k_sset_gather", gather_elems * (dtype_size(S->dtype) + 8)))) return rc;
+        AUKIT_HIP_CHECK(hipMemcpyAsync(S->cache + S->cache_used, S->d_gather.p, (size_t)gather_elems * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (auto &f : fresh) {
+        f.second.at += S->cache_used;
+        S->m[f.first].q.push_back(f.second);
+    }
+    S->cache_used += (size_t)gather_elems;
+    S->cache_live += fresh.size();
+    ready();
+    return AUKIT_OK;
+}
+
+}  // namespace aukit
+
+using namespace aukit;
+
+extern "C" {
+
+int aukit_streamset_open(aukit_ctx *ctx, const aukit_codec_desc *descs, uint32_t n, int interp, int mono, int dtype, aukit_streamset **out) {
+    if (!ctx || !out || (!descs && n)) return fail(AUKIT_E_ARG, "null argument");
+    if (dtype != AUKIT_F64 && dtype != AUKIT_F32) return fail(AUKIT_E_ARG, "dtype must be AUKIT_F64 or AUKIT_F32");
+    if (interp < 0 || interp > 3) return fail(AUKIT_E_ARG, "invalid interpolation");
+    if (interp == AUKIT_INTERP_SINC) return fail(AUKIT_E_UNSUPPORTED, "sinc interpolation is not served for a stream set: it keeps aukit_stream_open");
+    int rc;
+    if ((rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV},
+                                 "stream %u: codec %d keeps aukit_stream_open (a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711 and AUKIT_CODEC_ADPCM_WAV)")))
+        return rc;
+    if ((rc = mixed_check_channels(n, mono, [&](uint32_t s) { return descs[s].channels; }))) return rc;
+    for (uint32_t s = 0; s < n; s++)
+        if ((rc = check_smix_stream(&descs[s], 0, mono != 0))) return fail_for_stream(rc, s);
+    aukit_streamset *S = new aukit_streamset();
+    S->ctx = ctx; S->interp = interp; S->mono = mono ? 1 : 0; S->dtype = dtype;
+    S->m.resize(n);
+    for (uint32_t s = 0; s < n; s++) {
+        S->m[s].desc = descs[s];
+        sset_restart(S->m[s], interp);
+    }
+    *out = S;
+    return AUKIT_OK;
+}
+
+int aukit_streamset_feed(aukit_streamset *S, uint32_t s, const uint8_t *bytes, uint64_t nbytes) {
+    if (!S || (!bytes && nbytes)) return fail(AUKIT_E_ARG, "null argument");
+    if (s >= S->m.size()) return fail(AUKIT_E_ARG, "member %u of a set of %zu", s, S->m.size());
+    SSetMember &M = S->m[s];
+    if (M.finished) return fail(AUKIT_E_ARG, "aukit_streamset_feed after aukit_streamset_finish");
+    if (!nbytes) return AUKIT_OK;
+    if (M.over) return AUKIT_OK;   // (a member that has ended on its own words: the bytes have nowhere to go)
+    // the piece starts at the residue modulo 16 it will have in the arena: slots start at multiples of 16, the rest and what is pending lie in front
+    const size_t want = (size_t)((M.resident + M.pending) & 15);
+    size_t at = S->stage_used;
+    at += (want + 16 - (at & 15)) & 15;
+    void *p = S->stage;
+    if (at + nbytes > S->stage_cap) {
+        if (hipSetDevice(S->ctx->device) != hipSuccess) { (void)hipGetLastError(); return fail(AUKIT_E_HIP, "hipSetDevice failed"); }
+        int rc = pinned_grow(&p, &S->stage_cap, S->stage_used, at + (size_t)nbytes, 1);
+        if (rc) return rc;
+        S->stage = reinterpret_cast<unsigned char *>(p);
+    }
+    memcpy(S->stage + at, bytes, (size_t)nbytes);
+    S->stage_used = at + (size_t)nbytes;
+    S->feeds.push_back(SSetFeed{s, (uint64_t)at, nbytes});
+    M.pending += nbytes;
+    M.fed_any = true;
+    return AUKIT_OK;
+}
+
+int aukit_streamset_finish(aukit_streamset *S, uint32_t s) {
+    if (!S) return fail(AUKIT_E_ARG, "null argument");
+    if (s >= S->m.size()) return fail(AUKIT_E_ARG, "member %u of a set of %zu", s, S->m.size());
+    SSetMember &M = S->m[s];
+    M.finished = true;
+    if (!M.fed_any) M.over = true;   // finished while empty: the iterator's first call returns nil
+    return AUKIT_OK;
+}
+
+int aukit_streamset_pump(aukit_streamset *S, uint32_t *n_ready) {
+    if (!S) return fail(AUKIT_E_ARG, "null argument");
+    const int rc = sset_pump(S, n_ready);
+    if (rc) {   // whatever was queued reads the staging buffer and the tables no longer: the next feed may write them
+        const std::string msg = aukit_last_error();
+        (void)hipStreamSynchronize(S->ctx->stream);
+        (void)hipGetLastError();
+        return fail(rc, "%s", msg.c_str());
+    }
+    return AUKIT_OK;
+}
+
+int aukit_streamset_next(aukit_streamset *S, uint32_t s, double *dst, uint64_t dst_elems, uint32_t cap, uint32_t *len, int32_t *channels, double *pos, int32_t *state) {
+    if (!S || !len || !state) return fail(AUKIT_E_ARG, "null argument");
+    if (s >= S->m.size()) return fail(AUKIT_E_ARG, "member %u of a set of %zu", s, S->m.size());
+    SSetMember &M = S->m[s];
+    *len = 0;
+    if (M.q.empty()) {
+        if (!M.over) { *state = AUKIT_STREAM_NEED_INPUT; return AUKIT_OK; }
+        if (M.end_status) return fail(M.end_status, "%s", M.end_msg.c_str());
+        *state = AUKIT_STREAM_END;
+        return AUKIT_OK;
+    }
+    const SSetChunk &c = M.q.front();
+    const uint32_t n = c.len;
+    const int C = c.channels;
+    if (channels) *channels = C;
+    if (pos) *pos = c.pos;
+    if (n > cap) { *len = n; return fail(AUKIT_E_ARG, "chunk of %u samples does not fit the %u offered", n, cap); }
+    if ((uint64_t)C * cap > dst_elems) {
+        *len = n;
+        return fail(AUKIT_E_ARG, "%d channels of %u samples need %llu elements at dst, %llu offered", C, cap, (unsigned long long)C * cap, (unsigned long long)dst_elems);
+    }
+    if (n && !dst) return fail(AUKIT_E_ARG, "null argument");
+    for (int ch = 0; ch < C && n; ch++) memcpy(dst + (size_t)ch * cap, S->cache + c.at + (size_t)ch * n, (size_t)n * sizeof(double));
+    *len = n;
+    *state = AUKIT_STREAM_CHUNK;
+    M.q.pop_front();
+    S->cache_live--;
+    return AUKIT_OK;
+}
+
+int aukit_streamset_length(aukit_streamset *S, uint32_t s, double *seconds) {
+    if (!S || !seconds) return fail(AUKIT_E_ARG, "null argument");
+    if (s >= S->m.size()) return fail(AUKIT_E_ARG, "member %u of a set of %zu", s, S->m.size());
+    *seconds = S->m[s].length;
+    return AUKIT_OK;
+}
+
+int aukit_streamset_resident(const aukit_streamset *S, uint32_t s, uint64_t *resident, uint64_t *dropped, uint64_t *decoded_total) {
+    if (!S) return fail(AUKIT_E_ARG, "null argument");
+    if (s >= S->m.size()) return fail(AUKIT_E_ARG, "member %u of a set of %zu", s, S->m.size());
+    const SSetMember &M = S->m[s];
+    if (resident) *resident = M.resident + M.pending;
+    if (dropped) *dropped = M.sb_bytes;
+    if (decoded_total) *decoded_total = M.decoded_total;
+    return AUKIT_OK;
+}
+
+void aukit_streamset_close(aukit_streamset *S) {
+    if (!S) return;
+    (void)hipSetDevice(S->ctx->device);
+    (void)hipStreamSynchronize(S->ctx->stream);
+    if (S->ck) aukit_chunks_free(S->ck);
+    if (S->out) aukit_audio_free(S->out);
+    for (int i = 0; i < 2; i++) if (S->arena[i]) (void)hipFree(S->arena[i]);
+    if (S->stage) (void)hipHostFree(S->stage);
+    if (S->cache) (void)hipHostFree(S->cache);
+    S->d_stage.release(); S->d_tab.release(); S->d_gather.release();
+    delete S;
+}
+
+}  // extern "C"

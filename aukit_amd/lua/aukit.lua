@@ -84,6 +84,14 @@ int aukit_stream_feed(aukit_stream *, const uint8_t *bytes, uint64_t n); int auk
 int aukit_stream_next(aukit_stream *, double *dst, uint64_t dst_elems, uint32_t cap, uint32_t *len, int32_t *channels, double *pos, int32_t *state);
 int aukit_stream_chunk_lens(aukit_stream *, uint32_t *lens, uint32_t n_lens);
 int aukit_stream_length(aukit_stream *, double *seconds); void aukit_stream_close(aukit_stream *);
+typedef struct aukit_streamset aukit_streamset;
+int aukit_streamset_open(aukit_ctx *, const aukit_codec_desc *descs, uint32_t n, int interp, int mono, int dtype, aukit_streamset **out);
+int aukit_streamset_feed(aukit_streamset *, uint32_t s, const uint8_t *bytes, uint64_t nbytes); int aukit_streamset_finish(aukit_streamset *, uint32_t s);
+int aukit_streamset_pump(aukit_streamset *, uint32_t *n_ready);
+int aukit_streamset_next(aukit_streamset *, uint32_t s, double *dst, uint64_t dst_elems, uint32_t cap, uint32_t *len, int32_t *channels, double *pos, int32_t *state);
+int aukit_streamset_length(aukit_streamset *, uint32_t s, double *seconds);
+int aukit_streamset_resident(const aukit_streamset *, uint32_t s, uint64_t *resident, uint64_t *dropped, uint64_t *decoded_total);
+void aukit_streamset_close(aukit_streamset *);
 ]]
 
 local C = ffi.load(os.getenv("AUKIT_HIP_LIB") or "aukit_hip")
@@ -906,6 +914,87 @@ function aukit.stream.many(files, mono)
         end
         res[i] = {it, lengths[i] == lengths[i] and lengths[i] or length[s]}
         at = at + row * ch[0]
+    end
+    return res
+end
+-- many live sources as one batch (aukit_streamset): `readers` = reader functions, each a WAV / AIFF / AU stream of PCM, G.711 or IMA-ADPCM blocks whose
+-- first piece holds the whole header (:2918) -> a list of {iterator, length} pairs in input order, each iterator handing out what aukit.stream.wav / aiff /
+-- au(fn, mono) hands out.  A round starts when any iterator has nothing decided: one piece is pulled from every unfinished reader, then one pump does the
+-- device work of all of them (one upload, three launches, one download).  A payload the set does not take is refused by the reader's index.
+function aukit.stream.set(readers, mono)
+    expect(1, readers, "table") expect(2, mono, "boolean", "nil")
+    local n = #readers
+    local descs = ffi.new("aukit_codec_desc[?]", math.max(n, 1))
+    local firsts, lengths, done = {}, {}, {}
+    local takes = "stream.set takes PCM and G.711 payloads and IMA-ADPCM blocks (the other codecs keep their own streams)"
+    for i = 1, n do
+        if type(readers[i]) ~= "function" then error("bad argument #1 (reader " .. (i - 1) .. ": expected function)", 2) end
+        local f = readers[i]()
+        if type(f) ~= "string" then error("bad argument #1 (reader " .. (i - 1) .. ": expected string from the first call)", 2) end
+        if f:sub(1, 4) == "qoaf" then error("reader " .. (i - 1) .. ": qoa payload: " .. takes, 2) end
+        local kind
+        for _, m in ipairs(MAGIC) do if f:find(m[1]) then kind = m[2] break end end
+        if not kind then error("reader " .. (i - 1) .. ": not a WAV, AIFF or AU stream", 2) end
+        local c = ffi.new("aukit_container")
+        if C.aukit_parse_container(ffi.cast("const uint8_t*", f), #f, kind, 2, c) ~= 0 then error("reader " .. (i - 1) .. ": " .. ffi.string(C.aukit_last_error()), 2) end
+        if c.desc.codec > 1 and c.desc.codec ~= 3 then   -- 0: PCM, 1: G.711, 3: AUKIT_CODEC_ADPCM_WAV
+            error("reader " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: " .. takes, 2)
+        end
+        descs[i - 1] = c.desc
+        firsts[i] = f:sub(tonumber(c.payload_off) + 1, tonumber(c.payload_off + c.payload_len))
+        lengths[i] = c.length_seconds   -- NaN: the stream factory's own figure stands
+        done[i] = false
+    end
+    local sp = ffi.new("aukit_streamset*[1]")
+    check(C.aukit_streamset_open(ctx(), descs, n, INTERP[aukit.defaultInterpolation], mono and 1 or 0, F64, sp))
+    local set = ffi.gc(sp[0], C.aukit_streamset_close)
+    local ready = ffi.new("uint32_t[1]")
+    local function round(pieces)
+        for i = 1, n do
+            if not done[i] then
+                local piece
+                if pieces then piece = pieces[i] else piece = readers[i]() end
+                if piece == nil then done[i] = true check(C.aukit_streamset_finish(set, i - 1))
+                else check(C.aukit_streamset_feed(set, i - 1, ffi.cast("const uint8_t*", piece), #piece)) end
+            end
+        end
+        check(C.aukit_streamset_pump(set, ready))
+    end
+    round(firsts)
+    local CAP = 48000   -- a chunk of stream.pcm / g711 / adpcm never exceeds a second of output
+    local buf_ch = 2
+    local buf = ffi.new("double[?]", CAP * buf_ch)
+    local len, ch, st, pos, secs = ffi.new("uint32_t[1]"), ffi.new("int32_t[1]"), ffi.new("int32_t[1]"), ffi.new("double[1]"), ffi.new("double[1]")
+    local res = {}
+    for i = 1, n do
+        local s, ended = i - 1, false
+        local it = function()
+            while not ended do
+                local rc = C.aukit_streamset_next(set, s, buf, CAP * buf_ch, CAP, len, ch, pos, st)
+                if rc == -1 and ch[0] > buf_ch and len[0] <= CAP then   -- more channels than the buffer was sized for: the chunk is still there
+                    buf_ch = ch[0]
+                    buf = ffi.new("double[?]", CAP * buf_ch)
+                    rc = C.aukit_streamset_next(set, s, buf, CAP * buf_ch, CAP, len, ch, pos, st)
+                end
+                check(rc)
+                if st[0] == 0 then      -- AUKIT_STREAM_CHUNK
+                    local chunk = {}
+                    for c = 1, ch[0] do
+                        local t = {}
+                        for j = 1, len[0] do t[j] = buf[(c - 1) * CAP + j - 1] end
+                        chunk[c] = t
+                    end
+                    return chunk, pos[0]
+                elseif st[0] == 2 then  -- AUKIT_STREAM_END
+                    ended = true
+                else                    -- AUKIT_STREAM_NEED_INPUT: the next round, for every member
+                    round(nil)
+                end
+            end
+            return nil
+        end
+        check(C.aukit_streamset_length(set, s, secs))
+        res[i] = {it, lengths[i] == lengths[i] and lengths[i] or secs[0]}
     end
     return res
 end

@@ -441,6 +441,45 @@ int aukit_stream_length(aukit_stream *s, double *seconds);                   /* 
 int aukit_stream_resident(const aukit_stream *s, uint64_t *resident, uint64_t *dropped, uint64_t *decoded_total);
 void aukit_stream_close(aukit_stream *s);
 
+/* ---- many live streams as one batch: a SET of reader-function streams (a host that serves a thousand listeners: austream.lua:19-64 once per
+ * listener).  Member s is aukit_stream_open(ctx, &descs[s], interp, mono, dtype) fed the same bytes and finished at the same point: the chunks
+ * it hands out — samples, length, channel count, position, the END or the AUKIT_E_LUA raise behind the last one, aukit_streamset_length — are
+ * those of aukit_stream_decode for the member's concatenated bytes.  How the bytes are cut into pieces and how the pumps are spaced decides only
+ * WHEN a chunk is there, never what it is.  What differs is the cost: aukit_streamset_feed copies into a pinned host buffer and touches no
+ * device; aukit_streamset_pump does the device work of a tick for all members at once — one upload of everything fed since the last pump, one
+ * repack launch (k_sset_repack: every member's rest, without the bytes of the iterator calls whose chunks are out, followed by its new bytes,
+ * into the other of two device arenas; slots at multiples of 16 bytes), one aukit_stream_decode_mixed plan and launch chain over the members
+ * that have news (with what each has dropped added to its positions and length), one gather launch (k_sset_gather: the newly decided chunks of
+ * all members as doubles, [item][channel][len]), one download into the set's pinned cache and one wait (members of AUKIT_CODEC_ADPCM_WAV add the
+ * mixed call's header-scan read-back).  A pump in which no member has news launches nothing.  aukit_streamset_next only reads the cache.
+ * A chunk is decided as in the handle: a later chunk of the same decode exists, or the member is finished; undrained chunks queue on the host.
+ * A member is compacted in every pump in which a call of its became droppable (no 64 KiB threshold: the repack runs anyway): stream.pcm keeps
+ * the call in front of the next one and skips its chunk, stream.g711 and stream.adpcm calls stand alone.
+ * Members: AUKIT_CODEC_PCM (rates at or below 48 kHz), AUKIT_CODEC_G711 (integer rates), AUKIT_CODEC_ADPCM_WAV — aukit_stream_decode_mixed's
+ * checks and words; interpolation none / linear / cubic; dtype AUKIT_F64, or AUKIT_F32 — the F64 result rounded once, which is the handle's on a
+ * context with AUKIT_OPT_EXACT_MATH = 2 (the mixed call's arithmetic) —; without `mono` the descriptors agree in channel count.
+ * What a descriptor alone decides is refused at open with the member's index appended.  Every other codec keeps aukit_stream_open
+ * (AUKIT_E_UNSUPPORTED by name) — AUKIT_CODEC_DFPWM too, although the mixed call streams it: its decoder's state crosses iterator calls and a
+ * set carries none (out of scope here).  The set is the handle of a context WITHOUT AUKIT_OPT_CHANNEL_LENS, whatever the context says.
+ * One bad member ends alone.  A finished member whose bytes the string call refuses (data that ends inside a sample; inside a frame without
+ * the mix-down) hands out, as the handle does, the chunks of its whole frames — those decided earlier, then the rest — and from then on that
+ * status and message; it enters no later pump, and no other member notices. */
+typedef struct aukit_streamset aukit_streamset;
+int aukit_streamset_open(aukit_ctx *ctx, const aukit_codec_desc *descs /* n */, uint32_t n, int interp, int mono, int dtype, aukit_streamset **out);
+/* host copy only: no device call, no wait (the pinned buffer grows, rarely, outside the steady state).  After aukit_streamset_finish: AUKIT_E_ARG */
+int aukit_streamset_feed(aukit_streamset *set, uint32_t s, const uint8_t *bytes, uint64_t nbytes);
+int aukit_streamset_finish(aukit_streamset *set, uint32_t s);                /* a member finished while empty ends at once */
+/* all device work of a tick; `*n_ready` = members with a chunk waiting in the host cache */
+int aukit_streamset_pump(aukit_streamset *set, uint32_t *n_ready);
+/* aukit_stream_next for member s, from the host cache: CHUNK, NEED_INPUT (nothing decided: feed or finish, then pump), END (finished, pumped and
+ * drained), or — after the last chunk — the status and message aukit_stream_next ends that stream with.  The `dst_elems` / `cap` refusals are
+ * aukit_stream_next's: nothing is written and the chunk stays */
+int aukit_streamset_next(aukit_streamset *set, uint32_t s, double *dst, uint64_t dst_elems, uint32_t cap, uint32_t *len, int32_t *channels, double *pos, int32_t *state);
+int aukit_streamset_length(aukit_streamset *set, uint32_t s, double *seconds);   /* as of the last pump that decoded the member */
+/* member s: bytes in the device arena, bytes dropped in front of them, input bytes of all its decodes so far */
+int aukit_streamset_resident(const aukit_streamset *set, uint32_t s, uint64_t *resident, uint64_t *dropped, uint64_t *decoded_total);
+void aukit_streamset_close(aukit_streamset *set);
+
 #ifdef __cplusplus
 }
 #endif
