@@ -28,7 +28,7 @@ MAX_CH = 8            # AUKIT_MAX_CHANNELS
 MAX_PLANAR_CH = 64    # AUKIT_MAX_PLANAR_CHANNELS (the descriptor's predictor / step_index arrays)
 OPT_EXACT_MATH, OPT_STORE_X4, OPT_COLLECT_STATS, OPT_DFPWM_SPECULATE, OPT_CHANNEL_LENS = 0, 1, 2, 3, 4
 COUNTER_DFPWM_CHUNKS, COUNTER_DFPWM_CHUNKS_REDONE, COUNTER_FLAC_FUSED, COUNTER_TIER1_ERR_NANO, COUNTER_TIER1_OUTPUTS = 0, 1, 2, 3, 4
-COUNTER_DFPWM_RESPECULATED, COUNTER_DFPWM_HARD, COUNTER_RECURRENCE_F32 = 5, 6, 7
+COUNTER_DFPWM_RESPECULATED, COUNTER_DFPWM_HARD, COUNTER_RECURRENCE_F32, COUNTER_QOA_WAVE = 5, 6, 7, 8
 WAVE_NONE, WAVE_SINE, WAVE_TRIANGLE, WAVE_SAWTOOTH, WAVE_SQUARE = 0, 1, 2, 3, 4
 PACK_TRUNC, PACK_FLOOR, PACK_STRICT = 0, 1, 2
 STREAM_CHUNK, STREAM_NEED_INPUT, STREAM_END = 0, 1, 2

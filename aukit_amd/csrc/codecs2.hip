@@ -119,6 +119,7 @@ static int qoa_scan(const uint8_t *hdr, uint64_t nb, bool audio_mode, int *file_
 // round 2's aukit.qoa (host-side header walk on a copy of the batch, lane-per-job kernel): the fallback of qoa.hip
 int decode_qoa_audio_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *, double new_rate, int interp, bool do_resample, int dtype,
                           aukit_audio **out) {
+    ctx->counters[AUKIT_COUNTER_QOA_WAVE] = 0;
     // headers are parsed on the host (8 bytes per 5120-sample frame); the batch is read back once for that
     // (through the context's pinned staging buffer: a fresh 360 MB std::vector — zero-filled, then page-faulted in by a pageable copy — was
     // 80 of the 100 ms a 1024-stream call took)
@@ -145,13 +146,15 @@ int decode_qoa_audio_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_cod
         for (size_t k = 0; k < frames.size(); k++) { L = std::max<uint64_t>(L, sp + (uint64_t)((frames[k].samples + 19) / 20) * 20); sp += frames[k].samples; }
         const uint64_t stride = round_up(std::max<uint64_t>(L, 1), 8);
         sp = 0;
+        size_t lastnz = frames.size();   // the last frame that holds samples: frames of zero samples behind it overwrite nothing
+        for (size_t k = 0; k < frames.size(); k++) if (frames[k].samples > 0) lastnz = k;
         for (size_t k = 0; k < frames.size(); k++) {
-            const bool lastf = k + 1 == frames.size();
+            const bool lastf = k == lastnz;
             for (int c = 0; c < C; c++) {
                 QoaJob j;
                 j.frame_off = in->off[s] + frames[k].off; j.out_off = tot + (uint64_t)c * stride + sp;
                 j.c = c; j.channels = C; j.samples = frames[k].samples;
-                j.emit = lastf ? ((frames[k].samples + 19) / 20) * 20 : frames[k].samples;  // Q15: the ≤19-sample tail survives only after the last frame
+                j.emit = lastf ? ((frames[k].samples + 19) / 20) * 20 : frames[k].samples;  // Q15: the ≤19-sample tail survives only after the last frame that holds samples
                 jobs.push_back(j);
             }
             sp += frames[k].samples;

@@ -134,7 +134,7 @@ struct aukit_ctx {
     struct aukit_chunks *spcm_ck = nullptr;
     // AUKIT_OPT_COLLECT_STATS: counters of the last call that has any (aukit_ctx_get_counter)
     bool collect_stats = false;
-    uint64_t counters[8] = {};
+    uint64_t counters[9] = {};
 };
 
 struct aukit_batch {

@@ -146,6 +146,13 @@ __global__ __launch_bounds__(64) void k_msadpcm(const MsParams P) {
     }
 }
 
+// a stream that ends inside a block: the reference's error is that of the first read that finds nothing — the header's str_unpack (stereo: fewer than 14
+// bytes left, :1310; mono reads the stream's first 7 bytes for every block, :1331), else str_byte's nil in bit32_rshift (:1317-1318, :1336-1337)
+static int ms_partial_block(int C, uint64_t nb, uint64_t ba) {
+    if (C == 2 ? nb % ba < 14 : nb < 7) return fail(AUKIT_E_LUA, "data string too short");
+    return fail(AUKIT_E_LUA, "bad argument #1 to 'rshift' (number expected, got nil)");
+}
+
 static const int ms_c1_default[7] = {256, 512, 0, 192, 240, 460, 392}, ms_c2_default[7] = {0, -256, 0, 64, 0, -208, -232};  // :1304
 
 // decodes every block of every stream into fp64 rows in ctx->tmp_buf; rows are per (stream, channel), blocks back to back
@@ -154,7 +161,7 @@ static int msadpcm_rows(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
     const int C = d->channels;
     if (C != 1 && C != 2) return fail(AUKIT_E_LUA, "Unsupported number of channels: %d", C);
     const uint64_t ba = (uint64_t)d->block_align;
-    if (d->block_align < (C == 2 ? 15 : 8)) return fail(AUKIT_E_ARG, "bad blockAlign");
+    if (d->block_align < (stream_mode ? 7 * C + 1 : 7 * C)) return fail(AUKIT_E_ARG, "bad blockAlign");   // (a block that is only a header: two samples, :1312-1315)
     const uint64_t spb = C == 2 ? (ba - 14) + 2 : (ba - 7) * 2 + 2;  // samples decoded per block per channel
     *spb_out = spb;
     std::vector<MsJob> jobs;
@@ -165,7 +172,8 @@ static int msadpcm_rows(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
     for (uint32_t s = 0; s < in->n; s++) {
         const uint64_t nb = in->off[s + 1] - in->off[s];
         const uint64_t nblk = (nb + ba - 1) / ba;  // for n = 1, #data, blockAlign
-        if (nblk && nb % ba != 0) return fail(AUKIT_E_LUA, "bad argument #1 to 'rshift' (number expected, got nil)");
+        // (mono blocks that are only a header read nothing but the stream's first seven bytes: a partial last one is a block like the others)
+        if (nblk && nb % ba != 0 && !(C == 1 && ba == 7 && nb >= 7)) return ms_partial_block(C, nb, ba);
         nblocks[s] = nblk;
         const uint64_t L = nblk * spb, stride = round_up(std::max<uint64_t>(L, 1), 2);
         for (int c = 0; c < C; c++) { row_off[(size_t)s * C + c] = tot + (uint64_t)c * stride; row_len[(size_t)s * C + c] = L; }
@@ -884,16 +892,16 @@ static size_t ms_lds_bytes(int C, int rb, unsigned wt_floats, int fb = 0, size_t
 
 struct MsBlocks { std::vector<uint64_t> blk0; uint64_t bps = 0; };
 // per stream block counts (a partial last block is the reference's `str_byte` returning nil: an error, as before)
-static int ms_count_blocks(const aukit_batch *in, const aukit_codec_desc *d, MsBlocks &B) {
+static int ms_count_blocks(const aukit_batch *in, const aukit_codec_desc *d, MsBlocks &B, bool stream_mode) {
     const int C = d->channels;
     if (C != 1 && C != 2) return fail(AUKIT_E_LUA, "Unsupported number of channels: %d", C);
     const uint64_t ba = (uint64_t)d->block_align;
-    if (d->block_align < (C == 2 ? 15 : 8)) return fail(AUKIT_E_ARG, "bad blockAlign");
+    if (d->block_align < (stream_mode ? 7 * C + 1 : 7 * C)) return fail(AUKIT_E_ARG, "bad blockAlign");
     B.blk0.assign((size_t)in->n + 1, 0);
     bool uni = in->n > 0;
     for (uint32_t s = 0; s < in->n; s++) {
         const uint64_t nb = in->off[s + 1] - in->off[s], nblk = (nb + ba - 1) / ba;
-        if (nblk && nb % ba != 0) return fail(AUKIT_E_LUA, "bad argument #1 to 'rshift' (number expected, got nil)");
+        if (nblk && nb % ba != 0) return ms_partial_block(C, nb, ba);   // (the stream's iterator fails on the same reads, :2646 / :2706)
         B.blk0[s + 1] = B.blk0[s] + nblk;
         uni = uni && nblk > 0 && nblk == B.blk0[1];
     }
@@ -907,10 +915,11 @@ int decode_msadpcm_audio(aukit_ctx *ctx, const aukit_batch *in, const aukit_code
     static const bool magic_ok = ms_magic_ok();
     MsWaveParams P{};
     const int C = d->channels;
-    const bool wave = magic_ok && ms_fill_coefs(d, P) && (dtype == AUKIT_F64 || dtype == AUKIT_F32) && (C == 1 || C == 2);
+    // (blocks that are only a header, block_align 7 C: no round for the wave kernel to run — the lane-per-block kernel writes their two samples)
+    const bool wave = magic_ok && ms_fill_coefs(d, P) && (dtype == AUKIT_F64 || dtype == AUKIT_F32) && (C == 1 || C == 2) && d->block_align != 7 * C;
     if (wave) {
         MsBlocks B;
-        int rc = ms_count_blocks(in, d, B);
+        int rc = ms_count_blocks(in, d, B, false);
         if (rc) return rc;
         const uint64_t ba = (uint64_t)d->block_align, nblocks = B.blk0[in->n];
         const uint64_t spb = C == 2 ? (ba - 14) + 2 : (ba - 7) * 2 + 2;
@@ -1001,7 +1010,7 @@ int stream_msadpcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc
     if (interp < 0 || interp > 3) return fail(AUKIT_E_ARG, "invalid interpolation");
     if (dtype != AUKIT_I8 && dtype != AUKIT_F64) return fail(AUKIT_E_ARG, "stream.msadpcm output must be AUKIT_I8 or AUKIT_F64");
     MsBlocks B;
-    int rc = ms_count_blocks(in, d, B);
+    int rc = ms_count_blocks(in, d, B, true);
     if (rc) return rc;
     std::vector<unsigned char> first_byte;
     hipStream_t scan_stream = nullptr;

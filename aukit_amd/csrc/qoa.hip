@@ -49,11 +49,11 @@ struct QoaFillIn { unsigned long long job_first, call_first, row_base, stride; }
 struct QoaCallRec { unsigned long long row0; unsigned stride, n, sample_pos, pad; };
 static_assert(sizeof(QoaWalkOut) == 56 && sizeof(QoaFillIn) == 32 && sizeof(QoaCallRec) == 24, "walk records");
 
-struct QoaCallWalk { unsigned long long end_pos, n, sample_pos; unsigned nframes; bool raised, big; };
+struct QoaCallWalk { unsigned long long end_pos, n, sample_pos; unsigned nframes, lastnz; bool raised, big; };   // lastnz: the last frame that holds samples, counted from 1 (0: none)
 // one iterator call (mode 1) or the whole file (mode 0) from `pos`; emit(frame_pos, samples, sp) per accepted frame
 template <class Emit>
 static AUKIT_DEV QoaCallWalk qoa_walk_call(const unsigned char *h, unsigned long long nb, unsigned long long pos, int mode, int fc, unsigned fr, double file_samples, Emit emit) {
-    QoaCallWalk w{pos, 0, 0, 0, false, false};
+    QoaCallWalk w{pos, 0, 0, 0, 0, false, false};
     auto header_ok = [&](const unsigned char *f, int &channels, int &samples, int &frame_size) {
         channels = f[0];
         const unsigned rate = (unsigned)f[1] << 16 | (unsigned)f[2] << 8 | f[3];
@@ -89,6 +89,7 @@ static AUKIT_DEV QoaCallWalk qoa_walk_call(const unsigned char *h, unsigned long
         }
         emit(fpos, samples, sp);
         w.nframes++;
+        if (samples > 0) w.lastnz = w.nframes;
         if (samples > 8192) w.big = true;
         const unsigned long long top = sp + (unsigned long long)((samples + 19) / 20) * 20;
         w.n = top > w.n ? top : w.n;
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(64) void k_qoa_walk(const unsigned char *src, const
                 if (mode == 1 && w.n == 0) break;                              // #chunk[1] == 0 → nil
                 const unsigned long long stride = mode == 0 ? (FILL ? fin[s].stride : 0) : ((w.n + 2 + 15) / 16) * 16;
                 if (FILL) {
-                    const unsigned nfr = w.nframes;
+                    const unsigned nfr = w.lastnz;   // frames of zero samples behind it overwrite nothing: its last slice stays whole (:1758-1765)
                     unsigned k = 0;
                     qoa_walk_call(h, nb, pos, mode, fc, fr, file_samples, [&](unsigned long long fpos, int samples, unsigned long long sp) {
                         const bool lastf = ++k == nfr;
@@ -135,7 +136,7 @@ __global__ __launch_bounds__(64) void k_qoa_walk(const unsigned char *src, const
                             QoaJob j;
                             j.frame_off = off[g] + fpos; j.out_off = rat + (unsigned long long)c * stride + sp;
                             j.c = c; j.channels = fc; j.samples = samples;
-                            j.emit = lastf ? ((samples + 19) / 20) * 20 : samples;   // Q15: the ≤19-sample tail survives only after the last frame of a table
+                            j.emit = lastf ? ((samples + 19) / 20) * 20 : samples;   // Q15: the ≤19-sample tail survives only after the last frame of a table that holds samples
                             jobs[jat++] = j;
                         }
                     });
@@ -388,6 +389,7 @@ static int qoa_walk_fill(aukit_ctx *ctx, const aukit_batch *in, int mode, const 
 
 template <bool S8>
 static int qoa_decode_launch(aukit_ctx *ctx, const aukit_batch *in, const QoaJob *djobs, uint64_t njobs, void *rows, uint64_t row_bytes) {
+    ctx->counters[AUKIT_COUNTER_QOA_WAVE] = 1;
     if (!njobs) return AUKIT_OK;
     int rc = ctx_begin_kernel(ctx);
     if (rc) return rc;
@@ -448,6 +450,7 @@ int qoa_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<Qo
         jat += q.njobs; row_elems += q.rows_total;
     }
     int rc = qoa_walk_fill(ctx, in, 0, S, reinterpret_cast<QoaJob *>(djobs), S.size(), nullptr, nullptr, nullptr, true);
+    ctx->counters[AUKIT_COUNTER_QOA_WAVE] = 1;
     if (rc || !jat) return rc;
     if ((rc = ctx_begin_kernel(ctx))) return rc;
     hipLaunchKernelGGL((k_qoa_wave<false>), dim3((unsigned)((jat + 63) / 64)), dim3(64), 0, ctx->stream, in->data(), reinterpret_cast<const QoaJob *>(djobs), (unsigned long long)jat, rows);

@@ -140,6 +140,7 @@ struct QFrame { uint64_t off; int samples; };
 
 // round 2's aukit.stream.qoa: the fallback of qoa.hip (frames of more than 8192 samples, sample rates below ≈ 300 Hz)
 int stream_qoa_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *, int interp, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks_out) {
+    ctx->counters[AUKIT_COUNTER_QOA_WAVE] = 0;
     if (interp < 0 || interp > 3) return fail(AUKIT_E_ARG, "stream.qoa: bad interpolation");
     if (dtype != AUKIT_F64 && dtype != AUKIT_F32) return fail(AUKIT_E_ARG, "stream.qoa output must be AUKIT_F64 or AUKIT_F32");
     if (in->n == 0) return fail(AUKIT_E_ARG, "empty batch");
@@ -209,8 +210,10 @@ int stream_qoa_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_des
             if (n == 0) break;                                                                      // #chunk[1] == 0 → nil
             const uint64_t stride = round_up(n + 2, 8);
             sp = 0;
+            size_t lastnz = frames.size();   // (frames of zero samples behind the last one that holds samples overwrite nothing: codecs2.hip)
+            for (size_t k = 0; k < frames.size(); k++) if (frames[k].samples > 0) lastnz = k;
             for (size_t k = 0; k < frames.size(); k++) {
-                const bool lastf = k + 1 == frames.size();
+                const bool lastf = k == lastnz;
                 for (int c = 0; c < C; c++) {
                     QoaJob j;
                     j.frame_off = in->off[s] + frames[k].off; j.out_off = tot + (uint64_t)c * stride + sp;

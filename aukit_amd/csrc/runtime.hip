@@ -321,7 +321,7 @@ int aukit_ctx_set_option(aukit_ctx *c, int option, int value) {
 
 int aukit_ctx_get_counter(aukit_ctx *c, int counter, uint64_t *value) {
     if (!c || !value) return fail(AUKIT_E_ARG, "null argument");
-    if (counter < 0 || counter >= 8) return fail(AUKIT_E_ARG, "unknown counter %d", counter);
+    if (counter < 0 || counter >= 9) return fail(AUKIT_E_ARG, "unknown counter %d", counter);
     *value = c->counters[counter];
     return AUKIT_OK;
 }

@@ -170,6 +170,8 @@ typedef enum {
     AUKIT_COUNTER_RECURRENCE_F32 = 7,      /* the most recent one-pole filter launch (effects.lowpass / highpass with an owed resample, the stream.qoa / stream.flac tails:
                                               k_rs_onepole) ran its recurrence and scan in f32 (1) or in fp64 (0) — set with or without AUKIT_OPT_COLLECT_STATS */
     AUKIT_COUNTER_DFPWM_HARD = 6,          /* ... and how many streams it gave up on and left to the schedule with one encoder lane per stream (noise-like input) */
+    AUKIT_COUNTER_QOA_WAVE = 8,            /* 1: the most recent QOA decode (aukit.qoa, stream.qoa, the mixed call's QOA pre-pass) ran on k_qoa_wave; 0: a frame of more
+                                              than 8192 samples (or stream.qoa's sinc / rate fallbacks) sent it to the lane-per-job decoders.  Set without COLLECT_STATS. */
     AUKIT_COUNTER_FLAC_FUSED = 2           /* 1: the most recent FLAC decode was served by a fused decoder (k_flac_stream / k_flac_pq); 0: a frame it declines was on
                                               the chain (or the batch is deeper than 24 bits) and the two-kernel decoder ran.  Set without COLLECT_STATS. */
 } aukit_counter;
