@@ -9,10 +9,6 @@
 
 namespace aukit {
 
-int decode_block_codec(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d, double new_rate, int interp, bool do_resample,
-                       int dtype, aukit_audio **out);
-int stream_block_codec(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d, int interp, int mono, int dtype,
-                       aukit_audio **out, aukit_chunks **chunks);
 int launch_stream_pcm_sinc(aukit_ctx *ctx, const std::vector<SincCall> &calls, const SincMap &m, const aukit_batch *in, const aukit_codec_desc *d,
                            bool table, bool mono, int dtype, aukit_audio *a, uint64_t algorithmic_bytes);   // stream_pcm_sinc.hip
 
@@ -397,7 +393,7 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     std::vector<PcmTail> tails;   // the uneven last chunks (AUKIT_OPT_CHANNEL_LENS): stream_pcm_tail.hip behind the segments
     std::vector<uint64_t> lens(in->n, 0);
     uint64_t in_bytes = 0, out_elems = 0;
-    aukit_chunks *ck = new aukit_chunks();
+    ChunksOwner ck = chunks_create(in->n);
     const bool plan_hit = ctx->spcm_ck && ctx->spcm_key == keyb;
     double cp_ratio = 48000 / d->sample_rate;
     // sinc (stream_pcm_sinc.h): one work item per iterator call instead of segments; the cache keeps the map in front of the calls
@@ -425,13 +421,9 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     SincGrid sgrid;
     if (sinc) {
         sm.nd = nd;
-        if (!sinc_grid(d->sample_rate, ctx->sinc_w, sgrid, sm) || sm.K != cp.K) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "stream.pcm with sinc: the lazy tables' read order at %.17g Hz is not modelled", d->sample_rate); }
+        if (!sinc_grid(d->sample_rate, ctx->sinc_w, sgrid, sm) || sm.K != cp.K) return fail(AUKIT_E_UNSUPPORTED, "stream.pcm with sinc: the lazy tables' read order at %.17g Hz is not modelled", d->sample_rate);
     }
 
-    ck->n = in->n;
-    ck->nchunks.assign(in->n, 0);
-    ck->status.assign(in->n, 0);
-    ck->length_seconds.assign(in->n, 0);
     std::vector<std::vector<uint32_t>> clens(in->n);
     std::vector<uint32_t> n_long_ch(in->n, 0);   // != 0: how many of the stream's channels (the first ones) are one output LONGER in its last chunk; clens holds their length
     bool any_uneven = false;
@@ -445,8 +437,8 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         // that ends inside a SAMPLE either way (`string.rep` with a fractional count is the VM's business).
         const int part = (int)((nb / (size_t)bd) % (size_t)C);   // channels the partial frame holds
         if (nb % ((size_t)bd * C) != 0) {
-            if (nb % (size_t)bd != 0) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: data ends inside a sample (stream %u)", s); }
-            if (!mono && !ctx->chan_lens) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: data ends inside a frame and the channels are not mixed down: the reference's last chunk is longer in its first channels (stream %u)", s); }
+            if (nb % (size_t)bd != 0) return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: data ends inside a sample (stream %u)", s);
+            if (!mono && !ctx->chan_lens) return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: data ends inside a frame and the channels are not mixed down: the reference's last chunk is longer in its first channels (stream %u)", s);
         }
         const long long nframes = (long long)(nb / ((size_t)bd * C));
         ck->length_seconds[s] = ((double)(nb + ctx->sb_bytes) / bd) / C / d->sample_rate;  // :2245, :2423 (sb_bytes: what a stream handle has dropped already)
@@ -458,7 +450,7 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
             for (size_t k = first; k < scalls.size(); k++) {
                 const uint32_t n0 = scalls[k].n_out + (scalls[k].pad ? 1 : 0);   // the first table's length; tables pad .. nd-1 have one less
                 if (scalls[k].pad) {
-                    if (k + 1 != scalls.size()) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: an uneven chunk that is not the stream's last (stream %u)", s); }
+                    if (k + 1 != scalls.size()) return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: an uneven chunk that is not the stream's last (stream %u)", s);
                     n_long_ch[s] = scalls[k].pad; any_uneven = true;
                 }
                 scalls[k].out_off = lens[s];
@@ -479,7 +471,7 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
                 // output n_out + 1 and are written before channel `part` raises.  An invariant, not a case: at or below 48 kHz x moves up by at most one
                 // per output and the prefill has read up to iend, so `need` rises by at most one index per output and need[n_out], the first entry above
                 // w_avail, is w_avail + 1 — the check only keeps a plan that broke it from reading past the data
-                if (need[n_out] != (int)w_avail + 1) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: the last chunk's read order at %.17g Hz is not modelled (stream %u)", d->sample_rate, s); }
+                if (need[n_out] != (int)w_avail + 1) return fail(AUKIT_E_UNSUPPORTED, "stream.pcm: the last chunk's read order at %.17g Hz is not modelled (stream %u)", d->sample_rate, s);
                 PcmTail t;
                 t.src_base = src_base;
                 t.w_lo = g.w_lo; t.w_hi = g.w_hi;
@@ -512,22 +504,19 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
             lens[s] += n_out;
             if (n_out < 48000) break;  // ok = false → next call returns nil
         }
-        ck->nchunks[s] = (uint32_t)clens[s].size();
-        ck->max_chunks = std::max<uint32_t>(ck->max_chunks, ck->nchunks[s]);
+        chunks_set_count(*ck, s, (uint32_t)clens[s].size());
         out_elems += lens[s] * (uint64_t)nd;
     }
-    ck->lens.assign((size_t)ck->n * std::max<uint32_t>(ck->max_chunks, 1), 0);
-    ck->pos.assign((size_t)ck->n * std::max<uint32_t>(ck->max_chunks, 1), 0);
+    const size_t mc = chunks_shape(*ck);
     for (uint32_t s = 0; s < in->n; s++) {
         double nacc = (double)ctx->sb_outputs;
         for (uint32_t k = 0; k < ck->nchunks[s]; k++) {
-            ck->lens[(size_t)s * ck->max_chunks + k] = clens[s][k];
-            ck->pos[(size_t)s * ck->max_chunks + k] = nacc / 48000;  // (n - #chunk[1]) / 48000  :2422
+            ck->lens[(size_t)s * mc + k] = clens[s][k];
+            ck->pos[(size_t)s * mc + k] = nacc / 48000;  // (n - #chunk[1]) / 48000  :2422
             nacc += clens[s][k];
         }
     }
     if (any_uneven) {   // every channel's length; only a stream's last chunk differs
-        const size_t mc = std::max<uint32_t>(ck->max_chunks, 1);
         ck->chan_lens.assign((size_t)ck->n * mc * nd, 0);
         for (uint32_t s = 0; s < in->n; s++)
             for (uint32_t k = 0; k < ck->nchunks[s]; k++)
@@ -544,19 +533,19 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     ctx->spcm_segs.assign(reinterpret_cast<const unsigned char *>(segs.data()), reinterpret_cast<const unsigned char *>(segs.data()) + segs.size() * sizeof(Seg));
     ctx->spcm_lens = lens;
     ctx->spcm_in_bytes = in_bytes; ctx->spcm_out_elems = out_elems;
-    if (!ctx->spcm_ck) ctx->spcm_ck = new aukit_chunks();
+    if (!ctx->spcm_ck) ctx->spcm_ck = chunks_create(0);
     *ctx->spcm_ck = *ck;
     }  // (plan)
     aukit_audio *a = *out;
-    if ((rc = audio_prepare(ctx, &a, in->n, nd, 48000, dtype, lens.data()))) { delete ck; return rc; }
+    if ((rc = audio_prepare(ctx, &a, in->n, nd, 48000, dtype, lens.data()))) return rc;
     *out = a;
     if (sinc) {   // every format, the table input and both storage types: one kernel (stream_pcm_sinc.hip)
         for (SincCall &c : scalls) {
             c.out_off += a->row_off[c.stream];
             c.out_stride = (unsigned)a->row_stride[c.stream];
         }
-        if ((rc = launch_stream_pcm_sinc(ctx, scalls, sm, in, d, table, mono != 0, dtype, a, in_bytes + out_elems * dtype_size(dtype)))) { delete ck; return rc; }
-        if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
+        if ((rc = launch_stream_pcm_sinc(ctx, scalls, sm, in, d, table, mono != 0, dtype, a, in_bytes + out_elems * dtype_size(dtype)))) return rc;
+        chunks_deliver(ck, chunks_out);
         return AUKIT_OK;
     }
     for (Seg &g : segs) {
@@ -578,24 +567,24 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     TP.ratio = cp_ratio;
     auto finish = [&]() -> int {   // behind whichever kernel ran the segments: the long channels of the uneven last chunks
         int trc = launch_stream_pcm_tail(ctx, tails, TP, interp, dtype);
-        if (trc) { delete ck; return trc; }
-        if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
+        if (trc) return trc;
+        chunks_deliver(ck, chunks_out);
         return AUKIT_OK;
     };
     int src = table ? SRC_PCM_GENERIC : pick_pcm_source(in, d, false, mono != 0);
     bool done = false;
     if (table) {   // the numbers of a table are not bytes: only the generic staging reads them (reference order, fp64)
         size_t lds;
-        if ((rc = plan_tiles(ctx, segs, cp_ratio, interp, nd, P, &lds))) { delete ck; return rc; }
+        if ((rc = plan_tiles(ctx, segs, cp_ratio, interp, nd, P, &lds))) return rc;
         rc = launch_resample(ctx, src, interp, EPI_STREAM_PCM, dtype, P, lds, in_bytes + out_elems * dtype_size(dtype), nullptr);
-        if (rc) { delete ck; return rc; }
+        if (rc) return rc;
         done = true;
     }
     if (!done)
     if (dtype == AUKIT_F32 && src == SRC_PCM_S16LE_MONO && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {  // f32 tolerance path
         int frc = AUKIT_OK;
         done = fast_try(ctx, src, interp, d->sample_rate, 48000, segs, P, in_bytes + out_elems * 4, &frc, 1, P.lp_alpha);
-        if (done && frc) { delete ck; return frc; }
+        if (done && frc) return frc;
     }
     if (!done && dtype == AUKIT_F32 && C == 2 && bd == 2 && d->data_type == AUKIT_SIGNED && !d->big_endian && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {
         // interleaved 16-bit stereo (nearly every WAV file): both channels, or averaged as they are read when `mono`
@@ -603,19 +592,19 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         for (uint32_t s = 0; s < in->n && aligned4; s++) aligned4 = (in->off[s] & 3) == 0;
         int frc = AUKIT_OK;
         if (aligned4) done = fast_try(ctx, SRC_PCM_S16LE_STEREO, interp, d->sample_rate, 48000, segs, P, in_bytes + out_elems * 4, &frc, mono ? 2 : 1, P.lp_alpha);
-        if (done && frc) { delete ck; return frc; }
+        if (done && frc) return frc;
     }
     if (!done && dtype == AUKIT_F32 && C == 1 && bd == 1 && d->data_type != AUKIT_FLOAT && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {
         int frc = AUKIT_OK;  // 8-bit mono: the wave kernel reads the bytes themselves (fast_stream_u8.hip)
         done = fast_try(ctx, SRC_PCM8_MONO, interp, d->sample_rate, 48000, segs, P, in_bytes + out_elems * 4, &frc, 1, P.lp_alpha);
-        if (done && frc) { delete ck; return frc; }
+        if (done && frc) return frc;
     }
     if (!done && dtype == AUKIT_F32 && !ctx->exact_math && C <= 2 && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {
         // every other interleaved format of one or two channels: unpack + resample + the stream.pcm epilogue in one launch (fast_fmt.hip, round 3)
         int frc = AUKIT_OK;
         const int *unused = nullptr;
         done = fast_fmt_try(ctx, d, interp, 48000, segs, P, in_bytes + out_elems * 4, &frc, &unused, (mono && C > 1) ? 2 : 1, P.lp_alpha);
-        if (done && frc) { delete ck; return frc; }
+        if (done && frc) return frc;
     }
     if (!done && dtype == AUKIT_F32 && !ctx->exact_math && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {
         // every other PCM format (8-bit unsigned at 48 kHz is what most ComputerCraft audio is kept in), f32 tolerance path: the string is
@@ -649,7 +638,7 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
             (rc = upload_table(ctx, ctx->misc_buf, roff.data(), roff.size() * sizeof(uint64_t))) == AUKIT_OK) {
             const UnpackRow *d_ur = reinterpret_cast<const UnpackRow *>(ctx->tmp_buf2.p);
             const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((longest / 4 + 255) / 256 / 4, 64));
-            if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
+            if ((rc = ctx_begin_kernel(ctx))) return rc;
             for (size_t first = 0; first < ur.size(); first += 65535) {
                 const dim3 grid(gx, (unsigned)std::min<size_t>(65535, ur.size() - first));
                 float *rows = reinterpret_cast<float *>(ctx->tmp_buf.p);
@@ -658,8 +647,8 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
                 else if (bd == 3) hipLaunchKernelGGL((k_pcm_unpack<3, float>), grid, dim3(256), 0, ctx->stream, in->data(), d_ur + first, rows, d->data_type, d->big_endian ? 1 : 0);
                 else hipLaunchKernelGGL((k_pcm_unpack<4, float>), grid, dim3(256), 0, ctx->stream, in->data(), d_ur + first, rows, d->data_type, d->big_endian ? 1 : 0);
             }
-            if (hipGetLastError() != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "k_pcm_unpack launch failed"); }
-            if ((rc = ctx_end_kernel(ctx, "k_pcm_unpack", in_bytes + tot * 4))) { delete ck; return rc; }
+            if (hipGetLastError() != hipSuccess) return fail(AUKIT_E_HIP, "k_pcm_unpack launch failed");
+            if ((rc = ctx_end_kernel(ctx, "k_pcm_unpack", in_bytes + tot * 4))) return rc;
             ResampleParams R;
             memset(&R, 0, sizeof R);
             R.src = reinterpret_cast<const unsigned char *>(ctx->tmp_buf.p);
@@ -671,25 +660,25 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
             R.safe_hi = R.src + ctx->tmp_buf.cap;
             int frc = AUKIT_OK;
             done = fast_try(ctx, SRC_AUDIO_F32, interp, d->sample_rate, 48000, rsegs, R, in_bytes + out_elems * 4, &frc, 1, P.lp_alpha);
-            if (done && frc) { delete ck; return frc; }
-        } else if (rc) { delete ck; return rc; }
+            if (done && frc) return frc;
+        } else if (rc) return rc;
     }
     if (!done && ctx->exact_math == 1 && dtype == AUKIT_F32 && src == SRC_PCM_S16LE_MONO && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {
         // AUKIT_OPT_EXACT_MATH = 1: fp64 arithmetic behind the f32 store, phase-weight table (wave_f64.hip with the stream.pcm epilogue)
         int wrc = AUKIT_OK;
         done = wave_f64_try(ctx, src, interp, d->sample_rate, 48000, segs, P, in_bytes + out_elems * 4, &wrc, 1, P.lp_alpha);
-        if (done && wrc) { delete ck; return wrc; }
+        if (done && wrc) return wrc;
     }
     if (!done && src == SRC_PCM_S16LE_MONO && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {  // reference order, wave tiles
         int erc = AUKIT_OK;
         done = exact_wave_try(ctx, src, interp, d->sample_rate, 48000, segs, P, dtype, in_bytes + out_elems * dtype_size(dtype), &erc, 1);
-        if (done && erc) { delete ck; return erc; }
+        if (done && erc) return erc;
     }
     if (!done) {
         size_t lds;
-        if ((rc = plan_tiles(ctx, segs, cp_ratio, interp, nd, P, &lds))) { delete ck; return rc; }
+        if ((rc = plan_tiles(ctx, segs, cp_ratio, interp, nd, P, &lds))) return rc;
         rc = launch_resample(ctx, src, interp, EPI_STREAM_PCM, dtype, P, lds, in_bytes + out_elems * dtype_size(dtype), nullptr);
-        if (rc) { delete ck; return rc; }
+        if (rc) return rc;
     }
     return finish();
 }
@@ -746,11 +735,7 @@ static int stream_g711(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_
     const double ratio = 48000 / d->sample_rate;
     const uint64_t per_call = (uint64_t)d->sample_rate * (uint64_t)C;
     const int nd = mono ? 1 : C;
-    aukit_chunks *ck = new aukit_chunks();
-    ck->n = in->n;
-    ck->nchunks.assign(in->n, 0);
-    ck->status.assign(in->n, 0);
-    ck->length_seconds.assign(in->n, 0);
+    ChunksOwner ck = chunks_create(in->n);
     std::vector<uint64_t> lens(in->n, 0);
     std::vector<Seg> segs;
     uint64_t in_bytes = 0, out_elems = 0;
@@ -761,16 +746,14 @@ static int stream_g711(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_
         // nil in the shorter channels — "attempt to perform arithmetic on a nil value" out of the iterator itself (nothing catches it, :2898-2909):
         // the calls before it deliver their chunks, that call raises.  (Above 48 kHz the last outputs stop short of the last sample: not modelled.)
         const bool ragged = nb % (uint64_t)C != 0;
-        if (ragged && ratio < 1) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "G.711 data length is not a multiple of the channel count at a rate above 48 kHz (stream %u)", s); }
+        if (ragged && ratio < 1) return fail(AUKIT_E_UNSUPPORTED, "G.711 data length is not a multiple of the channel count at a rate above 48 kHz (stream %u)", s);
         ck->length_seconds[s] = (double)(nb + ctx->sb_bytes) / d->sample_rate / C;
         in_bytes += nb;
         uint32_t calls = (uint32_t)((nb + per_call - 1) / per_call);  // calls that see data; the reference then returns {{}} forever (Q13)
         if (ragged) { calls--; ck->status[s] = AUKIT_E_LUA; }
-        ck->nchunks[s] = calls;
-        ck->max_chunks = std::max(ck->max_chunks, calls);
+        chunks_set_count(*ck, s, calls);
     }
-    ck->lens.assign((size_t)ck->n * std::max<uint32_t>(ck->max_chunks, 1), 0);
-    ck->pos.assign((size_t)ck->n * std::max<uint32_t>(ck->max_chunks, 1), 0);
+    const size_t mc = chunks_shape(*ck);
     for (uint32_t s = 0; s < in->n; s++) {
         uint64_t nb = in->off[s + 1] - in->off[s];
         for (uint32_t k = 0; k < ck->nchunks[s]; k++) {
@@ -788,15 +771,15 @@ static int stream_g711(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_
             g.out_stride = 0;
             g.pad = 0;
             segs.push_back(g);
-            ck->lens[(size_t)s * ck->max_chunks + k] = n_out;
-            ck->pos[(size_t)s * ck->max_chunks + k] = ((double)(pos + ctx->sb_bytes + 1) - 1) / d->sample_rate / C;  // (lp - 1) / sampleRate / channels
+            ck->lens[(size_t)s * mc + k] = n_out;
+            ck->pos[(size_t)s * mc + k] = ((double)(pos + ctx->sb_bytes + 1) - 1) / d->sample_rate / C;  // (lp - 1) / sampleRate / channels
             lens[s] += n_out;
         }
         out_elems += lens[s] * (uint64_t)nd;
     }
     int rc;
     aukit_audio *a = *out;
-    if ((rc = audio_prepare(ctx, &a, in->n, nd, 48000, dtype, lens.data()))) { delete ck; return rc; }
+    if ((rc = audio_prepare(ctx, &a, in->n, nd, 48000, dtype, lens.data()))) return rc;
     *out = a;
     for (Seg &g : segs) {
         g.out_off += a->row_off[g.stream];
@@ -812,7 +795,7 @@ static int stream_g711(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_
     if (C == 1 && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {  // guarded short-cut under the floor(), bit-exact (floor_wave.hip)
         int frc = AUKIT_OK;
         done = floor_wave_g711_try(ctx, interp, d->sample_rate, segs, P, dtype, in_bytes + out_elems * dtype_size(dtype), &frc);
-        if (done && frc) { delete ck; return frc; }
+        if (done && frc) return frc;
     }
     if (!done && C >= 2 && !mono && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC) && !ctx->exact_math && !getenv("AUKIT_G711_NO_PLANAR") && in->n) {
         // planar byte rows, then the mono floor kernel on n * C rows (k_deinterleave_bytes above)
@@ -823,9 +806,9 @@ static int stream_g711(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_
             for (int c = 0; c < C; c++) { roff[(size_t)s * C + c] = tot; tot += (fr + 15) & ~15ull; }
         }
         const size_t tab_at = (size_t)((tot + 16 + 255) & ~255ull);
-        if ((rc = ctx->tmp_buf2.ensure(tab_at + roff.size() * 8))) { delete ck; return rc; }
+        if ((rc = ctx->tmp_buf2.ensure(tab_at + roff.size() * 8))) return rc;
         unsigned char *pl = reinterpret_cast<unsigned char *>(ctx->tmp_buf2.p);
-        if ((rc = h2d_table(ctx, pl + tab_at, roff.data(), roff.size() * 8))) { delete ck; return rc; }
+        if ((rc = h2d_table(ctx, pl + tab_at, roff.data(), roff.size() * 8))) return rc;
         uint64_t maxfr = 0;
         for (uint32_t s = 0; s < in->n; s++) maxfr = std::max<uint64_t>(maxfr, (in->off[s + 1] - in->off[s]) / (uint64_t)C);
         const unsigned gx = (unsigned)std::min<uint64_t>(std::max<uint64_t>((maxfr / 4 + 255) / 256, 1), 64);
@@ -835,7 +818,7 @@ static int stream_g711(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_
         else
         hipLaunchKernelGGL(k_deinterleave_bytes, dim3(gx, in->n * (unsigned)C), dim3(256), 0, ctx->stream, in->data(), reinterpret_cast<const unsigned long long *>(in->d_off),
                            reinterpret_cast<const unsigned long long *>(pl + tab_at), C, pl);
-        if (hipGetLastError() != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "k_deinterleave_bytes launch failed"); }
+        if (hipGetLastError() != hipSuccess) return fail(AUKIT_E_HIP, "k_deinterleave_bytes launch failed");
         std::vector<Seg> ps;
         ps.reserve(segs.size() * C);
         for (const Seg &g : segs)
@@ -854,15 +837,15 @@ static int stream_g711(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_
         Q.channels = 1;
         int frc = AUKIT_OK;
         done = floor_wave_g711_try(ctx, interp, d->sample_rate, ps, Q, dtype, in_bytes + out_elems * dtype_size(dtype), &frc);
-        if (done && frc) { delete ck; return frc; }
+        if (done && frc) return frc;
     }
     if (!done) {
         size_t lds;
-        if ((rc = plan_tiles(ctx, segs, ratio, interp, C, P, &lds))) { delete ck; return rc; }
+        if ((rc = plan_tiles(ctx, segs, ratio, interp, C, P, &lds))) return rc;
         rc = launch_resample(ctx, C == 1 ? SRC_G711_MONO : SRC_G711, interp, EPI_STREAM_FLOOR, dtype, P, lds, in_bytes + out_elems * dtype_size(dtype), nullptr);
-        if (rc) { delete ck; return rc; }
+        if (rc) return rc;
     }
-    if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
+    chunks_deliver(ck, chunks_out);
     return AUKIT_OK;
 }
 

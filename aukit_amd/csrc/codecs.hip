@@ -17,10 +17,6 @@
 
 namespace aukit {
 
-int audio_from_int_rows(aukit_ctx *ctx, int src_kind, const void *rows_dev, const std::vector<uint64_t> &row_off, const std::vector<uint64_t> &row_len,
-                        uint32_t n, int channels, double rate, double new_rate, int interp, bool do_resample, int dtype, double norm_pos,
-                        double norm_neg, aukit_audio **out);
-
 // ================================================================= DFPWM1a
 // aukit.dfpwm  aukit.lua:1399-1412: 6001-byte slices advanced by 6000 (Q10); output de-interleaved int8 rows
 __global__ __launch_bounds__(64) void k_dfpwm_decode(const unsigned char *src, const unsigned long long *off, unsigned n, int C,
@@ -1414,11 +1410,7 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     const double ratio = G.ratio, spb = G.spb;
     const uint32_t newlen_full = (uint32_t)G.newlen_full;
     const int nd = mono ? 1 : C;
-    aukit_chunks *ck = new aukit_chunks();
-    ck->n = in->n;
-    ck->nchunks.assign(in->n, 0);
-    ck->status.assign(in->n, 0);
-    ck->length_seconds.assign(in->n, 0);
+    ChunksOwner ck = chunks_create(in->n);
     std::vector<uint64_t> lens(in->n, 0), blk0(in->n + 1, 0);
     std::vector<unsigned> first_bad(in->n, 0xFFFFFFFFu);
     hipStream_t scan_stream = ctx->stream;
@@ -1426,16 +1418,16 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         // (round 6, late: on the look-ahead stream — the scan reads the input batch and nothing else, and its host wait was a wait for everything the call
         // BEFORE had left on ctx->stream: back-to-back calls now plan while the kernel of the call before runs)
         int prc = ctx_pre_stream(ctx, &scan_stream);
-        if (prc) { delete ck; return prc; }
-        if (in->ready && hipStreamWaitEvent(scan_stream, in->ready, 0) != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "hipStreamWaitEvent failed"); }
+        if (prc) return prc;
+        if (in->ready && hipStreamWaitEvent(scan_stream, in->ready, 0) != hipSuccess) return fail(AUKIT_E_HIP, "hipStreamWaitEvent failed");
         DevBuf &sb = ctx->scan_buf;
         int rc0 = sb.ensure((size_t)in->n * 4 + 16);
-        if (rc0) { delete ck; return rc0; }
+        if (rc0) return rc0;
         unsigned *dfb = reinterpret_cast<unsigned *>(sb.p);
         hipLaunchKernelGGL(k_ima_scan_headers, dim3(in->n), dim3(64), 0, scan_stream, in->data(), reinterpret_cast<const unsigned long long *>(in->d_off), in->n, C,
                            (unsigned long long)ba, dfb);
         if (hipGetLastError() != hipSuccess || hipMemcpyAsync(first_bad.data(), dfb, (size_t)in->n * 4, hipMemcpyDeviceToHost, scan_stream) != hipSuccess) {
-            delete ck; return fail(AUKIT_E_HIP, "stream.adpcm header scan failed");
+            return fail(AUKIT_E_HIP, "stream.adpcm header scan failed");
         }
     }
     // The iterator calls of one stream depend on its byte count and on where a bad header stops it: one plan per distinct pair.
@@ -1469,7 +1461,7 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         }
         plan_of[s] = last;
     }
-    if (in->n && hipStreamSynchronize(scan_stream) != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "stream.adpcm header scan failed"); }
+    if (in->n && hipStreamSynchronize(scan_stream) != hipSuccess) return fail(AUKIT_E_HIP, "stream.adpcm header scan failed");
     for (uint32_t s = 0; s < in->n; s++) {
         const uint64_t nb = in->off[s + 1] - in->off[s];
         ck->length_seconds[s] = (double)(nb + ctx->sb_bytes) / (double)ba * spb / d->sample_rate;   // :2834
@@ -1484,12 +1476,9 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         const Plan &pl = *plan_of[s];
         blk0[s + 1] = blk0[s] + pl.blocks;
         lens[s] = pl.total;
-        ck->nchunks[s] = (uint32_t)pl.len.size();
-        ck->max_chunks = std::max<uint32_t>(ck->max_chunks, ck->nchunks[s]);
+        chunks_set_count(*ck, s, (uint32_t)pl.len.size());
     }
-    const uint32_t mc = std::max<uint32_t>(ck->max_chunks, 1);
-    ck->lens.assign((size_t)ck->n * mc, 0);
-    ck->pos.assign((size_t)ck->n * mc, 0);
+    const uint32_t mc = chunks_shape(*ck);
     for (uint32_t s = 0; s < in->n; s++) {
         const Plan &pl = *plan_of[s];
         if (!pl.len.empty()) {
@@ -1499,7 +1488,7 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     }
     int rc;
     aukit_audio *a = *out;
-    if ((rc = audio_prepare(ctx, &a, in->n, nd, 48000, dtype, lens.data()))) { delete ck; return rc; }
+    if ((rc = audio_prepare(ctx, &a, in->n, nd, 48000, dtype, lens.data()))) return rc;
     *out = a;
     const uint64_t nblocks = blk0[in->n];
     if (nblocks) {
@@ -1507,7 +1496,7 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         tab.insert(tab.end(), a->row_off.begin(), a->row_off.end());
         tab.insert(tab.end(), a->row_stride.begin(), a->row_stride.end());
         tab.push_back(0);
-        if ((rc = upload_table(ctx, ctx->tmp_buf2, tab.data(), tab.size() * 8))) { delete ck; return rc; }
+        if ((rc = upload_table(ctx, ctx->tmp_buf2, tab.data(), tab.size() * 8))) return rc;
         const unsigned long long *t = reinterpret_cast<const unsigned long long *>(ctx->tmp_buf2.p);
         int *err = reinterpret_cast<int *>(const_cast<unsigned long long *>(t + tab.size() - 1));
         ImaStreamParams P{};
@@ -1548,7 +1537,7 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
                 }
             }
             DevBuf &S3 = ctx_scratch3(ctx);
-            if ((rc = upload_table(ctx, S3, w.data(), w.size() * 4))) { delete ck; return rc; }
+            if ((rc = upload_table(ctx, S3, w.data(), w.size() * 4))) return rc;
             P.bps = 0;
             if (in->n) {
                 const uint64_t b1 = blk0[1] - blk0[0];
@@ -1563,7 +1552,7 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
                 const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));
                 const unsigned gmul = 8;   // 1 / 2 / 4 / 8 / 16 / 32 measured 2.98 / 2.83 / 2.74 / 2.71 / 2.72 / 2.74 ms on config 3a
                 const unsigned grid = (unsigned)std::min<uint64_t>((nblocks + 3) / 4, (uint64_t)ctx->num_cus * per_cu * gmul);
-                if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
+                if ((rc = ctx_begin_kernel(ctx))) return rc;
                 const float *wgp = reinterpret_cast<const float *>(S3.p);
                 // the phases in registers when a lane meets 3 or 5 of them (fb = 3 · 2^i or 5 · 2^i, i <= 6: 22 050 and 44 100 Hz have 5)
                 unsigned g64 = P.fb, h64 = 64;
@@ -1572,7 +1561,7 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
                 if (ph != 3 && ph != 5) ph = 0;
                 P.audit = nullptr;
                 if (ctx->collect_stats) {   // the audited instantiation (floor_wave.hip): tier 1's values against tier 2's, every output
-                    if ((rc = ctx->fmt_flag.ensure(64))) { delete ck; return rc; }
+                    if ((rc = ctx->fmt_flag.ensure(64))) return rc;
                     P.audit = reinterpret_cast<unsigned *>(ctx->fmt_flag.p) + 8;
                     AUKIT_HIP_CHECK(hipMemsetAsync(P.audit, 0, 8, ctx->stream));
                     ph = 0;
@@ -1585,10 +1574,10 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
                 if (dtype == AUKIT_I8) { if (interp == AUKIT_INTERP_LINEAR) AUKIT_IMA_F32(AUKIT_INTERP_LINEAR, signed char); else AUKIT_IMA_F32(AUKIT_INTERP_CUBIC, signed char); }
                 else { if (interp == AUKIT_INTERP_LINEAR) AUKIT_IMA_F32(AUKIT_INTERP_LINEAR, double); else AUKIT_IMA_F32(AUKIT_INTERP_CUBIC, double); }
 #undef AUKIT_IMA_F32
-                if (hipGetLastError() != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "k_ima_stream_f32 launch failed"); }
+                if (hipGetLastError() != hipSuccess) return fail(AUKIT_E_HIP, "k_ima_stream_f32 launch failed");
                 uint64_t out_elems = 0;
                 for (uint64_t l : lens) out_elems += l * nd;
-                if ((rc = ctx_end_kernel(ctx, "k_ima_stream_f32", in->total() + out_elems * dtype_size(dtype)))) { delete ck; return rc; }
+                if ((rc = ctx_end_kernel(ctx, "k_ima_stream_f32", in->total() + out_elems * dtype_size(dtype)))) return rc;
                 // (the plans end in front of the first block whose header index is above 88 — k_ima_scan_headers —: the kernel's own flag for such a block cannot
                 // be raised by a planned block.  Waiting for it kept the host behind every call's kernel; the audited runs wait and look)
                 int herr = 0;
@@ -1601,8 +1590,8 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
                     ctx->counters[AUKIT_COUNTER_TIER1_ERR_NANO] = (uint64_t)std::llround((double)e * 1e9);
                     ctx->counters[AUKIT_COUNTER_TIER1_OUTPUTS] = h[1];
                 }
-                if (herr) { delete ck; return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (field '?')"); }  // ima_step_table[idx > 88]
-                if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
+                if (herr) return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (field '?')");  // ima_step_table[idx > 88]
+                chunks_deliver(ck, chunks_out);
                 return AUKIT_OK;
             }
         }
@@ -1611,30 +1600,25 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         const size_t lds = (size_t)P.cap * C * 8 * nwv;
         // one wave per block and the CU's whole 160 KiB (less what the kernel declares itself): blockAlign x channels up to ~10 KiB — every WAV
         // encoder's blocks; the reference has no limit at all, a block-at-a-time path for more than that does not exist here
-        if (lds > 156 * 1024) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "blockAlign %d with %d channels needs more than 156 KiB of LDS", d->block_align, C); }
+        if (lds > 156 * 1024) return fail(AUKIT_E_UNSUPPORTED, "blockAlign %d with %d channels needs more than 156 KiB of LDS", d->block_align, C);
         unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(32 / nwv, (160 * 1024) / lds));
         unsigned grid = (unsigned)std::min<uint64_t>((nblocks + nwv - 1) / nwv, (uint64_t)ctx->num_cus * per_cu * 2);
-        if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
+        if ((rc = ctx_begin_kernel(ctx))) return rc;
         rc = dtype == AUKIT_I8 ? launch_ima_stream<signed char>(ctx, interp, P, grid, lds, nwv * 64) : launch_ima_stream<double>(ctx, interp, P, grid, lds, nwv * 64);
-        if (rc) { delete ck; return rc; }
+        if (rc) return rc;
         uint64_t out_elems = 0;
         for (uint64_t l : lens) out_elems += l * nd;
-        if ((rc = ctx_end_kernel(ctx, "k_ima_stream", in->total() + out_elems * dtype_size(dtype)))) { delete ck; return rc; }
+        if ((rc = ctx_end_kernel(ctx, "k_ima_stream", in->total() + out_elems * dtype_size(dtype)))) return rc;
         int herr = 0;
         AUKIT_HIP_CHECK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, ctx->stream));
         AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (herr) { delete ck; return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (field '?')"); }  // ima_step_table[idx > 88]
+        if (herr) return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (field '?')");  // ima_step_table[idx > 88]
     }
-    if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
+    chunks_deliver(ck, chunks_out);
     return AUKIT_OK;
 }
 
 // ================================================================= dispatch
-int decode_msadpcm_audio(aukit_ctx *, const aukit_batch *, const aukit_codec_desc *, double, int, bool, int, aukit_audio **);
-int decode_qoa_audio(aukit_ctx *, const aukit_batch *, const aukit_codec_desc *, double, int, bool, int, aukit_audio **);
-int decode_flac_audio(aukit_ctx *, const aukit_batch *, const aukit_codec_desc *, double, int, bool, int, aukit_audio **);
-int decode_mdfpwm_audio(aukit_ctx *, const aukit_batch *, const aukit_codec_desc *, double, int, bool, int, aukit_audio **);
-
 int decode_block_codec(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d, double new_rate, int interp, bool do_resample, int dtype,
                        aukit_audio **out) {
     switch (d->codec) {
@@ -1648,8 +1632,6 @@ int decode_block_codec(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_
     }
     return fail(AUKIT_E_ARG, "unknown codec %d", d->codec);
 }
-
-int stream_more_codecs(aukit_ctx *, const aukit_batch *, const aukit_codec_desc *, int, int, int, aukit_audio **, aukit_chunks **);
 
 int stream_block_codec(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d, int interp, int mono, int dtype, aukit_audio **out,
                        aukit_chunks **chunks) {

@@ -8,12 +8,6 @@
 
 namespace aukit {
 
-int audio_from_int_rows(aukit_ctx *ctx, int src_kind, const void *rows_dev, const std::vector<uint64_t> &row_off, const std::vector<uint64_t> &row_len,
-                        uint32_t n, int channels, double rate, double new_rate, int interp, bool do_resample, int dtype, double norm_pos,
-                        double norm_neg, aukit_audio **out);
-
-int stream_msadpcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d, int interp, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks);  // msadpcm.hip
-
 // ================================================================= QOA
 __constant__ int c_qoa_dequant[16][8] = {
     {1, -1, 3, -3, 5, -5, 7, -7}, {5, -5, 18, -18, 32, -32, 49, -49}, {16, -16, 53, -53, 95, -95, 147, -147},
@@ -429,9 +423,7 @@ static int stream_dfpwm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
     const uint64_t adv = 6000ull * C, slice = adv + 1;
     const double ratio = 48000 / d->sample_rate;
     const int nd = mono ? 1 : C;
-    aukit_chunks *ck = new aukit_chunks();
-    ck->n = in->n;
-    ck->nchunks.assign(in->n, 0); ck->status.assign(in->n, 0); ck->length_seconds.assign(in->n, 0);
+    ChunksOwner ck = chunks_create(in->n);
     std::vector<uint64_t> lens(in->n, 0), rowo(in->n, 0);
     std::vector<Seg> segs;
     std::vector<std::vector<uint32_t>> clen(in->n);
@@ -454,13 +446,10 @@ static int stream_dfpwm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
             lens[s] += m;
             fed += na;
         }
-        ck->nchunks[s] = (uint32_t)clen[s].size();
-        ck->max_chunks = std::max(ck->max_chunks, ck->nchunks[s]);
+        chunks_set_count(*ck, s, (uint32_t)clen[s].size());
         tot += round_up(fed + 1, 16);
     }
-    const uint32_t mc = std::max<uint32_t>(ck->max_chunks, 1);
-    ck->lens.assign((size_t)ck->n * mc, 0);
-    ck->pos.assign((size_t)ck->n * mc, 0);
+    const uint32_t mc = chunks_shape(*ck);
     for (uint32_t s = 0; s < in->n; s++)
         for (uint32_t k = 0; k < ck->nchunks[s]; k++) {
             ck->lens[(size_t)s * mc + k] = clen[s][k];
@@ -468,16 +457,16 @@ static int stream_dfpwm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
         }
     int rc;
     aukit_audio *a = *out;
-    if ((rc = audio_prepare(ctx, &a, in->n, nd, 48000, dtype, lens.data()))) { delete ck; return rc; }
+    if ((rc = audio_prepare(ctx, &a, in->n, nd, 48000, dtype, lens.data()))) return rc;
     *out = a;
     for (Seg &g : segs) { g.out_off += a->row_off[g.stream]; g.out_stride = (unsigned)a->row_stride[g.stream]; }
     if (in->n && !segs.empty()) {
-        if ((rc = ctx->tmp_buf.ensure((size_t)tot + 64))) { delete ck; return rc; }
-        if ((rc = upload_table(ctx, ctx->misc_buf, rowo.data(), rowo.size() * 8))) { delete ck; return rc; }
+        if ((rc = ctx->tmp_buf.ensure((size_t)tot + 64))) return rc;
+        if ((rc = upload_table(ctx, ctx->misc_buf, rowo.data(), rowo.size() * 8))) return rc;
         int prc = AUKIT_OK;
         const unsigned long long *d_rowo = reinterpret_cast<const unsigned long long *>(ctx->misc_buf.p);
         if (dfpwm_decode_parallel(ctx, in, 0, 1, reinterpret_cast<signed char *>(ctx->tmp_buf.p), d_rowo, nullptr, &prc, (uint64_t)adv, 1)) {  // chunk-parallel, exact (dfpwm_par.hip)
-            if (prc) { delete ck; return prc; }
+            if (prc) return prc;
             hipLaunchKernelGGL(k_row_heads_zero, dim3((in->n + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<signed char *>(ctx->tmp_buf.p), d_rowo, in->n,
                                ctx->sb_dfpwm_on ? ctx->sb_dfpwm[3] : 0);  // audio[0] of the first chunk = `last` = 0 (or the last sample in front of the rest of a stream)
         } else {
@@ -489,9 +478,9 @@ static int stream_dfpwm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
         }
         AUKIT_HIP_CHECK(hipGetLastError());
         if (d->sample_rate == 48000) {  // ratio 1: a strided copy (k_dfpwm_stream_copy)
-            if ((rc = upload_table(ctx, ctx->seg_buf, segs.data(), segs.size() * sizeof(Seg)))) { delete ck; return rc; }
+            if ((rc = upload_table(ctx, ctx->seg_buf, segs.data(), segs.size() * sizeof(Seg)))) return rc;
             ctx->plan_key.clear();  // (seg_buf no longer holds a resample plan)
-            if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
+            if ((rc = ctx_begin_kernel(ctx))) return rc;
             uint32_t mmax = 0;
             for (const Seg &g : segs) mmax = std::max(mmax, g.n_out);
             const unsigned gx = (unsigned)std::max<uint32_t>(1, std::min<uint32_t>((mmax / 4 + 255) / 256, 64));
@@ -504,8 +493,8 @@ static int stream_dfpwm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
             AUKIT_HIP_CHECK(hipGetLastError());
             uint64_t oe1 = 0;
             for (uint64_t l : lens) oe1 += l * nd;
-            if ((rc = ctx_end_kernel(ctx, "k_dfpwm_stream_copy", in->total() + oe1 * dtype_size(dtype)))) { delete ck; return rc; }
-            if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
+            if ((rc = ctx_end_kernel(ctx, "k_dfpwm_stream_copy", in->total() + oe1 * dtype_size(dtype)))) return rc;
+            chunks_deliver(ck, chunks_out);
             return AUKIT_OK;
         }
         ResampleParams P;
@@ -526,16 +515,16 @@ static int stream_dfpwm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
         if (dtype == AUKIT_F32 && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {   // the wave kernel (fast_stream_dfpwm.hip)
             int wrc = AUKIT_OK;
             took = dfpwm_stream_wave_try(ctx, interp, d->sample_rate, C, nd, mono, segs, P, in->total() + oe * dtype_size(dtype), &wrc);
-            if (took && wrc) { delete ck; return wrc; }
+            if (took && wrc) return wrc;
         }
         if (!took) {
             size_t lds;
-            if ((rc = plan_tiles(ctx, segs, ratio, interp, 1, P, &lds))) { delete ck; return rc; }
+            if ((rc = plan_tiles(ctx, segs, ratio, interp, 1, P, &lds))) return rc;
             rc = launch_resample(ctx, SRC_I8, interp, EPI_STREAM_DFPWM, dtype, P, lds, in->total() + oe * dtype_size(dtype), nullptr);
-            if (rc) { delete ck; return rc; }
+            if (rc) return rc;
         }
     }
-    if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
+    chunks_deliver(ck, chunks_out);
     return AUKIT_OK;
 }
 
@@ -590,9 +579,7 @@ static int stream_mdfpwm(aukit_ctx *ctx, const aukit_batch *in, const aukit_code
     std::vector<uint64_t> row_off, row_len;
     int rc = mdfpwm_rows(ctx, in, "bad argument #1 (invalid MDFPWM data)", hdrs, row_off, row_len);
     if (rc) return rc;
-    aukit_chunks *ck = new aukit_chunks();
-    ck->n = in->n;
-    ck->nchunks.assign(in->n, 0); ck->status.assign(in->n, 0); ck->length_seconds.assign(in->n, 0);
+    ChunksOwner ck = chunks_create(in->n);
     std::vector<uint64_t> lens(in->n, 0);
     for (uint32_t s = 0; s < in->n; s++) {
         const uint64_t pl = in->off[s + 1] - in->off[s] - hdrs[s].payload;
@@ -605,22 +592,19 @@ static int stream_mdfpwm(aukit_ctx *ctx, const aukit_batch *in, const aukit_code
             if (!full || trimmed) { ck->status[s] = mono ? AUKIT_E_LUA : AUKIT_E_UNSUPPORTED; break; }
             good++;
         }
-        ck->nchunks[s] = good;
-        ck->max_chunks = std::max(ck->max_chunks, good);
+        chunks_set_count(*ck, s, good);
         lens[s] = (uint64_t)good * 48000;
     }
-    const uint32_t mc = std::max<uint32_t>(ck->max_chunks, 1);
-    ck->lens.assign((size_t)ck->n * mc, 0);
-    ck->pos.assign((size_t)ck->n * mc, 0);
+    const uint32_t mc = chunks_shape(*ck);
     for (uint32_t s = 0; s < in->n; s++)
         for (uint32_t k = 0; k < ck->nchunks[s]; k++) { ck->lens[(size_t)s * mc + k] = 48000; ck->pos[(size_t)s * mc + k] = (double)(ctx->sb_bytes + 12000ull * k + 1) / 12000; }
     aukit_audio *a = *out;
-    if ((rc = audio_prepare(ctx, &a, in->n, mono ? 1 : 2, 48000, AUKIT_I8, lens.data()))) { delete ck; return rc; }
+    if ((rc = audio_prepare(ctx, &a, in->n, mono ? 1 : 2, 48000, AUKIT_I8, lens.data()))) return rc;
     *out = a;
     if (in->n) {
         std::vector<uint64_t> tab(row_off);
         tab.insert(tab.end(), lens.begin(), lens.end());
-        if ((rc = upload_table(ctx, ctx->misc_buf, tab.data(), tab.size() * 8))) { delete ck; return rc; }
+        if ((rc = upload_table(ctx, ctx->misc_buf, tab.data(), tab.size() * 8))) return rc;
         const unsigned long long *t = reinterpret_cast<const unsigned long long *>(ctx->misc_buf.p);
         const unsigned long long *m = reinterpret_cast<const unsigned long long *>(a->d_meta);
         hipLaunchKernelGGL(k_mdfpwm_chunks, dim3(64, in->n), dim3(256), 0, ctx->stream, reinterpret_cast<const signed char *>(ctx->tmp_buf.p), t, t + 2 * (size_t)in->n,
@@ -628,12 +612,9 @@ static int stream_mdfpwm(aukit_ctx *ctx, const aukit_batch *in, const aukit_code
         AUKIT_HIP_CHECK(hipGetLastError());
         ctx->last_kernel = "k_mdfpwm_chunks";
     }
-    if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
+    chunks_deliver(ck, chunks_out);
     return AUKIT_OK;
 }
-
-int stream_qoa(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d, int interp, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks);
-int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d, int interp, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks);
 
 int stream_more_codecs(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d, int interp, int mono, int dtype, aukit_audio **out,
                        aukit_chunks **chunks) {

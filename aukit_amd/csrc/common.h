@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 #include "../../include/aukit_hip.h"
+#include "chunks.h"
 
 namespace aukit {
 
@@ -131,7 +132,7 @@ struct aukit_ctx {
     std::vector<unsigned char> spcm_tail;   // ... and the work items of the uneven last chunks (stream_pcm_tail.hip), before their row offsets
     std::vector<uint64_t> spcm_lens;
     uint64_t spcm_in_bytes = 0, spcm_out_elems = 0;
-    struct aukit_chunks *spcm_ck = nullptr;
+    aukit::ChunksOwner spcm_ck;   // empty: no plan is cached
     // AUKIT_OPT_COLLECT_STATS: counters of the last call that has any (aukit_ctx_get_counter)
     bool collect_stats = false;
     uint64_t counters[9] = {};
@@ -199,21 +200,6 @@ struct aukit_audio {
     uint64_t lazy_nfr = 0, lazy_tot = 0;
     int lazy_min_bs = 0;                                 // the shortest full-size frame of any stream with more than one (k_rsp's window must fit two)
     size_t lazy_o_fbase = 0, lazy_o_bs0 = 0, lazy_o_rowoff = 0;
-};
-
-struct aukit_chunks {
-    uint32_t n = 0, max_chunks = 0;
-    std::vector<uint32_t> nchunks, lens;
-    std::vector<double> pos, length_seconds;
-    std::vector<int32_t> status;
-    // stream.flac (fused decoder): the byte, relative to the stream's start, behind the last frame of every chunk, and where the first frame starts —
-    // what a bounded reader-function handle cuts at (stream_handle.hip); empty where it is not known
-    std::vector<uint64_t> in_end;
-    std::vector<uint64_t> in_first;
-    // AUKIT_OPT_CHANNEL_LENS: chunk tables per chunk (set by aukit_stream_decode for every codec) and, only where some chunk's channels differ in
-    // length, every channel's: chan_lens[(s * max_chunks + k) * channels + ch].  Empty: every channel has lens[s * max_chunks + k]
-    uint32_t channels = 1;
-    std::vector<uint32_t> chan_lens;
 };
 
 namespace aukit {

@@ -28,11 +28,6 @@
 
 namespace aukit {
 
-int audio_from_int_rows(aukit_ctx *ctx, int src_kind, const void *rows_dev, const std::vector<uint64_t> &row_off, const std::vector<uint64_t> &row_len,
-                        uint32_t n, int channels, double rate, double new_rate, int interp, bool do_resample, int dtype, double norm_pos,
-                        double norm_neg, aukit_audio **out);
-
-
 #ifndef AUKIT_FLAC_WN
 #define AUKIT_FLAC_WN 16
 #endif
@@ -2081,9 +2076,7 @@ int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *,
     const int C = D.channels;
     const double ratio = 48000 / D.rate;                                      // :3154
     const double lp_alpha = 1 - std::exp(-(D.rate / 96000) * 2 * M_PI);       // :3155
-    aukit_chunks *ck = new aukit_chunks();
-    ck->n = in->n;
-    ck->nchunks.assign(in->n, 0); ck->status.assign(in->n, 0); ck->length_seconds.assign(in->n, 0);
+    ChunksOwner ck = chunks_create(in->n);
     std::vector<uint64_t> lens(in->n, 0);
     uint64_t max_nout = 0, sum_nout = 0, njobs = 0;
     const bool brief = !D.brief.empty();
@@ -2125,13 +2118,10 @@ int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *,
                 cpos.push_back(pos);
                 cend.push_back(f > 0 && s < D.frame_end.size() && f - 1 < D.frame_end[s].size() ? (uint64_t)D.frame_end[s][f - 1] : 0ull);
             }
-            ck->nchunks[s] = (uint32_t)clen.size() - first[s];
-            ck->max_chunks = std::max(ck->max_chunks, ck->nchunks[s]);
+            chunks_set_count(*ck, s, (uint32_t)clen.size() - first[s]);
         }
         first[in->n] = (uint32_t)clen.size();
-        const uint32_t mc = std::max<uint32_t>(ck->max_chunks, 1);
-        ck->lens.assign((size_t)ck->n * mc, 0);
-        ck->pos.assign((size_t)ck->n * mc, 0);
+        const uint32_t mc = chunks_shape(*ck);
         for (uint32_t s = 0; s < in->n; s++)
             for (uint32_t k = 0; k < ck->nchunks[s]; k++) { ck->lens[(size_t)s * mc + k] = clen[first[s] + k]; ck->pos[(size_t)s * mc + k] = cpos[first[s] + k]; }
         if (!D.frame_end.empty()) {   // where a bounded handle may cut (stream_handle.hip)
@@ -2144,42 +2134,42 @@ int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *,
         }
     };
     aukit_audio *a = *out;
-    if ((rc = audio_prepare(ctx, &a, in->n, C, 48000, dtype, lens.data()))) { delete ck; return rc; }
+    if ((rc = audio_prepare(ctx, &a, in->n, C, 48000, dtype, lens.data()))) return rc;
     *out = a;
     {   // round 3: jobs written on the device from the decoder's frame records, one launch from the decoded rows (k_iir_tail, stream_tail.hip)
         const int rk = D.wide ? TAIL_ROWS_F64 : TAIL_ROWS_I32;
         const double fullv = std::ldexp(1.0, D.depth);
         if (njobs && D.d_frames && iir_tail_served(ctx, TAIL_FLAC, rk, 1, D.rate, fullv, interp, dtype, max_nout)) {
-            if ((rc = ctx->misc_buf.ensure(njobs * sizeof(TailJob) + (size_t)in->n * 4 + 64))) { delete ck; return rc; }
+            if ((rc = ctx->misc_buf.ensure(njobs * sizeof(TailJob) + (size_t)in->n * 4 + 64))) return rc;
             TailJob *dj = reinterpret_cast<TailJob *>(ctx->misc_buf.p);
             unsigned *dnf = reinterpret_cast<unsigned *>(dj + njobs);
-            if ((rc = h2d_table(ctx, dnf, D.nframes.data(), (size_t)in->n * 4))) { delete ck; return rc; }
+            if ((rc = h2d_table(ctx, dnf, D.nframes.data(), (size_t)in->n * 4))) return rc;
             hipLaunchKernelGGL(k_flac_tail_jobs, dim3((in->n + 63) / 64), dim3(64), 0, ctx->stream, D.d_frames, D.d_fbase, dnf, D.d_rowoff, reinterpret_cast<const u64 *>(a->d_meta), in->n, C,
                                ratio, dj, D.in_scratch ? 1 : 0);
-            if (hipGetLastError() != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "k_flac_tail_jobs launch failed"); }
+            if (hipGetLastError() != hipSuccess) return fail(AUKIT_E_HIP, "k_flac_tail_jobs launch failed");
             int trc = AUKIT_OK;
             if (rk == TAIL_ROWS_I32 && dtype == AUKIT_F32 &&
                 rs_onepole_jobs_try_dev(ctx, D.in_scratch ? ctx->tmp_buf3.p : ctx->tmp_buf.p, fullv, dj, njobs, D.rate, interp, lp_alpha, reinterpret_cast<float *>(a->dev),
                                         in->total() + sum_nout * dtype_size(dtype), "k_rs_onepole<flac>", &trc)) {   // the tile chain of flac_tail.hip (state carried from tile to tile, a workgroup takes frame after frame)
-                if (trc) { delete ck; return trc; }
+                if (trc) return trc;
                 if (brief) frames_from_brief(D);
                 build_chunks();
-                if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
+                chunks_deliver(ck, chunks_out);
                 return AUKIT_OK;
             }
             if (iir_tail_try_dev(ctx, TAIL_FLAC, rk, D.in_scratch ? ctx->tmp_buf3.p : ctx->tmp_buf.p, fullv, dj, njobs, max_nout, sum_nout, 1, D.rate, interp, dtype, a->dev, in->total() + sum_nout * dtype_size(dtype),
                                  "k_iir_tail<flac>", &trc)) {
-                if (trc) { delete ck; return trc; }
+                if (trc) return trc;
                 if (brief) frames_from_brief(D);
                 build_chunks();
-                if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
+                chunks_deliver(ck, chunks_out);
                 return AUKIT_OK;
             }
         }
     }
     if (brief) frames_from_brief(D);
     build_chunks();
-    if ((rc = flac_rows_materialize(ctx, D))) { delete ck; return rc; }
+    if ((rc = flac_rows_materialize(ctx, D))) return rc;
     std::vector<FsJob> jobs;
     uint64_t nouts = 0;
     for (uint32_t s = 0; s < in->n; s++) {
@@ -2205,7 +2195,7 @@ int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *,
         }
     }
     if (!jobs.empty()) {
-        if ((rc = upload_table(ctx, ctx->seg_buf, jobs.data(), jobs.size() * sizeof(FsJob)))) { delete ck; return rc; }
+        if ((rc = upload_table(ctx, ctx->seg_buf, jobs.data(), jobs.size() * sizeof(FsJob)))) return rc;
         const uint64_t maxn = 1ull << 17;
         const int exact = exact_div_verified(ctx, ratio, maxn) ? 1 : 0;
         const unsigned grid = (unsigned)((jobs.size() + 63) / 64);
@@ -2218,14 +2208,14 @@ int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *,
         if (ctx->exact_math == 2 && interp == AUKIT_INTERP_CUBIC && max_nout && max_nout <= maxn) {
             std::vector<double> f3(max_nout);
             for (uint64_t i = 0; i < max_nout; i++) { const double x = (double)i / ratio + 1.0; f3[i] = std::pow(x - std::floor(x), 3); }   // :263, :265
-            if ((rc = upload_table(ctx, ctx->tile_buf, f3.data(), f3.size() * 8))) { delete ck; return rc; }
+            if ((rc = upload_table(ctx, ctx->tile_buf, f3.data(), f3.size() * 8))) return rc;
             f3tab = reinterpret_cast<const double *>(ctx->tile_buf.p);
         }
-        if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
+        if ((rc = ctx_begin_kernel(ctx))) return rc;
         if (scr_elems * 8 <= (48ull << 30) && max_nout) {  // two passes
             DevBuf &S3 = ctx_scratch3(ctx);
-            if ((rc = S3.ensure((size_t)scr_elems * 8 + 64))) { delete ck; return rc; }
-            if ((rc = upload_table(ctx, ctx->misc_buf, scr_off.data(), scr_off.size() * 8))) { delete ck; return rc; }
+            if ((rc = S3.ensure((size_t)scr_elems * 8 + 64))) return rc;
+            if ((rc = upload_table(ctx, ctx->misc_buf, scr_off.data(), scr_off.size() * 8))) return rc;
             const u64 *dso = reinterpret_cast<const u64 *>(ctx->misc_buf.p);
             double *scr = reinterpret_cast<double *>(S3.p);
             for (size_t first = 0; first < jobs.size(); first += 65535) {
@@ -2249,9 +2239,9 @@ int stream_flac(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *,
 #undef AUKIT_FS2
         }
         AUKIT_HIP_CHECK(hipGetLastError());
-        if ((rc = ctx_end_kernel(ctx, "k_flac_stream", in->total() + nouts * dtype_size(dtype)))) { delete ck; return rc; }
+        if ((rc = ctx_end_kernel(ctx, "k_flac_stream", in->total() + nouts * dtype_size(dtype)))) return rc;
     }
-    if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
+    chunks_deliver(ck, chunks_out);
     return AUKIT_OK;
 }
 

@@ -33,10 +33,6 @@ namespace aukit {
 #endif
 constexpr float MS_TIER1_GUARD = AUKIT_MS_TIER1_GUARD;
 
-int audio_from_int_rows(aukit_ctx *ctx, int src_kind, const void *rows_dev, const std::vector<uint64_t> &row_off, const std::vector<uint64_t> &row_len,
-                        uint32_t n, int channels, double rate, double new_rate, int interp, bool do_resample, int dtype, double norm_pos,
-                        double norm_neg, aukit_audio **out);
-
 static AUKIT_DEV double ms_lclamp(double n, double mn, double mx) { return n < mn ? mn : (n > mx ? mx : n); }
 
 __constant__ int c_ms_adapt[16] = {230, 230, 230, 230, 307, 409, 512, 614, 768, 614, 512, 409, 307, 230, 230, 230};  // [0..7], [-8..-1]  :173-176
@@ -1034,20 +1030,15 @@ int stream_msadpcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc
     const uint32_t newlen = (uint32_t)std::max(0.0, std::floor(samplesPerBlock * ratio));
     const uint64_t ips = (uint64_t)ips_d;
     const int nd = (C == 2 && !mono) ? 2 : 1;
-    aukit_chunks *ck = new aukit_chunks();
-    ck->n = in->n;
-    ck->nchunks.assign(in->n, 0); ck->status.assign(in->n, 0); ck->length_seconds.assign(in->n, 0);
+    ChunksOwner ck = chunks_create(in->n);
     std::vector<uint64_t> lens(in->n, 0);
     for (uint32_t s = 0; s < in->n; s++) {
         const uint64_t nb = in->off[s + 1] - in->off[s], nblk = B.blk0[s + 1] - B.blk0[s];
         ck->length_seconds[s] = (double)(nb + ctx->sb_bytes) / (double)ba * samplesPerBlock / d->sample_rate;
-        ck->nchunks[s] = newlen ? (uint32_t)((nblk + ips - 1) / ips) : 0;
-        ck->max_chunks = std::max(ck->max_chunks, ck->nchunks[s]);
+        chunks_set_count(*ck, s, newlen ? (uint32_t)((nblk + ips - 1) / ips) : 0);
         lens[s] = nblk * newlen;
     }
-    const uint32_t mc = std::max<uint32_t>(ck->max_chunks, 1);
-    ck->lens.assign((size_t)ck->n * mc, 0);
-    ck->pos.assign((size_t)ck->n * mc, 0);
+    const uint32_t mc = chunks_shape(*ck);
     for (uint32_t s = 0; s < in->n; s++) {
         const uint64_t nblk = B.blk0[s + 1] - B.blk0[s];
         for (uint32_t k = 0; k < ck->nchunks[s]; k++) {
@@ -1057,9 +1048,9 @@ int stream_msadpcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc
         }
     }
     aukit_audio *a = *out;
-    if ((rc = audio_prepare(ctx, &a, in->n, nd, 48000, dtype, lens.data()))) { delete ck; return rc; }
+    if ((rc = audio_prepare(ctx, &a, in->n, nd, 48000, dtype, lens.data()))) return rc;
     *out = a;
-    auto done = [&]() { if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck; return AUKIT_OK; };
+    auto done = [&]() { chunks_deliver(ck, chunks_out); return AUKIT_OK; };
     const uint64_t nblocks = B.blk0[in->n];
     if (!nblocks || !newlen) return done();
     uint64_t out_elems = 0;
@@ -1127,7 +1118,7 @@ int stream_msadpcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc
         tab.resize(jl_at + jl_words + w_words, 0);
         memcpy(&tab[jl_at], rt.data(), rt.size() * sizeof(MsRound));
         memcpy(&tab[jl_at + jl_words], w.data(), w.size() * 4);
-        if ((rc = upload_table(ctx, ctx->tmp_buf2, tab.data(), tab.size() * 8))) { delete ck; return rc; }
+        if ((rc = upload_table(ctx, ctx->tmp_buf2, tab.data(), tab.size() * 8))) return rc;
         const unsigned long long *t = reinterpret_cast<const unsigned long long *>(ctx->tmp_buf2.p);
         P.src = in->data(); P.safe_hi = in->base + in->cap;
         P.off = reinterpret_cast<const unsigned long long *>(in->d_off);
@@ -1145,18 +1136,18 @@ int stream_msadpcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc
         P.sst = sst;
         P.audit = nullptr;
         if (ctx->collect_stats && dtype == AUKIT_I8 && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {
-            if ((rc = ctx->fmt_flag.ensure(64))) { delete ck; return rc; }
+            if ((rc = ctx->fmt_flag.ensure(64))) return rc;
             P.audit = reinterpret_cast<unsigned *>(ctx->fmt_flag.p) + 8;
-            if (hipMemsetAsync(P.audit, 0, 8, ctx->stream) != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "hipMemsetAsync failed"); }
+            if (hipMemsetAsync(P.audit, 0, 8, ctx->stream) != hipSuccess) return fail(AUKIT_E_HIP, "hipMemsetAsync failed");
         }
         const unsigned grid = (unsigned)((nblocks + 63) / 64);
         bool scanned = false;
         if (scan_stream) {   // the predictor indices of the streams that have a block at all: the reference's error, before anything is decoded
             for (uint32_t s2 = 0; s2 < in->n; s2++)
-                if (B.blk0[s2 + 1] > B.blk0[s2] && (int)first_byte[s2] >= P.ncoef) { delete ck; return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (local 'c1')"); }
+                if (B.blk0[s2 + 1] > B.blk0[s2] && (int)first_byte[s2] >= P.ncoef) return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (local 'c1')");
             scanned = true;
         }
-        if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
+        if ((rc = ctx_begin_kernel(ctx))) return rc;
 #define AUKIT_MS_STREAM(CC, RBB, MIXX)                                                                                                 \
         do {                                                                                                                            \
             if (dtype == AUKIT_I8) ms_launch_stream<CC, RBB, MIXX, signed char>(interp, P, grid, lds, ctx->stream);                    \
@@ -1166,26 +1157,26 @@ int stream_msadpcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc
         else if (mono) AUKIT_MS_STREAM(2, MS_RB, true);
         else AUKIT_MS_STREAM(2, MS_RB, false);
 #undef AUKIT_MS_STREAM
-        if (hipGetLastError() != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "k_ms_wave launch failed"); }
-        if ((rc = ctx_end_kernel(ctx, "k_ms_wave", in->total() + out_elems * dtype_size(dtype)))) { delete ck; return rc; }
+        if (hipGetLastError() != hipSuccess) return fail(AUKIT_E_HIP, "k_ms_wave launch failed");
+        if ((rc = ctx_end_kernel(ctx, "k_ms_wave", in->total() + out_elems * dtype_size(dtype)))) return rc;
         int herr = 0;
         // (scanned: no planned block can raise the kernel's flag — the host looked at every index it will meet)
         if (!scanned || P.audit)
-        if (hipMemcpyAsync(&herr, P.err, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "k_ms_wave failed"); }
+        if (hipMemcpyAsync(&herr, P.err, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(AUKIT_E_HIP, "k_ms_wave failed");
         if (P.audit) {
             unsigned h[2] = {0, 0};
-            if (hipMemcpy(h, P.audit, 8, hipMemcpyDeviceToHost) != hipSuccess) { delete ck; return fail(AUKIT_E_HIP, "audit read-back failed"); }
+            if (hipMemcpy(h, P.audit, 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(AUKIT_E_HIP, "audit read-back failed");
             float e; memcpy(&e, &h[0], 4);
             ctx->counters[AUKIT_COUNTER_TIER1_ERR_NANO] = (uint64_t)std::llround((double)e * 1e9);
             ctx->counters[AUKIT_COUNTER_TIER1_OUTPUTS] = h[1];
         }
-        if (herr) { delete ck; return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (local 'c1')"); }
+        if (herr) return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (local 'c1')");
         return done();
     }
     // ---- generic: rows of doubles, then the segment resampler with its floor epilogue
     std::vector<uint64_t> row_off, row_len, nblk;
     uint64_t spb_chk;
-    if ((rc = msadpcm_rows(ctx, in, d, true, row_off, row_len, nblk, &spb_chk))) { delete ck; return rc; }
+    if ((rc = msadpcm_rows(ctx, in, d, true, row_off, row_len, nblk, &spb_chk))) return rc;
     // one segment per block; its C source rows are consecutive entries of the row table
     std::vector<Seg> segs;
     std::vector<uint64_t> blkrows;
@@ -1205,7 +1196,7 @@ int stream_msadpcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc
         }
     }
     if (!segs.empty()) {
-        if ((rc = upload_table(ctx, ctx->misc_buf, blkrows.data(), blkrows.size() * 8))) { delete ck; return rc; }
+        if ((rc = upload_table(ctx, ctx->misc_buf, blkrows.data(), blkrows.size() * 8))) return rc;
         ResampleParams RP;
         memset(&RP, 0, sizeof RP);
         RP.src = reinterpret_cast<const unsigned char *>(ctx->tmp_buf.p);
@@ -1215,9 +1206,9 @@ int stream_msadpcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc
         RP.sinc_hole = (C == 2 && interp == AUKIT_INTERP_SINC) ? 1 : 0;
         RP.out = a->dev;
         size_t glds;
-        if ((rc = plan_tiles(ctx, segs, ratio, interp, C, RP, &glds))) { delete ck; return rc; }
+        if ((rc = plan_tiles(ctx, segs, ratio, interp, C, RP, &glds))) return rc;
         rc = launch_resample(ctx, SRC_AUDIO_F64, interp, EPI_STREAM_FLOOR, dtype, RP, glds, in->total() + out_elems * dtype_size(dtype), nullptr);
-        if (rc) { delete ck; return rc; }
+        if (rc) return rc;
     }
     return done();
 }

@@ -18,13 +18,7 @@
 
 namespace aukit {
 
-int audio_from_int_rows(aukit_ctx *ctx, int src_kind, const void *rows_dev, const std::vector<uint64_t> &row_off, const std::vector<uint64_t> &row_len,
-                        uint32_t n, int channels, double rate, double new_rate, int interp, bool do_resample, int dtype, double norm_pos,
-                        double norm_neg, aukit_audio **out);
-// round 2's implementations (host-side header walk, lane-per-job kernels): the fallback
-int decode_qoa_audio_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *, double new_rate, int interp, bool do_resample, int dtype, aukit_audio **out);
-int stream_qoa_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d, int interp, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks);
-
+// the fallback, decode_qoa_audio_host and stream_qoa_host (declared in resample.h): round 2's implementations — host-side header walk, lane-per-job kernels
 struct QoaJob { unsigned long long frame_off, out_off; int c, channels, samples, emit; };   // as in codecs2.hip
 
 __constant__ int c_qoa_deq[16][8] = {
@@ -500,9 +494,7 @@ int stream_qoa(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d,
     sw.back();   // ctx->stream behind the walks (the decoder reads their jobs)
     AUKIT_HIP_CHECK(hipEventRecord(ctx->pre_ev, pre));
     AUKIT_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->pre_ev, 0));
-    aukit_chunks *ck = new aukit_chunks();
-    ck->n = in->n;
-    ck->nchunks.assign(in->n, 0); ck->status.assign(in->n, 0); ck->length_seconds.assign(in->n, 0);
+    ChunksOwner ck = chunks_create(in->n);
     std::vector<uint64_t> lens(in->n, 0);
     std::vector<uint64_t> nouts(ncalls, 0);
     for (uint32_t s = 0; s < in->n; s++) {
@@ -511,17 +503,14 @@ int stream_qoa(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d,
             const QoaCallRec &cr = calls[S[s].call_first + k];
             const double newlen = (double)cr.n * ratio;                                            // :3312
             const uint64_t nout = newlen >= 1 ? (uint64_t)std::floor(newlen) : 0;
-            if (nout > 0x7FFFFFF0ull) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "stream too long"); }
+            if (nout > 0x7FFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "stream too long");
             nouts[S[s].call_first + k] = nout;
             lens[s] += nout;
         }
         if (S[s].raised) ck->status[s] = AUKIT_E_LUA;
-        ck->nchunks[s] = S[s].ncalls;
-        ck->max_chunks = std::max(ck->max_chunks, S[s].ncalls);
+        chunks_set_count(*ck, s, S[s].ncalls);
     }
-    const uint32_t mc = std::max<uint32_t>(ck->max_chunks, 1);
-    ck->lens.assign((size_t)ck->n * mc, 0);
-    ck->pos.assign((size_t)ck->n * mc, 0);
+    const uint32_t mc = chunks_shape(*ck);
     for (uint32_t s = 0; s < in->n; s++) {
         double file_pos = (double)ctx->sb_samples;   // (the rest of a stream behind a bounded reader-function handle: what was dropped counts)
         for (unsigned k = 0; k < S[s].ncalls; k++) {
@@ -532,10 +521,10 @@ int stream_qoa(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d,
     }
     const bool mix = mono && C > 1;
     aukit_audio *a = *out;
-    if ((rc = audio_prepare(ctx, &a, in->n, mix ? 1 : C, 48000, dtype, lens.data()))) { delete ck; return rc; }
+    if ((rc = audio_prepare(ctx, &a, in->n, mix ? 1 : C, 48000, dtype, lens.data()))) return rc;
     *out = a;
     if (ncalls) {
-        if ((rc = qoa_decode_launch<true>(ctx, in, djobs, njobs, ctx->tmp_buf.p, tot))) { delete ck; return rc; }
+        if ((rc = qoa_decode_launch<true>(ctx, in, djobs, njobs, ctx->tmp_buf.p, tot))) return rc;
         std::vector<TailJob> jobs;
         jobs.reserve((size_t)ncalls * (mix ? 1 : C));
         uint64_t total_out = 0;
@@ -571,12 +560,11 @@ int stream_qoa(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d,
             // (the tile chain of flac_tail.hip: the state carried, not warmed up)
         } else
         if (!iir_tail_try(ctx, TAIL_QOA, TAIL_ROWS_I8, ctx->tmp_buf.p, 1.0, jobs, mix ? C : 1, rate, interp, dtype, a->dev, tot + total_out * dtype_size(dtype), "k_iir_tail<qoa>", &trc)) {
-            delete ck;
             return stream_qoa_host(ctx, in, d, interp, mono, dtype, out, chunks_out);   // very low sample rates: the filter's memory outlasts a tile's warm-up
         }
-        if (trc) { delete ck; return trc; }
+        if (trc) return trc;
     }
-    if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
+    chunks_deliver(ck, chunks_out);
     return AUKIT_OK;
 }
 

@@ -154,9 +154,7 @@ int stream_qoa_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_des
     AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     int C = 0;
     double rate = 0;
-    aukit_chunks *ck = new aukit_chunks();
-    ck->n = in->n;
-    ck->nchunks.assign(in->n, 0); ck->status.assign(in->n, 0); ck->length_seconds.assign(in->n, 0);
+    ChunksOwner ck = chunks_create(in->n);
     std::vector<std::vector<uint32_t>> clen(in->n);
     std::vector<std::vector<double>> cpos(in->n);
     std::vector<uint64_t> lens(in->n, 0);
@@ -169,16 +167,16 @@ int stream_qoa_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_des
     for (uint32_t s = 0; s < in->n; s++) {
         const uint8_t *h = host.data() + in->off[s];
         const uint64_t nb = in->off[s + 1] - in->off[s];
-        if (nb < 8) { delete ck; return fail(AUKIT_E_LUA, "Not a QOA file"); }                    // assert(read(8), ...)
-        if (memcmp(h, "qoaf", 4) != 0) { delete ck; return fail(AUKIT_E_ARG, "Not a QOA file"); }
+        if (nb < 8) return fail(AUKIT_E_LUA, "Not a QOA file");                    // assert(read(8), ...)
+        if (memcmp(h, "qoaf", 4) != 0) return fail(AUKIT_E_ARG, "Not a QOA file");
         const double file_samples = (double)((uint32_t)h[4] << 24 | (uint32_t)h[5] << 16 | (uint32_t)h[6] << 8 | h[7]);
-        if (nb == 8) { delete ck; return fail(AUKIT_E_LUA, "Not a QOA file"); }                   // assert(peek(4), ...)
-        if (nb < 12) { delete ck; return fail(AUKIT_E_LUA, "data string too short"); }
+        if (nb == 8) return fail(AUKIT_E_LUA, "Not a QOA file");                   // assert(peek(4), ...)
+        if (nb < 12) return fail(AUKIT_E_LUA, "data string too short");
         const int fc = h[8];
         const double fr = (double)((uint32_t)h[9] << 16 | (uint32_t)h[10] << 8 | h[11]);
-        if (fc < 1 || fc > AUKIT_MAX_PLANAR_CHANNELS) { delete ck; return fail(AUKIT_E_UNSUPPORTED, "QOA channel count %d", fc); }
+        if (fc < 1 || fc > AUKIT_MAX_PLANAR_CHANNELS) return fail(AUKIT_E_UNSUPPORTED, "QOA channel count %d", fc);
         if (s == 0) { C = fc; rate = fr; ratio = 48000 / rate; }
-        else if (fc != C || fr != rate) { delete ck; return fail(AUKIT_E_ARG, "all QOA streams of a batch must share channel count and sample rate"); }
+        else if (fc != C || fr != rate) return fail(AUKIT_E_ARG, "all QOA streams of a batch must share channel count and sample rate");
         ck->length_seconds[s] = file_samples / fr;
         uint64_t pos = 8;
         double file_pos = (double)ctx->sb_samples;
@@ -233,23 +231,20 @@ int stream_qoa_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_des
             lens[s] += nout;
             tot += stride * C;
         }
-        ck->nchunks[s] = (uint32_t)clen[s].size();
-        ck->max_chunks = std::max(ck->max_chunks, ck->nchunks[s]);
+        chunks_set_count(*ck, s, (uint32_t)clen[s].size());
     }
-    const uint32_t mc = std::max<uint32_t>(ck->max_chunks, 1);
-    ck->lens.assign((size_t)ck->n * mc, 0);
-    ck->pos.assign((size_t)ck->n * mc, 0);
+    const uint32_t mc = chunks_shape(*ck);
     for (uint32_t s = 0; s < in->n; s++)
         for (uint32_t k = 0; k < ck->nchunks[s]; k++) { ck->lens[(size_t)s * mc + k] = clen[s][k]; ck->pos[(size_t)s * mc + k] = cpos[s][k]; }
     int rc;
     aukit_audio *&full = ctx->stream_full;  // reused from call to call (audio_prepare keeps buffers that are large enough)
     aukit_audio **dst = mono && C > 1 ? &full : out;
     aukit_audio *a = *dst;
-    if ((rc = audio_prepare(ctx, &a, in->n, C, 48000, dtype, lens.data()))) { delete ck; return rc; }
+    if ((rc = audio_prepare(ctx, &a, in->n, C, 48000, dtype, lens.data()))) return rc;
     *dst = a;
     if (!calls.empty()) {
-        if ((rc = ctx->tmp_buf.ensure((size_t)tot * 2 + 64))) { delete ck; return rc; }
-        if ((rc = upload_table(ctx, ctx->tmp_buf2, djobs.data(), djobs.size() * sizeof(QoaJob)))) { delete ck; return rc; }
+        if ((rc = ctx->tmp_buf.ensure((size_t)tot * 2 + 64))) return rc;
+        if ((rc = upload_table(ctx, ctx->tmp_buf2, djobs.data(), djobs.size() * sizeof(QoaJob)))) return rc;
         hipLaunchKernelGGL(k_qoa, dim3((unsigned)((djobs.size() + 63) / 64)), dim3(64), 0, ctx->stream, in->data(), reinterpret_cast<const QoaJob *>(ctx->tmp_buf2.p),
                            (unsigned long long)djobs.size(), reinterpret_cast<short *>(ctx->tmp_buf.p), 1);
         AUKIT_HIP_CHECK(hipGetLastError());
@@ -270,13 +265,13 @@ int stream_qoa_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_des
             outpos[cl.stream] += cl.nout;
             prev[cl.stream] = (long long)k;
         }
-        if ((rc = upload_table(ctx, ctx->seg_buf, jobs.data(), jobs.size() * sizeof(QsJob)))) { delete ck; return rc; }
+        if ((rc = upload_table(ctx, ctx->seg_buf, jobs.data(), jobs.size() * sizeof(QsJob)))) return rc;
         const double lp_alpha = 1 - std::exp(-(rate / 96000) * 2 * M_PI);  // :3251
         const int exact = exact_div_verified(ctx, ratio, 1ull << 18) ? 1 : 0;
         const unsigned grid = (unsigned)((jobs.size() + 63) / 64);
         const QsJob *dj = reinterpret_cast<const QsJob *>(ctx->seg_buf.p);
         const short *rows = reinterpret_cast<const short *>(ctx->tmp_buf.p);
-        if ((rc = ctx_begin_kernel(ctx))) { delete ck; return rc; }
+        if ((rc = ctx_begin_kernel(ctx))) return rc;
         uint64_t scr_elems = 0, max_nout = 0;
         std::vector<uint64_t> scr_off(jobs.size());
         for (size_t k = 0; k < jobs.size(); k++) { scr_off[k] = scr_elems; scr_elems += ((uint64_t)jobs[k].nout + 1) & ~1ull; max_nout = std::max<uint64_t>(max_nout, (uint64_t)jobs[k].nout); }
@@ -284,8 +279,8 @@ int stream_qoa_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_des
         // and ~60 fp64 operations per output on a few hundred waves (1024 stereo streams of ten seconds: 94 ms against 7 ms in two passes)
         if (scr_elems * 8 <= (48ull << 30) && max_nout) {
             DevBuf &S3 = ctx_scratch3(ctx);
-            if ((rc = S3.ensure((size_t)scr_elems * 8 + 64))) { delete ck; return rc; }
-            if ((rc = upload_table(ctx, ctx->misc_buf, scr_off.data(), scr_off.size() * 8))) { delete ck; return rc; }
+            if ((rc = S3.ensure((size_t)scr_elems * 8 + 64))) return rc;
+            if ((rc = upload_table(ctx, ctx->misc_buf, scr_off.data(), scr_off.size() * 8))) return rc;
             const unsigned long long *dso = reinterpret_cast<const unsigned long long *>(ctx->misc_buf.p);
             double *scr = reinterpret_cast<double *>(S3.p);
             for (size_t first = 0; first < jobs.size(); first += 65535) {  // (grid.y holds 65535 jobs)
@@ -304,13 +299,13 @@ int stream_qoa_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_des
 #undef AUKIT_QS
         }
         AUKIT_HIP_CHECK(hipGetLastError());
-        if ((rc = ctx_end_kernel(ctx, "k_qoa_stream", in->total()))) { delete ck; return rc; }
+        if ((rc = ctx_end_kernel(ctx, "k_qoa_stream", in->total()))) return rc;
     }
     if (mono && C > 1) {  // lines[1][i] = (0 + s_1 + ... + s_C) / C  :3326-3329 — the same sum order as Audio:mono
         rc = aukit_mono(ctx, full, out);
-        if (rc) { delete ck; return rc; }
+        if (rc) return rc;
     }
-    if (chunks_out) { if (*chunks_out) aukit_chunks_free(*chunks_out); *chunks_out = ck; } else delete ck;
+    chunks_deliver(ck, chunks_out);
     return AUKIT_OK;
 }
 

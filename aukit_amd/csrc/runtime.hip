@@ -264,7 +264,6 @@ void aukit_ctx_destroy(aukit_ctx *c) {
         (void)hipStreamDestroy(c->aux_stream);
     }
     if (c->stream_full) { aukit_audio_free(c->stream_full); c->stream_full = nullptr; }
-    delete c->spcm_ck;
     if (c->host_stage) (void)hipHostFree(c->host_stage);
     if (c->pre_stream) { (void)hipStreamSynchronize(c->pre_stream); (void)hipStreamDestroy(c->pre_stream); c->pre_stream = nullptr; }
     for (hipEvent_t *e : {&c->pre_ev, &c->entry_ev[0], &c->entry_ev[1], &c->scratch_ev}) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }

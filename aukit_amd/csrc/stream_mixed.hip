@@ -613,7 +613,7 @@ struct SMixPlan {
     std::vector<SMixSeg> segs;                // stream after stream, call after call
     std::vector<double> cpos;                 // per segment: the position its iterator call returns
     std::vector<uint64_t> lens;               // per stream: outputs of all its calls
-    std::unique_ptr<aukit_chunks> ck;         // held here until the call delivers it
+    ChunksOwner ck;                           // held here until the call delivers it
     std::map<double, ChunkPlan> pcm_plans;    // stream.pcm's plan is made once per distinct rate
     // the DFPWM streams that have bytes, by channel count (the engine's run and stride are per call); bytes of all rows, source bytes, streams
     std::map<int, SMixDfGroup> df_groups;
@@ -624,12 +624,7 @@ struct SMixPlan {
     uint64_t ima_elems = 0, ima_jobs = 0, ima_src = 0;
     uint64_t in_bytes = 0;
 
-    explicit SMixPlan(uint32_t n) : lens(n, 0), ck(new aukit_chunks()) {
-        ck->n = n;
-        ck->nchunks.assign(n, 0);
-        ck->status.assign(n, 0);
-        ck->length_seconds.assign(n, 0);
-    }
+    explicit SMixPlan(uint32_t n) : lens(n, 0), ck(chunks_create(n)) {}
     // one iterator call of stream s: g.n_out outputs behind the stream's earlier ones (the row's offset is added once the audio is laid out)
     void add_call(uint32_t s, SMixSeg &g, double pos) {
         g.out_off = lens[s];
@@ -760,9 +755,7 @@ static void smix_plan(const aukit_batch *in, const aukit_codec_desc *descs, cons
 static void smix_chunk_table(SMixPlan &pl, int C_out) {
     aukit_chunks &ck = *pl.ck;
     for (uint32_t s = 0; s < ck.n; s++) ck.max_chunks = std::max<uint32_t>(ck.max_chunks, ck.nchunks[s]);
-    const size_t mc = std::max<uint32_t>(ck.max_chunks, 1);
-    ck.lens.assign((size_t)ck.n * mc, 0);
-    ck.pos.assign((size_t)ck.n * mc, 0);
+    const size_t mc = chunks_shape(ck);
     size_t i = 0;
     for (uint32_t s = 0; s < ck.n; s++)
         for (uint32_t k = 0; k < ck.nchunks[s]; k++, i++) {
@@ -915,10 +908,7 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
         const std::vector<SMixTile> tiles = smix_tiles(T, pl, a, nt);
         if ((rc = smix_launch(ctx, in, T, pl, tiles, L, a, interp, dtype))) return rc;
     }
-    if (chunks) {  // delivery: the caller's table is replaced
-        if (*chunks) aukit_chunks_free(*chunks);
-        *chunks = pl.ck.release();
-    }
+    chunks_deliver(pl.ck, chunks);   // the caller's table is replaced
     return AUKIT_OK;
 }
 
