@@ -461,7 +461,7 @@ def au(data):  # aukit.lua:1639
 _MAGIC_KIND = {"wav": N.CONTAINER_WAV, "aiff": N.CONTAINER_AIFF, "au": N.CONTAINER_AU}
 
 
-def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False):
+def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm=False):
     """load_many's host half, up to the device call: every file sniffed by magic as `detect` does and walked by aukit_parse_container
     -> ([descriptor per file], [(first payload byte, byte count) per file], [info table per file]).  A file that is no WAV / AIFF / AU / QOA, or
     whose payload is none of PCM, G.711 and DFPWM, raises LuaError naming the file's index (0-based, the position in `files`).
@@ -476,7 +476,10 @@ def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False):
     are refused by index, as before aukit_stream_decode_mixed took the codec.
     `stream_ima` (with `stream`): an IMA-ADPCM WAV file (format 0x11, or extensible with the ADPCM GUID) is taken too — the descriptor is the
     container walk's, blockAlign included, the payload the `data` chunk, the length NaN (aukit.stream.adpcm's own figure stands, :2992).  Without
-    it such a file is refused by index in the words of before."""
+    it such a file is refused by index in the words of before.
+    `adpcm` (without `stream`): load_many's switch — a WAV file whose payload is IMA-ADPCM or MS-ADPCM blocks is taken too: the descriptor is the
+    container walk's (blockAlign, and for MS-ADPCM the `fmt` chunk's coefficient list), the payload the `data` chunk, the info table aukit.wav's.
+    Without it both are refused by index in the words of before."""
     _expect(1, files, "table")
     takes = "PCM, G.711 and DFPWM" if stream_dfpwm else "PCM and G.711"
     if stream_ima:
@@ -484,6 +487,8 @@ def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False):
     served = (N.CODEC_PCM, N.CODEC_G711) if stream and not stream_dfpwm else (N.CODEC_PCM, N.CODEC_G711, N.CODEC_DFPWM)
     if stream and stream_ima:
         served += (N.CODEC_ADPCM_WAV,)
+    if adpcm and not stream:
+        served += (N.CODEC_ADPCM_WAV, N.CODEC_MSADPCM)
     others = "the other block codecs" if stream_ima else "the block codecs"
     descs, ranges, infos = [], [], []
     for i, f in enumerate(files):
@@ -605,20 +610,31 @@ class _RowView(B.AudioBatch):
             self._own = None
 
 
-def load_many(files, sampleRate=None, interpolation=None, mono=None):
+def load_many(files, sampleRate=None, interpolation=None, mono=None, adpcm=None):
     """aukit.wav / aukit.aiff / aukit.au / aukit.qoa (file):resample(sampleRate, interpolation) [:mono()] for a LIST of whole files of any mix of
     containers, rates, PCM formats / G.711 / DFPWM / QOA and channel counts: the payload ranges go up as one batch, one aukit_decode_resample_mixed
     call resamples (and, by default, mixes down) all of them, and one Audio per file comes back, in input order, each a view of its row of the
     result.  Without `mono` the files must agree in channel count.  A raw .dfpwm file, which has no header, is given as
-    (data, "dfpwm"[, channels[, sampleRate]]): aukit.dfpwm's arguments.  A .qoa file goes up whole."""
+    (data, "dfpwm"[, channels[, sampleRate]]): aukit.dfpwm's arguments.  A .qoa file goes up whole.
+    `adpcm` = True: WAV files of IMA-ADPCM or MS-ADPCM blocks are taken as well (aukit.wav's dispatch to aukit.adpcm's block splitter and to
+    aukit.msadpcm); for this one call the context is opted in to MS-ADPCM descriptors (AUKIT_OPT_MIXED_CODECS) and put back as it was behind it.
+    Without it (the default) both kinds are refused by index, as before."""
     sampleRate = 48000 if sampleRate is None else _expect(2, sampleRate, "number")
     interpolation = interpolation if interpolation is not None else defaultInterpolation
     ip = _interp(interpolation, 3)
     mono = True if mono is None else _expect(4, mono, "boolean")
-    descs, ranges, infos = _sniff_many(files)
+    adpcm = False if adpcm is None else _expect(5, adpcm, "boolean")
+    descs, ranges, infos = _sniff_many(files, adpcm=adpcm)
     ctx = context()
     bt = _wrap(B.Batch.upload, ctx, [bytes((f[0] if isinstance(f, (list, tuple)) else f)[o:o + n]) for f, (o, n) in zip(files, ranges)])
-    out = _wrap(B.decode_resample_mixed, ctx, bt, descs, float(sampleRate), ip, mono, ctx.dtype)
+    was = ctx.option(N.OPT_MIXED_CODECS)
+    try:
+        if adpcm:
+            _wrap(ctx.set_option, N.OPT_MIXED_CODECS, was | 1 << N.CODEC_MSADPCM)
+        out = _wrap(B.decode_resample_mixed, ctx, bt, descs, float(sampleRate), ip, mono, ctx.dtype)
+    finally:
+        if adpcm:
+            ctx.set_option(N.OPT_MIXED_CODECS, was)
     shared = {}
     return [Audio(_RowView(out, s, shared), {}, infos[s]) for s in range(len(files))]
 

@@ -91,6 +91,11 @@ class Context:
 
     def set_option(self, option, value):
         N.check(N.lib().aukit_ctx_set_option(self._h, int(option), int(value)))
+        self.__dict__.setdefault("_options", {})[int(option)] = int(value)
+
+    def option(self, option, default=0):
+        """the value this object last set for `option` (the C ABI has no getter): `default` where it set none"""
+        return self.__dict__.get("_options", {}).get(int(option), default)
 
     def counter(self, which):
         """a counter of the most recent call that produced it (set_option(OPT_COLLECT_STATS, 1) first): N.COUNTER_*"""
@@ -469,7 +474,9 @@ def decode_resample_mixed(ctx, batch, descs, new_rate, interp, mono=False, dtype
     a WAV file, any rate), resampled to `new_rate` and, with `mono`, mixed down — one call, one resample launch (behind decode pre-passes when the
     batch holds DFPWM, QOA or IMA-ADPCM streams), one AudioBatch at `new_rate` in the batch's order.  `descs`: one CodecDesc per stream —
     make_desc(N.CODEC_QOA) for a QOA file (channel count and rate are its header's), make_desc(N.CODEC_ADPCM_WAV, channels, rate, block_align=...)
-    for IMA blocks.  Every refusal, those only the device can detect included, comes before `out` is touched."""
+    for IMA blocks, make_desc(N.CODEC_MSADPCM, channels, rate, block_align=..., coefficients=...) for the MS-ADPCM blocks of a WAV file — those
+    only on a context that asked for them: ctx.set_option(N.OPT_MIXED_CODECS, 1 << N.CODEC_MSADPCM).  Every refusal, those only the device can
+    detect included, comes before `out` is touched."""
     out = out if out is not None else AudioBatch(ctx)
     arr = (N.CodecDesc * max(len(descs), 1))()
     for i, d in enumerate(descs):

@@ -3,7 +3,9 @@
 // :1399-1413, :1706-1777, :1509-1548, :653-673, :677-689), in one launch — after pre-passes that leave the DFPWM streams of the batch, if it has any,
 // as flat int8 rows in the context's scratch (the chunk-parallel decoder of dfpwm_par.hip, or a lane per stream where every stream is too short for
 // it), and its QOA and IMA-ADPCM streams as int16 rows, one per channel, beside them (the walks and k_qoa_wave of qoa.hip on the QOA streams only;
-// k_ima_mixed of codecs.hip, a lane per block with the block's own geometry).
+// k_ima_mixed of codecs.hip, a lane per block with the block's own geometry) — and, on a context that asked for them (AUKIT_OPT_MIXED_CODECS), the
+// MS-ADPCM blocks of WAV files (aukit.msadpcm, :1283-1353) as int16 rows among those: k_ms_mixed of msadpcm_mixed.hip, a run of blocks of one stream per
+// workgroup.
 //
 // k_resample (resample.hip) takes format, channel count and ratio from the launch-uniform ResampleParams; k_resample_mixed is its sibling that takes
 // them per tile.  The host plans
@@ -20,7 +22,7 @@
 // fp64 in the reference's operation order whatever the storage type; F32 rounds once, at the store.
 //
 // The host half reads as the call's phases: mix_validate (the QOA header read-back inside it), mix_classes, the scratch layout, the int16-row
-// pre-passes (QOA and IMA jobs, and the stereo-IMA flag read-back), the DFPWM row pre-pass, segments and tiles, the launch.  What the call shares
+// pre-passes (QOA and IMA jobs, MS-ADPCM units, and the read-back of the IMA and MS-ADPCM flags), the DFPWM row pre-pass, segments and tiles, the launch.  What the call shares
 // with aukit_stream_decode_mixed is in mixed_plan.h.
 #include <algorithm>
 #include <tuple>
@@ -36,6 +38,17 @@ int qoa_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<Qo
 size_t qoa_mixed_job_bytes(uint64_t njobs);
 struct ImaMixJob { unsigned long long src_off, row_off; unsigned nbytes, stream; int c, channels; };  // codecs.hip
 int ima_mixed_decode(aukit_ctx *ctx, const unsigned char *src, const void *d_jobs, uint64_t njobs, short *rows, unsigned *flag, uint64_t bytes);
+struct MsMixUnit {  // msadpcm_mixed.hip: a run of up to 64 consecutive blocks of one MS-ADPCM stream
+    unsigned long long src_off, hdr_off, row_off;
+    unsigned stride, nblk, block_align, stream;
+    unsigned short coef_set, ncoef, channels, plain;
+};
+static_assert(sizeof(MsMixUnit) == 48, "MsMixUnit layout");
+size_t ms_mixed_unit_lds(uint64_t nblk, uint64_t block_align, int channels);
+int ms_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const void *d_units, uint64_t n_units, const void *d_coefs, short *rows, unsigned *flags, size_t lds, uint64_t bytes);
+// LDS a unit of k_ms_mixed may stage (source span and output spans): five workgroups of one wave each on a CU's 160 KiB.  A block that does not fit
+// alone (5 * blockAlign + 28 bytes or so: blockAlign above about 6550) takes the kernel's plain path
+constexpr size_t MS_MIX_LDS = 32 * 1024;
 
 constexpr int MIX_SRC_I16 = 100;  // MixClass::codec of a QOA or IMA-ADPCM class: the window comes from int16 rows in the scratch behind MixParams::rows, one per channel
 
@@ -220,6 +233,31 @@ static int check_mixed_ima(const aukit_codec_desc *d, uint64_t nb, uint64_t *fra
     return AUKIT_OK;
 }
 
+// what decode_msadpcm_audio (msadpcm.hip) refuses of one aukit.wav MS-ADPCM stream, with its words; fills the samples per channel (:1283-1353)
+static int check_mixed_msadpcm(const aukit_codec_desc *d, uint64_t nb, uint64_t *frames) {
+    const int C = d->channels;
+    if (d->sample_rate < 1) return fail(AUKIT_E_ARG, "bad argument #4 (number outside of range)");
+    if (C != 1 && C != 2) return fail(AUKIT_E_LUA, "Unsupported number of channels: %d", C);
+    if (d->block_align < 7 * C) return fail(AUKIT_E_ARG, "bad blockAlign");   // (a block that is only a header: two samples, :1312-1315)
+    const uint64_t ba = (uint64_t)d->block_align, nblk = (nb + ba - 1) / ba;   // for n = 1, #data, blockAlign
+    // a stream that ends inside a block raises at the first read that finds nothing (ms_partial_block); one-channel blocks that are only a header
+    // read nothing but the stream's first seven bytes, so a partial last one is a block like the others
+    if (nblk && nb % ba != 0 && !(C == 1 && ba == 7 && nb >= 7)) {
+        if (C == 2 ? nb % ba < 14 : nb < 7) return fail(AUKIT_E_LUA, "data string too short");
+        return fail(AUKIT_E_LUA, "bad argument #1 to 'rshift' (number expected, got nil)");
+    }
+    *frames = nblk * (C == 2 ? (ba - 14) + 2 : (ba - 7) * 2 + 2);
+    return AUKIT_OK;
+}
+// the stream's coefficient table: min(ncoef, 32) pairs of the descriptor, or the seven defaults (:1304) -> count; c1[32], c2[32], zeros behind the count
+static int mixed_ms_coefs(const aukit_codec_desc *d, int *tab) {
+    static const int c1d[7] = {256, 512, 0, 192, 240, 460, 392}, c2d[7] = {0, -256, 0, 64, 0, -208, -232};
+    std::fill(tab, tab + 64, 0);
+    const int nc = d->ncoef > 0 ? std::min(d->ncoef, 32) : 7;
+    for (int i = 0; i < nc; i++) { tab[i] = d->ncoef > 0 ? d->coef1[i] : c1d[i]; tab[32 + i] = d->ncoef > 0 ? d->coef2[i] : c2d[i]; }
+    return nc;
+}
+
 // ---- phase 1: validation.  What the batch is, per stream, once nothing is left to refuse from descriptors, byte counts and QOA headers
 struct MixStreams {
     std::vector<int> ch;           // channel count and sample rate of every stream: the descriptor's, or (QOA) the file header's  :1708-1711
@@ -238,10 +276,16 @@ static int mix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
         return rc;
     if (!(new_rate > 0)) return fail(AUKIT_E_ARG, "bad sample rate");
     const uint32_t n = in->n;
-    if ((rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV},
-                                 "stream %u: codec %d has its own loader (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, "
-                                 "AUKIT_CODEC_QOA and AUKIT_CODEC_ADPCM_WAV)")))
-        return rc;
+    // AUKIT_OPT_MIXED_CODECS: MS-ADPCM joins the list on a context that asked for it; without the bit the call answers in the words of before
+    if ((ctx->mixed_codecs >> AUKIT_CODEC_MSADPCM) & 1u)
+        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_MSADPCM},
+                                "stream %u: codec %d has its own loader (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, "
+                                "AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_MIXED_CODECS, AUKIT_CODEC_MSADPCM)");
+    else
+        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV},
+                                "stream %u: codec %d has its own loader (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, "
+                                "AUKIT_CODEC_QOA and AUKIT_CODEC_ADPCM_WAV)");
+    if (rc) return rc;
     S.ch.resize(n);
     S.rate.resize(n);
     for (uint32_t s = 0; s < n; s++) {
@@ -249,7 +293,7 @@ static int mix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
         S.ch[s] = descs[s].channels;
         S.rate[s] = descs[s].sample_rate;
         if (codec == AUKIT_CODEC_QOA) S.q_list.push_back(s);
-        if (codec == AUKIT_CODEC_QOA || codec == AUKIT_CODEC_ADPCM_WAV) S.has_i16 = true;
+        if (codec == AUKIT_CODEC_QOA || codec == AUKIT_CODEC_ADPCM_WAV || codec == AUKIT_CODEC_MSADPCM) S.has_i16 = true;
     }
     // QOA: the count pass of the device walk on these streams only, and the header read-back — what a header is refused for comes first, with
     // aukit.qoa's words.  It writes ctx->tmp_buf3 and nothing of `*out`.
@@ -274,10 +318,19 @@ static int mix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
             else rc = check_mixed_rows(S.rate[s], new_rate, S.frames[s], &S.lens[s]);
         } else if (codec == AUKIT_CODEC_ADPCM_WAV) {
             if (!(rc = check_mixed_ima(&descs[s], nb, &S.frames[s]))) rc = check_mixed_rows(S.rate[s], new_rate, S.frames[s], &S.lens[s]);
+        } else if (codec == AUKIT_CODEC_MSADPCM) {
+            if (!(rc = check_mixed_msadpcm(&descs[s], nb, &S.frames[s]))) rc = check_mixed_rows(S.rate[s], new_rate, S.frames[s], &S.lens[s]);
+            if (!rc) {  // (k_ms_mixed's int32 sums need 16-bit operands: ms_fill_coefs' condition, where the single call leaves its wave kernel)
+                int tab[64];
+                const int nc = mixed_ms_coefs(&descs[s], tab);
+                for (int i = 0; i < nc && !rc; i++)
+                    if (std::abs(tab[i]) + std::abs(tab[32 + i]) >= 65536)
+                        rc = fail(AUKIT_E_UNSUPPORTED, "MS-ADPCM coefficient pair %d with |c1| + |c2| >= 65536: aukit_decode_resample takes this stream", i);
+            }
         } else rc = check_mixed_stream(&descs[s], nb, new_rate, &S.frames[s], &S.lens[s]);
         if (rc) return fail_for_stream(rc, s);
         if (codec == AUKIT_CODEC_DFPWM) { S.has_df = true; S.in_bytes += mixed_dfpwm_fed(nb) * 8; }
-        else if (codec == AUKIT_CODEC_QOA || codec == AUKIT_CODEC_ADPCM_WAV) S.in_bytes += S.frames[s] * (uint64_t)S.ch[s] * 2;
+        else if (codec == AUKIT_CODEC_QOA || codec == AUKIT_CODEC_ADPCM_WAV || codec == AUKIT_CODEC_MSADPCM) S.in_bytes += S.frames[s] * (uint64_t)S.ch[s] * 2;
         else S.in_bytes += nb;
         S.out_elems += S.lens[s] * (uint64_t)(mono ? 1 : S.ch[s]);
     }
@@ -303,7 +356,7 @@ static int mix_classes(aukit_ctx *ctx, const aukit_codec_desc *descs, uint32_t n
         const bool pcm = d.codec == AUKIT_CODEC_PCM;
         const int planar = (pcm && d.channels > 1 && !d.interleaved) ? 1 : 0;  // aukit.lua:1156-1169
         const bool g711 = d.codec == AUKIT_CODEC_G711;  // (a DFPWM class is keyed by codec, channels and sample rate)
-        const bool i16 = d.codec == AUKIT_CODEC_QOA || d.codec == AUKIT_CODEC_ADPCM_WAV;  // (one kind of class for both: keyed by channels and sample rate)
+        const bool i16 = d.codec == AUKIT_CODEC_QOA || d.codec == AUKIT_CODEC_ADPCM_WAV || d.codec == AUKIT_CODEC_MSADPCM;  // (one kind of class for all three: keyed by channels and sample rate)
         const int kcodec = i16 ? MIX_SRC_I16 : d.codec, kch = S.ch[s];
         bool fresh;
         const unsigned c = T.cls_of[s] = index.of({kcodec, pcm ? d.bit_depth : i16 ? 16 : 8, pcm ? d.data_type : 0, pcm ? (d.big_endian ? 1 : 0) : 0, planar, kch,
@@ -373,17 +426,47 @@ struct MixI16Rows {
     std::vector<ImaMixJob> ijobs;   // one job per (IMA block, channel): where the block is, how long, where its samples go
     uint64_t el = 0, q_jobs = 0, q_src = 0, i_src = 0;  // elements of all rows; QOA jobs; source bytes of the QOA / the IMA streams
     bool stereo_ima = false;
+    std::vector<MsMixUnit> munits;  // the MS-ADPCM tile table: one unit per run of consecutive blocks of a stream, as many as MS_MIX_LDS holds (64 at the most)
+    std::vector<int> mcoefs;        // the distinct coefficient sets: c1[32], c2[32] each
+    uint64_t m_src = 0, m_el = 0;   // source bytes and row elements of the MS-ADPCM streams
+    size_t m_lds = 0;               // the largest staged unit's LDS
 };
+// blocks per unit of k_ms_mixed for a stream's geometry: as many as fit MS_MIX_LDS, 64 at the most; 0: a single block does not fit (the plain path)
+static unsigned mix_ms_blocks_per_unit(uint64_t ba, int C) {
+    if (ms_mixed_unit_lds(1, ba, C) > MS_MIX_LDS) return 0;
+    unsigned t = 64;
+    while (ms_mixed_unit_lds(t, ba, C) > MS_MIX_LDS) t--;
+    return t;
+}
 static MixI16Rows mix_i16_plan(const aukit_batch *in, const aukit_codec_desc *descs, const MixStreams &S) {
     MixI16Rows R;
     R.row.assign(in->n, 0);
     for (uint32_t s = 0, qk = 0; s < in->n; s++) {
         const int codec = descs[s].codec;
-        if (codec != AUKIT_CODEC_QOA && codec != AUKIT_CODEC_ADPCM_WAV) continue;
+        if (codec != AUKIT_CODEC_QOA && codec != AUKIT_CODEC_ADPCM_WAV && codec != AUKIT_CODEC_MSADPCM) continue;
         const uint64_t stride = round_up(std::max<uint64_t>(S.frames[s], 1), 8), nb = in->off[s + 1] - in->off[s];
         R.row[s] = R.el;
         if (codec == AUKIT_CODEC_QOA) { R.q_rows.push_back(R.el); R.q_jobs += S.Q[qk++].njobs; R.q_src += nb; }
-        else {
+        else if (codec == AUKIT_CODEC_MSADPCM) {
+            const uint64_t ba = (uint64_t)descs[s].block_align, C = (uint64_t)S.ch[s], spb = C == 2 ? (ba - 14) + 2 : (ba - 7) * 2 + 2, nblk = (nb + ba - 1) / ba;
+            int tab[64];
+            const int nc = mixed_ms_coefs(&descs[s], tab);
+            size_t set = 0;
+            for (; set < R.mcoefs.size() / 64; set++)
+                if (std::equal(tab, tab + 64, R.mcoefs.begin() + set * 64)) break;
+            if (set == R.mcoefs.size() / 64) R.mcoefs.insert(R.mcoefs.end(), tab, tab + 64);
+            const unsigned T = mix_ms_blocks_per_unit(ba, (int)C), step = T ? T : 64;
+            for (uint64_t b0 = 0; b0 < nblk; b0 += step) {
+                MsMixUnit u;
+                u.src_off = in->off[s] + b0 * ba; u.hdr_off = in->off[s]; u.row_off = R.el + b0 * spb;
+                u.stride = (unsigned)stride; u.nblk = (unsigned)std::min<uint64_t>(step, nblk - b0); u.block_align = (unsigned)ba; u.stream = s;
+                u.coef_set = (unsigned short)set; u.ncoef = (unsigned short)nc; u.channels = (unsigned short)C; u.plain = T ? 0 : 1;
+                if (T) R.m_lds = std::max(R.m_lds, ms_mixed_unit_lds(u.nblk, ba, (int)C));
+                R.munits.push_back(u);
+            }
+            R.m_src += nb;
+            R.m_el += stride * C;
+        } else {
             const uint64_t ba = (uint64_t)descs[s].block_align, C = (uint64_t)S.ch[s], spb = (ba - 4 * C) * 2 / C;
             if (C == 2) R.stereo_ima = true;
             R.i_src += nb;
@@ -398,7 +481,7 @@ static MixI16Rows mix_i16_plan(const aukit_batch *in, const aukit_codec_desc *de
 
 // The int8 rows first; the DFPWM decoders' tables behind them in the same buffer (ctx->misc_buf, where the class table goes, and ctx->tmp_buf2,
 // which the chunk engine carves, stay free of them); then the int16 rows, the QOA and the IMA job tables and the IMA flag
-struct MixScratch { size_t df_tab_at = 0, i16_at = 0, qj_at = 0, ij_at = 0, flag_at = 0, size = 0; };
+struct MixScratch { size_t df_tab_at = 0, i16_at = 0, qj_at = 0, ij_at = 0, mu_at = 0, mc_at = 0, flag_at = 0, size = 0; };
 static MixScratch mix_scratch(const MixStreams &S, const MixDfRows &D, const MixI16Rows &R) {
     Carve carve;
     MixScratch L;
@@ -407,29 +490,44 @@ static MixScratch mix_scratch(const MixStreams &S, const MixDfRows &D, const Mix
         L.i16_at = carve.take((size_t)R.el * 2);
         L.qj_at = carve.take(S.q_list.empty() ? 0 : qoa_mixed_job_bytes(R.q_jobs), 0);
         L.ij_at = carve.take(R.ijobs.size() * sizeof(ImaMixJob), 0);
-        L.flag_at = carve.take(4, 60);
+        L.mu_at = carve.take(R.munits.size() * sizeof(MsMixUnit), 0);
+        L.mc_at = carve.take(R.mcoefs.size() * sizeof(int), 0);
+        L.flag_at = carve.take(12, 52);  // the IMA flag, then the two MS-ADPCM words (predictor index, delta)
     }
     L.size = carve.end;
     return L;
 }
 
-// ---- phase 4: the int16-row pre-passes.  They can still refuse (a stereo IMA block's step index), and they write nothing but the scratch: so they
-// run, and their flag is read back, BEFORE `*out` is touched
+// ---- phase 4: the int16-row pre-passes.  They can still refuse (a stereo IMA block's step index; an MS-ADPCM predictor index beyond the stream's
+// coefficient table or a delta that leaves k_ms_mixed's int32 range), and they write nothing but the scratch: so they run, and their flags are read
+// back — all three words in one copy, one wait — BEFORE `*out` is touched.  Of several offenders the lowest stream is the one named
 static int mix_i16_prepass(aukit_ctx *ctx, const aukit_batch *in, const MixStreams &S, const MixI16Rows &R, const MixScratch &L) {
     int rc;
     char *const T = reinterpret_cast<char *>(ctx->tmp_buf.p);
     short *const rows16 = reinterpret_cast<short *>(T + L.i16_at);
     if (!S.q_list.empty() && (rc = qoa_mixed_decode(ctx, in, S.Q, R.q_rows.data(), rows16, T + L.qj_at, R.q_src))) return rc;
-    if (R.ijobs.empty()) return AUKIT_OK;
+    if (R.ijobs.empty() && R.munits.empty()) return AUKIT_OK;
     unsigned *flag = reinterpret_cast<unsigned *>(T + L.flag_at);
-    if ((rc = h2d_table(ctx, T + L.ij_at, R.ijobs.data(), R.ijobs.size() * sizeof(ImaMixJob)))) return rc;
-    AUKIT_HIP_CHECK(hipMemsetAsync(flag, 0xFF, 4, ctx->stream));
-    if ((rc = ima_mixed_decode(ctx, in->data(), T + L.ij_at, R.ijobs.size(), rows16, flag, R.i_src + R.el * 2))) return rc;
-    if (R.stereo_ima) {  // (a one-channel block's masked index cannot leave 0 .. 88: no flag to wait for)
-        unsigned hflag = 0xFFFFFFFFu;
-        AUKIT_HIP_CHECK(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+    AUKIT_HIP_CHECK(hipMemsetAsync(flag, 0xFF, 12, ctx->stream));
+    if (!R.ijobs.empty()) {
+        if ((rc = h2d_table(ctx, T + L.ij_at, R.ijobs.data(), R.ijobs.size() * sizeof(ImaMixJob)))) return rc;
+        if ((rc = ima_mixed_decode(ctx, in->data(), T + L.ij_at, R.ijobs.size(), rows16, flag, R.i_src + (R.el - R.m_el) * 2))) return rc;
+    }
+    if (!R.munits.empty()) {
+        if ((rc = h2d_table(ctx, T + L.mu_at, R.munits.data(), R.munits.size() * sizeof(MsMixUnit))) ||
+            (rc = h2d_table(ctx, T + L.mc_at, R.mcoefs.data(), R.mcoefs.size() * sizeof(int))))
+            return rc;
+        if ((rc = ms_mixed_decode(ctx, in, T + L.mu_at, R.munits.size(), T + L.mc_at, rows16, flag + 1, R.m_lds, R.m_src + R.m_el * 2))) return rc;
+    }
+    if (R.stereo_ima || !R.munits.empty()) {  // (a one-channel IMA block's masked index cannot leave 0 .. 88: no flag to wait for)
+        unsigned h[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+        AUKIT_HIP_CHECK(hipMemcpyAsync(h, flag, 12, hipMemcpyDeviceToHost, ctx->stream));
         AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (hflag != 0xFFFFFFFFu) return fail(AUKIT_E_ARG, "bad argument #7 (number outside of range) (stream %u)", hflag);
+        const unsigned low = std::min(h[0], std::min(h[1], h[2]));
+        if (low == 0xFFFFFFFFu) return AUKIT_OK;
+        if (h[0] == low) return fail(AUKIT_E_ARG, "bad argument #7 (number outside of range) (stream %u)", low);
+        if (h[1] == low) return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (local 'c1') (stream %u)", low);  // (before the delta: the reference raises here)
+        return fail(AUKIT_E_UNSUPPORTED, "MS-ADPCM delta of 2^21 or more: aukit_decode_resample takes this stream (stream %u)", low);
     }
     return AUKIT_OK;
 }
@@ -459,7 +557,7 @@ static void mix_tiles(const aukit_batch *in, const aukit_codec_desc *descs, cons
                       const MixScratch &L, const aukit_audio *a, std::vector<MixSeg> &segs, std::vector<MixTile> &tiles) {
     for (uint32_t s = 0; s < in->n; s++) {
         MixSeg &g = segs[s];
-        const bool i16 = descs[s].codec == AUKIT_CODEC_QOA || descs[s].codec == AUKIT_CODEC_ADPCM_WAV;
+        const bool i16 = descs[s].codec == AUKIT_CODEC_QOA || descs[s].codec == AUKIT_CODEC_ADPCM_WAV || descs[s].codec == AUKIT_CODEC_MSADPCM;
         g.src_off = descs[s].codec == AUKIT_CODEC_DFPWM ? D.row[s] : i16 ? L.i16_at + 2 * R.row[s] : in->off[s];
         g.out_off = a->row_off[s];
         g.frames = (unsigned)S.frames[s];

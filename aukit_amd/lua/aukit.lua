@@ -580,7 +580,9 @@ end
 -- {data, "dfpwm"[, channels[, sampleRate]]}: aukit.dfpwm's arguments.  A .qoa file (magic "qoaf") goes up whole: its header carries its channel
 -- count and sample rate.  IMA-ADPCM WAV files stay refused here (the batch API, aukit_decode_resample_mixed with AUKIT_CODEC_ADPCM_WAV, takes them).
 local MAGIC = {{"^RIFF....WAVE", 0}, {"^FORM....AIF[FC]", 1}, {"^%.snd", 2}}
+local load_many_adpcm = false   -- the fifth argument of aukit.load_many for the call in flight (the wrapper behind the function sets it)
 function aukit.load_many(files, sampleRate, interpolation, mono)
+    local adpcm = load_many_adpcm
     expect(1, files, "table")
     sampleRate = expect(2, sampleRate, "number", "nil") or 48000
     interpolation = expect(3, interpolation, "string", "nil") or aukit.defaultInterpolation
@@ -614,7 +616,7 @@ function aukit.load_many(files, sampleRate, interpolation, mono)
         if not kind then error("file " .. (i - 1) .. ": not a WAV, AIFF or AU file", 2) end
         local c = ffi.new("aukit_container")
         if C.aukit_parse_container(ffi.cast("const uint8_t*", f), #f, kind, 0, c) ~= 0 then error("file " .. (i - 1) .. ": " .. ffi.string(C.aukit_last_error()), 2) end
-        if c.desc.codec > 1 and c.desc.codec ~= CODEC.dfpwm then error("file " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: load_many takes PCM, G.711, DFPWM and QOA files (the block codecs keep their own loaders; the batch API takes IMA blocks)", 2) end
+        if c.desc.codec > 1 and c.desc.codec ~= CODEC.dfpwm and not (adpcm and (c.desc.codec == CODEC.adpcm_wav or c.desc.codec == CODEC.msadpcm)) then error("file " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: load_many takes PCM, G.711, DFPWM and QOA files (the block codecs keep their own loaders; the batch API takes IMA blocks)", 2) end
         descs[i - 1] = c.desc
         parts[i] = f:sub(tonumber(c.payload_off) + 1, tonumber(c.payload_off + c.payload_len))
         offs[i] = offs[i - 1] + #parts[i]
@@ -626,7 +628,12 @@ function aukit.load_many(files, sampleRate, interpolation, mono)
     check(C.aukit_batch_upload(ctx(), b, ffi.cast("const uint8_t*", table.concat(parts)), offs, n))
     local batch = ffi.gc(b[0], C.aukit_batch_free)
     local o = ffi.new("aukit_audio*[1]")
-    check(C.aukit_decode_resample_mixed(ctx(), batch, descs, n, sampleRate, INTERP[interpolation], mono and 1 or 0, F64, o))
+    -- adpcm: AUKIT_OPT_MIXED_CODECS (5) with bit 1 << AUKIT_CODEC_MSADPCM for this one call; the shim's context sets no other bit, so 0 puts it back
+    if adpcm then check(C.aukit_ctx_set_option(ctx(), 5, 2 ^ CODEC.msadpcm)) end
+    local rc = C.aukit_decode_resample_mixed(ctx(), batch, descs, n, sampleRate, INTERP[interpolation], mono and 1 or 0, F64, o)
+    local words = rc ~= 0 and ffi.string(C.aukit_last_error()) or nil
+    if adpcm then C.aukit_ctx_set_option(ctx(), 5, 0) end
+    if words then error(words, 2) end
     local whole = ffi.gc(o[0], C.aukit_audio_free)
     local cnt, ch, rate, dt, tot = ffi.new("uint32_t[1]"), ffi.new("int[1]"), ffi.new("double[1]"), ffi.new("int[1]"), ffi.new("uint64_t[1]")
     check(C.aukit_audio_info(whole, cnt, ch, rate, dt, tot))
@@ -644,6 +651,18 @@ function aukit.load_many(files, sampleRate, interpolation, mono)
         at = at + tonumber(lens[i - 1]) * ch[0]
     end
     return res
+end
+-- aukit.load_many(files, sampleRate, interpolation, mono, adpcm): `adpcm` = true takes WAV files of IMA-ADPCM and MS-ADPCM blocks too (aukit.wav's
+-- dispatch, aukit.lua:1509-1548 and :1283-1353); nil / false: both are refused by index, as before
+do
+    local four = aukit.load_many
+    aukit.load_many = function(files, sampleRate, interpolation, mono, adpcm)
+        load_many_adpcm = expect(5, adpcm, "boolean", "nil") or false
+        local ok, res = pcall(four, files, sampleRate, interpolation, mono)
+        load_many_adpcm = false
+        if not ok then error(res, 2) end
+        return res
+    end
 end
 
 -- ---------------------------------------------------------------- effects (in place, return the same object: :3356-3618)

@@ -150,11 +150,17 @@ typedef enum {
                                    0 where the guesses fail and the probe does not notice (noise-like streams; silence INSIDE the streams of a
                                    batch too large for a second round is noticed and declined).  0: one encoder lane per stream behind the
                                    chunk-parallel decoder. */
-    AUKIT_OPT_CHANNEL_LENS = 4 /* 1: this host reads chunk lengths per channel (aukit_chunks_channel_lens, aukit_stream_chunk_lens).  stream.pcm without the
+    AUKIT_OPT_CHANNEL_LENS = 4,/* 1: this host reads chunk lengths per channel (aukit_chunks_channel_lens, aukit_stream_chunk_lens).  stream.pcm without the
                                    mix-down on data that ends inside a frame — or, with sinc, inside a later call's burst of taps — then delivers the
                                    reference's last chunk, one output longer in the channels in front of the gap, with the reference's status,
                                    instead of refusing it.  0 (default): one length per chunk, those inputs are refused by name.  No effect on
                                    mono streams, the mix-down or any other codec. */
+    AUKIT_OPT_MIXED_CODECS = 5 /* a bit mask, 0 by default: bit (1 << codec) lets the per-stream-descriptor calls take that aukit_codec beyond the lists
+                                   they serve by default.  Today exactly one bit is known, 1 << AUKIT_CODEC_MSADPCM, and exactly one call reads the
+                                   mask, aukit_decode_resample_mixed; aukit_stream_decode_mixed and aukit_streamset_open ignore it and keep refusing
+                                   that codec by name.  Any other bit is AUKIT_E_UNSUPPORTED, the codec named, and the context keeps the mask it
+                                   had.  The mask is meant to carry later codecs (and the stream calls) as they are taken: a host sets the bits of
+                                   what it is prepared to receive.  With 0 every call answers as it did before the option existed. */
 } aukit_option;
 int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);
 /* counters of the most recent call that produced them (AUKIT_OPT_COLLECT_STATS = 1) */
@@ -241,11 +247,24 @@ int aukit_decode_resample(aukit_ctx *ctx, const aukit_batch *in, const aukit_cod
  *                         AUKIT_E_UNSUPPORTED here;
  *   AUKIT_CODEC_ADPCM_WAV the `data` chunk of an IMA-ADPCM WAV file: `channels` (1 or 2), `sample_rate` and `block_align`, each the stream's own.  A
  *                         pre-pass decodes every block, a lane each, to int16 rows beside the QOA streams'.
+ * and a sixth only on a context that asked for it, AUKIT_OPT_MIXED_CODECS with bit 1 << AUKIT_CODEC_MSADPCM (without it the codec is refused by
+ * name, in the words of before the option):
+ *   AUKIT_CODEC_MSADPCM   the `data` chunk of an MS-ADPCM WAV file (format tag 2), aukit.msadpcm (aukit.lua:1283-1353): `channels` (1 or 2),
+ *                         `sample_rate` (>= 1), `block_align` (>= 7 * channels; a block that is only a header gives its two samples), `ncoef`,
+ *                         `coef1`, `coef2` (ncoef > 0: min(ncoef, 32) pairs; else the seven defaults), each the stream's own.  One channel: every
+ *                         block is decoded from the STREAM'S FIRST seven bytes (`str_unpack("<!1Bhhh", data)` has no position, :1331) — predictor
+ *                         index, delta and both samples are the first block's, bytes 0 .. 6 of every later block are skipped unread, and only the
+ *                         first block's predictor index can be beyond the coefficient table.  A third pre-pass (k_ms_mixed: a run of up to 64
+ *                         blocks of one stream per workgroup, a lane per block, int32) decodes these streams to int16 rows beside the QOA and IMA
+ *                         streams'.  Two exceptions to "what the stream's own call gives", both AUKIT_E_UNSUPPORTED naming the stream and
+ *                         pointing to aukit_decode_resample: a delta of 2^21 or more anywhere in the stream (where the single call leaves its
+ *                         int32 path; no encoder writes one), and a coefficient pair with |c1| + |c2| >= 65536.
  * Interpolation none / linear / cubic; any other codec or interpolation is AUKIT_E_UNSUPPORTED by name.  n_descs must be the batch's stream count;
  * without `mono` the streams must agree in channel count (AUKIT_E_ARG).  A stream whose own call would fail fails the whole call with that status
  * and message, the stream's index appended.  Ordering: everything that can refuse does so before `*out` is touched — the descriptor and length
- * checks of the host, and what only the device can tell (a QOA walk's verdict, a two-channel IMA block whose step index is beyond 88): the QOA and
- * IMA pre-passes write context scratch only, and they run, and their verdicts are read back, first.  A refused call leaves `*out` and its samples as
+ * checks of the host, and what only the device can tell (a QOA walk's verdict, a two-channel IMA block whose step index is beyond 88, an
+ * MS-ADPCM predictor index beyond the coefficient table or a delta of 2^21; of several offenders the lowest stream is named): the QOA, IMA and
+ * MS-ADPCM pre-passes write context scratch only, and they run, and their verdicts are read back, first.  A refused call leaves `*out` and its samples as
  * they were. */
 int aukit_decode_resample_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs /* n */, uint32_t n_descs,
                                 double new_rate, int interp, int mono, int dtype, aukit_audio **out);
