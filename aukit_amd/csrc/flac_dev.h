@@ -1,5 +1,5 @@
-// flac_dev.h — what the two FLAC decoders (flac.hip: extract → chain → restore; flac_stream.hip / flac_pq.hip: decode → chain → gather) share: stream / candidate /
-// frame records, the byte-position hash table, the error codes of decodeFrame (aukit.lua:510-567).
+// flac_dev.h — what the two FLAC decoder designs (flac_first.hip: extract → chain → restore; flac_stream.hip / flac_pq.hip: decode → chain → gather) and their one
+// host driver (flac.hip) share: stream / candidate / frame records, the byte-position hash table, the error codes of decodeFrame (aukit.lua:510-567), the launch functions.
 #pragma once
 #include "resample.h"
 
@@ -73,6 +73,28 @@ struct Carve {
     size_t take(size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; }
 };
 struct Counters { u64 ncand, scratch_cursor, kind_count[16], kind_fill[16]; unsigned flags, ticket; u64 stats[8]; };   // stats: -DAUKIT_FLAC_STATS builds of k_flac_stream count their rounds and turns here; the host does not read them
+
+// The tables of one decode call, carved out of one buffer by the host driver (flac.hip: flac_drive); both designs' launches take them from here.
+struct FlacTables {
+    FlacGlobals G;
+    Counters *cnt;
+    ChainOut *chain;      // [n]
+    Cand *cand;           // [capc], `ncand` of them filled
+    CandInfo *ci;
+    CandHash H;
+    u64 *rowoff, *fbase;  // [n * C], [n]
+    unsigned ncand;
+    u64 scap;             // elements of the frame scratch (ctx->tmp_buf3)
+    int C, depth;         // channels / bit depth of the batch
+};
+
+// ---- the first design (flac_first.hip): extract → chain → jobs → restore (→ finish), rows in ctx->tmp_buf: int32, or double when `wide`
+// candidates [first, first + count) → values in the scratch, predictors in sd[candidate * C + channel]
+int flac_first_extract_launch(aukit_ctx *ctx, const FlacTables &T, SubDesc *sd, unsigned first, unsigned count, int limit_factor, bool wide);
+// the walk from every stream's first frame → T.chain, and the jobs per order class → T.cnt->kind_count
+int flac_first_chain_launch(aukit_ctx *ctx, const FlacTables &T, const SubDesc *sd, unsigned n);
+// the chained subframes' jobs (kbase[q]: first job of class q, kbase[16]: their number; kbase_dev: the first 16 on the device), the prediction and the tail
+int flac_first_restore_launch(aukit_ctx *ctx, const FlacTables &T, const SubDesc *sd, const u64 *kbase_dev, const u64 (&kbase)[17], SubJob *jobs, FrameRec *frames, u64 tot, u64 nfr, bool wide);
 
 // ---- the fused decoders (flac_stream.hip, flac_pq.hip): decodeFrame (:510-567) with the prediction (:411-419), the wasted-bits shift (:467-469), the stereo decorrelation and the
 // wrap (:482-507) done by the lane that reads the frame's bits — final integers leave the kernel once

@@ -712,6 +712,24 @@ def h_beyond_int16(seed=0):
     return encode_stream(pcm, 16, 256, lambda f, c: dict(kind="verbatim") if f == 3 else _e_plan(f, c), asgn=lambda f: 8 if f == 3 else (1, 9, 10)[f % 3])
 
 
+# ---- I: streams that send the host driver round its retry loops (tests/test_flac_retry_host.py, tests/test_gpu_flac_retry.py)
+@functools.lru_cache(maxsize=None)
+def i_table_growth():
+    """mono 16-bit, 4400 frames of 16 samples: more real frames than the driver's first candidate table holds"""
+    x = _signal(4400 * 16, 16, _rng(0x14), amp=0.3)
+    return encode_stream(x[:, None], 16, 16, lambda f, c: dict(kind="fixed", order=1))
+
+
+@functools.lru_cache(maxsize=None)
+def i_scratch_growth():
+    """stereo 16-bit, 40 000 samples per channel, whose STREAMINFO says 0 and 16 samples: the driver's first frame scratch is sized by that"""
+    rng = _rng(0x15)
+    pcm = np.stack([_signal(40000, 16, rng), _signal(40000, 16, rng)], 1)
+    s0 = encode_stream(pcm, 16, 4096, lambda f, c: dict(kind="fixed", order=2), nsamples=0)
+    s16 = Stream(metadata([(0, 34, streaminfo_body(44100, 2, 16, 16))]), s0.frames, s0.pcm, 44100, 2, 16)
+    return {0: s0, 16: s16}
+
+
 def ordinary_pcm(n, ch, seed):
     rng = _rng(0x13, ch, seed)
     return np.stack([_signal(n, 16, rng) for _ in range(ch)], 1)
