@@ -461,7 +461,7 @@ def au(data):  # aukit.lua:1639
 _MAGIC_KIND = {"wav": N.CONTAINER_WAV, "aiff": N.CONTAINER_AIFF, "au": N.CONTAINER_AU}
 
 
-def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm=False):
+def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm=False, stream_ms=False):
     """load_many's host half, up to the device call: every file sniffed by magic as `detect` does and walked by aukit_parse_container
     -> ([descriptor per file], [(first payload byte, byte count) per file], [info table per file]).  A file that is no WAV / AIFF / AU / QOA, or
     whose payload is none of PCM, G.711 and DFPWM, raises LuaError naming the file's index (0-based, the position in `files`).
@@ -479,17 +479,26 @@ def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm
     it such a file is refused by index in the words of before.
     `adpcm` (without `stream`): load_many's switch — a WAV file whose payload is IMA-ADPCM or MS-ADPCM blocks is taken too: the descriptor is the
     container walk's (blockAlign, and for MS-ADPCM the `fmt` chunk's coefficient list), the payload the `data` chunk, the info table aukit.wav's.
-    Without it both are refused by index in the words of before."""
+    Without it both are refused by index in the words of before.
+    `stream_ms` (with `stream`): an MS-ADPCM WAV file (format 2) is taken too — the descriptor is the container walk's (blockAlign and the `fmt`
+    chunk's coefficient list, as `adpcm` takes it for load_many), the payload the `data` chunk, the length what aukit.stream.wav returns for the
+    file.  Without it such a file is refused by index in the words of before, whatever `stream_ima` and `adpcm` say."""
     _expect(1, files, "table")
     takes = "PCM, G.711 and DFPWM" if stream_dfpwm else "PCM and G.711"
-    if stream_ima:
+    if stream_ima and stream_ms:
+        takes += " payloads and IMA-ADPCM and MS-ADPCM blocks"
+    elif stream_ima:
         takes += " payloads and IMA-ADPCM blocks"
+    elif stream_ms:
+        takes += " payloads and MS-ADPCM blocks"
     served = (N.CODEC_PCM, N.CODEC_G711) if stream and not stream_dfpwm else (N.CODEC_PCM, N.CODEC_G711, N.CODEC_DFPWM)
     if stream and stream_ima:
         served += (N.CODEC_ADPCM_WAV,)
+    if stream and stream_ms:
+        served += (N.CODEC_MSADPCM,)
     if adpcm and not stream:
         served += (N.CODEC_ADPCM_WAV, N.CODEC_MSADPCM)
-    others = "the other block codecs" if stream_ima else "the block codecs"
+    others = "the other block codecs" if stream_ima or stream_ms else "the block codecs"
     descs, ranges, infos = [], [], []
     for i, f in enumerate(files):
         if isinstance(f, (list, tuple)):
@@ -859,7 +868,7 @@ class _StreamNS:
             it, length = self._run(d, p, mono, dtype, endless_empty=d.codec == N.CODEC_G711)
         return it, (length if math.isnan(c.length_seconds) else c.length_seconds)
 
-    def many(self, files, mono=None, adpcm=None):
+    def many(self, files, mono=None, adpcm=None, msadpcm=None):
         """aukit.stream.wav / aiff / au (file, mono) for a LIST of whole files of any mix of containers, rates, PCM formats / G.711 / DFPWM /
         IMA-ADPCM WAV blocks (each file its own blockAlign; the raise behind a block whose header step index is above 88 included) and
         channel counts: the payload ranges go up as one batch, one aukit_stream_decode_mixed call computes every iterator call of every file, and
@@ -868,17 +877,29 @@ class _StreamNS:
         A raw .dfpwm file, which has no header, is given as (data, "dfpwm"[, channels[, sampleRate]]) — load_many's tuple, channels first — and
         its pair is aukit.stream.dfpwm(data, sampleRate, channels, mono)'s.
         IMA-ADPCM WAV files are taken on request only — `adpcm=True`, or `mono` given as the options table of the LuaJIT shim,
-        {"mono": ..., "adpcm": True} —: without it such a file is refused by index, as before aukit_stream_decode_mixed took the codec."""
+        {"mono": ..., "adpcm": True} —: without it such a file is refused by index, as before aukit_stream_decode_mixed took the codec.
+        `adpcm` means IMA-ADPCM only.  MS-ADPCM WAV files (format 2: aukit.stream.wav's dispatch to aukit.stream.msadpcm with the file's blockAlign
+        and coefficient list) are taken with `msadpcm=True`, or the key "msadpcm" of the options table: for this one call the context is opted in
+        to MS-ADPCM descriptors (AUKIT_OPT_STREAM_MIXED_CODECS) and put back as it was behind it, also where the call is refused.  Without it
+        such a file is refused by index, as before."""
         if isinstance(mono, dict):
-            if set(mono) - {"mono", "adpcm"}:
-                raise LuaError("bad argument #2 (unknown option " + sorted(set(mono) - {"mono", "adpcm"})[0] + ")")
-            mono, adpcm = mono.get("mono"), mono.get("adpcm", adpcm)
+            if set(mono) - {"mono", "adpcm", "msadpcm"}:
+                raise LuaError("bad argument #2 (unknown option " + sorted(set(mono) - {"mono", "adpcm", "msadpcm"})[0] + ")")
+            mono, adpcm, msadpcm = mono.get("mono"), mono.get("adpcm", adpcm), mono.get("msadpcm", msadpcm)
         _expect(2, mono, "boolean", "nil")
         _expect(3, adpcm, "boolean", "nil")
-        descs, ranges, lengths = _sniff_many(files, stream=True, stream_dfpwm=True, stream_ima=bool(adpcm))
+        _expect(4, msadpcm, "boolean", "nil")
+        descs, ranges, lengths = _sniff_many(files, stream=True, stream_dfpwm=True, stream_ima=bool(adpcm), stream_ms=bool(msadpcm))
         ctx = context()
         bt = _wrap(B.Batch.upload, ctx, [bytes((f[0] if isinstance(f, (list, tuple)) else f)[o:o + n]) for f, (o, n) in zip(files, ranges)])
-        out, ck = _wrap(B.stream_decode_mixed, ctx, bt, descs, _interp(defaultInterpolation, 0), bool(mono), N.F64)
+        was = ctx.option(N.OPT_STREAM_MIXED_CODECS)
+        try:
+            if msadpcm:
+                _wrap(ctx.set_option, N.OPT_STREAM_MIXED_CODECS, was | 1 << N.CODEC_MSADPCM)
+            out, ck = _wrap(B.stream_decode_mixed, ctx, bt, descs, _interp(defaultInterpolation, 0), bool(mono), N.F64)
+        finally:
+            if msadpcm:
+                ctx.set_option(N.OPT_STREAM_MIXED_CODECS, was)
         rows = out.download()
         return [self._chunk_iter(out, ck, None if math.isnan(lengths[i]) else lengths[i], d.codec == N.CODEC_G711, i, rows) for i, d in enumerate(descs)]
 

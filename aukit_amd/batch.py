@@ -611,7 +611,11 @@ def stream_decode_mixed(ctx, batch, descs, interp, mono=False, dtype=None, out=N
     """aukit_stream_decode_mixed: aukit.stream.pcm / aukit.stream.g711 / aukit.stream.dfpwm of stream s with descs[s] (PCM of any format at or below
     48 kHz, G.711 at integer rates, DFPWM with the descriptor's channels and rate: a pre-pass decodes those streams to int8 rows first;
     aukit.stream.adpcm for CODEC_ADPCM_WAV with the descriptor's channels, rate and block_align: a header scan, then a pre-pass to int16 rows), every
-    iterator call at once — one call, one resample launch -> (AudioBatch at 48 kHz in the batch's order, Chunks).  `descs`: one
+    iterator call at once — one call, one resample launch -> (AudioBatch at 48 kHz in the batch's order, Chunks).  aukit.stream.msadpcm for
+    CODEC_MSADPCM (channels 1 or 2, rate, block_align and the coefficient list of make_desc) only on a context that asked this call for it:
+    ctx.set_option(N.OPT_STREAM_MIXED_CODECS, 1 << N.CODEC_MSADPCM) — option 6; OPT_MIXED_CODECS is decode_resample_mixed's and means nothing
+    here.  Those streams pay a third pre-pass (k_ms_mixed, int16 rows); a predictor index beyond the coefficient table, a delta of 2^21 or more
+    and a coefficient pair with |c1| + |c2| >= 65536 refuse the call by the stream's index, before `out` / `chunks` are touched.  `descs`: one
     CodecDesc per stream.  `out` / `chunks`: what an earlier call returned — the audio's buffers are reused, the chunk table is replaced (after
     a refusal both keep what they held)."""
     out = out if out is not None else AudioBatch(ctx)

@@ -51,6 +51,7 @@ struct aukit_ctx {
                                 //   one does not apply), 2 = always the reference-order kernels; 0 = f32 taps
     bool chan_lens = false;     // AUKIT_OPT_CHANNEL_LENS: the host reads chunk lengths per channel (stream.pcm delivers its uneven last chunk)
     unsigned mixed_codecs = 0;  // AUKIT_OPT_MIXED_CODECS: bit 1 << codec lets aukit_decode_resample_mixed take that codec beyond its default list
+    unsigned stream_mixed_codecs = 0;  // AUKIT_OPT_STREAM_MIXED_CODECS: the same for aukit_stream_decode_mixed, which reads this mask and no other
     bool fast_store_x4 = true;  // AUKIT_OPT_STORE_X4: LDS-transposed 16-byte stores in the fast kernels
     std::string last_kernel;
     float last_ms = 0.f;

@@ -1,7 +1,7 @@
 // mixed_plan.h — what the two per-stream-descriptor calls share on the host (aukit_decode_resample_mixed, resample_mixed.hip;
 // aukit_stream_decode_mixed, stream_mixed.hip): the checks of the call's own arguments, the class index, the tile-height search, the grid, the
-// launcher of a kernel template instantiated over <INTERP, OUT_T, flags...>, the driver of the DFPWM row pre-pass, and the layout of the
-// pre-passes' scratch in ctx->tmp_buf.  Host only: no kernel lives here.
+// launcher of a kernel template instantiated over <INTERP, OUT_T, flags...>, the driver of the DFPWM row pre-pass, the unit planner of the MS-ADPCM
+// row pre-pass, and the layout of the pre-passes' scratch in ctx->tmp_buf.  Host only: no kernel lives here.
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -95,8 +95,9 @@ static inline int mixed_launch(aukit_ctx *ctx, const aukit_batch *in, const auki
 // Tile height of a class: the staged window (tile_out / eff_ratio + slack doubles) x staged channels x 8 B within plan_tiles' budget of 24 KiB, where
 // that leaves at least 256 outputs; `hard` bytes at the most (what a launch may ask for).  slack: the halos, the vector paths' alignment head and
 // tail and the kernel's own margin.  -> *tile_out, and *cap: LDS doubles per staged channel (even).  `ratio`, `s`: for the words of the refusal
-static inline int mixed_tile_height(double ratio, double eff_ratio, int staged, int slack, size_t hard, unsigned s, int *tile_out, int *cap) {
-    auto cap_for = [&](int to) { return (int)std::ceil((double)to / eff_ratio) + slack; };
+// `table`: where a tile's window cannot leave a table of that many entries (a block codec's block), the window is that at the most
+static inline int mixed_tile_height(double ratio, double eff_ratio, int staged, int slack, size_t hard, unsigned s, int *tile_out, int *cap, uint64_t table = ~0ull) {
+    auto cap_for = [&](int to) { return (int)std::min<double>(std::ceil((double)to / eff_ratio), (double)std::min<uint64_t>(table, 1ull << 30)) + slack; };
     const size_t budget = 24 * 1024;
     int to = 2048;
     while (to > 256 && (size_t)cap_for(to) * 8 * staged > budget) to -= 256;
@@ -158,6 +159,83 @@ static inline int mixed_dfpwm_rows(aukit_ctx *ctx, const aukit_batch *in, const 
         } else declined->push_back(g);
     }
     return AUKIT_OK;
+}
+
+// ---- the MS-ADPCM row pre-pass (k_ms_mixed, msadpcm_mixed.hip): the blocks of every MS-ADPCM stream of a batch decoded to int16 rows, one per
+// (stream, channel), blocks back to back, samplesPerBlock + 2 entries each.  The work unit is a run of up to 64 consecutive blocks of one stream
+struct MsMixUnit {
+    unsigned long long src_off;   // the unit's first block, relative to the batch's data
+    unsigned long long hdr_off;   // one channel: the stream's first byte
+    unsigned long long row_off;   // int16 elements from `rows`: channel 0, the unit's first sample
+    unsigned stride;              // elements between the channels' rows (a multiple of 8)
+    unsigned nblk, block_align, stream;
+    unsigned short coef_set, ncoef;
+    unsigned short channels, plain;
+};
+static_assert(sizeof(MsMixUnit) == 48, "MsMixUnit layout");
+size_t ms_mixed_unit_lds(uint64_t nblk, uint64_t block_align, int channels);
+int ms_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const void *d_units, uint64_t n_units, const void *d_coefs, short *rows, unsigned *flags, size_t lds, uint64_t bytes);
+// LDS a unit of k_ms_mixed may stage (source span and output spans): five workgroups of one wave each on a CU's 160 KiB.  A block that does not fit
+// alone (5 * blockAlign + 28 bytes or so: blockAlign above about 6550) takes the kernel's plain path
+constexpr size_t MS_MIX_LDS = 32 * 1024;
+// blocks per unit of k_ms_mixed for a stream's geometry: as many as fit MS_MIX_LDS, 64 at the most; 0: a single block does not fit (the plain path)
+static inline unsigned mix_ms_blocks_per_unit(uint64_t ba, int C) {
+    if (ms_mixed_unit_lds(1, ba, C) > MS_MIX_LDS) return 0;
+    unsigned t = 64;
+    while (ms_mixed_unit_lds(t, ba, C) > MS_MIX_LDS) t--;
+    return t;
+}
+// the stream's coefficient table: min(ncoef, 32) pairs of the descriptor, or the seven defaults (:1304) -> count; c1[32], c2[32], zeros behind the count
+static inline int mixed_ms_coefs(const aukit_codec_desc *d, int *tab) {
+    static const int c1d[7] = {256, 512, 0, 192, 240, 460, 392}, c2d[7] = {0, -256, 0, 64, 0, -208, -232};
+    std::fill(tab, tab + 64, 0);
+    const int nc = d->ncoef > 0 ? std::min(d->ncoef, 32) : 7;
+    for (int i = 0; i < nc; i++) { tab[i] = d->ncoef > 0 ? d->coef1[i] : c1d[i]; tab[32 + i] = d->ncoef > 0 ? d->coef2[i] : c2d[i]; }
+    return nc;
+}
+// k_ms_mixed's int32 sums need 16-bit operands (ms_fill_coefs' condition, where the single call leaves its wave kernel): the first pair with
+// |c1| + |c2| >= 65536, or -1
+static inline int mixed_ms_wide_pair(const aukit_codec_desc *d) {
+    int tab[64];
+    const int nc = mixed_ms_coefs(d, tab);
+    for (int i = 0; i < nc; i++)
+        if (std::abs(tab[i]) + std::abs(tab[32 + i]) >= 65536) return i;
+    return -1;
+}
+// the unit table of a batch's MS-ADPCM streams and their distinct coefficient sets (c1[32], c2[32] each); source bytes, the largest staged unit's LDS
+struct MsMixPlan {
+    std::vector<MsMixUnit> units;
+    std::vector<int> coefs;
+    uint64_t src = 0;   // (the caller's to count)
+    size_t lds = 0;
+    // stream s: nblk blocks of d.block_align bytes from byte src_off of the batch's data on; its channel 0's row starts at element row_off of the
+    // rows (a multiple of 8), channel 1's `stride` elements (a multiple of 8) behind
+    void add_stream(const aukit_codec_desc &d, unsigned s, uint64_t src_off, uint64_t nblk, uint64_t row_off, uint64_t stride) {
+        const uint64_t ba = (uint64_t)d.block_align, C = (uint64_t)d.channels, spb = C == 2 ? (ba - 14) + 2 : (ba - 7) * 2 + 2;
+        int tab[64];
+        const int nc = mixed_ms_coefs(&d, tab);
+        size_t set = 0;
+        for (; set < coefs.size() / 64; set++)
+            if (std::equal(tab, tab + 64, coefs.begin() + set * 64)) break;
+        if (set == coefs.size() / 64) coefs.insert(coefs.end(), tab, tab + 64);
+        const unsigned T = mix_ms_blocks_per_unit(ba, (int)C), step = T ? T : 64;
+        for (uint64_t b0 = 0; b0 < nblk; b0 += step) {
+            MsMixUnit u;
+            u.src_off = src_off + b0 * ba; u.hdr_off = src_off; u.row_off = row_off + b0 * spb;
+            u.stride = (unsigned)stride; u.nblk = (unsigned)std::min<uint64_t>(step, nblk - b0); u.block_align = (unsigned)ba; u.stream = s;
+            u.coef_set = (unsigned short)set; u.ncoef = (unsigned short)nc; u.channels = (unsigned short)C; u.plain = T ? 0 : 1;
+            if (T) lds = std::max(lds, ms_mixed_unit_lds(u.nblk, ba, (int)C));
+            units.push_back(u);
+        }
+    }
+};
+// k_ms_mixed's two flag words (the lowest stream with a predictor index beyond its table; with a delta of 2^21 or more; 0xFFFFFFFF: none) as the
+// call's answer: of several offenders the lowest stream is named, the index before the delta (the reference raises there).  `single`: the call
+// that serves such a delta
+static inline int mixed_ms_verdict(unsigned bad_index, unsigned big_delta, const char *single) {
+    if (bad_index == 0xFFFFFFFFu && big_delta == 0xFFFFFFFFu) return AUKIT_OK;
+    if (bad_index <= big_delta) return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (local 'c1') (stream %u)", bad_index);
+    return fail(AUKIT_E_UNSUPPORTED, "MS-ADPCM delta of 2^21 or more: %s takes this stream (stream %u)", single, big_delta);
 }
 
 // ---- the pre-passes' scratch: regions of ctx->tmp_buf, one behind the other, each at a multiple of 256 bytes with `tail` bytes to spare behind it

@@ -24,6 +24,7 @@
 #include <type_traits>
 #include "resample.h"
 #include "resample_dev.h"
+#include "ms_geom.h"
 
 namespace aukit {
 
@@ -142,13 +143,7 @@ __global__ __launch_bounds__(64) void k_msadpcm(const MsParams P) {
     }
 }
 
-// a stream that ends inside a block: the reference's error is that of the first read that finds nothing — the header's str_unpack (stereo: fewer than 14
-// bytes left, :1310; mono reads the stream's first 7 bytes for every block, :1331), else str_byte's nil in bit32_rshift (:1317-1318, :1336-1337)
-static int ms_partial_block(int C, uint64_t nb, uint64_t ba) {
-    if (C == 2 ? nb % ba < 14 : nb < 7) return fail(AUKIT_E_LUA, "data string too short");
-    return fail(AUKIT_E_LUA, "bad argument #1 to 'rshift' (number expected, got nil)");
-}
-
+// (a stream that ends inside a block: ms_partial_block, ms_geom.h)
 static const int ms_c1_default[7] = {256, 512, 0, 192, 240, 460, 392}, ms_c2_default[7] = {0, -256, 0, 64, 0, -208, -232};  // :1304
 
 // decodes every block of every stream into fp64 rows in ctx->tmp_buf; rows are per (stream, channel), blocks back to back
@@ -1023,12 +1018,10 @@ int stream_msadpcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc
     }
     const uint64_t ba = (uint64_t)d->block_align;
     const uint64_t spb_dec = C == 2 ? (ba - 14) + 2 : (ba - 7) * 2 + 2;
-    const double ratio = 48000 / d->sample_rate;
-    const double samplesPerBlock = C == 2 ? (double)(ba - 14) : (double)(ba - 7) * 2;  // :2617 / :2682 (2 short, Q9)
-    const double ips_d = std::ceil(d->sample_rate / samplesPerBlock);
-    const double bytesPerSecond = (double)ba * ips_d;
-    const uint32_t newlen = (uint32_t)std::max(0.0, std::floor(samplesPerBlock * ratio));
-    const uint64_t ips = (uint64_t)ips_d;
+    const MsGeom G(C, d->block_align, d->sample_rate);  // :2617-2620 / :2682-2685 (samplesPerBlock 2 short, Q9)
+    const double ratio = G.ratio, samplesPerBlock = G.spb, bytesPerSecond = G.bytes_per_second;
+    const uint32_t newlen = (uint32_t)G.newlen_d;
+    const uint64_t ips = G.ips;
     const int nd = (C == 2 && !mono) ? 2 : 1;
     ChunksOwner ck = chunks_create(in->n);
     std::vector<uint64_t> lens(in->n, 0);

@@ -18,20 +18,11 @@
 // memory (unaligned dword loads) to the rows (element stores).
 // One channel: every block is decoded from the stream's FIRST header (:1331, `str_unpack` without a position); a block's own first seven bytes are
 // never read.  A predictor index at or beyond the coefficient count, in a block with at least one data byte, lowers flags[0] likewise.
-#include "resample.h"
+// aukit_stream_decode_mixed (stream_mixed.hip) runs the same pre-pass on the MS-ADPCM streams of its batch and reads the rows block by block; the
+// unit record and its planner are in mixed_plan.h.
+#include "mixed_plan.h"
 
 namespace aukit {
-
-struct MsMixUnit {
-    unsigned long long src_off;   // the unit's first block, relative to the batch's data
-    unsigned long long hdr_off;   // one channel: the stream's first byte
-    unsigned long long row_off;   // int16 elements from `rows`: channel 0, the unit's first sample
-    unsigned stride;              // elements between the channels' rows (a multiple of 8)
-    unsigned nblk, block_align, stream;
-    unsigned short coef_set, ncoef;
-    unsigned short channels, plain;
-};
-static_assert(sizeof(MsMixUnit) == 48, "MsMixUnit layout");
 
 struct MsMixParams {
     const unsigned char *src, *safe_lo, *safe_hi;   // a 16-byte load at p needs safe_lo <= p and p + 16 <= safe_hi

@@ -38,17 +38,7 @@ int qoa_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<Qo
 size_t qoa_mixed_job_bytes(uint64_t njobs);
 struct ImaMixJob { unsigned long long src_off, row_off; unsigned nbytes, stream; int c, channels; };  // codecs.hip
 int ima_mixed_decode(aukit_ctx *ctx, const unsigned char *src, const void *d_jobs, uint64_t njobs, short *rows, unsigned *flag, uint64_t bytes);
-struct MsMixUnit {  // msadpcm_mixed.hip: a run of up to 64 consecutive blocks of one MS-ADPCM stream
-    unsigned long long src_off, hdr_off, row_off;
-    unsigned stride, nblk, block_align, stream;
-    unsigned short coef_set, ncoef, channels, plain;
-};
-static_assert(sizeof(MsMixUnit) == 48, "MsMixUnit layout");
-size_t ms_mixed_unit_lds(uint64_t nblk, uint64_t block_align, int channels);
-int ms_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const void *d_units, uint64_t n_units, const void *d_coefs, short *rows, unsigned *flags, size_t lds, uint64_t bytes);
-// LDS a unit of k_ms_mixed may stage (source span and output spans): five workgroups of one wave each on a CU's 160 KiB.  A block that does not fit
-// alone (5 * blockAlign + 28 bytes or so: blockAlign above about 6550) takes the kernel's plain path
-constexpr size_t MS_MIX_LDS = 32 * 1024;
+// (the MS-ADPCM streams' pre-pass, k_ms_mixed of msadpcm_mixed.hip, and its unit planner: mixed_plan.h)
 
 constexpr int MIX_SRC_I16 = 100;  // MixClass::codec of a QOA or IMA-ADPCM class: the window comes from int16 rows in the scratch behind MixParams::rows, one per channel
 
@@ -249,14 +239,6 @@ static int check_mixed_msadpcm(const aukit_codec_desc *d, uint64_t nb, uint64_t 
     *frames = nblk * (C == 2 ? (ba - 14) + 2 : (ba - 7) * 2 + 2);
     return AUKIT_OK;
 }
-// the stream's coefficient table: min(ncoef, 32) pairs of the descriptor, or the seven defaults (:1304) -> count; c1[32], c2[32], zeros behind the count
-static int mixed_ms_coefs(const aukit_codec_desc *d, int *tab) {
-    static const int c1d[7] = {256, 512, 0, 192, 240, 460, 392}, c2d[7] = {0, -256, 0, 64, 0, -208, -232};
-    std::fill(tab, tab + 64, 0);
-    const int nc = d->ncoef > 0 ? std::min(d->ncoef, 32) : 7;
-    for (int i = 0; i < nc; i++) { tab[i] = d->ncoef > 0 ? d->coef1[i] : c1d[i]; tab[32 + i] = d->ncoef > 0 ? d->coef2[i] : c2d[i]; }
-    return nc;
-}
 
 // ---- phase 1: validation.  What the batch is, per stream, once nothing is left to refuse from descriptors, byte counts and QOA headers
 struct MixStreams {
@@ -320,13 +302,8 @@ static int mix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
             if (!(rc = check_mixed_ima(&descs[s], nb, &S.frames[s]))) rc = check_mixed_rows(S.rate[s], new_rate, S.frames[s], &S.lens[s]);
         } else if (codec == AUKIT_CODEC_MSADPCM) {
             if (!(rc = check_mixed_msadpcm(&descs[s], nb, &S.frames[s]))) rc = check_mixed_rows(S.rate[s], new_rate, S.frames[s], &S.lens[s]);
-            if (!rc) {  // (k_ms_mixed's int32 sums need 16-bit operands: ms_fill_coefs' condition, where the single call leaves its wave kernel)
-                int tab[64];
-                const int nc = mixed_ms_coefs(&descs[s], tab);
-                for (int i = 0; i < nc && !rc; i++)
-                    if (std::abs(tab[i]) + std::abs(tab[32 + i]) >= 65536)
-                        rc = fail(AUKIT_E_UNSUPPORTED, "MS-ADPCM coefficient pair %d with |c1| + |c2| >= 65536: aukit_decode_resample takes this stream", i);
-            }
+            const int wide = rc ? -1 : mixed_ms_wide_pair(&descs[s]);
+            if (wide >= 0) rc = fail(AUKIT_E_UNSUPPORTED, "MS-ADPCM coefficient pair %d with |c1| + |c2| >= 65536: aukit_decode_resample takes this stream", wide);
         } else rc = check_mixed_stream(&descs[s], nb, new_rate, &S.frames[s], &S.lens[s]);
         if (rc) return fail_for_stream(rc, s);
         if (codec == AUKIT_CODEC_DFPWM) { S.has_df = true; S.in_bytes += mixed_dfpwm_fed(nb) * 8; }
@@ -426,18 +403,9 @@ struct MixI16Rows {
     std::vector<ImaMixJob> ijobs;   // one job per (IMA block, channel): where the block is, how long, where its samples go
     uint64_t el = 0, q_jobs = 0, q_src = 0, i_src = 0;  // elements of all rows; QOA jobs; source bytes of the QOA / the IMA streams
     bool stereo_ima = false;
-    std::vector<MsMixUnit> munits;  // the MS-ADPCM tile table: one unit per run of consecutive blocks of a stream, as many as MS_MIX_LDS holds (64 at the most)
-    std::vector<int> mcoefs;        // the distinct coefficient sets: c1[32], c2[32] each
-    uint64_t m_src = 0, m_el = 0;   // source bytes and row elements of the MS-ADPCM streams
-    size_t m_lds = 0;               // the largest staged unit's LDS
+    MsMixPlan ms;                   // the MS-ADPCM unit table (mixed_plan.h) and the distinct coefficient sets
+    uint64_t m_el = 0;              // row elements of the MS-ADPCM streams
 };
-// blocks per unit of k_ms_mixed for a stream's geometry: as many as fit MS_MIX_LDS, 64 at the most; 0: a single block does not fit (the plain path)
-static unsigned mix_ms_blocks_per_unit(uint64_t ba, int C) {
-    if (ms_mixed_unit_lds(1, ba, C) > MS_MIX_LDS) return 0;
-    unsigned t = 64;
-    while (ms_mixed_unit_lds(t, ba, C) > MS_MIX_LDS) t--;
-    return t;
-}
 static MixI16Rows mix_i16_plan(const aukit_batch *in, const aukit_codec_desc *descs, const MixStreams &S) {
     MixI16Rows R;
     R.row.assign(in->n, 0);
@@ -448,23 +416,9 @@ static MixI16Rows mix_i16_plan(const aukit_batch *in, const aukit_codec_desc *de
         R.row[s] = R.el;
         if (codec == AUKIT_CODEC_QOA) { R.q_rows.push_back(R.el); R.q_jobs += S.Q[qk++].njobs; R.q_src += nb; }
         else if (codec == AUKIT_CODEC_MSADPCM) {
-            const uint64_t ba = (uint64_t)descs[s].block_align, C = (uint64_t)S.ch[s], spb = C == 2 ? (ba - 14) + 2 : (ba - 7) * 2 + 2, nblk = (nb + ba - 1) / ba;
-            int tab[64];
-            const int nc = mixed_ms_coefs(&descs[s], tab);
-            size_t set = 0;
-            for (; set < R.mcoefs.size() / 64; set++)
-                if (std::equal(tab, tab + 64, R.mcoefs.begin() + set * 64)) break;
-            if (set == R.mcoefs.size() / 64) R.mcoefs.insert(R.mcoefs.end(), tab, tab + 64);
-            const unsigned T = mix_ms_blocks_per_unit(ba, (int)C), step = T ? T : 64;
-            for (uint64_t b0 = 0; b0 < nblk; b0 += step) {
-                MsMixUnit u;
-                u.src_off = in->off[s] + b0 * ba; u.hdr_off = in->off[s]; u.row_off = R.el + b0 * spb;
-                u.stride = (unsigned)stride; u.nblk = (unsigned)std::min<uint64_t>(step, nblk - b0); u.block_align = (unsigned)ba; u.stream = s;
-                u.coef_set = (unsigned short)set; u.ncoef = (unsigned short)nc; u.channels = (unsigned short)C; u.plain = T ? 0 : 1;
-                if (T) R.m_lds = std::max(R.m_lds, ms_mixed_unit_lds(u.nblk, ba, (int)C));
-                R.munits.push_back(u);
-            }
-            R.m_src += nb;
+            const uint64_t ba = (uint64_t)descs[s].block_align, C = (uint64_t)S.ch[s];
+            R.ms.add_stream(descs[s], s, in->off[s], (nb + ba - 1) / ba, R.el, stride);
+            R.ms.src += nb;
             R.m_el += stride * C;
         } else {
             const uint64_t ba = (uint64_t)descs[s].block_align, C = (uint64_t)S.ch[s], spb = (ba - 4 * C) * 2 / C;
@@ -490,8 +444,8 @@ static MixScratch mix_scratch(const MixStreams &S, const MixDfRows &D, const Mix
         L.i16_at = carve.take((size_t)R.el * 2);
         L.qj_at = carve.take(S.q_list.empty() ? 0 : qoa_mixed_job_bytes(R.q_jobs), 0);
         L.ij_at = carve.take(R.ijobs.size() * sizeof(ImaMixJob), 0);
-        L.mu_at = carve.take(R.munits.size() * sizeof(MsMixUnit), 0);
-        L.mc_at = carve.take(R.mcoefs.size() * sizeof(int), 0);
+        L.mu_at = carve.take(R.ms.units.size() * sizeof(MsMixUnit), 0);
+        L.mc_at = carve.take(R.ms.coefs.size() * sizeof(int), 0);
         L.flag_at = carve.take(12, 52);  // the IMA flag, then the two MS-ADPCM words (predictor index, delta)
     }
     L.size = carve.end;
@@ -506,28 +460,27 @@ static int mix_i16_prepass(aukit_ctx *ctx, const aukit_batch *in, const MixStrea
     char *const T = reinterpret_cast<char *>(ctx->tmp_buf.p);
     short *const rows16 = reinterpret_cast<short *>(T + L.i16_at);
     if (!S.q_list.empty() && (rc = qoa_mixed_decode(ctx, in, S.Q, R.q_rows.data(), rows16, T + L.qj_at, R.q_src))) return rc;
-    if (R.ijobs.empty() && R.munits.empty()) return AUKIT_OK;
+    if (R.ijobs.empty() && R.ms.units.empty()) return AUKIT_OK;
     unsigned *flag = reinterpret_cast<unsigned *>(T + L.flag_at);
     AUKIT_HIP_CHECK(hipMemsetAsync(flag, 0xFF, 12, ctx->stream));
     if (!R.ijobs.empty()) {
         if ((rc = h2d_table(ctx, T + L.ij_at, R.ijobs.data(), R.ijobs.size() * sizeof(ImaMixJob)))) return rc;
         if ((rc = ima_mixed_decode(ctx, in->data(), T + L.ij_at, R.ijobs.size(), rows16, flag, R.i_src + (R.el - R.m_el) * 2))) return rc;
     }
-    if (!R.munits.empty()) {
-        if ((rc = h2d_table(ctx, T + L.mu_at, R.munits.data(), R.munits.size() * sizeof(MsMixUnit))) ||
-            (rc = h2d_table(ctx, T + L.mc_at, R.mcoefs.data(), R.mcoefs.size() * sizeof(int))))
+    if (!R.ms.units.empty()) {
+        if ((rc = h2d_table(ctx, T + L.mu_at, R.ms.units.data(), R.ms.units.size() * sizeof(MsMixUnit))) ||
+            (rc = h2d_table(ctx, T + L.mc_at, R.ms.coefs.data(), R.ms.coefs.size() * sizeof(int))))
             return rc;
-        if ((rc = ms_mixed_decode(ctx, in, T + L.mu_at, R.munits.size(), T + L.mc_at, rows16, flag + 1, R.m_lds, R.m_src + R.m_el * 2))) return rc;
+        if ((rc = ms_mixed_decode(ctx, in, T + L.mu_at, R.ms.units.size(), T + L.mc_at, rows16, flag + 1, R.ms.lds, R.ms.src + R.m_el * 2))) return rc;
     }
-    if (R.stereo_ima || !R.munits.empty()) {  // (a one-channel IMA block's masked index cannot leave 0 .. 88: no flag to wait for)
+    if (R.stereo_ima || !R.ms.units.empty()) {  // (a one-channel IMA block's masked index cannot leave 0 .. 88: no flag to wait for)
         unsigned h[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
         AUKIT_HIP_CHECK(hipMemcpyAsync(h, flag, 12, hipMemcpyDeviceToHost, ctx->stream));
         AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         const unsigned low = std::min(h[0], std::min(h[1], h[2]));
         if (low == 0xFFFFFFFFu) return AUKIT_OK;
         if (h[0] == low) return fail(AUKIT_E_ARG, "bad argument #7 (number outside of range) (stream %u)", low);
-        if (h[1] == low) return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (local 'c1') (stream %u)", low);  // (before the delta: the reference raises here)
-        return fail(AUKIT_E_UNSUPPORTED, "MS-ADPCM delta of 2^21 or more: aukit_decode_resample takes this stream (stream %u)", low);
+        return mixed_ms_verdict(h[1], h[2], "aukit_decode_resample");  // (the index before the delta: the reference raises there)
     }
     return AUKIT_OK;
 }

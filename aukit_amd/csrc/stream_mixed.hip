@@ -37,20 +37,34 @@
 // p / (p < 0 and 128 or 127) (:2812; 16-byte loads), runs the position, fall-back and interpolation code of the other kinds and ends in the G.711
 // epilogue: clamp(floor(c_j)) per channel or clamp(floor(((0 + c_1) + c_2 ...) / channels)) (:2818-2828).
 //
+// aukit.stream.msadpcm (data_s, blockAlign, channels, rate, mono, coefficients) (:2588-2736) is the fourth kind (MS = true, launched only for a batch
+// that has an AUKIT_CODEC_MSADPCM stream, which only a context that set AUKIT_OPT_STREAM_MIXED_CODECS hands in).  Its pre-pass is the decode call's:
+// k_ms_mixed (msadpcm_mixed.hip; the unit planner is mixed_plan.h's) decodes every planned block to int16 in ctx->tmp_buf behind the IMA rows — a row
+// per (stream, channel), blocks back to back, samplesPerBlock + 2 entries each, a one-channel block from the stream's first seven bytes (:2706) —
+// and its two flag words (a predictor index beyond the coefficient table; a delta of 2^21 or more) are read back before `*out` is touched.  A
+// segment is a (stream, iterator call) of ceil(rate / samplesPerBlock) blocks; a tile lies within one block, whose table is indices
+// 1 .. samplesPerBlock + 2 with the nil fall-backs at both ends; every block is whole.  A block's table starts at any 2-byte phase of its row (two
+// channels, odd blockAlign: 3 entries at 15), so the tile loads 16-byte vectors from the aligned address at or below its window and carries the head
+// shift (smix_stage_ms).  The staged doubles are floor(p / (p < 0 and 128 or 127)) for two channels (:2648-2662: floored BEFORE interpolation) and the
+// plain quotient for one (:2708-2720); the epilogue is clamp(floor(c)) per channel, or with `mono` on two channels clamp(floor(l + r / 2)) (:2672: the
+// reference's precedence, not the mean).
+//
 // The host half reads as the call's phases: smix_validate, smix_classes, the IMA header scan, one planner per codec (plan_pcm, plan_g711, plan_dfpwm,
-// plan_ima: they fill an SMixPlan and touch neither the context nor HIP), the scratch layout, the two pre-passes, smix_tiles, the launch.  What the
-// call shares with aukit_decode_resample_mixed is in mixed_plan.h, stream.adpcm's arithmetic in ima_geom.h.
+// plan_ima, plan_ms: they fill an SMixPlan and touch neither the context nor HIP), the scratch layout, the MS-ADPCM pre-pass and its verdict, the two
+// other pre-passes, smix_tiles, the launch.  What the call shares with aukit_decode_resample_mixed is in mixed_plan.h, stream.adpcm's arithmetic in
+// ima_geom.h; stream.msadpcm's is in ms_geom.h.
 #include <algorithm>
 #include <memory>
 #include <tuple>
 #include "mixed_plan.h"
 #include "ima_geom.h"
+#include "ms_geom.h"
 #include "resample_dev.h"
 #include "dfpwm_dev.h"
 
 namespace aukit {
 
-enum { SMIX_EPI_PCM = 0, SMIX_EPI_FLOOR = 1, SMIX_EPI_DFPWM = 2 };
+enum { SMIX_EPI_PCM = 0, SMIX_EPI_FLOOR = 1, SMIX_EPI_DFPWM = 2, SMIX_EPI_MS_MONO = 3 };
 
 struct SMixClass {
     double ratio, rcp;     // x = (i - 1) / ratio + 1
@@ -66,20 +80,21 @@ struct SMixClass {
     int exact_rcp;         // 1: RN((i-1)/ratio) via rcp + two fmas is verified exact for 48 001 outputs (DFPWM: for every (i - 1) its longest call reaches)
     int cap;               // LDS doubles per staged channel
     int s16le_mono;        // 16-byte vector staging where the stream's bytes start at an even address
-    unsigned nl_full;      // IMA: floor(samplesPerBlock * ratio), the outputs of a full block  :2768
-    int row_len;           // IMA: int16 entries per (block, channel) in the pre-pass's rows: samplesPerBlock + 8
+    unsigned nl_full;      // IMA: floor(samplesPerBlock * ratio), the outputs of a full block  :2768; MS: of every block  :2620, :2685
+    int row_len;           // IMA: int16 entries per (block, channel) in the pre-pass's rows: samplesPerBlock + 8; MS: samplesPerBlock + 2, the block's table
 };
 static_assert(sizeof(SMixClass) == 88, "SMixClass layout");
 struct SMixSeg {
     unsigned long long src_off;  // the stream's first byte, relative to the batch's data (DFPWM: its row's, relative to SMixParams::rows; IMA: its first row's
-                                 // first int16 entry, relative to SMixParams::rows16)
-    long long src_base;          // source frame (within the stream) of table index 0 (IMA: the call's first block within the stream)
+                                 // first int16 entry, relative to SMixParams::rows16; MS: its channel 0 row's, relative to SMixParams::rows_ms)
+    long long src_base;          // source frame (within the stream) of table index 0 (IMA, MS: the call's first block within the stream)
     unsigned long long out_off;  // element offset of output channel 0, output index 0 of this call
-    int w_lo, w_hi;              // valid table indices (anything else reads as nil) (IMA: of the call's LAST block; a block before it has row_len entries)
+    int w_lo, w_hi;              // valid table indices (anything else reads as nil) (IMA: of the call's LAST block; a block before it has row_len entries;
+                                 // MS: every block's are 1 .. row_len, and w_hi carries the elements between the stream's channel rows to the kernel)
     unsigned n_out;
     unsigned out_stride;         // elements between output channels
     unsigned cls;
-    unsigned nblk;               // IMA: blocks of the call
+    unsigned nblk;               // IMA, MS: blocks of the call
 };
 static_assert(sizeof(SMixSeg) == 48, "SMixSeg layout");
 struct SMixTile { unsigned seg, o0, cnt; };
@@ -94,6 +109,8 @@ struct SMixParams {
     void *out;
     const signed char *rows;  // DF: the pre-pass's int8 rows (ctx->tmp_buf): 16-byte aligned, 64 bytes to spare behind the last
     const short *rows16;      // IM: the pre-pass's int16 rows (ctx->tmp_buf, behind the DFPWM scratch): every (block, channel) row at a multiple of 16 bytes
+    const short *rows_ms;     // MS: k_ms_mixed's int16 rows (ctx->tmp_buf, behind the IMA scratch): 16-byte aligned, a stream's channel rows a multiple of
+                              // eight entries apart, 64 bytes to spare behind the last
 };
 
 template <bool DF = false>
@@ -181,7 +198,38 @@ AUKIT_DEV int smix_stage_i16(const short *row, int e0, int n_stage, int C, int r
     return head;
 }
 
-template <int INTERP, typename OUT_T, bool DF, bool IM>
+// MS: table indices e0 + 1 .. e0 + n_stage of every channel of one block — `blk` its first entry in channel 0's row, channel 1's `stride` entries on —
+// become the reference's doubles: floor(p / (p < 0 and 128 or 127)) for two channels (:2648-2662), the quotient itself for one (:2708-2720).  A block
+// starts wherever the blocks before it end, at any 2-byte phase: 16 bytes (eight entries) per lane from the 16-byte aligned address at or below the
+// window's first entry, the head shift the same for both channels (the rows are 16-byte aligned and a multiple of eight entries apart).  The rows
+// region starts at a multiple of 256 bytes and has 64 bytes to spare behind it, so no load leaves the scratch; what a vector holds beyond the window
+// (the neighbouring blocks' entries, or bytes nothing wrote) lands in slots no output indexes.  The caller keeps head + n_stage + 7 <= cap.
+// -> the window's first slot
+AUKIT_DEV int smix_stage_ms(const short *blk, unsigned stride, int e0, int n_stage, int C, int cap, double *sm, int tid) {
+    const short *a0 = blk + e0;
+    const int head = (int)(((uintptr_t)a0 & 15) >> 1);
+    const short *al = a0 - head;
+    const int nvec = (head + n_stage + 7) >> 3;
+    const int total = nvec * C;
+    const double r127 = 1.0 / 127.0;
+    const bool floored = C == 2;
+    for (int i = tid; i < total; i += 256) {
+        const int c = i >= nvec ? 1 : 0, v = i - c * nvec;  // (one or two channels)
+        const uint4 u = *reinterpret_cast<const uint4 *>(al + (size_t)c * stride + 8 * v);
+        const unsigned w[4] = {u.x, u.y, u.z, u.w};
+        double2 *o = reinterpret_cast<double2 *>(sm + (size_t)c * cap + 8 * v);
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const int lo = ((int)w[e] << 16) >> 16, hi = (int)w[e] >> 16;
+            double a = lo < 0 ? (double)lo * (1.0 / 128) : div_rcp((double)lo, 127.0, r127), b = hi < 0 ? (double)hi * (1.0 / 128) : div_rcp((double)hi, 127.0, r127);
+            if (floored) { a = floor(a); b = floor(b); }
+            o[e] = make_double2(a, b);
+        }
+    }
+    return head;
+}
+
+template <int INTERP, typename OUT_T, bool DF, bool IM, bool MS = false>
 __global__ __launch_bounds__(256) void k_stream_mixed(const SMixParams P) {
     extern __shared__ double sm[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -205,6 +253,18 @@ __global__ __launch_bounds__(256) void k_stream_mixed(const SMixParams P) {
                 ima_row = sg.src_off + (unsigned long long)(sg.src_base + kb) * (unsigned)C * (unsigned)K.row_len;
             }
         }
+        unsigned long long ms_row = 0;  // MS: the tile's block in channel 0's row: first int16 entry
+        unsigned ms_stride = 0;         //     and the entries between the channel rows
+        if constexpr (MS) {
+            if (K.codec == AUKIT_CODEC_MSADPCM) {  // the tile lies within block kb of the call; every block is whole and yields nl_full outputs
+                const unsigned kb = o0 / K.nl_full;
+                o0 -= kb * K.nl_full;
+                sg.out_off += (unsigned long long)kb * K.nl_full;
+                ms_stride = (unsigned)sg.w_hi;
+                sg.w_hi = K.row_len;  // indices 1 .. samplesPerBlock + 2
+                ms_row = sg.src_off + (unsigned long long)(sg.src_base + kb) * (unsigned)K.row_len;
+            }
+        }
 
         // window of the table this tile touches
         const unsigned o_first = (K.epi == SMIX_EPI_PCM && o0 > 0) ? o0 - 1 : o0;  // the FIR needs s(o0 - 1)
@@ -225,6 +285,8 @@ __global__ __launch_bounds__(256) void k_stream_mixed(const SMixParams P) {
                 if constexpr (DF) shift = smix_stage_i8(P.rows + sg.src_off, g0, n_stage, sm, tid);
             } else if (IM && K.codec == AUKIT_CODEC_ADPCM_WAV) {
                 if constexpr (IM) shift = smix_stage_i16(P.rows16 + ima_row, k_lo - 1, n_stage, C, K.row_len, cap, sm, tid);  // table index 1 is entry 0
+            } else if (MS && K.codec == AUKIT_CODEC_MSADPCM) {
+                if constexpr (MS) shift = smix_stage_ms(P.rows_ms + ms_row, ms_stride, k_lo - 1, n_stage, C, cap, sm, tid);   // table index 1 is entry 0
             } else if (K.s16le_mono && (((uintptr_t)base) & 1) == 0) {
                 const unsigned char *a0 = base + 2 * g0;
                 const unsigned char *al = (const unsigned char *)((uintptr_t)a0 & ~(uintptr_t)15);
@@ -298,6 +360,15 @@ __global__ __launch_bounds__(256) void k_stream_mixed(const SMixParams P) {
                     } else {
                         for (int c = 0; c < C; c++) smix_store<OUT_T>(out + sg.out_off + (size_t)c * sg.out_stride + o, v);      // :2486
                     }
+                }
+            }
+        } else if (MS && K.epi == SMIX_EPI_MS_MONO) {
+            if constexpr (MS) {
+                for (unsigned j = tid; j < cnt; j += 256) {
+                    const unsigned o = o0 + j;
+                    const SMixAt a = smix_at<INTERP>(K, sg, k_lo, last, o);
+                    const double l = smix_tap<INTERP>(tab0, a), r = smix_tap<INTERP>(tab0 + cap, a);
+                    smix_store<OUT_T>(out + sg.out_off + o, lua_clamp(floor(l + r / 2), -128, 127));                                // :2672
                 }
             }
         } else if (K.epi == SMIX_EPI_FLOOR) {
@@ -461,6 +532,21 @@ int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) {
             return fail(AUKIT_E_UNSUPPORTED, "stream too long");
         return AUKIT_OK;
     }
+    if (d->codec == AUKIT_CODEC_MSADPCM) {  // stream_msadpcm's and ms_count_blocks' (msadpcm.hip); and what k_ms_mixed's int32 arithmetic cannot hold
+        const int C = d->channels;
+        if (d->sample_rate < 1) return fail(AUKIT_E_ARG, "bad argument #4 (number outside of range)");
+        if (C != 1 && C != 2) return fail(AUKIT_E_LUA, "Unsupported number of channels: %d", C);
+        if (d->block_align < 7 * C + 1) return fail(AUKIT_E_ARG, "bad blockAlign");
+        const MsGeom G(C, d->block_align, d->sample_rate);
+        const uint64_t nblk = (nb + G.ba - 1) / G.ba;  // for n = 1, #data, blockAlign
+        if (nblk && nb % G.ba != 0) return ms_partial_block(C, nb, G.ba);  // the iterator fails on the first read that finds nothing: the whole stream is refused there, and here
+        const int wide = mixed_ms_wide_pair(d);
+        if (wide >= 0) return fail(AUKIT_E_UNSUPPORTED, "MS-ADPCM coefficient pair %d with |c1| + |c2| >= 65536: aukit_stream_decode takes this stream", wide);
+        // blocks, a channel row's entries and a call's outputs are counted in 32 bits here
+        if (nblk > 0x7FFFFFF0ull || nblk * G.row_len > 0x7FFFFFF0ull || !(G.ips_d < 9e18) || G.newlen_d * (double)std::max<uint64_t>(std::min<uint64_t>(nblk, G.ips), 1) > 2147483632.0)
+            return fail(AUKIT_E_UNSUPPORTED, "stream too long");
+        return AUKIT_OK;
+    }
     if (d->codec == AUKIT_CODEC_PCM) {
         int rc;
         if ((rc = check_pcm_desc(d))) return rc;
@@ -492,10 +578,16 @@ static int smix_validate(const aukit_ctx *ctx, const aukit_batch *in, const auki
                          const SMixCarry *carry) {
     int rc;
     if ((rc = mixed_check_call(ctx, in, out, descs, n_descs, interp, dtype, "invalid interpolation", "stream each class with aukit_stream_decode"))) return rc;
-    if ((rc = mixed_check_codecs(descs, in->n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV},
-                                 "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, "
-                                 "AUKIT_CODEC_DFPWM and AUKIT_CODEC_ADPCM_WAV)")))
-        return rc;
+    // AUKIT_OPT_STREAM_MIXED_CODECS: MS-ADPCM joins the list on a context that asked this call for it; without the bit the call answers in the words of before
+    if ((ctx->stream_mixed_codecs >> AUKIT_CODEC_MSADPCM) & 1u)
+        rc = mixed_check_codecs(descs, in->n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_MSADPCM},
+                                "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, "
+                                "AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_STREAM_MIXED_CODECS, AUKIT_CODEC_MSADPCM)");
+    else
+        rc = mixed_check_codecs(descs, in->n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV},
+                                "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, "
+                                "AUKIT_CODEC_DFPWM and AUKIT_CODEC_ADPCM_WAV)");
+    if (rc) return rc;
     if ((rc = mixed_check_channels(in->n, mono, [&](uint32_t s) { return descs[s].channels; }))) return rc;
     for (uint32_t s = 0; s < in->n; s++) {
         if (carry && carry[s].nbytes > in->off[s + 1] - in->off[s]) return fail(AUKIT_E_ARG, "stream %u: the carry names more bytes than the batch holds", s);
@@ -510,22 +602,31 @@ struct SMixClasses {
     std::vector<int> tile_out;     // per class
     std::vector<unsigned> cls_of;  // per stream
     size_t lds = 0;                // the largest class's
-    bool has_df = false, has_ima = false;
+    bool has_df = false, has_ima = false, has_ms = false;
 };
 
 static int smix_classes(const aukit_codec_desc *descs, uint32_t n, int interp, int mono, SMixClasses &T) {
     int hl, hr;
     mixed_halos(interp, &hl, &hr);
-    ClassIndex<std::tuple<int, int, int, int, int, int, int, double>> index;
+    ClassIndex<std::tuple<int, int, int, int, int, int, int, int, double>> index;
+    std::vector<std::vector<int>> ms_sets;  // the distinct MS-ADPCM coefficient sets (count, c1[32], c2[32]): part of that codec's class key
     T.cls_of.resize(n);
     for (uint32_t s = 0; s < n; s++) {
         const aukit_codec_desc &d = descs[s];
-        const bool pcm = d.codec == AUKIT_CODEC_PCM, df = d.codec == AUKIT_CODEC_DFPWM, ima = d.codec == AUKIT_CODEC_ADPCM_WAV;
+        const bool pcm = d.codec == AUKIT_CODEC_PCM, df = d.codec == AUKIT_CODEC_DFPWM, ima = d.codec == AUKIT_CODEC_ADPCM_WAV, ms = d.codec == AUKIT_CODEC_MSADPCM;
         T.has_df = T.has_df || df;
         T.has_ima = T.has_ima || ima;
+        T.has_ms = T.has_ms || ms;
+        int ms_set = 0;
+        if (ms) {
+            std::vector<int> tab(65);
+            tab[64] = mixed_ms_coefs(&d, tab.data());
+            ms_set = (int)(std::find(ms_sets.begin(), ms_sets.end(), tab) - ms_sets.begin());
+            if (ms_set == (int)ms_sets.size()) ms_sets.push_back(tab);
+        }
         bool fresh;
-        T.cls_of[s] = index.of({d.codec, pcm ? d.bit_depth : 8, pcm ? d.data_type : 0, pcm ? (d.big_endian ? 1 : 0) : 0, d.channels, pcm || df || ima ? 0 : (d.ulaw ? 1 : 0),
-                                ima ? d.block_align : 0, d.sample_rate}, &fresh);
+        T.cls_of[s] = index.of({d.codec, pcm ? d.bit_depth : 8, pcm ? d.data_type : 0, pcm ? (d.big_endian ? 1 : 0) : 0, d.channels, pcm || df || ima || ms ? 0 : (d.ulaw ? 1 : 0),
+                                ima || ms ? d.block_align : 0, ms_set, d.sample_rate}, &fresh);
         if (!fresh) continue;
         SMixClass K;
         memset(&K, 0, sizeof K);
@@ -547,6 +648,10 @@ static int smix_classes(const aukit_codec_desc *descs, uint32_t n, int interp, i
             K.mix = (mono && d.channels > 1) ? 1 : 0;  // if channels == 1 then mono = false end  :2445
             K.stage = 1;                               // the row is flat: the step of `channels` is in the position
             K.epi = SMIX_EPI_DFPWM;
+        } else if (ms) {
+            K.mix = (mono && d.channels == 2) ? 1 : 0;  // one channel: `mono` is ignored  :2726
+            K.stage = d.channels;
+            K.epi = K.mix ? SMIX_EPI_MS_MONO : SMIX_EPI_FLOOR;  // clamp(floor(l + r / 2)) (:2672), or clamp(floor(c)) per channel as stream.g711's
         } else {
             K.mix = mono ? 1 : 0;
             K.stage = d.channels;
@@ -557,12 +662,19 @@ static int smix_classes(const aukit_codec_desc *descs, uint32_t n, int interp, i
         // kernel's margin is 32.  +32 otherwise: the vector path's alignment head and tail, the FIR's look-back, the kernel's own margin of 16
         const int slack = hl + hr + 2 + (df ? 64 : 32);
         int to, rc;
-        if ((rc = mixed_tile_height(K.ratio, df ? K.ratio / d.channels : K.ratio, K.stage, slack, 64 * 1024, s, &to, &K.cap))) return rc;
+        // (an MS-ADPCM tile's window never leaves its block's table: that bounds the LDS whatever the ratio)
+        const uint64_t table = ms ? MsGeom(d.channels, d.block_align, d.sample_rate).row_len : ~0ull;
+        if ((rc = mixed_tile_height(K.ratio, df ? K.ratio / d.channels : K.ratio, K.stage, slack, 64 * 1024, s, &to, &K.cap, table))) return rc;
         if (ima) {  // stream.adpcm's epilogue is stream.g711's (above); a tile's window never leaves its block's table
             const ImaGeom G(d.channels, d.block_align, d.sample_rate);
             K.nl_full = (unsigned)G.newlen_full;
             K.row_len = (int)G.row_len;
             K.cap = (int)std::min<uint64_t>((uint64_t)K.cap, (G.row_len + (uint64_t)slack + 1) & ~1ull);
+        }
+        if (ms) {  // (cap is a block's table plus slack at the most, by `table` above; a table beyond one tile's window is cut into several tiles)
+            const MsGeom G(d.channels, d.block_align, d.sample_rate);
+            K.nl_full = (unsigned)G.newlen_d;
+            K.row_len = (int)G.row_len;
         }
         T.lds = std::max(T.lds, (size_t)K.cap * 8 * K.stage);
         T.classes.push_back(K);
@@ -574,7 +686,7 @@ static int smix_classes(const aukit_codec_desc *descs, uint32_t n, int interp, i
 // the exact_div_verified verdict of every class, for as many positions as one of its segments (an IMA class: one of its blocks) can ask for
 static void smix_exact_division(aukit_ctx *ctx, std::vector<SMixClass> &classes) {
     for (SMixClass &K : classes) {
-        if (K.codec == AUKIT_CODEC_ADPCM_WAV) {  // outputs are counted within a block: the verdict covers a full block's, or the kernel divides
+        if (K.codec == AUKIT_CODEC_ADPCM_WAV || K.codec == AUKIT_CODEC_MSADPCM) {  // outputs are counted within a block: the verdict covers a full block's, or the kernel divides
             K.exact_rcp = (K.nl_full <= 4000000u && exact_div_verified(ctx, K.ratio, (uint64_t)K.nl_full + 2)) ? 1 : 0;
             continue;
         }
@@ -622,6 +734,9 @@ struct SMixPlan {
     // the IMA streams that have a planned block; int16 entries of their rows, (block, channel) jobs, bytes read
     std::vector<SMixImaStream> ima_rows;
     uint64_t ima_elems = 0, ima_jobs = 0, ima_src = 0;
+    // the MS-ADPCM streams that have a planned block: k_ms_mixed's units and coefficient sets; int16 entries of their rows
+    MsMixPlan ms;
+    uint64_t ms_elems = 0;
     uint64_t in_bytes = 0;
 
     explicit SMixPlan(uint32_t n) : lens(n, 0), ck(chunks_create(n)) {}
@@ -732,6 +847,27 @@ static void plan_ima(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc
     pl.ima_src += std::min<uint64_t>(nb, done * G.ba + G.hdr);
 }
 
+// stream_msadpcm's plan (msadpcm.hip) from byte 0: every block is whole (check_smix_stream), call k takes blocks k ips .. min((k + 1) ips, nblk) - 1.
+// A stream whose blocks yield no output has no chunk and no row: nothing of it is decoded, as in the stream's own call
+static void plan_ms(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc &d, uint64_t nb) {
+    const int C = d.channels;
+    const MsGeom G(C, d.block_align, d.sample_rate);
+    const uint64_t nblk = nb / G.ba, src_off = g.src_off, newlen = (uint64_t)G.newlen_d;
+    pl.ck->length_seconds[s] = (double)nb / (double)G.ba * G.spb / d.sample_rate;  // :2680, :2734
+    if (!nblk || !newlen) return;
+    const uint64_t stride = round_up(nblk * G.row_len, 8);
+    g.src_off = pl.ms_elems;
+    g.w_lo = 1; g.w_hi = (int)stride;  // (the kernel takes the stride from here and puts the table's last index, row_len, in its place)
+    for (uint64_t first = 0; first < nblk; first += G.ips) {
+        const uint64_t done = std::min<uint64_t>(first + G.ips, nblk);
+        g.src_base = (long long)first; g.nblk = (unsigned)(done - first); g.n_out = (uint32_t)((done - first) * newlen);
+        pl.add_call(s, g, (double)(done * G.ba + 1) / G.bytes_per_second);  // (n + pos) / bytesPerSecond  :2679, :2733
+    }
+    pl.ms.add_stream(d, s, src_off, nblk, pl.ms_elems, stride);
+    pl.ms.src += nb;
+    pl.ms_elems += stride * (uint64_t)C;
+}
+
 static void smix_plan(const aukit_batch *in, const aukit_codec_desc *descs, const SMixCarry *carry, const std::vector<unsigned> &cls_of, int interp, bool mono,
                       const std::vector<unsigned> &ima_bad, SMixPlan &pl) {
     size_t ima_i = 0;
@@ -746,6 +882,7 @@ static void smix_plan(const aukit_batch *in, const aukit_codec_desc *descs, cons
         g.cls = cls_of[s];
         if (d.codec == AUKIT_CODEC_DFPWM) plan_dfpwm(pl, s, g, d, nb);
         else if (d.codec == AUKIT_CODEC_ADPCM_WAV) plan_ima(pl, s, g, d, nb, ima_bad[ima_i++], cy);
+        else if (d.codec == AUKIT_CODEC_MSADPCM) plan_ms(pl, s, g, d, nb);  // (a stream set has no such member: no carry)
         else if (d.codec == AUKIT_CODEC_PCM) plan_pcm(pl, s, g, d, nb, interp, mono, cy);
         else plan_g711(pl, s, g, d, nb, cy);
     }
@@ -767,13 +904,21 @@ static void smix_chunk_table(SMixPlan &pl, int C_out) {
 
 // ---- phase 5: the pre-passes' scratch in ctx->tmp_buf: the DFPWM streams' int8 rows (each at a multiple of 16 bytes) and behind them the pre-pass's
 // tables (a row offset per stream, then a lane-per-stream item per stream); behind the DFPWM scratch the IMA pre-pass's int16 rows (planned blocks x
-// channels x (samplesPerBlock + 8) entries: every row at a multiple of 16 bytes) and its stream table
-struct SMixScratch { size_t df_tab_at = 0, ima_at = 0, ima_tab_at = 0, size = 0; };
+// channels x (samplesPerBlock + 8) entries: every row at a multiple of 16 bytes) and its stream table;
+// behind the IMA scratch k_ms_mixed's int16 rows (a row per (stream, channel) at a multiple of 16 bytes, 64 bytes to spare behind the last: the
+// tiles' 16-byte loads rely on them), its unit table, its coefficient sets and its two flag words
+struct SMixScratch { size_t df_tab_at = 0, ima_at = 0, ima_tab_at = 0, ms_at = 0, ms_unit_at = 0, ms_coef_at = 0, ms_flag_at = 0, size = 0; };
 static SMixScratch smix_scratch(const SMixPlan &pl) {
     Carve carve;
     SMixScratch L;
     if (pl.df_n) { carve.take((size_t)pl.df_tot); L.df_tab_at = carve.take((size_t)pl.df_n * (8 + sizeof(SMixDfItem))); }  // (the rows are at 0)
     if (pl.ima_jobs) { L.ima_at = carve.take((size_t)pl.ima_elems * 2); L.ima_tab_at = carve.take(pl.ima_rows.size() * sizeof(SMixImaStream)); }
+    if (!pl.ms.units.empty()) {
+        L.ms_at = carve.take((size_t)pl.ms_elems * 2);
+        L.ms_unit_at = carve.take(pl.ms.units.size() * sizeof(MsMixUnit), 0);
+        L.ms_coef_at = carve.take(pl.ms.coefs.size() * sizeof(int), 0);
+        L.ms_flag_at = carve.take(8, 56);
+    }
     L.size = carve.end;
     return L;
 }
@@ -814,11 +959,30 @@ static int smix_ima_prepass(aukit_ctx *ctx, const aukit_batch *in, const SMixPla
     return ctx_end_kernel(ctx, "k_smix_ima_rows", pl.ima_src + pl.ima_elems * 2);
 }
 
+// The MS-ADPCM pre-pass can still refuse — a predictor index beyond the stream's coefficient table, a delta that leaves k_ms_mixed's int32 range —
+// and writes nothing but the scratch: it runs, and its two flag words are read back, BEFORE `*out` is touched
+static int smix_ms_prepass(aukit_ctx *ctx, const aukit_batch *in, const SMixPlan &pl, const SMixScratch &L) {
+    char *const T = reinterpret_cast<char *>(ctx->tmp_buf.p);
+    unsigned *flags = reinterpret_cast<unsigned *>(T + L.ms_flag_at);
+    int rc;
+    AUKIT_HIP_CHECK(hipMemsetAsync(flags, 0xFF, 8, ctx->stream));
+    if ((rc = h2d_table(ctx, T + L.ms_unit_at, pl.ms.units.data(), pl.ms.units.size() * sizeof(MsMixUnit))) ||
+        (rc = h2d_table(ctx, T + L.ms_coef_at, pl.ms.coefs.data(), pl.ms.coefs.size() * sizeof(int))))
+        return rc;
+    if ((rc = ms_mixed_decode(ctx, in, T + L.ms_unit_at, pl.ms.units.size(), T + L.ms_coef_at, reinterpret_cast<short *>(T + L.ms_at), flags, pl.ms.lds, pl.ms.src + pl.ms_elems * 2)))
+        return rc;
+    unsigned h[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+    AUKIT_HIP_CHECK(hipMemcpyAsync(h, flags, 8, hipMemcpyDeviceToHost, ctx->stream));
+    AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return mixed_ms_verdict(h[0], h[1], "aukit_stream_decode");
+}
+
 // ---- phase 7: tiles.  A segment is cut into tiles of the class's height.  An IMA segment: no tile straddles a block, and a block's outputs are cut
-// in equal parts of at most the tile height (12 240 outputs under a height of 2048: six tiles of 2040, no sliver).
+// in equal parts of at most the tile height (12 240 outputs under a height of 2048: six tiles of 2040, no sliver).  An MS-ADPCM segment likewise; all
+// its blocks are full ones.
 // -> the segment's tiles, appended to `tiles` where it is given
 static uint64_t smix_cut(const SMixClass &K, unsigned to, const SMixSeg &g, unsigned seg, std::vector<SMixTile> *tiles) {
-    if (K.codec != AUKIT_CODEC_ADPCM_WAV) {
+    if (K.codec != AUKIT_CODEC_ADPCM_WAV && K.codec != AUKIT_CODEC_MSADPCM) {
         if (tiles)
             for (unsigned o0 = 0; o0 < g.n_out; o0 += to) tiles->push_back(SMixTile{seg, o0, std::min(to, g.n_out - o0)});
         return ((uint64_t)g.n_out + to - 1) / to;
@@ -856,18 +1020,22 @@ static std::vector<SMixTile> smix_tiles(const SMixClasses &T, SMixPlan &pl, cons
     return tiles;
 }
 
-// ---- phase 8: the launch.  The DFPWM and the IMA class live in instantiations of their own: a batch without one launches the kernels it always did
+// ---- phase 8: the launch.  The DFPWM, the IMA and the MS-ADPCM class live in instantiations of their own: a batch without one launches the kernels it always did
 static int smix_launch(aukit_ctx *ctx, const aukit_batch *in, const SMixClasses &T, const SMixPlan &pl, const std::vector<SMixTile> &tiles, const SMixScratch &L,
                        const aukit_audio *a, int interp, int dtype) {
     SMixParams P;
     memset(&P, 0, sizeof P);
     P.rows16 = reinterpret_cast<const short *>(reinterpret_cast<const char *>(ctx->tmp_buf.p) + L.ima_at);
+    P.rows_ms = reinterpret_cast<const short *>(reinterpret_cast<const char *>(ctx->tmp_buf.p) + L.ms_at);
     static const char *names[] = {"k_stream_mixed<none>", "k_stream_mixed<linear>", "k_stream_mixed<cubic>"};
     uint64_t out_elems = 0;
     for (uint64_t len : pl.lens) out_elems += len * pl.ck->channels;
     const size_t lds = T.lds;
     return mixed_launch(ctx, in, a, T.classes, pl.segs, tiles, P, lds, names[interp], pl.in_bytes + out_elems * dtype_size(dtype), [&](unsigned grid) {
-        if (T.has_ima && T.has_df) AUKIT_MIXED_LAUNCH(ctx, k_stream_mixed, interp, dtype, grid, lds, P, true, true);
+        // (MS-ADPCM: two sets of instantiations, alone with PCM / G.711, or with both other pre-pass kinds compiled in)
+        if (T.has_ms && (T.has_ima || T.has_df)) AUKIT_MIXED_LAUNCH(ctx, k_stream_mixed, interp, dtype, grid, lds, P, true, true, true);
+        else if (T.has_ms) AUKIT_MIXED_LAUNCH(ctx, k_stream_mixed, interp, dtype, grid, lds, P, false, false, true);
+        else if (T.has_ima && T.has_df) AUKIT_MIXED_LAUNCH(ctx, k_stream_mixed, interp, dtype, grid, lds, P, true, true);
         else if (T.has_ima) AUKIT_MIXED_LAUNCH(ctx, k_stream_mixed, interp, dtype, grid, lds, P, false, true);
         else if (T.has_df) AUKIT_MIXED_LAUNCH(ctx, k_stream_mixed, interp, dtype, grid, lds, P, true, false);
         else AUKIT_MIXED_LAUNCH(ctx, k_stream_mixed, interp, dtype, grid, lds, P, false, false);
@@ -894,11 +1062,13 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
     smix_plan(in, descs, carry, T.cls_of, interp, mono != 0, ima_bad, pl);
     smix_chunk_table(pl, C_out);
     const uint64_t nt = smix_count_tiles(T, pl);
-    if (nt > 0xFFFFFFF0ull || pl.ima_jobs > 0x7FFFFFF0ull * 64) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
+    if (nt > 0xFFFFFFF0ull || pl.ima_jobs > 0x7FFFFFF0ull * 64 || pl.ms.units.size() > 0x7FFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
 
     // the scratch is sized before `*out` is touched, and its pointer is read after
     const SMixScratch L = smix_scratch(pl);
-    if ((pl.df_n || pl.ima_jobs) && (rc = mixed_scratch_ensure(ctx, *out, L.size))) return rc;
+    const bool ms = !pl.ms.units.empty();
+    if ((pl.df_n || pl.ima_jobs || ms) && (rc = mixed_scratch_ensure(ctx, *out, L.size))) return rc;
+    if (ms && (rc = smix_ms_prepass(ctx, in, pl, L))) return rc;
     aukit_audio *a = *out;
     if ((rc = audio_prepare(ctx, &a, n, C_out, 48000, dtype, pl.lens.data()))) return rc;
     *out = a;

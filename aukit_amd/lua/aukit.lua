@@ -850,14 +850,18 @@ end
 -- returns (aukit.stream.adpcm's raise behind a header step index above 88 included); one upload, one launch.  Without `mono` the files must agree in channel count.  A raw .dfpwm file, which has no header, is given as
 -- {data, "dfpwm"[, channels[, sampleRate]]} (load_many's entry: channels first): its pair is aukit.stream.dfpwm(data, sampleRate, channels, mono)'s.
 -- IMA-ADPCM WAV files are taken on request only: `mono` given as an options table, {mono = ..., adpcm = true}.  Without it such a file is refused by index, as before
--- aukit_stream_decode_mixed took the codec.
+-- aukit_stream_decode_mixed took the codec.  `adpcm` means IMA-ADPCM only; MS-ADPCM WAV files (format 2: the walk's descriptor carries block_align and the
+-- `fmt` chunk's coefficient list) are taken with {mono = ..., adpcm = ..., msadpcm = true}: for this one call the context is opted in
+-- (AUKIT_OPT_STREAM_MIXED_CODECS, option 6, bit 1 << AUKIT_CODEC_MSADPCM) and put back behind it, also where the call is refused.
 function aukit.stream.many(files, mono)
     expect(1, files, "table") expect(2, mono, "boolean", "table", "nil")
-    local adpcm = false
+    local adpcm, msadpcm = false, false
     if type(mono) == "table" then
-        for k in pairs(mono) do if k ~= "mono" and k ~= "adpcm" then error("bad argument #2 (unknown option " .. tostring(k) .. ")", 2) end end
-        if (mono.mono ~= nil and type(mono.mono) ~= "boolean") or (mono.adpcm ~= nil and type(mono.adpcm) ~= "boolean") then error("bad argument #2 (expected boolean options)", 2) end
-        mono, adpcm = mono.mono, mono.adpcm or false
+        for k in pairs(mono) do if k ~= "mono" and k ~= "adpcm" and k ~= "msadpcm" then error("bad argument #2 (unknown option " .. tostring(k) .. ")", 2) end end
+        if (mono.mono ~= nil and type(mono.mono) ~= "boolean") or (mono.adpcm ~= nil and type(mono.adpcm) ~= "boolean") or (mono.msadpcm ~= nil and type(mono.msadpcm) ~= "boolean") then
+            error("bad argument #2 (expected boolean options)", 2)
+        end
+        mono, adpcm, msadpcm = mono.mono, mono.adpcm or false, mono.msadpcm or false
     end
     local n = #files
     local descs = ffi.new("aukit_codec_desc[?]", math.max(n, 1))
@@ -881,8 +885,11 @@ function aukit.stream.many(files, mono)
             local c = ffi.new("aukit_container")
             if C.aukit_parse_container(ffi.cast("const uint8_t*", f), #f, kind, 1, c) ~= 0 then error("file " .. (i - 1) .. ": " .. ffi.string(C.aukit_last_error()), 2) end
             -- 5: AUKIT_CODEC_DFPWM (a WAV with the DFPWM GUID); 3: AUKIT_CODEC_ADPCM_WAV (format 0x11 or the ADPCM GUID: the walk's descriptor carries block_align)
-            if c.desc.codec > 1 and c.desc.codec ~= 5 and (c.desc.codec ~= 3 or not adpcm) then
-                error("file " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: " .. (adpcm and
+            -- 4: AUKIT_CODEC_MSADPCM (format 2: block_align and the coefficient list)
+            if c.desc.codec > 1 and c.desc.codec ~= 5 and (c.desc.codec ~= 3 or not adpcm) and (c.desc.codec ~= 4 or not msadpcm) then
+                error("file " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: " .. ((adpcm and msadpcm) and
+                      "stream.many takes PCM, G.711 and DFPWM payloads and IMA-ADPCM and MS-ADPCM blocks (the other block codecs keep their own streams)" or msadpcm and
+                      "stream.many takes PCM, G.711 and DFPWM payloads and MS-ADPCM blocks (the other block codecs keep their own streams)" or adpcm and
                       "stream.many takes PCM, G.711 and DFPWM payloads and IMA-ADPCM blocks (the other block codecs keep their own streams)" or
                       "stream.many takes PCM, G.711 and DFPWM (the block codecs keep their own streams)"), 2)
             end
@@ -896,7 +903,12 @@ function aukit.stream.many(files, mono)
     check(C.aukit_batch_upload(ctx(), b, ffi.cast("const uint8_t*", table.concat(parts)), offs, n))
     local batch = ffi.gc(b[0], C.aukit_batch_free)
     local o, ck = ffi.new("aukit_audio*[1]"), ffi.new("aukit_chunks*[1]")
-    check(C.aukit_stream_decode_mixed(ctx(), batch, descs, n, INTERP[aukit.defaultInterpolation], mono and 1 or 0, F64, o, ck))
+    -- msadpcm: AUKIT_OPT_STREAM_MIXED_CODECS (6) with bit 1 << AUKIT_CODEC_MSADPCM for this one call; the shim's context sets no other bit, so 0 puts it back
+    if msadpcm then check(C.aukit_ctx_set_option(ctx(), 6, 2 ^ CODEC.msadpcm)) end
+    local rc = C.aukit_stream_decode_mixed(ctx(), batch, descs, n, INTERP[aukit.defaultInterpolation], mono and 1 or 0, F64, o, ck)
+    local words = rc ~= 0 and ffi.string(C.aukit_last_error()) or nil
+    if msadpcm then C.aukit_ctx_set_option(ctx(), 6, 0) end
+    if words then error(words, 2) end
     local whole = ffi.gc(o[0], C.aukit_audio_free)
     local cnt, mx = ffi.new("uint32_t[1]"), ffi.new("uint32_t[1]")
     check(C.aukit_chunks_info(ck[0], cnt, mx))

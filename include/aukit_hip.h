@@ -155,12 +155,19 @@ typedef enum {
                                    reference's last chunk, one output longer in the channels in front of the gap, with the reference's status,
                                    instead of refusing it.  0 (default): one length per chunk, those inputs are refused by name.  No effect on
                                    mono streams, the mix-down or any other codec. */
-    AUKIT_OPT_MIXED_CODECS = 5 /* a bit mask, 0 by default: bit (1 << codec) lets the per-stream-descriptor calls take that aukit_codec beyond the lists
+    AUKIT_OPT_MIXED_CODECS = 5,/* a bit mask, 0 by default: bit (1 << codec) lets the per-stream-descriptor calls take that aukit_codec beyond the lists
                                    they serve by default.  Today exactly one bit is known, 1 << AUKIT_CODEC_MSADPCM, and exactly one call reads the
-                                   mask, aukit_decode_resample_mixed; aukit_stream_decode_mixed and aukit_streamset_open ignore it and keep refusing
-                                   that codec by name.  Any other bit is AUKIT_E_UNSUPPORTED, the codec named, and the context keeps the mask it
-                                   had.  The mask is meant to carry later codecs (and the stream calls) as they are taken: a host sets the bits of
-                                   what it is prepared to receive.  With 0 every call answers as it did before the option existed. */
+                                   mask, aukit_decode_resample_mixed; aukit_stream_decode_mixed (which has a mask of its own, below) and
+                                   aukit_streamset_open ignore it and keep refusing that codec by name.  Any other bit is AUKIT_E_UNSUPPORTED, the
+                                   codec named, and the context keeps the mask it had.  The mask is meant to carry later codecs as they are taken:
+                                   a host sets the bits of what it is prepared to receive.  With 0 every call answers as it did before the option
+                                   existed. */
+    AUKIT_OPT_STREAM_MIXED_CODECS = 6 /* the same for aukit_stream_decode_mixed, the only call that reads it: a bit mask of 1 << codec, 0 by default,
+                                   exactly one bit known, 1 << AUKIT_CODEC_MSADPCM (aukit.stream.msadpcm's streams, see that call); any other bit is
+                                   AUKIT_E_UNSUPPORTED, the codec named (or "bit N"), and the context keeps the mask it had.  A mask of its own and
+                                   not a second reader of option 5: a host that asked aukit_decode_resample_mixed for MS-ADPCM rows has not asked
+                                   the stream call for anything.  aukit_decode_resample_mixed and aukit_streamset_open ignore it (a stream set
+                                   keeps refusing the codec whatever either mask says).  With 0 every call answers exactly as before. */
 } aukit_option;
 int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);
 /* counters of the most recent call that produced them (AUKIT_OPT_COLLECT_STATS = 1) */
@@ -347,7 +354,7 @@ int aukit_stream_decode_table(aukit_ctx *ctx, const double *values, const uint64
  * one channel it is ignored.  AUKIT_CODEC_PCM (every format stream.pcm takes, rates at or below 48 kHz), AUKIT_CODEC_G711 (integer rates),
  * AUKIT_CODEC_DFPWM (the descriptor's `channels` and `sample_rate`, rates above 48 kHz included; positions count from byte 0 whatever a stream
  * handle on the context carries; the same sample goes to every channel, and `mono` is ((0 + v) + v ...) / channels, :2485-2488) and
- * AUKIT_CODEC_ADPCM_WAV (IMA-ADPCM WAV blocks, below) only, interpolation none / linear / cubic; anything else is AUKIT_E_UNSUPPORTED by name.  A batch with a DFPWM stream pays a pre-pass in front of the
+ * AUKIT_CODEC_ADPCM_WAV (IMA-ADPCM WAV blocks, below) and, on request, AUKIT_CODEC_MSADPCM (below) only, interpolation none / linear / cubic; anything else is AUKIT_E_UNSUPPORTED by name.  A batch with a DFPWM stream pays a pre-pass in front of the
  * one resample launch: every DFPWM stream is decoded to a flat int8 row in the context's scratch (the chunk-parallel decoder, one run per distinct
  * channel count, or a lane per stream where every stream is short) — element 0 a leading 0, then the samples in feed order (slices of
  * 6000 * channels + 1 bytes advanced by 6000 * channels, the slice's last byte decoded again as the next one's first), rows at multiples of 16
@@ -361,11 +368,33 @@ int aukit_stream_decode_table(aukit_ctx *ctx, const double *values, const uint64
  * are not —; then a lane per (block, channel) decodes every planned block to an int16 row of predictors in the context's scratch, behind the
  * int8 rows and 16-byte aligned: up to samplesPerBlock + 8 entries per channel, the last eight those of the junk word (the next block's header
  * bytes read as nibbles, Q6).  A block is one independent table, indices 1 .. 8 * words, and block k of a call writes its outputs at
- * k * floor(samplesPerBlock * ratio) of the call's chunk.  n_descs must be the batch's stream count; without
+ * k * floor(samplesPerBlock * ratio) of the call's chunk.
+ * AUKIT_CODEC_MSADPCM is taken only on a context that asked for it, AUKIT_OPT_STREAM_MIXED_CODECS with bit 1 << AUKIT_CODEC_MSADPCM (without it
+ * the codec is refused by name in the words of before; AUKIT_OPT_MIXED_CODECS is the decode call's and means nothing here).  Stream s is
+ * aukit.stream.msadpcm (data_s, block_align, channels, sample_rate, mono, coefficients) (:2588-2736): `channels` 1 or 2, `sample_rate` >= 1 (any
+ * rate), `block_align` >= 7 * channels + 1, and `ncoef` / `coef1` / `coef2` (min(ncoef, 32) pairs; ncoef 0: the seven defaults) are the stream's
+ * own.  samplesPerBlock is block_align - 14 (two channels) or (block_align - 7) * 2 (one) — two short of the samplesPerBlock + 2 entries a block's
+ * table holds (Q9) —, a block yields floor(samplesPerBlock * 48000 / rate) outputs, an iterator call takes ceil(rate / samplesPerBlock) blocks,
+ * pos = (blocks done * block_align + 1) / (block_align * blocks per call), length_seconds = bytes / block_align * samplesPerBlock / rate; a
+ * stream whose blocks yield no output has no chunk.  Every block is one independent table, indices 1 .. samplesPerBlock + 2.  Two channels:
+ * the entries are floor(p / (p < 0 and 128 or 127)), floored BEFORE interpolation; the samples are clamp(floor(l)) and clamp(floor(r)), or with
+ * `mono` clamp(floor(l + r / 2)) — the reference's precedence, not the mean (:2672).  One channel: the entries are not floored, `mono` is
+ * ignored, and every block is decoded from the stream's first seven bytes (str_unpack without a position, :2706): bytes 0 .. 6 of later blocks
+ * are never read.  Exact in both storage types.  A batch with such a stream pays a third pre-pass, the decode call's k_ms_mixed: every block to
+ * samplesPerBlock + 2 int16 per channel in the context's scratch, behind the other rows; it runs, and its two flag words are read back, before
+ * `*out` is touched (the context's scratch is sized first).  A tile's window never leaves its block's table, so the table bounds the LDS a class
+ * needs whatever the rate; only a stream whose block table AND whose window of 64 outputs both exceed 64 KiB of doubles per tile is refused
+ * (AUKIT_E_UNSUPPORTED, "needs more than 64 KiB of LDS per tile"), as for the other kinds.  What the stream's own call refuses is refused with its words — sample rate, channel count, `bad blockAlign`, a stream that
+ * ends inside a block (the whole stream, as there), and what only the device can tell: a predictor index at or beyond the coefficient count (one
+ * channel: the first block's) is AUKIT_E_LUA, attempt to perform arithmetic on a nil value (local 'c1'), the lowest such stream named.  Two things
+ * k_ms_mixed's int32 arithmetic cannot hold are AUKIT_E_UNSUPPORTED and point to aukit_stream_decode, which serves them: a delta of 2^21 or more
+ * anywhere in the stream, and a coefficient pair with |c1| + |c2| >= 65536.
+ * n_descs must be the batch's stream count; without
  * `mono` the descriptors must agree in channel count (AUKIT_E_ARG).  A stream whose own call would fail fails the whole call with that status
  * and message, the stream's index appended.  PCM data that ends inside a frame is served with the mix-down (the partial frame counts for
  * nothing) and refused without it whatever AUKIT_OPT_CHANNEL_LENS says: the uneven last chunk stays with aukit_stream_decode.  Every refusal
- * happens before anything is allocated or launched (the header scan and its scratch excepted) and leaves `*out` and `*chunks` as they were. */
+ * happens before anything is allocated or launched (the header scan, the MS-ADPCM pre-pass and their scratch excepted) and leaves `*out` and
+ * `*chunks` as they were. */
 int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs /* n */, uint32_t n_descs,
                               int interp, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks);
 /* per stream s: nchunks[s]; chunk k of stream s: length and the iterator's second return value.

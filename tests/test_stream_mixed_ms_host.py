@@ -1,0 +1,183 @@
+"""CPU: Library M (tests/stream_mixed_ms_util.py) holds the shapes AUKIT_CODEC_MSADPCM in aukit_stream_decode_mixed can go wrong at, every stream
+of it meets the conditions the call serves (whole blocks, every delta below 2^21, predictor indices inside the table, status 0 on the oracle) and
+the oracle's chunk tables are the closed forms the call plans with; aukit.stream.many's host half with MS-ADPCM WAV files taken (the `stream_ms`
+keyword of aukit._sniff_many); and what the header, the mirrors and the LuaJIT shim say about the codec and its option."""
+import math
+import os
+import re
+
+import pytest
+
+import aukit_amd.aukit as aukit
+from aukit_amd import _native as N
+from tests import mixed_ms_util as MU
+from tests import ms_qoa_write_util as W
+from tests import stream_mixed_ms_util as T
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def lib(oracle):
+    return T.library_m(oracle, "linear")
+
+
+def test_library_holds_the_shapes(lib):
+    ms = [s for s in lib if s["kind"] == "ms"]
+    assert len(ms) == 34 and len(lib) == 48 and {s["kind"] for s in lib} == {"ms", "pcm", "g711", "dfpwm", "ima"}
+    assert lib[0]["kind"] == lib[-1]["kind"] == "ms"
+    assert {(s["ch"], s["block_align"]) for s in ms} >= set(T.SHAPES) and {s["rate"] for s in ms} == set(T.RATES)
+    assert sum(len(s["bytes"]) for s in lib) < 2_000_000
+    for e in T.BLOCKS:
+        assert any(s["blocks"] == int(eval(e, {}, dict(ips=T.geometry(s["ch"], s["block_align"], s["rate"])[1]))) for s in ms), e
+    assert {s["note"] for s in ms} >= {"random", "small nibbles", "encoded", "oracle.gen_msadpcm", "custom table", "other headers behind the first", "both clamps", "delta at its floor"}
+    pairs = list(zip(ms, ms[1:]))
+    assert any((a["ch"], a["rate"], a["coefficients"]) == (b["ch"], b["rate"], b["coefficients"]) and a["block_align"] != b["block_align"] for a, b in pairs)
+    assert any((a["ch"], a["rate"], a["block_align"]) == (b["ch"], b["rate"], b["block_align"]) and a["coefficients"] != b["coefficients"] for a, b in pairs)
+    assert any(s["coefficients"] == MU.CUSTOM and s["ch"] == c for c in (1, 2) for s in ms)
+    # the geometry the tile kernel branches on: several tiles per block; a table beyond one tile's window; a table of three entries at any
+    # 2-byte phase; no output at all; a chunk above 48 000 outputs
+    assert T.geometry(1, 1024, 8000)[2] == 12204 and T.geometry(1, 7000, 48000)[0] + 2 == 13988 and T.geometry(2, 15, 48000)[0] + 2 == 3
+    assert T.geometry(2, 15, 96000)[2] == 0 and any((s["ch"], s["block_align"], s["rate"]) == (2, 15, 96000) and s["blocks"] == 65 for s in ms)
+    spb, ips, newlen = T.geometry(1, 256, 11025.5)
+    assert (ips, newlen, ips * newlen) == (23, 2168, 49864) and any((s["block_align"], s["rate"], s["blocks"]) == (256, 11025.5, 23) for s in ms)
+    # 65 blocks are two units of the pre-pass; blockAlign 7000 is its plain path
+    assert MU.blocks_per_unit(46, 2) == MU.blocks_per_unit(22, 1) == 64 and MU.blocks_per_unit(7000, 1) == 0
+
+
+def test_every_stream_meets_the_conditions_of_the_call(oracle, lib):
+    for s in lib:
+        if s["kind"] != "ms":
+            continue
+        what = T.tag(s)
+        assert len(s["bytes"]) == s["blocks"] * s["block_align"], what                       # whole blocks
+        _, rep = W.model_msadpcm(s["bytes"], s["block_align"], s["ch"], s["coefficients"])     # (raises on an index beyond the table that a data byte meets)
+        assert rep.max_delta < 2 ** 21 and rep.first_nan is None, what + (rep.max_delta,)
+        ncoef = len(s["coefficients"][0]) if s["coefficients"] else 7
+        assert all(p < ncoef for p in rep.pred_indices), what
+        if s["coefficients"]:
+            assert max(abs(a) + abs(b) for a, b in zip(*s["coefficients"])) < 65536, what
+    other = [s for s in lib if s.get("note") == "other headers behind the first"][0]
+    assert other["bytes"][7 * other["block_align"]] == 200 and other["bytes"][:7] != other["bytes"][other["block_align"]:other["block_align"] + 7]
+
+
+def test_the_oracles_chunk_tables_are_the_closed_forms(oracle, lib):
+    """nchunks, lens, pos, length_seconds as include/aukit_hip.h states them, on every MS stream, mixed down and not"""
+    seen = set()
+    for mono in (True, False):
+        for s in lib:
+            if s["kind"] != "ms":
+                continue
+            what = T.tag(s) + (mono,)
+            ref = T.oracle_stream(oracle, s, "linear", mono)
+            ba, nblk, nb = s["block_align"], s["blocks"], len(s["bytes"])
+            spb, ips, newlen = T.geometry(s["ch"], ba, s["rate"])
+            assert ref.final_status == 0, what
+            assert ref.channels == (2 if s["ch"] == 2 and not mono else 1), what
+            assert ref.length_seconds == nb / ba * spb / s["rate"], what
+            n = math.ceil(nblk / ips) if newlen else 0
+            assert ref.nchunks == n, what
+            for k in range(n):
+                done = min((k + 1) * ips, nblk)
+                assert int(ref.chunk_len[k, 0]) == (done - k * ips) * newlen, what + (k,)
+                assert ref.chunk_pos[k] == (done * ba + 1) / (ba * ips), what + (k,)
+            assert len(ref.data[0]) == (nblk * newlen if newlen else 0), what
+            seen.add(n)
+            if mono and s["note"] == "both clamps":
+                assert ref.data[0].max() == 127 and ref.data[0].min() == -128, what
+    assert seen == {0, 1, 2}
+
+
+def _files(oracle):
+    return MU.four_files(oracle)   # a PCM WAV, an IMA-ADPCM WAV, a mono MS-ADPCM WAV (the custom table), a stereo MS-ADPCM WAV
+
+
+def test_stream_many_sniffs_msadpcm_wav_files(oracle):
+    files, (m1, m2) = _files(oracle)
+    descs, ranges, lengths = aukit._sniff_many(files, stream=True, stream_dfpwm=True, stream_ima=True, stream_ms=True)
+    assert [d.codec for d in descs] == [N.CODEC_PCM, N.CODEC_ADPCM_WAV, N.CODEC_MSADPCM, N.CODEC_MSADPCM]
+    for i, s in ((2, m1), (3, m2)):
+        d = descs[i]
+        c1, c2 = s["coefficients"] if s["coefficients"] else W.MS_DEFAULT
+        assert (d.channels, d.sample_rate, d.block_align, d.ncoef) == (s["ch"], s["rate"], s["block_align"], len(c1)), i
+        assert list(d.coef1[:d.ncoef]) == list(c1) and list(d.coef2[:d.ncoef]) == list(c2), i
+        c, p = aukit._parse(files[i], N.CONTAINER_WAV, stream=True)   # what aukit.stream.wav hands to aukit.stream.msadpcm
+        assert ranges[i] == (c.payload_off, c.payload_len) and p == s["bytes"] and files[i][ranges[i][0]:ranges[i][0] + ranges[i][1]] == s["bytes"], i
+        assert math.isnan(lengths[i]) and math.isnan(c.length_seconds), i   # aukit.stream.msadpcm's own figure stands, as in aukit.stream.wav (:2993)
+    # alone, without the IMA switch
+    d2, r2, _ = aukit._sniff_many(files[2:], stream=True, stream_dfpwm=True, stream_ms=True)
+    assert [d.codec for d in d2] == [N.CODEC_MSADPCM] * 2 and r2 == ranges[2:]
+
+
+def test_without_the_keyword_every_refusal_keeps_its_words(oracle):
+    files, _ = _files(oracle)
+    old = r"stream\.many takes PCM, G\.711 and DFPWM \(the block codecs keep their own streams\)"
+    with pytest.raises(aukit.LuaError, match=r"^file 0: msadpcm payload: " + old + "$"):
+        aukit._sniff_many([files[2]], stream=True, stream_dfpwm=True)
+    with pytest.raises(aukit.LuaError, match=r"^file 2: msadpcm payload: stream\.many takes PCM, G\.711 and DFPWM payloads and IMA-ADPCM blocks \(the other block codecs keep their own streams\)$"):
+        aukit._sniff_many(files, stream=True, stream_dfpwm=True, stream_ima=True)
+    with pytest.raises(aukit.LuaError, match=r"^file 0: msadpcm payload: " + old + "$"):
+        aukit._sniff_many([files[2]], stream=True, stream_dfpwm=True, adpcm=True)
+    # the keyword means nothing without `stream`, and takes nothing but MS-ADPCM
+    with pytest.raises(aukit.LuaError, match=r"file 1: msadpcm payload: load_many takes"):
+        aukit._sniff_many([files[0], files[2]], stream_ms=True)
+    with pytest.raises(aukit.LuaError, match=r"^file 1: adpcm payload: stream\.many takes PCM, G\.711 and DFPWM payloads and MS-ADPCM blocks \(the other block codecs keep their own streams\)$"):
+        aukit._sniff_many(files, stream=True, stream_dfpwm=True, stream_ms=True)
+    with pytest.raises(aukit.LuaError, match=r"^file 1: qoa payload: stream\.many takes PCM, G\.711 and DFPWM payloads and IMA-ADPCM and MS-ADPCM blocks \(the other block codecs keep their own streams\)$"):
+        aukit._sniff_many([files[2], b"qoaf" + bytes(60)], stream=True, stream_dfpwm=True, stream_ima=True, stream_ms=True)
+    a, b = aukit._sniff_many(files[:2], stream=True, stream_dfpwm=True, stream_ima=True), aukit._sniff_many(files[:2], stream=True, stream_dfpwm=True, stream_ima=True, stream_ms=True)
+    assert a[1] == b[1] and [bytes(d) for d in a[0]] == [bytes(d) for d in b[0]]
+
+
+def test_stream_many_checks_its_arguments_before_any_device_work(oracle):
+    files, _ = _files(oracle)
+    old = r"file 2: msadpcm payload: stream\.many takes PCM, G\.711 and DFPWM payloads and IMA-ADPCM blocks \(the other block codecs keep their own streams\)"
+    for args, kw in (((True,), dict(adpcm=True)), ((True, True), {}), (({"mono": True, "adpcm": True},), {}), ((True, True, False), {})):
+        with pytest.raises(aukit.LuaError, match=old):       # `adpcm` alone keeps meaning IMA only
+            aukit.stream.many(files, *args, **kw)
+    with pytest.raises(aukit.LuaError, match=r"bad argument #4"):
+        aukit.stream.many(files[:1], True, True, "yes")
+    with pytest.raises(aukit.LuaError, match=r"bad argument #4"):
+        aukit.stream.many(files[:1], {"mono": True, "msadpcm": 1})
+    with pytest.raises(aukit.LuaError, match=r"bad argument #3"):
+        aukit.stream.many(files[:1], True, "yes", True)
+    with pytest.raises(aukit.LuaError, match=r"bad argument #2 \(unknown option ms\)"):
+        aukit.stream.many(files[:1], {"ms": True})
+    with pytest.raises(aukit.LuaError, match=r"file 1: adpcm payload: stream\.many takes PCM, G\.711 and DFPWM payloads and MS-ADPCM blocks"):
+        aukit.stream.many(files, True, msadpcm=True)
+
+
+def test_header_mirrors_and_shim_name_the_codec_and_the_option():
+    hdr = open(os.path.join(ROOT, "include", "aukit_hip.h")).read()
+    assert re.search(r"AUKIT_OPT_STREAM_MIXED_CODECS\s*=\s*6\b", hdr) and N.OPT_STREAM_MIXED_CODECS == 6
+    assert re.search(r"AUKIT_OPT_MIXED_CODECS\s*=\s*5\b", hdr) and N.OPT_MIXED_CODECS == 5
+    assert re.search(r"#define\s+AUKIT_ABI_VERSION\s+2\b", hdr)
+    at = hdr.index("int aukit_stream_decode_mixed(")
+    comment = hdr[hdr.rindex("/*", 0, at):at]
+    for word in ("AUKIT_CODEC_MSADPCM", "AUKIT_OPT_STREAM_MIXED_CODECS", "block_align", "ncoef", "coef1", "coef2", "first seven bytes", "l + r / 2", "2^21", "65536",
+                 "aukit.stream.msadpcm", "k_ms_mixed"):
+        assert word in comment, word
+    src = open(os.path.join(ROOT, "aukit_amd", "csrc", "stream_mixed.hip")).read()
+    assert "AUKIT_CODEC_DFPWM and AUKIT_CODEC_ADPCM_WAV)" in src and "under AUKIT_OPT_STREAM_MIXED_CODECS, AUKIT_CODEC_MSADPCM)" in src
+    # one planner of the pre-pass's units, in the header both calls include
+    plan = open(os.path.join(ROOT, "aukit_amd", "csrc", "mixed_plan.h")).read()
+    dec = open(os.path.join(ROOT, "aukit_amd", "csrc", "resample_mixed.hip")).read()
+    assert "mix_ms_blocks_per_unit" in plan and "mixed_ms_coefs" in plan and "struct MsMixUnit" in plan
+    for text in (src, dec):
+        assert "add_stream(" in text and "mix_ms_blocks_per_unit" not in text and "struct MsMixUnit" not in text
+    assert "__global__" not in src[src.index("static void plan_ms("):src.index("static void smix_plan(")]
+    from aukit_amd import batch as B
+    assert "OPT_STREAM_MIXED_CODECS" in B.stream_decode_mixed.__doc__ and "CODEC_MSADPCM" in B.stream_decode_mixed.__doc__
+    lua = open(os.path.join(ROOT, "aukit_amd", "lua", "aukit.lua")).read()
+    at = lua.index("function aukit.stream.many(files, mono)")
+    body = lua[at:lua.index("\nend\n", at)]
+    assert "mono.msadpcm" in body and "(c.desc.codec ~= 4 or not msadpcm)" in body and "(c.desc.codec ~= 3 or not adpcm)" in body
+    assert "aukit_ctx_set_option(ctx(), 6, 2 ^ CODEC.msadpcm)" in body and "aukit_ctx_set_option(ctx(), 6, 0)" in body
+    assert body.index("aukit_ctx_set_option(ctx(), 6, 0)") < body.index("if words then error(words, 2) end")   # put back also after a refused call
+    assert "stream.many takes PCM, G.711 and DFPWM payloads and IMA-ADPCM and MS-ADPCM blocks (the other block codecs keep their own streams)" in body
+    assert "stream.many takes PCM, G.711 and DFPWM (the block codecs keep their own streams)" in body
+
+
+def test_exports_are_unchanged():
+    """no new symbol: the option travels through aukit_ctx_set_option"""
+    assert len(N.EXPORTS) == 87 and not [e for e in N.EXPORTS if "msadpcm" in e or "codecs" in e]
