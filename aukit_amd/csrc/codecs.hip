@@ -905,6 +905,7 @@ struct ImaStreamParams {
     unsigned mid_lo, mid_end_full;       // k_ima_stream_f32: the clean rows of a full block (host-made: two 64-bit divisions per block otherwise)
     unsigned qstep;                      // k_ima_stream_f32<…, PH>: 64 PH fa / fb, the table entries that 64 PH outputs span (a whole number)
     unsigned *audit;                     // k_ima_stream_f32<…, 0, true>: [0] bits of the largest |tier 1 - tier 2| (a non-negative float), [1] outputs compared
+    int sinc_w;                          // k_ima_stream<SINC>: interpolate.sinc's window (aukit.lua:129: 10, or 30 under LuaJIT), the context's
 };
 
 template <int INTERP, typename OUT_T>
@@ -916,8 +917,10 @@ __global__ __launch_bounds__(256) void k_ima_stream(const ImaStreamParams P) {
     const unsigned long long ba = (unsigned long long)P.block_align;
     const unsigned long long nwr = (ba - 4ull * P.C) / (4ull * P.C);  // real word groups per block
     const double spb = (double)(ba - 4ull * P.C) * 2 / P.C;           // samplesPerBlock :2765
-    ResampleParams RP;  // only the position fields are used by pos_of / eval_at
-    RP.ratio = P.ratio; RP.rcp = P.rcp; RP.exact_rcp = P.exact_rcp; RP.sinc_w = 10;
+    // what pos_of / eval_at read: the position fields and, for sinc, the window and the hole flag — every one is set (eval_at branches on
+    // sinc_hole: left unset, the compiler may and did drop the whole sum, and k_ima_stream<SINC> was k_ima_stream<NONE>)
+    ResampleParams RP;
+    RP.ratio = P.ratio; RP.rcp = P.rcp; RP.exact_rcp = P.exact_rcp; RP.sinc_w = P.sinc_w; RP.sinc_hole = 0; RP.pos_mul = 0;
     for (unsigned long long gb = (unsigned long long)blockIdx.x * nwv + wave; gb < P.nblocks; gb += (unsigned long long)gridDim.x * nwv) {
         // stream of this block: binary search in blk0 (wave-uniform)
         unsigned lo = 0, hi = P.nstreams;
@@ -1057,8 +1060,8 @@ __global__ __launch_bounds__(256) void k_ima_stream_f32(const ImaStreamParams P,
     const unsigned long long ba = (unsigned long long)P.block_align;
     const unsigned long long nwr = (ba - 4ull) / 4ull;     // real word groups per block
     const double spb = (double)(ba - 4ull) * 2;            // samplesPerBlock :2765
-    ResampleParams RP;  // only the position fields are used by pos_of / eval_at
-    RP.ratio = P.ratio; RP.rcp = P.rcp; RP.exact_rcp = P.exact_rcp; RP.sinc_w = 10;
+    ResampleParams RP;  // only the position fields are used by pos_of / eval_at (linear and cubic only: the sinc fields are set for tidiness)
+    RP.ratio = P.ratio; RP.rcp = P.rcp; RP.exact_rcp = P.exact_rcp; RP.sinc_w = P.sinc_w; RP.sinc_hole = 0; RP.pos_mul = 0;
     const float c127 = 1.0f / 127.0f;
     constexpr int NPH = PH > 0 ? PH : 1;
     [[maybe_unused]] float4 pw[NPH];     // cubic: w0..w3 of the phase; linear: .x = fx
@@ -1507,7 +1510,7 @@ static int ima_stream(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         P.exact_rcp = exact_div_verified(ctx, ratio, (uint64_t)newlen_full + 2) ? 1 : 0;
         P.cap = (int)((ba - 4ull * C) * 2 / C + 8 + 8);
         P.cap += P.cap / 16 + 2;  // skewed LDS slots
-        P.out = a->dev; P.err = err;
+        P.out = a->dev; P.err = err; P.sinc_w = ctx->sinc_w;
         if (C == 1 && !ctx->exact_math && d->sample_rate == std::floor(d->sample_rate) && d->sample_rate <= 4e9) {
             unsigned long long x = 48000, y = (unsigned long long)d->sample_rate;
             while (y) { const unsigned long long tq = x % y; x = y; y = tq; }

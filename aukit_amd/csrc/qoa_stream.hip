@@ -136,6 +136,19 @@ __global__ __launch_bounds__(64) void k_qoa_stream_iir(const QsJob *jobs, const 
     }
 }
 
+// lines[1][i] = (0 + s_1 + ... + s_C) / C (:3326-3329) from the channels' doubles into AUKIT_F32 rows: the mean is rounded once.  (Audio:mono on F32
+// rows would take the mean of channels that were each rounded to float first: with l ~ -r the result is tens of its own float spacings off.)  meta: the audio's device layout table, len[n] | off[n] | stride[n] (audio_prepare); `bps` workgroups per stream
+__global__ __launch_bounds__(256) void k_qoa_mixdown_f32(const double *in, const unsigned long long *mi, float *out, const unsigned long long *mo, unsigned n, int C, unsigned bps) {
+    const unsigned s = blockIdx.x / bps, bx = blockIdx.x - s * bps;
+    if (s >= n) return;
+    const unsigned long long len = mi[s], ib = mi[n + s], st = mi[2ull * n + s], ob = mo[n + s];
+    for (unsigned long long i = (unsigned long long)bx * 256 + threadIdx.x; i < len; i += (unsigned long long)bps * 256) {
+        double acc = 0;
+        for (int c = 0; c < C; c++) acc = acc + in[ib + (unsigned long long)c * st + i];
+        out[ob + i] = (float)(acc / C);
+    }
+}
+
 struct QFrame { uint64_t off; int samples; };
 
 // round 2's aukit.stream.qoa: the fallback of qoa.hip (frames of more than 8192 samples, sample rates below ≈ 300 Hz)
@@ -238,7 +251,10 @@ int stream_qoa_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_des
         for (uint32_t k = 0; k < ck->nchunks[s]; k++) { ck->lens[(size_t)s * mc + k] = clen[s][k]; ck->pos[(size_t)s * mc + k] = cpos[s][k]; }
     int rc;
     aukit_audio *&full = ctx->stream_full;  // reused from call to call (audio_prepare keeps buffers that are large enough)
-    aukit_audio **dst = mono && C > 1 ? &full : out;
+    const bool mix = mono && C > 1;
+    const int out_dtype = dtype;
+    if (mix) dtype = AUKIT_F64;   // the channels stay the reference's doubles until their mean is taken: one rounding for AUKIT_F32 storage
+    aukit_audio **dst = mix ? &full : out;
     aukit_audio *a = *dst;
     if ((rc = audio_prepare(ctx, &a, in->n, C, 48000, dtype, lens.data()))) return rc;
     *dst = a;
@@ -301,9 +317,23 @@ int stream_qoa_host(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_des
         AUKIT_HIP_CHECK(hipGetLastError());
         if ((rc = ctx_end_kernel(ctx, "k_qoa_stream", in->total()))) return rc;
     }
-    if (mono && C > 1) {  // lines[1][i] = (0 + s_1 + ... + s_C) / C  :3326-3329 — the same sum order as Audio:mono
+    if (mix && out_dtype == AUKIT_F64) {  // lines[1][i] = (0 + s_1 + ... + s_C) / C  :3326-3329 — the same sum order as Audio:mono
         rc = aukit_mono(ctx, full, out);
         if (rc) return rc;
+    } else if (mix) {
+        aukit_audio *o = *out;
+        if ((rc = audio_prepare(ctx, &o, in->n, 1, 48000, AUKIT_F32, lens.data()))) return rc;
+        *out = o;
+        uint64_t longest = 0;
+        for (uint64_t l : lens) longest = std::max(longest, l);
+        if (longest) {
+            if ((rc = ctx_begin_kernel(ctx))) return rc;
+            const unsigned bps = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>((longest + 1023) / 1024, 1024), 0x7FFFFFFFull / in->n));
+            hipLaunchKernelGGL(k_qoa_mixdown_f32, dim3(in->n * bps), dim3(256), 0, ctx->stream, reinterpret_cast<const double *>(full->dev), reinterpret_cast<const unsigned long long *>(full->d_meta),
+                               reinterpret_cast<float *>(o->dev), reinterpret_cast<const unsigned long long *>(o->d_meta), in->n, C, bps);
+            AUKIT_HIP_CHECK(hipGetLastError());
+            if ((rc = ctx_end_kernel(ctx, "k_qoa_mixdown_f32", full->total * 8 + o->total * 4))) return rc;
+        }
     }
     chunks_deliver(ck, chunks_out);
     return AUKIT_OK;

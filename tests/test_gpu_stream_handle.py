@@ -6,6 +6,7 @@ pieces cut inside headers / blocks / frames."""
 import numpy as np
 import pytest
 
+from tests.stream_handle_util import pieces as _pieces, via_handle as _via_handle, whole as _whole
 from tests.util import pcm16
 
 pytestmark = pytest.mark.gpu
@@ -15,58 +16,6 @@ def _mods():
     from aukit_amd import _native as N
     from aukit_amd import batch as B
     return B, N
-
-
-def _whole(ctx, B, data, desc, interp, mono, dtype):
-    out, ck = B.stream_decode(ctx, B.Batch.upload(ctx, [data]), desc, interp, mono=mono, dtype=dtype)
-    chans = out.download()[0]
-    n = int(ck.nchunks[0])
-    res, off = [], 0
-    for k in range(n):
-        ln = int(ck.lens[0][k])
-        res.append(([c[off:off + ln] for c in chans], float(ck.pos[0][k])))
-        off += ln
-    return res, int(ck.status[0]), float(ck.length_seconds[0])
-
-
-def _pieces(rng, data, mode):
-    if mode == "bytes":
-        cuts = sorted(set(rng.integers(1, len(data), min(len(data) - 1, 300)).tolist()))
-    elif mode == "few":
-        cuts = sorted(set(rng.integers(1, len(data), 3).tolist()))
-    else:  # "mixed": runs of tiny pieces between big ones
-        cuts, p = [], 0
-        while p < len(data):
-            p += int(rng.choice([1, 2, 7, 100, 4096, 30000, 200000]))
-            if p < len(data):
-                cuts.append(p)
-    cuts = [0] + cuts + [len(data)]
-    return [data[a:b] for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
-
-
-def _via_handle(ctx, B, N, pieces, desc, interp, mono, dtype):
-    h = B.StreamHandle(ctx, desc, interp, mono, dtype)
-    res, err, it = [], None, iter(pieces)
-    done = False
-    try:
-        while True:
-            kind, chans, pos = h.next()
-            if kind == "chunk":
-                res.append((chans, pos))
-            elif kind == "end":
-                break
-            else:
-                p = None if done else next(it, None)
-                if p is None:
-                    done = True
-                    h.finish()
-                else:
-                    h.feed(p)
-    except N.AukitError as e:
-        err = e.code
-    length = h.length() if err is None else None
-    h.close()
-    return res, err, length
 
 
 def _inputs(oracle, N, B):
