@@ -547,16 +547,39 @@ def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm
     return descs, ranges, infos
 
 
-def _sniff_set(readers):
+def _sniff_set(readers, dfpwm=False):
     """aukit.stream.set's host half, up to the device: every reader is called once; its first piece, which holds the whole header (:2918), is
     sniffed by magic and walked by aukit_parse_container in its first-piece mode
     -> ([descriptor per reader], [the payload bytes behind the header per reader], [the container's length in seconds, NaN where the stream
     factory's own figure stands]).  A reader whose stream is no WAV / AIFF / AU, or whose payload is none of PCM, G.711 and IMA-ADPCM blocks,
-    raises LuaError naming the reader's index (0-based)."""
+    raises LuaError naming the reader's index (0-based).
+    `dfpwm`: stream.set's request for DFPWM members — a WAV reader whose payload is DFPWM is taken too, its length the container's; and an entry
+    may be a sequence (reader, "dfpwm"[, channels[, sampleRate]]) — stream.many's tuple shape, channels first, 1 channel and 48000 Hz where
+    they are left out — for a raw .dfpwm stream, which has no header: the reader's first piece is payload (None: the stream is empty) and the
+    length is None, as in the reference's function mode (:2495).  Without it both are refused by index in the words of before."""
     _expect(1, readers, "table")
     takes = "stream.set takes PCM and G.711 payloads and IMA-ADPCM blocks (the other codecs keep their own streams)"
+    if dfpwm:
+        takes = "stream.set takes PCM, G.711 and DFPWM payloads and IMA-ADPCM blocks (the other codecs keep their own streams)"
+    served = (N.CODEC_PCM, N.CODEC_G711, N.CODEC_ADPCM_WAV) + ((N.CODEC_DFPWM,) if dfpwm else ())
     descs, firsts, lengths = [], [], []
     for i, fn in enumerate(readers):
+        if isinstance(fn, (list, tuple)):
+            if not 2 <= len(fn) <= 4 or not callable(fn[0]) or fn[1] != "dfpwm":
+                raise LuaError(f"bad argument #1 (reader {i}: expected (function, \"dfpwm\"[, channels[, sampleRate]]))")
+            ch, rate = (fn[2] if len(fn) > 2 else None), (fn[3] if len(fn) > 3 else None)
+            for v, integral in ((ch, True), (rate, False)):
+                if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or (integral and v != int(v))):
+                    raise LuaError(f"bad argument #1 (reader {i}: expected number for channels and sampleRate)")
+            if not dfpwm:
+                raise LuaError(f"reader {i}: dfpwm payload: {takes}")
+            first = fn[0]()
+            if first is not None and not isinstance(first, (bytes, bytearray, memoryview)):
+                raise LuaError(f"bad argument #1 (reader {i}: expected string from the first call)")
+            descs.append(B.make_desc(N.CODEC_DFPWM, 1 if ch is None else int(ch), 48000 if rate is None else rate))
+            firsts.append(None if first is None else bytes(first))
+            lengths.append(None)
+            continue
         if not callable(fn):
             raise LuaError(f"bad argument #1 (reader {i}: expected function)")
         first = fn()
@@ -573,7 +596,7 @@ def _sniff_set(readers):
         except LuaError as e:
             raise LuaError(f"reader {i}: {e}") from None
         d = _desc_copy(c)
-        if d.codec not in (N.CODEC_PCM, N.CODEC_G711, N.CODEC_ADPCM_WAV):
+        if d.codec not in served:
             what = N.WAVDT[c.wav_data_type] if kind == "wav" else f"codec {d.codec}"
             raise LuaError(f"reader {i}: {what} payload: {takes}")
         descs.append(d)
@@ -903,17 +926,36 @@ class _StreamNS:
         rows = out.download()
         return [self._chunk_iter(out, ck, None if math.isnan(lengths[i]) else lengths[i], d.codec == N.CODEC_G711, i, rows) for i, d in enumerate(descs)]
 
-    def set(self, readers, mono=None):
+    def set(self, readers, mono=None, dfpwm=None):
         """aukit.stream.wav / aiff / au (fn, mono) for a LIST of reader functions — live sources, each a WAV / AIFF / AU stream of PCM, G.711 or
         IMA-ADPCM blocks with its own rate, format and channel count — served by ONE aukit_streamset: a list of (iterator, length) pairs in
         input order, each iterator handing out what the reader's own factory hands out.  Every reader's first piece holds the whole header
         (the reference's rule for function input, :2918).  A round starts when any iterator has nothing decided: the set pulls one piece from
         every unfinished reader and pumps once — the device work of all listeners is one upload, three launches and one download per round.
-        Without `mono` the streams must agree in channel count.  A payload the set does not take is refused by the reader's index."""
+        Without `mono` the streams must agree in channel count.  A payload the set does not take is refused by the reader's index.
+        DFPWM members are taken on request only — `dfpwm=True`, or `mono` given as the options table of the LuaJIT shim,
+        {"mono": ..., "dfpwm": True} —: a WAV reader whose payload is DFPWM (its length the container's), and raw entries
+        (reader, "dfpwm"[, channels[, sampleRate]]) — stream.many's tuple shape, channels first; 1 channel and 48000 Hz by default — whose pair
+        is aukit.stream.dfpwm(fn, sampleRate, channels, mono)'s: the length is None (:2495).  For the one open the context is opted in to DFPWM
+        members (AUKIT_OPT_STREAMSET_CODECS) and put back as it was behind it, also where the open is refused.  Without the request every
+        message is the one of before."""
+        if isinstance(mono, dict):
+            if set(mono) - {"mono", "dfpwm"}:
+                raise LuaError("bad argument #2 (unknown option " + sorted(set(mono) - {"mono", "dfpwm"})[0] + ")")
+            mono, dfpwm = mono.get("mono"), mono.get("dfpwm", dfpwm)
         _expect(2, mono, "boolean", "nil")
-        descs, firsts, lengths = _sniff_set(readers)
+        _expect(3, dfpwm, "boolean", "nil")
+        descs, firsts, lengths = _sniff_set(readers, dfpwm=bool(dfpwm))
         ctx = context()
-        st = _wrap(B.StreamSet, ctx, descs, _interp(defaultInterpolation, 0), bool(mono), N.F64)
+        was = ctx.option(N.OPT_STREAMSET_CODECS)
+        try:
+            if dfpwm:
+                _wrap(ctx.set_option, N.OPT_STREAMSET_CODECS, was | 1 << N.CODEC_DFPWM)
+            st = _wrap(B.StreamSet, ctx, descs, _interp(defaultInterpolation, 0), bool(mono), N.F64)
+        finally:
+            if dfpwm:
+                ctx.set_option(N.OPT_STREAMSET_CODECS, was)
+        readers = [r[0] if isinstance(r, (list, tuple)) else r for r in readers]
         n = len(readers)
         done = [False] * n
 
@@ -942,7 +984,7 @@ class _StreamNS:
                     raise LuaError("stream.set: every reader has ended and nothing is decided")   # (cannot happen: a finished member ends)
                 else:
                     a_round()
-        return [(it(s), (_wrap(st.length, s) if math.isnan(lengths[s]) else lengths[s])) for s in range(n)]
+        return [(it(s), (None if lengths[s] is None else _wrap(st.length, s) if math.isnan(lengths[s]) else lengths[s])) for s in range(n)]
 
     def wav(self, data, mono=None, ignoreHeader=None):  # :2927: header walk (library) + dispatch (:2992-2996)
         _expect_src(1, data)

@@ -701,7 +701,11 @@ class StreamSet:
     same bytes — the same chunks, positions, length and end — but `feed` only copies on the host, `pump` does the device work of a tick for all
     members at once (one upload, a repack launch, one mixed stream decode, a gather launch, one download, one wait) and `next` reads the host
     cache the last pump filled.  CODEC_PCM at or below 48 kHz, CODEC_G711, CODEC_ADPCM_WAV; none / linear / cubic; F64 or F32
-    (include/aukit_hip.h)."""
+    (include/aukit_hip.h).
+    CODEC_DFPWM members (aukit.stream.dfpwm) join on a context that asked for them before the set is opened:
+    ctx.set_option(N.OPT_STREAMSET_CODECS, 1 << N.CODEC_DFPWM) — option 7, read by the open alone.  Their decoder's state crosses iterator calls
+    and is carried from pump to pump inside the pump's one download.  A chunk of theirs may be longer than `cap` samples (48008 for a 48 kHz mono
+    stream): `next` then grows its buffer to the length the library names and asks again."""
 
     def __init__(self, ctx, descs, interp, mono=False, dtype=None, cap=48000):
         self.ctx = ctx
@@ -738,6 +742,11 @@ class StreamSet:
                                               C.byref(ch), C.byref(pos), C.byref(st))
             if rc == N.E_ARG and ch.value > self._buf_ch and ln.value <= self._cap:  # more channels than the buffer was sized for: the chunk is still there
                 self._buf_ch = ch.value
+                self._buf = np.empty(self._cap * self._buf_ch, dtype=np.float64)
+                continue
+            if rc == N.E_ARG and ln.value > self._cap:  # a chunk longer than the buffer was sized for (a DFPWM member's): the chunk is still there
+                self._cap = int(ln.value)
+                self._buf_ch = max(self._buf_ch, ch.value)
                 self._buf = np.empty(self._cap * self._buf_ch, dtype=np.float64)
                 continue
             N.check(rc)

@@ -52,6 +52,7 @@ struct aukit_ctx {
     bool chan_lens = false;     // AUKIT_OPT_CHANNEL_LENS: the host reads chunk lengths per channel (stream.pcm delivers its uneven last chunk)
     unsigned mixed_codecs = 0;  // AUKIT_OPT_MIXED_CODECS: bit 1 << codec lets aukit_decode_resample_mixed take that codec beyond its default list
     unsigned stream_mixed_codecs = 0;  // AUKIT_OPT_STREAM_MIXED_CODECS: the same for aukit_stream_decode_mixed, which reads this mask and no other
+    unsigned streamset_codecs = 0;     // AUKIT_OPT_STREAMSET_CODECS: bit 1 << codec lets aukit_streamset_open, which reads this mask and no other, take that codec
     bool fast_store_x4 = true;  // AUKIT_OPT_STORE_X4: LDS-transposed 16-byte stores in the fast kernels
     std::string last_kernel;
     float last_ms = 0.f;
@@ -216,6 +217,15 @@ int audio_prepare(aukit_ctx *ctx, aukit_audio **out, uint32_t n, int channels, d
 struct DfSliceHook {
     int slices = 1;
     std::function<int(unsigned, unsigned, unsigned long long, unsigned long long)> after_slice;
+};
+// a decoder state per stream and the states at given fed-byte positions, for the chunk-parallel DFPWM decoder (dfpwm_par.hip): stream s starts from
+// init6[6 s ..] (n, strength, pb, lpf, pn, - as dfpwm_par_dev.h packs them) where init6 is given, and behind the last verify pass a lane per
+// entry of `at` writes the state its stream's decoder has after `fed` fed bytes to d_states[6 slot ..] (a device table the caller owns)
+struct DfBoundary { unsigned stream, slot; unsigned long long fed; };
+struct DfStatesReq {
+    const int *init6 = nullptr;          // [n][6], host; null: every stream from the reset state
+    std::vector<DfBoundary> at;
+    int *d_states = nullptr;
 };
 // contexts that exist (runtime.hip): an audio remembers the context its deferred work was queued on (pend_ctx, lazy_ctx) and must not touch it once
 // it is gone; owner_ready() makes `ctx` (the context about to pay the work) wait for what `owner` has queued when the two differ

@@ -72,9 +72,11 @@ __global__ __launch_bounds__(256) void k_df_blockmaps(const DfParParams P) {
     SatMap f{0, -(1 << 28), 1 << 28};
     bool anyflat = false;
     if (f0 < f1) {
-        int prev = f0 ? (p[dfp_src_index(f0 - 1, P.feed)] >> 7) & 1 : 0;
+        // (a stream that starts from a given state, P.init: its previous bit is the state's, and its first step is a step like any other — from the
+        // reset state's strength 0 that lands on 8 as well)
+        int prev = f0 ? (p[dfp_src_index(f0 - 1, P.feed)] >> 7) & 1 : (P.init ? (P.init[(s % (unsigned)P.init_n) * 6 + 2] > 0 ? 1 : 0) : 0);
         u64 b = f0;
-        if (b == 0) {  // from the reset state (strength 0) the first step lands on 8 either way: do the stream's first byte bit by bit
+        if (b == 0 && !P.init) {  // from the reset state (strength 0) the first step lands on 8 either way: do the stream's first byte bit by bit
             unsigned byte = p[0];
             for (int k = 0; k < 8; k++) {
                 const int bit = byte & 1;
@@ -314,6 +316,32 @@ __global__ __launch_bounds__(64) void k_df_verify(const DfParParams P) {
     }
 }
 
+// Behind the last k_df_verify (which leaves every chunk's st_end final: a chunk it decodes again gets its true end state written over the recorded
+// one, and a chunk it does not touch started from the true state): a lane per (stream, fed-byte position) — the decoder's state there, for a caller
+// that carries it to a later call (a stream set's DFPWM members, stream_mixed.hip).  The lane starts from the end state of the last chunk that ends
+// at or before the position — from the stream's starting state where there is none — and walks only the fed bytes between that chunk's end and the
+// position: less than one chunk, state only, nothing is stored but the six words.  A position beyond the stream's fed bytes is not asked for
+__global__ __launch_bounds__(64) void k_df_boundary_states(const DfParParams P, const DfBoundary *list, unsigned n_list, int *states) {
+    const unsigned i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n_list) return;
+    const DfBoundary b = list[i];
+    const unsigned s = b.stream;
+    if (s >= P.n) return;
+    const u64 fed = P.fed[s], F = b.fed < fed ? b.fed : fed, L = (u64)P.bpc * P.W;
+    u64 done = F / L;                        // chunks that end at or before F (a chunk before the stream's last one is L fed bytes long)
+    if (done > P.nchunk) done = P.nchunk;
+    DfDec d{};
+    if (done) {
+        const int *se = P.st_end + ((size_t)s * P.nchunk + (done - 1)) * 6;
+        if (se[1] < 0) return;               // (no such chunk: the host asks for no position behind the fed bytes)
+        dfp_unpack(se, d);
+    } else if (P.init) dfp_unpack(P.init + (s % (unsigned)P.init_n) * 6, d);
+    DfOut O{};
+    O.feed = P.feed;
+    dfp_run<false>(P.src + P.off[s], done * L, F, d, O);
+    dfp_pack(d, states + (size_t)b.slot * 6);
+}
+
 // the exact strength at every chunk's warm-up start (P.s_start), for planners outside this file (dfpwm_spec.hip)
 int dfpwm_strength_scan(aukit_ctx *ctx, const DfParParams &P) {
     const unsigned F = P.msub ? P.msub : 1;
@@ -465,7 +493,7 @@ __global__ __launch_bounds__(256) void k_dfpwm_compact(const unsigned char *stag
 // (nothing launched) when the batch is better served one lane per stream.
 bool dfpwm_decode_parallel_feed(aukit_ctx *ctx, const unsigned char *src, const std::vector<uint64_t> &h_off, const std::vector<uint64_t> &h_fed, uint64_t run,
                                 uint64_t stride, int mode, int C, signed char *out, const u64 *d_out_off, const u64 *d_out_stride, uint64_t lead, int *rc,
-                                const DfSliceHook *hook) {
+                                const DfSliceHook *hook, const DfStatesReq *states) {
     const uint32_t n = (uint32_t)h_off.size();
     uint64_t fed_max = 0;
     for (uint64_t f : h_fed) fed_max = std::max(fed_max, f);
@@ -487,9 +515,11 @@ bool dfpwm_decode_parallel_feed(aukit_ctx *ctx, const unsigned char *src, const 
             if ((uint64_t)n * ((nblk + b - 1) / b) * 4 <= (uint64_t)ctx->num_cus * 4 * 64 * 3) { bpc = b; break; }
     const unsigned nchunk = nblk ? (nblk + bpc - 1) / bpc : 0;
     if (n == 0 || nchunk < 2 || getenv("AUKIT_DFPWM_SERIAL")) return false;
-    // scratch: stream table, maps, strengths, states, stats
+    // scratch: stream table, maps, strengths, states, stats, the context's carried state; for a caller with states of its own (DfStatesReq) a starting
+    // state per stream and the positions it asks for
     const size_t b_tab = (size_t)n * 16, b_maps = (size_t)n * nchunk * sizeof(SatMap), b_ss = (size_t)n * (nchunk + 1) * 4, b_st = (size_t)n * nchunk * 6 * 4;
-    if ((*rc = ctx->tmp_buf2.ensure(b_tab + b_maps + b_ss + 2 * b_st + 256 + 64))) return true;
+    const size_t b_fix = (size_t)round_up(b_tab + b_maps + b_ss + 2 * b_st + 256 + 64, 16), b_init = states && states->init6 ? (size_t)n * 24 : 0;
+    if ((*rc = ctx->tmp_buf2.ensure(b_fix + b_init + (states ? states->at.size() * sizeof(DfBoundary) : 0) + 64))) return true;
     char *B = reinterpret_cast<char *>(ctx->tmp_buf2.p);
     if ((*rc = h2d_table(ctx, B, h_off.data(), (size_t)n * 8)) || (*rc = h2d_table(ctx, B + (size_t)n * 8, h_fed.data(), (size_t)n * 8))) return true;
     DfParParams P{};
@@ -507,6 +537,12 @@ bool dfpwm_decode_parallel_feed(aukit_ctx *ctx, const unsigned char *src, const 
         P.init = di;
         P.init_n = ctx->sb_dfpwm_n == 2 ? 2 : 1;
     }
+    if (b_init) {   // a table of the caller's, a state per stream, in place of the context-wide one
+        int *di = reinterpret_cast<int *>(B + b_fix);
+        if ((*rc = h2d_table(ctx, di, states->init6, b_init))) return true;
+        P.init = di;
+        P.init_n = (int)n;
+    }
     P.mode = mode; P.C = C; P.out = out; P.out_off = d_out_off; P.out_stride = d_out_stride; P.lead = lead;
     if (hipMemsetAsync(P.stats, 0, 8, ctx->stream) != hipSuccess) { *rc = fail(AUKIT_E_HIP, "hipMemsetAsync failed"); return true; }
     hipLaunchKernelGGL((k_df_blockmaps<4, false>), dim3((unsigned)(((size_t)n * nchunk + 255) / 256)), dim3(256), 0, ctx->stream, P);
@@ -520,6 +556,12 @@ bool dfpwm_decode_parallel_feed(aukit_ctx *ctx, const unsigned char *src, const 
         hipLaunchKernelGGL(k_df_verify, dim3(n), dim3(64), 0, ctx->stream, P);
         if (hipGetLastError() != hipSuccess) { *rc = fail(AUKIT_E_HIP, "parallel DFPWM decode launch failed"); return true; }
         if (sliced && (*rc = hook->after_slice(k, nsl, (u64)P.c_lo * bpc * W, (u64)P.c_hi * bpc * W))) return true;  // fed bytes [lo, hi) of every stream are final
+    }
+    if (states && !states->at.empty()) {   // every st_end is final: the states at the positions the caller asked for
+        DfBoundary *d_at = reinterpret_cast<DfBoundary *>(B + b_fix + b_init);
+        if ((*rc = h2d_table(ctx, d_at, states->at.data(), states->at.size() * sizeof(DfBoundary)))) return true;
+        hipLaunchKernelGGL(k_df_boundary_states, dim3(((unsigned)states->at.size() + 63) / 64), dim3(64), 0, ctx->stream, P, d_at, (unsigned)states->at.size(), states->d_states);
+        if (hipGetLastError() != hipSuccess) { *rc = fail(AUKIT_E_HIP, "DFPWM boundary state launch failed"); return true; }
     }
     if (ctx->collect_stats) {
         unsigned h[2] = {0, 0};
@@ -539,7 +581,7 @@ bool dfpwm_decode_parallel(aukit_ctx *ctx, const aukit_batch *in, int mode, int 
         const uint64_t nb = in->off[s + 1] - in->off[s];
         h_fed[s] = nb ? nb + (nb + adv - 1) / adv - 1 : 0;  // Σ min(adv + 1, nb - adv k)
     }
-    return dfpwm_decode_parallel_feed(ctx, in->data(), h_off, h_fed, adv + 1, adv, mode, C, out, d_out_off, d_out_stride, lead, rc, hook);
+    return dfpwm_decode_parallel_feed(ctx, in->data(), h_off, h_fed, adv + 1, adv, mode, C, out, d_out_off, d_out_stride, lead, rc, hook, nullptr);
 }
 
 // aukit.dfpwm(d, 2, rate):mono():dfpwm() on a large batch (config 4).  The encoder is one serial chain per stream (its bits depend on its

@@ -46,9 +46,25 @@ static inline int fail_for_stream(int rc, unsigned s) {
 // aukit_stream_decode_mixed for a stream set (stream_mixed.hip, streamset.hip): stream s is the REST of a longer stream.  bytes_dropped / outputs_dropped
 // are what was dropped in front of it (the chunk positions and the length are the whole stream's: what aukit_ctx::sb_bytes / sb_outputs are to the
 // single-descriptor calls); nbytes is how many of the bytes from the batch's offset on are the stream's (the batch's next offset is only an upper bound)
-struct SMixCarry { uint64_t bytes_dropped, outputs_dropped, nbytes; };
+struct SMixCarry {
+    uint64_t bytes_dropped, outputs_dropped, nbytes;
+    // an AUKIT_CODEC_DFPWM stream (zeros otherwise, and in the public call): df_back — the pre-pass reports the decoder's state at every call boundary
+    // (SMixDfBack); df_on — the stream's decoder starts from df_state, the five words of DfDec as dfpwm_par_dev.h packs them (n, strength, pb, lpf, pn),
+    // and its row's element 0 (`last`, aukit.lua:2470) is df_state[3]: what aukit_ctx::sb_dfpwm is to the single-descriptor call
+    int df_back, df_on;
+    int df_state[6];
+};
+// where the pre-pass left the states of the streams that asked (df_back): entry first[s] + k of the device table `dev` (six ints each; scratch of the
+// call, valid until the context's next call) is stream s's decoder in front of call k of this decode — after the slices of calls 0 .. k - 1,
+// 6000 C + 1 bytes each, the overlap byte included; entry first[s] itself is the state the stream started from.  calls[s] entries per stream
+struct SMixDfBack {
+    const int *dev = nullptr;
+    size_t entries = 0;
+    std::vector<uint64_t> first;   // per stream of the batch (~0: none)
+    std::vector<uint32_t> calls;
+};
 int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
-                              aukit_chunks **chunks, const SMixCarry *carry /* n_descs, or null */);
+                              aukit_chunks **chunks, const SMixCarry *carry /* n_descs, or null */, SMixDfBack *back = nullptr /* where a carry sets df_back */);
 // what the stream's own aukit_stream_decode call refuses of a descriptor and a byte count, and the uneven last chunk (stream_mixed.hip)
 int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono);
 
@@ -129,7 +145,15 @@ static inline void mixed_dispatch(int interp, int dtype, F &&f) {
 
 // ---- the DFPWM row pre-pass: streams decoded to flat int8 rows by the chunk engine (dfpwm_par.hip)
 // the streams of one engine call: first byte, fed bytes and row offset of each; slices of `run` bytes advanced by `stride`
-struct DfRowGroup { std::vector<uint64_t> off, fed, row; uint64_t run = 0, stride = 0; };
+// `carried`: some stream of the group starts from a state of its own — init6 then holds six ints per stream (the reset state {-1, 0, -1, 0, -1} for
+// a stream that carries nothing) and `head` its row's element in front of the samples; `at`: the fed-byte positions whose states are handed back
+// (DfStatesReq, common.h).  A group with neither runs the engine exactly as before
+struct DfRowGroup {
+    std::vector<uint64_t> off, fed, row; uint64_t run = 0, stride = 0;
+    bool carried = false;
+    std::vector<int> init6, head;
+    std::vector<DfBoundary> at;
+};
 // a stream handle's carried decoder state is not a mixed call's: every stream starts from reset.  Off for a scope, whatever way it is left
 struct DfCarriedStateOff {
     aukit_ctx *ctx;
@@ -138,11 +162,12 @@ struct DfCarriedStateOff {
     ~DfCarriedStateOff() { ctx->sb_dfpwm_on = was; }
 };
 // Opens the pre-pass's timed region and runs the engine on group after group: the group's row offsets go to `table` (the groups' tables lie one behind
-// the other), its samples to rows + row offset + lead.  Behind a group the engine took, taken(d_row, streams) may enqueue more; a group it declined
-// (dfpwm_par.hip: nchunk < 2, every stream short) is listed in `declined` — the caller runs its lane-per-stream kernel on those and closes the region
+// the other), its samples to rows + row offset + lead.  Behind a group the engine took, taken(group index, d_row, streams) may enqueue more; a group it declined
+// (dfpwm_par.hip: nchunk < 2, every stream short) is listed in `declined` — the caller runs its lane-per-stream kernel on those and closes the region.
+// d_states: where the engine writes the states a group asks for (DfRowGroup::at)
 template <class Taken>
 static inline int mixed_dfpwm_rows(aukit_ctx *ctx, const aukit_batch *in, const std::vector<const DfRowGroup *> &groups, uint64_t lead, signed char *rows, char *table,
-                                   std::vector<size_t> *declined, Taken taken) {
+                                   std::vector<size_t> *declined, Taken taken, int *d_states = nullptr) {
     int rc;
     if ((rc = ctx_begin_kernel(ctx))) return rc;
     const DfCarriedStateOff from_reset(ctx);
@@ -153,9 +178,13 @@ static inline int mixed_dfpwm_rows(aukit_ctx *ctx, const aukit_batch *in, const 
         table += m * 8;
         int prc = AUKIT_OK;
         if ((rc = h2d_table(ctx, d_row, G.row.data(), m * 8))) return rc;
-        if (dfpwm_decode_parallel_feed(ctx, in->data(), G.off, G.fed, G.run, G.stride, 0 /* rows */, 1 /* one "channel": flat */, rows, d_row, nullptr, lead, &prc)) {
+        DfStatesReq req;
+        const bool with_states = G.carried || !G.at.empty();
+        if (with_states) { req.init6 = G.carried ? G.init6.data() : nullptr; req.at = G.at; req.d_states = d_states; }
+        if (dfpwm_decode_parallel_feed(ctx, in->data(), G.off, G.fed, G.run, G.stride, 0 /* rows */, 1 /* one "channel": flat */, rows, d_row, nullptr, lead, &prc, nullptr,
+                                       with_states ? &req : nullptr)) {
             if (prc) return prc;
-            taken(d_row, (uint32_t)m);
+            taken(g, d_row, (uint32_t)m);
         } else declined->push_back(g);
     }
     return AUKIT_OK;

@@ -174,7 +174,7 @@ int audio_from_int_rows(aukit_ctx *ctx, int src_kind, const void *rows_dev, cons
 // the DFPWM decoders the mixed-library calls run as pre-passes
 bool dfpwm_decode_parallel_feed(aukit_ctx *ctx, const unsigned char *src, const std::vector<uint64_t> &h_off, const std::vector<uint64_t> &h_fed, uint64_t run,
                                 uint64_t stride, int mode, int C, signed char *out, const unsigned long long *d_out_off, const unsigned long long *d_out_stride,
-                                uint64_t lead, int *rc, const DfSliceHook *hook = nullptr);  // dfpwm_par.hip
+                                uint64_t lead, int *rc, const DfSliceHook *hook = nullptr, const DfStatesReq *states = nullptr);  // dfpwm_par.hip
 int dfpwm_decode_list(aukit_ctx *ctx, const unsigned char *src, const unsigned long long *d_list, uint32_t n, signed char *rows);  // codecs.hip
 
 // position of output o (0-based) exactly as the reference computes it on the host

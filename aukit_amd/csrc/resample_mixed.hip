@@ -491,7 +491,7 @@ static int mix_dfpwm_prepass(aukit_ctx *ctx, const aukit_batch *in, const MixDfR
     char *const T = reinterpret_cast<char *>(ctx->tmp_buf.p) + L.df_tab_at;
     signed char *const rows = reinterpret_cast<signed char *>(ctx->tmp_buf.p);
     std::vector<size_t> declined;
-    int rc = mixed_dfpwm_rows(ctx, in, {&D.group}, 0, rows, T, &declined, [](const unsigned long long *, uint32_t) {});
+    int rc = mixed_dfpwm_rows(ctx, in, {&D.group}, 0, rows, T, &declined, [](size_t, const unsigned long long *, uint32_t) {});
     if (rc) return rc;
     if (declined.empty()) return ctx_end_kernel(ctx, "k_df_chunks(parallel dfpwm decode)", D.src + D.tot);
     unsigned long long *list = reinterpret_cast<unsigned long long *>(T + (size_t)D.n * 8);

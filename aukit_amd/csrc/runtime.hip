@@ -307,16 +307,16 @@ int aukit_ctx_set_sinc_window(aukit_ctx *c, int w) {
     c->sinc_w = w;
     return AUKIT_OK;
 }
-// AUKIT_OPT_MIXED_CODECS / AUKIT_OPT_STREAM_MIXED_CODECS: a mask of 1 << codec; refused as a whole, the mask as it was, where a bit names a codec the
-// option's calls (`who`) do not take on request
-static int set_codec_mask(unsigned *mask, int value, const char *opt, const char *who) {
-    const unsigned known = 1u << AUKIT_CODEC_MSADPCM, extra = (unsigned)value & ~known;
+// AUKIT_OPT_MIXED_CODECS / AUKIT_OPT_STREAM_MIXED_CODECS / AUKIT_OPT_STREAMSET_CODECS: a mask of 1 << codec; refused as a whole, the mask as it was,
+// where a bit names a codec the option's calls (`who`) do not take on request.  `only`: the one codec the option knows
+static int set_codec_mask(unsigned *mask, int value, const char *opt, const char *who, int only = AUKIT_CODEC_MSADPCM) {
+    const unsigned known = 1u << only, extra = (unsigned)value & ~known;
     if (extra) {
         static const char *names[] = {"AUKIT_CODEC_PCM", "AUKIT_CODEC_G711", "AUKIT_CODEC_ADPCM", "AUKIT_CODEC_ADPCM_WAV", "AUKIT_CODEC_MSADPCM", "AUKIT_CODEC_DFPWM",
                                       "AUKIT_CODEC_MDFPWM", "AUKIT_CODEC_QOA", "AUKIT_CODEC_FLAC"};
         const int bit = __builtin_ctz(extra);
-        if (bit < 9) return fail(AUKIT_E_UNSUPPORTED, "%s: %s (bit %d) is not a codec %s on request; only AUKIT_CODEC_MSADPCM is", opt, names[bit], bit, who);
-        return fail(AUKIT_E_UNSUPPORTED, "%s: bit %d names no codec (codec %d); only AUKIT_CODEC_MSADPCM is taken on request", opt, bit, bit);
+        if (bit < 9) return fail(AUKIT_E_UNSUPPORTED, "%s: %s (bit %d) is not a codec %s on request; only %s is", opt, names[bit], bit, who, names[only]);
+        return fail(AUKIT_E_UNSUPPORTED, "%s: bit %d names no codec (codec %d); only %s is taken on request", opt, bit, bit, names[only]);
     }
     *mask = (unsigned)value;
     return AUKIT_OK;
@@ -330,6 +330,7 @@ int aukit_ctx_set_option(aukit_ctx *c, int option, int value) {
     else if (option == AUKIT_OPT_CHANNEL_LENS) c->chan_lens = value != 0;
     else if (option == AUKIT_OPT_MIXED_CODECS) return set_codec_mask(&c->mixed_codecs, value, "AUKIT_OPT_MIXED_CODECS", "the per-stream-descriptor calls take");
     else if (option == AUKIT_OPT_STREAM_MIXED_CODECS) return set_codec_mask(&c->stream_mixed_codecs, value, "AUKIT_OPT_STREAM_MIXED_CODECS", "aukit_stream_decode_mixed takes");
+    else if (option == AUKIT_OPT_STREAMSET_CODECS) return set_codec_mask(&c->streamset_codecs, value, "AUKIT_OPT_STREAMSET_CODECS", "aukit_streamset_open takes", AUKIT_CODEC_DFPWM);
     else return fail(AUKIT_E_ARG, "unknown option %d", option);
     return AUKIT_OK;
 }

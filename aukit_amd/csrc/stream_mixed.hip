@@ -26,6 +26,11 @@
 // (k_smix_dfpwm_rows).  Iterator call k's table is the row from element 8 * (bytes fed before it) on: audio[0] is the call before's last sample.
 // A tile stages its window of raw int8 values as doubles (16-byte loads; one flat "channel"), a lane per output reads x = (o C) / ratio + 1,
 // v = isint ? audio[x] : clamp(interp(audio, x), -128, 127), and v goes to all C rows or, mixed down, ((0 + v) + v ...) / C to one (Q11).
+// A DFPWM stream may be the REST of a longer one (a stream set's member under AUKIT_OPT_STREAMSET_CODECS; stream_decode_mixed_carry, never the public
+// call): its carry then holds the decoder's state in front of the bytes (n, strength, pb, lpf, pn) — both pre-passes start from it, row element 0 is
+// the carried lpf (`last`, :2470), call k is the stream's call bytes_dropped / (6000 C) + k — and asks for the state at every call boundary of this
+// decode, a device table [stream][call][6]: the lane kernel writes an entry as it passes the boundary, the chunk engine's k_df_boundary_states
+// (dfpwm_par.hip) derives it from the end state of the last engine chunk at or before it.  A batch without such a carry launches what it always did.
 //
 // aukit.stream.adpcm (data_s, blockAlign, channels, rate, mono) (:2753-2835) is the third kind (IM = true, launched only for a batch that has an
 // AUKIT_CODEC_ADPCM_WAV stream).  k_smix_ima_scan finds, per stream, the first block that decodes a word under a header step index above 88 — the
@@ -413,17 +418,26 @@ __global__ __launch_bounds__(256) void k_stream_mixed(const SMixParams P) {
 // The pre-pass where the chunk engine declines (every DFPWM stream short): a lane per entry (first byte, byte count, row offset, advance) decodes
 // slices of adv + 1 bytes advanced by adv with one decoder into its row — element 0 the leading 0, the eight samples of a fed byte one 8-byte store
 // behind it (codecs.hip's k_dfpwm_decode_list is this for aukit.dfpwm's 6001 / 6000, without the leading element)
-struct SMixDfItem { unsigned long long src_off, nb, row_off, adv; };
-__global__ __launch_bounds__(64) void k_smix_dfpwm_rows(const unsigned char *src, const SMixDfItem *list, unsigned n, signed char *rows) {
+// The rest of a longer stream (a stream set's member, SMixCarry): `on` — the decoder starts from `st` (n, strength, pb, lpf, pn) and element 0 is
+// st[3], the last sample in front of the rest (the decoder's low-pass state IS its last output); st_slot (~0: not asked for) — the state in front of
+// call k goes to entry st_slot + k of `states`, six ints each, as the lane passes the boundary
+struct SMixDfItem { unsigned long long src_off, nb, row_off, adv, st_slot; int on, st[5]; };
+static_assert(sizeof(SMixDfItem) == 64, "SMixDfItem layout");
+__global__ __launch_bounds__(64) void k_smix_dfpwm_rows(const unsigned char *src, const SMixDfItem *list, unsigned n, signed char *rows, int *states) {
     const unsigned s = blockIdx.x * 64 + threadIdx.x;
     if (s >= n) return;
     const SMixDfItem it = list[s];
     const unsigned char *p = src + it.src_off;
     signed char *o = rows + it.row_off;
     DfDec d{};
-    o[0] = 0;  // audio[0] of the first call: `last` = 0  :2448
-    unsigned long long i = 1;
-    for (unsigned long long pos = 0; pos < it.nb; pos += it.adv) {
+    if (it.on) { d.p.n = it.st[0]; d.p.strength = it.st[1]; d.p.pb = it.st[2]; d.lpf = it.st[3]; d.pn = it.st[4]; }
+    o[0] = it.on ? (signed char)it.st[3] : 0;  // audio[0] of the first call: `last` = 0  :2448 — or the carried one  :2470
+    unsigned long long i = 1, k = 0;
+    for (unsigned long long pos = 0; pos < it.nb; pos += it.adv, k++) {
+        if (it.st_slot != ~0ull) {
+            int *q = states + (it.st_slot + k) * 6;
+            q[0] = d.p.n; q[1] = d.p.strength; q[2] = d.p.pb; q[3] = d.lpf; q[4] = d.pn; q[5] = 0;
+        }
         const unsigned long long cnt = it.nb - pos < it.adv + 1 ? it.nb - pos : it.adv + 1;  // str_sub(data, pos, pos + 6000 * channels)  :2455
         for (unsigned long long b = 0; b < cnt; b++) {
             unsigned byte = p[pos + b];
@@ -433,10 +447,11 @@ __global__ __launch_bounds__(64) void k_smix_dfpwm_rows(const unsigned char *src
         }
     }
 }
-// behind the chunk engine, which writes a row from element 1 on: the leading 0 of every row
-__global__ __launch_bounds__(256) void k_smix_row_heads(signed char *rows, const unsigned long long *row_off, unsigned n) {
+// behind the chunk engine, which writes a row from element 1 on: the leading 0 of every row — or, for a group with a carried stream, head[s]: the
+// carried low-pass state, 0 for a stream that carries nothing (null: every row's is 0)
+__global__ __launch_bounds__(256) void k_smix_row_heads(signed char *rows, const unsigned long long *row_off, unsigned n, const int *head) {
     const unsigned s = blockIdx.x * 256 + threadIdx.x;
-    if (s < n) rows[row_off[s]] = 0;
+    if (s < n) rows[row_off[s]] = head ? (signed char)head[s] : 0;
 }
 
 // ---- aukit.stream.adpcm's pre-pass: codecs.hip's k_ima_scan_headers and k_ima_mixed with the channel count and blockAlign taken per stream
@@ -731,6 +746,10 @@ struct SMixPlan {
     std::map<int, SMixDfGroup> df_groups;
     uint64_t df_tot = 0, df_src = 0;
     uint32_t df_n = 0;
+    // the decoder states handed back (SMixDfBack): entries of the device table, and per stream its first entry (~0: none) and its entries
+    uint64_t df_states = 0;
+    std::vector<uint64_t> df_first;
+    std::vector<uint32_t> df_calls;
     // the IMA streams that have a planned block; int16 entries of their rows, (block, channel) jobs, bytes read
     std::vector<SMixImaStream> ima_rows;
     uint64_t ima_elems = 0, ima_jobs = 0, ima_src = 0;
@@ -739,7 +758,7 @@ struct SMixPlan {
     uint64_t ms_elems = 0;
     uint64_t in_bytes = 0;
 
-    explicit SMixPlan(uint32_t n) : lens(n, 0), ck(chunks_create(n)) {}
+    explicit SMixPlan(uint32_t n) : lens(n, 0), ck(chunks_create(n)), df_first(n, ~0ull), df_calls(n, 0) {}
     // one iterator call of stream s: g.n_out outputs behind the stream's earlier ones (the row's offset is added once the audio is laid out)
     void add_call(uint32_t s, SMixSeg &g, double pos) {
         g.out_off = lens[s];
@@ -795,12 +814,15 @@ static void plan_g711(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_des
 
 // stream_dfpwm's plan (codecs2.hip) from byte 0: slices of adv + 1 bytes advanced by adv; a call's table starts at the row element that holds the
 // call before's last sample (element 0: the leading 0)
-static void plan_dfpwm(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc &d, uint64_t nb) {
+// `cy`: a stream set's member is the rest of a stream whose first bytes_dropped bytes — whole calls — are gone: call k here is the stream's call
+// bytes_dropped / (6000 C) + k, the length is the whole stream's, and with df_on the decoder and element 0 (`last`, :2470) carry on from df_state
+static void plan_dfpwm(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc &d, uint64_t nb, const SMixCarry &cy) {
     const int C = d.channels;
     const uint64_t adv = 6000ull * C, slice = adv + 1, src_off = g.src_off;
     const double ratio = 48000 / d.sample_rate;  // :2473
-    pl.ck->length_seconds[s] = (double)nb * 8 / d.sample_rate / C;  // :2495
-    uint64_t fed8 = 0, k = 0;
+    pl.ck->length_seconds[s] = (double)(nb + cy.bytes_dropped) * 8 / d.sample_rate / C;  // :2495
+    uint64_t fed8 = 0, k = cy.bytes_dropped / adv;
+    const uint64_t k0 = k;
     g.src_off = pl.df_tot;  // the row; where it lies is settled here, before anything is allocated
     g.w_lo = 0;
     for (uint64_t pos = 0; pos < nb; pos += adv, k++) {
@@ -815,7 +837,20 @@ static void plan_dfpwm(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_de
     SMixDfGroup &G = pl.df_groups[C];
     G.run = slice; G.stride = adv;
     G.off.push_back(src_off); G.fed.push_back(fed8 / 8); G.row.push_back(pl.df_tot);
-    G.items.push_back(SMixDfItem{src_off, nb, pl.df_tot, adv});
+    SMixDfItem it{src_off, nb, pl.df_tot, adv, ~0ull, cy.df_on ? 1 : 0, {-1, 0, -1, 0, -1}};   // (the reset state: DfDec's)
+    if (cy.df_on) for (int i = 0; i < 5; i++) it.st[i] = cy.df_state[i];
+    G.carried = G.carried || cy.df_on;
+    for (int i = 0; i < 5; i++) G.init6.push_back(it.st[i]);
+    G.init6.push_back(0);
+    G.head.push_back(cy.df_on ? it.st[3] : 0);
+    if (cy.df_back) {   // a boundary per call of this decode: the state in front of call j lies j whole slices into the feed
+        const uint64_t calls = k - k0;
+        it.st_slot = pl.df_states;
+        for (uint64_t j = 0; j < calls; j++) G.at.push_back(DfBoundary{(unsigned)(G.off.size() - 1), (unsigned)(pl.df_states + j), j * slice});
+        pl.df_first[s] = pl.df_states; pl.df_calls[s] = (uint32_t)calls;
+        pl.df_states += calls;
+    }
+    G.items.push_back(it);
     pl.df_tot += round_up(fed8 + 1, 16);
     pl.df_src += nb;
     pl.df_n++;
@@ -874,13 +909,13 @@ static void smix_plan(const aukit_batch *in, const aukit_codec_desc *descs, cons
     for (uint32_t s = 0; s < in->n; s++) {
         const aukit_codec_desc &d = descs[s];
         const uint64_t nb = smix_nbytes(in, carry, s);
-        const SMixCarry cy = carry ? carry[s] : SMixCarry{0, 0, nb};
+        const SMixCarry cy = carry ? carry[s] : SMixCarry{0, 0, nb, 0, 0, {0, 0, 0, 0, 0, 0}};
         pl.in_bytes += nb;
         SMixSeg g;
         memset(&g, 0, sizeof g);
         g.src_off = in->off[s];
         g.cls = cls_of[s];
-        if (d.codec == AUKIT_CODEC_DFPWM) plan_dfpwm(pl, s, g, d, nb);
+        if (d.codec == AUKIT_CODEC_DFPWM) plan_dfpwm(pl, s, g, d, nb, cy);
         else if (d.codec == AUKIT_CODEC_ADPCM_WAV) plan_ima(pl, s, g, d, nb, ima_bad[ima_i++], cy);
         else if (d.codec == AUKIT_CODEC_MSADPCM) plan_ms(pl, s, g, d, nb);  // (a stream set has no such member: no carry)
         else if (d.codec == AUKIT_CODEC_PCM) plan_pcm(pl, s, g, d, nb, interp, mono, cy);
@@ -903,15 +938,17 @@ static void smix_chunk_table(SMixPlan &pl, int C_out) {
 }
 
 // ---- phase 5: the pre-passes' scratch in ctx->tmp_buf: the DFPWM streams' int8 rows (each at a multiple of 16 bytes) and behind them the pre-pass's
-// tables (a row offset per stream, then a lane-per-stream item per stream); behind the DFPWM scratch the IMA pre-pass's int16 rows (planned blocks x
+// tables (a row offset per stream, then a lane-per-stream item per stream, then a row head per stream) and, where states are handed back, their table
+// (six ints per entry); behind the DFPWM scratch the IMA pre-pass's int16 rows (planned blocks x
 // channels x (samplesPerBlock + 8) entries: every row at a multiple of 16 bytes) and its stream table;
 // behind the IMA scratch k_ms_mixed's int16 rows (a row per (stream, channel) at a multiple of 16 bytes, 64 bytes to spare behind the last: the
 // tiles' 16-byte loads rely on them), its unit table, its coefficient sets and its two flag words
-struct SMixScratch { size_t df_tab_at = 0, ima_at = 0, ima_tab_at = 0, ms_at = 0, ms_unit_at = 0, ms_coef_at = 0, ms_flag_at = 0, size = 0; };
+struct SMixScratch { size_t df_tab_at = 0, df_states_at = 0, ima_at = 0, ima_tab_at = 0, ms_at = 0, ms_unit_at = 0, ms_coef_at = 0, ms_flag_at = 0, size = 0; };
 static SMixScratch smix_scratch(const SMixPlan &pl) {
     Carve carve;
     SMixScratch L;
-    if (pl.df_n) { carve.take((size_t)pl.df_tot); L.df_tab_at = carve.take((size_t)pl.df_n * (8 + sizeof(SMixDfItem))); }  // (the rows are at 0)
+    if (pl.df_n) { carve.take((size_t)pl.df_tot); L.df_tab_at = carve.take((size_t)pl.df_n * (8 + sizeof(SMixDfItem) + 4)); }  // (the rows are at 0)
+    if (pl.df_states) L.df_states_at = carve.take((size_t)pl.df_states * 24, 0);
     if (pl.ima_jobs) { L.ima_at = carve.take((size_t)pl.ima_elems * 2); L.ima_tab_at = carve.take(pl.ima_rows.size() * sizeof(SMixImaStream)); }
     if (!pl.ms.units.empty()) {
         L.ms_at = carve.take((size_t)pl.ms_elems * 2);
@@ -930,10 +967,19 @@ static int smix_dfpwm_prepass(aukit_ctx *ctx, const aukit_batch *in, const SMixP
     std::vector<const DfRowGroup *> groups;
     for (const auto &kv : pl.df_groups) groups.push_back(&kv.second);
     std::vector<size_t> declined;
-    int rc = mixed_dfpwm_rows(ctx, in, groups, 1 /* behind the leading 0 */, rows, T, &declined, [&](const unsigned long long *d_row, uint32_t m) {
-        hipLaunchKernelGGL(k_smix_row_heads, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, rows, d_row, m);
-    });
-    if (rc) return rc;
+    int *const d_states = pl.df_states ? reinterpret_cast<int *>(reinterpret_cast<char *>(ctx->tmp_buf.p) + L.df_states_at) : nullptr;
+    int *const d_heads = reinterpret_cast<int *>(T + (size_t)pl.df_n * (8 + sizeof(SMixDfItem)));
+    int hrc = AUKIT_OK;
+    int rc = mixed_dfpwm_rows(ctx, in, groups, 1 /* behind the leading 0 */, rows, T, &declined, [&](size_t g, const unsigned long long *d_row, uint32_t m) {
+        const int *heads = nullptr;
+        if (groups[g]->carried) {   // (the groups' heads lie one behind the other, as their row offsets do)
+            int *h = d_heads + (d_row - reinterpret_cast<const unsigned long long *>(T));
+            if (!hrc) hrc = h2d_table(ctx, h, groups[g]->head.data(), (size_t)m * 4);
+            heads = h;
+        }
+        hipLaunchKernelGGL(k_smix_row_heads, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, rows, d_row, m, heads);
+    }, d_states);
+    if (rc || (rc = hrc)) return rc;
     std::vector<SMixDfItem> lanes;  // the streams of the groups the engine declined
     for (size_t g : declined) {
         const std::vector<SMixDfItem> &items = static_cast<const SMixDfGroup *>(groups[g])->items;
@@ -942,7 +988,7 @@ static int smix_dfpwm_prepass(aukit_ctx *ctx, const aukit_batch *in, const SMixP
     if (!lanes.empty()) {
         SMixDfItem *d_items = reinterpret_cast<SMixDfItem *>(T + (size_t)pl.df_n * 8);
         if ((rc = h2d_table(ctx, d_items, lanes.data(), lanes.size() * sizeof(SMixDfItem)))) return rc;
-        hipLaunchKernelGGL(k_smix_dfpwm_rows, dim3(((unsigned)lanes.size() + 63) / 64), dim3(64), 0, ctx->stream, in->data(), d_items, (unsigned)lanes.size(), rows);
+        hipLaunchKernelGGL(k_smix_dfpwm_rows, dim3(((unsigned)lanes.size() + 63) / 64), dim3(64), 0, ctx->stream, in->data(), d_items, (unsigned)lanes.size(), rows, d_states);
     }
     if (hipGetLastError() != hipSuccess) return fail(AUKIT_E_HIP, "DFPWM pre-pass launch failed");
     return ctx_end_kernel(ctx, declined.size() < groups.size() ? "k_df_chunks(parallel dfpwm decode)" : "k_smix_dfpwm_rows", pl.df_src + pl.df_tot);
@@ -1043,9 +1089,11 @@ static int smix_launch(aukit_ctx *ctx, const aukit_batch *in, const SMixClasses 
 }
 
 // the call itself.  `carry` (null: the public call, every stream counted from byte 0): per stream, what a stream set has dropped in front of the
-// bytes and how many of the slot's bytes are the stream's (mixed_plan.h).  A DFPWM stream's decoder state is not carried: a set has none
+// bytes and how many of the slot's bytes are the stream's (mixed_plan.h); a DFPWM stream's carry may hold the decoder's state in front of the bytes
+// and ask for the states at this decode's call boundaries, which `back` then names (the set's next carry comes from there).  A batch in which no
+// carry does either launches what it always launched
 int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
-                              aukit_chunks **chunks, const SMixCarry *carry) {
+                              aukit_chunks **chunks, const SMixCarry *carry, SMixDfBack *back) {
     // what can be refused is refused before the device is touched; `*out` and `*chunks` keep what they held
     int rc;
     if ((rc = smix_validate(ctx, in, descs, n_descs, interp, mono, dtype, out, carry))) return rc;
@@ -1062,7 +1110,8 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
     smix_plan(in, descs, carry, T.cls_of, interp, mono != 0, ima_bad, pl);
     smix_chunk_table(pl, C_out);
     const uint64_t nt = smix_count_tiles(T, pl);
-    if (nt > 0xFFFFFFF0ull || pl.ima_jobs > 0x7FFFFFF0ull * 64 || pl.ms.units.size() > 0x7FFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
+    if (nt > 0xFFFFFFF0ull || pl.ima_jobs > 0x7FFFFFF0ull * 64 || pl.ms.units.size() > 0x7FFFFFF0ull || pl.df_states > 0x7FFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
+    if (pl.df_states && !back) return fail(AUKIT_E_ARG, "null argument");
 
     // the scratch is sized before `*out` is touched, and its pointer is read after
     const SMixScratch L = smix_scratch(pl);
@@ -1072,8 +1121,13 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
     aukit_audio *a = *out;
     if ((rc = audio_prepare(ctx, &a, n, C_out, 48000, dtype, pl.lens.data()))) return rc;
     *out = a;
+    if ((nt || pl.df_states) && pl.df_n && (rc = smix_dfpwm_prepass(ctx, in, pl, L))) return rc;   // (states are owed even where no call has an output)
+    if (back) {
+        back->dev = pl.df_states ? reinterpret_cast<const int *>(reinterpret_cast<const char *>(ctx->tmp_buf.p) + L.df_states_at) : nullptr;
+        back->entries = (size_t)pl.df_states;
+        back->first = pl.df_first; back->calls = pl.df_calls;
+    }
     if (nt) {
-        if (pl.df_n && (rc = smix_dfpwm_prepass(ctx, in, pl, L))) return rc;
         if (pl.ima_jobs && (rc = smix_ima_prepass(ctx, in, pl, L))) return rc;
         const std::vector<SMixTile> tiles = smix_tiles(T, pl, a, nt);
         if ((rc = smix_launch(ctx, in, T, pl, tiles, L, a, interp, dtype))) return rc;

@@ -20,6 +20,13 @@
 // The contract is the handle's: member s hands out aukit_stream_decode's chunk list for its concatenated bytes.  A chunk is decided once a later
 // chunk of the same decode exists, or the member is finished.  One bad member ends alone: whatever would refuse the whole mixed call is asked of
 // every member on the host first (check_smix_stream), and such a member never enters a batch.
+//
+// stream.dfpwm members (AUKIT_CODEC_DFPWM; only a set opened on a context that set AUKIT_OPT_STREAMSET_CODECS has them): ONE decoder runs through the
+// whole stream, so a member holds the decoder's state in front of its rest (n, strength, pb, lpf, pn: the handle's df_state) and hands it to the engine
+// in its carry; the engine's pre-pass starts from it and reports the state at every call boundary of the decode into a device table.  That table is
+// copied to pinned host memory on the pump's stream in front of the pump's one wait — no launch and no read-back of its own — and the compaction plan,
+// which drops `shift` whole calls of 6000 C bytes (restart_rule's DFPWM case: lead 0), takes the state at boundary `shift` behind the wait.  An
+// unfinished member is decoded up to a multiple of `channels` bytes, a finished one whole, as the handle does.
 #include <algorithm>
 #include <deque>
 #include "mixed_plan.h"
@@ -109,8 +116,13 @@ struct SSetMember {
     int end_status = 0;
     std::string end_msg;
     double length = 0;
+    // stream.dfpwm: the decoder's state in front of the rest (n, strength, pb, lpf, pn: dfpwm_par_dev.h), valid once calls were dropped — the handle's df_state
+    bool df_on = false;
+    int df_state[6] = {0, 0, 0, 0, 0, 0};
     std::deque<SSetChunk> q;
 };
+// a compaction planned in front of the pump's wait: member s's next state is entry `entry` of the states the pump downloads
+struct SSetDfFix { uint32_t s; size_t entry; };
 
 }  // namespace aukit
 
@@ -134,6 +146,10 @@ struct aukit_streamset {
     // pinned host cache of decided chunks: appended to by every pump, rewound once every chunk in it has been handed out
     double *cache = nullptr;
     size_t cache_cap = 0, cache_used = 0, cache_live = 0;
+    // pinned host copy of the DFPWM boundary states of the last decode (part of the pump's one download), and the members that take theirs from it
+    int *df_host = nullptr;
+    size_t df_host_cap = 0;
+    std::vector<aukit::SSetDfFix> df_fix;
 };
 
 namespace aukit {
@@ -150,7 +166,17 @@ static int pinned_grow(void **p, size_t *cap, size_t used, size_t need, size_t e
     return AUKIT_OK;
 }
 
-// restart_rule's PCM / G.711 / IMA cases (stream_handle.hip): the bytes of a whole iterator call, and whether the rest starts one call early
+// behind a wait on the set's stream: the members compacted in this pump take the state in front of their rest from the downloaded table
+static void sset_apply_states(aukit_streamset *S) {
+    for (const SSetDfFix &f : S->df_fix) {
+        SSetMember &M = S->m[f.s];
+        for (int i = 0; i < 6; i++) M.df_state[i] = S->df_host[f.entry * 6 + i];
+        M.df_on = true;
+    }
+    S->df_fix.clear();
+}
+
+// restart_rule's PCM / G.711 / IMA / DFPWM cases (stream_handle.hip): the bytes of a whole iterator call, and whether the rest starts one call early
 static void sset_restart(SSetMember &M, int interp) {
     const aukit_codec_desc &d = M.desc;
     const uint64_t C = (uint64_t)std::max(d.channels, 1);
@@ -159,6 +185,8 @@ static void sset_restart(SSetMember &M, int interp) {
         M.call_bytes = (uint64_t)stream_pcm_call_frames(d.sample_rate, interp) * C * (uint64_t)std::max(d.bit_depth / 8, 1);
     } else if (d.codec == AUKIT_CODEC_G711) {
         M.call_bytes = (uint64_t)d.sample_rate * C;
+    } else if (d.codec == AUKIT_CODEC_DFPWM) {
+        M.call_bytes = 6000 * C;   // lead 0: the rest starts at the next call, with the decoder's state and its last output carried (df_state)
     } else {
         const double spb = (double)((uint64_t)d.block_align - 4 * C) * 2 / (double)C;   // :2765
         M.call_bytes = (uint64_t)std::ceil(d.sample_rate / spb) * (uint64_t)d.block_align;   // :2766-2767
@@ -169,7 +197,7 @@ static void sset_restart(SSetMember &M, int interp) {
 static uint64_t sset_whole_frames(const SSetMember &M, uint64_t nb) {
     const uint64_t C = (uint64_t)std::max(M.desc.channels, 1);
     if (M.desc.codec == AUKIT_CODEC_PCM) return nb - nb % (C * (uint64_t)std::max(M.desc.bit_depth / 8, 1));
-    if (M.desc.codec == AUKIT_CODEC_G711) return nb - nb % C;
+    if (M.desc.codec == AUKIT_CODEC_G711 || M.desc.codec == AUKIT_CODEC_DFPWM) return nb - nb % C;
     return nb;
 }
 
@@ -286,6 +314,7 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
     std::vector<SSetGPiece> gpieces;
     std::vector<std::pair<uint32_t, SSetChunk>> fresh;   // (member, chunk), `at` relative to this pump's part of the cache
     uint64_t gather_elems = 0;
+    S->df_fix.clear();
     if (!jobs.empty()) {
         const uint32_t nj = (uint32_t)jobs.size();
         std::vector<aukit_codec_desc> descs(nj);
@@ -298,11 +327,25 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
         for (uint32_t i = 0; i < nj; i++) {
             const SSetMember &M = S->m[jobs[i].s];
             descs[i] = M.desc;
-            carry[i] = SMixCarry{M.sb_bytes, M.sb_outputs, jobs[i].usable};
+            carry[i] = SMixCarry{M.sb_bytes, M.sb_outputs, jobs[i].usable, 0, 0, {0, 0, 0, 0, 0, 0}};
+            if (M.desc.codec == AUKIT_CODEC_DFPWM && !jobs[i].ends) {   // an unfinished stream.dfpwm member: the states at this decode's call boundaries come back
+                carry[i].df_back = 1;
+            }
+            if (M.desc.codec == AUKIT_CODEC_DFPWM && M.df_on) {
+                carry[i].df_on = 1;
+                for (int k = 0; k < 6; k++) carry[i].df_state[k] = M.df_state[k];
+            }
             B.off[i] = M.slot;
         }
         B.off[nj] = S->arena_used;
-        if ((rc = stream_decode_mixed_carry(ctx, &B, descs.data(), nj, S->interp, S->mono, S->dtype, &S->out, &S->ck, carry.data()))) return rc;
+        SMixDfBack back;
+        if ((rc = stream_decode_mixed_carry(ctx, &B, descs.data(), nj, S->interp, S->mono, S->dtype, &S->out, &S->ck, carry.data(), &back))) return rc;
+        if (back.entries) {   // the states travel with the pump's one download: queued here, on the set's stream, awaited with the chunks below
+            void *hp = S->df_host;
+            if ((rc = pinned_grow(&hp, &S->df_host_cap, 0, back.entries * 6, sizeof(int)))) return rc;
+            S->df_host = reinterpret_cast<int *>(hp);
+            AUKIT_HIP_CHECK(hipMemcpyAsync(S->df_host, back.dev, back.entries * 24, hipMemcpyDeviceToHost, ctx->stream));
+        }
         const aukit_chunks &ck = *S->ck;
         const aukit_audio &a = *S->out;
         const size_t mc = std::max<uint32_t>(ck.max_chunks, 1);
@@ -336,10 +379,16 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
                 M.sb_bytes += M.resident; M.resident = 0;
                 continue;
             }
-            // (5) the compaction plan: the whole calls whose chunks are out and that no later chunk depends on stay behind at the next repack
+            // (5) the compaction plan: the whole calls whose chunks are out and that no later chunk depends on stay behind at the next repack.
+            // stream.dfpwm: a decided call k has its overlap byte — call k + 1 exists only if byte (k + 1) 6000 C does, and that IS call k's overlap byte —
+            // so the state at boundary `shift` is the decoder's behind `shift` whole slices, whatever is fed later
             const uint64_t shift = M.lead ? (M.skip ? M.skip - 1 : 0) : M.skip;   // the fresh decode's chunk 0 is this one's chunk `shift`
             if (shift && M.call_bytes && shift * M.call_bytes <= M.resident) {
                 const uint64_t drop = shift * M.call_bytes;
+                if (M.desc.codec == AUKIT_CODEC_DFPWM) {
+                    if (back.first[i] == ~0ull || shift >= back.calls[i]) continue;   // (no state for that boundary: the member keeps its prefix)
+                    S->df_fix.push_back(SSetDfFix{J.s, (size_t)(back.first[i] + shift)});
+                }
                 for (uint32_t k = 0; k < shift; k++) M.sb_outputs += ck.lens[(size_t)i * mc + k];
                 M.sb_bytes += drop;
                 M.drop += drop; M.resident -= drop;
@@ -371,6 +420,7 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
         AUKIT_HIP_CHECK(hipMemcpyAsync(S->cache + S->cache_used, S->d_gather.p, (size_t)gather_elems * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
     AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    sset_apply_states(S);
     for (auto &f : fresh) {
         f.second.at += S->cache_used;
         S->m[f.first].q.push_back(f.second);
@@ -393,9 +443,16 @@ int aukit_streamset_open(aukit_ctx *ctx, const aukit_codec_desc *descs, uint32_t
     if (interp < 0 || interp > 3) return fail(AUKIT_E_ARG, "invalid interpolation");
     if (interp == AUKIT_INTERP_SINC) return fail(AUKIT_E_UNSUPPORTED, "sinc interpolation is not served for a stream set: it keeps aukit_stream_open");
     int rc;
-    if ((rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV},
-                                 "stream %u: codec %d keeps aukit_stream_open (a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711 and AUKIT_CODEC_ADPCM_WAV)")))
-        return rc;
+    // AUKIT_OPT_STREAMSET_CODECS: stream.dfpwm members join on a context that asked for them, read here and nowhere else; without the bit the call
+    // answers in the words of before
+    if ((ctx->streamset_codecs >> AUKIT_CODEC_DFPWM) & 1u)
+        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_DFPWM},
+                                "stream %u: codec %d keeps aukit_stream_open (a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV and, under "
+                                "AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM)");
+    else
+        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV},
+                                "stream %u: codec %d keeps aukit_stream_open (a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711 and AUKIT_CODEC_ADPCM_WAV)");
+    if (rc) return rc;
     if ((rc = mixed_check_channels(n, mono, [&](uint32_t s) { return descs[s].channels; }))) return rc;
     for (uint32_t s = 0; s < n; s++)
         if ((rc = check_smix_stream(&descs[s], 0, mono != 0))) return fail_for_stream(rc, s);
@@ -450,8 +507,9 @@ int aukit_streamset_pump(aukit_streamset *S, uint32_t *n_ready) {
     const int rc = sset_pump(S, n_ready);
     if (rc) {   // whatever was queued reads the staging buffer and the tables no longer: the next feed may write them
         const std::string msg = aukit_last_error();
-        (void)hipStreamSynchronize(S->ctx->stream);
+        const bool waited = hipStreamSynchronize(S->ctx->stream) == hipSuccess;
         (void)hipGetLastError();
+        if (waited) sset_apply_states(S); else S->df_fix.clear();
         return fail(rc, "%s", msg.c_str());
     }
     return AUKIT_OK;
@@ -513,6 +571,7 @@ void aukit_streamset_close(aukit_streamset *S) {
     for (int i = 0; i < 2; i++) if (S->arena[i]) (void)hipFree(S->arena[i]);
     if (S->stage) (void)hipHostFree(S->stage);
     if (S->cache) (void)hipHostFree(S->cache);
+    if (S->df_host) (void)hipHostFree(S->df_host);
     S->d_stage.release(); S->d_tab.release(); S->d_gather.release();
     delete S;
 }

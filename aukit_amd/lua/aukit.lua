@@ -952,39 +952,73 @@ end
 -- first piece holds the whole header (:2918) -> a list of {iterator, length} pairs in input order, each iterator handing out what aukit.stream.wav / aiff /
 -- au(fn, mono) hands out.  A round starts when any iterator has nothing decided: one piece is pulled from every unfinished reader, then one pump does the
 -- device work of all of them (one upload, three launches, one download).  A payload the set does not take is refused by the reader's index.
+-- DFPWM members are taken on request only: `mono` given as an options table, {mono = ..., dfpwm = true}.  A WAV reader whose payload is DFPWM is then
+-- taken too (its length the container's), and an entry may be {reader, "dfpwm"[, channels[, sampleRate]]} — stream.many's entry, channels first; 1 channel
+-- and 48000 Hz by default — for a raw .dfpwm stream, which has no header: its pair is aukit.stream.dfpwm(fn, sampleRate, channels, mono)'s, the length nil
+-- (:2495).  For the one open the context is opted in (AUKIT_OPT_STREAMSET_CODECS, option 7, bit 1 << AUKIT_CODEC_DFPWM) and put back behind it, also where
+-- the open is refused.  Without the request every message is the one of before.
 function aukit.stream.set(readers, mono)
-    expect(1, readers, "table") expect(2, mono, "boolean", "nil")
+    expect(1, readers, "table") expect(2, mono, "boolean", "table", "nil")
+    local dfpwm = false
+    if type(mono) == "table" then
+        for k in pairs(mono) do if k ~= "mono" and k ~= "dfpwm" then error("bad argument #2 (unknown option " .. tostring(k) .. ")", 2) end end
+        if (mono.mono ~= nil and type(mono.mono) ~= "boolean") or (mono.dfpwm ~= nil and type(mono.dfpwm) ~= "boolean") then
+            error("bad argument #2 (expected boolean options)", 2)
+        end
+        mono, dfpwm = mono.mono, mono.dfpwm or false
+    end
     local n = #readers
     local descs = ffi.new("aukit_codec_desc[?]", math.max(n, 1))
-    local firsts, lengths, done = {}, {}, {}
-    local takes = "stream.set takes PCM and G.711 payloads and IMA-ADPCM blocks (the other codecs keep their own streams)"
+    local firsts, lengths, done, raw = {}, {}, {}, {}
+    local takes = dfpwm and "stream.set takes PCM, G.711 and DFPWM payloads and IMA-ADPCM blocks (the other codecs keep their own streams)"
+                  or "stream.set takes PCM and G.711 payloads and IMA-ADPCM blocks (the other codecs keep their own streams)"
+    local fns = {}
     for i = 1, n do
-        if type(readers[i]) ~= "function" then error("bad argument #1 (reader " .. (i - 1) .. ": expected function)", 2) end
-        local f = readers[i]()
-        if type(f) ~= "string" then error("bad argument #1 (reader " .. (i - 1) .. ": expected string from the first call)", 2) end
-        if f:sub(1, 4) == "qoaf" then error("reader " .. (i - 1) .. ": qoa payload: " .. takes, 2) end
-        local kind
-        for _, m in ipairs(MAGIC) do if f:find(m[1]) then kind = m[2] break end end
-        if not kind then error("reader " .. (i - 1) .. ": not a WAV, AIFF or AU stream", 2) end
-        local c = ffi.new("aukit_container")
-        if C.aukit_parse_container(ffi.cast("const uint8_t*", f), #f, kind, 2, c) ~= 0 then error("reader " .. (i - 1) .. ": " .. ffi.string(C.aukit_last_error()), 2) end
-        if c.desc.codec > 1 and c.desc.codec ~= 3 then   -- 0: PCM, 1: G.711, 3: AUKIT_CODEC_ADPCM_WAV
-            error("reader " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: " .. takes, 2)
+        local e = readers[i]
+        if type(e) == "table" then
+            if type(e[1]) ~= "function" or e[2] ~= "dfpwm" or #e > 4 then error("bad argument #1 (reader " .. (i - 1) .. ": expected {function, \"dfpwm\"[, channels[, sampleRate]]})", 2) end
+            if (e[3] ~= nil and (type(e[3]) ~= "number" or e[3] % 1 ~= 0)) or (e[4] ~= nil and type(e[4]) ~= "number") then
+                error("bad argument #1 (reader " .. (i - 1) .. ": expected number for channels and sampleRate)", 2)
+            end
+            if not dfpwm then error("reader " .. (i - 1) .. ": dfpwm payload: " .. takes, 2) end
+            local f = e[1]()
+            if f ~= nil and type(f) ~= "string" then error("bad argument #1 (reader " .. (i - 1) .. ": expected string from the first call)", 2) end
+            descs[i - 1] = desc {codec = "dfpwm", channels = e[3] or 1, sampleRate = e[4] or 48000}
+            fns[i], firsts[i], raw[i], done[i] = e[1], f, true, false   -- (firsts[i] == nil: the stream is empty, the first round finishes it)
+        else
+            fns[i] = e
+            if type(readers[i]) ~= "function" then error("bad argument #1 (reader " .. (i - 1) .. ": expected function)", 2) end
+            local f = readers[i]()
+            if type(f) ~= "string" then error("bad argument #1 (reader " .. (i - 1) .. ": expected string from the first call)", 2) end
+            if f:sub(1, 4) == "qoaf" then error("reader " .. (i - 1) .. ": qoa payload: " .. takes, 2) end
+            local kind
+            for _, m in ipairs(MAGIC) do if f:find(m[1]) then kind = m[2] break end end
+            if not kind then error("reader " .. (i - 1) .. ": not a WAV, AIFF or AU stream", 2) end
+            local c = ffi.new("aukit_container")
+            if C.aukit_parse_container(ffi.cast("const uint8_t*", f), #f, kind, 2, c) ~= 0 then error("reader " .. (i - 1) .. ": " .. ffi.string(C.aukit_last_error()), 2) end
+            if c.desc.codec > 1 and c.desc.codec ~= 3 and (c.desc.codec ~= 5 or not dfpwm) then   -- 0: PCM, 1: G.711, 3: AUKIT_CODEC_ADPCM_WAV; 5: AUKIT_CODEC_DFPWM, on request
+                error("reader " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: " .. takes, 2)
+            end
+            descs[i - 1] = c.desc
+            firsts[i] = f:sub(tonumber(c.payload_off) + 1, tonumber(c.payload_off + c.payload_len))
+            lengths[i] = c.length_seconds   -- NaN: the stream factory's own figure stands
+            done[i] = false
         end
-        descs[i - 1] = c.desc
-        firsts[i] = f:sub(tonumber(c.payload_off) + 1, tonumber(c.payload_off + c.payload_len))
-        lengths[i] = c.length_seconds   -- NaN: the stream factory's own figure stands
-        done[i] = false
     end
     local sp = ffi.new("aukit_streamset*[1]")
-    check(C.aukit_streamset_open(ctx(), descs, n, INTERP[aukit.defaultInterpolation], mono and 1 or 0, F64, sp))
+    -- dfpwm: AUKIT_OPT_STREAMSET_CODECS (7) with bit 1 << AUKIT_CODEC_DFPWM for this one open; the shim's context sets no other bit, so 0 puts it back
+    if dfpwm then check(C.aukit_ctx_set_option(ctx(), 7, 2 ^ CODEC.dfpwm)) end
+    local rc = C.aukit_streamset_open(ctx(), descs, n, INTERP[aukit.defaultInterpolation], mono and 1 or 0, F64, sp)
+    local words = rc ~= 0 and ffi.string(C.aukit_last_error()) or nil
+    if dfpwm then C.aukit_ctx_set_option(ctx(), 7, 0) end
+    if words then error(words, 2) end
     local set = ffi.gc(sp[0], C.aukit_streamset_close)
     local ready = ffi.new("uint32_t[1]")
     local function round(pieces)
         for i = 1, n do
             if not done[i] then
                 local piece
-                if pieces then piece = pieces[i] else piece = readers[i]() end
+                if pieces then piece = pieces[i] else piece = fns[i]() end
                 if piece == nil then done[i] = true check(C.aukit_streamset_finish(set, i - 1))
                 else check(C.aukit_streamset_feed(set, i - 1, ffi.cast("const uint8_t*", piece), #piece)) end
             end
@@ -992,7 +1026,7 @@ function aukit.stream.set(readers, mono)
         check(C.aukit_streamset_pump(set, ready))
     end
     round(firsts)
-    local CAP = 48000   -- a chunk of stream.pcm / g711 / adpcm never exceeds a second of output
+    local CAP = 48000   -- a chunk of stream.pcm / g711 / adpcm never exceeds a second of output; stream.dfpwm's may (48008 at 48 kHz mono): the buffer grows
     local buf_ch = 2
     local buf = ffi.new("double[?]", CAP * buf_ch)
     local len, ch, st, pos, secs = ffi.new("uint32_t[1]"), ffi.new("int32_t[1]"), ffi.new("int32_t[1]"), ffi.new("double[1]"), ffi.new("double[1]")
@@ -1002,6 +1036,12 @@ function aukit.stream.set(readers, mono)
         local it = function()
             while not ended do
                 local rc = C.aukit_streamset_next(set, s, buf, CAP * buf_ch, CAP, len, ch, pos, st)
+                if rc == -1 and len[0] > CAP then   -- a chunk longer than the buffer was sized for (a DFPWM member's): the chunk is still there
+                    CAP = len[0]
+                    buf_ch = math.max(buf_ch, ch[0])
+                    buf = ffi.new("double[?]", CAP * buf_ch)
+                    rc = C.aukit_streamset_next(set, s, buf, CAP * buf_ch, CAP, len, ch, pos, st)
+                end
                 if rc == -1 and ch[0] > buf_ch and len[0] <= CAP then   -- more channels than the buffer was sized for: the chunk is still there
                     buf_ch = ch[0]
                     buf = ffi.new("double[?]", CAP * buf_ch)
@@ -1025,7 +1065,8 @@ function aukit.stream.set(readers, mono)
             return nil
         end
         check(C.aukit_streamset_length(set, s, secs))
-        res[i] = {it, lengths[i] == lengths[i] and lengths[i] or secs[0]}
+        if raw[i] then res[i] = {it, nil}   -- function mode has no length (:2495)
+        else res[i] = {it, lengths[i] == lengths[i] and lengths[i] or secs[0]} end
     end
     return res
 end

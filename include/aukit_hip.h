@@ -162,12 +162,17 @@ typedef enum {
                                    codec named, and the context keeps the mask it had.  The mask is meant to carry later codecs as they are taken:
                                    a host sets the bits of what it is prepared to receive.  With 0 every call answers as it did before the option
                                    existed. */
-    AUKIT_OPT_STREAM_MIXED_CODECS = 6 /* the same for aukit_stream_decode_mixed, the only call that reads it: a bit mask of 1 << codec, 0 by default,
+    AUKIT_OPT_STREAM_MIXED_CODECS = 6,/* the same for aukit_stream_decode_mixed, the only call that reads it: a bit mask of 1 << codec, 0 by default,
                                    exactly one bit known, 1 << AUKIT_CODEC_MSADPCM (aukit.stream.msadpcm's streams, see that call); any other bit is
                                    AUKIT_E_UNSUPPORTED, the codec named (or "bit N"), and the context keeps the mask it had.  A mask of its own and
                                    not a second reader of option 5: a host that asked aukit_decode_resample_mixed for MS-ADPCM rows has not asked
                                    the stream call for anything.  aukit_decode_resample_mixed and aukit_streamset_open ignore it (a stream set
                                    keeps refusing the codec whatever either mask says).  With 0 every call answers exactly as before. */
+    AUKIT_OPT_STREAMSET_CODECS = 7 /* the same for aukit_streamset_open, the only call that reads it, and only while it opens (a set that is open keeps
+                                   what it was opened with): a bit mask of 1 << codec, 0 by default, exactly one bit known, 1 << AUKIT_CODEC_DFPWM
+                                   (aukit.stream.dfpwm's streams as members of a set, see that call); any other bit is AUKIT_E_UNSUPPORTED, the codec
+                                   named (or "bit N"), and the context keeps the mask it had.  Options 5 and 6 keep their one bit each: a DFPWM bit
+                                   there is still refused, and neither opens a set to anything.  With 0 every call answers exactly as before. */
 } aukit_option;
 int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);
 /* counters of the most recent call that produced them (AUKIT_OPT_COLLECT_STATS = 1) */
@@ -511,6 +516,19 @@ void aukit_stream_close(aukit_stream *s);
  * What a descriptor alone decides is refused at open with the member's index appended.  Every other codec keeps aukit_stream_open
  * (AUKIT_E_UNSUPPORTED by name) — AUKIT_CODEC_DFPWM too, although the mixed call streams it: its decoder's state crosses iterator calls and a
  * set carries none (out of scope here).  The set is the handle of a context WITHOUT AUKIT_OPT_CHANNEL_LENS, whatever the context says.
+ * On request, AUKIT_OPT_STREAMSET_CODECS with bit 1 << AUKIT_CODEC_DFPWM set on the context when the set is opened, AUKIT_CODEC_DFPWM members join
+ * (without the bit the refusal above stands, word for word; with it a refusal of a further codec names AUKIT_CODEC_DFPWM in its list; sinc stays
+ * refused, and AUKIT_CODEC_MDFPWM, QOA, FLAC and MS-ADPCM keep aukit_stream_open).  Such a member is aukit.stream.dfpwm (aukit.lua:2439-2496) as the
+ * handle serves it: an unfinished member is decoded up to a multiple of `channels` bytes, a finished one whole; an iterator call is 6000 * channels
+ * bytes and the rest starts at the next call (no call is kept in front of it).  The decoder's state does cross iterator calls, and the set carries
+ * it ON THE DEVICE SIDE of the pump: the mixed engine's DFPWM pre-pass starts every member from the state the member holds (n, strength, pb, lpf, pn;
+ * row element 0, the reference's `last`, is the carried lpf), and reports the state at every call boundary of the decode — the lane-per-stream
+ * kernel as it passes them, the chunk engine through one more kernel (k_df_boundary_states: a lane per (stream, boundary) that starts from the end
+ * state of the last engine chunk ending at or before the boundary and walks less than one chunk).  The boundary states ride in the pump's one
+ * download; the compaction plan keeps the one at the boundary the rest will start from.  A pump still has one wait, no launch per member and no
+ * read-back of its own for states; no dropped byte is decoded a second time to learn a state (the handle walks all of them with one lane).  A chunk
+ * of such a member may be longer than 48000 samples (8 * (6000 * channels + 1) * (48000 / rate) / channels, rounded up): size `cap` for it, or read
+ * `*len` from the AUKIT_E_ARG refusal and call again.
  * One bad member ends alone.  A finished member whose bytes the string call refuses (data that ends inside a sample; inside a frame without
  * the mix-down) hands out, as the handle does, the chunks of its whole frames — those decided earlier, then the rest — and from then on that
  * status and message; it enters no later pump, and no other member notices. */
