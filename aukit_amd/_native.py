@@ -29,6 +29,7 @@ MAX_PLANAR_CH = 64    # AUKIT_MAX_PLANAR_CHANNELS (the descriptor's predictor / 
 OPT_EXACT_MATH, OPT_STORE_X4, OPT_COLLECT_STATS, OPT_DFPWM_SPECULATE, OPT_CHANNEL_LENS, OPT_MIXED_CODECS = 0, 1, 2, 3, 4, 5
 OPT_STREAM_MIXED_CODECS = 6   # aukit_stream_decode_mixed's mask of 1 << codec (only CODEC_MSADPCM is known); OPT_MIXED_CODECS is the decode call's
 OPT_STREAMSET_CODECS = 7      # aukit_streamset_open's mask of 1 << codec (only CODEC_DFPWM is known), read when a set is opened
+OPT_STREAMSET_BLOCK_CODECS = 8   # aukit_streamset_open's second mask (only CODEC_MSADPCM is known), read when a set is opened
 COUNTER_DFPWM_CHUNKS, COUNTER_DFPWM_CHUNKS_REDONE, COUNTER_FLAC_FUSED, COUNTER_TIER1_ERR_NANO, COUNTER_TIER1_OUTPUTS = 0, 1, 2, 3, 4
 COUNTER_DFPWM_RESPECULATED, COUNTER_DFPWM_HARD, COUNTER_RECURRENCE_F32, COUNTER_QOA_WAVE = 5, 6, 7, 8
 WAVE_NONE, WAVE_SINE, WAVE_TRIANGLE, WAVE_SAWTOOTH, WAVE_SQUARE = 0, 1, 2, 3, 4

@@ -547,7 +547,7 @@ def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm
     return descs, ranges, infos
 
 
-def _sniff_set(readers, dfpwm=False):
+def _sniff_set(readers, dfpwm=False, msadpcm=False):
     """aukit.stream.set's host half, up to the device: every reader is called once; its first piece, which holds the whole header (:2918), is
     sniffed by magic and walked by aukit_parse_container in its first-piece mode
     -> ([descriptor per reader], [the payload bytes behind the header per reader], [the container's length in seconds, NaN where the stream
@@ -556,12 +556,14 @@ def _sniff_set(readers, dfpwm=False):
     `dfpwm`: stream.set's request for DFPWM members — a WAV reader whose payload is DFPWM is taken too, its length the container's; and an entry
     may be a sequence (reader, "dfpwm"[, channels[, sampleRate]]) — stream.many's tuple shape, channels first, 1 channel and 48000 Hz where
     they are left out — for a raw .dfpwm stream, which has no header: the reader's first piece is payload (None: the stream is empty) and the
-    length is None, as in the reference's function mode (:2495).  Without it both are refused by index in the words of before."""
+    length is None, as in the reference's function mode (:2495).  Without it both are refused by index in the words of before.
+    `msadpcm`: stream.set's request for MS-ADPCM members — a WAV reader whose payload is MS-ADPCM blocks (format 2) is taken too: the descriptor is
+    the container walk's (blockAlign and the `fmt` chunk's coefficient list), the payload what follows the header in the first piece, the length NaN
+    (aukit.stream.msadpcm's own figure stands, as for IMA-ADPCM blocks).  Without it such a reader is refused by index in the words of before, whatever `dfpwm` says."""
     _expect(1, readers, "table")
-    takes = "stream.set takes PCM and G.711 payloads and IMA-ADPCM blocks (the other codecs keep their own streams)"
-    if dfpwm:
-        takes = "stream.set takes PCM, G.711 and DFPWM payloads and IMA-ADPCM blocks (the other codecs keep their own streams)"
-    served = (N.CODEC_PCM, N.CODEC_G711, N.CODEC_ADPCM_WAV) + ((N.CODEC_DFPWM,) if dfpwm else ())
+    takes = "stream.set takes " + ("PCM, G.711 and DFPWM" if dfpwm else "PCM and G.711") + " payloads and " + ("IMA-ADPCM and MS-ADPCM" if msadpcm else "IMA-ADPCM") + \
+        " blocks (the other codecs keep their own streams)"
+    served = (N.CODEC_PCM, N.CODEC_G711, N.CODEC_ADPCM_WAV) + ((N.CODEC_DFPWM,) if dfpwm else ()) + ((N.CODEC_MSADPCM,) if msadpcm else ())
     descs, firsts, lengths = [], [], []
     for i, fn in enumerate(readers):
         if isinstance(fn, (list, tuple)):
@@ -926,7 +928,7 @@ class _StreamNS:
         rows = out.download()
         return [self._chunk_iter(out, ck, None if math.isnan(lengths[i]) else lengths[i], d.codec == N.CODEC_G711, i, rows) for i, d in enumerate(descs)]
 
-    def set(self, readers, mono=None, dfpwm=None):
+    def set(self, readers, mono=None, dfpwm=None, msadpcm=None):
         """aukit.stream.wav / aiff / au (fn, mono) for a LIST of reader functions — live sources, each a WAV / AIFF / AU stream of PCM, G.711 or
         IMA-ADPCM blocks with its own rate, format and channel count — served by ONE aukit_streamset: a list of (iterator, length) pairs in
         input order, each iterator handing out what the reader's own factory hands out.  Every reader's first piece holds the whole header
@@ -938,23 +940,32 @@ class _StreamNS:
         (reader, "dfpwm"[, channels[, sampleRate]]) — stream.many's tuple shape, channels first; 1 channel and 48000 Hz by default — whose pair
         is aukit.stream.dfpwm(fn, sampleRate, channels, mono)'s: the length is None (:2495).  For the one open the context is opted in to DFPWM
         members (AUKIT_OPT_STREAMSET_CODECS) and put back as it was behind it, also where the open is refused.  Without the request every
-        message is the one of before."""
+        message is the one of before.
+        MS-ADPCM WAV readers (format 2: aukit.stream.wav's dispatch to aukit.stream.msadpcm with the stream's blockAlign and coefficient list) are
+        taken with `msadpcm=True`, or the key "msadpcm" of the options table: for the one open the context is opted in to MS-ADPCM members
+        (AUKIT_OPT_STREAMSET_BLOCK_CODECS, an option of its own) and put back as it was behind it, also where the open is refused.  Without it such a
+        reader is refused by index, as before."""
         if isinstance(mono, dict):
-            if set(mono) - {"mono", "dfpwm"}:
-                raise LuaError("bad argument #2 (unknown option " + sorted(set(mono) - {"mono", "dfpwm"})[0] + ")")
-            mono, dfpwm = mono.get("mono"), mono.get("dfpwm", dfpwm)
+            if set(mono) - {"mono", "dfpwm", "msadpcm"}:
+                raise LuaError("bad argument #2 (unknown option " + sorted(set(mono) - {"mono", "dfpwm", "msadpcm"})[0] + ")")
+            mono, dfpwm, msadpcm = mono.get("mono"), mono.get("dfpwm", dfpwm), mono.get("msadpcm", msadpcm)
         _expect(2, mono, "boolean", "nil")
         _expect(3, dfpwm, "boolean", "nil")
-        descs, firsts, lengths = _sniff_set(readers, dfpwm=bool(dfpwm))
+        _expect(4, msadpcm, "boolean", "nil")
+        descs, firsts, lengths = _sniff_set(readers, dfpwm=bool(dfpwm), msadpcm=bool(msadpcm))
         ctx = context()
-        was = ctx.option(N.OPT_STREAMSET_CODECS)
+        was, was_block = ctx.option(N.OPT_STREAMSET_CODECS), ctx.option(N.OPT_STREAMSET_BLOCK_CODECS)
         try:
             if dfpwm:
                 _wrap(ctx.set_option, N.OPT_STREAMSET_CODECS, was | 1 << N.CODEC_DFPWM)
+            if msadpcm:
+                _wrap(ctx.set_option, N.OPT_STREAMSET_BLOCK_CODECS, was_block | 1 << N.CODEC_MSADPCM)
             st = _wrap(B.StreamSet, ctx, descs, _interp(defaultInterpolation, 0), bool(mono), N.F64)
         finally:
             if dfpwm:
                 ctx.set_option(N.OPT_STREAMSET_CODECS, was)
+            if msadpcm:
+                ctx.set_option(N.OPT_STREAMSET_BLOCK_CODECS, was_block)
         readers = [r[0] if isinstance(r, (list, tuple)) else r for r in readers]
         n = len(readers)
         done = [False] * n

@@ -705,7 +705,11 @@ class StreamSet:
     CODEC_DFPWM members (aukit.stream.dfpwm) join on a context that asked for them before the set is opened:
     ctx.set_option(N.OPT_STREAMSET_CODECS, 1 << N.CODEC_DFPWM) — option 7, read by the open alone.  Their decoder's state crosses iterator calls
     and is carried from pump to pump inside the pump's one download.  A chunk of theirs may be longer than `cap` samples (48008 for a 48 kHz mono
-    stream): `next` then grows its buffer to the length the library names and asks again."""
+    stream): `next` then grows its buffer to the length the library names and asks again.
+    CODEC_MSADPCM members (aukit.stream.msadpcm: make_desc with block_align and, where the file has its own, coefficients) join under an option of
+    their own, ctx.set_option(N.OPT_STREAMSET_BLOCK_CODECS, 1 << N.CODEC_MSADPCM) — option 8, read by the open alone; OPT_STREAM_MIXED_CODECS is
+    not needed.  A member whose blocks carry a predictor index beyond the coefficient table, or reach a delta of 2^21 or more, ends alone: its
+    earlier chunks, then E_LUA / E_UNSUPPORTED from `next`.  A chunk of theirs may exceed `cap` too (48060 for blockAlign 22 at 8 kHz, mono)."""
 
     def __init__(self, ctx, descs, interp, mono=False, dtype=None, cap=48000):
         self.ctx = ctx

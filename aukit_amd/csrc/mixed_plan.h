@@ -64,7 +64,8 @@ struct SMixDfBack {
     std::vector<uint32_t> calls;
 };
 int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
-                              aukit_chunks **chunks, const SMixCarry *carry /* n_descs, or null */, SMixDfBack *back = nullptr /* where a carry sets df_back */);
+                              aukit_chunks **chunks, const SMixCarry *carry /* n_descs, or null */, SMixDfBack *back = nullptr /* where a carry sets df_back */,
+                              unsigned block_codecs = 0 /* 1 << AUKIT_CODEC_MSADPCM: the caller takes such streams, whatever the context's masks say */);
 // what the stream's own aukit_stream_decode call refuses of a descriptor and a byte count, and the uneven last chunk (stream_mixed.hip)
 int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono);
 
@@ -203,7 +204,10 @@ struct MsMixUnit {
 };
 static_assert(sizeof(MsMixUnit) == 48, "MsMixUnit layout");
 size_t ms_mixed_unit_lds(uint64_t nblk, uint64_t block_align, int channels);
-int ms_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const void *d_units, uint64_t n_units, const void *d_coefs, short *rows, unsigned *flags, size_t lds, uint64_t bytes);
+// faults (null: the two public calls, k_ms_mixed<false>): two words per stream of the batch, cleared by the caller — k_ms_mixed<true> sets [2 s] where stream
+// s has a predictor index beyond its table and [2 s + 1] where it has a delta of 2^21 or more
+int ms_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const void *d_units, uint64_t n_units, const void *d_coefs, short *rows, unsigned *flags, size_t lds, uint64_t bytes,
+                    unsigned *faults = nullptr);
 // LDS a unit of k_ms_mixed may stage (source span and output spans): five workgroups of one wave each on a CU's 160 KiB.  A block that does not fit
 // alone (5 * blockAlign + 28 bytes or so: blockAlign above about 6550) takes the kernel's plain path
 constexpr size_t MS_MIX_LDS = 32 * 1024;

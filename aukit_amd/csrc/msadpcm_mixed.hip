@@ -30,6 +30,7 @@ struct MsMixParams {
     const int *coefs;                               // per coefficient set: c1[32], c2[32] (zeros behind the set's count)
     short *rows;
     unsigned *flags;                                // [0]: lowest stream with a predictor index beyond its table, [1]: ... with a delta of 2^21 or more
+    unsigned *faults;                               // k_ms_mixed<true> only: per stream of the batch, [2 s] != 0: such an index, [2 s + 1] != 0: such a delta
 };
 
 struct MsMixChan { int s1, s2, d, c1, c2; };
@@ -82,7 +83,7 @@ static AUKIT_DEV void msx_block(const unsigned char *data, unsigned nd, MsMixCha
     for (; i < nd; i++) byte(data[i], i);
 }
 
-template <int C>
+template <int C, bool PER_STREAM>
 static AUKIT_DEV void msx_unit(const MsMixParams &P, const MsMixUnit &U, unsigned char *sm, const int *adl, int lane) {
     const unsigned ba = U.block_align, HB = 7u * C, nd = ba - HB, spb = C == 2 ? nd + 2u : nd * 2u + 2u;
     const unsigned char *g0 = P.src + U.src_off;
@@ -123,7 +124,10 @@ static AUKIT_DEV void msx_unit(const MsMixParams &P, const MsMixUnit &U, unsigne
             K[0].d = msx_rd16(h + 1); K[0].s1 = msx_rd16(h + 3); K[0].s2 = msx_rd16(h + 5);
             K[0].c1 = c1t[pi & 31]; K[0].c2 = c2t[pi & 31];
         }
-        if (bad && nd) atomicMin(P.flags, U.stream);   // (c1 is nil: the first data byte's arithmetic raises; a block without one never gets there)
+        if (bad && nd) {   // (c1 is nil: the first data byte's arithmetic raises; a block without one never gets there)
+            atomicMin(P.flags, U.stream);
+            if constexpr (PER_STREAM) P.faults[2 * (size_t)U.stream] = 1u;   // (every lane that gets here stores the same word: a plain vector store)
+        }
         unsigned ovf = 0;
         if (U.plain) {
             short *o0 = row + (size_t)lane * spb, *o1 = o0 + U.stride;
@@ -136,7 +140,10 @@ static AUKIT_DEV void msx_unit(const MsMixParams &P, const MsMixUnit &U, unsigne
             if constexpr (C == 2) { o1[0] = (short)K[1].s2; o1[1] = (short)K[1].s1; }
             msx_block<C, false>(sm + sph + (size_t)lane * ba + HB, nd, K, adl, o0 + 2, o1 + 2, ovf);
         }
-        if (ovf >> 21) atomicMin(P.flags + 1, U.stream);
+        if (ovf >> 21) {
+            atomicMin(P.flags + 1, U.stream);
+            if constexpr (PER_STREAM) P.faults[2 * (size_t)U.stream + 1] = 1u;
+        }
     }
     if (U.plain) return;
     __syncthreads();
@@ -155,14 +162,17 @@ static AUKIT_DEV void msx_unit(const MsMixParams &P, const MsMixUnit &U, unsigne
     }
 }
 
+// PER_STREAM: beside the two batch-wide words, which of the two faults every stream has (P.faults, cleared by the host in front of the launch) — what a
+// stream set, whose bad member ends alone, reads back; the two public calls launch <false>, the kernel they always launched
+template <bool PER_STREAM>
 __global__ __launch_bounds__(64) void k_ms_mixed(const MsMixParams P) {
     extern __shared__ uint4 msx_sm[];
     __shared__ int adl[16];
     const int lane = threadIdx.x;
     if (lane < 16) { const int a[16] = {230, 230, 230, 230, 307, 409, 512, 614, 768, 614, 512, 409, 307, 230, 230, 230}; adl[lane] = a[lane]; }   // [0..7], [-8..-1]  :173-176
     const MsMixUnit U = P.units[blockIdx.x];
-    if (U.channels == 2) msx_unit<2>(P, U, reinterpret_cast<unsigned char *>(msx_sm), adl, lane);
-    else msx_unit<1>(P, U, reinterpret_cast<unsigned char *>(msx_sm), adl, lane);
+    if (U.channels == 2) msx_unit<2, PER_STREAM>(P, U, reinterpret_cast<unsigned char *>(msx_sm), adl, lane);
+    else msx_unit<1, PER_STREAM>(P, U, reinterpret_cast<unsigned char *>(msx_sm), adl, lane);
 }
 
 // LDS bytes of a staged unit of nblk blocks (what msx_unit carves: the source span in its address phase, the output spans in their row phase)
@@ -171,16 +181,18 @@ size_t ms_mixed_unit_lds(uint64_t nblk, uint64_t block_align, int channels) {
     return (size_t)(round_up(15 + nblk * block_align, 16) + (uint64_t)channels * round_up(7 + nblk * spb, 8) * 2);
 }
 
-int ms_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const void *d_units, uint64_t n_units, const void *d_coefs, short *rows, unsigned *flags, size_t lds, uint64_t bytes) {
+int ms_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const void *d_units, uint64_t n_units, const void *d_coefs, short *rows, unsigned *flags, size_t lds, uint64_t bytes,
+                    unsigned *faults) {
     if (!n_units) return AUKIT_OK;
     MsMixParams P;
     P.src = in->data(); P.safe_lo = in->base; P.safe_hi = in->base + in->cap;
     P.units = reinterpret_cast<const MsMixUnit *>(d_units);
     P.coefs = reinterpret_cast<const int *>(d_coefs);
-    P.rows = rows; P.flags = flags;
+    P.rows = rows; P.flags = flags; P.faults = faults;
     int rc = ctx_begin_kernel(ctx);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ms_mixed, dim3((unsigned)n_units), dim3(64), lds, ctx->stream, P);
+    if (faults) hipLaunchKernelGGL(k_ms_mixed<true>, dim3((unsigned)n_units), dim3(64), lds, ctx->stream, P);
+    else hipLaunchKernelGGL(k_ms_mixed<false>, dim3((unsigned)n_units), dim3(64), lds, ctx->stream, P);
     AUKIT_HIP_CHECK(hipGetLastError());
     return ctx_end_kernel(ctx, "k_ms_mixed", bytes);
 }

@@ -53,6 +53,11 @@
 // shift (smix_stage_ms).  The staged doubles are floor(p / (p < 0 and 128 or 127)) for two channels (:2648-2662: floored BEFORE interpolation) and the
 // plain quotient for one (:2708-2720); the epilogue is clamp(floor(c)) per channel, or with `mono` on two channels clamp(floor(l + r / 2)) (:2672: the
 // reference's precedence, not the mean).
+// An MS-ADPCM stream may be the REST of a longer one too (a stream set's member under AUKIT_OPT_STREAMSET_BLOCK_CODECS: the set hands in the mask it was
+// opened with, the context's AUKIT_OPT_STREAM_MIXED_CODECS is the public call's alone).  Its carry holds no state — every block decodes alone; a
+// one-channel stream's first seven bytes are put back at the front of its slot by the set — only what was dropped: plan_ms counts positions and length
+// from the whole stream.  With a carry the pre-pass runs k_ms_mixed<true>, reads the per-stream fault words back with the two flag words (one copy,
+// one wait) and, instead of refusing the batch, takes every offending stream out of the plan: no chunk, the fault as its status (smix_drop_faulted).
 //
 // The host half reads as the call's phases: smix_validate, smix_classes, the IMA header scan, one planner per codec (plan_pcm, plan_g711, plan_dfpwm,
 // plan_ima, plan_ms: they fill an SMixPlan and touch neither the context nor HIP), the scratch layout, the MS-ADPCM pre-pass and its verdict, the two
@@ -590,11 +595,12 @@ int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) {
 static inline uint64_t smix_nbytes(const aukit_batch *in, const SMixCarry *carry, uint32_t s) { return carry ? carry[s].nbytes : in->off[s + 1] - in->off[s]; }
 
 static int smix_validate(const aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
-                         const SMixCarry *carry) {
+                         const SMixCarry *carry, unsigned block_codecs) {
     int rc;
     if ((rc = mixed_check_call(ctx, in, out, descs, n_descs, interp, dtype, "invalid interpolation", "stream each class with aukit_stream_decode"))) return rc;
-    // AUKIT_OPT_STREAM_MIXED_CODECS: MS-ADPCM joins the list on a context that asked this call for it; without the bit the call answers in the words of before
-    if ((ctx->stream_mixed_codecs >> AUKIT_CODEC_MSADPCM) & 1u)
+    // AUKIT_OPT_STREAM_MIXED_CODECS: MS-ADPCM joins the list on a context that asked this call for it; without the bit the call answers in the words of before.
+    // (The mask is the caller's: the public call hands in the context's, a stream set the one it was opened with)
+    if ((block_codecs >> AUKIT_CODEC_MSADPCM) & 1u)
         rc = mixed_check_codecs(descs, in->n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_MSADPCM},
                                 "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, "
                                 "AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_STREAM_MIXED_CODECS, AUKIT_CODEC_MSADPCM)");
@@ -883,12 +889,14 @@ static void plan_ima(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc
 }
 
 // stream_msadpcm's plan (msadpcm.hip) from byte 0: every block is whole (check_smix_stream), call k takes blocks k ips .. min((k + 1) ips, nblk) - 1.
-// A stream whose blocks yield no output has no chunk and no row: nothing of it is decoded, as in the stream's own call
-static void plan_ms(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc &d, uint64_t nb) {
+// A stream whose blocks yield no output has no chunk and no row: nothing of it is decoded, as in the stream's own call.
+// `cy`: a stream set's member is the rest of a stream whose first bytes_dropped bytes — whole calls, so whole blocks — are gone: positions and length
+// are the whole stream's, in stream_msadpcm's expression order with ctx->sb_bytes (msadpcm.hip), so that the doubles are equal
+static void plan_ms(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc &d, uint64_t nb, const SMixCarry &cy) {
     const int C = d.channels;
     const MsGeom G(C, d.block_align, d.sample_rate);
     const uint64_t nblk = nb / G.ba, src_off = g.src_off, newlen = (uint64_t)G.newlen_d;
-    pl.ck->length_seconds[s] = (double)nb / (double)G.ba * G.spb / d.sample_rate;  // :2680, :2734
+    pl.ck->length_seconds[s] = (double)(nb + cy.bytes_dropped) / (double)G.ba * G.spb / d.sample_rate;  // :2680, :2734
     if (!nblk || !newlen) return;
     const uint64_t stride = round_up(nblk * G.row_len, 8);
     g.src_off = pl.ms_elems;
@@ -896,7 +904,7 @@ static void plan_ms(SMixPlan &pl, uint32_t s, SMixSeg g, const aukit_codec_desc 
     for (uint64_t first = 0; first < nblk; first += G.ips) {
         const uint64_t done = std::min<uint64_t>(first + G.ips, nblk);
         g.src_base = (long long)first; g.nblk = (unsigned)(done - first); g.n_out = (uint32_t)((done - first) * newlen);
-        pl.add_call(s, g, (double)(done * G.ba + 1) / G.bytes_per_second);  // (n + pos) / bytesPerSecond  :2679, :2733
+        pl.add_call(s, g, ((double)(done * G.ba + cy.bytes_dropped + 1)) / G.bytes_per_second);  // (n + pos) / bytesPerSecond  :2679, :2733
     }
     pl.ms.add_stream(d, s, src_off, nblk, pl.ms_elems, stride);
     pl.ms.src += nb;
@@ -917,7 +925,7 @@ static void smix_plan(const aukit_batch *in, const aukit_codec_desc *descs, cons
         g.cls = cls_of[s];
         if (d.codec == AUKIT_CODEC_DFPWM) plan_dfpwm(pl, s, g, d, nb, cy);
         else if (d.codec == AUKIT_CODEC_ADPCM_WAV) plan_ima(pl, s, g, d, nb, ima_bad[ima_i++], cy);
-        else if (d.codec == AUKIT_CODEC_MSADPCM) plan_ms(pl, s, g, d, nb);  // (a stream set has no such member: no carry)
+        else if (d.codec == AUKIT_CODEC_MSADPCM) plan_ms(pl, s, g, d, nb, cy);
         else if (d.codec == AUKIT_CODEC_PCM) plan_pcm(pl, s, g, d, nb, interp, mono, cy);
         else plan_g711(pl, s, g, d, nb, cy);
     }
@@ -926,6 +934,7 @@ static void smix_plan(const aukit_batch *in, const aukit_codec_desc *descs, cons
 // the chunk table of the plan: lengths and positions of every stream's calls, max_chunks apart
 static void smix_chunk_table(SMixPlan &pl, int C_out) {
     aukit_chunks &ck = *pl.ck;
+    ck.max_chunks = 0;   // (made a second time where the MS-ADPCM pre-pass took streams out of the plan)
     for (uint32_t s = 0; s < ck.n; s++) ck.max_chunks = std::max<uint32_t>(ck.max_chunks, ck.nchunks[s]);
     const size_t mc = chunks_shape(ck);
     size_t i = 0;
@@ -942,9 +951,10 @@ static void smix_chunk_table(SMixPlan &pl, int C_out) {
 // (six ints per entry); behind the DFPWM scratch the IMA pre-pass's int16 rows (planned blocks x
 // channels x (samplesPerBlock + 8) entries: every row at a multiple of 16 bytes) and its stream table;
 // behind the IMA scratch k_ms_mixed's int16 rows (a row per (stream, channel) at a multiple of 16 bytes, 64 bytes to spare behind the last: the
-// tiles' 16-byte loads rely on them), its unit table, its coefficient sets and its two flag words
+// tiles' 16-byte loads rely on them), its unit table, its coefficient sets and its two flag words — for a stream set with, right behind them, the two
+// fault words of every stream of the batch (one read-back takes both)
 struct SMixScratch { size_t df_tab_at = 0, df_states_at = 0, ima_at = 0, ima_tab_at = 0, ms_at = 0, ms_unit_at = 0, ms_coef_at = 0, ms_flag_at = 0, size = 0; };
-static SMixScratch smix_scratch(const SMixPlan &pl) {
+static SMixScratch smix_scratch(const SMixPlan &pl, bool ms_per_stream) {
     Carve carve;
     SMixScratch L;
     if (pl.df_n) { carve.take((size_t)pl.df_tot); L.df_tab_at = carve.take((size_t)pl.df_n * (8 + sizeof(SMixDfItem) + 4)); }  // (the rows are at 0)
@@ -954,7 +964,7 @@ static SMixScratch smix_scratch(const SMixPlan &pl) {
         L.ms_at = carve.take((size_t)pl.ms_elems * 2);
         L.ms_unit_at = carve.take(pl.ms.units.size() * sizeof(MsMixUnit), 0);
         L.ms_coef_at = carve.take(pl.ms.coefs.size() * sizeof(int), 0);
-        L.ms_flag_at = carve.take(8, 56);
+        L.ms_flag_at = carve.take(8 + (ms_per_stream ? (size_t)pl.ck->n * 8 : 0), 56);
     }
     L.size = carve.end;
     return L;
@@ -1007,11 +1017,30 @@ static int smix_ima_prepass(aukit_ctx *ctx, const aukit_batch *in, const SMixPla
 
 // The MS-ADPCM pre-pass can still refuse — a predictor index beyond the stream's coefficient table, a delta that leaves k_ms_mixed's int32 range —
 // and writes nothing but the scratch: it runs, and its two flag words are read back, BEFORE `*out` is touched
-static int smix_ms_prepass(aukit_ctx *ctx, const aukit_batch *in, const SMixPlan &pl, const SMixScratch &L) {
+// `faults` (a stream set's batch, where one bad member ends alone): the launch is k_ms_mixed<true>, the per-stream fault words come back with the two flag
+// words — the one copy and the one wait the pre-pass always had — and instead of a refusal the answer is, per stream, 0, AUKIT_E_LUA (the predictor
+// index; of both faults this one, where the reference raises first) or AUKIT_E_UNSUPPORTED (the delta).  No second decode, no loop over offenders
+static int smix_ms_prepass(aukit_ctx *ctx, const aukit_batch *in, const SMixPlan &pl, const SMixScratch &L, std::vector<int> *faults) {
     char *const T = reinterpret_cast<char *>(ctx->tmp_buf.p);
     unsigned *flags = reinterpret_cast<unsigned *>(T + L.ms_flag_at);
     int rc;
     AUKIT_HIP_CHECK(hipMemsetAsync(flags, 0xFF, 8, ctx->stream));
+    if (faults) {
+        const size_t n = pl.ck->n;
+        AUKIT_HIP_CHECK(hipMemsetAsync(flags + 2, 0, n * 8, ctx->stream));
+        if ((rc = h2d_table(ctx, T + L.ms_unit_at, pl.ms.units.data(), pl.ms.units.size() * sizeof(MsMixUnit))) ||
+            (rc = h2d_table(ctx, T + L.ms_coef_at, pl.ms.coefs.data(), pl.ms.coefs.size() * sizeof(int))))
+            return rc;
+        if ((rc = ms_mixed_decode(ctx, in, T + L.ms_unit_at, pl.ms.units.size(), T + L.ms_coef_at, reinterpret_cast<short *>(T + L.ms_at), flags, pl.ms.lds,
+                                  pl.ms.src + pl.ms_elems * 2, flags + 2)))
+            return rc;
+        std::vector<unsigned> h(2 + 2 * n, 0u);
+        AUKIT_HIP_CHECK(hipMemcpyAsync(h.data(), flags, h.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        faults->assign(n, 0);
+        for (size_t s = 0; s < n; s++) (*faults)[s] = h[2 + 2 * s] ? AUKIT_E_LUA : (h[3 + 2 * s] ? AUKIT_E_UNSUPPORTED : 0);
+        return AUKIT_OK;
+    }
     if ((rc = h2d_table(ctx, T + L.ms_unit_at, pl.ms.units.data(), pl.ms.units.size() * sizeof(MsMixUnit))) ||
         (rc = h2d_table(ctx, T + L.ms_coef_at, pl.ms.coefs.data(), pl.ms.coefs.size() * sizeof(int))))
         return rc;
@@ -1021,6 +1050,28 @@ static int smix_ms_prepass(aukit_ctx *ctx, const aukit_batch *in, const SMixPlan
     AUKIT_HIP_CHECK(hipMemcpyAsync(h, flags, 8, hipMemcpyDeviceToHost, ctx->stream));
     AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return mixed_ms_verdict(h[0], h[1], "aukit_stream_decode");
+}
+
+// a stream set's batch: the streams the pre-pass found at fault (smix_ms_prepass) leave the plan — no chunk, no output, the fault as the stream's status;
+// their segments go, so that phase 7 cuts no tile that would read their rows.  The other streams' segments keep their order
+static void smix_drop_faulted(SMixPlan &pl, const std::vector<int> &faults) {
+    std::vector<SMixSeg> segs;
+    std::vector<double> cpos;
+    size_t i = 0;
+    for (uint32_t s = 0; s < pl.ck->n; s++) {
+        const uint32_t k = pl.ck->nchunks[s];
+        if (faults[s]) {
+            pl.ck->nchunks[s] = 0;
+            pl.ck->status[s] = faults[s];
+            pl.lens[s] = 0;
+        } else {
+            segs.insert(segs.end(), pl.segs.begin() + i, pl.segs.begin() + i + k);
+            cpos.insert(cpos.end(), pl.cpos.begin() + i, pl.cpos.begin() + i + k);
+        }
+        i += k;
+    }
+    pl.segs.swap(segs);
+    pl.cpos.swap(cpos);
 }
 
 // ---- phase 7: tiles.  A segment is cut into tiles of the class's height.  An IMA segment: no tile straddles a block, and a block's outputs are cut
@@ -1093,10 +1144,10 @@ static int smix_launch(aukit_ctx *ctx, const aukit_batch *in, const SMixClasses 
 // and ask for the states at this decode's call boundaries, which `back` then names (the set's next carry comes from there).  A batch in which no
 // carry does either launches what it always launched
 int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
-                              aukit_chunks **chunks, const SMixCarry *carry, SMixDfBack *back) {
+                              aukit_chunks **chunks, const SMixCarry *carry, SMixDfBack *back, unsigned block_codecs) {
     // what can be refused is refused before the device is touched; `*out` and `*chunks` keep what they held
     int rc;
-    if ((rc = smix_validate(ctx, in, descs, n_descs, interp, mono, dtype, out, carry))) return rc;
+    if ((rc = smix_validate(ctx, in, descs, n_descs, interp, mono, dtype, out, carry, block_codecs))) return rc;
     const uint32_t n = in->n;
     SMixClasses T;
     if ((rc = smix_classes(descs, n, interp, mono, T))) return rc;
@@ -1109,15 +1160,21 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
     SMixPlan pl(n);
     smix_plan(in, descs, carry, T.cls_of, interp, mono != 0, ima_bad, pl);
     smix_chunk_table(pl, C_out);
-    const uint64_t nt = smix_count_tiles(T, pl);
+    uint64_t nt = smix_count_tiles(T, pl);
     if (nt > 0xFFFFFFF0ull || pl.ima_jobs > 0x7FFFFFF0ull * 64 || pl.ms.units.size() > 0x7FFFFFF0ull || pl.df_states > 0x7FFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
     if (pl.df_states && !back) return fail(AUKIT_E_ARG, "null argument");
 
     // the scratch is sized before `*out` is touched, and its pointer is read after
-    const SMixScratch L = smix_scratch(pl);
+    const SMixScratch L = smix_scratch(pl, carry != nullptr);
     const bool ms = !pl.ms.units.empty();
     if ((pl.df_n || pl.ima_jobs || ms) && (rc = mixed_scratch_ensure(ctx, *out, L.size))) return rc;
-    if (ms && (rc = smix_ms_prepass(ctx, in, pl, L))) return rc;
+    std::vector<int> ms_faults;
+    if (ms && (rc = smix_ms_prepass(ctx, in, pl, L, carry ? &ms_faults : nullptr))) return rc;
+    if (std::any_of(ms_faults.begin(), ms_faults.end(), [](int f) { return f != 0; })) {   // (a stream set's batch only: the public call was refused above)
+        smix_drop_faulted(pl, ms_faults);
+        smix_chunk_table(pl, C_out);
+        nt = smix_count_tiles(T, pl);
+    }
     aukit_audio *a = *out;
     if ((rc = audio_prepare(ctx, &a, n, C_out, 48000, dtype, pl.lens.data()))) return rc;
     *out = a;
@@ -1142,5 +1199,5 @@ using namespace aukit;
 
 extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype,
                                          aukit_audio **out, aukit_chunks **chunks) {
-    return stream_decode_mixed_carry(ctx, in, descs, n_descs, interp, mono, dtype, out, chunks, nullptr);
+    return stream_decode_mixed_carry(ctx, in, descs, n_descs, interp, mono, dtype, out, chunks, nullptr, nullptr, ctx ? ctx->stream_mixed_codecs : 0u);
 }

@@ -12,7 +12,7 @@
 //           (3) aukit_stream_decode_mixed's engine (stream_decode_mixed_carry, stream_mixed.hip) over the members that have news, straight from the
 //               arena, each with what it has dropped so far (SMixCarry): positions and lengths are the whole stream's;
 //           (4) one launch of k_sset_gather: the newly decided chunks of all members, as doubles, [item][channel][len]; one download into the
-//               pinned host cache; one wait — the pump's only one (a set with stream.adpcm members adds the mixed call's header-scan read-back);
+//               pinned host cache; one wait — the pump's only one (a set with stream.adpcm members adds the mixed call's header-scan read-back, one with stream.msadpcm members the pre-pass's flag read-back);
 //           (5) host: the compaction plan for the next repack (restart_rule's PCM / G.711 / IMA cases, stream_handle.hip: stream.pcm keeps the call
 //               in front of the next one and skips its chunk, stream.g711 / stream.adpcm calls stand alone).  No 64 KiB threshold: the repack runs
 //               anyway, so a member is compacted whenever a call of its became droppable;
@@ -27,9 +27,22 @@
 // copied to pinned host memory on the pump's stream in front of the pump's one wait — no launch and no read-back of its own — and the compaction plan,
 // which drops `shift` whole calls of 6000 C bytes (restart_rule's DFPWM case: lead 0), takes the state at boundary `shift` behind the wait.  An
 // unfinished member is decoded up to a multiple of `channels` bytes, a finished one whole, as the handle does.
+//
+// stream.msadpcm members (AUKIT_CODEC_MSADPCM; only a set opened on a context that set AUKIT_OPT_STREAMSET_BLOCK_CODECS has them — the set keeps that
+// mask and hands it to the engine, so AUKIT_OPT_STREAM_MIXED_CODECS is not needed): every block decodes alone, an iterator call is
+// ceil(rate / samplesPerBlock) blocks and the rest starts at the next call (restart_rule's MS-ADPCM case: lead 0); an unfinished member is decoded up to
+// a whole block.  Two things are the codec's own.  (1) A one-channel stream reads its FIRST seven bytes for every block (Q9, :2706; no block reads its
+// own header), and a repack drops them with the first call: the member keeps them on the host (captured by aukit_streamset_feed, in however many pieces
+// they arrive) and every repack in which it drops bytes writes them over the first seven bytes of its new slot — appended to the staging buffer in
+// front of the pump's one upload, a seven-byte segment of the one repack launch, the rest's own segment starting seven bytes in (no two segments
+// write the same byte) — as the handle's compact() does with head7.  (2) A predictor index beyond the coefficient table, or a delta of 2^21 or more,
+// is known only on the device: the engine's pre-pass (k_ms_mixed<true>) records per stream which fault it has, the set's batch gets that stream back
+// with no chunk and the fault as its status, and the member ends alone at that pump, behind the chunks of earlier pumps, with the single call's words.
+// The pre-pass's flag read-back is a second wait in a pump that decodes such members (as the header scan is for stream.adpcm members).
 #include <algorithm>
 #include <deque>
 #include "mixed_plan.h"
+#include "ms_geom.h"
 
 namespace aukit {
 
@@ -119,6 +132,9 @@ struct SSetMember {
     // stream.dfpwm: the decoder's state in front of the rest (n, strength, pb, lpf, pn: dfpwm_par_dev.h), valid once calls were dropped — the handle's df_state
     bool df_on = false;
     int df_state[6] = {0, 0, 0, 0, 0, 0};
+    // stream.msadpcm, one channel: the stream's first seven bytes as fed (the header every block is read from) — the handle's head7
+    unsigned char head7[7] = {0, 0, 0, 0, 0, 0, 0};
+    uint32_t head7_n = 0;
     std::deque<SSetChunk> q;
 };
 // a compaction planned in front of the pump's wait: member s's next state is entry `entry` of the states the pump downloads
@@ -129,6 +145,7 @@ struct SSetDfFix { uint32_t s; size_t entry; };
 struct aukit_streamset {
     aukit_ctx *ctx = nullptr;
     int interp = 0, mono = 0, dtype = AUKIT_F64;
+    unsigned block_codecs = 0;   // AUKIT_OPT_STREAMSET_BLOCK_CODECS as it was when the set was opened
     std::vector<aukit::SSetMember> m;
     // pinned host staging of what was fed since the last pump, and its device copy
     unsigned char *stage = nullptr;
@@ -176,7 +193,7 @@ static void sset_apply_states(aukit_streamset *S) {
     S->df_fix.clear();
 }
 
-// restart_rule's PCM / G.711 / IMA / DFPWM cases (stream_handle.hip): the bytes of a whole iterator call, and whether the rest starts one call early
+// restart_rule's PCM / G.711 / IMA / DFPWM / MS-ADPCM cases (stream_handle.hip): the bytes of a whole iterator call, and whether the rest starts one call early
 static void sset_restart(SSetMember &M, int interp) {
     const aukit_codec_desc &d = M.desc;
     const uint64_t C = (uint64_t)std::max(d.channels, 1);
@@ -187,6 +204,9 @@ static void sset_restart(SSetMember &M, int interp) {
         M.call_bytes = (uint64_t)d.sample_rate * C;
     } else if (d.codec == AUKIT_CODEC_DFPWM) {
         M.call_bytes = 6000 * C;   // lead 0: the rest starts at the next call, with the decoder's state and its last output carried (df_state)
+    } else if (d.codec == AUKIT_CODEC_MSADPCM) {
+        const double spb = C == 2 ? (double)(d.block_align - 14) : (double)(d.block_align - 7) * 2;   // :2617 / :2682 (MsGeom's)
+        M.call_bytes = (uint64_t)std::ceil(d.sample_rate / spb) * (uint64_t)d.block_align;            // lead 0: every block decodes alone
     } else {
         const double spb = (double)((uint64_t)d.block_align - 4 * C) * 2 / (double)C;   // :2765
         M.call_bytes = (uint64_t)std::ceil(d.sample_rate / spb) * (uint64_t)d.block_align;   // :2766-2767
@@ -198,6 +218,7 @@ static uint64_t sset_whole_frames(const SSetMember &M, uint64_t nb) {
     const uint64_t C = (uint64_t)std::max(M.desc.channels, 1);
     if (M.desc.codec == AUKIT_CODEC_PCM) return nb - nb % (C * (uint64_t)std::max(M.desc.bit_depth / 8, 1));
     if (M.desc.codec == AUKIT_CODEC_G711 || M.desc.codec == AUKIT_CODEC_DFPWM) return nb - nb % C;
+    if (M.desc.codec == AUKIT_CODEC_MSADPCM && M.desc.block_align > 0) return nb - nb % (uint64_t)M.desc.block_align;   // a partial block raises (:2640)
     return nb;
 }
 
@@ -205,6 +226,8 @@ static uint64_t sset_whole_frames(const SSetMember &M, uint64_t nb) {
 // included.  -> 0: served
 static int sset_finished_refusal(const SSetMember &M, uint64_t nb, bool mono) {
     const aukit_codec_desc &d = M.desc;
+    // stream.msadpcm finished inside a block: ms_partial_block's words for the WHOLE stream's byte count (its `nb < 7`), no index appended, as the handle
+    if (d.codec == AUKIT_CODEC_MSADPCM && d.block_align > 0 && nb % (uint64_t)d.block_align != 0) return ms_partial_block(d.channels, M.sb_bytes + nb, (uint64_t)d.block_align);
     if (d.codec == AUKIT_CODEC_PCM) {
         const uint64_t bd = (uint64_t)std::max(d.bit_depth / 8, 1), C = (uint64_t)std::max(d.channels, 1);
         if (nb % (bd * C) != 0) {
@@ -237,7 +260,19 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
         SSetMember &M = S->m[s];
         slot[s] = cursor;
         if (M.resident) {
-            for (uint64_t at = 0; at < M.resident; at += 0x40000000ull)   // (a segment's length is 32 bits)
+            // a one-channel stream.msadpcm member that drops bytes: the first bytes of its new slot are the STREAM's first seven, from the host by way
+            // of the staging buffer; the rest's own segment starts behind them (the same relation modulo 16, and no byte is written twice)
+            uint64_t head = 0;
+            if (M.drop && M.desc.codec == AUKIT_CODEC_MSADPCM && M.desc.channels == 1 && M.head7_n == 7) {
+                head = std::min<uint64_t>(M.resident, 7);
+                void *p = S->stage;
+                if ((rc = pinned_grow(&p, &S->stage_cap, S->stage_used, S->stage_used + 7, 1))) return rc;
+                S->stage = reinterpret_cast<unsigned char *>(p);
+                memcpy(S->stage + S->stage_used, M.head7, 7);
+                segs.push_back(SSetSeg{(unsigned long long)S->stage_used, cursor, (unsigned)head, 1u});
+                S->stage_used += 7;
+            }
+            for (uint64_t at = head; at < M.resident; at += 0x40000000ull)   // (a segment's length is 32 bits)
                 segs.push_back(SSetSeg{M.slot + M.drop + at, cursor + at, (unsigned)std::min<uint64_t>(M.resident - at, 0x40000000ull), 0u});
         }
         filled[s] = M.resident;
@@ -339,7 +374,7 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
         }
         B.off[nj] = S->arena_used;
         SMixDfBack back;
-        if ((rc = stream_decode_mixed_carry(ctx, &B, descs.data(), nj, S->interp, S->mono, S->dtype, &S->out, &S->ck, carry.data(), &back))) return rc;
+        if ((rc = stream_decode_mixed_carry(ctx, &B, descs.data(), nj, S->interp, S->mono, S->dtype, &S->out, &S->ck, carry.data(), &back, S->block_codecs))) return rc;
         if (back.entries) {   // the states travel with the pump's one download: queued here, on the set's stream, awaited with the chunks below
             void *hp = S->df_host;
             if ((rc = pinned_grow(&hp, &S->df_host_cap, 0, back.entries * 6, sizeof(int)))) return rc;
@@ -372,6 +407,13 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
                 before += len;
             }
             M.skip = std::max(M.skip, decided);
+            if (M.desc.codec == AUKIT_CODEC_MSADPCM && ck.status[i]) {   // the pre-pass's verdict on this member (no chunk came back): it ends here, alone
+                M.over = true;
+                M.end_status = ck.status[i];
+                M.end_msg = ck.status[i] == AUKIT_E_LUA ? "attempt to perform arithmetic on a nil value (local 'c1')" : "MS-ADPCM delta of 2^21 or more: aukit_stream_open takes this stream";
+                M.sb_bytes += M.resident; M.resident = 0;
+                continue;
+            }
             if (J.ends) {   // what follows the queued chunks is settled: the member leaves the arena
                 M.over = true;
                 M.end_status = J.end_status ? J.end_status : ck.status[i];
@@ -445,7 +487,17 @@ int aukit_streamset_open(aukit_ctx *ctx, const aukit_codec_desc *descs, uint32_t
     int rc;
     // AUKIT_OPT_STREAMSET_CODECS: stream.dfpwm members join on a context that asked for them, read here and nowhere else; without the bit the call
     // answers in the words of before
-    if ((ctx->streamset_codecs >> AUKIT_CODEC_DFPWM) & 1u)
+    // AUKIT_OPT_STREAMSET_BLOCK_CODECS: stream.msadpcm members likewise, under an option of their own; a refusal of a further codec names what is served
+    const bool with_df = (ctx->streamset_codecs >> AUKIT_CODEC_DFPWM) & 1u, with_ms = (ctx->streamset_block_codecs >> AUKIT_CODEC_MSADPCM) & 1u;
+    if (with_df && with_ms)
+        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_DFPWM, AUKIT_CODEC_MSADPCM},
+                                "stream %u: codec %d keeps aukit_stream_open (a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV and, under "
+                                "AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM and, under AUKIT_OPT_STREAMSET_BLOCK_CODECS, AUKIT_CODEC_MSADPCM)");
+    else if (with_ms)
+        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_MSADPCM},
+                                "stream %u: codec %d keeps aukit_stream_open (a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV and, under "
+                                "AUKIT_OPT_STREAMSET_BLOCK_CODECS, AUKIT_CODEC_MSADPCM)");
+    else if (with_df)
         rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_DFPWM},
                                 "stream %u: codec %d keeps aukit_stream_open (a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV and, under "
                                 "AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM)");
@@ -458,6 +510,7 @@ int aukit_streamset_open(aukit_ctx *ctx, const aukit_codec_desc *descs, uint32_t
         if ((rc = check_smix_stream(&descs[s], 0, mono != 0))) return fail_for_stream(rc, s);
     aukit_streamset *S = new aukit_streamset();
     S->ctx = ctx; S->interp = interp; S->mono = mono ? 1 : 0; S->dtype = dtype;
+    S->block_codecs = with_ms ? 1u << AUKIT_CODEC_MSADPCM : 0u;
     S->m.resize(n);
     for (uint32_t s = 0; s < n; s++) {
         S->m[s].desc = descs[s];
@@ -486,6 +539,8 @@ int aukit_streamset_feed(aukit_streamset *S, uint32_t s, const uint8_t *bytes, u
         S->stage = reinterpret_cast<unsigned char *>(p);
     }
     memcpy(S->stage + at, bytes, (size_t)nbytes);
+    if (M.head7_n < 7 && M.desc.codec == AUKIT_CODEC_MSADPCM && M.desc.channels == 1)   // (nothing is dropped before the first call is whole: these are the stream's first bytes)
+        for (uint64_t i = 0; i < nbytes && M.head7_n < 7; i++) M.head7[M.head7_n++] = bytes[i];
     S->stage_used = at + (size_t)nbytes;
     S->feeds.push_back(SSetFeed{s, (uint64_t)at, nbytes});
     M.pending += nbytes;

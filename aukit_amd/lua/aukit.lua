@@ -957,21 +957,25 @@ end
 -- and 48000 Hz by default — for a raw .dfpwm stream, which has no header: its pair is aukit.stream.dfpwm(fn, sampleRate, channels, mono)'s, the length nil
 -- (:2495).  For the one open the context is opted in (AUKIT_OPT_STREAMSET_CODECS, option 7, bit 1 << AUKIT_CODEC_DFPWM) and put back behind it, also where
 -- the open is refused.  Without the request every message is the one of before.
+-- MS-ADPCM WAV readers (format 2: aukit.stream.wav's dispatch to aukit.stream.msadpcm with the stream's blockAlign and coefficient list) are taken with the
+-- key `msadpcm` of the options table, {mono = ..., msadpcm = true}: for the one open the context is opted in under an option of its own
+-- (AUKIT_OPT_STREAMSET_BLOCK_CODECS, option 8, bit 1 << AUKIT_CODEC_MSADPCM) and put back behind it, also where the open is refused.
 function aukit.stream.set(readers, mono)
     expect(1, readers, "table") expect(2, mono, "boolean", "table", "nil")
-    local dfpwm = false
+    local dfpwm, msadpcm = false, false
     if type(mono) == "table" then
-        for k in pairs(mono) do if k ~= "mono" and k ~= "dfpwm" then error("bad argument #2 (unknown option " .. tostring(k) .. ")", 2) end end
-        if (mono.mono ~= nil and type(mono.mono) ~= "boolean") or (mono.dfpwm ~= nil and type(mono.dfpwm) ~= "boolean") then
+        for k in pairs(mono) do if k ~= "mono" and k ~= "dfpwm" and k ~= "msadpcm" then error("bad argument #2 (unknown option " .. tostring(k) .. ")", 2) end end
+        if (mono.mono ~= nil and type(mono.mono) ~= "boolean") or (mono.dfpwm ~= nil and type(mono.dfpwm) ~= "boolean") or (mono.msadpcm ~= nil and type(mono.msadpcm) ~= "boolean") then
             error("bad argument #2 (expected boolean options)", 2)
         end
-        mono, dfpwm = mono.mono, mono.dfpwm or false
+        mono, dfpwm, msadpcm = mono.mono, mono.dfpwm or false, mono.msadpcm or false
     end
     local n = #readers
     local descs = ffi.new("aukit_codec_desc[?]", math.max(n, 1))
     local firsts, lengths, done, raw = {}, {}, {}, {}
     local takes = dfpwm and "stream.set takes PCM, G.711 and DFPWM payloads and IMA-ADPCM blocks (the other codecs keep their own streams)"
                   or "stream.set takes PCM and G.711 payloads and IMA-ADPCM blocks (the other codecs keep their own streams)"
+    if msadpcm then takes = takes:gsub("IMA%-ADPCM blocks", "IMA-ADPCM and MS-ADPCM blocks") end
     local fns = {}
     for i = 1, n do
         local e = readers[i]
@@ -996,7 +1000,7 @@ function aukit.stream.set(readers, mono)
             if not kind then error("reader " .. (i - 1) .. ": not a WAV, AIFF or AU stream", 2) end
             local c = ffi.new("aukit_container")
             if C.aukit_parse_container(ffi.cast("const uint8_t*", f), #f, kind, 2, c) ~= 0 then error("reader " .. (i - 1) .. ": " .. ffi.string(C.aukit_last_error()), 2) end
-            if c.desc.codec > 1 and c.desc.codec ~= 3 and (c.desc.codec ~= 5 or not dfpwm) then   -- 0: PCM, 1: G.711, 3: AUKIT_CODEC_ADPCM_WAV; 5: AUKIT_CODEC_DFPWM, on request
+            if c.desc.codec > 1 and c.desc.codec ~= 3 and (c.desc.codec ~= 5 or not dfpwm) and (c.desc.codec ~= 4 or not msadpcm) then   -- 0: PCM, 1: G.711, 3: AUKIT_CODEC_ADPCM_WAV; 5: AUKIT_CODEC_DFPWM, 4: AUKIT_CODEC_MSADPCM, on request
                 error("reader " .. (i - 1) .. ": " .. (kind == 0 and WAVDT[c.wav_data_type] or ("codec " .. c.desc.codec)) .. " payload: " .. takes, 2)
             end
             descs[i - 1] = c.desc
@@ -1008,9 +1012,12 @@ function aukit.stream.set(readers, mono)
     local sp = ffi.new("aukit_streamset*[1]")
     -- dfpwm: AUKIT_OPT_STREAMSET_CODECS (7) with bit 1 << AUKIT_CODEC_DFPWM for this one open; the shim's context sets no other bit, so 0 puts it back
     if dfpwm then check(C.aukit_ctx_set_option(ctx(), 7, 2 ^ CODEC.dfpwm)) end
+    -- msadpcm: AUKIT_OPT_STREAMSET_BLOCK_CODECS (8) with bit 1 << AUKIT_CODEC_MSADPCM, likewise
+    if msadpcm then check(C.aukit_ctx_set_option(ctx(), 8, 2 ^ CODEC.msadpcm)) end
     local rc = C.aukit_streamset_open(ctx(), descs, n, INTERP[aukit.defaultInterpolation], mono and 1 or 0, F64, sp)
     local words = rc ~= 0 and ffi.string(C.aukit_last_error()) or nil
     if dfpwm then C.aukit_ctx_set_option(ctx(), 7, 0) end
+    if msadpcm then C.aukit_ctx_set_option(ctx(), 8, 0) end
     if words then error(words, 2) end
     local set = ffi.gc(sp[0], C.aukit_streamset_close)
     local ready = ffi.new("uint32_t[1]")
@@ -1026,7 +1033,7 @@ function aukit.stream.set(readers, mono)
         check(C.aukit_streamset_pump(set, ready))
     end
     round(firsts)
-    local CAP = 48000   -- a chunk of stream.pcm / g711 / adpcm never exceeds a second of output; stream.dfpwm's may (48008 at 48 kHz mono): the buffer grows
+    local CAP = 48000   -- a chunk of stream.pcm / g711 / adpcm never exceeds a second of output; stream.dfpwm's and stream.msadpcm's may (48008 at 48 kHz mono; 48060 for blockAlign 22 at 8 kHz): the buffer grows
     local buf_ch = 2
     local buf = ffi.new("double[?]", CAP * buf_ch)
     local len, ch, st, pos, secs = ffi.new("uint32_t[1]"), ffi.new("int32_t[1]"), ffi.new("int32_t[1]"), ffi.new("double[1]"), ffi.new("double[1]")

@@ -168,11 +168,17 @@ typedef enum {
                                    not a second reader of option 5: a host that asked aukit_decode_resample_mixed for MS-ADPCM rows has not asked
                                    the stream call for anything.  aukit_decode_resample_mixed and aukit_streamset_open ignore it (a stream set
                                    keeps refusing the codec whatever either mask says).  With 0 every call answers exactly as before. */
-    AUKIT_OPT_STREAMSET_CODECS = 7 /* the same for aukit_streamset_open, the only call that reads it, and only while it opens (a set that is open keeps
+    AUKIT_OPT_STREAMSET_CODECS = 7,/* the same for aukit_streamset_open, the only call that reads it, and only while it opens (a set that is open keeps
                                    what it was opened with): a bit mask of 1 << codec, 0 by default, exactly one bit known, 1 << AUKIT_CODEC_DFPWM
                                    (aukit.stream.dfpwm's streams as members of a set, see that call); any other bit is AUKIT_E_UNSUPPORTED, the codec
                                    named (or "bit N"), and the context keeps the mask it had.  Options 5 and 6 keep their one bit each: a DFPWM bit
                                    there is still refused, and neither opens a set to anything.  With 0 every call answers exactly as before. */
+    AUKIT_OPT_STREAMSET_BLOCK_CODECS = 8 /* a second mask of aukit_streamset_open's, read by that call alone and only while it opens (an open set keeps
+                                   what it was opened with): a bit mask of 1 << codec, 0 by default, exactly one bit known, 1 << AUKIT_CODEC_MSADPCM
+                                   (aukit.stream.msadpcm's streams as members of a set, see that call); any other bit is AUKIT_E_UNSUPPORTED, the codec
+                                   named (or "bit N"), and the context keeps the mask it had.  A second option and not a second bit of option 7, which
+                                   knows its one bit and refuses this one by name.  Options 5 and 6 are not needed for a set and open it to nothing;
+                                   this option opens neither mixed call.  With 0 every call answers exactly as before. */
 } aukit_option;
 int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);
 /* counters of the most recent call that produced them (AUKIT_OPT_COLLECT_STATS = 1) */
@@ -531,7 +537,23 @@ void aukit_stream_close(aukit_stream *s);
  * `*len` from the AUKIT_E_ARG refusal and call again.
  * One bad member ends alone.  A finished member whose bytes the string call refuses (data that ends inside a sample; inside a frame without
  * the mix-down) hands out, as the handle does, the chunks of its whole frames — those decided earlier, then the rest — and from then on that
- * status and message; it enters no later pump, and no other member notices. */
+ * status and message; it enters no later pump, and no other member notices.
+ * On request, AUKIT_OPT_STREAMSET_BLOCK_CODECS with bit 1 << AUKIT_CODEC_MSADPCM set on the context when the set is opened, AUKIT_CODEC_MSADPCM members
+ * join (without the bit every refusal above stands, word for word, whatever options 5, 6 and 7 say; with it a refusal of a further codec names
+ * AUKIT_CODEC_MSADPCM in its list, behind option 7's clause where both are set; sinc stays refused).  AUKIT_OPT_STREAM_MIXED_CODECS is not needed: the
+ * set keeps the mask it was opened with.  Such a member is aukit.stream.msadpcm (aukit.lua:2588-2736) as the handle serves it: channels 1 or 2,
+ * block_align and the coefficient list of the descriptor; an iterator call is ceil(rate / samplesPerBlock) blocks and the rest starts at the next call;
+ * an unfinished member is decoded up to a whole block.  What the descriptor alone decides — channels, `bad blockAlign`, the rate, a coefficient pair
+ * with |c1| + |c2| >= 65536 — is refused at open with the member's index.  A one-channel stream decodes every block from the stream's first seven bytes
+ * (no block reads its own header): the set keeps them on the host, captured by aukit_streamset_feed in however many pieces they arrive, and every repack
+ * in which the member drops bytes writes them over the first seven bytes of its new slot (appended to the staging buffer in front of the pump's one
+ * upload; a seven-byte segment of the one k_sset_repack launch).  A predictor index beyond the coefficient table and a delta of 2^21 or more are found
+ * on the device: the engine's pre-pass (k_ms_mixed, its per-stream instantiation) records which fault each stream has, and such a member ends alone at
+ * that pump — the chunks queued by earlier pumps, then AUKIT_E_LUA "attempt to perform arithmetic on a nil value (local 'c1')" or AUKIT_E_UNSUPPORTED
+ * "MS-ADPCM delta of 2^21 or more: aukit_stream_open takes this stream"; no other member notices.  A member finished inside a block hands out the chunks
+ * of its whole blocks, then the string call's status and words for those bytes.  A pump that decodes such members has a second wait, the pre-pass's
+ * flag read-back (as AUKIT_CODEC_ADPCM_WAV members add their header scan's).  A chunk may be longer than 48000 samples (block_align 22, one channel,
+ * 8000 Hz: 267 blocks x 180 = 48060): size `cap` for it, or read `*len` from the AUKIT_E_ARG refusal and call again. */
 typedef struct aukit_streamset aukit_streamset;
 int aukit_streamset_open(aukit_ctx *ctx, const aukit_codec_desc *descs /* n */, uint32_t n, int interp, int mono, int dtype, aukit_streamset **out);
 /* host copy only: no device call, no wait (the pinned buffer grows, rarely, outside the steady state).  After aukit_streamset_finish: AUKIT_E_ARG */
