@@ -461,7 +461,7 @@ def au(data):  # aukit.lua:1639
 _MAGIC_KIND = {"wav": N.CONTAINER_WAV, "aiff": N.CONTAINER_AIFF, "au": N.CONTAINER_AU}
 
 
-def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm=False, stream_ms=False):
+def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm=False, stream_ms=False, stream_qoa=False):
     """load_many's host half, up to the device call: every file sniffed by magic as `detect` does and walked by aukit_parse_container
     -> ([descriptor per file], [(first payload byte, byte count) per file], [info table per file]).  A file that is no WAV / AIFF / AU / QOA, or
     whose payload is none of PCM, G.711 and DFPWM, raises LuaError naming the file's index (0-based, the position in `files`).
@@ -482,7 +482,9 @@ def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm
     Without it both are refused by index in the words of before.
     `stream_ms` (with `stream`): an MS-ADPCM WAV file (format 2) is taken too — the descriptor is the container walk's (blockAlign and the `fmt`
     chunk's coefficient list, as `adpcm` takes it for load_many), the payload the `data` chunk, the length what aukit.stream.wav returns for the
-    file.  Without it such a file is refused by index in the words of before, whatever `stream_ima` and `adpcm` say."""
+    file.  Without it such a file is refused by index in the words of before, whatever `stream_ima` and `adpcm` say.
+    `stream_qoa` (with `stream`): a QOA file is taken too, whole, as load_many takes it — the descriptor names the codec only, the length is NaN
+    (aukit.stream.qoa's own figure stands, file_samples / sampleRate, :3336).  Without it such a file is refused by index in the words of before."""
     _expect(1, files, "table")
     takes = "PCM, G.711 and DFPWM" if stream_dfpwm else "PCM and G.711"
     if stream_ima and stream_ms:
@@ -518,6 +520,11 @@ def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm
             raise LuaError(f"bad argument #1 (file {i}: expected string)")
         kind = detect(bytes(f[:12]))[0]
         if kind == "qoa":
+            if stream and stream_qoa:
+                descs.append(B.make_desc(N.CODEC_QOA))
+                ranges.append((0, len(f)))
+                infos.append(float("nan"))
+                continue
             if stream:
                 raise LuaError(f"file {i}: qoa payload: stream.many takes {takes} ({others} keep their own streams)")
             descs.append(B.make_desc(N.CODEC_QOA))
@@ -893,7 +900,7 @@ class _StreamNS:
             it, length = self._run(d, p, mono, dtype, endless_empty=d.codec == N.CODEC_G711)
         return it, (length if math.isnan(c.length_seconds) else c.length_seconds)
 
-    def many(self, files, mono=None, adpcm=None, msadpcm=None):
+    def many(self, files, mono=None, adpcm=None, msadpcm=None, qoa=None):
         """aukit.stream.wav / aiff / au (file, mono) for a LIST of whole files of any mix of containers, rates, PCM formats / G.711 / DFPWM /
         IMA-ADPCM WAV blocks (each file its own blockAlign; the raise behind a block whose header step index is above 88 included) and
         channel counts: the payload ranges go up as one batch, one aukit_stream_decode_mixed call computes every iterator call of every file, and
@@ -906,25 +913,35 @@ class _StreamNS:
         `adpcm` means IMA-ADPCM only.  MS-ADPCM WAV files (format 2: aukit.stream.wav's dispatch to aukit.stream.msadpcm with the file's blockAlign
         and coefficient list) are taken with `msadpcm=True`, or the key "msadpcm" of the options table: for this one call the context is opted in
         to MS-ADPCM descriptors (AUKIT_OPT_STREAM_MIXED_CODECS) and put back as it was behind it, also where the call is refused.  Without it
-        such a file is refused by index, as before."""
+        such a file is refused by index, as before.
+        QOA files (magic "qoaf") are taken with `qoa=True`, or the key "qoa" of the options table: the file goes up whole under a descriptor that
+        names the codec only (channel count and rate are its header's), its pair is what aukit.stream.qoa(file, mono) returns (length
+        file_samples / sampleRate), and for this one call the context is opted in under an option of its own
+        (AUKIT_OPT_STREAM_MIXED_FRAME_CODECS) and put back as it was behind it, also where the call is refused.  Without it such a file is refused
+        by index, as before."""
         if isinstance(mono, dict):
-            if set(mono) - {"mono", "adpcm", "msadpcm"}:
-                raise LuaError("bad argument #2 (unknown option " + sorted(set(mono) - {"mono", "adpcm", "msadpcm"})[0] + ")")
-            mono, adpcm, msadpcm = mono.get("mono"), mono.get("adpcm", adpcm), mono.get("msadpcm", msadpcm)
+            if set(mono) - {"mono", "adpcm", "msadpcm", "qoa"}:
+                raise LuaError("bad argument #2 (unknown option " + sorted(set(mono) - {"mono", "adpcm", "msadpcm", "qoa"})[0] + ")")
+            mono, adpcm, msadpcm, qoa = mono.get("mono"), mono.get("adpcm", adpcm), mono.get("msadpcm", msadpcm), mono.get("qoa", qoa)
         _expect(2, mono, "boolean", "nil")
         _expect(3, adpcm, "boolean", "nil")
         _expect(4, msadpcm, "boolean", "nil")
-        descs, ranges, lengths = _sniff_many(files, stream=True, stream_dfpwm=True, stream_ima=bool(adpcm), stream_ms=bool(msadpcm))
+        _expect(5, qoa, "boolean", "nil")
+        descs, ranges, lengths = _sniff_many(files, stream=True, stream_dfpwm=True, stream_ima=bool(adpcm), stream_ms=bool(msadpcm), stream_qoa=bool(qoa))
         ctx = context()
         bt = _wrap(B.Batch.upload, ctx, [bytes((f[0] if isinstance(f, (list, tuple)) else f)[o:o + n]) for f, (o, n) in zip(files, ranges)])
-        was = ctx.option(N.OPT_STREAM_MIXED_CODECS)
+        was, was_frame = ctx.option(N.OPT_STREAM_MIXED_CODECS), ctx.option(N.OPT_STREAM_MIXED_FRAME_CODECS)
         try:
             if msadpcm:
                 _wrap(ctx.set_option, N.OPT_STREAM_MIXED_CODECS, was | 1 << N.CODEC_MSADPCM)
+            if qoa:
+                _wrap(ctx.set_option, N.OPT_STREAM_MIXED_FRAME_CODECS, was_frame | 1 << N.CODEC_QOA)
             out, ck = _wrap(B.stream_decode_mixed, ctx, bt, descs, _interp(defaultInterpolation, 0), bool(mono), N.F64)
         finally:
             if msadpcm:
                 ctx.set_option(N.OPT_STREAM_MIXED_CODECS, was)
+            if qoa:
+                ctx.set_option(N.OPT_STREAM_MIXED_FRAME_CODECS, was_frame)
         rows = out.download()
         return [self._chunk_iter(out, ck, None if math.isnan(lengths[i]) else lengths[i], d.codec == N.CODEC_G711, i, rows) for i, d in enumerate(descs)]
 

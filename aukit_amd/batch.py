@@ -615,7 +615,13 @@ def stream_decode_mixed(ctx, batch, descs, interp, mono=False, dtype=None, out=N
     CODEC_MSADPCM (channels 1 or 2, rate, block_align and the coefficient list of make_desc) only on a context that asked this call for it:
     ctx.set_option(N.OPT_STREAM_MIXED_CODECS, 1 << N.CODEC_MSADPCM) — option 6; OPT_MIXED_CODECS is decode_resample_mixed's and means nothing
     here.  Those streams pay a third pre-pass (k_ms_mixed, int16 rows); a predictor index beyond the coefficient table, a delta of 2^21 or more
-    and a coefficient pair with |c1| + |c2| >= 65536 refuse the call by the stream's index, before `out` / `chunks` are touched.  `descs`: one
+    and a coefficient pair with |c1| + |c2| >= 65536 refuse the call by the stream's index, before `out` / `chunks` are touched.
+    aukit.stream.qoa for CODEC_QOA (make_desc(N.CODEC_QOA): only the codec is read, channel count and rate are the file header's; positions count
+    from sample 0) only on a context that asked for it under an option of its own: ctx.set_option(N.OPT_STREAM_MIXED_FRAME_CODECS,
+    1 << N.CODEC_QOA) — option 9; options 5 to 8 do not open the call to QOA.  Those streams pay the device walk of their frame headers (two
+    read-backs, both before `out` / `chunks` are touched) and the decoder to int8 rows, and their tail — the recursive low-pass over a whole
+    iterator call — is one more launch, k_smix_qoa_tail, the call's last; a frame of more than 8192 samples, and a rate whose warm-up or window
+    one tile does not hold, refuse the call by the stream's index and name aukit_stream_decode.  `descs`: one
     CodecDesc per stream.  `out` / `chunks`: what an earlier call returned — the audio's buffers are reused, the chunk table is replaced (after
     a refusal both keep what they held)."""
     out = out if out is not None else AudioBatch(ctx)

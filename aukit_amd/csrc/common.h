@@ -52,6 +52,7 @@ struct aukit_ctx {
     bool chan_lens = false;     // AUKIT_OPT_CHANNEL_LENS: the host reads chunk lengths per channel (stream.pcm delivers its uneven last chunk)
     unsigned mixed_codecs = 0;  // AUKIT_OPT_MIXED_CODECS: bit 1 << codec lets aukit_decode_resample_mixed take that codec beyond its default list
     unsigned stream_mixed_codecs = 0;  // AUKIT_OPT_STREAM_MIXED_CODECS: the same for aukit_stream_decode_mixed, which reads this mask and no other
+    unsigned stream_mixed_frame_codecs = 0;   // AUKIT_OPT_STREAM_MIXED_FRAME_CODECS: that call's second mask (1 << AUKIT_CODEC_QOA), read by the public call alone
     unsigned streamset_codecs = 0;     // AUKIT_OPT_STREAMSET_CODECS: bit 1 << codec lets aukit_streamset_open, which reads this mask and no other, take that codec
     unsigned streamset_block_codecs = 0;   // AUKIT_OPT_STREAMSET_BLOCK_CODECS: the same call's second mask (1 << AUKIT_CODEC_MSADPCM), read while a set opens
     bool fast_store_x4 = true;  // AUKIT_OPT_STORE_X4: LDS-transposed 16-byte stores in the fast kernels

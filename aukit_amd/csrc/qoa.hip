@@ -15,6 +15,7 @@
 #include <algorithm>
 #include "resample.h"
 #include "stream_tail.h"
+#include "stream_mixed_qoa.h"
 
 namespace aukit {
 
@@ -452,6 +453,44 @@ int qoa_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<Qo
     return ctx_end_kernel(ctx, "k_qoa_wave", src_bytes + row_elems * 2);
 }
 size_t qoa_mixed_job_bytes(uint64_t njobs) { return (size_t)std::max<uint64_t>(njobs, 1) * sizeof(QoaJob) + 64; }
+
+// The stream-mode twin, the QOA pre-pass of aukit_stream_decode_mixed (stream_mixed.hip): aukit.stream.qoa's walks (mode 1: one iterator call after
+// the other) and decoder on the streams `list` names and on no other stream of the batch.  Two halves again, each with a read-back and a wait:
+//   qoa_smix_count: the count pass and the header read-back; refuses what stream_qoa refuses of a header, with its words (*bad: which entry);
+//   qoa_smix_decode: the fill pass — a stream's calls one behind the other from the int8 element the prefix sums of rows_total give it, a call's
+//     channel c at row0 + c * stride, stride = round_up(n + 2, 16) —, the read-back of the call records, then k_qoa_wave<true> into `rows`.
+//     `djobs`: room for the jobs the count pass reported (qoa_mixed_job_bytes).
+// The jobs are stream_qoa's: what no job writes is what that call leaves there too.
+int qoa_smix_count(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<QoaSMixStream> &Q, uint32_t *bad) {
+    std::vector<QoaStreamInfo> S;
+    const int rc = qoa_walk_count(ctx, in, 1, S, nullptr, &list, bad);
+    if (rc) return rc;
+    Q.resize(S.size());
+    for (size_t s = 0; s < S.size(); s++) Q[s] = QoaSMixStream{S[s].channels, S[s].rate, S[s].file_samples, S[s].raised, S[s].big, S[s].ncalls, S[s].njobs, S[s].rows_total};
+    return AUKIT_OK;
+}
+int qoa_smix_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<QoaSMixStream> &Q, signed char *rows, void *djobs, uint64_t src_bytes, std::vector<QoaSMixCall> &calls) {
+    std::vector<QoaStreamInfo> S(Q.size());
+    uint64_t jat = 0, cat = 0, rat = 0;
+    for (size_t s = 0; s < Q.size(); s++) {
+        QoaStreamInfo &q = S[s];
+        q.channels = Q[s].channels; q.rate = Q[s].rate; q.file_samples = Q[s].file_samples; q.ncalls = Q[s].ncalls; q.njobs = Q[s].njobs;
+        q.rows_total = Q[s].rows_total; q.stride = 0;
+        q.job_first = jat; q.call_first = cat; q.row_base = rat;
+        jat += q.njobs; cat += q.ncalls; rat += q.rows_total;
+    }
+    std::vector<QoaCallRec> recs;
+    int rc = qoa_walk_fill(ctx, in, 1, S, reinterpret_cast<QoaJob *>(djobs), cat, &recs, nullptr, nullptr, true);
+    if (rc) return rc;
+    calls.resize(recs.size());
+    for (size_t i = 0; i < recs.size(); i++) calls[i] = QoaSMixCall{recs[i].row0, recs[i].stride, recs[i].n, recs[i].sample_pos};
+    ctx->counters[AUKIT_COUNTER_QOA_WAVE] = 1;
+    if (!jat) return AUKIT_OK;
+    if ((rc = ctx_begin_kernel(ctx))) return rc;
+    hipLaunchKernelGGL((k_qoa_wave<true>), dim3((unsigned)((jat + 63) / 64)), dim3(64), 0, ctx->stream, in->data(), reinterpret_cast<const QoaJob *>(djobs), (unsigned long long)jat, rows);
+    AUKIT_HIP_CHECK(hipGetLastError());
+    return ctx_end_kernel(ctx, "k_qoa_wave", src_bytes + rat);
+}
 
 // aukit.stream.qoa(data, mono)  aukit.lua:3202-3337
 int stream_qoa(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *d, int interp, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks_out) {

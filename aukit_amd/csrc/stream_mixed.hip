@@ -59,6 +59,17 @@
 // from the whole stream.  With a carry the pre-pass runs k_ms_mixed<true>, reads the per-stream fault words back with the two flag words (one copy,
 // one wait) and, instead of refusing the batch, takes every offending stream out of the plan: no chunk, the fault as its status (smix_drop_faulted).
 //
+// aukit.stream.qoa (data_s, mono) (:3202-3337) is the fifth kind, and the one that is NOT a class of k_stream_mixed: its iterator ends in a recursive
+// filter over the whole call (:3316-3325), which a lane per output cannot run.  Only a context that set AUKIT_OPT_STREAM_MIXED_FRAME_CODECS hands such a
+// stream in.  The batch's QOA streams — a list; channel count and rate are each file header's — go through qoa.hip's walks in stream mode
+// (qoa_smix_count: the count pass and the header read-back, inside smix_validate; qoa_smix_decode: the fill pass, the read-back of the call records
+// and k_qoa_wave<true> into int8 rows behind the other pre-passes' scratch), are planned from the call records (stream_mixed_qoa.h: a class per
+// (channels, rate), the chunk table as stream_qoa computes it, jobs and tiles) and end in ONE launch of k_smix_qoa_tail (stream_mixed_qoa.hip), the
+// call's last kernel, which writes their rows of `*out`.  Their segments stand in the plan for the chunk table and the audio's layout, marked
+// SMIX_CLS_QOA: k_stream_mixed gets no tile for them, and a batch of QOA streams alone launches no k_stream_mixed.  The host waits twice for the
+// device on their account — the two read-backs, both before `*out` and `*chunks` are touched —, a second kind of wait beside the IMA scan's and
+// the MS-ADPCM verdict's, paid only by a batch that has a QOA stream.
+//
 // The host half reads as the call's phases: smix_validate, smix_classes, the IMA header scan, one planner per codec (plan_pcm, plan_g711, plan_dfpwm,
 // plan_ima, plan_ms: they fill an SMixPlan and touch neither the context nor HIP), the scratch layout, the MS-ADPCM pre-pass and its verdict, the two
 // other pre-passes, smix_tiles, the launch.  What the call shares with aukit_decode_resample_mixed is in mixed_plan.h, stream.adpcm's arithmetic in
@@ -69,10 +80,20 @@
 #include "mixed_plan.h"
 #include "ima_geom.h"
 #include "ms_geom.h"
+#include "stream_mixed_qoa.h"
 #include "resample_dev.h"
 #include "dfpwm_dev.h"
 
 namespace aukit {
+
+// qoa.hip's stream-mode walks and stream_mixed_qoa.hip's launch
+int qoa_smix_count(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<QoaSMixStream> &Q, uint32_t *bad);
+int qoa_smix_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<QoaSMixStream> &Q, signed char *rows, void *djobs, uint64_t src_bytes, std::vector<QoaSMixCall> &calls);
+size_t qoa_mixed_job_bytes(uint64_t njobs);
+int smix_qoa_tail_launch(aukit_ctx *ctx, const std::vector<SMixQoaClass> &classes, const std::vector<SMixQoaJob> &jobs, const std::vector<SMixQoaTile> &tiles, size_t lds,
+                         const signed char *rows, void *out, int interp, int dtype, uint64_t algorithmic_bytes);
+
+constexpr unsigned SMIX_CLS_QOA = 0xFFFFFFFFu;   // SMixSeg::cls of a QOA call: no class of k_stream_mixed, no tile of it
 
 enum { SMIX_EPI_PCM = 0, SMIX_EPI_FLOOR = 1, SMIX_EPI_DFPWM = 2, SMIX_EPI_MS_MONO = 3 };
 
@@ -594,13 +615,37 @@ int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) {
 // frame — what its carry says
 static inline uint64_t smix_nbytes(const aukit_batch *in, const SMixCarry *carry, uint32_t s) { return carry ? carry[s].nbytes : in->off[s + 1] - in->off[s]; }
 
-static int smix_validate(const aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
-                         const SMixCarry *carry, unsigned block_codecs) {
+// the QOA streams of the batch, in batch order, as the count pass of the walk found them (smix_validate), and what is planned from that
+struct SMixQoa {
+    std::vector<uint32_t> list;           // their indices in the batch
+    std::vector<QoaSMixStream> Q;
+    std::vector<SMixQoaClass> classes;    // one per distinct (channels, rate), in order of first appearance
+    std::vector<unsigned> cls_of;         // per entry of `list`
+    std::vector<uint64_t> max_nout;       // per class: its longest job
+    size_t lds = 0;                       // the largest class's
+    uint64_t rows = 0, njobs = 0, ncalls = 0, src = 0;   // int8 elements of all rows; decode jobs; iterator calls; source bytes
+    std::vector<QoaSMixCall> calls;       // stream after stream (qoa_smix_decode)
+    std::vector<std::vector<SMixQoaCallPlan>> plan;   // per entry of `list`
+};
+
+static int smix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
+                         const SMixCarry *carry, unsigned block_codecs, unsigned frame_codecs, SMixQoa &QS, std::vector<int> &ch_of) {
     int rc;
     if ((rc = mixed_check_call(ctx, in, out, descs, n_descs, interp, dtype, "invalid interpolation", "stream each class with aukit_stream_decode"))) return rc;
     // AUKIT_OPT_STREAM_MIXED_CODECS: MS-ADPCM joins the list on a context that asked this call for it; without the bit the call answers in the words of before.
     // (The mask is the caller's: the public call hands in the context's, a stream set the one it was opened with)
-    if ((block_codecs >> AUKIT_CODEC_MSADPCM) & 1u)
+    // AUKIT_OPT_STREAM_MIXED_FRAME_CODECS: QOA likewise, under an option of its own; its clause stands behind option 6's
+    const bool with_qoa = (frame_codecs >> AUKIT_CODEC_QOA) & 1u;
+    if (with_qoa && ((block_codecs >> AUKIT_CODEC_MSADPCM) & 1u))
+        rc = mixed_check_codecs(descs, in->n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_MSADPCM, AUKIT_CODEC_QOA},
+                                "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, "
+                                "AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_STREAM_MIXED_CODECS, AUKIT_CODEC_MSADPCM and, under "
+                                "AUKIT_OPT_STREAM_MIXED_FRAME_CODECS, AUKIT_CODEC_QOA)");
+    else if (with_qoa)
+        rc = mixed_check_codecs(descs, in->n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_QOA},
+                                "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, "
+                                "AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_STREAM_MIXED_FRAME_CODECS, AUKIT_CODEC_QOA)");
+    else if ((block_codecs >> AUKIT_CODEC_MSADPCM) & 1u)
         rc = mixed_check_codecs(descs, in->n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_MSADPCM},
                                 "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, "
                                 "AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_STREAM_MIXED_CODECS, AUKIT_CODEC_MSADPCM)");
@@ -609,8 +654,23 @@ static int smix_validate(const aukit_ctx *ctx, const aukit_batch *in, const auki
                                 "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, "
                                 "AUKIT_CODEC_DFPWM and AUKIT_CODEC_ADPCM_WAV)");
     if (rc) return rc;
-    if ((rc = mixed_check_channels(in->n, mono, [&](uint32_t s) { return descs[s].channels; }))) return rc;
+    ch_of.resize(in->n);
     for (uint32_t s = 0; s < in->n; s++) {
+        ch_of[s] = descs[s].channels;
+        if (descs[s].codec == AUKIT_CODEC_QOA) QS.list.push_back(s);
+    }
+    // QOA: only `codec` of the descriptor is read.  The count pass of the device walk on these streams, and the header read-back: what stream_qoa
+    // refuses of a header is refused first, with its words.  It writes ctx->tmp_buf3 and nothing of `*out`
+    if (!QS.list.empty()) {
+        if (carry) return fail(AUKIT_E_UNSUPPORTED, "stream %u: a stream set takes no AUKIT_CODEC_QOA member", QS.list[0]);
+        AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
+        uint32_t bad = 0;
+        if ((rc = qoa_smix_count(ctx, in, QS.list, QS.Q, &bad))) return fail_for_stream(rc, QS.list[bad]);
+        for (size_t i = 0; i < QS.list.size(); i++) ch_of[QS.list[i]] = QS.Q[i].channels;   // the file header's  :3241
+    }
+    if ((rc = mixed_check_channels(in->n, mono, [&](uint32_t s) { return ch_of[s]; }))) return rc;
+    for (uint32_t s = 0; s < in->n; s++) {
+        if (descs[s].codec == AUKIT_CODEC_QOA) continue;   // (its header was the check)
         if (carry && carry[s].nbytes > in->off[s + 1] - in->off[s]) return fail(AUKIT_E_ARG, "stream %u: the carry names more bytes than the batch holds", s);
         if ((rc = check_smix_stream(&descs[s], smix_nbytes(in, carry, s), mono != 0))) return fail_for_stream(rc, s);
     }
@@ -634,6 +694,7 @@ static int smix_classes(const aukit_codec_desc *descs, uint32_t n, int interp, i
     T.cls_of.resize(n);
     for (uint32_t s = 0; s < n; s++) {
         const aukit_codec_desc &d = descs[s];
+        if (d.codec == AUKIT_CODEC_QOA) { T.cls_of[s] = SMIX_CLS_QOA; continue; }   // (smix_qoa_classes)
         const bool pcm = d.codec == AUKIT_CODEC_PCM, df = d.codec == AUKIT_CODEC_DFPWM, ima = d.codec == AUKIT_CODEC_ADPCM_WAV, ms = d.codec == AUKIT_CODEC_MSADPCM;
         T.has_df = T.has_df || df;
         T.has_ima = T.has_ima || ima;
@@ -701,6 +762,35 @@ static int smix_classes(const aukit_codec_desc *descs, uint32_t n, int interp, i
         T.classes.push_back(K);
         T.tile_out.push_back(to);
     }
+    return AUKIT_OK;
+}
+
+// the QOA streams' classes, one per distinct (channels, rate) of the file headers, and what is refused of a walk or a class by stream index: the
+// stream's own call serves all of it (its host path)
+static int smix_qoa_classes(SMixQoa &QS) {
+    ClassIndex<std::tuple<int, double>> index;
+    QS.cls_of.resize(QS.list.size());
+    for (size_t i = 0; i < QS.list.size(); i++) {
+        const QoaSMixStream &q = QS.Q[i];
+        const unsigned s = QS.list[i];
+        if (q.big) return fail(AUKIT_E_UNSUPPORTED, "QOA frame of more than 8192 samples: aukit_stream_decode takes this file (stream %u)", s);
+        bool fresh;
+        QS.cls_of[i] = index.of({q.channels, q.rate}, &fresh);
+        QS.rows += q.rows_total; QS.njobs += q.njobs; QS.ncalls += q.ncalls;
+        if (!fresh) continue;
+        SMixQoaClass K;
+        size_t lds = 0;
+        const int why = smix_qoa_class_shape(q.channels, q.rate, &K, &lds);
+        if (why == 1)
+            return fail(AUKIT_E_UNSUPPORTED, "QOA at %g Hz: the low-pass needs a warm-up beyond one tile of %d outputs: aukit_stream_decode takes this file (stream %u)", q.rate,
+                        SMIX_QOA_TMAX, s);
+        if (why)
+            return fail(AUKIT_E_UNSUPPORTED, "QOA at %g Hz: a tile's window needs more than %d KiB of LDS: aukit_stream_decode takes this file (stream %u)", q.rate,
+                        (int)(SMIX_QOA_LDS / 1024), s);
+        QS.lds = std::max(QS.lds, lds);
+        QS.classes.push_back(K);
+    }
+    QS.max_nout.assign(QS.classes.size(), 0);
     return AUKIT_OK;
 }
 
@@ -923,12 +1013,53 @@ static void smix_plan(const aukit_batch *in, const aukit_codec_desc *descs, cons
         memset(&g, 0, sizeof g);
         g.src_off = in->off[s];
         g.cls = cls_of[s];
+        if (d.codec == AUKIT_CODEC_QOA) continue;   // (planned from its call records, behind the fill pass: plan_qoa)
         if (d.codec == AUKIT_CODEC_DFPWM) plan_dfpwm(pl, s, g, d, nb, cy);
         else if (d.codec == AUKIT_CODEC_ADPCM_WAV) plan_ima(pl, s, g, d, nb, ima_bad[ima_i++], cy);
         else if (d.codec == AUKIT_CODEC_MSADPCM) plan_ms(pl, s, g, d, nb, cy);
         else if (d.codec == AUKIT_CODEC_PCM) plan_pcm(pl, s, g, d, nb, interp, mono, cy);
         else plan_g711(pl, s, g, d, nb, cy);
     }
+}
+
+// stream_qoa's plan (qoa.hip) for every QOA stream, from the call records: the chunk table's numbers per call (smix_qoa_plan_stream), the length
+// file_samples / rate (:3336), AUKIT_E_LUA where the walk raised — the chunks of the calls before it are delivered —, and the class's longest job.
+// The calls join the plan as segments in the stream's place, so that the chunk table and the audio's rows are laid out as for every other kind
+static int plan_qoa(SMixPlan &pl, SMixQoa &QS) {
+    QS.plan.resize(QS.list.size());
+    std::vector<SMixSeg> segs;
+    std::vector<double> cpos;
+    size_t i = 0, qi = 0, call0 = 0;
+    for (uint32_t s = 0; s < pl.ck->n; s++) {
+        if (qi < QS.list.size() && QS.list[qi] == s) {
+            const QoaSMixStream &q = QS.Q[qi];
+            if (!smix_qoa_plan_stream(q.rate, QS.calls.data() + call0, q.ncalls, QS.plan[qi])) return fail_for_stream(fail(AUKIT_E_UNSUPPORTED, "stream too long"), s);
+            pl.ck->length_seconds[s] = q.file_samples / q.rate;
+            if (q.raised) pl.ck->status[s] = AUKIT_E_LUA;   // assert(read(8), "Invalid QOA data") / a short unpack
+            for (const SMixQoaCallPlan &c : QS.plan[qi]) {
+                SMixSeg g;
+                memset(&g, 0, sizeof g);
+                g.cls = SMIX_CLS_QOA;
+                g.n_out = (unsigned)c.nout;
+                g.out_off = pl.lens[s];
+                segs.push_back(g);
+                cpos.push_back(c.pos);
+                pl.lens[s] += c.nout;
+                pl.ck->nchunks[s]++;
+                QS.max_nout[QS.cls_of[qi]] = std::max(QS.max_nout[QS.cls_of[qi]], c.nout);
+            }
+            call0 += q.ncalls;
+            qi++;
+            continue;
+        }
+        const uint32_t k = pl.ck->nchunks[s];
+        segs.insert(segs.end(), pl.segs.begin() + i, pl.segs.begin() + i + k);
+        cpos.insert(cpos.end(), pl.cpos.begin() + i, pl.cpos.begin() + i + k);
+        i += k;
+    }
+    pl.segs.swap(segs);
+    pl.cpos.swap(cpos);
+    return AUKIT_OK;
 }
 
 // the chunk table of the plan: lengths and positions of every stream's calls, max_chunks apart
@@ -953,8 +1084,10 @@ static void smix_chunk_table(SMixPlan &pl, int C_out) {
 // behind the IMA scratch k_ms_mixed's int16 rows (a row per (stream, channel) at a multiple of 16 bytes, 64 bytes to spare behind the last: the
 // tiles' 16-byte loads rely on them), its unit table, its coefficient sets and its two flag words — for a stream set with, right behind them, the two
 // fault words of every stream of the batch (one read-back takes both)
-struct SMixScratch { size_t df_tab_at = 0, df_states_at = 0, ima_at = 0, ima_tab_at = 0, ms_at = 0, ms_unit_at = 0, ms_coef_at = 0, ms_flag_at = 0, size = 0; };
-static SMixScratch smix_scratch(const SMixPlan &pl, bool ms_per_stream) {
+struct SMixScratch { size_t df_tab_at = 0, df_states_at = 0, ima_at = 0, ima_tab_at = 0, ms_at = 0, ms_unit_at = 0, ms_coef_at = 0, ms_flag_at = 0, qoa_at = 0, qoa_jobs_at = 0, size = 0; };
+// (behind everything else, so that a batch without a QOA stream lays its scratch out as before: the QOA streams' int8 rows, 16-byte aligned as every
+// call's row is, and the decoder's job table)
+static SMixScratch smix_scratch(const SMixPlan &pl, bool ms_per_stream, const SMixQoa &QS) {
     Carve carve;
     SMixScratch L;
     if (pl.df_n) { carve.take((size_t)pl.df_tot); L.df_tab_at = carve.take((size_t)pl.df_n * (8 + sizeof(SMixDfItem) + 4)); }  // (the rows are at 0)
@@ -966,6 +1099,7 @@ static SMixScratch smix_scratch(const SMixPlan &pl, bool ms_per_stream) {
         L.ms_coef_at = carve.take(pl.ms.coefs.size() * sizeof(int), 0);
         L.ms_flag_at = carve.take(8 + (ms_per_stream ? (size_t)pl.ck->n * 8 : 0), 56);
     }
+    if (!QS.list.empty()) { L.qoa_at = carve.take((size_t)QS.rows); L.qoa_jobs_at = carve.take(qoa_mixed_job_bytes(QS.njobs), 0); }
     L.size = carve.end;
     return L;
 }
@@ -1099,7 +1233,7 @@ static uint64_t smix_cut(const SMixClass &K, unsigned to, const SMixSeg &g, unsi
 }
 static uint64_t smix_count_tiles(const SMixClasses &T, const SMixPlan &pl) {
     uint64_t nt = 0;
-    for (const SMixSeg &g : pl.segs) nt += smix_cut(T.classes[g.cls], (unsigned)T.tile_out[g.cls], g, 0, nullptr);
+    for (const SMixSeg &g : pl.segs) if (g.cls != SMIX_CLS_QOA) nt += smix_cut(T.classes[g.cls], (unsigned)T.tile_out[g.cls], g, 0, nullptr);
     return nt;
 }
 // the segments get their place in the audio's rows on the way
@@ -1112,6 +1246,7 @@ static std::vector<SMixTile> smix_tiles(const SMixClasses &T, SMixPlan &pl, cons
             SMixSeg &g = pl.segs[i];
             g.out_off += a->row_off[s];
             g.out_stride = (unsigned)a->row_stride[s];
+            if (g.cls == SMIX_CLS_QOA) continue;   // k_smix_qoa_tail's
             smix_cut(T.classes[g.cls], (unsigned)T.tile_out[g.cls], g, (unsigned)i, &tiles);
         }
     return tiles;
@@ -1143,20 +1278,48 @@ static int smix_launch(aukit_ctx *ctx, const aukit_batch *in, const SMixClasses 
 // bytes and how many of the slot's bytes are the stream's (mixed_plan.h); a DFPWM stream's carry may hold the decoder's state in front of the bytes
 // and ask for the states at this decode's call boundaries, which `back` then names (the set's next carry comes from there).  A batch in which no
 // carry does either launches what it always launched
+// ---- phase 9: the QOA streams' tail, the call's last kernel: jobs and tiles with their place in the audio's rows, the exact_div_verified verdict of
+// every class over its longest job (the quotient rule of the single call), one launch
+static int smix_qoa_tail(aukit_ctx *ctx, SMixQoa &QS, const SMixScratch &L, const aukit_audio *a, bool mono, int interp, int dtype) {
+    std::vector<SMixQoaJob> jobs;
+    std::vector<SMixQoaTile> tiles;
+    size_t call0 = 0;
+    uint64_t out_elems = 0;
+    for (size_t i = 0; i < QS.list.size(); i++) {
+        const uint32_t s = QS.list[i];
+        const SMixQoaClass &K = QS.classes[QS.cls_of[i]];
+        const bool mix = mono && K.channels > 1;
+        smix_qoa_jobs(K, QS.cls_of[i], mix, QS.calls.data() + call0, QS.plan[i].data(), QS.Q[i].ncalls, a->row_off[s], a->row_stride[s], jobs, tiles);
+        for (const SMixQoaCallPlan &c : QS.plan[i]) out_elems += c.nout * (uint64_t)(mix || mono ? 1 : K.channels);
+        call0 += QS.Q[i].ncalls;
+    }
+    if (tiles.empty()) return AUKIT_OK;
+    if (tiles.size() > 0xFFFFFFF0ull || jobs.size() > 0xFFFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
+    for (size_t c = 0; c < QS.classes.size(); c++)
+        QS.classes[c].exact = exact_div_verified(ctx, QS.classes[c].ratio, std::max<uint64_t>(QS.max_nout[c] + 2, 1ull << 17)) ? 1 : 0;
+    const signed char *rows = reinterpret_cast<const signed char *>(ctx->tmp_buf.p) + L.qoa_at;
+    return smix_qoa_tail_launch(ctx, QS.classes, jobs, tiles, QS.lds, rows, a->dev, interp, dtype, QS.rows + out_elems * dtype_size(dtype));
+}
+
 int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
-                              aukit_chunks **chunks, const SMixCarry *carry, SMixDfBack *back, unsigned block_codecs) {
-    // what can be refused is refused before the device is touched; `*out` and `*chunks` keep what they held
+                              aukit_chunks **chunks, const SMixCarry *carry, SMixDfBack *back, unsigned block_codecs, unsigned frame_codecs) {
+    // what can be refused is refused before the device is touched (a batch with a QOA stream: behind the walk's count pass); `*out` and `*chunks` keep
+    // what they held
     int rc;
-    if ((rc = smix_validate(ctx, in, descs, n_descs, interp, mono, dtype, out, carry, block_codecs))) return rc;
+    SMixQoa QS;
+    std::vector<int> ch_of;
+    if ((rc = smix_validate(ctx, in, descs, n_descs, interp, mono, dtype, out, carry, block_codecs, frame_codecs, QS, ch_of))) return rc;
     const uint32_t n = in->n;
+    const bool qoa = !QS.list.empty();
     SMixClasses T;
     if ((rc = smix_classes(descs, n, interp, mono, T))) return rc;
+    if (qoa && (rc = smix_qoa_classes(QS))) return rc;
     AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
     smix_exact_division(ctx, T.classes);
     std::vector<unsigned> ima_bad;
     if (T.has_ima && (rc = smix_ima_scan(ctx, in, descs, carry, ima_bad))) return rc;
 
-    const int C_out = mono ? 1 : (n ? descs[0].channels : 1);
+    const int C_out = mono ? 1 : (n ? ch_of[0] : 1);
     SMixPlan pl(n);
     smix_plan(in, descs, carry, T.cls_of, interp, mono != 0, ima_bad, pl);
     smix_chunk_table(pl, C_out);
@@ -1165,9 +1328,16 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
     if (pl.df_states && !back) return fail(AUKIT_E_ARG, "null argument");
 
     // the scratch is sized before `*out` is touched, and its pointer is read after
-    const SMixScratch L = smix_scratch(pl, carry != nullptr);
+    const SMixScratch L = smix_scratch(pl, carry != nullptr, QS);
     const bool ms = !pl.ms.units.empty();
-    if ((pl.df_n || pl.ima_jobs || ms) && (rc = mixed_scratch_ensure(ctx, *out, L.size))) return rc;
+    if ((pl.df_n || pl.ima_jobs || ms || qoa) && (rc = mixed_scratch_ensure(ctx, *out, L.size))) return rc;
+    if (qoa) {   // the fill pass, the read-back of the call records, the decoder; then the streams' calls join the plan
+        char *const S = reinterpret_cast<char *>(ctx->tmp_buf.p);
+        for (uint32_t s : QS.list) QS.src += in->off[s + 1] - in->off[s];
+        if ((rc = qoa_smix_decode(ctx, in, QS.Q, reinterpret_cast<signed char *>(S + L.qoa_at), S + L.qoa_jobs_at, QS.src, QS.calls))) return rc;
+        if ((rc = plan_qoa(pl, QS))) return rc;
+        smix_chunk_table(pl, C_out);
+    }
     std::vector<int> ms_faults;
     if (ms && (rc = smix_ms_prepass(ctx, in, pl, L, carry ? &ms_faults : nullptr))) return rc;
     if (std::any_of(ms_faults.begin(), ms_faults.end(), [](int f) { return f != 0; })) {   // (a stream set's batch only: the public call was refused above)
@@ -1189,6 +1359,7 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
         const std::vector<SMixTile> tiles = smix_tiles(T, pl, a, nt);
         if ((rc = smix_launch(ctx, in, T, pl, tiles, L, a, interp, dtype))) return rc;
     }
+    if (qoa && (rc = smix_qoa_tail(ctx, QS, L, a, mono != 0, interp, dtype))) return rc;
     chunks_deliver(pl.ck, chunks);   // the caller's table is replaced
     return AUKIT_OK;
 }
@@ -1199,5 +1370,6 @@ using namespace aukit;
 
 extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype,
                                          aukit_audio **out, aukit_chunks **chunks) {
-    return stream_decode_mixed_carry(ctx, in, descs, n_descs, interp, mono, dtype, out, chunks, nullptr, nullptr, ctx ? ctx->stream_mixed_codecs : 0u);
+    return stream_decode_mixed_carry(ctx, in, descs, n_descs, interp, mono, dtype, out, chunks, nullptr, nullptr, ctx ? ctx->stream_mixed_codecs : 0u,
+                                     ctx ? ctx->stream_mixed_frame_codecs : 0u);
 }

@@ -1,0 +1,138 @@
+// stream_mixed_qoa.h — aukit.stream.qoa (data_s, mono) (aukit.lua:3202-3337) in aukit_stream_decode_mixed: what the host half (stream_mixed.hip),
+// the walks (qoa.hip) and the tail kernel (stream_mixed_qoa.hip) share.  The records and the planners below are plain C++ on std types — no HIP,
+// no context — so that they build and run on a CPU alone (tools/smix_qoa_plan_check.cpp puts them under a sanitizer).
+//
+// A QOA stream of the batch is walked on the device (k_qoa_walk in mode 1, one lane per stream: count, then fill), its iterator calls come back as
+// QoaSMixCall records, and k_qoa_wave<true> decodes every call's table to int8 rows: channel c of a call at row0 + c * stride, table index 1 first.
+// From the records the host plans
+//   - a class per distinct (channels, rate): ratio, low-pass weight, the warm-up W, the tile height T and the LDS window (smix_qoa_class_shape);
+//   - the chunk table of every stream (smix_qoa_plan_stream), exactly as stream_qoa (qoa.hip) computes it;
+//   - a job per (stream, call) — mixed down: its channels are walked one after another — or per (stream, call, channel), and the tiles of every
+//     job, each naming its job and its first output (smix_qoa_jobs).
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+namespace aukit {
+
+constexpr int SMIX_QOA_E = 8;                   // consecutive outputs per thread of k_smix_qoa_tail
+constexpr int SMIX_QOA_TMAX = 256 * SMIX_QOA_E; // outputs per tile at the most
+constexpr size_t SMIX_QOA_LDS = 64 * 1024;      // what a class's window and sample buffer may take together
+
+// one iterator call of a stream as the fill pass of the walk reports it (qoa.hip's QoaCallRec)
+struct QoaSMixCall {
+    unsigned long long row0;   // int8 elements from the rows: channel 0, table index 1
+    unsigned stride;           // elements between the call's channel rows (a multiple of 16, at least n + 2)
+    unsigned n;                // #chunk[1]
+    unsigned sample_pos;       // what the call adds to file_pos  :3333
+};
+// one QOA stream as the count pass reports it
+struct QoaSMixStream {
+    int channels; double rate, file_samples;
+    bool raised, big;          // the walk raised (the calls before are delivered); a frame of more than 8192 samples
+    unsigned ncalls;
+    uint64_t njobs, rows_total;   // decode jobs; int8 elements of all its calls' rows
+};
+
+struct SMixQoaClass {
+    double ratio, rcp;         // x = (i - 1) / ratio + 1  :3320
+    double lp_alpha;           // 1 - exp(-(rate / 96000) * 2 pi)  :3251
+    int exact;                 // 1: RN((i - 1) / ratio) via rcp and two fmas is verified over the class's longest job
+    int W, T;                  // warm-up outputs; outputs per tile (a multiple of SMIX_QOA_E)
+    int cap, xbn;              // LDS doubles of the table window / of the tile's samples
+    int channels;              // of the file
+};
+static_assert(sizeof(SMixQoaClass) == 48, "SMixQoaClass layout");
+struct SMixQoaJob {
+    unsigned long long src_off;    // rows: table index 1 of the job's first channel
+    unsigned long long last_off;   // rows: the call before's last sample of that channel — table index 0, and one in front of it index -1 (:3255); ~0: both 0
+    unsigned long long out_off;    // element of output 0
+    unsigned src_cstride, last_cstride;   // elements between the channels of a mixed-down job
+    int n, nout;                   // #table, outputs
+    unsigned cls;
+    int nch;                       // channels walked: the file's where the job mixes down, else 1
+};
+static_assert(sizeof(SMixQoaJob) == 48, "SMixQoaJob layout");
+struct SMixQoaTile { unsigned job, o0; };
+struct SMixQoaParams {
+    const SMixQoaTile *tiles;
+    const SMixQoaJob *jobs;
+    const SMixQoaClass *classes;
+    unsigned n_tiles;
+    const signed char *rows;
+    void *out;
+};
+
+// The class of (channels, rate): stream_tail.hip's tail_shape for int8 rows, with the tile height the class's own.  A state W outputs back still shows
+// as a^W of it, a = exp(-decay): below 1e-16 of a sample of magnitude 128 after W = ceil((37 + ln 128) / decay) outputs.
+// -> 0; 1: the warm-up does not fit one tile (very low rates); 2: the window exceeds the LDS budget (very high rates)
+static inline int smix_qoa_class_shape(int channels, double rate, SMixQoaClass *K, size_t *lds) {
+    *K = SMixQoaClass{};
+    K->channels = channels;
+    K->ratio = 48000 / rate;                                         // :3250
+    K->rcp = 1.0 / K->ratio;
+    K->lp_alpha = 1 - std::exp(-(rate / 96000) * 2 * M_PI);          // :3251
+    const double decay = (rate / 96000) * 2 * M_PI;
+    const double wd = std::ceil((37.0 + std::log(128.0)) / decay);
+    auto shape = [&](int T, double w, int *cap, int *xbn) {
+        const double capd = std::ceil(((double)T + w) / K->ratio) + 8;
+        const double tot = (double)T + w;
+        *cap = capd < 1e9 ? (((int)capd + 3) & ~3) : 0x40000000;
+        *xbn = ((int)tot + (int)tot / SMIX_QOA_E + 2 + 3) & ~3;
+        return ((size_t)*cap + (size_t)*xbn) * 8;
+    };
+    int T = SMIX_QOA_TMAX;
+    if (!(wd <= (double)T)) return 1;
+    while (T > 256 && (double)(T / 2) >= wd && shape(T, wd, &K->cap, &K->xbn) > SMIX_QOA_LDS) T /= 2;
+    *lds = shape(T, wd, &K->cap, &K->xbn);
+    if (*lds > SMIX_QOA_LDS) return 2;
+    K->W = (int)wd;
+    K->T = T;
+    return 0;
+}
+
+// The chunk table of one stream from its call records, exactly as stream_qoa computes it: n_out = floor(n * ratio), 0 below 1 (:3312, :3317);
+// pos = file_pos / rate with file_pos advanced by the call's sample_pos (:3332-3333), counted from sample 0.
+// -> false: a call of more than 0x7FFFFFF0 outputs ("stream too long")
+struct SMixQoaCallPlan { uint64_t nout; double pos; };
+static inline bool smix_qoa_plan_stream(double rate, const QoaSMixCall *calls, unsigned ncalls, std::vector<SMixQoaCallPlan> &plan) {
+    const double ratio = 48000 / rate;
+    double file_pos = 0;
+    plan.clear();
+    for (unsigned k = 0; k < ncalls; k++) {
+        const double newlen = (double)calls[k].n * ratio;
+        if (!(newlen <= 2147483632.0)) return false;
+        plan.push_back(SMixQoaCallPlan{newlen >= 1 ? (uint64_t)std::floor(newlen) : 0, file_pos / rate});
+        file_pos += (double)calls[k].sample_pos;
+    }
+    return true;
+}
+
+// The jobs and tiles of one stream's calls.  out0: element of the stream's output 0, channel 0; out_stride: elements between its output channels
+// (mix: one output row, the job walks the file's channels)
+static inline void smix_qoa_jobs(const SMixQoaClass &K, unsigned cls, bool mix, const QoaSMixCall *calls, const SMixQoaCallPlan *plan, unsigned ncalls, uint64_t out0,
+                                 uint64_t out_stride, std::vector<SMixQoaJob> &jobs, std::vector<SMixQoaTile> &tiles) {
+    uint64_t outpos = 0;
+    for (unsigned k = 0; k < ncalls; k++) {
+        const uint64_t nout = plan[k].nout;
+        for (int c = 0; c < (mix ? 1 : K.channels) && nout; c++) {
+            SMixQoaJob j{};
+            j.src_off = calls[k].row0 + (uint64_t)c * calls[k].stride;
+            j.last_off = ~0ull;
+            if (k > 0) {   // chunk[i] = {[-1] = last[i][1], [0] = last[i][2]}  :3255
+                j.last_off = calls[k - 1].row0 + (uint64_t)c * calls[k - 1].stride + calls[k - 1].n - 1;
+                j.last_cstride = calls[k - 1].stride;
+            }
+            j.src_cstride = calls[k].stride;
+            j.out_off = out0 + (uint64_t)c * out_stride + outpos;
+            j.n = (int)calls[k].n; j.nout = (int)nout;
+            j.cls = cls; j.nch = mix ? K.channels : 1;
+            for (uint64_t o0 = 0; o0 < nout; o0 += (uint64_t)K.T) tiles.push_back(SMixQoaTile{(unsigned)jobs.size(), (unsigned)o0});
+            jobs.push_back(j);
+        }
+        outpos += nout;
+    }
+}
+
+}  // namespace aukit

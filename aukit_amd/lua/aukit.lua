@@ -22,7 +22,7 @@ typedef struct { int32_t codec, channels; double sample_rate; int32_t bit_depth,
 typedef struct { aukit_codec_desc desc; uint64_t payload_off, payload_len; int32_t wav_data_type, bit_depth; double length_seconds; } aukit_container;
 const char *aukit_last_error(void);
 int aukit_ctx_create(aukit_ctx **out, int device); void aukit_ctx_destroy(aukit_ctx *ctx);
-int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);
+int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);  /* 9: AUKIT_OPT_STREAM_MIXED_FRAME_CODECS (stream.many's `qoa`) */
 int aukit_parse_container(const uint8_t *bytes, uint64_t n, int kind, int stream, aukit_container *out);
 int aukit_batch_upload(aukit_ctx *, aukit_batch **, const uint8_t *bytes, const uint64_t *offsets, uint32_t n);
 int aukit_batch_info(const aukit_batch *, uint32_t *n, uint64_t *total); int aukit_batch_download(aukit_ctx *, const aukit_batch *, uint8_t *dst); void aukit_batch_free(aukit_batch *);
@@ -853,15 +853,19 @@ end
 -- aukit_stream_decode_mixed took the codec.  `adpcm` means IMA-ADPCM only; MS-ADPCM WAV files (format 2: the walk's descriptor carries block_align and the
 -- `fmt` chunk's coefficient list) are taken with {mono = ..., adpcm = ..., msadpcm = true}: for this one call the context is opted in
 -- (AUKIT_OPT_STREAM_MIXED_CODECS, option 6, bit 1 << AUKIT_CODEC_MSADPCM) and put back behind it, also where the call is refused.
+-- QOA files (magic "qoaf") are taken whole with the key `qoa` of the options table, {mono = ..., qoa = true}: the descriptor names the codec only, the
+-- pair is aukit.stream.qoa(file, mono)'s (length file_samples / rate), and for this one call the context is opted in under an option of its own
+-- (AUKIT_OPT_STREAM_MIXED_FRAME_CODECS, option 9, bit 1 << AUKIT_CODEC_QOA) and put back behind it, also where the call is refused.
 function aukit.stream.many(files, mono)
     expect(1, files, "table") expect(2, mono, "boolean", "table", "nil")
-    local adpcm, msadpcm = false, false
+    local adpcm, msadpcm, qoa = false, false, false
     if type(mono) == "table" then
-        for k in pairs(mono) do if k ~= "mono" and k ~= "adpcm" and k ~= "msadpcm" then error("bad argument #2 (unknown option " .. tostring(k) .. ")", 2) end end
-        if (mono.mono ~= nil and type(mono.mono) ~= "boolean") or (mono.adpcm ~= nil and type(mono.adpcm) ~= "boolean") or (mono.msadpcm ~= nil and type(mono.msadpcm) ~= "boolean") then
+        for k in pairs(mono) do if k ~= "mono" and k ~= "adpcm" and k ~= "msadpcm" and k ~= "qoa" then error("bad argument #2 (unknown option " .. tostring(k) .. ")", 2) end end
+        if (mono.mono ~= nil and type(mono.mono) ~= "boolean") or (mono.adpcm ~= nil and type(mono.adpcm) ~= "boolean") or (mono.msadpcm ~= nil and type(mono.msadpcm) ~= "boolean") or
+           (mono.qoa ~= nil and type(mono.qoa) ~= "boolean") then
             error("bad argument #2 (expected boolean options)", 2)
         end
-        mono, adpcm, msadpcm = mono.mono, mono.adpcm or false, mono.msadpcm or false
+        mono, adpcm, msadpcm, qoa = mono.mono, mono.adpcm or false, mono.msadpcm or false, mono.qoa or false
     end
     local n = #files
     local descs = ffi.new("aukit_codec_desc[?]", math.max(n, 1))
@@ -877,6 +881,10 @@ function aukit.stream.many(files, mono)
             descs[i - 1] = desc {codec = "dfpwm", channels = f[3] or 1, sampleRate = f[4] or 48000}
             parts[i] = f[1]
             lengths[i] = 0 / 0   -- NaN: aukit.stream.dfpwm's own figure stands (#data * 8 / sampleRate / channels)
+        elseif qoa and type(f) == "string" and f:sub(1, 4) == "qoaf" then
+            descs[i - 1] = desc {codec = "qoa"}   -- only the codec is read: channel count and rate are the file header's
+            parts[i] = f
+            lengths[i] = 0 / 0   -- NaN: aukit.stream.qoa's own figure stands (file_samples / sampleRate)
         else
             if type(f) ~= "string" then error("bad argument #1 (file " .. (i - 1) .. ": expected string)", 2) end
             local kind
@@ -905,9 +913,12 @@ function aukit.stream.many(files, mono)
     local o, ck = ffi.new("aukit_audio*[1]"), ffi.new("aukit_chunks*[1]")
     -- msadpcm: AUKIT_OPT_STREAM_MIXED_CODECS (6) with bit 1 << AUKIT_CODEC_MSADPCM for this one call; the shim's context sets no other bit, so 0 puts it back
     if msadpcm then check(C.aukit_ctx_set_option(ctx(), 6, 2 ^ CODEC.msadpcm)) end
+    -- qoa: AUKIT_OPT_STREAM_MIXED_FRAME_CODECS (9) with bit 1 << AUKIT_CODEC_QOA, likewise
+    if qoa then check(C.aukit_ctx_set_option(ctx(), 9, 2 ^ CODEC.qoa)) end
     local rc = C.aukit_stream_decode_mixed(ctx(), batch, descs, n, INTERP[aukit.defaultInterpolation], mono and 1 or 0, F64, o, ck)
     local words = rc ~= 0 and ffi.string(C.aukit_last_error()) or nil
     if msadpcm then C.aukit_ctx_set_option(ctx(), 6, 0) end
+    if qoa then C.aukit_ctx_set_option(ctx(), 9, 0) end
     if words then error(words, 2) end
     local whole = ffi.gc(o[0], C.aukit_audio_free)
     local cnt, mx = ffi.new("uint32_t[1]"), ffi.new("uint32_t[1]")

@@ -173,12 +173,19 @@ typedef enum {
                                    (aukit.stream.dfpwm's streams as members of a set, see that call); any other bit is AUKIT_E_UNSUPPORTED, the codec
                                    named (or "bit N"), and the context keeps the mask it had.  Options 5 and 6 keep their one bit each: a DFPWM bit
                                    there is still refused, and neither opens a set to anything.  With 0 every call answers exactly as before. */
-    AUKIT_OPT_STREAMSET_BLOCK_CODECS = 8 /* a second mask of aukit_streamset_open's, read by that call alone and only while it opens (an open set keeps
+    AUKIT_OPT_STREAMSET_BLOCK_CODECS = 8,/* a second mask of aukit_streamset_open's, read by that call alone and only while it opens (an open set keeps
                                    what it was opened with): a bit mask of 1 << codec, 0 by default, exactly one bit known, 1 << AUKIT_CODEC_MSADPCM
                                    (aukit.stream.msadpcm's streams as members of a set, see that call); any other bit is AUKIT_E_UNSUPPORTED, the codec
                                    named (or "bit N"), and the context keeps the mask it had.  A second option and not a second bit of option 7, which
                                    knows its one bit and refuses this one by name.  Options 5 and 6 are not needed for a set and open it to nothing;
                                    this option opens neither mixed call.  With 0 every call answers exactly as before. */
+    AUKIT_OPT_STREAM_MIXED_FRAME_CODECS = 9 /* a second mask of aukit_stream_decode_mixed's, the only call that reads it: a bit mask of 1 << codec, 0 by
+                                   default, exactly one bit known, 1 << AUKIT_CODEC_QOA (aukit.stream.qoa's files, see that call); any other bit is
+                                   AUKIT_E_UNSUPPORTED, the codec named (or "bit N"), and the context keeps the mask it had.  A second option and not a
+                                   second bit of option 6, which knows its one bit and refuses this one by name.  Options 5, 6, 7 and 8 do not open
+                                   the call to QOA; this option opens it to nothing else, and opens neither aukit_decode_resample_mixed (which takes
+                                   QOA without being asked) nor aukit_streamset_open (a stream set keeps refusing the codec).  With 0 every call
+                                   answers exactly as before. */
 } aukit_option;
 int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);
 /* counters of the most recent call that produced them (AUKIT_OPT_COLLECT_STATS = 1) */
@@ -365,7 +372,7 @@ int aukit_stream_decode_table(aukit_ctx *ctx, const double *values, const uint64
  * one channel it is ignored.  AUKIT_CODEC_PCM (every format stream.pcm takes, rates at or below 48 kHz), AUKIT_CODEC_G711 (integer rates),
  * AUKIT_CODEC_DFPWM (the descriptor's `channels` and `sample_rate`, rates above 48 kHz included; positions count from byte 0 whatever a stream
  * handle on the context carries; the same sample goes to every channel, and `mono` is ((0 + v) + v ...) / channels, :2485-2488) and
- * AUKIT_CODEC_ADPCM_WAV (IMA-ADPCM WAV blocks, below) and, on request, AUKIT_CODEC_MSADPCM (below) only, interpolation none / linear / cubic; anything else is AUKIT_E_UNSUPPORTED by name.  A batch with a DFPWM stream pays a pre-pass in front of the
+ * AUKIT_CODEC_ADPCM_WAV (IMA-ADPCM WAV blocks, below) and, on request, AUKIT_CODEC_MSADPCM and AUKIT_CODEC_QOA (both below) only, interpolation none / linear / cubic; anything else is AUKIT_E_UNSUPPORTED by name.  A batch with a DFPWM stream pays a pre-pass in front of the
  * one resample launch: every DFPWM stream is decoded to a flat int8 row in the context's scratch (the chunk-parallel decoder, one run per distinct
  * channel count, or a lane per stream where every stream is short) — element 0 a leading 0, then the samples in feed order (slices of
  * 6000 * channels + 1 bytes advanced by 6000 * channels, the slice's last byte decoded again as the next one's first), rows at multiples of 16
@@ -400,11 +407,29 @@ int aukit_stream_decode_table(aukit_ctx *ctx, const double *values, const uint64
  * channel: the first block's) is AUKIT_E_LUA, attempt to perform arithmetic on a nil value (local 'c1'), the lowest such stream named.  Two things
  * k_ms_mixed's int32 arithmetic cannot hold are AUKIT_E_UNSUPPORTED and point to aukit_stream_decode, which serves them: a delta of 2^21 or more
  * anywhere in the stream, and a coefficient pair with |c1| + |c2| >= 65536.
+ * AUKIT_CODEC_QOA is taken only on a context that asked for it, AUKIT_OPT_STREAM_MIXED_FRAME_CODECS with bit 1 << AUKIT_CODEC_QOA (without it the
+ * codec is refused by name in the words of before; with it the refusal of a further codec names AUKIT_CODEC_QOA under its option, behind option
+ * 6's clause where both are set).  Stream s is aukit.stream.qoa (data_s, mono) (:3202-3337): only `codec` of the descriptor is read, channel count
+ * (1 .. 64) and sample rate are the file header's, and the channel rule below reads that count.  Positions count from sample 0, whatever a stream
+ * handle on the context carries: call k's pos is (the samples of the calls before it) / rate, length_seconds is file_samples / rate, a call
+ * yields floor(#table * 48000 / rate) outputs (a chunk may be longer than 48000: two frames at 8000 Hz are 61440).  The samples are not floored:
+ * AUKIT_F64 holds the reference's doubles to the bar of aukit_stream_decode's warm-up tail, AUKIT_F32 that value rounded once.  `mono` is
+ * ((0 + s_1) + s_2 ...) / channels (:3326-3329).  A stream whose walk raises (the file ends inside a frame) has status[s] = AUKIT_E_LUA and the
+ * chunks of the calls before the raise.  A batch with such a stream pays two pre-passes with a wait each, both before `*out` and `*chunks` are
+ * touched: the frame headers are walked on the device, a lane per QOA stream, twice — the count pass, whose file headers are read back and
+ * refused as the stream's own call refuses them ("Not a QOA file", "data string too short", a channel count outside 1 .. 64), then, the scratch
+ * sized, the fill pass, whose call records are read back — and k_qoa_wave decodes every call's table to int8 rows in the context's scratch,
+ * behind the other rows, 16-byte aligned.  The tail — interpolation, the clamp on fractional positions, the recursive low-pass over the whole
+ * call, the mix-down — is one more launch behind the resample launch, k_smix_qoa_tail, for every (channels, rate) class of the batch at once; a
+ * batch of QOA files alone launches only it.  Three things that launch cannot hold are AUKIT_E_UNSUPPORTED by stream index and point to
+ * aukit_stream_decode, which serves them: a frame of more than 8192 samples, a rate so low that the low-pass's warm-up (ceil(41.86 / (2 pi rate /
+ * 96000)) outputs: 640 at 1000 Hz) exceeds one tile of 2048 outputs, and a rate so high that a tile's window exceeds 64 KiB of LDS.  Sinc is
+ * refused as for the whole call.
  * n_descs must be the batch's stream count; without
  * `mono` the descriptors must agree in channel count (AUKIT_E_ARG).  A stream whose own call would fail fails the whole call with that status
  * and message, the stream's index appended.  PCM data that ends inside a frame is served with the mix-down (the partial frame counts for
  * nothing) and refused without it whatever AUKIT_OPT_CHANNEL_LENS says: the uneven last chunk stays with aukit_stream_decode.  Every refusal
- * happens before anything is allocated or launched (the header scan, the MS-ADPCM pre-pass and their scratch excepted) and leaves `*out` and
+ * happens before anything is allocated or launched (the header scan, the MS-ADPCM pre-pass, the QOA walks and decoder and their scratch excepted) and leaves `*out` and
  * `*chunks` as they were. */
 int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs /* n */, uint32_t n_descs,
                               int interp, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks);
