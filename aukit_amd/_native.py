@@ -30,6 +30,7 @@ OPT_EXACT_MATH, OPT_STORE_X4, OPT_COLLECT_STATS, OPT_DFPWM_SPECULATE, OPT_CHANNE
 OPT_STREAM_MIXED_CODECS = 6   # aukit_stream_decode_mixed's mask of 1 << codec (only CODEC_MSADPCM is known); OPT_MIXED_CODECS is the decode call's
 OPT_STREAMSET_CODECS = 7      # aukit_streamset_open's mask of 1 << codec (only CODEC_DFPWM is known), read when a set is opened
 OPT_STREAMSET_BLOCK_CODECS = 8   # aukit_streamset_open's second mask (only CODEC_MSADPCM is known), read when a set is opened
+OPT_STREAMSET_FRAME_CODECS = 10   # aukit_streamset_open's third mask (only CODEC_QOA is known), read when a set is opened; options 7 and 8 refuse the bit by name
 OPT_STREAM_MIXED_FRAME_CODECS = 9   # aukit_stream_decode_mixed's second mask (only CODEC_QOA is known); options 5 to 8 do not open that call to QOA
 COUNTER_DFPWM_CHUNKS, COUNTER_DFPWM_CHUNKS_REDONE, COUNTER_FLAC_FUSED, COUNTER_TIER1_ERR_NANO, COUNTER_TIER1_OUTPUTS = 0, 1, 2, 3, 4
 COUNTER_DFPWM_RESPECULATED, COUNTER_DFPWM_HARD, COUNTER_RECURRENCE_F32, COUNTER_QOA_WAVE = 5, 6, 7, 8

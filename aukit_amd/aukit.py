@@ -554,7 +554,7 @@ def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm
     return descs, ranges, infos
 
 
-def _sniff_set(readers, dfpwm=False, msadpcm=False):
+def _sniff_set(readers, dfpwm=False, msadpcm=False, qoa=False):
     """aukit.stream.set's host half, up to the device: every reader is called once; its first piece, which holds the whole header (:2918), is
     sniffed by magic and walked by aukit_parse_container in its first-piece mode
     -> ([descriptor per reader], [the payload bytes behind the header per reader], [the container's length in seconds, NaN where the stream
@@ -566,10 +566,14 @@ def _sniff_set(readers, dfpwm=False, msadpcm=False):
     length is None, as in the reference's function mode (:2495).  Without it both are refused by index in the words of before.
     `msadpcm`: stream.set's request for MS-ADPCM members — a WAV reader whose payload is MS-ADPCM blocks (format 2) is taken too: the descriptor is
     the container walk's (blockAlign and the `fmt` chunk's coefficient list), the payload what follows the header in the first piece, the length NaN
-    (aukit.stream.msadpcm's own figure stands, as for IMA-ADPCM blocks).  Without it such a reader is refused by index in the words of before, whatever `dfpwm` says."""
+    (aukit.stream.msadpcm's own figure stands, as for IMA-ADPCM blocks).  Without it such a reader is refused by index in the words of before, whatever `dfpwm` says.
+    `qoa`: stream.set's request for QOA members — a reader whose first piece starts with the magic "qoaf" is taken too.  That piece holds the twelve
+    header bytes (the first-piece rule, :2918; :3241 peeks at bytes 8..11): the descriptor carries the channel count (byte 8) and the rate (bytes 9..11)
+    — a set's QOA member is described, unlike a mixed call's stream —, the whole piece is payload (there is no container around it) and the length is
+    file_samples / rate (:3336).  Without it such a reader is refused by index in the words of before."""
     _expect(1, readers, "table")
     takes = "stream.set takes " + ("PCM, G.711 and DFPWM" if dfpwm else "PCM and G.711") + " payloads and " + ("IMA-ADPCM and MS-ADPCM" if msadpcm else "IMA-ADPCM") + \
-        " blocks (the other codecs keep their own streams)"
+        " blocks" + (" and QOA files" if qoa else "") + " (the other codecs keep their own streams)"
     served = (N.CODEC_PCM, N.CODEC_G711, N.CODEC_ADPCM_WAV) + ((N.CODEC_DFPWM,) if dfpwm else ()) + ((N.CODEC_MSADPCM,) if msadpcm else ())
     descs, firsts, lengths = [], [], []
     for i, fn in enumerate(readers):
@@ -596,6 +600,14 @@ def _sniff_set(readers, dfpwm=False, msadpcm=False):
             raise LuaError(f"bad argument #1 (reader {i}: expected string from the first call)")
         first = bytes(first)
         kind = detect(first[:12])[0]
+        if kind == "qoa" and qoa:
+            if len(first) < 12:
+                raise LuaError(f"reader {i}: the first piece of a QOA stream holds its 12 header bytes")
+            ch, rate = first[8], int.from_bytes(first[9:12], "big")
+            descs.append(B.make_desc(N.CODEC_QOA, ch, rate))
+            firsts.append(first)
+            lengths.append(int.from_bytes(first[4:8], "big") / rate if rate else math.nan)
+            continue
         if kind == "qoa":
             raise LuaError(f"reader {i}: qoa payload: {takes}")
         if kind not in _MAGIC_KIND:
@@ -945,7 +957,7 @@ class _StreamNS:
         rows = out.download()
         return [self._chunk_iter(out, ck, None if math.isnan(lengths[i]) else lengths[i], d.codec == N.CODEC_G711, i, rows) for i, d in enumerate(descs)]
 
-    def set(self, readers, mono=None, dfpwm=None, msadpcm=None):
+    def set(self, readers, mono=None, dfpwm=None, msadpcm=None, qoa=None):
         """aukit.stream.wav / aiff / au (fn, mono) for a LIST of reader functions — live sources, each a WAV / AIFF / AU stream of PCM, G.711 or
         IMA-ADPCM blocks with its own rate, format and channel count — served by ONE aukit_streamset: a list of (iterator, length) pairs in
         input order, each iterator handing out what the reader's own factory hands out.  Every reader's first piece holds the whole header
@@ -961,28 +973,37 @@ class _StreamNS:
         MS-ADPCM WAV readers (format 2: aukit.stream.wav's dispatch to aukit.stream.msadpcm with the stream's blockAlign and coefficient list) are
         taken with `msadpcm=True`, or the key "msadpcm" of the options table: for the one open the context is opted in to MS-ADPCM members
         (AUKIT_OPT_STREAMSET_BLOCK_CODECS, an option of its own) and put back as it was behind it, also where the open is refused.  Without it such a
-        reader is refused by index, as before."""
+        reader is refused by index, as before.
+        QOA readers (a first piece that starts with "qoaf" and holds the twelve header bytes) are taken with `qoa=True`, or the key "qoa" of the
+        options table: the pair is what aukit.stream.qoa(fn, mono) returns (length file_samples / sampleRate), and for the one open the context is
+        opted in to QOA members (AUKIT_OPT_STREAMSET_FRAME_CODECS, a third option) and put back as it was behind it, also where the open is
+        refused.  Without it such a reader is refused by index, as before."""
         if isinstance(mono, dict):
-            if set(mono) - {"mono", "dfpwm", "msadpcm"}:
-                raise LuaError("bad argument #2 (unknown option " + sorted(set(mono) - {"mono", "dfpwm", "msadpcm"})[0] + ")")
-            mono, dfpwm, msadpcm = mono.get("mono"), mono.get("dfpwm", dfpwm), mono.get("msadpcm", msadpcm)
+            if set(mono) - {"mono", "dfpwm", "msadpcm", "qoa"}:
+                raise LuaError("bad argument #2 (unknown option " + sorted(set(mono) - {"mono", "dfpwm", "msadpcm", "qoa"})[0] + ")")
+            mono, dfpwm, msadpcm, qoa = mono.get("mono"), mono.get("dfpwm", dfpwm), mono.get("msadpcm", msadpcm), mono.get("qoa", qoa)
         _expect(2, mono, "boolean", "nil")
         _expect(3, dfpwm, "boolean", "nil")
         _expect(4, msadpcm, "boolean", "nil")
-        descs, firsts, lengths = _sniff_set(readers, dfpwm=bool(dfpwm), msadpcm=bool(msadpcm))
+        _expect(5, qoa, "boolean", "nil")
+        descs, firsts, lengths = _sniff_set(readers, dfpwm=bool(dfpwm), msadpcm=bool(msadpcm), qoa=bool(qoa))
         ctx = context()
-        was, was_block = ctx.option(N.OPT_STREAMSET_CODECS), ctx.option(N.OPT_STREAMSET_BLOCK_CODECS)
+        was, was_block, was_frame = ctx.option(N.OPT_STREAMSET_CODECS), ctx.option(N.OPT_STREAMSET_BLOCK_CODECS), ctx.option(N.OPT_STREAMSET_FRAME_CODECS)
         try:
             if dfpwm:
                 _wrap(ctx.set_option, N.OPT_STREAMSET_CODECS, was | 1 << N.CODEC_DFPWM)
             if msadpcm:
                 _wrap(ctx.set_option, N.OPT_STREAMSET_BLOCK_CODECS, was_block | 1 << N.CODEC_MSADPCM)
+            if qoa:
+                _wrap(ctx.set_option, N.OPT_STREAMSET_FRAME_CODECS, was_frame | 1 << N.CODEC_QOA)
             st = _wrap(B.StreamSet, ctx, descs, _interp(defaultInterpolation, 0), bool(mono), N.F64)
         finally:
             if dfpwm:
                 ctx.set_option(N.OPT_STREAMSET_CODECS, was)
             if msadpcm:
                 ctx.set_option(N.OPT_STREAMSET_BLOCK_CODECS, was_block)
+            if qoa:
+                ctx.set_option(N.OPT_STREAMSET_FRAME_CODECS, was_frame)
         readers = [r[0] if isinstance(r, (list, tuple)) else r for r in readers]
         n = len(readers)
         done = [False] * n

@@ -715,7 +715,13 @@ class StreamSet:
     CODEC_MSADPCM members (aukit.stream.msadpcm: make_desc with block_align and, where the file has its own, coefficients) join under an option of
     their own, ctx.set_option(N.OPT_STREAMSET_BLOCK_CODECS, 1 << N.CODEC_MSADPCM) — option 8, read by the open alone; OPT_STREAM_MIXED_CODECS is
     not needed.  A member whose blocks carry a predictor index beyond the coefficient table, or reach a delta of 2^21 or more, ends alone: its
-    earlier chunks, then E_LUA / E_UNSUPPORTED from `next`.  A chunk of theirs may exceed `cap` too (48060 for blockAlign 22 at 8 kHz, mono)."""
+    earlier chunks, then E_LUA / E_UNSUPPORTED from `next`.  A chunk of theirs may exceed `cap` too (48060 for blockAlign 22 at 8 kHz, mono).
+    CODEC_QOA members (aukit.stream.qoa) join under a third option, ctx.set_option(N.OPT_STREAMSET_FRAME_CODECS, 1 << N.CODEC_QOA) — option 10,
+    read by the open alone; OPT_STREAM_MIXED_FRAME_CODECS is not needed.  Unlike the mixed calls' QOA descriptor, a member's carries the file
+    header's channel count and rate: make_desc(N.CODEC_QOA, channels, sample_rate).  The member is fed the file from its first byte; the last
+    two samples of a call and the position are carried across compactions, so the rest starts at the next call.  A member whose header is no
+    QOA header or disagrees with the descriptor, one with a frame of more than 8192 samples and one finished inside a frame end alone.  A pump
+    that decodes such members waits two more times (the frame walk's read-backs).  A chunk of theirs may exceed `cap` (61440 at 8 kHz)."""
 
     def __init__(self, ctx, descs, interp, mono=False, dtype=None, cap=48000):
         self.ctx = ctx

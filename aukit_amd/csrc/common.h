@@ -54,6 +54,7 @@ struct aukit_ctx {
     unsigned stream_mixed_codecs = 0;  // AUKIT_OPT_STREAM_MIXED_CODECS: the same for aukit_stream_decode_mixed, which reads this mask and no other
     unsigned stream_mixed_frame_codecs = 0;   // AUKIT_OPT_STREAM_MIXED_FRAME_CODECS: that call's second mask (1 << AUKIT_CODEC_QOA), read by the public call alone
     unsigned streamset_codecs = 0;     // AUKIT_OPT_STREAMSET_CODECS: bit 1 << codec lets aukit_streamset_open, which reads this mask and no other, take that codec
+    unsigned streamset_fcodecs = 0;   // AUKIT_OPT_STREAMSET_FRAME_CODECS: the same call's third mask (1 << AUKIT_CODEC_QOA), read while a set opens
     unsigned streamset_block_codecs = 0;   // AUKIT_OPT_STREAMSET_BLOCK_CODECS: the same call's second mask (1 << AUKIT_CODEC_MSADPCM), read while a set opens
     bool fast_store_x4 = true;  // AUKIT_OPT_STORE_X4: LDS-transposed 16-byte stores in the fast kernels
     std::string last_kernel;

@@ -53,6 +53,13 @@ struct SMixCarry {
     // and its row's element 0 (`last`, aukit.lua:2470) is df_state[3]: what aukit_ctx::sb_dfpwm is to the single-descriptor call
     int df_back, df_on;
     int df_state[6];
+    // an AUKIT_CODEC_QOA stream (zeros otherwise; the public call takes no carry): the rest is the file's first eight bytes and whole frames from some
+    // iterator call's start on.  samples_dropped — the sum of sample_pos (:3333) over the calls dropped in front: file_pos starts there;
+    // qoa_last_on — the rest's first call reads qoa_last[2 c] and qoa_last[2 c + 1] as channel c's table indices -1 and 0 (`last`, :3255, :3334);
+    // qoa_back — the samples every call boundary of this decode hands on, and where its calls end, come back (SMixDfBack)
+    uint64_t samples_dropped;
+    int qoa_back, qoa_last_on;
+    signed char qoa_last[2 * AUKIT_MAX_PLANAR_CHANNELS];
 };
 // where the pre-pass left the states of the streams that asked (df_back): entry first[s] + k of the device table `dev` (six ints each; scratch of the
 // call, valid until the context's next call) is stream s's decoder in front of call k of this decode — after the slices of calls 0 .. k - 1,
@@ -62,11 +69,21 @@ struct SMixDfBack {
     size_t entries = 0;
     std::vector<uint64_t> first;   // per stream of the batch (~0: none)
     std::vector<uint32_t> calls;
+    // the QOA streams that asked (qoa_back): pair qoa_first[s] + (k - 1) channels + c of the device table qoa_dev (two int8 each, scratch of the call as
+    // `dev` is) holds what channel c of the call behind boundary k reads as its table indices -1 and 0, k = 1 .. qoa_calls[s]: the last two samples of
+    // call k - 1 of this decode (k_smix_qoa_last, stream_mixed_qoa.hip).  qoa_end / qoa_samples, from qoa_call0[s] on: per call the byte behind it,
+    // counted from the rest's first, and its sample_pos
+    const signed char *qoa_dev = nullptr;
+    size_t qoa_pairs = 0;
+    std::vector<uint64_t> qoa_first, qoa_call0;   // per stream of the batch (~0: none)
+    std::vector<uint32_t> qoa_calls;
+    std::vector<uint32_t> qoa_end, qoa_samples;
 };
 int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
                               aukit_chunks **chunks, const SMixCarry *carry /* n_descs, or null */, SMixDfBack *back = nullptr /* where a carry sets df_back */,
-                              unsigned block_codecs = 0 /* 1 << AUKIT_CODEC_MSADPCM: the caller takes such streams, whatever the context's masks say */,
-                              unsigned frame_codecs = 0 /* 1 << AUKIT_CODEC_QOA: the public call's AUKIT_OPT_STREAM_MIXED_FRAME_CODECS; a stream set hands in 0 */);
+                              unsigned block_codecs = 0 /* 1 << AUKIT_CODEC_MSADPCM: the caller takes such streams, whatever the context's masks say; with a carry (a stream
+                              set, which keeps ONE mask of what it was opened with) also 1 << AUKIT_CODEC_QOA, read as that bit of the next mask */,
+                              unsigned frame_codecs = 0 /* 1 << AUKIT_CODEC_QOA: the public call's AUKIT_OPT_STREAM_MIXED_FRAME_CODECS */);
 // what the stream's own aukit_stream_decode call refuses of a descriptor and a byte count, and the uneven last chunk (stream_mixed.hip)
 int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono);
 

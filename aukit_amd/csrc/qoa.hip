@@ -41,7 +41,7 @@ __constant__ int c_qoa_deq[16][8] = {
 // A call is walked dry first (its row stride depends on its last frame), then again to emit.
 struct QoaWalkOut { unsigned char head[12]; unsigned ncalls, raised, big, pad; unsigned long long njobs, rows_total, L; };
 struct QoaFillIn { unsigned long long job_first, call_first, row_base, stride; };
-struct QoaCallRec { unsigned long long row0; unsigned stride, n, sample_pos, pad; };
+struct QoaCallRec { unsigned long long row0; unsigned stride, n, sample_pos, end; };   // end: the byte behind the call, from the stream's first (a call is below 4 GiB)
 static_assert(sizeof(QoaWalkOut) == 56 && sizeof(QoaFillIn) == 32 && sizeof(QoaCallRec) == 24, "walk records");
 
 struct QoaCallWalk { unsigned long long end_pos, n, sample_pos; unsigned nframes, lastnz; bool raised, big; };   // lastnz: the last frame that holds samples, counted from 1 (0: none)
@@ -98,21 +98,27 @@ static AUKIT_DEV QoaCallWalk qoa_walk_call(const unsigned char *h, unsigned long
 
 // IDX: the walk's streams are a LIST of the batch's (`list[s]`: the mixed-library call, whose other streams are not QOA and are not walked); the words
 // of both passes are per list entry, the jobs' frame offsets the batch's.
-template <bool FILL, bool IDX = false>
+// SET (mode 1, a stream set's batch): list entry s is the REST of a longer stream and set[s] says where it lies, how many bytes are its own and what
+// the file header's channel count and rate were (QoaSetIn, stream_mixed_qoa.h) — `off` and `list` are not read, nor bytes 8..11 as a header; an
+// entry of fewer than eight bytes is not walked.  The call records carry the byte behind each call (QoaCallRec::end)
+template <bool FILL, bool IDX = false, bool SET = false>
 __global__ __launch_bounds__(64) void k_qoa_walk(const unsigned char *src, const unsigned long long *off, unsigned n, int mode, QoaWalkOut *wo,
-                                                const QoaFillIn *fin, QoaJob *jobs, QoaCallRec *calls, const unsigned *list) {
+                                                const QoaFillIn *fin, QoaJob *jobs, QoaCallRec *calls, const unsigned *list, const QoaSetIn *set = nullptr) {
     const unsigned s = blockIdx.x * 64 + threadIdx.x;
     if (s >= n) return;
-    const unsigned g = IDX ? list[s] : s;   // the stream of the batch
-    const unsigned char *h = src + off[g];
-    const unsigned long long nb = off[g + 1] - off[g];
+    unsigned long long base, nb;
+    if constexpr (SET) { base = set[s].off; nb = set[s].nbytes; }
+    else { const unsigned g = IDX ? list[s] : s; base = off[g]; nb = off[g + 1] - off[g]; }   // the stream of the batch
+    const unsigned char *h = src + base;
     QoaWalkOut o;
     for (int i = 0; i < 12; i++) o.head[i] = (unsigned long long)i < nb ? h[i] : 0;
     o.ncalls = 0; o.raised = 0; o.big = 0; o.pad = 0; o.njobs = 0; o.rows_total = 0; o.L = 0;
-    if (nb >= 12 && h[0] == 'q' && h[1] == 'o' && h[2] == 'a' && h[3] == 'f') {
+    if (nb >= (SET ? 8 : 12) && h[0] == 'q' && h[1] == 'o' && h[2] == 'a' && h[3] == 'f') {
         const double file_samples = (double)((unsigned)h[4] << 24 | (unsigned)h[5] << 16 | (unsigned)h[6] << 8 | h[7]);
-        const int fc = h[8];
-        const unsigned fr = (unsigned)h[9] << 16 | (unsigned)h[10] << 8 | h[11];
+        int fc;
+        unsigned fr;
+        if constexpr (SET) { fc = set[s].channels; fr = set[s].rate; }
+        else { fc = h[8]; fr = (unsigned)h[9] << 16 | (unsigned)h[10] << 8 | h[11]; }
         if (fc >= 1 && fc <= AUKIT_MAX_PLANAR_CHANNELS) {
             unsigned long long pos = 8, jat = 0, rat = 0;
             if (FILL) { jat = fin[s].job_first; rat = fin[s].row_base; }
@@ -129,14 +135,14 @@ __global__ __launch_bounds__(64) void k_qoa_walk(const unsigned char *src, const
                         const bool lastf = ++k == nfr;
                         for (int c = 0; c < fc; c++) {
                             QoaJob j;
-                            j.frame_off = off[g] + fpos; j.out_off = rat + (unsigned long long)c * stride + sp;
+                            j.frame_off = base + fpos; j.out_off = rat + (unsigned long long)c * stride + sp;
                             j.c = c; j.channels = fc; j.samples = samples;
                             j.emit = lastf ? ((samples + 19) / 20) * 20 : samples;   // Q15: the ≤19-sample tail survives only after the last frame of a table that holds samples
                             jobs[jat++] = j;
                         }
                     });
                     QoaCallRec cr;
-                    cr.row0 = rat; cr.stride = (unsigned)stride; cr.n = (unsigned)w.n; cr.sample_pos = (unsigned)w.sample_pos; cr.pad = 0;
+                    cr.row0 = rat; cr.stride = (unsigned)stride; cr.n = (unsigned)w.n; cr.sample_pos = (unsigned)w.sample_pos; cr.end = (unsigned)w.end_pos;
                     calls[fin[s].call_first + o.ncalls] = cr;
                     rat += stride * (unsigned long long)fc;
                 }
@@ -298,19 +304,28 @@ struct QoaStreamInfo { int channels; double rate, file_samples; bool raised, big
 // (wb: where the walks keep their words — tmp_buf3, or the call's set of ctx->qoa_set when they run on the look-ahead stream: stream_qoa)
 // (list: the streams to walk, where they are not the whole batch — its device copy goes behind the walks' words and serves the fill pass too; a
 // refusal then leaves the refused entry's position in *bad)
+// (set: the list's entries are a stream set's rests, QoaSetIn each — the device copy goes behind the list's and serves the fill pass too; byte count,
+// channel count and rate are the table's)
+static size_t qoa_walk_set_at(uint32_t n) { return (size_t)round_up((size_t)n * (sizeof(QoaWalkOut) + sizeof(QoaFillIn) + sizeof(unsigned)), 8); }
 static int qoa_walk_count(aukit_ctx *ctx, const aukit_batch *in, int mode, std::vector<QoaStreamInfo> &S, DevBuf *wb = nullptr, const std::vector<uint32_t> *list = nullptr,
-                          uint32_t *bad = nullptr) {
+                          uint32_t *bad = nullptr, const std::vector<QoaSetIn> *set = nullptr) {
     const uint32_t n = list ? (uint32_t)list->size() : in->n;
     S.assign(n, QoaStreamInfo{});
     if (!n) return AUKIT_OK;
     DevBuf &W = wb ? *wb : ctx_scratch3(ctx);
-    int rc = W.ensure((size_t)n * (sizeof(QoaWalkOut) + sizeof(QoaFillIn) + (list ? sizeof(unsigned) : 0)) + 64);
+    int rc = W.ensure(set ? qoa_walk_set_at(n) + (size_t)n * sizeof(QoaSetIn) + 64 : (size_t)n * (sizeof(QoaWalkOut) + sizeof(QoaFillIn) + (list ? sizeof(unsigned) : 0)) + 64);
     if (rc) return rc;
     QoaWalkOut *dwo = reinterpret_cast<QoaWalkOut *>(W.p);
     const unsigned long long *doff = reinterpret_cast<const unsigned long long *>(in->d_off);
     if (list) {
         unsigned *dlist = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(W.p) + (size_t)n * (sizeof(QoaWalkOut) + sizeof(QoaFillIn)));
         if ((rc = h2d_table(ctx, dlist, list->data(), (size_t)n * sizeof(unsigned)))) return rc;
+        if (set) {
+            QoaSetIn *dset = reinterpret_cast<QoaSetIn *>(reinterpret_cast<char *>(W.p) + qoa_walk_set_at(n));
+            if ((rc = h2d_table(ctx, dset, set->data(), (size_t)n * sizeof(QoaSetIn)))) return rc;
+            hipLaunchKernelGGL((k_qoa_walk<false, true, true>), dim3((n + 63) / 64), dim3(64), 0, ctx->stream, in->data(), static_cast<const unsigned long long *>(nullptr), n, mode, dwo,
+                               static_cast<const QoaFillIn *>(nullptr), static_cast<QoaJob *>(nullptr), static_cast<QoaCallRec *>(nullptr), dlist, dset);
+        } else
         hipLaunchKernelGGL((k_qoa_walk<false, true>), dim3((n + 63) / 64), dim3(64), 0, ctx->stream, in->data(), doff, n, mode, dwo, static_cast<const QoaFillIn *>(nullptr),
                            static_cast<QoaJob *>(nullptr), static_cast<QoaCallRec *>(nullptr), dlist);
     } else
@@ -329,17 +344,17 @@ static int qoa_walk_count(aukit_ctx *ctx, const aukit_batch *in, int mode, std::
     uint64_t jat = 0, cat = 0, rat = 0;
     for (uint32_t s = 0; s < n; s++) {
         const uint32_t g = list ? (*list)[s] : s;
-        const uint64_t nb = in->off[g + 1] - in->off[g];
+        const uint64_t nb = set ? (*set)[s].nbytes : in->off[g + 1] - in->off[g];
         const unsigned char *h = wo[s].head;
         if (bad) *bad = s;
         // aukit.qoa: (">c4I4"):unpack / (">BI3"):unpack on a short string raise; stream.qoa: assert(read(8), ...) / assert(peek(4), ...)
         if (nb < 8) return fail(AUKIT_E_LUA, mode == 0 ? "data string too short" : "Not a QOA file");
         if (memcmp(h, "qoaf", 4) != 0) return fail(AUKIT_E_ARG, "Not a QOA file");
-        if (nb < 12) return fail(AUKIT_E_LUA, nb == 8 && mode == 1 ? "Not a QOA file" : "data string too short");
+        if (nb < 12 && !set) return fail(AUKIT_E_LUA, nb == 8 && mode == 1 ? "Not a QOA file" : "data string too short");
         QoaStreamInfo &q = S[s];
         q.file_samples = (double)((uint32_t)h[4] << 24 | (uint32_t)h[5] << 16 | (uint32_t)h[6] << 8 | h[7]);
-        q.channels = h[8];
-        q.rate = (double)((uint32_t)h[9] << 16 | (uint32_t)h[10] << 8 | h[11]);
+        q.channels = set ? (*set)[s].channels : h[8];
+        q.rate = set ? (double)(*set)[s].rate : (double)((uint32_t)h[9] << 16 | (uint32_t)h[10] << 8 | h[11]);
         if (q.channels < 1 || q.channels > AUKIT_MAX_PLANAR_CHANNELS) return fail(AUKIT_E_UNSUPPORTED, "QOA channel count %d", q.channels);
         q.raised = wo[s].raised != 0; q.big = wo[s].big != 0; q.ncalls = wo[s].ncalls;
         q.njobs = wo[s].njobs; q.L = wo[s].L;
@@ -353,7 +368,7 @@ static int qoa_walk_count(aukit_ctx *ctx, const aukit_batch *in, int mode, std::
 
 // pass 2: the decode jobs into `djobs` (device), the call records to the host (stream mode: want_calls)
 static int qoa_walk_fill(aukit_ctx *ctx, const aukit_batch *in, int mode, const std::vector<QoaStreamInfo> &S, QoaJob *djobs, uint64_t ncalls, std::vector<QoaCallRec> *calls, DevBuf *wb = nullptr, DevBuf *cb = nullptr,
-                         bool listed = false) {
+                         bool listed = false, const std::vector<QoaSetIn> *set = nullptr) {
     const uint32_t n = (uint32_t)S.size();   // (the batch's streams, or the list qoa_walk_count left behind the words)
     std::vector<QoaFillIn> fin(n);
     for (uint32_t s = 0; s < n; s++) fin[s] = QoaFillIn{S[s].job_first, S[s].call_first, S[s].row_base, S[s].stride};
@@ -363,7 +378,12 @@ static int qoa_walk_fill(aukit_ctx *ctx, const aukit_batch *in, int mode, const 
     int rc = CB.ensure((size_t)std::max<uint64_t>(ncalls, 1) * sizeof(QoaCallRec) + 64);
     if (rc) return rc;
     QoaCallRec *dcalls = reinterpret_cast<QoaCallRec *>(CB.p);
-    if (listed)
+    if (set) {   // (copied again: the caller may have emptied an entry whose calls it does not take)
+        QoaSetIn *dset = reinterpret_cast<QoaSetIn *>(reinterpret_cast<char *>((wb ? *wb : ctx_scratch3(ctx)).p) + qoa_walk_set_at(n));
+        { int hrc = h2d_table(ctx, dset, set->data(), (size_t)n * sizeof(QoaSetIn)); if (hrc) return hrc; }
+        hipLaunchKernelGGL((k_qoa_walk<true, true, true>), dim3((n + 63) / 64), dim3(64), 0, ctx->stream, in->data(), static_cast<const unsigned long long *>(nullptr), n, mode,
+                           static_cast<QoaWalkOut *>(nullptr), dfin, djobs, dcalls, static_cast<const unsigned *>(nullptr), dset);
+    } else if (listed)
         hipLaunchKernelGGL((k_qoa_walk<true, true>), dim3((n + 63) / 64), dim3(64), 0, ctx->stream, in->data(), reinterpret_cast<const unsigned long long *>(in->d_off), n, mode,
                            static_cast<QoaWalkOut *>(nullptr), dfin, djobs, dcalls, reinterpret_cast<const unsigned *>(dfin + n));
     else
@@ -461,15 +481,18 @@ size_t qoa_mixed_job_bytes(uint64_t njobs) { return (size_t)std::max<uint64_t>(n
 //     channel c at row0 + c * stride, stride = round_up(n + 2, 16) —, the read-back of the call records, then k_qoa_wave<true> into `rows`.
 //     `djobs`: room for the jobs the count pass reported (qoa_mixed_job_bytes).
 // The jobs are stream_qoa's: what no job writes is what that call leaves there too.
-int qoa_smix_count(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<QoaSMixStream> &Q, uint32_t *bad) {
+// set (null: the public call): the list's streams are a stream set's rests (k_qoa_walk's set mode) — both passes take the table, the fill pass again
+// because the caller empties the entries whose calls it does not plan (the count pass's figures for such an entry are then zeros in Q as well)
+int qoa_smix_count(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<QoaSMixStream> &Q, uint32_t *bad, const std::vector<QoaSetIn> *set) {
     std::vector<QoaStreamInfo> S;
-    const int rc = qoa_walk_count(ctx, in, 1, S, nullptr, &list, bad);
+    const int rc = qoa_walk_count(ctx, in, 1, S, nullptr, &list, bad, set);
     if (rc) return rc;
     Q.resize(S.size());
     for (size_t s = 0; s < S.size(); s++) Q[s] = QoaSMixStream{S[s].channels, S[s].rate, S[s].file_samples, S[s].raised, S[s].big, S[s].ncalls, S[s].njobs, S[s].rows_total};
     return AUKIT_OK;
 }
-int qoa_smix_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<QoaSMixStream> &Q, signed char *rows, void *djobs, uint64_t src_bytes, std::vector<QoaSMixCall> &calls) {
+int qoa_smix_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<QoaSMixStream> &Q, signed char *rows, void *djobs, uint64_t src_bytes, std::vector<QoaSMixCall> &calls,
+                    const std::vector<QoaSetIn> *set) {
     std::vector<QoaStreamInfo> S(Q.size());
     uint64_t jat = 0, cat = 0, rat = 0;
     for (size_t s = 0; s < Q.size(); s++) {
@@ -480,10 +503,10 @@ int qoa_smix_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<Qoa
         jat += q.njobs; cat += q.ncalls; rat += q.rows_total;
     }
     std::vector<QoaCallRec> recs;
-    int rc = qoa_walk_fill(ctx, in, 1, S, reinterpret_cast<QoaJob *>(djobs), cat, &recs, nullptr, nullptr, true);
+    int rc = qoa_walk_fill(ctx, in, 1, S, reinterpret_cast<QoaJob *>(djobs), cat, &recs, nullptr, nullptr, true, set);
     if (rc) return rc;
     calls.resize(recs.size());
-    for (size_t i = 0; i < recs.size(); i++) calls[i] = QoaSMixCall{recs[i].row0, recs[i].stride, recs[i].n, recs[i].sample_pos};
+    for (size_t i = 0; i < recs.size(); i++) calls[i] = QoaSMixCall{recs[i].row0, recs[i].stride, recs[i].n, recs[i].sample_pos, recs[i].end};
     ctx->counters[AUKIT_COUNTER_QOA_WAVE] = 1;
     if (!jat) return AUKIT_OK;
     if ((rc = ctx_begin_kernel(ctx))) return rc;

@@ -69,6 +69,13 @@
 // SMIX_CLS_QOA: k_stream_mixed gets no tile for them, and a batch of QOA streams alone launches no k_stream_mixed.  The host waits twice for the
 // device on their account — the two read-backs, both before `*out` and `*chunks` are touched —, a second kind of wait beside the IMA scan's and
 // the MS-ADPCM verdict's, paid only by a batch that has a QOA stream.
+// A QOA stream may be the REST of a longer one too (a stream set's member under AUKIT_OPT_STREAMSET_FRAME_CODECS; stream_decode_mixed_carry, never the
+// public call): the file's first eight bytes, then whole frames from some iterator call's start on.  Its byte count is the carry's, its channel count
+// and rate the descriptor's — the walks run in their set mode on a table of those (QoaSetIn), never on bytes 8..11 of the rest —, file_pos starts at
+// the carry's samples_dropped, and its first call reads the carry's two samples per channel as table indices -1 and 0: they are copied into the int8
+// rows behind the last call's and the first call's jobs point there.  For a stream that asks (qoa_back) k_smix_qoa_last copies the last two samples of
+// every call into a device table, handed back with the calls' ends and sample counts as the DFPWM states are (SMixDfBack).  A frame of more than 8192
+// samples is then the stream's own verdict: no chunk, AUKIT_E_UNSUPPORTED as its status, no refusal of the batch.
 //
 // The host half reads as the call's phases: smix_validate, smix_classes, the IMA header scan, one planner per codec (plan_pcm, plan_g711, plan_dfpwm,
 // plan_ima, plan_ms: they fill an SMixPlan and touch neither the context nor HIP), the scratch layout, the MS-ADPCM pre-pass and its verdict, the two
@@ -87,8 +94,10 @@
 namespace aukit {
 
 // qoa.hip's stream-mode walks and stream_mixed_qoa.hip's launch
-int qoa_smix_count(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<QoaSMixStream> &Q, uint32_t *bad);
-int qoa_smix_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<QoaSMixStream> &Q, signed char *rows, void *djobs, uint64_t src_bytes, std::vector<QoaSMixCall> &calls);
+int qoa_smix_count(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<QoaSMixStream> &Q, uint32_t *bad, const std::vector<QoaSetIn> *set);
+int qoa_smix_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<QoaSMixStream> &Q, signed char *rows, void *djobs, uint64_t src_bytes, std::vector<QoaSMixCall> &calls,
+                    const std::vector<QoaSetIn> *set);
+int smix_qoa_last_launch(aukit_ctx *ctx, const signed char *rows, const unsigned long long *d_at, unsigned n, signed char *d_pairs);
 size_t qoa_mixed_job_bytes(uint64_t njobs);
 int smix_qoa_tail_launch(aukit_ctx *ctx, const std::vector<SMixQoaClass> &classes, const std::vector<SMixQoaJob> &jobs, const std::vector<SMixQoaTile> &tiles, size_t lds,
                          const signed char *rows, void *out, int interp, int dtype, uint64_t algorithmic_bytes);
@@ -588,6 +597,19 @@ int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) {
             return fail(AUKIT_E_UNSUPPORTED, "stream too long");
         return AUKIT_OK;
     }
+    if (d->codec == AUKIT_CODEC_QOA) {  // a stream set's member (the mixed call reads a file's header instead): the descriptor carries the header's figures
+        if (d->channels < 1 || d->channels > AUKIT_MAX_PLANAR_CHANNELS) return fail(AUKIT_E_UNSUPPORTED, "QOA channel count %d", d->channels);
+        if (!(d->sample_rate >= 1 && d->sample_rate <= 16777215) || d->sample_rate != std::floor(d->sample_rate))
+            return fail(AUKIT_E_ARG, "QOA sample rate %g: a file header holds 1 to 16777215 Hz", d->sample_rate);
+        SMixQoaClass K;
+        size_t lds = 0;
+        const int why = smix_qoa_class_shape(d->channels, d->sample_rate, &K, &lds);   // what smix_qoa_classes refuses of a file, in its words
+        if (why == 1)
+            return fail(AUKIT_E_UNSUPPORTED, "QOA at %g Hz: the low-pass needs a warm-up beyond one tile of %d outputs: aukit_stream_open takes this stream", d->sample_rate, SMIX_QOA_TMAX);
+        if (why)
+            return fail(AUKIT_E_UNSUPPORTED, "QOA at %g Hz: a tile's window needs more than %d KiB of LDS: aukit_stream_open takes this stream", d->sample_rate, (int)(SMIX_QOA_LDS / 1024));
+        return AUKIT_OK;
+    }
     if (d->codec == AUKIT_CODEC_PCM) {
         int rc;
         if ((rc = check_pcm_desc(d))) return rc;
@@ -626,6 +648,12 @@ struct SMixQoa {
     uint64_t rows = 0, njobs = 0, ncalls = 0, src = 0;   // int8 elements of all rows; decode jobs; iterator calls; source bytes
     std::vector<QoaSMixCall> calls;       // stream after stream (qoa_smix_decode)
     std::vector<std::vector<SMixQoaCallPlan>> plan;   // per entry of `list`
+    // a stream set's batch (a carry): the walks' set-mode table, per entry of `list`; the rows' bytes behind the calls' that hold the samples carried
+    // into the rests' first calls (two per channel; first_last: per entry, ~0 where nothing is carried); the pairs handed back (SMixDfBack)
+    std::vector<QoaSetIn> set;
+    std::vector<signed char> last_in;
+    std::vector<uint64_t> first_last;
+    uint64_t back_pairs = 0;
 };
 
 static int smix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
@@ -661,12 +689,24 @@ static int smix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_code
     }
     // QOA: only `codec` of the descriptor is read.  The count pass of the device walk on these streams, and the header read-back: what stream_qoa
     // refuses of a header is refused first, with its words.  It writes ctx->tmp_buf3 and nothing of `*out`
+    // With a carry (a stream set's batch) a stream is the rest of a longer one: its byte count is the carry's, its channel count and rate the
+    // descriptor's — the set checked them against the file's first twelve bytes — and a frame of more than 8192 samples is the stream's own verdict:
+    // it gets no chunk (its entry of the table is emptied for the fill pass) and AUKIT_E_UNSUPPORTED as its status
     if (!QS.list.empty()) {
-        if (carry) return fail(AUKIT_E_UNSUPPORTED, "stream %u: a stream set takes no AUKIT_CODEC_QOA member", QS.list[0]);
+        if (carry)
+            for (uint32_t s : QS.list) {
+                if (carry[s].nbytes > in->off[s + 1] - in->off[s]) return fail(AUKIT_E_ARG, "stream %u: the carry names more bytes than the batch holds", s);
+                if (descs[s].channels < 1 || descs[s].channels > AUKIT_MAX_PLANAR_CHANNELS || !(descs[s].sample_rate >= 1 && descs[s].sample_rate < 16777216.0))
+                    return fail(AUKIT_E_ARG, "stream %u: a QOA member's descriptor carries the file header's channel count and rate", s);
+                QS.set.push_back(QoaSetIn{in->off[s], carry[s].nbytes, descs[s].channels, (unsigned)descs[s].sample_rate});
+            }
         AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
         uint32_t bad = 0;
-        if ((rc = qoa_smix_count(ctx, in, QS.list, QS.Q, &bad))) return fail_for_stream(rc, QS.list[bad]);
-        for (size_t i = 0; i < QS.list.size(); i++) ch_of[QS.list[i]] = QS.Q[i].channels;   // the file header's  :3241
+        if ((rc = qoa_smix_count(ctx, in, QS.list, QS.Q, &bad, carry ? &QS.set : nullptr))) return fail_for_stream(rc, QS.list[bad]);
+        for (size_t i = 0; i < QS.list.size(); i++) {
+            ch_of[QS.list[i]] = QS.Q[i].channels;   // the file header's  :3241
+            if (carry && QS.Q[i].big) { QS.Q[i].raised = false; QS.Q[i].ncalls = 0; QS.Q[i].njobs = 0; QS.Q[i].rows_total = 0; QS.set[i].nbytes = 0; }
+        }
     }
     if ((rc = mixed_check_channels(in->n, mono, [&](uint32_t s) { return ch_of[s]; }))) return rc;
     for (uint32_t s = 0; s < in->n; s++) {
@@ -773,6 +813,7 @@ static int smix_qoa_classes(SMixQoa &QS) {
     for (size_t i = 0; i < QS.list.size(); i++) {
         const QoaSMixStream &q = QS.Q[i];
         const unsigned s = QS.list[i];
+        if (q.big && !QS.set.empty()) { QS.cls_of[i] = 0; continue; }   // (a stream set's member: its own verdict, no call, no class)
         if (q.big) return fail(AUKIT_E_UNSUPPORTED, "QOA frame of more than 8192 samples: aukit_stream_decode takes this file (stream %u)", s);
         bool fresh;
         QS.cls_of[i] = index.of({q.channels, q.rate}, &fresh);
@@ -1007,7 +1048,7 @@ static void smix_plan(const aukit_batch *in, const aukit_codec_desc *descs, cons
     for (uint32_t s = 0; s < in->n; s++) {
         const aukit_codec_desc &d = descs[s];
         const uint64_t nb = smix_nbytes(in, carry, s);
-        const SMixCarry cy = carry ? carry[s] : SMixCarry{0, 0, nb, 0, 0, {0, 0, 0, 0, 0, 0}};
+        const SMixCarry cy = carry ? carry[s] : SMixCarry{0, 0, nb, 0, 0, {0, 0, 0, 0, 0, 0}, 0, 0, 0, {0}};
         pl.in_bytes += nb;
         SMixSeg g;
         memset(&g, 0, sizeof g);
@@ -1025,7 +1066,7 @@ static void smix_plan(const aukit_batch *in, const aukit_codec_desc *descs, cons
 // stream_qoa's plan (qoa.hip) for every QOA stream, from the call records: the chunk table's numbers per call (smix_qoa_plan_stream), the length
 // file_samples / rate (:3336), AUKIT_E_LUA where the walk raised — the chunks of the calls before it are delivered —, and the class's longest job.
 // The calls join the plan as segments in the stream's place, so that the chunk table and the audio's rows are laid out as for every other kind
-static int plan_qoa(SMixPlan &pl, SMixQoa &QS) {
+static int plan_qoa(SMixPlan &pl, SMixQoa &QS, const SMixCarry *carry) {
     QS.plan.resize(QS.list.size());
     std::vector<SMixSeg> segs;
     std::vector<double> cpos;
@@ -1033,9 +1074,11 @@ static int plan_qoa(SMixPlan &pl, SMixQoa &QS) {
     for (uint32_t s = 0; s < pl.ck->n; s++) {
         if (qi < QS.list.size() && QS.list[qi] == s) {
             const QoaSMixStream &q = QS.Q[qi];
-            if (!smix_qoa_plan_stream(q.rate, QS.calls.data() + call0, q.ncalls, QS.plan[qi])) return fail_for_stream(fail(AUKIT_E_UNSUPPORTED, "stream too long"), s);
+            if (!smix_qoa_plan_stream(q.rate, QS.calls.data() + call0, q.ncalls, QS.plan[qi], carry ? carry[s].samples_dropped : 0))
+                return fail_for_stream(fail(AUKIT_E_UNSUPPORTED, "stream too long"), s);
             pl.ck->length_seconds[s] = q.file_samples / q.rate;
             if (q.raised) pl.ck->status[s] = AUKIT_E_LUA;   // assert(read(8), "Invalid QOA data") / a short unpack
+            if (q.big) pl.ck->status[s] = AUKIT_E_UNSUPPORTED;   // (a stream set's member only: the public call was refused above)
             for (const SMixQoaCallPlan &c : QS.plan[qi]) {
                 SMixSeg g;
                 memset(&g, 0, sizeof g);
@@ -1084,9 +1127,10 @@ static void smix_chunk_table(SMixPlan &pl, int C_out) {
 // behind the IMA scratch k_ms_mixed's int16 rows (a row per (stream, channel) at a multiple of 16 bytes, 64 bytes to spare behind the last: the
 // tiles' 16-byte loads rely on them), its unit table, its coefficient sets and its two flag words — for a stream set with, right behind them, the two
 // fault words of every stream of the batch (one read-back takes both)
-struct SMixScratch { size_t df_tab_at = 0, df_states_at = 0, ima_at = 0, ima_tab_at = 0, ms_at = 0, ms_unit_at = 0, ms_coef_at = 0, ms_flag_at = 0, qoa_at = 0, qoa_jobs_at = 0, size = 0; };
+struct SMixScratch { size_t df_tab_at = 0, df_states_at = 0, ima_at = 0, ima_tab_at = 0, ms_at = 0, ms_unit_at = 0, ms_coef_at = 0, ms_flag_at = 0, qoa_at = 0, qoa_jobs_at = 0, qoa_back_at = 0, qoa_back_tab_at = 0, size = 0; };
 // (behind everything else, so that a batch without a QOA stream lays its scratch out as before: the QOA streams' int8 rows, 16-byte aligned as every
-// call's row is, and the decoder's job table)
+// call's row is — behind the last call's the samples carried into the rests of a stream set's batch, two bytes per channel —, the decoder's job table and,
+// where a set asked for them, the pairs handed back and the table of where k_smix_qoa_last finds them)
 static SMixScratch smix_scratch(const SMixPlan &pl, bool ms_per_stream, const SMixQoa &QS) {
     Carve carve;
     SMixScratch L;
@@ -1099,7 +1143,8 @@ static SMixScratch smix_scratch(const SMixPlan &pl, bool ms_per_stream, const SM
         L.ms_coef_at = carve.take(pl.ms.coefs.size() * sizeof(int), 0);
         L.ms_flag_at = carve.take(8 + (ms_per_stream ? (size_t)pl.ck->n * 8 : 0), 56);
     }
-    if (!QS.list.empty()) { L.qoa_at = carve.take((size_t)QS.rows); L.qoa_jobs_at = carve.take(qoa_mixed_job_bytes(QS.njobs), 0); }
+    if (!QS.list.empty()) { L.qoa_at = carve.take((size_t)QS.rows + QS.last_in.size()); L.qoa_jobs_at = carve.take(qoa_mixed_job_bytes(QS.njobs), 0); }
+    if (QS.back_pairs) { L.qoa_back_at = carve.take((size_t)QS.back_pairs * 2, 0); L.qoa_back_tab_at = carve.take((size_t)QS.back_pairs * 8, 0); }
     L.size = carve.end;
     return L;
 }
@@ -1287,9 +1332,11 @@ static int smix_qoa_tail(aukit_ctx *ctx, SMixQoa &QS, const SMixScratch &L, cons
     uint64_t out_elems = 0;
     for (size_t i = 0; i < QS.list.size(); i++) {
         const uint32_t s = QS.list[i];
+        if (!QS.Q[i].ncalls) continue;   // (no call, perhaps no class: a stream set's member with a verdict of its own)
         const SMixQoaClass &K = QS.classes[QS.cls_of[i]];
         const bool mix = mono && K.channels > 1;
-        smix_qoa_jobs(K, QS.cls_of[i], mix, QS.calls.data() + call0, QS.plan[i].data(), QS.Q[i].ncalls, a->row_off[s], a->row_stride[s], jobs, tiles);
+        smix_qoa_jobs(K, QS.cls_of[i], mix, QS.calls.data() + call0, QS.plan[i].data(), QS.Q[i].ncalls, a->row_off[s], a->row_stride[s], jobs, tiles,
+                      QS.first_last.empty() ? ~0ull : QS.first_last[i]);
         for (const SMixQoaCallPlan &c : QS.plan[i]) out_elems += c.nout * (uint64_t)(mix || mono ? 1 : K.channels);
         call0 += QS.Q[i].ncalls;
     }
@@ -1297,8 +1344,56 @@ static int smix_qoa_tail(aukit_ctx *ctx, SMixQoa &QS, const SMixScratch &L, cons
     if (tiles.size() > 0xFFFFFFF0ull || jobs.size() > 0xFFFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
     for (size_t c = 0; c < QS.classes.size(); c++)
         QS.classes[c].exact = exact_div_verified(ctx, QS.classes[c].ratio, std::max<uint64_t>(QS.max_nout[c] + 2, 1ull << 17)) ? 1 : 0;
-    const signed char *rows = reinterpret_cast<const signed char *>(ctx->tmp_buf.p) + L.qoa_at;
+    signed char *rows = reinterpret_cast<signed char *>(ctx->tmp_buf.p) + L.qoa_at;
+    int rc;
+    if (!QS.last_in.empty() && (rc = h2d_table(ctx, rows + QS.rows, QS.last_in.data(), QS.last_in.size()))) return rc;   // the carried samples, in front of the launch
     return smix_qoa_tail_launch(ctx, QS.classes, jobs, tiles, QS.lds, rows, a->dev, interp, dtype, QS.rows + out_elems * dtype_size(dtype));
+}
+
+// a stream set's batch: what the rests' first calls read as their table indices -1 and 0 (the carries' samples, behind the calls' rows), and how many
+// pairs go back — one per channel and call of every stream that asked
+static void smix_qoa_carried(SMixQoa &QS, const SMixCarry *carry) {
+    QS.first_last.assign(QS.list.size(), ~0ull);
+    for (size_t i = 0; i < QS.list.size(); i++) {
+        const SMixCarry &cy = carry[QS.list[i]];
+        const int C = QS.Q[i].channels;
+        if (cy.qoa_last_on && QS.Q[i].ncalls) {
+            QS.first_last[i] = QS.rows + QS.last_in.size();
+            QS.last_in.insert(QS.last_in.end(), cy.qoa_last, cy.qoa_last + 2 * C);
+        }
+        if (cy.qoa_back) QS.back_pairs += (uint64_t)QS.Q[i].ncalls * (uint64_t)C;
+    }
+}
+// ... and behind the decoder (k_qoa_wave<true> has been enqueued: the rows are complete in stream order): the pairs of every boundary, the calls' ends
+// and sample counts, handed back.  One small launch, nothing is awaited: the set copies the table out in front of its pump's wait
+static int smix_qoa_hand_back(aukit_ctx *ctx, const SMixQoa &QS, const SMixScratch &L, const SMixCarry *carry, uint32_t n, SMixDfBack *back) {
+    back->qoa_first.assign(n, ~0ull); back->qoa_call0.assign(n, ~0ull); back->qoa_calls.assign(n, 0);
+    back->qoa_end.clear(); back->qoa_samples.clear();
+    back->qoa_dev = nullptr; back->qoa_pairs = 0;
+    std::vector<unsigned long long> at;
+    size_t call0 = 0;
+    for (size_t i = 0; i < QS.list.size(); i++) {
+        const uint32_t s = QS.list[i], nc = QS.Q[i].ncalls;
+        if (carry[s].qoa_back) {
+            back->qoa_first[s] = at.size(); back->qoa_call0[s] = back->qoa_end.size(); back->qoa_calls[s] = nc;
+            for (uint32_t k = 0; k < nc; k++) {
+                const QoaSMixCall &c = QS.calls[call0 + k];
+                back->qoa_end.push_back(c.end); back->qoa_samples.push_back(c.sample_pos);
+                for (int ch = 0; ch < QS.Q[i].channels; ch++) at.push_back(smix_qoa_boundary_at(c, ch));
+            }
+        }
+        call0 += nc;
+    }
+    if (at.empty()) return AUKIT_OK;
+    char *const S = reinterpret_cast<char *>(ctx->tmp_buf.p);
+    int rc;
+    if ((rc = h2d_table(ctx, S + L.qoa_back_tab_at, at.data(), at.size() * 8))) return rc;
+    if ((rc = smix_qoa_last_launch(ctx, reinterpret_cast<const signed char *>(S + L.qoa_at), reinterpret_cast<const unsigned long long *>(S + L.qoa_back_tab_at), (unsigned)at.size(),
+                                   reinterpret_cast<signed char *>(S + L.qoa_back_at))))
+        return rc;
+    back->qoa_dev = reinterpret_cast<const signed char *>(S + L.qoa_back_at);
+    back->qoa_pairs = at.size();
+    return AUKIT_OK;
 }
 
 int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
@@ -1308,12 +1403,19 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
     int rc;
     SMixQoa QS;
     std::vector<int> ch_of;
+    if (carry) {   // a stream set's one mask: the QOA bit is the frame mask's
+        frame_codecs |= block_codecs & (1u << AUKIT_CODEC_QOA);
+        block_codecs &= ~(1u << AUKIT_CODEC_QOA);
+    }
     if ((rc = smix_validate(ctx, in, descs, n_descs, interp, mono, dtype, out, carry, block_codecs, frame_codecs, QS, ch_of))) return rc;
     const uint32_t n = in->n;
     const bool qoa = !QS.list.empty();
     SMixClasses T;
     if ((rc = smix_classes(descs, n, interp, mono, T))) return rc;
     if (qoa && (rc = smix_qoa_classes(QS))) return rc;
+    if (qoa && carry) smix_qoa_carried(QS, carry);
+    if (QS.back_pairs > 0x7FFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
+    if (QS.back_pairs && !back) return fail(AUKIT_E_ARG, "null argument");
     AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
     smix_exact_division(ctx, T.classes);
     std::vector<unsigned> ima_bad;
@@ -1333,9 +1435,9 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
     if ((pl.df_n || pl.ima_jobs || ms || qoa) && (rc = mixed_scratch_ensure(ctx, *out, L.size))) return rc;
     if (qoa) {   // the fill pass, the read-back of the call records, the decoder; then the streams' calls join the plan
         char *const S = reinterpret_cast<char *>(ctx->tmp_buf.p);
-        for (uint32_t s : QS.list) QS.src += in->off[s + 1] - in->off[s];
-        if ((rc = qoa_smix_decode(ctx, in, QS.Q, reinterpret_cast<signed char *>(S + L.qoa_at), S + L.qoa_jobs_at, QS.src, QS.calls))) return rc;
-        if ((rc = plan_qoa(pl, QS))) return rc;
+        for (uint32_t s : QS.list) QS.src += smix_nbytes(in, carry, s);
+        if ((rc = qoa_smix_decode(ctx, in, QS.Q, reinterpret_cast<signed char *>(S + L.qoa_at), S + L.qoa_jobs_at, QS.src, QS.calls, carry ? &QS.set : nullptr))) return rc;
+        if ((rc = plan_qoa(pl, QS, carry))) return rc;
         smix_chunk_table(pl, C_out);
     }
     std::vector<int> ms_faults;
@@ -1353,6 +1455,7 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
         back->dev = pl.df_states ? reinterpret_cast<const int *>(reinterpret_cast<const char *>(ctx->tmp_buf.p) + L.df_states_at) : nullptr;
         back->entries = (size_t)pl.df_states;
         back->first = pl.df_first; back->calls = pl.df_calls;
+        if (qoa && carry && (rc = smix_qoa_hand_back(ctx, QS, L, carry, n, back))) return rc;
     }
     if (nt) {
         if (pl.ima_jobs && (rc = smix_ima_prepass(ctx, in, pl, L))) return rc;

@@ -26,7 +26,13 @@ struct QoaSMixCall {
     unsigned stride;           // elements between the call's channel rows (a multiple of 16, at least n + 2)
     unsigned n;                // #chunk[1]
     unsigned sample_pos;       // what the call adds to file_pos  :3333
+    unsigned end = 0;          // the byte behind the call's last consumed byte, counted from the stream's first (a stream set cuts its rests there)
 };
+// a stream set's member in the walks' set mode (k_qoa_walk<.., .., true>): the REST of a longer stream — the file's first eight bytes, then whole
+// frames from some call's start on.  Where it lies in the batch's data and how many bytes are its own (the set's arena has slot starts only), and the
+// channel count and rate of the descriptor: bytes 8..11 of a rest are whatever follows the dropped calls, not the file header's
+struct QoaSetIn { unsigned long long off, nbytes; int channels; unsigned rate; };
+static_assert(sizeof(QoaSetIn) == 24, "QoaSetIn layout");
 // one QOA stream as the count pass reports it
 struct QoaSMixStream {
     int channels; double rate, file_samples;
@@ -64,6 +70,27 @@ struct SMixQoaParams {
     void *out;
 };
 
+// Where a stream set finds, behind a decode, the two samples the call after boundary k would read as its table indices -1 and 0 (k = 1 .. calls: the
+// last two of call k - 1's table): the rows' element of index 0, channel c's `stride` further on.  k_smix_qoa_last copies them out
+static inline uint64_t smix_qoa_boundary_at(const QoaSMixCall &before, int c) { return before.row0 + (uint64_t)c * before.stride + before.n - 1; }
+
+// A stream set's compaction of a QOA member behind a decode of its rest (streamset.hip): the first `shift` calls of the decode go.  end[k] / samples[k]:
+// the byte behind call k, counted from the rest's first, and its sample_pos (the walk's records); resident: the rest's bytes.  The rest keeps the eight
+// bytes in front of end[shift - 1] — the next repack writes the file's first eight over them — so `bytes` = end[shift - 1] - 8 leave; `samples` joins
+// the member's samples_dropped; the pairs of boundary `shift` are pair first_pair + (shift - 1) channels and the channels - 1 behind it.
+// -> false: nothing is dropped (no call, no record of that boundary, or an end the rest does not hold)
+struct SMixQoaDrop { uint64_t bytes, samples, pair; };
+static inline bool smix_qoa_drop(const uint32_t *end, const uint32_t *samples, uint32_t ncalls, uint64_t shift, uint64_t resident, int channels, uint64_t first_pair, SMixQoaDrop *d) {
+    if (!shift || shift > ncalls) return false;
+    const uint64_t cut = end[shift - 1];
+    if (cut <= 8 || cut > resident) return false;
+    d->bytes = cut - 8;
+    d->samples = 0;
+    for (uint64_t k = 0; k < shift; k++) d->samples += samples[k];
+    d->pair = first_pair + (shift - 1) * (uint64_t)channels;
+    return true;
+}
+
 // The class of (channels, rate): stream_tail.hip's tail_shape for int8 rows, with the tile height the class's own.  A state W outputs back still shows
 // as a^W of it, a = exp(-decay): below 1e-16 of a sample of magnitude 128 after W = ceil((37 + ln 128) / decay) outputs.
 // -> 0; 1: the warm-up does not fit one tile (very low rates); 2: the window exceeds the LDS budget (very high rates)
@@ -95,10 +122,11 @@ static inline int smix_qoa_class_shape(int channels, double rate, SMixQoaClass *
 // The chunk table of one stream from its call records, exactly as stream_qoa computes it: n_out = floor(n * ratio), 0 below 1 (:3312, :3317);
 // pos = file_pos / rate with file_pos advanced by the call's sample_pos (:3332-3333), counted from sample 0.
 // -> false: a call of more than 0x7FFFFFF0 outputs ("stream too long")
+// samples_dropped: the rest of a longer stream (a stream set's member) — what the calls dropped in front of it added to file_pos
 struct SMixQoaCallPlan { uint64_t nout; double pos; };
-static inline bool smix_qoa_plan_stream(double rate, const QoaSMixCall *calls, unsigned ncalls, std::vector<SMixQoaCallPlan> &plan) {
+static inline bool smix_qoa_plan_stream(double rate, const QoaSMixCall *calls, unsigned ncalls, std::vector<SMixQoaCallPlan> &plan, uint64_t samples_dropped = 0) {
     const double ratio = 48000 / rate;
-    double file_pos = 0;
+    double file_pos = (double)samples_dropped;
     plan.clear();
     for (unsigned k = 0; k < ncalls; k++) {
         const double newlen = (double)calls[k].n * ratio;
@@ -110,9 +138,10 @@ static inline bool smix_qoa_plan_stream(double rate, const QoaSMixCall *calls, u
 }
 
 // The jobs and tiles of one stream's calls.  out0: element of the stream's output 0, channel 0; out_stride: elements between its output channels
-// (mix: one output row, the job walks the file's channels)
+// (mix: one output row, the job walks the file's channels).  first_last: the rest of a longer stream — where the rows hold the two samples carried
+// into its first call, channel c's at first_last + 2 c (table index -1) and first_last + 2 c + 1 (index 0); ~0: both are 0, the stream's start
 static inline void smix_qoa_jobs(const SMixQoaClass &K, unsigned cls, bool mix, const QoaSMixCall *calls, const SMixQoaCallPlan *plan, unsigned ncalls, uint64_t out0,
-                                 uint64_t out_stride, std::vector<SMixQoaJob> &jobs, std::vector<SMixQoaTile> &tiles) {
+                                 uint64_t out_stride, std::vector<SMixQoaJob> &jobs, std::vector<SMixQoaTile> &tiles, uint64_t first_last = ~0ull) {
     uint64_t outpos = 0;
     for (unsigned k = 0; k < ncalls; k++) {
         const uint64_t nout = plan[k].nout;
@@ -123,6 +152,9 @@ static inline void smix_qoa_jobs(const SMixQoaClass &K, unsigned cls, bool mix, 
             if (k > 0) {   // chunk[i] = {[-1] = last[i][1], [0] = last[i][2]}  :3255
                 j.last_off = calls[k - 1].row0 + (uint64_t)c * calls[k - 1].stride + calls[k - 1].n - 1;
                 j.last_cstride = calls[k - 1].stride;
+            } else if (first_last != ~0ull) {
+                j.last_off = first_last + 2 * (uint64_t)c + 1;
+                j.last_cstride = 2;
             }
             j.src_cstride = calls[k].stride;
             j.out_off = out0 + (uint64_t)c * out_stride + outpos;

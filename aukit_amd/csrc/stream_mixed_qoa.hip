@@ -141,4 +141,24 @@ int smix_qoa_tail_launch(aukit_ctx *ctx, const std::vector<SMixQoaClass> &classe
     return ctx_end_kernel(ctx, names[interp], algorithmic_bytes);
 }
 
+// k_smix_qoa_last: for a stream set, behind a decode — pair i of `pairs` is what the call after a boundary reads as its table indices -1 and 0: the
+// rows' elements at[i] - 1 and at[i], the last two samples of the call in front of the boundary (`last[j] = {chunk[#chunk - 1], chunk[#chunk]}`, :3334).
+// The host made at[i] from a call record (smix_qoa_boundary_at: at least 19, inside the call's row).  Plain vector loads and stores only
+__global__ __launch_bounds__(256) void k_smix_qoa_last(const signed char *__restrict__ rows, const unsigned long long *__restrict__ at, unsigned n, signed char *__restrict__ pairs) {
+    const unsigned i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long a = at[i];
+    pairs[2 * (size_t)i] = rows[a - 1];
+    pairs[2 * (size_t)i + 1] = rows[a];
+}
+
+int smix_qoa_last_launch(aukit_ctx *ctx, const signed char *rows, const unsigned long long *d_at, unsigned n, signed char *d_pairs) {
+    int rc;
+    if (!n) return AUKIT_OK;
+    if ((rc = ctx_begin_kernel(ctx))) return rc;
+    hipLaunchKernelGGL(k_smix_qoa_last, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, rows, d_at, n, d_pairs);
+    AUKIT_HIP_CHECK(hipGetLastError());
+    return ctx_end_kernel(ctx, "k_smix_qoa_last", (uint64_t)n * 12);
+}
+
 }  // namespace aukit

@@ -39,10 +39,26 @@
 // is known only on the device: the engine's pre-pass (k_ms_mixed<true>) records per stream which fault it has, the set's batch gets that stream back
 // with no chunk and the fault as its status, and the member ends alone at that pump, behind the chunks of earlier pumps, with the single call's words.
 // The pre-pass's flag read-back is a second wait in a pump that decodes such members (as the header scan is for stream.adpcm members).
+//
+// stream.qoa members (AUKIT_CODEC_QOA; only a set opened on a context that set AUKIT_OPT_STREAMSET_FRAME_CODECS has them — the set keeps that mask and
+// hands it to the engine, so AUKIT_OPT_STREAM_MIXED_FRAME_CODECS is not needed): the descriptor carries the file header's channel count and rate
+// (bytes 8 and 9..11), which the open checks as the mixed call checks a file's.  Every frame carries its own LMS state and an iterator call takes
+// whole frames until it has a second of samples, so all that crosses a call boundary are the last two samples of a chunk per channel (`last`, :3334)
+// and file_pos.  The member carries both (restart lead 0, where the handle restarts a call early): the engine reports, for every call boundary of a
+// decode, the two samples the next call reads (k_smix_qoa_last into a device table, copied to pinned memory in front of the pump's wait, as the DFPWM
+// states are) and the byte behind every call; the compaction plan drops `shift` decided calls up to that byte — frames of any size, no whole-frame
+// condition — and keeps the eight bytes in front of it, which the next repack overwrites with the FILE's first eight (magic and sample count, kept
+// on the host with bytes 8..11 as head12: an eight-byte staging segment, the rest's own segment starting eight bytes in, as head7).  Channels and
+// rate of a rest are the descriptor's, never its bytes 8..11.  The first twelve bytes are checked on the host before the member's first batch (a wrong
+// magic, a header that disagrees with the descriptor: the member ends alone); an unfinished member is decoded with all its resident bytes — a prefix
+// that ends inside a frame just yields the calls before it — and a frame of more than 8192 samples is the member's own verdict from the walk.
+// The walk's two read-backs (count, call records) are two more waits in a pump that decodes such members, as the header scan is one for
+// stream.adpcm members and the flag read-back one for stream.msadpcm members.
 #include <algorithm>
 #include <deque>
 #include "mixed_plan.h"
 #include "ms_geom.h"
+#include "stream_mixed_qoa.h"
 
 namespace aukit {
 
@@ -135,17 +151,28 @@ struct SSetMember {
     // stream.msadpcm, one channel: the stream's first seven bytes as fed (the header every block is read from) — the handle's head7
     unsigned char head7[7] = {0, 0, 0, 0, 0, 0, 0};
     uint32_t head7_n = 0;
+    // stream.qoa: the stream's first twelve bytes as fed (the file header: its first eight go in front of every rest) and whether they were checked;
+    // what the dropped calls added to file_pos; the last two samples per channel of the call in front of the rest, valid once calls were dropped
+    unsigned char head12[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t head12_n = 0;
+    bool qoa_checked = false, qoa_last_on = false;
+    uint64_t samples_dropped = 0;
+    signed char qoa_last[2 * AUKIT_MAX_PLANAR_CHANNELS] = {0};
     std::deque<SSetChunk> q;
 };
 // a compaction planned in front of the pump's wait: member s's next state is entry `entry` of the states the pump downloads
 struct SSetDfFix { uint32_t s; size_t entry; };
+// ... and a stream.qoa member's next two samples per channel are pairs `pair` .. `pair` + channels - 1 of the pairs the pump downloads
+struct SSetQoaFix { uint32_t s; size_t pair; };
 
 }  // namespace aukit
 
 struct aukit_streamset {
     aukit_ctx *ctx = nullptr;
     int interp = 0, mono = 0, dtype = AUKIT_F64;
-    unsigned block_codecs = 0;   // AUKIT_OPT_STREAMSET_BLOCK_CODECS as it was when the set was opened
+    // the codecs the set takes on request, as the context's masks were when it was opened: AUKIT_OPT_STREAMSET_BLOCK_CODECS's bit (1 << AUKIT_CODEC_MSADPCM)
+    // and AUKIT_OPT_STREAMSET_FRAME_CODECS's (1 << AUKIT_CODEC_QOA) — distinct bits, so one mask holds both, and the engine gets this one mask
+    unsigned block_codecs = 0;
     std::vector<aukit::SSetMember> m;
     // pinned host staging of what was fed since the last pump, and its device copy
     unsigned char *stage = nullptr;
@@ -167,6 +194,10 @@ struct aukit_streamset {
     int *df_host = nullptr;
     size_t df_host_cap = 0;
     std::vector<aukit::SSetDfFix> df_fix;
+    // the same for the QOA boundary pairs
+    signed char *qoa_host = nullptr;
+    size_t qoa_host_cap = 0;
+    std::vector<aukit::SSetQoaFix> qoa_fix;
 };
 
 namespace aukit {
@@ -191,6 +222,12 @@ static void sset_apply_states(aukit_streamset *S) {
         M.df_on = true;
     }
     S->df_fix.clear();
+    for (const SSetQoaFix &f : S->qoa_fix) {
+        SSetMember &M = S->m[f.s];
+        for (int i = 0; i < 2 * M.desc.channels; i++) M.qoa_last[i] = S->qoa_host[f.pair * 2 + i];
+        M.qoa_last_on = true;
+    }
+    S->qoa_fix.clear();
 }
 
 // restart_rule's PCM / G.711 / IMA / DFPWM / MS-ADPCM cases (stream_handle.hip): the bytes of a whole iterator call, and whether the rest starts one call early
@@ -204,6 +241,8 @@ static void sset_restart(SSetMember &M, int interp) {
         M.call_bytes = (uint64_t)d.sample_rate * C;
     } else if (d.codec == AUKIT_CODEC_DFPWM) {
         M.call_bytes = 6000 * C;   // lead 0: the rest starts at the next call, with the decoder's state and its last output carried (df_state)
+    } else if (d.codec == AUKIT_CODEC_QOA) {
+        M.call_bytes = 0;   // lead 0, and no constant: the walk reports where every call ends
     } else if (d.codec == AUKIT_CODEC_MSADPCM) {
         const double spb = C == 2 ? (double)(d.block_align - 14) : (double)(d.block_align - 7) * 2;   // :2617 / :2682 (MsGeom's)
         M.call_bytes = (uint64_t)std::ceil(d.sample_rate / spb) * (uint64_t)d.block_align;            // lead 0: every block decodes alone
@@ -239,6 +278,22 @@ static int sset_finished_refusal(const SSetMember &M, uint64_t nb, bool mono) {
     return check_smix_stream(&d, nb, mono);
 }
 
+// A stream.qoa member's first bytes against its descriptor, before its first batch.  Fewer than twelve (the member is finished): the status and words
+// aukit_stream_decode gives those bytes (qoa_walk_count, qoa.hip)
+static int sset_qoa_header(const SSetMember &M) {
+    const unsigned char *h = M.head12;
+    const uint64_t nb = M.resident;
+    if (nb < 8) return fail(AUKIT_E_LUA, "Not a QOA file");                              // assert(read(8), ...)
+    if (nb < 12 && memcmp(h, "qoaf", 4) != 0) return fail(AUKIT_E_ARG, "Not a QOA file");
+    if (nb < 12) return fail(AUKIT_E_LUA, nb == 8 ? "Not a QOA file" : "data string too short");   // assert(peek(4), ...) / a short unpack
+    if (memcmp(h, "qoaf", 4) != 0) return fail(AUKIT_E_LUA, "Not a QOA file");
+    const int fc = h[8];
+    const unsigned fr = (unsigned)h[9] << 16 | (unsigned)h[10] << 8 | h[11];
+    if (fc != M.desc.channels || (double)fr != M.desc.sample_rate)
+        return fail(AUKIT_E_ARG, "the QOA file header names %d channels at %u Hz, the member's descriptor %d channels at %g Hz", fc, fr, M.desc.channels, M.desc.sample_rate);
+    return AUKIT_OK;
+}
+
 struct SSetJob { uint32_t s; uint64_t usable; bool all_decided, ends; int end_status; std::string end_msg; };
 
 static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
@@ -262,15 +317,20 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
         if (M.resident) {
             // a one-channel stream.msadpcm member that drops bytes: the first bytes of its new slot are the STREAM's first seven, from the host by way
             // of the staging buffer; the rest's own segment starts behind them (the same relation modulo 16, and no byte is written twice)
+            // a stream.qoa member likewise: the FILE's first eight bytes (head12's) over the last eight of the dropped frames
             uint64_t head = 0;
-            if (M.drop && M.desc.codec == AUKIT_CODEC_MSADPCM && M.desc.channels == 1 && M.head7_n == 7) {
-                head = std::min<uint64_t>(M.resident, 7);
+            const unsigned char *hsrc = nullptr;
+            size_t hn = 0;
+            if (M.drop && M.desc.codec == AUKIT_CODEC_MSADPCM && M.desc.channels == 1 && M.head7_n == 7) { hsrc = M.head7; hn = 7; }
+            if (M.drop && M.desc.codec == AUKIT_CODEC_QOA && M.head12_n >= 8) { hsrc = M.head12; hn = 8; }
+            if (hsrc) {
+                head = std::min<uint64_t>(M.resident, hn);
                 void *p = S->stage;
-                if ((rc = pinned_grow(&p, &S->stage_cap, S->stage_used, S->stage_used + 7, 1))) return rc;
+                if ((rc = pinned_grow(&p, &S->stage_cap, S->stage_used, S->stage_used + hn, 1))) return rc;
                 S->stage = reinterpret_cast<unsigned char *>(p);
-                memcpy(S->stage + S->stage_used, M.head7, 7);
+                memcpy(S->stage + S->stage_used, hsrc, hn);
                 segs.push_back(SSetSeg{(unsigned long long)S->stage_used, cursor, (unsigned)head, 1u});
-                S->stage_used += 7;
+                S->stage_used += hn;
             }
             for (uint64_t at = head; at < M.resident; at += 0x40000000ull)   // (a segment's length is 32 bits)
                 segs.push_back(SSetSeg{M.slot + M.drop + at, cursor + at, (unsigned)std::min<uint64_t>(M.resident - at, 0x40000000ull), 0u});
@@ -330,6 +390,16 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
     for (uint32_t s = 0; s < n; s++) {
         SSetMember &M = S->m[s];
         if (M.over || !(fed[s] || M.finished)) continue;
+        if (M.desc.codec == AUKIT_CODEC_QOA && !M.qoa_checked) {
+            // the file header, once twelve bytes are in (nothing was dropped yet: the rest is the stream): a member that fails it ends here, alone
+            if (M.resident < 12 && !M.finished) continue;
+            if ((rc = sset_qoa_header(M))) {
+                M.over = true; M.end_status = rc; M.end_msg = aukit_last_error();
+                M.sb_bytes += M.resident; M.resident = 0;
+                continue;
+            }
+            M.qoa_checked = true;
+        }
         SSetJob J{s, M.finished ? M.resident : sset_whole_frames(M, M.resident), M.finished, M.finished, 0, std::string()};
         if (M.finished && (rc = sset_finished_refusal(M, M.resident, S->mono != 0))) {
             // the string call refuses these bytes: as the handle, the member hands out the chunks of its whole frames, then that status
@@ -350,6 +420,7 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
     std::vector<std::pair<uint32_t, SSetChunk>> fresh;   // (member, chunk), `at` relative to this pump's part of the cache
     uint64_t gather_elems = 0;
     S->df_fix.clear();
+    S->qoa_fix.clear();
     if (!jobs.empty()) {
         const uint32_t nj = (uint32_t)jobs.size();
         std::vector<aukit_codec_desc> descs(nj);
@@ -362,7 +433,15 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
         for (uint32_t i = 0; i < nj; i++) {
             const SSetMember &M = S->m[jobs[i].s];
             descs[i] = M.desc;
-            carry[i] = SMixCarry{M.sb_bytes, M.sb_outputs, jobs[i].usable, 0, 0, {0, 0, 0, 0, 0, 0}};
+            carry[i] = SMixCarry{M.sb_bytes, M.sb_outputs, jobs[i].usable, 0, 0, {0, 0, 0, 0, 0, 0}, 0, 0, 0, {0}};
+            if (M.desc.codec == AUKIT_CODEC_QOA) {   // positions count from the file's start; an unfinished member gets its call boundaries back
+                carry[i].samples_dropped = M.samples_dropped;
+                carry[i].qoa_back = jobs[i].ends ? 0 : 1;
+                if (M.qoa_last_on) {
+                    carry[i].qoa_last_on = 1;
+                    memcpy(carry[i].qoa_last, M.qoa_last, sizeof M.qoa_last);
+                }
+            }
             if (M.desc.codec == AUKIT_CODEC_DFPWM && !jobs[i].ends) {   // an unfinished stream.dfpwm member: the states at this decode's call boundaries come back
                 carry[i].df_back = 1;
             }
@@ -375,6 +454,12 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
         B.off[nj] = S->arena_used;
         SMixDfBack back;
         if ((rc = stream_decode_mixed_carry(ctx, &B, descs.data(), nj, S->interp, S->mono, S->dtype, &S->out, &S->ck, carry.data(), &back, S->block_codecs))) return rc;
+        if (back.qoa_pairs) {   // the boundary pairs likewise
+            void *hp = S->qoa_host;
+            if ((rc = pinned_grow(&hp, &S->qoa_host_cap, 0, back.qoa_pairs * 2, 1))) return rc;
+            S->qoa_host = reinterpret_cast<signed char *>(hp);
+            AUKIT_HIP_CHECK(hipMemcpyAsync(S->qoa_host, back.qoa_dev, back.qoa_pairs * 2, hipMemcpyDeviceToHost, ctx->stream));
+        }
         if (back.entries) {   // the states travel with the pump's one download: queued here, on the set's stream, awaited with the chunks below
             void *hp = S->df_host;
             if ((rc = pinned_grow(&hp, &S->df_host_cap, 0, back.entries * 6, sizeof(int)))) return rc;
@@ -414,6 +499,13 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
                 M.sb_bytes += M.resident; M.resident = 0;
                 continue;
             }
+            if (M.desc.codec == AUKIT_CODEC_QOA && ck.status[i] == AUKIT_E_UNSUPPORTED) {   // the walk's verdict on this member (no chunk came back): it ends here, alone
+                M.over = true;
+                M.end_status = ck.status[i];
+                M.end_msg = "QOA frame of more than 8192 samples: aukit_stream_open takes this stream";
+                M.sb_bytes += M.resident; M.resident = 0;
+                continue;
+            }
             if (J.ends) {   // what follows the queued chunks is settled: the member leaves the arena
                 M.over = true;
                 M.end_status = J.end_status ? J.end_status : ck.status[i];
@@ -425,6 +517,24 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
             // stream.dfpwm: a decided call k has its overlap byte — call k + 1 exists only if byte (k + 1) 6000 C does, and that IS call k's overlap byte —
             // so the state at boundary `shift` is the decoder's behind `shift` whole slices, whatever is fed later
             const uint64_t shift = M.lead ? (M.skip ? M.skip - 1 : 0) : M.skip;   // the fresh decode's chunk 0 is this one's chunk `shift`
+            if (M.desc.codec == AUKIT_CODEC_QOA) {
+                // stream.qoa: the rest starts behind the last dropped call's last consumed byte, eight bytes early (the file header's place); the two
+                // samples boundary `shift` hands on come from the downloaded pairs behind the wait.  (A prefix that ended inside a frame came back with
+                // AUKIT_E_LUA behind the calls before it: that is not this member's status while more bytes may come)
+                if (back.qoa_first.empty() || back.qoa_first[i] == ~0ull) continue;   // (no pair for that boundary: the member keeps its prefix)
+                const uint64_t c0 = back.qoa_call0[i];
+                SMixQoaDrop D;
+                if (!smix_qoa_drop(back.qoa_end.data() + c0, back.qoa_samples.data() + c0, back.qoa_calls[i], shift, M.resident, M.desc.channels, back.qoa_first[i], &D)) continue;
+                const uint64_t drop = D.bytes;
+                for (uint32_t k = 0; k < shift; k++) M.sb_outputs += ck.lens[(size_t)i * mc + k];
+                M.samples_dropped += D.samples;
+                S->qoa_fix.push_back(SSetQoaFix{J.s, (size_t)D.pair});
+                M.sb_bytes += drop;
+                M.drop += drop; M.resident -= drop;
+                M.decoded_usable -= drop;
+                M.skip -= (uint32_t)shift;
+                continue;
+            }
             if (shift && M.call_bytes && shift * M.call_bytes <= M.resident) {
                 const uint64_t drop = shift * M.call_bytes;
                 if (M.desc.codec == AUKIT_CODEC_DFPWM) {
@@ -489,7 +599,20 @@ int aukit_streamset_open(aukit_ctx *ctx, const aukit_codec_desc *descs, uint32_t
     // answers in the words of before
     // AUKIT_OPT_STREAMSET_BLOCK_CODECS: stream.msadpcm members likewise, under an option of their own; a refusal of a further codec names what is served
     const bool with_df = (ctx->streamset_codecs >> AUKIT_CODEC_DFPWM) & 1u, with_ms = (ctx->streamset_block_codecs >> AUKIT_CODEC_MSADPCM) & 1u;
-    if (with_df && with_ms)
+    // AUKIT_OPT_STREAMSET_FRAME_CODECS: stream.qoa members, under a third option; its clause stands behind the others', which read as they do without it
+    const bool with_qoa = (ctx->streamset_fcodecs >> AUKIT_CODEC_QOA) & 1u;
+    if (with_qoa) {
+        std::string words = "stream %u: codec %d keeps aukit_stream_open (a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV";
+        if (with_df) words += " and, under AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM";
+        if (with_ms) words += " and, under AUKIT_OPT_STREAMSET_BLOCK_CODECS, AUKIT_CODEC_MSADPCM";
+        words += " and, under AUKIT_OPT_STREAMSET_FRAME_CODECS, AUKIT_CODEC_QOA)";
+        rc = AUKIT_OK;
+        for (uint32_t s = 0; s < n && !rc; s++) {
+            const int c = descs[s].codec;
+            if (!(c == AUKIT_CODEC_PCM || c == AUKIT_CODEC_G711 || c == AUKIT_CODEC_ADPCM_WAV || c == AUKIT_CODEC_QOA || (with_df && c == AUKIT_CODEC_DFPWM) || (with_ms && c == AUKIT_CODEC_MSADPCM)))
+                rc = fail(AUKIT_E_UNSUPPORTED, words.c_str(), s, c);
+        }
+    } else if (with_df && with_ms)
         rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_DFPWM, AUKIT_CODEC_MSADPCM},
                                 "stream %u: codec %d keeps aukit_stream_open (a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV and, under "
                                 "AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM and, under AUKIT_OPT_STREAMSET_BLOCK_CODECS, AUKIT_CODEC_MSADPCM)");
@@ -510,7 +633,7 @@ int aukit_streamset_open(aukit_ctx *ctx, const aukit_codec_desc *descs, uint32_t
         if ((rc = check_smix_stream(&descs[s], 0, mono != 0))) return fail_for_stream(rc, s);
     aukit_streamset *S = new aukit_streamset();
     S->ctx = ctx; S->interp = interp; S->mono = mono ? 1 : 0; S->dtype = dtype;
-    S->block_codecs = with_ms ? 1u << AUKIT_CODEC_MSADPCM : 0u;
+    S->block_codecs = (with_ms ? 1u << AUKIT_CODEC_MSADPCM : 0u) | (with_qoa ? 1u << AUKIT_CODEC_QOA : 0u);
     S->m.resize(n);
     for (uint32_t s = 0; s < n; s++) {
         S->m[s].desc = descs[s];
@@ -541,6 +664,8 @@ int aukit_streamset_feed(aukit_streamset *S, uint32_t s, const uint8_t *bytes, u
     memcpy(S->stage + at, bytes, (size_t)nbytes);
     if (M.head7_n < 7 && M.desc.codec == AUKIT_CODEC_MSADPCM && M.desc.channels == 1)   // (nothing is dropped before the first call is whole: these are the stream's first bytes)
         for (uint64_t i = 0; i < nbytes && M.head7_n < 7; i++) M.head7[M.head7_n++] = bytes[i];
+    if (M.head12_n < 12 && M.desc.codec == AUKIT_CODEC_QOA)   // (likewise: the file header)
+        for (uint64_t i = 0; i < nbytes && M.head12_n < 12; i++) M.head12[M.head12_n++] = bytes[i];
     S->stage_used = at + (size_t)nbytes;
     S->feeds.push_back(SSetFeed{s, (uint64_t)at, nbytes});
     M.pending += nbytes;
@@ -564,7 +689,7 @@ int aukit_streamset_pump(aukit_streamset *S, uint32_t *n_ready) {
         const std::string msg = aukit_last_error();
         const bool waited = hipStreamSynchronize(S->ctx->stream) == hipSuccess;
         (void)hipGetLastError();
-        if (waited) sset_apply_states(S); else S->df_fix.clear();
+        if (waited) sset_apply_states(S); else { S->df_fix.clear(); S->qoa_fix.clear(); }
         return fail(rc, "%s", msg.c_str());
     }
     return AUKIT_OK;
@@ -627,6 +752,7 @@ void aukit_streamset_close(aukit_streamset *S) {
     if (S->stage) (void)hipHostFree(S->stage);
     if (S->cache) (void)hipHostFree(S->cache);
     if (S->df_host) (void)hipHostFree(S->df_host);
+    if (S->qoa_host) (void)hipHostFree(S->qoa_host);
     S->d_stage.release(); S->d_tab.release(); S->d_gather.release();
     delete S;
 }

@@ -971,15 +971,20 @@ end
 -- MS-ADPCM WAV readers (format 2: aukit.stream.wav's dispatch to aukit.stream.msadpcm with the stream's blockAlign and coefficient list) are taken with the
 -- key `msadpcm` of the options table, {mono = ..., msadpcm = true}: for the one open the context is opted in under an option of its own
 -- (AUKIT_OPT_STREAMSET_BLOCK_CODECS, option 8, bit 1 << AUKIT_CODEC_MSADPCM) and put back behind it, also where the open is refused.
+-- QOA readers (a first piece that starts with "qoaf" and holds the twelve header bytes) are taken with the key `qoa`, {mono = ..., qoa = true}: the
+-- descriptor carries the header's channel count and rate, the whole piece is payload, the pair is aukit.stream.qoa(fn, mono)'s (length file_samples /
+-- sampleRate); for the one open the context is opted in under a third option (AUKIT_OPT_STREAMSET_FRAME_CODECS, option 10, bit 1 << AUKIT_CODEC_QOA)
+-- and put back behind it, also where the open is refused.
 function aukit.stream.set(readers, mono)
     expect(1, readers, "table") expect(2, mono, "boolean", "table", "nil")
-    local dfpwm, msadpcm = false, false
+    local dfpwm, msadpcm, qoa = false, false, false
     if type(mono) == "table" then
-        for k in pairs(mono) do if k ~= "mono" and k ~= "dfpwm" and k ~= "msadpcm" then error("bad argument #2 (unknown option " .. tostring(k) .. ")", 2) end end
-        if (mono.mono ~= nil and type(mono.mono) ~= "boolean") or (mono.dfpwm ~= nil and type(mono.dfpwm) ~= "boolean") or (mono.msadpcm ~= nil and type(mono.msadpcm) ~= "boolean") then
+        for k in pairs(mono) do if k ~= "mono" and k ~= "dfpwm" and k ~= "msadpcm" and k ~= "qoa" then error("bad argument #2 (unknown option " .. tostring(k) .. ")", 2) end end
+        if (mono.mono ~= nil and type(mono.mono) ~= "boolean") or (mono.dfpwm ~= nil and type(mono.dfpwm) ~= "boolean") or (mono.msadpcm ~= nil and type(mono.msadpcm) ~= "boolean") or
+           (mono.qoa ~= nil and type(mono.qoa) ~= "boolean") then
             error("bad argument #2 (expected boolean options)", 2)
         end
-        mono, dfpwm, msadpcm = mono.mono, mono.dfpwm or false, mono.msadpcm or false
+        mono, dfpwm, msadpcm, qoa = mono.mono, mono.dfpwm or false, mono.msadpcm or false, mono.qoa or false
     end
     local n = #readers
     local descs = ffi.new("aukit_codec_desc[?]", math.max(n, 1))
@@ -987,6 +992,7 @@ function aukit.stream.set(readers, mono)
     local takes = dfpwm and "stream.set takes PCM, G.711 and DFPWM payloads and IMA-ADPCM blocks (the other codecs keep their own streams)"
                   or "stream.set takes PCM and G.711 payloads and IMA-ADPCM blocks (the other codecs keep their own streams)"
     if msadpcm then takes = takes:gsub("IMA%-ADPCM blocks", "IMA-ADPCM and MS-ADPCM blocks") end
+    if qoa then takes = takes:gsub(" blocks %(", " blocks and QOA files (") end
     local fns = {}
     for i = 1, n do
         local e = readers[i]
@@ -1005,8 +1011,15 @@ function aukit.stream.set(readers, mono)
             if type(readers[i]) ~= "function" then error("bad argument #1 (reader " .. (i - 1) .. ": expected function)", 2) end
             local f = readers[i]()
             if type(f) ~= "string" then error("bad argument #1 (reader " .. (i - 1) .. ": expected string from the first call)", 2) end
-            if f:sub(1, 4) == "qoaf" then error("reader " .. (i - 1) .. ": qoa payload: " .. takes, 2) end
+            if f:sub(1, 4) == "qoaf" and not qoa then error("reader " .. (i - 1) .. ": qoa payload: " .. takes, 2) end
             local kind
+            if f:sub(1, 4) == "qoaf" then   -- the twelve header bytes: "qoaf", samples, channels, rate (:3241); the whole piece is payload
+                if #f < 12 then error("reader " .. (i - 1) .. ": the first piece of a QOA stream holds its 12 header bytes", 2) end
+                local rate = f:byte(10) * 65536 + f:byte(11) * 256 + f:byte(12)
+                descs[i - 1] = desc {codec = "qoa", channels = f:byte(9), sampleRate = rate}
+                firsts[i], done[i] = f, false
+                lengths[i] = (f:byte(5) * 16777216 + f:byte(6) * 65536 + f:byte(7) * 256 + f:byte(8)) / rate
+            else
             for _, m in ipairs(MAGIC) do if f:find(m[1]) then kind = m[2] break end end
             if not kind then error("reader " .. (i - 1) .. ": not a WAV, AIFF or AU stream", 2) end
             local c = ffi.new("aukit_container")
@@ -1018,6 +1031,7 @@ function aukit.stream.set(readers, mono)
             firsts[i] = f:sub(tonumber(c.payload_off) + 1, tonumber(c.payload_off + c.payload_len))
             lengths[i] = c.length_seconds   -- NaN: the stream factory's own figure stands
             done[i] = false
+            end
         end
     end
     local sp = ffi.new("aukit_streamset*[1]")
@@ -1025,10 +1039,13 @@ function aukit.stream.set(readers, mono)
     if dfpwm then check(C.aukit_ctx_set_option(ctx(), 7, 2 ^ CODEC.dfpwm)) end
     -- msadpcm: AUKIT_OPT_STREAMSET_BLOCK_CODECS (8) with bit 1 << AUKIT_CODEC_MSADPCM, likewise
     if msadpcm then check(C.aukit_ctx_set_option(ctx(), 8, 2 ^ CODEC.msadpcm)) end
+    -- qoa: AUKIT_OPT_STREAMSET_FRAME_CODECS (10) with bit 1 << AUKIT_CODEC_QOA, likewise
+    if qoa then check(C.aukit_ctx_set_option(ctx(), 10, 2 ^ CODEC.qoa)) end
     local rc = C.aukit_streamset_open(ctx(), descs, n, INTERP[aukit.defaultInterpolation], mono and 1 or 0, F64, sp)
     local words = rc ~= 0 and ffi.string(C.aukit_last_error()) or nil
     if dfpwm then C.aukit_ctx_set_option(ctx(), 7, 0) end
     if msadpcm then C.aukit_ctx_set_option(ctx(), 8, 0) end
+    if qoa then C.aukit_ctx_set_option(ctx(), 10, 0) end
     if words then error(words, 2) end
     local set = ffi.gc(sp[0], C.aukit_streamset_close)
     local ready = ffi.new("uint32_t[1]")

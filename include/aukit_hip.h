@@ -179,13 +179,19 @@ typedef enum {
                                    named (or "bit N"), and the context keeps the mask it had.  A second option and not a second bit of option 7, which
                                    knows its one bit and refuses this one by name.  Options 5 and 6 are not needed for a set and open it to nothing;
                                    this option opens neither mixed call.  With 0 every call answers exactly as before. */
-    AUKIT_OPT_STREAM_MIXED_FRAME_CODECS = 9 /* a second mask of aukit_stream_decode_mixed's, the only call that reads it: a bit mask of 1 << codec, 0 by
+    AUKIT_OPT_STREAM_MIXED_FRAME_CODECS = 9,/* a second mask of aukit_stream_decode_mixed's, the only call that reads it: a bit mask of 1 << codec, 0 by
                                    default, exactly one bit known, 1 << AUKIT_CODEC_QOA (aukit.stream.qoa's files, see that call); any other bit is
                                    AUKIT_E_UNSUPPORTED, the codec named (or "bit N"), and the context keeps the mask it had.  A second option and not a
                                    second bit of option 6, which knows its one bit and refuses this one by name.  Options 5, 6, 7 and 8 do not open
                                    the call to QOA; this option opens it to nothing else, and opens neither aukit_decode_resample_mixed (which takes
-                                   QOA without being asked) nor aukit_streamset_open (a stream set keeps refusing the codec).  With 0 every call
+                                   QOA without being asked) nor aukit_streamset_open (a stream set has option 10 for the codec).  With 0 every call
                                    answers exactly as before. */
+    AUKIT_OPT_STREAMSET_FRAME_CODECS = 10 /* a third mask of aukit_streamset_open's, read by that call alone and only while it opens (an open set keeps
+                                   what it was opened with): a bit mask of 1 << codec, 0 by default, exactly one bit known, 1 << AUKIT_CODEC_QOA
+                                   (aukit.stream.qoa's streams as members of a set, see that call); any other bit is AUKIT_E_UNSUPPORTED, the codec
+                                   named (or "bit N"), and the context keeps the mask it had.  Options 7 and 8 know their one bit each and refuse
+                                   this one by name; options 5, 6 and 9 are not needed for a set and open it to nothing; this option opens neither
+                                   mixed call.  With 0 every call answers exactly as before. */
 } aukit_option;
 int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);
 /* counters of the most recent call that produced them (AUKIT_OPT_COLLECT_STATS = 1) */
@@ -580,6 +586,23 @@ void aukit_stream_close(aukit_stream *s);
  * flag read-back (as AUKIT_CODEC_ADPCM_WAV members add their header scan's).  A chunk may be longer than 48000 samples (block_align 22, one channel,
  * 8000 Hz: 267 blocks x 180 = 48060): size `cap` for it, or read `*len` from the AUKIT_E_ARG refusal and call again. */
 typedef struct aukit_streamset aukit_streamset;
+/* AUKIT_CODEC_QOA members of a set.
+ * On request, AUKIT_OPT_STREAMSET_FRAME_CODECS with bit 1 << AUKIT_CODEC_QOA set on the context when the set is opened, AUKIT_CODEC_QOA members join
+ * (without the bit every refusal above stands, word for word; with it a refusal of a further codec names AUKIT_CODEC_QOA in its list, behind the
+ * clauses of options 7 and 8; sinc stays refused).  AUKIT_OPT_STREAM_MIXED_FRAME_CODECS is not needed.  Such a member is aukit.stream.qoa
+ * (aukit.lua:3202-3337).  Unlike the mixed calls, which read only `codec`, a member's descriptor carries `channels` and `sample_rate`: the file
+ * header's bytes 8 and 9..11.  The open refuses by index channels outside 1 .. AUKIT_MAX_PLANAR_CHANNELS, a rate outside 1 .. 2^24 - 1 and what the
+ * mixed call refuses of a file's rate (a warm-up beyond one tile, a window beyond 64 KiB of LDS; "aukit_stream_open takes this stream"); without
+ * `mono` the members agree in channel count.  The first twelve bytes fed are kept on the host and checked before the member's first batch: a wrong
+ * magic ends the member alone with AUKIT_E_LUA "Not a QOA file", a channel count or rate that differs from the descriptor's with AUKIT_E_ARG (both
+ * named); a member finished with fewer than twelve bytes ends with aukit_stream_decode's status and words for them.  All that crosses an iterator
+ * call are the last two samples per channel and the position: the member carries both, the rest starts at the next call (no call is kept in front of
+ * it, where the handle keeps one) and is cut at the byte behind the last dropped call, which the engine's walk reports — frames of any size.  The
+ * file's first eight bytes stay in front of every rest (written over the last eight dropped bytes by the repack).  An unfinished member is decoded
+ * with all its resident bytes; a finished one that ends inside a frame hands out the chunks of its whole calls, then AUKIT_E_LUA "attempt to perform
+ * arithmetic on a nil value (field '?')".  A frame of more than 8192 samples ends the member alone at the pump that meets it, behind the chunks of
+ * earlier pumps, with AUKIT_E_UNSUPPORTED "QOA frame of more than 8192 samples: aukit_stream_open takes this stream".  A pump that decodes such
+ * members waits two more times, the walk's two read-backs (count, call records). */
 int aukit_streamset_open(aukit_ctx *ctx, const aukit_codec_desc *descs /* n */, uint32_t n, int interp, int mono, int dtype, aukit_streamset **out);
 /* host copy only: no device call, no wait (the pinned buffer grows, rarely, outside the steady state).  After aukit_streamset_finish: AUKIT_E_ARG */
 int aukit_streamset_feed(aukit_streamset *set, uint32_t s, const uint8_t *bytes, uint64_t nbytes);
