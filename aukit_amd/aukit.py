@@ -461,7 +461,7 @@ def au(data):  # aukit.lua:1639
 _MAGIC_KIND = {"wav": N.CONTAINER_WAV, "aiff": N.CONTAINER_AIFF, "au": N.CONTAINER_AU}
 
 
-def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm=False, stream_ms=False, stream_qoa=False):
+def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm=False, stream_ms=False, stream_qoa=False, flac=False):
     """load_many's host half, up to the device call: every file sniffed by magic as `detect` does and walked by aukit_parse_container
     -> ([descriptor per file], [(first payload byte, byte count) per file], [info table per file]).  A file that is no WAV / AIFF / AU / QOA, or
     whose payload is none of PCM, G.711 and DFPWM, raises LuaError naming the file's index (0-based, the position in `files`).
@@ -484,7 +484,10 @@ def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm
     chunk's coefficient list, as `adpcm` takes it for load_many), the payload the `data` chunk, the length what aukit.stream.wav returns for the
     file.  Without it such a file is refused by index in the words of before, whatever `stream_ima` and `adpcm` say.
     `stream_qoa` (with `stream`): a QOA file is taken too, whole, as load_many takes it — the descriptor names the codec only, the length is NaN
-    (aukit.stream.qoa's own figure stands, file_samples / sampleRate, :3336).  Without it such a file is refused by index in the words of before."""
+    (aukit.stream.qoa's own figure stands, file_samples / sampleRate, :3336).  Without it such a file is refused by index in the words of before.
+    `flac` (without `stream`): load_many's switch — a file `detect` calls "flac" is taken too, whole: the descriptor names the codec only (channel
+    count, depth and rate are the file's STREAMINFO's) and the info table is aukit.flac's.  Without it such a file is refused by index in the words
+    of before."""
     _expect(1, files, "table")
     takes = "PCM, G.711 and DFPWM" if stream_dfpwm else "PCM and G.711"
     if stream_ima and stream_ms:
@@ -530,6 +533,11 @@ def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm
             descs.append(B.make_desc(N.CODEC_QOA))
             ranges.append((0, len(f)))
             infos.append({"bitDepth": 16, "dataType": "signed"})   # what aukit.qoa sets
+            continue
+        if kind == "flac" and flac and not stream:
+            descs.append(B.make_desc(N.CODEC_FLAC))
+            ranges.append((0, len(f)))
+            infos.append({"dataType": "signed"})   # what aukit.flac sets
             continue
         if kind not in _MAGIC_KIND:
             raise LuaError(f"file {i}: not a WAV, AIFF or AU file")
@@ -663,7 +671,7 @@ class _RowView(B.AudioBatch):
             self._own = None
 
 
-def load_many(files, sampleRate=None, interpolation=None, mono=None, adpcm=None):
+def load_many(files, sampleRate=None, interpolation=None, mono=None, adpcm=None, flac=None):
     """aukit.wav / aukit.aiff / aukit.au / aukit.qoa (file):resample(sampleRate, interpolation) [:mono()] for a LIST of whole files of any mix of
     containers, rates, PCM formats / G.711 / DFPWM / QOA and channel counts: the payload ranges go up as one batch, one aukit_decode_resample_mixed
     call resamples (and, by default, mixes down) all of them, and one Audio per file comes back, in input order, each a view of its row of the
@@ -671,23 +679,31 @@ def load_many(files, sampleRate=None, interpolation=None, mono=None, adpcm=None)
     (data, "dfpwm"[, channels[, sampleRate]]): aukit.dfpwm's arguments.  A .qoa file goes up whole.
     `adpcm` = True: WAV files of IMA-ADPCM or MS-ADPCM blocks are taken as well (aukit.wav's dispatch to aukit.adpcm's block splitter and to
     aukit.msadpcm); for this one call the context is opted in to MS-ADPCM descriptors (AUKIT_OPT_MIXED_CODECS) and put back as it was behind it.
-    Without it (the default) both kinds are refused by index, as before."""
+    Without it (the default) both kinds are refused by index, as before.
+    `flac` = True: files `detect` calls "flac" are taken as well, whole (aukit.flac: channel count, depth and rate are the file's own); for this
+    one call the context is opted in to FLAC descriptors (AUKIT_OPT_MIXED_FRAME_CODECS) and put back as it was behind it, also after a refusal.
+    Without it (the default) such a file is refused by index, as before."""
     sampleRate = 48000 if sampleRate is None else _expect(2, sampleRate, "number")
     interpolation = interpolation if interpolation is not None else defaultInterpolation
     ip = _interp(interpolation, 3)
     mono = True if mono is None else _expect(4, mono, "boolean")
     adpcm = False if adpcm is None else _expect(5, adpcm, "boolean")
-    descs, ranges, infos = _sniff_many(files, adpcm=adpcm)
+    flac = False if flac is None else _expect(6, flac, "boolean")
+    descs, ranges, infos = _sniff_many(files, adpcm=adpcm, flac=flac)
     ctx = context()
     bt = _wrap(B.Batch.upload, ctx, [bytes((f[0] if isinstance(f, (list, tuple)) else f)[o:o + n]) for f, (o, n) in zip(files, ranges)])
-    was = ctx.option(N.OPT_MIXED_CODECS)
+    was, was_frame = ctx.option(N.OPT_MIXED_CODECS), ctx.option(N.OPT_MIXED_FRAME_CODECS)
     try:
         if adpcm:
             _wrap(ctx.set_option, N.OPT_MIXED_CODECS, was | 1 << N.CODEC_MSADPCM)
+        if flac:
+            _wrap(ctx.set_option, N.OPT_MIXED_FRAME_CODECS, was_frame | 1 << N.CODEC_FLAC)
         out = _wrap(B.decode_resample_mixed, ctx, bt, descs, float(sampleRate), ip, mono, ctx.dtype)
     finally:
         if adpcm:
             ctx.set_option(N.OPT_MIXED_CODECS, was)
+        if flac:
+            ctx.set_option(N.OPT_MIXED_FRAME_CODECS, was_frame)
     shared = {}
     return [Audio(_RowView(out, s, shared), {}, infos[s]) for s in range(len(files))]
 

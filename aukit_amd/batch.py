@@ -475,8 +475,10 @@ def decode_resample_mixed(ctx, batch, descs, new_rate, interp, mono=False, dtype
     batch holds DFPWM, QOA or IMA-ADPCM streams), one AudioBatch at `new_rate` in the batch's order.  `descs`: one CodecDesc per stream —
     make_desc(N.CODEC_QOA) for a QOA file (channel count and rate are its header's), make_desc(N.CODEC_ADPCM_WAV, channels, rate, block_align=...)
     for IMA blocks, make_desc(N.CODEC_MSADPCM, channels, rate, block_align=..., coefficients=...) for the MS-ADPCM blocks of a WAV file — those
-    only on a context that asked for them: ctx.set_option(N.OPT_MIXED_CODECS, 1 << N.CODEC_MSADPCM).  Every refusal, those only the device can
-    detect included, comes before `out` is touched."""
+    only on a context that asked for them: ctx.set_option(N.OPT_MIXED_CODECS, 1 << N.CODEC_MSADPCM).  make_desc(N.CODEC_FLAC) for a whole FLAC
+    file (channel count, depth and rate are its STREAMINFO's), under an option of its own: ctx.set_option(N.OPT_MIXED_FRAME_CODECS,
+    1 << N.CODEC_FLAC); the FLAC streams are decoded group by group, (channels, depth) each, before `out` is touched.  Every refusal, those only
+    the device can detect included, comes before `out` is touched."""
     out = out if out is not None else AudioBatch(ctx)
     arr = (N.CodecDesc * max(len(descs), 1))()
     for i, d in enumerate(descs):

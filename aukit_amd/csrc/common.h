@@ -51,6 +51,12 @@ struct aukit_ctx {
                                 //   one does not apply), 2 = always the reference-order kernels; 0 = f32 taps
     bool chan_lens = false;     // AUKIT_OPT_CHANNEL_LENS: the host reads chunk lengths per channel (stream.pcm delivers its uneven last chunk)
     unsigned mixed_codecs = 0;  // AUKIT_OPT_MIXED_CODECS: bit 1 << codec lets aukit_decode_resample_mixed take that codec beyond its default list
+    unsigned mixed_frame_codecs = 0;   // AUKIT_OPT_MIXED_FRAME_CODECS: aukit_decode_resample_mixed's second mask (1 << AUKIT_CODEC_FLAC), read by that call alone
+    // that call's FLAC members (flac.hip: flac_mixed_decode): every (channels, depth) group's bytes compacted back to back in fmix_src, the decoder's
+    // int32 rows of all groups in fmix_rows — of their own, because the next group's decode, the other pre-passes and lazy_drop write or swap the
+    // shared scratch; both stay at their high-water size.  fmix_ev: the look-ahead stream behind the compaction
+    aukit::DevBuf fmix_src, fmix_rows;
+    hipEvent_t fmix_ev = nullptr;
     unsigned stream_mixed_codecs = 0;  // AUKIT_OPT_STREAM_MIXED_CODECS: the same for aukit_stream_decode_mixed, which reads this mask and no other
     unsigned stream_mixed_frame_codecs = 0;   // AUKIT_OPT_STREAM_MIXED_FRAME_CODECS: that call's second mask (1 << AUKIT_CODEC_QOA), read by the public call alone
     unsigned streamset_codecs = 0;     // AUKIT_OPT_STREAMSET_CODECS: bit 1 << codec lets aukit_streamset_open, which reads this mask and no other, take that codec

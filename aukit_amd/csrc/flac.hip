@@ -18,21 +18,24 @@
 //           double rows.  Takes what the fused decoders decline (FE_DECLINE), 32-bit streams and batches whose values
 //           overflow int32 (redone with double rows and the Lua's own floating-point prediction).
 // This file has the kernels of steps 1 and 2, the ONE host driver both designs run under (flac_drive, with FlacFirst and
-// FlacFused saying what is a design's own), flac_decode_rows, the loader and stream.flac.  The division by 2^depth (:505) happens in the consumer.
+// FlacFused saying what is a design's own), flac_decode_rows, the loader, the FLAC members of a mixed batch (flac_mixed_headers, flac_mixed_decode) and stream.flac.  The division by 2^depth (:505) happens in the consumer.
 #include <algorithm>
 #include "resample.h"
 #include "stream_tail.h"
 #include "flac_dev.h"
 #include "resample_dev.h"
+#include "flac_mixed.h"
 
 namespace aukit {
 
 // decodeFLAC header + metadata blocks  :569-606
+// IDX (the FLAC members of a mixed batch, which do not lie back to back): stream s is bytes off[2 s] .. off[2 s + 1] of src
+template <bool IDX>
 __global__ __launch_bounds__(64) void k_flac_header(const unsigned char *src, const u64 *off, unsigned n, FlacStreamInfo *out) {
     const unsigned s = blockIdx.x * 64 + threadIdx.x;
     if (s >= n) return;
-    const unsigned char *p = src + off[s];
-    const u64 nb = off[s + 1] - off[s];
+    const unsigned char *p = src + off[IDX ? 2 * s : s];
+    const u64 nb = off[IDX ? 2 * s + 1 : s + 1] - off[IDX ? 2 * s : s];
     FlacStreamInfo r{};
     r.status = 0;
     if (nb < 4) { r.status = 1; out[s] = r; return; }                                                    // nil arithmetic in intunpack
@@ -637,7 +640,10 @@ static int flac_rows_materialize(aukit_ctx *ctx, FlacDecoded &D) {
     return AUKIT_OK;
 }
 
-static int flac_decode_rows(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &D, bool want_frames) {
+// mixed (flac_mixed_decode: a (channels, depth) group of a mixed batch's FLAC members): the streams may differ in sample rate, which no decoder reads,
+// and rows of doubles are not made — FLAC_ROWS_WIDE comes back where they would be (a depth of 32, a value beyond int32, AUKIT_FLAC_WIDE)
+enum { FLAC_ROWS_WIDE = 100 };
+static int flac_decode_rows(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &D, bool want_frames, bool mixed = false) {
     const uint32_t n = in->n;
     if (n == 0) return fail(AUKIT_E_ARG, "empty batch");
     int rc;
@@ -674,7 +680,7 @@ static int flac_decode_rows(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &
         if ((rc = D.set->ensure(((size_t)n * sizeof(FlacStreamInfo) + 255) & ~(size_t)255))) return rc;
         d_info_pre = reinterpret_cast<FlacStreamInfo *>(D.set->p);
     }
-    hipLaunchKernelGGL(k_flac_header, dim3((n + 63) / 64), dim3(64), 0, pre, in->data(), reinterpret_cast<const u64 *>(in->d_off), n, d_info_pre);
+    hipLaunchKernelGGL(k_flac_header<false>, dim3((n + 63) / 64), dim3(64), 0, pre, in->data(), reinterpret_cast<const u64 *>(in->d_off), n, d_info_pre);
     AUKIT_HIP_CHECK(hipGetLastError());
     D.info.resize(n);
     AUKIT_HIP_CHECK(hipMemcpyAsync(D.info.data(), d_info_pre, (size_t)n * sizeof(FlacStreamInfo), hipMemcpyDeviceToHost, pre));
@@ -690,7 +696,7 @@ static int flac_decode_rows(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &
         default: return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value");
         }
         if (s == 0) { D.channels = D.info[0].channels; D.depth = D.info[0].depth; D.rate = D.info[0].rate; }
-        else if (D.info[s].channels != D.channels || D.info[s].depth != D.depth || D.info[s].rate != D.rate)
+        else if (D.info[s].channels != D.channels || D.info[s].depth != D.depth || (D.info[s].rate != D.rate && !mixed))
             return fail(AUKIT_E_ARG, "all FLAC streams of a batch must share channel count, bit depth and sample rate");
     }
     if (D.depth <= 24 && !g_flac_force_wide() && !getenv("AUKIT_FLAC_SLOW_RESTORE")) {
@@ -703,7 +709,172 @@ static int flac_decode_rows(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &
         rc = flac_run_first(ctx, in, D, want_frames, false);
         if (rc != 1) return rc;
     }
+    if (mixed) return FLAC_ROWS_WIDE;
     return flac_run_first(ctx, in, D, want_frames, true);
+}
+
+// ================================================================= the FLAC members of aukit_decode_resample_mixed (flac_mixed.h)
+int flac_mixed_headers(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F) {
+    int rc;
+    const size_t m = list.size();
+    F.assign(m, FlacMixedStream());
+    if (!m) return AUKIT_OK;
+    std::vector<u64> pairs(2 * m);
+    for (size_t k = 0; k < m; k++) { pairs[2 * k] = in->off[list[k]]; pairs[2 * k + 1] = in->off[list[k] + 1]; }
+    const size_t info_at = (size_t)round_up(2 * m * 8, 256);
+    if ((rc = ctx->misc_buf.ensure(info_at + m * sizeof(FlacStreamInfo)))) return rc;
+    char *B = reinterpret_cast<char *>(ctx->misc_buf.p);
+    if ((rc = h2d_table(ctx, B, pairs.data(), 2 * m * 8))) return rc;
+    hipLaunchKernelGGL(k_flac_header<true>, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, in->data(), reinterpret_cast<const u64 *>(B), (unsigned)m,
+                       reinterpret_cast<FlacStreamInfo *>(B + info_at));
+    AUKIT_HIP_CHECK(hipGetLastError());
+    std::vector<FlacStreamInfo> info(m);
+    AUKIT_HIP_CHECK(hipMemcpyAsync(info.data(), B + info_at, m * sizeof(FlacStreamInfo), hipMemcpyDeviceToHost, ctx->stream));
+    AUKIT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (size_t k = 0; k < m; k++) {
+        switch (info[k].status) {
+        case 0: break;
+        case 2: return fail(AUKIT_E_LUA, "Invalid magic string (stream %u)", list[k]);
+        case 3: return fail(AUKIT_E_LUA, "Stream info metadata block absent (stream %u)", list[k]);
+        case 4: return fail(AUKIT_E_LUA, "Sample depth not supported (stream %u)", list[k]);
+        case 5: return fail(AUKIT_E_LUA, "data string too short (stream %u)", list[k]);
+        default: return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (stream %u)", list[k]);
+        }
+        if (info[k].depth > 24 || g_flac_force_wide())   // (rows of doubles: the single-descriptor loader's)
+            return fail(AUKIT_E_UNSUPPORTED, "FLAC stream of %d bits whose rows are doubles: aukit_decode_resample takes this file (stream %u)", info[k].depth, list[k]);
+        F[k].channels = info[k].channels; F[k].depth = info[k].depth; F[k].rate = info[k].rate;
+    }
+    return AUKIT_OK;
+}
+
+// grows keeping the first `keep` bytes (the rows of the groups decoded so far)
+static int fmix_rows_grow(aukit_ctx *ctx, size_t need, size_t keep) {
+    DevBuf &R = ctx->fmix_rows;
+    if (need <= R.cap && R.p) return AUKIT_OK;
+    DevBuf bigger;
+    int rc = bigger.ensure(need + need / 2);
+    if (rc) return rc;
+    if (keep && R.p) {
+        hipError_t e = hipMemcpyAsync(bigger.p, R.p, keep, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) { bigger.release(); return fail(AUKIT_E_HIP, "copying the FLAC rows failed: %s", hipGetErrorString(e)); }
+    }
+    R.release();
+    R = bigger;
+    return AUKIT_OK;
+}
+
+int flac_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F) {
+    int rc;
+    const size_t m = list.size();
+    if (!m) return AUKIT_OK;
+    // ---- groups by (channels, depth), in order of first appearance; their bytes back to back, every group at a multiple of 256 bytes with 64 to spare
+    std::map<std::pair<int, int>, size_t> index;
+    std::vector<std::vector<size_t>> groups;
+    for (size_t k = 0; k < m; k++) {
+        const auto r = index.emplace(std::make_pair(F[k].channels, F[k].depth), groups.size());
+        if (r.second) groups.emplace_back();
+        groups[r.first->second].push_back(k);
+    }
+    struct Place { size_t at, tab_at; std::vector<uint64_t> off; };
+    std::vector<Place> place(groups.size());
+    std::vector<std::array<uint64_t, 3>> segments;
+    size_t end = 0;
+    for (size_t g = 0; g < groups.size(); g++) {
+        Place &P = place[g];
+        P.at = (size_t)round_up(end, 256);
+        P.off.push_back(0);
+        for (size_t k : groups[g]) {
+            const uint64_t b = in->off[list[k]], nb = in->off[list[k] + 1] - b;
+            for (uint64_t at = 0; at < nb; at += 0x20000000ull) segments.push_back({b + at, P.at + P.off.back() + at, std::min<uint64_t>(nb - at, 0x20000000ull)});
+            P.off.push_back(P.off.back() + nb);
+        }
+        end = P.at + (size_t)P.off.back() + 64;
+    }
+    for (Place &P : place) { P.tab_at = (size_t)round_up(end, 256); end = P.tab_at + P.off.size() * 8; }   // the groups' offset tables behind the bytes
+    const size_t one_tab_at = (size_t)round_up(end, 256);   // ... and the two offsets of a one-stream batch (the search for a stream whose rows are wide)
+    end = one_tab_at + 16;
+    if ((rc = ctx->fmix_src.ensure(end + 64))) return rc;
+    unsigned char *const src = reinterpret_cast<unsigned char *>(ctx->fmix_src.p);
+    if ((rc = segments_copy(ctx, in->data(), src, segments, ctx->tile_buf))) return rc;
+    for (const Place &P : place)
+        if ((rc = h2d_table(ctx, src + P.tab_at, P.off.data(), P.off.size() * 8))) return rc;
+    if (!ctx->fmix_ev) AUKIT_HIP_CHECK(hipEventCreateWithFlags(&ctx->fmix_ev, hipEventDisableTiming));
+    AUKIT_HIP_CHECK(hipEventRecord(ctx->fmix_ev, ctx->stream));   // (the look-ahead stream reads the compacted bytes: aukit_batch::ready)
+
+    // ---- a temporary batch per group: back-to-back calls of the look-ahead machinery.  The rows of every group go to ctx->fmix_rows at once — the next
+    // group's decode writes tmp_buf3 and may write tmp_buf
+    auto group_batch = [&](const Place &P, aukit_batch &tb) {
+        tb.n = (uint32_t)(P.off.size() - 1);
+        tb.off = P.off;
+        tb.base = src + P.at; tb.front_pad = 0; tb.cap = (size_t)P.off.back() + 64; tb.own = false;
+        tb.d_off = reinterpret_cast<uint64_t *>(src + P.tab_at);
+        tb.ready = ctx->fmix_ev;
+    };
+    // stream `who` of the group as a batch of its own, offsets from 0 (what lies behind it in the buffer is the next member, or the group's spare bytes)
+    auto member_batch = [&](const Place &P, size_t who, aukit_batch &tb) -> int {
+        tb.n = 1;
+        tb.off = {0, P.off[who + 1] - P.off[who]};
+        tb.base = src + P.at + P.off[who]; tb.front_pad = 0; tb.cap = (size_t)tb.off[1] + 64; tb.own = false;
+        tb.d_off = reinterpret_cast<uint64_t *>(src + one_tab_at);
+        if (int hrc = h2d_table(ctx, tb.d_off, tb.off.data(), 16)) return hrc;
+        AUKIT_HIP_CHECK(hipEventRecord(ctx->fmix_ev, ctx->stream));   // (the look-ahead stream reads the table too)
+        tb.ready = ctx->fmix_ev;
+        return AUKIT_OK;
+    };
+    // Of several streams the decoders refuse, the one with the lowest index in the library is named, as the int16-row pre-passes do: a group with an
+    // offender leaves no rows, the groups behind it are decoded all the same, and the call fails behind the last
+    unsigned bad = ~0u;
+    int bad_code = AUKIT_OK;
+    std::string bad_msg;
+    auto offender = [&](unsigned s, int code, const std::string &msg) { if (s < bad) { bad = s; bad_code = code; bad_msg = msg; } };
+    size_t rows_end = 0;
+    for (size_t g = 0; g < groups.size(); g++) {
+        const Place &P = place[g];
+        const std::vector<size_t> &G = groups[g];
+        aukit_batch tb;
+        group_batch(P, tb);
+        FlacDecoded D;
+        D.want16 = false;
+        rc = flac_decode_rows(ctx, &tb, D, false, true);
+        if (rc == FLAC_ROWS_WIDE) {   // a value beyond int32 somewhere in the group: which stream's, one at a time (the last one if no other)
+            size_t who = 0;
+            for (; who + 1 < G.size(); who++) {
+                aukit_batch one;
+                if ((rc = member_batch(P, who, one))) return rc;
+                FlacDecoded D1;
+                const int r1 = flac_decode_rows(ctx, &one, D1, false, true);
+                if (r1 == FLAC_ROWS_WIDE) break;
+                if (r1) return r1;
+            }
+            offender(list[G[who]], AUKIT_E_UNSUPPORTED, "FLAC stream with a value beyond int32, whose rows are doubles: aukit_decode_resample takes this file");
+            continue;
+        }
+        if (rc) return rc;
+        size_t raised = 0;
+        while (raised < G.size() && !D.status[raised]) raised++;
+        if (raised < G.size()) {   // decodeFLAC raises (the group's members are in library order: its first is its lowest)
+            offender(list[G[raised]], AUKIT_E_LUA, flac_err_msg(D.status[raised]));
+            continue;
+        }
+        const size_t at = (size_t)round_up(rows_end, 256), bytes = (size_t)D.tot_elems * 4;
+        if ((rc = fmix_rows_grow(ctx, at + bytes + 256, rows_end))) return rc;
+        int *const rows = reinterpret_cast<int *>(reinterpret_cast<char *>(ctx->fmix_rows.p) + at);
+        if (D.in_scratch) {
+            if (D.nfr) {
+                if ((rc = ctx_begin_kernel(ctx))) return rc;
+                if ((rc = flac_gather_launch(ctx, D.d_frames, D.nfr, D.channels, D.d_rowoff, reinterpret_cast<const int *>(ctx->tmp_buf3.p), rows, D.scratch16))) return rc;
+                if ((rc = ctx_end_kernel(ctx, "k_flac_gather", 2 * D.tot_elems * 4))) return rc;
+            }
+        } else if (bytes) AUKIT_HIP_CHECK(hipMemcpyAsync(rows, ctx->tmp_buf.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));   // the first design's rows
+        for (size_t i = 0; i < G.size(); i++) {
+            F[G[i]].frames = D.row_len[i * (size_t)D.channels];
+            F[G[i]].row = at + 4 * D.row_off[i * (size_t)D.channels];
+        }
+        rows_end = at + bytes + 64;
+    }
+    if (bad != ~0u) return fail(bad_code, "%s (stream %u)", bad_msg.c_str(), bad);
+    return AUKIT_OK;
 }
 
 static void frames_from_brief(FlacDecoded &D) {

@@ -1,0 +1,26 @@
+// flac_mixed.h — the FLAC members of aukit_decode_resample_mixed (AUKIT_OPT_MIXED_FRAME_CODECS): what resample_mixed.hip asks of flac.hip, and the
+// segment copier flac.hip borrows from streamset.hip.  Host only.  (A header of its own: flac_dev.h and mixed_plan.h each have a `Carve`.)
+#pragma once
+#include <array>
+#include "common.h"
+
+namespace aukit {
+
+// one FLAC stream of a mixed batch: its STREAMINFO's channel count, depth and rate (flac_mixed_headers); its chained length and where channel 0's
+// int32 row starts, in bytes from ctx->fmix_rows (flac_mixed_decode) — a multiple of 16; channel c lies c * round_up(max(frames, 1), 4) elements on
+struct FlacMixedStream { int channels = 0, depth = 0; double rate = 0; uint64_t frames = 0, row = 0; };
+
+// The header pass: k_flac_header<true> over the streams `list` names (batch order) and no other byte of the batch, one read-back.  What aukit.flac
+// refuses of a header is refused with its words, and a depth of 32 as AUKIT_E_UNSUPPORTED, the stream's index in the batch appended either way
+int flac_mixed_headers(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F);
+// Groups the streams by (channels, depth), compacts every group's bytes back to back into ctx->fmix_src (one launch of k_sset_repack for all groups),
+// and runs flac_decode_rows on a temporary batch per group; the rows of all groups end in ctx->fmix_rows.  Writes context scratch only.  A stream whose
+// chain ends in an error fails the call with flac_err_msg's words, a group whose rows would be doubles with AUKIT_E_UNSUPPORTED, the stream named —
+// of several offenders the one with the lowest index in the batch
+int flac_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F);
+
+// streamset.hip: k_sset_repack as a plain segment copier — {source offset, destination offset, bytes} each (bytes below 2^30), src + offset ->
+// dst + offset, on ctx->stream; the kernel's tables go to `table`.  Timed under the kernel's name
+int segments_copy(aukit_ctx *ctx, const unsigned char *src, unsigned char *dst, const std::vector<std::array<uint64_t, 3>> &segments, DevBuf &table);
+
+}  // namespace aukit

@@ -5,7 +5,9 @@
 // it), and its QOA and IMA-ADPCM streams as int16 rows, one per channel, beside them (the walks and k_qoa_wave of qoa.hip on the QOA streams only;
 // k_ima_mixed of codecs.hip, a lane per block with the block's own geometry) — and, on a context that asked for them (AUKIT_OPT_MIXED_CODECS), the
 // MS-ADPCM blocks of WAV files (aukit.msadpcm, :1283-1353) as int16 rows among those: k_ms_mixed of msadpcm_mixed.hip, a run of blocks of one stream per
-// workgroup.
+// workgroup.  And, on a context that asked for them (AUKIT_OPT_MIXED_FRAME_CODECS), whole FLAC files (aukit.flac, :311-619, :1657): their headers are read
+// in one pass, each (channels, depth) group's bytes are compacted and decoded by the frame-parallel decoder of flac.hip (flac_mixed.h) — inside
+// mix_validate, because a FLAC stream's length is known only once its frames are chained — and the decoder's int32 rows wait in a buffer of their own.
 //
 // k_resample (resample.hip) takes format, channel count and ratio from the launch-uniform ResampleParams; k_resample_mixed is its sibling that takes
 // them per tile.  The host plans
@@ -21,13 +23,14 @@
 //   (3) either every channel goes to its row, or ((0 + ch1) + ch2 ...) / cn goes to row 0 (Audio:mono on the clamped values) — coalesced stores.
 // fp64 in the reference's operation order whatever the storage type; F32 rounds once, at the store.
 //
-// The host half reads as the call's phases: mix_validate (the QOA header read-back inside it), mix_classes, the scratch layout, the int16-row
+// The host half reads as the call's phases: mix_validate (the FLAC decode and the QOA header read-back inside it), mix_classes, the scratch layout, the int16-row
 // pre-passes (QOA and IMA jobs, MS-ADPCM units, and the read-back of the IMA and MS-ADPCM flags), the DFPWM row pre-pass, segments and tiles, the launch.  What the call shares
 // with aukit_stream_decode_mixed is in mixed_plan.h.
 #include <algorithm>
 #include <tuple>
 #include "mixed_plan.h"
 #include "resample_dev.h"
+#include "flac_mixed.h"
 
 namespace aukit {
 
@@ -40,12 +43,13 @@ struct ImaMixJob { unsigned long long src_off, row_off; unsigned nbytes, stream;
 int ima_mixed_decode(aukit_ctx *ctx, const unsigned char *src, const void *d_jobs, uint64_t njobs, short *rows, unsigned *flag, uint64_t bytes);
 // (the MS-ADPCM streams' pre-pass, k_ms_mixed of msadpcm_mixed.hip, and its unit planner: mixed_plan.h)
 
+constexpr int MIX_SRC_I32 = 101;  // MixClass::codec of a FLAC class (AUKIT_OPT_MIXED_FRAME_CODECS): the window comes from the decoder's int32 rows in ctx->fmix_rows
 constexpr int MIX_SRC_I16 = 100;  // MixClass::codec of a QOA or IMA-ADPCM class: the window comes from int16 rows in the scratch behind MixParams::rows, one per channel
 
 struct MixClass {
     double ratio, rcp;     // x = (i - 1) / ratio + 1
-    double g711_scale;     // 1 / 0x2000  (:1379)
-    int codec;             // AUKIT_CODEC_PCM / AUKIT_CODEC_G711 / AUKIT_CODEC_DFPWM (int8 rows in MixParams::rows) / MIX_SRC_I16
+    double g711_scale;     // 1 / 0x2000  (:1379); a FLAC class (MIX_SRC_I32): 2^-depth, aukit.flac's `s / 2^sampleDepth`  (:505)
+    int codec;             // AUKIT_CODEC_PCM / AUKIT_CODEC_G711 / AUKIT_CODEC_DFPWM (int8 rows in MixParams::rows) / MIX_SRC_I16 / MIX_SRC_I32
     int bytes;             // per sample
     int data_type, big_endian, planar, ulaw;
     int channels;
@@ -57,7 +61,10 @@ static_assert(sizeof(MixClass) == 64, "MixClass layout");
 struct MixSeg {
     unsigned long long src_off;  // the stream's first byte, relative to the batch's data (a DFPWM stream: of its int8 row, relative to MixParams::rows;
                                  // an int16-row stream: the first BYTE of its channel 0's row, relative to MixParams::rows too, a multiple of 16 —
-                                 // channel c lies c * stride elements on, stride = round_up(max(frames, 1), 8))
+                                 // channel c lies c * stride elements on, stride = round_up(max(frames, 1), 8); an int32-row stream: the
+                                 // same with stride = round_up(max(frames, 1), 4) — its rows lie in a buffer of their own (ctx->fmix_rows, which
+                                 // outlives what the other pre-passes and lazy_drop do to ctx->tmp_buf), and the offset is that address minus
+                                 // MixParams::rows modulo 2^64: MixParams keeps its size, and the kernels of before their kernel arguments)
     unsigned long long out_off;  // element offset of output channel 0, output index 0
     unsigned frames;             // table indices 1 .. frames are valid
     unsigned n_out;
@@ -142,11 +149,33 @@ AUKIT_DEV int mixed_stage_i16(const short *row, long long g0, int n_stage, doubl
     return head;
 }
 
+// An int32-row class's window of ONE channel (a FLAC stream: the decoder's final integers, the sign wrap of :504 done): n_stage elements of the row
+// from element g0 on, in the shape of mixed_stage_i16 — 16 bytes per lane from the aligned address at or below the first element, four int32 each,
+// (double)x * scale with scale = 2^-depth: exact, so it is the reference's quotient x / 2^depth to the bit; the vector's four doubles to slots
+// 4 v .. 4 v + 3 (the window's first element lands in slot `head`, the same for every channel: rows start at multiples of 16 bytes).  A row's last
+// vector ends inside its stride of round_up(frames, 4) elements (host): no load leaves the allocation, no safe_lo / safe_hi fallback.
+AUKIT_DEV int mixed_stage_i32(const int *row, long long g0, int n_stage, double scale, double *st, int tid) {
+    const int *a0 = row + g0;
+    const int *al = (const int *)((uintptr_t)a0 & ~(uintptr_t)15);
+    const int head = (int)(a0 - al);
+    const int nvec = (head + n_stage + 3) >> 2;
+    for (int v = tid; v < nvec; v += 256) {
+        const int4 u = *reinterpret_cast<const int4 *>(al + 4 * (size_t)v);
+        double2 *o = reinterpret_cast<double2 *>(st + 4 * v);
+        o[0] = make_double2((double)u.x * scale, (double)u.y * scale);
+        o[1] = make_double2((double)u.z * scale, (double)u.w * scale);
+    }
+    return head;
+}
+
 // DF: the batch has a DFPWM class.  Its staging path is compiled into an instantiation of its own, so that a PCM / G.711 batch runs the kernel
 // without it: the same code, registers and residency as before there was one.  An int16-row class (QOA, IMA-ADPCM) likewise: its staging path is in
 // k_resample_mixed_i16, the same text compiled a second time (resample_mixed_body.h), and k_resample_mixed's instantiations are the ones they were.
+// An int32-row class (FLAC) a third time: k_resample_mixed_i32 has both row paths — a library has QOA and FLAC files together — and is launched only
+// where the batch has a FLAC class.
 #define AUKIT_MIXED_KERNEL k_resample_mixed
 #define AUKIT_MIXED_I16 false
+#define AUKIT_MIXED_I32 false
 #include "resample_mixed_body.h"
 #undef AUKIT_MIXED_KERNEL
 #undef AUKIT_MIXED_I16
@@ -154,7 +183,13 @@ AUKIT_DEV int mixed_stage_i16(const short *row, long long g0, int n_stage, doubl
 #define AUKIT_MIXED_I16 true
 #include "resample_mixed_body.h"
 #undef AUKIT_MIXED_KERNEL
+#undef AUKIT_MIXED_I32
+#define AUKIT_MIXED_KERNEL k_resample_mixed_i32
+#define AUKIT_MIXED_I32 true
+#include "resample_mixed_body.h"
+#undef AUKIT_MIXED_KERNEL
 #undef AUKIT_MIXED_I16
+#undef AUKIT_MIXED_I32
 
 // ------------------------------------------------------------------ host
 static inline uint64_t mixed_count(uint64_t n_in, double ratio) {  // `for i = 1, #data * ratio`  :659-664
@@ -246,9 +281,11 @@ struct MixStreams {
     std::vector<double> rate;
     std::vector<uint32_t> q_list;  // the QOA streams, in batch order
     std::vector<QoaMixedStream> Q;
+    std::vector<uint32_t> f_list;  // the FLAC streams, in batch order (AUKIT_OPT_MIXED_FRAME_CODECS), and what their headers and their decode said
+    std::vector<FlacMixedStream> F;
     std::vector<uint64_t> frames, lens;
     uint64_t in_bytes = 0, out_elems = 0;  // in_bytes: what the resample launch reads — a DFPWM stream's int8 row, not its source bytes
-    bool has_df = false, has_i16 = false;
+    bool has_df = false, has_i16 = false, has_i32 = false;
 };
 
 static int mix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, double new_rate, int interp, int mono, int dtype,
@@ -259,7 +296,18 @@ static int mix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
     if (!(new_rate > 0)) return fail(AUKIT_E_ARG, "bad sample rate");
     const uint32_t n = in->n;
     // AUKIT_OPT_MIXED_CODECS: MS-ADPCM joins the list on a context that asked for it; without the bit the call answers in the words of before
-    if ((ctx->mixed_codecs >> AUKIT_CODEC_MSADPCM) & 1u)
+    // AUKIT_OPT_MIXED_FRAME_CODECS: FLAC likewise, under an option of its own; its clause stands behind option 5's
+    const bool with_flac = (ctx->mixed_frame_codecs >> AUKIT_CODEC_FLAC) & 1u;
+    if (with_flac && ((ctx->mixed_codecs >> AUKIT_CODEC_MSADPCM) & 1u))
+        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_MSADPCM, AUKIT_CODEC_FLAC},
+                                "stream %u: codec %d has its own loader (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, "
+                                "AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_MIXED_CODECS, AUKIT_CODEC_MSADPCM and, under "
+                                "AUKIT_OPT_MIXED_FRAME_CODECS, AUKIT_CODEC_FLAC)");
+    else if (with_flac)
+        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_FLAC},
+                                "stream %u: codec %d has its own loader (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, "
+                                "AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_MIXED_FRAME_CODECS, AUKIT_CODEC_FLAC)");
+    else if ((ctx->mixed_codecs >> AUKIT_CODEC_MSADPCM) & 1u)
         rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_MSADPCM},
                                 "stream %u: codec %d has its own loader (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, "
                                 "AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_MIXED_CODECS, AUKIT_CODEC_MSADPCM)");
@@ -275,7 +323,16 @@ static int mix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
         S.ch[s] = descs[s].channels;
         S.rate[s] = descs[s].sample_rate;
         if (codec == AUKIT_CODEC_QOA) S.q_list.push_back(s);
+        if (codec == AUKIT_CODEC_FLAC) { S.f_list.push_back(s); S.has_i32 = true; }
         if (codec == AUKIT_CODEC_QOA || codec == AUKIT_CODEC_ADPCM_WAV || codec == AUKIT_CODEC_MSADPCM) S.has_i16 = true;
+    }
+    // FLAC: only `codec` of the descriptor is read.  A stream's length is known only once its frames are chained, so the whole decode is here: the
+    // header pass and its read-back — what aukit.flac refuses of a header comes first, with its words —, then group by group the decoder, whose rows
+    // stay in ctx->fmix_rows.  It writes context scratch and nothing of `*out`; it comes before the QOA count pass, which writes ctx->tmp_buf3 too
+    if (!S.f_list.empty()) {
+        AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
+        if ((rc = flac_mixed_headers(ctx, in, S.f_list, S.F)) || (rc = flac_mixed_decode(ctx, in, S.f_list, S.F))) return rc;
+        for (size_t k = 0; k < S.f_list.size(); k++) { S.ch[S.f_list[k]] = S.F[k].channels; S.rate[S.f_list[k]] = S.F[k].rate; }
     }
     // QOA: the count pass of the device walk on these streams only, and the header read-back — what a header is refused for comes first, with
     // aukit.qoa's words.  It writes ctx->tmp_buf3 and nothing of `*out`.
@@ -288,10 +345,13 @@ static int mix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
     if ((rc = mixed_check_channels(n, mono, [&](uint32_t s) { return S.ch[s]; }))) return rc;
     S.frames.resize(n);
     S.lens.resize(n);
-    for (uint32_t s = 0, qk = 0; s < n; s++) {
+    for (uint32_t s = 0, qk = 0, fk = 0; s < n; s++) {
         const uint64_t nb = in->off[s + 1] - in->off[s];
         const int codec = descs[s].codec;
-        if (codec == AUKIT_CODEC_QOA) {  // what decode_qoa_audio (qoa.hip) refuses of a walk
+        if (codec == AUKIT_CODEC_FLAC) {  // (its headers and its frames were the check)
+            S.frames[s] = S.F[fk++].frames;
+            rc = check_mixed_rows(S.rate[s], new_rate, S.frames[s], &S.lens[s]);
+        } else if (codec == AUKIT_CODEC_QOA) {  // what decode_qoa_audio (qoa.hip) refuses of a walk
             const QoaMixedStream &q = S.Q[qk++];
             S.frames[s] = q.L;
             if (q.raised) rc = fail(AUKIT_E_LUA, "data string too short");
@@ -308,6 +368,7 @@ static int mix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
         if (rc) return fail_for_stream(rc, s);
         if (codec == AUKIT_CODEC_DFPWM) { S.has_df = true; S.in_bytes += mixed_dfpwm_fed(nb) * 8; }
         else if (codec == AUKIT_CODEC_QOA || codec == AUKIT_CODEC_ADPCM_WAV || codec == AUKIT_CODEC_MSADPCM) S.in_bytes += S.frames[s] * (uint64_t)S.ch[s] * 2;
+        else if (codec == AUKIT_CODEC_FLAC) S.in_bytes += S.frames[s] * (uint64_t)S.ch[s] * 4;
         else S.in_bytes += nb;
         S.out_elems += S.lens[s] * (uint64_t)(mono ? 1 : S.ch[s]);
     }
@@ -328,24 +389,26 @@ static int mix_classes(aukit_ctx *ctx, const aukit_codec_desc *descs, uint32_t n
     ClassIndex<std::tuple<int, int, int, int, int, int, int, double>> index;
     std::vector<uint64_t> class_max;  // per class: the largest output count
     T.cls_of.resize(n);
-    for (uint32_t s = 0; s < n; s++) {
+    for (uint32_t s = 0, fk = 0; s < n; s++) {
         const aukit_codec_desc &d = descs[s];
         const bool pcm = d.codec == AUKIT_CODEC_PCM;
+        const bool i32 = d.codec == AUKIT_CODEC_FLAC;  // (keyed by channels, depth and sample rate)
+        const int fdepth = i32 ? S.F[fk++].depth : 0;
         const int planar = (pcm && d.channels > 1 && !d.interleaved) ? 1 : 0;  // aukit.lua:1156-1169
         const bool g711 = d.codec == AUKIT_CODEC_G711;  // (a DFPWM class is keyed by codec, channels and sample rate)
         const bool i16 = d.codec == AUKIT_CODEC_QOA || d.codec == AUKIT_CODEC_ADPCM_WAV || d.codec == AUKIT_CODEC_MSADPCM;  // (one kind of class for all three: keyed by channels and sample rate)
-        const int kcodec = i16 ? MIX_SRC_I16 : d.codec, kch = S.ch[s];
+        const int kcodec = i16 ? MIX_SRC_I16 : i32 ? MIX_SRC_I32 : d.codec, kch = S.ch[s];
         bool fresh;
-        const unsigned c = T.cls_of[s] = index.of({kcodec, pcm ? d.bit_depth : i16 ? 16 : 8, pcm ? d.data_type : 0, pcm ? (d.big_endian ? 1 : 0) : 0, planar, kch,
+        const unsigned c = T.cls_of[s] = index.of({kcodec, pcm ? d.bit_depth : i16 ? 16 : i32 ? fdepth : 8, pcm ? d.data_type : 0, pcm ? (d.big_endian ? 1 : 0) : 0, planar, kch,
                                                    g711 ? (d.ulaw ? 1 : 0) : 0, S.rate[s]}, &fresh);
         if (fresh) {
             MixClass K;
             memset(&K, 0, sizeof K);
             K.ratio = new_rate / S.rate[s];
             K.rcp = 1.0 / K.ratio;
-            K.g711_scale = 1.0 / 8192.0;  // m / 0x2000  :1379
+            K.g711_scale = i32 ? std::ldexp(1.0, -fdepth) : 1.0 / 8192.0;  // m / 0x2000  :1379; s / 2^sampleDepth  :505
             K.codec = kcodec;
-            K.bytes = pcm ? d.bit_depth / 8 : i16 ? 2 : 1;
+            K.bytes = pcm ? d.bit_depth / 8 : i16 ? 2 : i32 ? 4 : 1;
             K.data_type = pcm ? d.data_type : 0;
             K.big_endian = pcm && d.big_endian ? 1 : 0;
             K.planar = planar;
@@ -506,12 +569,12 @@ static uint64_t mix_count_tiles(const MixStreams &S, const MixClasses &T) {
     for (size_t s = 0; s < S.lens.size(); s++) nt += (S.lens[s] + T.tile_out[T.cls_of[s]] - 1) / T.tile_out[T.cls_of[s]];
     return nt;
 }
-static void mix_tiles(const aukit_batch *in, const aukit_codec_desc *descs, const MixStreams &S, const MixClasses &T, const MixDfRows &D, const MixI16Rows &R,
+static void mix_tiles(const aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, const MixStreams &S, const MixClasses &T, const MixDfRows &D, const MixI16Rows &R,
                       const MixScratch &L, const aukit_audio *a, std::vector<MixSeg> &segs, std::vector<MixTile> &tiles) {
-    for (uint32_t s = 0; s < in->n; s++) {
+    for (uint32_t s = 0, fk = 0; s < in->n; s++) {
         MixSeg &g = segs[s];
         const bool i16 = descs[s].codec == AUKIT_CODEC_QOA || descs[s].codec == AUKIT_CODEC_ADPCM_WAV || descs[s].codec == AUKIT_CODEC_MSADPCM;
-        g.src_off = descs[s].codec == AUKIT_CODEC_DFPWM ? D.row[s] : i16 ? L.i16_at + 2 * R.row[s] : in->off[s];
+        g.src_off = descs[s].codec == AUKIT_CODEC_DFPWM ? D.row[s] : i16 ? L.i16_at + 2 * R.row[s] : descs[s].codec == AUKIT_CODEC_FLAC ? (uint64_t)((uintptr_t)ctx->fmix_rows.p + S.F[fk++].row - (uintptr_t)ctx->tmp_buf.p) : in->off[s];
         g.out_off = a->row_off[s];
         g.frames = (unsigned)S.frames[s];
         g.n_out = (unsigned)S.lens[s];
@@ -522,8 +585,8 @@ static void mix_tiles(const aukit_batch *in, const aukit_codec_desc *descs, cons
     }
 }
 
-// ---- phase 7: the launch.  The DFPWM and the int16-row staging live in instantiations of their own: every other batch launches the kernels it
-// always did
+// ---- phase 7: the launch.  The DFPWM, the int16-row and the int32-row staging live in instantiations of their own: every other batch launches the
+// kernels it always did
 static int mix_launch(aukit_ctx *ctx, const aukit_batch *in, const MixStreams &S, const MixClasses &T, const std::vector<MixSeg> &segs, const std::vector<MixTile> &tiles,
                       const aukit_audio *a, int interp, int mono, int dtype) {
     MixParams P;
@@ -532,7 +595,9 @@ static int mix_launch(aukit_ctx *ctx, const aukit_batch *in, const MixStreams &S
     const size_t lds = T.lds + (S.has_df ? 2048 : 0);  // counted only then: a PCM / G.711 batch keeps its LDS size, its residency and its grid
     static const char *names[] = {"k_resample_mixed<none>", "k_resample_mixed<linear>", "k_resample_mixed<cubic>"};
     return mixed_launch(ctx, in, a, T.classes, segs, tiles, P, lds, names[interp], S.in_bytes + S.out_elems * dtype_size(dtype), [&](unsigned grid) {
-        if (S.has_i16 && S.has_df) AUKIT_MIXED_LAUNCH(ctx, k_resample_mixed_i16, interp, dtype, grid, lds, P, true);
+        if (S.has_i32 && S.has_df) AUKIT_MIXED_LAUNCH(ctx, k_resample_mixed_i32, interp, dtype, grid, lds, P, true);
+        else if (S.has_i32) AUKIT_MIXED_LAUNCH(ctx, k_resample_mixed_i32, interp, dtype, grid, lds, P, false);
+        else if (S.has_i16 && S.has_df) AUKIT_MIXED_LAUNCH(ctx, k_resample_mixed_i16, interp, dtype, grid, lds, P, true);
         else if (S.has_i16) AUKIT_MIXED_LAUNCH(ctx, k_resample_mixed_i16, interp, dtype, grid, lds, P, false);
         else if (S.has_df) AUKIT_MIXED_LAUNCH(ctx, k_resample_mixed, interp, dtype, grid, lds, P, true);
         else AUKIT_MIXED_LAUNCH(ctx, k_resample_mixed, interp, dtype, grid, lds, P, false);
@@ -574,6 +639,6 @@ extern "C" int aukit_decode_resample_mixed(aukit_ctx *ctx, const aukit_batch *in
     std::vector<MixSeg> segs(n);
     std::vector<MixTile> tiles;
     tiles.reserve((size_t)nt);
-    mix_tiles(in, descs, S, T, D, R, L, a, segs, tiles);
+    mix_tiles(ctx, in, descs, S, T, D, R, L, a, segs, tiles);
     return mix_launch(ctx, in, S, T, segs, tiles, a, interp, mono, dtype);
 }

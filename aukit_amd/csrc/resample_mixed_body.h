@@ -1,12 +1,15 @@
-// resample_mixed_body.h — the body of k_resample_mixed (resample_mixed.hip, which explains it), included TWICE there: as k_resample_mixed, and, with the
-// staging path of the int16-row classes compiled in, as k_resample_mixed_i16.  Two kernels of one text rather than one more template parameter or a shared
-// device function: k_resample_mixed keeps its template arguments and — checked on the disassembly — its instructions (reached through an inlined function
-// the same text came out three instructions longer and scheduled differently).
+// resample_mixed_body.h — the body of k_resample_mixed (resample_mixed.hip, which explains it), included THREE times there: as k_resample_mixed, with the
+// staging path of the int16-row classes compiled in as k_resample_mixed_i16, and with that of the int32-row classes (FLAC) beside it as
+// k_resample_mixed_i32.  Kernels of one text rather than one more template parameter or a shared device function: k_resample_mixed keeps its template
+// arguments and — checked on the disassembly — its instructions (reached through an inlined function the same text came out three instructions longer
+// and scheduled differently).
 //   AUKIT_MIXED_KERNEL  the kernel's name
 //   AUKIT_MIXED_I16     true: the batch has an int16-row class (QOA, IMA-ADPCM)
+//   AUKIT_MIXED_I32     true: the batch has an int32-row class (FLAC); such a kernel has the int16-row path as well
 template <int INTERP, typename OUT_T, bool DF>
 __global__ __launch_bounds__(256) void AUKIT_MIXED_KERNEL(const MixParams P) {
     constexpr bool I16 = AUKIT_MIXED_I16;
+    constexpr bool I32 = AUKIT_MIXED_I32;
     extern __shared__ double sm_all[];
     const int tid = threadIdx.x;
     double *const sm = sm_all + (DF ? 256 : 0);
@@ -71,6 +74,10 @@ __global__ __launch_bounds__(256) void AUKIT_MIXED_KERNEL(const MixParams P) {
                 const unsigned stride = (max(sg.frames, 1u) + 7u) & ~7u;
                 const short *row = reinterpret_cast<const short *>(P.rows + sg.src_off);
                 for (int c = 0; c < C; c++) shift = mixed_stage_i16(row + (size_t)c * stride, g0, n_stage, sm + c * cap, tid);
+            } else if (I32 && K.codec == MIX_SRC_I32) {
+                const unsigned stride = (max(sg.frames, 1u) + 3u) & ~3u;
+                const int *row = reinterpret_cast<const int *>((uintptr_t)P.rows + (uintptr_t)sg.src_off);  // (modulo 2^64: the rows lie in a buffer of their own)
+                for (int c = 0; c < C; c++) shift = mixed_stage_i32(row + (size_t)c * stride, g0, n_stage, K.g711_scale, sm + c * cap, tid);
             } else if (DF && K.codec == AUKIT_CODEC_DFPWM) {
                 const signed char *row = P.rows + sg.src_off;
                 if (C == 1) mixed_stage_i8<1>(row, g0, n_stage, 1, cap, sm_all, sm, tid);

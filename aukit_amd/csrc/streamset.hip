@@ -59,6 +59,7 @@
 #include "mixed_plan.h"
 #include "ms_geom.h"
 #include "stream_mixed_qoa.h"
+#include "flac_mixed.h"
 
 namespace aukit {
 
@@ -102,6 +103,33 @@ __global__ __launch_bounds__(256) void k_sset_repack(const unsigned char *__rest
             d4[v] = make_uint4(s1[0], s1[1], s1[2], s1[3]);
         }
     }
+}
+
+// the kernel as a plain segment copier (flac_mixed.h): the mixed decode call compacts its FLAC members' bytes with it
+int segments_copy(aukit_ctx *ctx, const unsigned char *src, unsigned char *dst, const std::vector<std::array<uint64_t, 3>> &segments, DevBuf &table) {
+    int rc;
+    std::vector<SSetSeg> segs;
+    std::vector<SSetPiece> pieces;
+    uint64_t moved = 0;
+    for (const auto &g : segments) {
+        if (g[2] >= 0x40000000ull) return fail(AUKIT_E_UNSUPPORTED, "a segment of 2^30 bytes or more");
+        if (!g[2]) continue;
+        for (unsigned off = 0; off < (unsigned)g[2]; off += SSET_PIECE) pieces.push_back(SSetPiece{(unsigned)segs.size(), off});
+        segs.push_back(SSetSeg{g[0], g[1], (unsigned)g[2], 0u});
+        moved += g[2];
+    }
+    if (pieces.empty()) return AUKIT_OK;
+    if (pieces.size() > 0x7FFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many pieces");
+    const size_t seg_bytes = (size_t)round_up(segs.size() * sizeof(SSetSeg), 64);
+    if ((rc = table.ensure(seg_bytes + pieces.size() * sizeof(SSetPiece)))) return rc;
+    if (&table == &ctx->seg_buf || &table == &ctx->tile_buf) ctx->plan_key.clear();
+    char *T = reinterpret_cast<char *>(table.p);
+    if ((rc = h2d_table(ctx, T, segs.data(), segs.size() * sizeof(SSetSeg))) || (rc = h2d_table(ctx, T + seg_bytes, pieces.data(), pieces.size() * sizeof(SSetPiece)))) return rc;
+    if ((rc = ctx_begin_kernel(ctx))) return rc;
+    hipLaunchKernelGGL(k_sset_repack, dim3((unsigned)pieces.size()), dim3(256), 0, ctx->stream, src, src, dst, reinterpret_cast<const SSetSeg *>(T),
+                       reinterpret_cast<const SSetPiece *>(T + seg_bytes), (unsigned)pieces.size());
+    AUKIT_HIP_CHECK(hipGetLastError());
+    return ctx_end_kernel(ctx, "k_sset_repack", 2 * moved);
 }
 
 // one newly decided chunk: `len` samples of each of `channels` rows of the decode's audio, `src_stride` elements apart from element `src` on, become

@@ -581,8 +581,9 @@ end
 -- count and sample rate.  IMA-ADPCM WAV files stay refused here (the batch API, aukit_decode_resample_mixed with AUKIT_CODEC_ADPCM_WAV, takes them).
 local MAGIC = {{"^RIFF....WAVE", 0}, {"^FORM....AIF[FC]", 1}, {"^%.snd", 2}}
 local load_many_adpcm = false   -- the fifth argument of aukit.load_many for the call in flight (the wrapper behind the function sets it)
+local load_many_flac = false    -- the sixth, likewise
 function aukit.load_many(files, sampleRate, interpolation, mono)
-    local adpcm = load_many_adpcm
+    local adpcm, flac = load_many_adpcm, load_many_flac
     expect(1, files, "table")
     sampleRate = expect(2, sampleRate, "number", "nil") or 48000
     interpolation = expect(3, interpolation, "string", "nil") or aukit.defaultInterpolation
@@ -610,6 +611,11 @@ function aukit.load_many(files, sampleRate, interpolation, mono)
             parts[i] = f
             offs[i] = offs[i - 1] + #f
             infos[i] = {bitDepth = 16, dataType = "signed"}
+        elseif flac and f:sub(1, 4) == "fLaC" then   -- on request: the whole file is the payload (channel count, depth and rate are its STREAMINFO's); the info table is aukit.flac's
+            descs[i - 1] = desc {codec = "flac"}
+            parts[i] = f
+            offs[i] = offs[i - 1] + #f
+            infos[i] = {dataType = "signed"}
         else
         local kind
         for _, m in ipairs(MAGIC) do if f:find(m[1]) then kind = m[2] break end end
@@ -630,9 +636,12 @@ function aukit.load_many(files, sampleRate, interpolation, mono)
     local o = ffi.new("aukit_audio*[1]")
     -- adpcm: AUKIT_OPT_MIXED_CODECS (5) with bit 1 << AUKIT_CODEC_MSADPCM for this one call; the shim's context sets no other bit, so 0 puts it back
     if adpcm then check(C.aukit_ctx_set_option(ctx(), 5, 2 ^ CODEC.msadpcm)) end
+    -- flac: AUKIT_OPT_MIXED_FRAME_CODECS (11) with bit 1 << AUKIT_CODEC_FLAC, likewise
+    if flac then check(C.aukit_ctx_set_option(ctx(), 11, 2 ^ CODEC.flac)) end
     local rc = C.aukit_decode_resample_mixed(ctx(), batch, descs, n, sampleRate, INTERP[interpolation], mono and 1 or 0, F64, o)
     local words = rc ~= 0 and ffi.string(C.aukit_last_error()) or nil
     if adpcm then C.aukit_ctx_set_option(ctx(), 5, 0) end
+    if flac then C.aukit_ctx_set_option(ctx(), 11, 0) end
     if words then error(words, 2) end
     local whole = ffi.gc(o[0], C.aukit_audio_free)
     local cnt, ch, rate, dt, tot = ffi.new("uint32_t[1]"), ffi.new("int[1]"), ffi.new("double[1]"), ffi.new("int[1]"), ffi.new("uint64_t[1]")
@@ -660,6 +669,18 @@ do
         load_many_adpcm = expect(5, adpcm, "boolean", "nil") or false
         local ok, res = pcall(four, files, sampleRate, interpolation, mono)
         load_many_adpcm = false
+        if not ok then error(res, 2) end
+        return res
+    end
+end
+-- aukit.load_many(files, sampleRate, interpolation, mono, adpcm, flac): `flac` = true takes whole FLAC files too (aukit.flac, :1657;
+-- AUKIT_OPT_MIXED_FRAME_CODECS for this one call); nil / false: such a file is refused by index, as before
+do
+    local five = aukit.load_many
+    aukit.load_many = function(files, sampleRate, interpolation, mono, adpcm, flac)
+        load_many_flac = expect(6, flac, "boolean", "nil") or false
+        local ok, res = pcall(five, files, sampleRate, interpolation, mono, adpcm)
+        load_many_flac = false
         if not ok then error(res, 2) end
         return res
     end

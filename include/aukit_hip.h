@@ -186,12 +186,18 @@ typedef enum {
                                    the call to QOA; this option opens it to nothing else, and opens neither aukit_decode_resample_mixed (which takes
                                    QOA without being asked) nor aukit_streamset_open (a stream set has option 10 for the codec).  With 0 every call
                                    answers exactly as before. */
-    AUKIT_OPT_STREAMSET_FRAME_CODECS = 10 /* a third mask of aukit_streamset_open's, read by that call alone and only while it opens (an open set keeps
+    AUKIT_OPT_STREAMSET_FRAME_CODECS = 10,/* a third mask of aukit_streamset_open's, read by that call alone and only while it opens (an open set keeps
                                    what it was opened with): a bit mask of 1 << codec, 0 by default, exactly one bit known, 1 << AUKIT_CODEC_QOA
                                    (aukit.stream.qoa's streams as members of a set, see that call); any other bit is AUKIT_E_UNSUPPORTED, the codec
                                    named (or "bit N"), and the context keeps the mask it had.  Options 7 and 8 know their one bit each and refuse
                                    this one by name; options 5, 6 and 9 are not needed for a set and open it to nothing; this option opens neither
                                    mixed call.  With 0 every call answers exactly as before. */
+    AUKIT_OPT_MIXED_FRAME_CODECS = 11 /* a second mask of aukit_decode_resample_mixed's, the only call that reads it: a bit mask of 1 << codec, 0 by
+                                   default, exactly one bit known, 1 << AUKIT_CODEC_FLAC (whole .flac files as streams of a mixed batch, see that
+                                   call); any other bit is AUKIT_E_UNSUPPORTED, the codec named (or "bit N"), and the context keeps the mask it had.
+                                   A second option and not a second bit of option 5, which knows its one bit and refuses this one by name.  It opens
+                                   neither aukit_stream_decode_mixed nor aukit_streamset_open to anything.  With 0 every call answers exactly as
+                                   before. */
 } aukit_option;
 int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);
 /* counters of the most recent call that produced them (AUKIT_OPT_COLLECT_STATS = 1) */
@@ -290,6 +296,18 @@ int aukit_decode_resample(aukit_ctx *ctx, const aukit_batch *in, const aukit_cod
  *                         streams'.  Two exceptions to "what the stream's own call gives", both AUKIT_E_UNSUPPORTED naming the stream and
  *                         pointing to aukit_decode_resample: a delta of 2^21 or more anywhere in the stream (where the single call leaves its
  *                         int32 path; no encoder writes one), and a coefficient pair with |c1| + |c2| >= 65536.
+ * and a seventh only on a context that asked for it, AUKIT_OPT_MIXED_FRAME_CODECS with bit 1 << AUKIT_CODEC_FLAC (without it the codec is refused
+ * by name, in the words of before the option; with it a further codec's refusal names this clause behind option 5's):
+ *   AUKIT_CODEC_FLAC      only `codec` is read: the stream is a whole .flac file, aukit.flac (aukit.lua:311-619, :1657), and its channel count, bit
+ *                         depth and sample rate are its STREAMINFO's (without `mono` it is the header's channel count that must agree with the
+ *                         other streams').  A FLAC stream's length is known only once its frames are chained, so the whole FLAC decode runs before
+ *                         `*out` is touched: a header pass over the FLAC streams alone, then, for every (channels, depth) group of them, the
+ *                         group's bytes compacted into a context-owned buffer and decoded there by the frame-parallel decoder of
+ *                         aukit_decode_resample (any mix of sample rates in a group), its int32 rows kept in a context-owned row buffer that the
+ *                         one resample launch reads with aukit.flac's `s / 2^depth`.  A header the reference refuses (magic, no STREAMINFO, a
+ *                         depth that is no multiple of 8, a string too short) and a frame it raises on fail the call with its words.  One
+ *                         exception to "what the stream's own call gives": a stream whose rows would be doubles — a depth of 32, a value beyond
+ *                         int32 — is AUKIT_E_UNSUPPORTED naming the stream and pointing to aukit_decode_resample.
  * Interpolation none / linear / cubic; any other codec or interpolation is AUKIT_E_UNSUPPORTED by name.  n_descs must be the batch's stream count;
  * without `mono` the streams must agree in channel count (AUKIT_E_ARG).  A stream whose own call would fail fails the whole call with that status
  * and message, the stream's index appended.  Ordering: everything that can refuse does so before `*out` is touched — the descriptor and length
