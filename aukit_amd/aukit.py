@@ -461,7 +461,7 @@ def au(data):  # aukit.lua:1639
 _MAGIC_KIND = {"wav": N.CONTAINER_WAV, "aiff": N.CONTAINER_AIFF, "au": N.CONTAINER_AU}
 
 
-def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm=False, stream_ms=False, stream_qoa=False, flac=False):
+def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm=False, stream_ms=False, stream_qoa=False, flac=False, stream_flac=False):
     """load_many's host half, up to the device call: every file sniffed by magic as `detect` does and walked by aukit_parse_container
     -> ([descriptor per file], [(first payload byte, byte count) per file], [info table per file]).  A file that is no WAV / AIFF / AU / QOA, or
     whose payload is none of PCM, G.711 and DFPWM, raises LuaError naming the file's index (0-based, the position in `files`).
@@ -487,7 +487,10 @@ def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm
     (aukit.stream.qoa's own figure stands, file_samples / sampleRate, :3336).  Without it such a file is refused by index in the words of before.
     `flac` (without `stream`): load_many's switch — a file `detect` calls "flac" is taken too, whole: the descriptor names the codec only (channel
     count, depth and rate are the file's STREAMINFO's) and the info table is aukit.flac's.  Without it such a file is refused by index in the words
-    of before."""
+    of before.
+    `stream_flac` (with `stream`): a file `detect` calls "flac" (magic "fLaC") is taken too, whole — the descriptor names the codec only (channel
+    count, depth and rate are the file's STREAMINFO's), the length is NaN (aukit.stream.flac's own figure stands, total samples / sampleRate,
+    :3190).  Without it such a file is refused by index in the words of before."""
     _expect(1, files, "table")
     takes = "PCM, G.711 and DFPWM" if stream_dfpwm else "PCM and G.711"
     if stream_ima and stream_ms:
@@ -533,6 +536,11 @@ def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm
             descs.append(B.make_desc(N.CODEC_QOA))
             ranges.append((0, len(f)))
             infos.append({"bitDepth": 16, "dataType": "signed"})   # what aukit.qoa sets
+            continue
+        if kind == "flac" and stream and stream_flac:
+            descs.append(B.make_desc(N.CODEC_FLAC))
+            ranges.append((0, len(f)))
+            infos.append(float("nan"))
             continue
         if kind == "flac" and flac and not stream:
             descs.append(B.make_desc(N.CODEC_FLAC))
@@ -928,7 +936,7 @@ class _StreamNS:
             it, length = self._run(d, p, mono, dtype, endless_empty=d.codec == N.CODEC_G711)
         return it, (length if math.isnan(c.length_seconds) else c.length_seconds)
 
-    def many(self, files, mono=None, adpcm=None, msadpcm=None, qoa=None):
+    def many(self, files, mono=None, adpcm=None, msadpcm=None, qoa=None, flac=None):
         """aukit.stream.wav / aiff / au (file, mono) for a LIST of whole files of any mix of containers, rates, PCM formats / G.711 / DFPWM /
         IMA-ADPCM WAV blocks (each file its own blockAlign; the raise behind a block whose header step index is above 88 included) and
         channel counts: the payload ranges go up as one batch, one aukit_stream_decode_mixed call computes every iterator call of every file, and
@@ -946,30 +954,43 @@ class _StreamNS:
         names the codec only (channel count and rate are its header's), its pair is what aukit.stream.qoa(file, mono) returns (length
         file_samples / sampleRate), and for this one call the context is opted in under an option of its own
         (AUKIT_OPT_STREAM_MIXED_FRAME_CODECS) and put back as it was behind it, also where the call is refused.  Without it such a file is refused
-        by index, as before."""
+        by index, as before.
+        FLAC files (magic "fLaC") are taken with `flac=True`, or the key "flac" of the options table: the file goes up whole under a descriptor
+        that names the codec only (channel count, depth and rate are its STREAMINFO's), its pair is what aukit.stream.flac(file, mono) returns
+        (length total samples / sampleRate), and for this one call the context is opted in under a third option
+        (AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS) and put back as it was behind it, also where the call is refused.  aukit.stream.flac ignores `mono`:
+        a FLAC file keeps its own channel count, so with `mono` only one-channel FLAC files join the list (a file with more is refused by
+        index).  Without the key such a file is refused by index, as before."""
         if isinstance(mono, dict):
-            if set(mono) - {"mono", "adpcm", "msadpcm", "qoa"}:
-                raise LuaError("bad argument #2 (unknown option " + sorted(set(mono) - {"mono", "adpcm", "msadpcm", "qoa"})[0] + ")")
-            mono, adpcm, msadpcm, qoa = mono.get("mono"), mono.get("adpcm", adpcm), mono.get("msadpcm", msadpcm), mono.get("qoa", qoa)
+            known = {"mono", "adpcm", "msadpcm", "qoa", "flac"}
+            if set(mono) - known:
+                raise LuaError("bad argument #2 (unknown option " + sorted(set(mono) - known)[0] + ")")
+            mono, adpcm, msadpcm, qoa, flac = mono.get("mono"), mono.get("adpcm", adpcm), mono.get("msadpcm", msadpcm), mono.get("qoa", qoa), mono.get("flac", flac)
         _expect(2, mono, "boolean", "nil")
         _expect(3, adpcm, "boolean", "nil")
         _expect(4, msadpcm, "boolean", "nil")
         _expect(5, qoa, "boolean", "nil")
-        descs, ranges, lengths = _sniff_many(files, stream=True, stream_dfpwm=True, stream_ima=bool(adpcm), stream_ms=bool(msadpcm), stream_qoa=bool(qoa))
+        _expect(6, flac, "boolean", "nil")
+        descs, ranges, lengths = _sniff_many(files, stream=True, stream_dfpwm=True, stream_ima=bool(adpcm), stream_ms=bool(msadpcm), stream_qoa=bool(qoa),
+                                             stream_flac=bool(flac))
         ctx = context()
         bt = _wrap(B.Batch.upload, ctx, [bytes((f[0] if isinstance(f, (list, tuple)) else f)[o:o + n]) for f, (o, n) in zip(files, ranges)])
-        was, was_frame = ctx.option(N.OPT_STREAM_MIXED_CODECS), ctx.option(N.OPT_STREAM_MIXED_FRAME_CODECS)
+        was, was_frame, was_chain = ctx.option(N.OPT_STREAM_MIXED_CODECS), ctx.option(N.OPT_STREAM_MIXED_FRAME_CODECS), ctx.option(N.OPT_STREAM_MIXED_CHAIN_CODECS)
         try:
             if msadpcm:
                 _wrap(ctx.set_option, N.OPT_STREAM_MIXED_CODECS, was | 1 << N.CODEC_MSADPCM)
             if qoa:
                 _wrap(ctx.set_option, N.OPT_STREAM_MIXED_FRAME_CODECS, was_frame | 1 << N.CODEC_QOA)
+            if flac:
+                _wrap(ctx.set_option, N.OPT_STREAM_MIXED_CHAIN_CODECS, was_chain | 1 << N.CODEC_FLAC)
             out, ck = _wrap(B.stream_decode_mixed, ctx, bt, descs, _interp(defaultInterpolation, 0), bool(mono), N.F64)
         finally:
             if msadpcm:
                 ctx.set_option(N.OPT_STREAM_MIXED_CODECS, was)
             if qoa:
                 ctx.set_option(N.OPT_STREAM_MIXED_FRAME_CODECS, was_frame)
+            if flac:
+                ctx.set_option(N.OPT_STREAM_MIXED_CHAIN_CODECS, was_chain)
         rows = out.download()
         return [self._chunk_iter(out, ck, None if math.isnan(lengths[i]) else lengths[i], d.codec == N.CODEC_G711, i, rows) for i, d in enumerate(descs)]
 

@@ -623,7 +623,14 @@ def stream_decode_mixed(ctx, batch, descs, interp, mono=False, dtype=None, out=N
     1 << N.CODEC_QOA) — option 9; options 5 to 8 do not open the call to QOA.  Those streams pay the device walk of their frame headers (two
     read-backs, both before `out` / `chunks` are touched) and the decoder to int8 rows, and their tail — the recursive low-pass over a whole
     iterator call — is one more launch, k_smix_qoa_tail, the call's last; a frame of more than 8192 samples, and a rate whose warm-up or window
-    one tile does not hold, refuse the call by the stream's index and name aukit_stream_decode.  `descs`: one
+    one tile does not hold, refuse the call by the stream's index and name aukit_stream_decode.
+    aukit.stream.flac for CODEC_FLAC (make_desc(N.CODEC_FLAC): only the codec is read, channel count, depth and rate are the file's STREAMINFO's;
+    positions count from 0) only on a context that asked for it under a third option: ctx.set_option(N.OPT_STREAM_MIXED_CHAIN_CODECS,
+    1 << N.CODEC_FLAC) — option 12; options 5 to 11 do not open the call to FLAC.  The reference ignores `mono` for FLAC: a member keeps its
+    header's channel count, so with `mono` a FLAC member of more than one channel refuses the call by index.  Those streams pay a header pass
+    and the frame-parallel decoder to int32 rows (both before `out` / `chunks` are touched), and their tail is one more launch,
+    k_smix_flac_tail, the call's last; rows that would be doubles (32 bits, a value beyond int32) and a rate whose warm-up one tile does not
+    hold refuse the call by the stream's index and name aukit_stream_decode.  `descs`: one
     CodecDesc per stream.  `out` / `chunks`: what an earlier call returned — the audio's buffers are reused, the chunk table is replaced (after
     a refusal both keep what they held)."""
     out = out if out is not None else AudioBatch(ctx)

@@ -59,6 +59,7 @@ struct aukit_ctx {
     hipEvent_t fmix_ev = nullptr;
     unsigned stream_mixed_codecs = 0;  // AUKIT_OPT_STREAM_MIXED_CODECS: the same for aukit_stream_decode_mixed, which reads this mask and no other
     unsigned stream_mixed_frame_codecs = 0;   // AUKIT_OPT_STREAM_MIXED_FRAME_CODECS: that call's second mask (1 << AUKIT_CODEC_QOA), read by the public call alone
+    unsigned stream_mixed_chain_codecs = 0;   // AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS: that call's third mask (1 << AUKIT_CODEC_FLAC), read by the public call alone
     unsigned streamset_codecs = 0;     // AUKIT_OPT_STREAMSET_CODECS: bit 1 << codec lets aukit_streamset_open, which reads this mask and no other, take that codec
     unsigned streamset_fcodecs = 0;   // AUKIT_OPT_STREAMSET_FRAME_CODECS: the same call's third mask (1 << AUKIT_CODEC_QOA), read while a set opens
     unsigned streamset_block_codecs = 0;   // AUKIT_OPT_STREAMSET_BLOCK_CODECS: the same call's second mask (1 << AUKIT_CODEC_MSADPCM), read while a set opens

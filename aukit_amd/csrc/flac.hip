@@ -714,7 +714,7 @@ static int flac_decode_rows(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &
 }
 
 // ================================================================= the FLAC members of aukit_decode_resample_mixed (flac_mixed.h)
-int flac_mixed_headers(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F) {
+int flac_mixed_headers(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F, const char *single) {
     int rc;
     const size_t m = list.size();
     F.assign(m, FlacMixedStream());
@@ -741,7 +741,7 @@ int flac_mixed_headers(aukit_ctx *ctx, const aukit_batch *in, const std::vector<
         default: return fail(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value (stream %u)", list[k]);
         }
         if (info[k].depth > 24 || g_flac_force_wide())   // (rows of doubles: the single-descriptor loader's)
-            return fail(AUKIT_E_UNSUPPORTED, "FLAC stream of %d bits whose rows are doubles: aukit_decode_resample takes this file (stream %u)", info[k].depth, list[k]);
+            return fail(AUKIT_E_UNSUPPORTED, "FLAC stream of %d bits whose rows are doubles: %s takes this file (stream %u)", info[k].depth, single, list[k]);
         F[k].channels = info[k].channels; F[k].depth = info[k].depth; F[k].rate = info[k].rate;
     }
     return AUKIT_OK;
@@ -764,9 +764,13 @@ static int fmix_rows_grow(aukit_ctx *ctx, size_t need, size_t keep) {
     return AUKIT_OK;
 }
 
-int flac_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F) {
+static void frames_from_brief(FlacDecoded &D);
+// `frames` (flac_smix_decode, the stream call): the decoders keep the frame lists, a chain that ends in an error is the stream's own end, and the
+// refusals name aukit_stream_decode; null: aukit_decode_resample_mixed's decode, as it always was
+static int flac_mixed_decode_groups(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F, std::vector<FlacSMixFrames> *frames) {
     int rc;
     const size_t m = list.size();
+    if (frames) frames->assign(m, FlacSMixFrames());
     if (!m) return AUKIT_OK;
     // ---- groups by (channels, depth), in order of first appearance; their bytes back to back, every group at a multiple of 256 bytes with 64 to spare
     std::map<std::pair<int, int>, size_t> index;
@@ -836,7 +840,7 @@ int flac_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<u
         group_batch(P, tb);
         FlacDecoded D;
         D.want16 = false;
-        rc = flac_decode_rows(ctx, &tb, D, false, true);
+        rc = flac_decode_rows(ctx, &tb, D, frames != nullptr, true);
         if (rc == FLAC_ROWS_WIDE) {   // a value beyond int32 somewhere in the group: which stream's, one at a time (the last one if no other)
             size_t who = 0;
             for (; who + 1 < G.size(); who++) {
@@ -847,13 +851,22 @@ int flac_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<u
                 if (r1 == FLAC_ROWS_WIDE) break;
                 if (r1) return r1;
             }
-            offender(list[G[who]], AUKIT_E_UNSUPPORTED, "FLAC stream with a value beyond int32, whose rows are doubles: aukit_decode_resample takes this file");
+            offender(list[G[who]], AUKIT_E_UNSUPPORTED, frames ? "FLAC stream with a value beyond int32, whose rows are doubles: aukit_stream_decode takes this file"
+                                                               : "FLAC stream with a value beyond int32, whose rows are doubles: aukit_decode_resample takes this file");
             continue;
         }
         if (rc) return rc;
         size_t raised = 0;
         while (raised < G.size() && !D.status[raised]) raised++;
-        if (raised < G.size()) {   // decodeFLAC raises (the group's members are in library order: its first is its lowest)
+        if (frames) {   // stream.flac swallows the error: the frames in front of it are the stream (stream_flac)
+            frames_from_brief(D);
+            for (size_t i = 0; i < G.size(); i++) {
+                FlacSMixFrames &fs = (*frames)[G[i]];
+                fs.nsamples = D.info[i].nsamples;
+                fs.status = D.status[i];
+                for (const auto &fr : D.frames[i]) { fs.at.push_back(fr.first); fs.bs.push_back((uint32_t)fr.second); }
+            }
+        } else if (raised < G.size()) {   // decodeFLAC raises (the group's members are in library order: its first is its lowest)
             offender(list[G[raised]], AUKIT_E_LUA, flac_err_msg(D.status[raised]));
             continue;
         }
@@ -875,6 +888,12 @@ int flac_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<u
     }
     if (bad != ~0u) return fail(bad_code, "%s (stream %u)", bad_msg.c_str(), bad);
     return AUKIT_OK;
+}
+int flac_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F) {
+    return flac_mixed_decode_groups(ctx, in, list, F, nullptr);
+}
+int flac_smix_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F, std::vector<FlacSMixFrames> &frames) {
+    return flac_mixed_decode_groups(ctx, in, list, F, &frames);
 }
 
 static void frames_from_brief(FlacDecoded &D) {

@@ -83,7 +83,8 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
                               aukit_chunks **chunks, const SMixCarry *carry /* n_descs, or null */, SMixDfBack *back = nullptr /* where a carry sets df_back */,
                               unsigned block_codecs = 0 /* 1 << AUKIT_CODEC_MSADPCM: the caller takes such streams, whatever the context's masks say; with a carry (a stream
                               set, which keeps ONE mask of what it was opened with) also 1 << AUKIT_CODEC_QOA, read as that bit of the next mask */,
-                              unsigned frame_codecs = 0 /* 1 << AUKIT_CODEC_QOA: the public call's AUKIT_OPT_STREAM_MIXED_FRAME_CODECS */);
+                              unsigned frame_codecs = 0 /* 1 << AUKIT_CODEC_QOA: the public call's AUKIT_OPT_STREAM_MIXED_FRAME_CODECS */,
+                              unsigned chain_codecs = 0 /* 1 << AUKIT_CODEC_FLAC: the public call's AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS; a stream set hands in 0 */);
 // what the stream's own aukit_stream_decode call refuses of a descriptor and a byte count, and the uneven last chunk (stream_mixed.hip)
 int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono);
 

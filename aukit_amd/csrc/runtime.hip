@@ -308,7 +308,7 @@ int aukit_ctx_set_sinc_window(aukit_ctx *c, int w) {
     c->sinc_w = w;
     return AUKIT_OK;
 }
-// AUKIT_OPT_MIXED_CODECS / AUKIT_OPT_MIXED_FRAME_CODECS / AUKIT_OPT_STREAM_MIXED_CODECS / AUKIT_OPT_STREAMSET_CODECS / AUKIT_OPT_STREAMSET_BLOCK_CODECS / AUKIT_OPT_STREAM_MIXED_FRAME_CODECS / AUKIT_OPT_STREAMSET_FRAME_CODECS: a mask of 1 << codec; refused as a whole, the mask as it was,
+// AUKIT_OPT_MIXED_CODECS / AUKIT_OPT_MIXED_FRAME_CODECS / AUKIT_OPT_STREAM_MIXED_CODECS / AUKIT_OPT_STREAMSET_CODECS / AUKIT_OPT_STREAMSET_BLOCK_CODECS / AUKIT_OPT_STREAM_MIXED_FRAME_CODECS / AUKIT_OPT_STREAMSET_FRAME_CODECS / AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS: a mask of 1 << codec; refused as a whole, the mask as it was,
 // where a bit names a codec the option's calls (`who`) do not take on request.  `only`: the one codec the option knows
 static int set_codec_mask(unsigned *mask, int value, const char *opt, const char *who, int only = AUKIT_CODEC_MSADPCM) {
     const unsigned known = 1u << only, extra = (unsigned)value & ~known;
@@ -339,6 +339,8 @@ int aukit_ctx_set_option(aukit_ctx *c, int option, int value) {
         return set_codec_mask(&c->streamset_fcodecs, value, "AUKIT_OPT_STREAMSET_FRAME_CODECS", "aukit_streamset_open takes", AUKIT_CODEC_QOA);
     else if (option == AUKIT_OPT_MIXED_FRAME_CODECS)
         return set_codec_mask(&c->mixed_frame_codecs, value, "AUKIT_OPT_MIXED_FRAME_CODECS", "aukit_decode_resample_mixed takes", AUKIT_CODEC_FLAC);
+    else if (option == AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS)
+        return set_codec_mask(&c->stream_mixed_chain_codecs, value, "AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS", "aukit_stream_decode_mixed takes", AUKIT_CODEC_FLAC);
     else return fail(AUKIT_E_ARG, "unknown option %d", option);
     return AUKIT_OK;
 }

@@ -77,6 +77,18 @@
 // every call into a device table, handed back with the calls' ends and sample counts as the DFPWM states are (SMixDfBack).  A frame of more than 8192
 // samples is then the stream's own verdict: no chunk, AUKIT_E_UNSUPPORTED as its status, no refusal of the batch.
 //
+// aukit.stream.flac (data_s, mono) (:3124-3191) is the sixth kind, and the second that is no class of k_stream_mixed: its tail filters recursively too
+// (:3179).  Only a context that set AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS hands such a stream in, and only the public call reads that option.  The FLAC
+// members' headers are read in one pass inside smix_validate (flac_mixed_headers: channel count, depth and rate are STREAMINFO's, and the reference
+// ignores `mono` for FLAC, so the channel rule reads the header's count and a mono batch takes one-channel members only); then, still before `*out` and
+// `*chunks` are touched, flac_smix_decode groups them by (channels, depth), compacts and decodes each group to int32 rows in ctx->fmix_rows — a buffer of
+// its own, so the other pre-passes' scratch lies where it lay — and hands back every stream's frame list; a chain that ends in an error or inside a
+// frame is the stream's own end, as in stream_flac.  The planners are stream_mixed_flac.h's: a class per (rate, depth), the chunk table by
+// stream_flac's loop (positions from 0), a job per (frame, channel) with `last` chained, tiles.  ONE launch of k_smix_flac_tail
+// (stream_mixed_flac.hip) writes their rows of `*out`; it is the call's last kernel — behind k_smix_qoa_tail where the batch has QOA members too: the
+// two tails write disjoint rows and either order gives the same audio, this one keeps the QOA tail's launch where it was.  Their segments are marked
+// SMIX_CLS_FLAC: k_stream_mixed gets no tile for them, and a batch of FLAC streams alone launches no k_stream_mixed.
+//
 // The host half reads as the call's phases: smix_validate, smix_classes, the IMA header scan, one planner per codec (plan_pcm, plan_g711, plan_dfpwm,
 // plan_ima, plan_ms: they fill an SMixPlan and touch neither the context nor HIP), the scratch layout, the MS-ADPCM pre-pass and its verdict, the two
 // other pre-passes, smix_tiles, the launch.  What the call shares with aukit_decode_resample_mixed is in mixed_plan.h, stream.adpcm's arithmetic in
@@ -88,6 +100,8 @@
 #include "ima_geom.h"
 #include "ms_geom.h"
 #include "stream_mixed_qoa.h"
+#include "stream_mixed_flac.h"
+#include "flac_mixed.h"
 #include "resample_dev.h"
 #include "dfpwm_dev.h"
 
@@ -102,7 +116,13 @@ size_t qoa_mixed_job_bytes(uint64_t njobs);
 int smix_qoa_tail_launch(aukit_ctx *ctx, const std::vector<SMixQoaClass> &classes, const std::vector<SMixQoaJob> &jobs, const std::vector<SMixQoaTile> &tiles, size_t lds,
                          const signed char *rows, void *out, int interp, int dtype, uint64_t algorithmic_bytes);
 
+// stream_mixed_flac.hip's launch (flac.hip's header pass and group decode: flac_mixed.h)
+int smix_flac_tail_launch(aukit_ctx *ctx, const std::vector<SMixFlacClass> &classes, const std::vector<SMixFlacJob> &jobs, const std::vector<SMixFlacTile> &tiles, size_t lds,
+                          const int *rows, void *out, int interp, int dtype, uint64_t algorithmic_bytes);
+
 constexpr unsigned SMIX_CLS_QOA = 0xFFFFFFFFu;   // SMixSeg::cls of a QOA call: no class of k_stream_mixed, no tile of it
+constexpr unsigned SMIX_CLS_FLAC = 0xFFFFFFFEu;  // ... of a FLAC call: k_smix_flac_tail's
+static inline bool smix_cls_tail(unsigned cls) { return cls == SMIX_CLS_QOA || cls == SMIX_CLS_FLAC; }
 
 enum { SMIX_EPI_PCM = 0, SMIX_EPI_FLOOR = 1, SMIX_EPI_DFPWM = 2, SMIX_EPI_MS_MONO = 3 };
 
@@ -656,15 +676,46 @@ struct SMixQoa {
     uint64_t back_pairs = 0;
 };
 
+// the FLAC streams of the batch, in batch order, as the header pass found them (smix_validate), their decode (flac_smix_decode) and what is planned from that
+struct SMixFlac {
+    std::vector<uint32_t> list;           // their indices in the batch
+    std::vector<FlacMixedStream> F;
+    std::vector<FlacSMixFrames> frames;   // per entry of `list`
+    std::vector<SMixFlacClass> classes;   // one per distinct (rate, depth), in order of first appearance
+    std::vector<unsigned> cls_of;         // per entry of `list`
+    std::vector<uint64_t> max_nout;       // per class: its longest job
+    size_t lds = 0;                       // the largest class's
+    std::vector<std::vector<SMixFlacChunk>> plan;   // per entry of `list`
+    uint64_t row_bytes = 0;               // of the decoded rows
+};
+
+// the refusal of a codec the call does not serve, on a context that opened it to FLAC: option 6's clause, option 9's and this option's, in that order
+static int smix_check_codecs_chain(const aukit_codec_desc *descs, uint32_t n, bool with_ms, bool with_qoa) {
+    for (uint32_t s = 0; s < n; s++) {
+        const int c = descs[s].codec;
+        if (c == AUKIT_CODEC_PCM || c == AUKIT_CODEC_G711 || c == AUKIT_CODEC_DFPWM || c == AUKIT_CODEC_ADPCM_WAV || c == AUKIT_CODEC_FLAC || (with_ms && c == AUKIT_CODEC_MSADPCM) ||
+            (with_qoa && c == AUKIT_CODEC_QOA))
+            continue;
+        std::string words = "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV";
+        if (with_ms) words += " and, under AUKIT_OPT_STREAM_MIXED_CODECS, AUKIT_CODEC_MSADPCM";
+        if (with_qoa) words += " and, under AUKIT_OPT_STREAM_MIXED_FRAME_CODECS, AUKIT_CODEC_QOA";
+        words += " and, under AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS, AUKIT_CODEC_FLAC)";
+        return fail(AUKIT_E_UNSUPPORTED, words.c_str(), s, c);
+    }
+    return AUKIT_OK;
+}
+
 static int smix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
-                         const SMixCarry *carry, unsigned block_codecs, unsigned frame_codecs, SMixQoa &QS, std::vector<int> &ch_of) {
+                         const SMixCarry *carry, unsigned block_codecs, unsigned frame_codecs, unsigned chain_codecs, SMixQoa &QS, SMixFlac &FS, std::vector<int> &ch_of) {
     int rc;
     if ((rc = mixed_check_call(ctx, in, out, descs, n_descs, interp, dtype, "invalid interpolation", "stream each class with aukit_stream_decode"))) return rc;
     // AUKIT_OPT_STREAM_MIXED_CODECS: MS-ADPCM joins the list on a context that asked this call for it; without the bit the call answers in the words of before.
     // (The mask is the caller's: the public call hands in the context's, a stream set the one it was opened with)
     // AUKIT_OPT_STREAM_MIXED_FRAME_CODECS: QOA likewise, under an option of its own; its clause stands behind option 6's
+    // AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS: FLAC, under a third option (the public call's alone: a stream set hands in 0); its clause stands last
     const bool with_qoa = (frame_codecs >> AUKIT_CODEC_QOA) & 1u;
-    if (with_qoa && ((block_codecs >> AUKIT_CODEC_MSADPCM) & 1u))
+    if ((chain_codecs >> AUKIT_CODEC_FLAC) & 1u) rc = smix_check_codecs_chain(descs, in->n, (block_codecs >> AUKIT_CODEC_MSADPCM) & 1u, with_qoa);
+    else if (with_qoa && ((block_codecs >> AUKIT_CODEC_MSADPCM) & 1u))
         rc = mixed_check_codecs(descs, in->n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_MSADPCM, AUKIT_CODEC_QOA},
                                 "stream %u: codec %d has its own stream (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, "
                                 "AUKIT_CODEC_DFPWM, AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_STREAM_MIXED_CODECS, AUKIT_CODEC_MSADPCM and, under "
@@ -686,6 +737,24 @@ static int smix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_code
     for (uint32_t s = 0; s < in->n; s++) {
         ch_of[s] = descs[s].channels;
         if (descs[s].codec == AUKIT_CODEC_QOA) QS.list.push_back(s);
+        if (descs[s].codec == AUKIT_CODEC_FLAC) FS.list.push_back(s);
+    }
+    // FLAC: only `codec` of the descriptor is read.  The header pass and its read-back: what stream_flac refuses of a header is refused first, with
+    // its words, and a depth of 32 by index.  It writes ctx->misc_buf and nothing of `*out`.  `mono` is ignored for FLAC (:3124-3191 never reads
+    // it): the member keeps its header's channel count, so a mono batch — one output row per stream — takes one-channel members only.
+    // A stream's frames are known only once they are chained, so the group decode is here too: it writes context scratch only (fmix_src, fmix_rows and
+    // the decoders' tables, ctx->tmp_buf and ctx->tmp_buf3 among them — hence in front of the QOA count pass, whose words in tmp_buf3 its fill pass
+    // reads again, and of the other pre-passes' scratch) and can still refuse, by stream index
+    if (!FS.list.empty()) {
+        AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
+        if ((rc = flac_mixed_headers(ctx, in, FS.list, FS.F, "aukit_stream_decode"))) return rc;
+        for (size_t i = 0; i < FS.list.size(); i++) ch_of[FS.list[i]] = FS.F[i].channels;
+        if (mono)
+            for (size_t i = 0; i < FS.list.size(); i++)
+                if (FS.F[i].channels != 1)
+                    return fail(AUKIT_E_ARG, "streams differ in channel count: stream.flac ignores `mono` and stream %u has %d channels: split the batch", FS.list[i], FS.F[i].channels);
+        if ((rc = flac_smix_decode(ctx, in, FS.list, FS.F, FS.frames))) return rc;
+        for (const FlacMixedStream &f : FS.F) FS.row_bytes += f.frames * (uint64_t)f.channels * 4;
     }
     // QOA: only `codec` of the descriptor is read.  The count pass of the device walk on these streams, and the header read-back: what stream_qoa
     // refuses of a header is refused first, with its words.  It writes ctx->tmp_buf3 and nothing of `*out`
@@ -710,7 +779,7 @@ static int smix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_code
     }
     if ((rc = mixed_check_channels(in->n, mono, [&](uint32_t s) { return ch_of[s]; }))) return rc;
     for (uint32_t s = 0; s < in->n; s++) {
-        if (descs[s].codec == AUKIT_CODEC_QOA) continue;   // (its header was the check)
+        if (descs[s].codec == AUKIT_CODEC_QOA || descs[s].codec == AUKIT_CODEC_FLAC) continue;   // (its header was the check)
         if (carry && carry[s].nbytes > in->off[s + 1] - in->off[s]) return fail(AUKIT_E_ARG, "stream %u: the carry names more bytes than the batch holds", s);
         if ((rc = check_smix_stream(&descs[s], smix_nbytes(in, carry, s), mono != 0))) return fail_for_stream(rc, s);
     }
@@ -735,6 +804,7 @@ static int smix_classes(const aukit_codec_desc *descs, uint32_t n, int interp, i
     for (uint32_t s = 0; s < n; s++) {
         const aukit_codec_desc &d = descs[s];
         if (d.codec == AUKIT_CODEC_QOA) { T.cls_of[s] = SMIX_CLS_QOA; continue; }   // (smix_qoa_classes)
+        if (d.codec == AUKIT_CODEC_FLAC) { T.cls_of[s] = SMIX_CLS_FLAC; continue; }   // (smix_flac_classes)
         const bool pcm = d.codec == AUKIT_CODEC_PCM, df = d.codec == AUKIT_CODEC_DFPWM, ima = d.codec == AUKIT_CODEC_ADPCM_WAV, ms = d.codec == AUKIT_CODEC_MSADPCM;
         T.has_df = T.has_df || df;
         T.has_ima = T.has_ima || ima;
@@ -832,6 +902,32 @@ static int smix_qoa_classes(SMixQoa &QS) {
         QS.classes.push_back(K);
     }
     QS.max_nout.assign(QS.classes.size(), 0);
+    return AUKIT_OK;
+}
+
+// the FLAC streams' classes, one per distinct (rate, depth) of the STREAMINFO blocks, and what is refused of a class by stream index
+static int smix_flac_classes(SMixFlac &FS) {
+    ClassIndex<std::tuple<double, int>> index;
+    FS.cls_of.resize(FS.list.size());
+    for (size_t i = 0; i < FS.list.size(); i++) {
+        const FlacMixedStream &f = FS.F[i];
+        const unsigned s = FS.list[i];
+        bool fresh;
+        FS.cls_of[i] = index.of({f.rate, f.depth}, &fresh);
+        if (!fresh) continue;
+        SMixFlacClass K;
+        size_t lds = 0;
+        const int why = smix_flac_class_shape(f.rate, f.depth, &K, &lds);
+        if (why == 1)
+            return fail(AUKIT_E_UNSUPPORTED, "FLAC at %g Hz: the low-pass needs a warm-up beyond one tile of %d outputs: aukit_stream_decode takes this file (stream %u)", f.rate,
+                        SMIX_FLAC_TMAX, s);
+        if (why)
+            return fail(AUKIT_E_UNSUPPORTED, "FLAC at %g Hz: a tile's window needs more than %d KiB of LDS: aukit_stream_decode takes this file (stream %u)", f.rate,
+                        (int)(SMIX_FLAC_LDS / 1024), s);
+        FS.lds = std::max(FS.lds, lds);
+        FS.classes.push_back(K);
+    }
+    FS.max_nout.assign(FS.classes.size(), 0);
     return AUKIT_OK;
 }
 
@@ -1055,6 +1151,7 @@ static void smix_plan(const aukit_batch *in, const aukit_codec_desc *descs, cons
         g.src_off = in->off[s];
         g.cls = cls_of[s];
         if (d.codec == AUKIT_CODEC_QOA) continue;   // (planned from its call records, behind the fill pass: plan_qoa)
+        if (d.codec == AUKIT_CODEC_FLAC) continue;  // (planned from its frame list: plan_flac)
         if (d.codec == AUKIT_CODEC_DFPWM) plan_dfpwm(pl, s, g, d, nb, cy);
         else if (d.codec == AUKIT_CODEC_ADPCM_WAV) plan_ima(pl, s, g, d, nb, ima_bad[ima_i++], cy);
         else if (d.codec == AUKIT_CODEC_MSADPCM) plan_ms(pl, s, g, d, nb, cy);
@@ -1093,6 +1190,46 @@ static int plan_qoa(SMixPlan &pl, SMixQoa &QS, const SMixCarry *carry) {
             }
             call0 += q.ncalls;
             qi++;
+            continue;
+        }
+        const uint32_t k = pl.ck->nchunks[s];
+        segs.insert(segs.end(), pl.segs.begin() + i, pl.segs.begin() + i + k);
+        cpos.insert(cpos.end(), pl.cpos.begin() + i, pl.cpos.begin() + i + k);
+        i += k;
+    }
+    pl.segs.swap(segs);
+    pl.cpos.swap(cpos);
+    return AUKIT_OK;
+}
+
+// stream_flac's plan (flac.hip) for every FLAC stream, from the frame lists: the chunk table by its loop (smix_flac_plan_stream), the length
+// nsamples / rate (:3190), status 0 whatever ended the chain — the iterator swallows the error —, and the class's longest job.  The calls join the
+// plan as segments in the stream's place (a QOA stream has none yet: plan_qoa comes behind)
+static int plan_flac(SMixPlan &pl, SMixFlac &FS) {
+    FS.plan.resize(FS.list.size());
+    std::vector<SMixSeg> segs;
+    std::vector<double> cpos;
+    size_t i = 0, fi = 0;
+    for (uint32_t s = 0; s < pl.ck->n; s++) {
+        if (fi < FS.list.size() && FS.list[fi] == s) {
+            const FlacMixedStream &f = FS.F[fi];
+            const FlacSMixFrames &fr = FS.frames[fi];
+            if (!smix_flac_plan_stream(f.rate, fr.bs.data(), fr.bs.size(), FS.plan[fi])) return fail_for_stream(fail(AUKIT_E_UNSUPPORTED, "stream too long"), s);
+            pl.ck->length_seconds[s] = fr.nsamples / f.rate;
+            for (const SMixFlacChunk &c : FS.plan[fi]) {
+                SMixSeg g;
+                memset(&g, 0, sizeof g);
+                g.cls = SMIX_CLS_FLAC;
+                g.n_out = (unsigned)c.nout;
+                g.out_off = pl.lens[s];
+                segs.push_back(g);
+                cpos.push_back(c.pos);
+                pl.lens[s] += c.nout;
+                pl.ck->nchunks[s]++;
+            }
+            if (pl.lens[s] > 0x7FFFFFF0ull) return fail_for_stream(fail(AUKIT_E_UNSUPPORTED, "stream too long"), s);
+            for (uint32_t b : fr.bs) FS.max_nout[FS.cls_of[fi]] = std::max(FS.max_nout[FS.cls_of[fi]], smix_flac_frame_out(b, FS.classes[FS.cls_of[fi]].ratio));
+            fi++;
             continue;
         }
         const uint32_t k = pl.ck->nchunks[s];
@@ -1278,7 +1415,7 @@ static uint64_t smix_cut(const SMixClass &K, unsigned to, const SMixSeg &g, unsi
 }
 static uint64_t smix_count_tiles(const SMixClasses &T, const SMixPlan &pl) {
     uint64_t nt = 0;
-    for (const SMixSeg &g : pl.segs) if (g.cls != SMIX_CLS_QOA) nt += smix_cut(T.classes[g.cls], (unsigned)T.tile_out[g.cls], g, 0, nullptr);
+    for (const SMixSeg &g : pl.segs) if (!smix_cls_tail(g.cls)) nt += smix_cut(T.classes[g.cls], (unsigned)T.tile_out[g.cls], g, 0, nullptr);
     return nt;
 }
 // the segments get their place in the audio's rows on the way
@@ -1291,7 +1428,7 @@ static std::vector<SMixTile> smix_tiles(const SMixClasses &T, SMixPlan &pl, cons
             SMixSeg &g = pl.segs[i];
             g.out_off += a->row_off[s];
             g.out_stride = (unsigned)a->row_stride[s];
-            if (g.cls == SMIX_CLS_QOA) continue;   // k_smix_qoa_tail's
+            if (smix_cls_tail(g.cls)) continue;   // k_smix_qoa_tail's, k_smix_flac_tail's
             smix_cut(T.classes[g.cls], (unsigned)T.tile_out[g.cls], g, (unsigned)i, &tiles);
         }
     return tiles;
@@ -1350,6 +1487,28 @@ static int smix_qoa_tail(aukit_ctx *ctx, SMixQoa &QS, const SMixScratch &L, cons
     return smix_qoa_tail_launch(ctx, QS.classes, jobs, tiles, QS.lds, rows, a->dev, interp, dtype, QS.rows + out_elems * dtype_size(dtype));
 }
 
+// ---- phase 10: the FLAC streams' tail, the call's last kernel: a job per (frame, channel) with `last` chained and its place in the audio's rows, tiles,
+// the exact_div_verified verdict of every class over its longest job, one launch.  (Behind the QOA tail: the two write disjoint rows)
+static int smix_flac_tail(aukit_ctx *ctx, SMixFlac &FS, const aukit_audio *a, int interp, int dtype) {
+    std::vector<SMixFlacJob> jobs;
+    std::vector<SMixFlacTile> tiles;
+    uint64_t out_elems = 0;
+    for (size_t i = 0; i < FS.list.size(); i++) {
+        const uint32_t s = FS.list[i];
+        const FlacMixedStream &f = FS.F[i];
+        const FlacSMixFrames &fr = FS.frames[i];
+        const uint64_t stride = round_up(std::max<uint64_t>(f.frames, 1), 4);
+        if (!smix_flac_jobs(FS.classes[FS.cls_of[i]], FS.cls_of[i], f.channels, fr.bs.data(), fr.at.data(), fr.bs.size(), f.row / 4, stride, a->row_off[s], a->row_stride[s], jobs, tiles))
+            return fail(AUKIT_E_HIP, "internal: a FLAC frame leaves its row (stream %u)", s);
+        for (const SMixFlacChunk &c : FS.plan[i]) out_elems += c.nout * (uint64_t)f.channels;
+    }
+    if (tiles.empty()) return AUKIT_OK;
+    if (tiles.size() > 0xFFFFFFF0ull || jobs.size() > 0xFFFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
+    for (size_t c = 0; c < FS.classes.size(); c++)
+        FS.classes[c].exact = exact_div_verified(ctx, FS.classes[c].ratio, std::max<uint64_t>(FS.max_nout[c] + 2, 1ull << 17)) ? 1 : 0;
+    return smix_flac_tail_launch(ctx, FS.classes, jobs, tiles, FS.lds, reinterpret_cast<const int *>(ctx->fmix_rows.p), a->dev, interp, dtype, FS.row_bytes + out_elems * dtype_size(dtype));
+}
+
 // a stream set's batch: what the rests' first calls read as their table indices -1 and 0 (the carries' samples, behind the calls' rows), and how many
 // pairs go back — one per channel and call of every stream that asked
 static void smix_qoa_carried(SMixQoa &QS, const SMixCarry *carry) {
@@ -1397,22 +1556,25 @@ static int smix_qoa_hand_back(aukit_ctx *ctx, const SMixQoa &QS, const SMixScrat
 }
 
 int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
-                              aukit_chunks **chunks, const SMixCarry *carry, SMixDfBack *back, unsigned block_codecs, unsigned frame_codecs) {
+                              aukit_chunks **chunks, const SMixCarry *carry, SMixDfBack *back, unsigned block_codecs, unsigned frame_codecs, unsigned chain_codecs) {
     // what can be refused is refused before the device is touched (a batch with a QOA stream: behind the walk's count pass); `*out` and `*chunks` keep
     // what they held
     int rc;
     SMixQoa QS;
+    SMixFlac FS;
     std::vector<int> ch_of;
     if (carry) {   // a stream set's one mask: the QOA bit is the frame mask's
         frame_codecs |= block_codecs & (1u << AUKIT_CODEC_QOA);
         block_codecs &= ~(1u << AUKIT_CODEC_QOA);
     }
-    if ((rc = smix_validate(ctx, in, descs, n_descs, interp, mono, dtype, out, carry, block_codecs, frame_codecs, QS, ch_of))) return rc;
+    if (carry) chain_codecs = 0;   // (a stream set keeps refusing the codec)
+    if ((rc = smix_validate(ctx, in, descs, n_descs, interp, mono, dtype, out, carry, block_codecs, frame_codecs, chain_codecs, QS, FS, ch_of))) return rc;
     const uint32_t n = in->n;
-    const bool qoa = !QS.list.empty();
+    const bool qoa = !QS.list.empty(), flac = !FS.list.empty();
     SMixClasses T;
     if ((rc = smix_classes(descs, n, interp, mono, T))) return rc;
     if (qoa && (rc = smix_qoa_classes(QS))) return rc;
+    if (flac && (rc = smix_flac_classes(FS))) return rc;
     if (qoa && carry) smix_qoa_carried(QS, carry);
     if (QS.back_pairs > 0x7FFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
     if (QS.back_pairs && !back) return fail(AUKIT_E_ARG, "null argument");
@@ -1424,6 +1586,7 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
     const int C_out = mono ? 1 : (n ? ch_of[0] : 1);
     SMixPlan pl(n);
     smix_plan(in, descs, carry, T.cls_of, interp, mono != 0, ima_bad, pl);
+    if (flac && (rc = plan_flac(pl, FS))) return rc;   // the FLAC streams' calls join the plan
     smix_chunk_table(pl, C_out);
     uint64_t nt = smix_count_tiles(T, pl);
     if (nt > 0xFFFFFFF0ull || pl.ima_jobs > 0x7FFFFFF0ull * 64 || pl.ms.units.size() > 0x7FFFFFF0ull || pl.df_states > 0x7FFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
@@ -1463,6 +1626,7 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
         if ((rc = smix_launch(ctx, in, T, pl, tiles, L, a, interp, dtype))) return rc;
     }
     if (qoa && (rc = smix_qoa_tail(ctx, QS, L, a, mono != 0, interp, dtype))) return rc;
+    if (flac && (rc = smix_flac_tail(ctx, FS, a, interp, dtype))) return rc;
     chunks_deliver(pl.ck, chunks);   // the caller's table is replaced
     return AUKIT_OK;
 }
@@ -1474,5 +1638,5 @@ using namespace aukit;
 extern "C" int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype,
                                          aukit_audio **out, aukit_chunks **chunks) {
     return stream_decode_mixed_carry(ctx, in, descs, n_descs, interp, mono, dtype, out, chunks, nullptr, nullptr, ctx ? ctx->stream_mixed_codecs : 0u,
-                                     ctx ? ctx->stream_mixed_frame_codecs : 0u);
+                                     ctx ? ctx->stream_mixed_frame_codecs : 0u, ctx ? ctx->stream_mixed_chain_codecs : 0u);
 }

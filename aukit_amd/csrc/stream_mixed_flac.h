@@ -1,0 +1,139 @@
+// stream_mixed_flac.h — aukit.stream.flac (data_s, mono) (aukit.lua:3124-3191) in aukit_stream_decode_mixed: what the host half (stream_mixed.hip)
+// and the tail kernel (stream_mixed_flac.hip) share.  The records and the planners below are plain C++ on std types — no HIP, no context — so that
+// they build and run on a CPU alone (tools/smix_flac_plan_check.cpp puts them under a sanitizer).
+//
+// A FLAC stream of the batch is decoded by flac.hip (flac_smix_decode, flac_mixed.h) to int32 rows, one per channel, and comes back with its frame
+// list.  From the frame lists the host plans
+//   - a class per distinct (rate, depth): ratio, low-pass weight, the warm-up W, the tile height T, the LDS window and 2^depth (smix_flac_class_shape);
+//   - the chunk table of every stream (smix_flac_plan_stream), exactly stream_flac's build_chunks loop (flac.hip);
+//   - a job per (frame, channel), in the order the reference walks them — `last = {src[#src-1], src[#src]}` is shared across channels and frames
+//     (Q14), so a stream's jobs chain as k_flac_tail_jobs chains them — and the tiles of every job (smix_flac_jobs).
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+namespace aukit {
+
+constexpr int SMIX_FLAC_E = 8;                     // consecutive outputs per thread of k_smix_flac_tail
+constexpr int SMIX_FLAC_TMAX = 256 * SMIX_FLAC_E;  // outputs per tile at the most
+constexpr size_t SMIX_FLAC_LDS = 64 * 1024;        // what a class's window and sample buffer may take together
+
+struct SMixFlacClass {
+    double ratio, rcp;         // x = (i - 1) / ratio + 1  :3174
+    double lp_alpha;           // 1 - exp(-(rate / 96000) * 2 pi)  :3155
+    double full, scale;        // 2^depth and 2^-depth: a row's integer times `scale` is the reference's quotient by 2^sampleDepth, to the bit
+    int exact;                 // 1: RN((i - 1) / ratio) via rcp and two fmas is verified over the class's longest job
+    int W, T;                  // warm-up outputs; outputs per tile (a multiple of SMIX_FLAC_E)
+    int cap, xbn;              // LDS doubles of the table window / of the tile's samples
+    int depth;
+};
+static_assert(sizeof(SMixFlacClass) == 64, "SMixFlacClass layout");
+struct SMixFlacJob {
+    unsigned long long src_off;    // rows (int32 elements): table index 1 of this (frame, channel) block
+    unsigned long long last_off;   // rows: table index 0 = last[2], the block before's last sample — another channel's or another frame's row; ~0: 0
+    unsigned long long m1_off;     // rows: table index -1 = last[1]; ~0: 0
+    unsigned long long out_off;    // element of output 0
+    int n, nout;                   // block size, outputs
+    unsigned cls;
+    int pad;
+};
+static_assert(sizeof(SMixFlacJob) == 48, "SMixFlacJob layout");
+struct SMixFlacTile { unsigned job, o0; };
+struct SMixFlacParams {
+    const SMixFlacTile *tiles;
+    const SMixFlacJob *jobs;
+    const SMixFlacClass *classes;
+    unsigned n_tiles;
+    const int *rows;           // 16-byte aligned; a channel row's stride is a multiple of four elements and the buffer has 256 bytes to spare
+    void *out;
+};
+
+// The class of (rate, depth): stream_mixed_qoa.h's shape with the tile height the class's own.  A state W outputs back still shows as a^W of it,
+// a = exp(-decay): below 1e-16 of a sample of magnitude 128 after W = ceil((37 + ln 128) / decay) outputs (a FLAC state is below 1 in magnitude:
+// the same W leaves 1e-18 of it).
+// -> 0; 1: the warm-up does not fit one tile (very low rates); 2: the window exceeds the LDS budget (very high rates)
+static inline int smix_flac_class_shape(double rate, int depth, SMixFlacClass *K, size_t *lds) {
+    *K = SMixFlacClass{};
+    K->depth = depth;
+    K->full = std::ldexp(1.0, depth);
+    K->scale = std::ldexp(1.0, -depth);
+    K->ratio = 48000 / rate;                                         // :3154
+    K->rcp = 1.0 / K->ratio;
+    K->lp_alpha = 1 - std::exp(-(rate / 96000) * 2 * M_PI);          // :3155
+    const double decay = (rate / 96000) * 2 * M_PI;
+    const double wd = std::ceil((37.0 + std::log(128.0)) / decay);
+    auto shape = [&](int T, double w, int *cap, int *xbn) {
+        const double capd = std::ceil(((double)T + w) / K->ratio) + 8;
+        const double tot = (double)T + w;
+        *cap = capd < 1e9 ? (((int)capd + 3) & ~3) : 0x40000000;
+        *xbn = ((int)tot + (int)tot / SMIX_FLAC_E + 2 + 3) & ~3;
+        return ((size_t)*cap + (size_t)*xbn) * 8;
+    };
+    int T = SMIX_FLAC_TMAX;
+    if (!(wd <= (double)T)) return 1;
+    while (T > 256 && (double)(T / 2) >= wd && shape(T, wd, &K->cap, &K->xbn) > SMIX_FLAC_LDS) T /= 2;
+    *lds = shape(T, wd, &K->cap, &K->xbn);
+    if (*lds > SMIX_FLAC_LDS) return 2;
+    K->W = (int)wd;
+    K->T = T;
+    return 0;
+}
+
+// what a frame of `bs` samples yields per channel: floor(blocksize * ratio)  (:3173)
+static inline uint64_t smix_flac_frame_out(uint32_t bs, double ratio) { return (uint64_t)std::floor((double)bs * ratio); }
+
+// The chunk table of one stream from its frame list, exactly stream_flac's build_chunks loop: an iterator call accumulates frames while
+// #chunk[1] < sampleRate (:3161); the end of the frames kills the coroutine, and that last call returns what it has (possibly nothing);
+// pos is summed from 0 and delivered behind the call's own outputs (:3188).
+// -> false: a call of more than 0x7FFFFFF0 outputs ("stream too long")
+struct SMixFlacChunk { uint64_t nout; double pos; };
+static inline bool smix_flac_plan_stream(double rate, const uint32_t *bs, size_t nframes, std::vector<SMixFlacChunk> &plan) {
+    const double ratio = 48000 / rate;
+    plan.clear();
+    size_t f = 0;
+    bool dead = false;
+    double pos = 0;
+    while (!dead) {
+        uint64_t got = 0;
+        while ((double)got < rate) {
+            if (f >= nframes) { dead = true; break; }
+            got += smix_flac_frame_out(bs[f], ratio);
+            f++;
+            if (got > 0x7FFFFFF0ull) return false;
+        }
+        pos = pos + (double)got / 48000;
+        plan.push_back(SMixFlacChunk{got, pos});
+    }
+    return true;
+}
+
+// The jobs and tiles of one stream's frames.  row0: the int32 element of channel 0's row; row_stride: elements between its channel rows; at[f]:
+// frame f's sample offset within a row.  out0: element of the stream's output 0, channel 0; out_stride: elements between its output channels.
+// A job without an output (a one-sample frame above 48 kHz) gets no tile and still moves `last`.
+// -> false: a frame that leaves its row (the decoder's lists disagree: nothing is appended for it)
+static inline bool smix_flac_jobs(const SMixFlacClass &K, unsigned cls, int channels, const uint32_t *bs, const uint64_t *at, size_t nframes, uint64_t row0, uint64_t row_stride,
+                                  uint64_t out0, uint64_t out_stride, std::vector<SMixFlacJob> &jobs, std::vector<SMixFlacTile> &tiles) {
+    uint64_t op = 0, l1 = ~0ull, l2 = ~0ull;   // where last[1], last[2] live in the rows (~0: the initial 0)
+    for (size_t f = 0; f < nframes; f++) {
+        if (at[f] + bs[f] > row_stride) return false;
+        const uint64_t nout = smix_flac_frame_out(bs[f], K.ratio);
+        for (int c = 0; c < channels; c++) {
+            SMixFlacJob j{};
+            j.src_off = row0 + (uint64_t)c * row_stride + at[f];
+            j.last_off = l2; j.m1_off = l1;
+            j.out_off = out0 + (uint64_t)c * out_stride + op;
+            j.n = (int)bs[f]; j.nout = (int)nout;
+            j.cls = cls;
+            for (uint64_t o0 = 0; o0 < nout; o0 += (uint64_t)K.T) tiles.push_back(SMixFlacTile{(unsigned)jobs.size(), (unsigned)o0});
+            jobs.push_back(j);
+            // for a one-sample block src[#src-1] is src[0] = the old last[2]  (:3183)
+            if (bs[f] >= 2) { l1 = j.src_off + (uint64_t)bs[f] - 2; l2 = l1 + 1; }
+            else if (bs[f] == 1) { l1 = l2; l2 = j.src_off; }
+        }
+        op += nout;
+    }
+    return true;
+}
+
+}  // namespace aukit

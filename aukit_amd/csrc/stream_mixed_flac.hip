@@ -1,0 +1,143 @@
+// stream_mixed_flac.hip — k_smix_flac_tail: the tail of aukit.stream.flac (aukit.lua:3166-3184) for the FLAC streams of aukit_stream_decode_mixed — a
+// (frame, channel) block of the decoder's int32 rows, scaled by 2^-depth → `if x % 1 == 0 then s = src[x] else s = interp(src, x) end` (no clamp) →
+// the recursive one-pole low-pass `s = ls + lp_alpha * (s - ls); ls = s`, seeded with last[2] / (last[2] < 0 and 128 or 127) →
+// clamp(s * (s < 0 and 128 or 127), -128, 127) — in ONE launch for every (rate, depth) class of the batch.  No mix-down: the reference ignores `mono`.
+//
+// The structure is k_smix_qoa_tail's (stream_mixed_qoa.hip), fp64 in the reference's operation order: (1) the window of the table the tile touches →
+// LDS as doubles; (2) a lane per output interpolates; (3) a thread per E consecutive outputs runs the recurrence behind a private warm-up of W
+// outputs — the exact seed where the warm-up reaches output 0 of the job — so a tile needs nothing from the tile before it; (4) coalesced stores,
+// AUKIT_F32 the fp64 value rounded once.  What differs:
+//   - the window is staged from int32 with 16-byte loads: a lane takes the aligned vector of four at or below its elements and keeps those inside
+//     the window (the rows are 16-byte aligned, a row's stride is a multiple of four elements, the buffer has 256 bytes to spare: no load leaves it);
+//   - table indices 0 and -1 are `last`, shared across channels and frames (Q14): the job names where they lie — another channel's or another
+//     frame's row, or nowhere (the initial 0);
+//   - the 128 / 127 scaling and the clamp come behind the filter, on the way to the sample buffer; the filter's state is the unscaled value.
+// The class (ratio, reciprocal, exact flag, lp_alpha, W, tile height, window capacity, 2^-depth) is read per tile from a device table; the dynamic
+// LDS is the largest class's.  The sample buffer keeps the skew (slot i + i / E) that spreads phase 3's strided reads over all banks.
+#include "mixed_plan.h"
+#include "stream_mixed_flac.h"
+#include "resample_dev.h"
+
+namespace aukit {
+
+template <int INTERP, typename OUT_T>
+__global__ __launch_bounds__(256) void k_smix_flac_tail(const SMixFlacParams P) {
+    extern __shared__ double fsm[];
+    constexpr int E = SMIX_FLAC_E;
+    const int tid = threadIdx.x;
+    OUT_T *const out = reinterpret_cast<OUT_T *>(P.out);
+    const int *const rows = P.rows;
+    auto skew = [](int i) { return i + i / E; };
+    for (unsigned t = blockIdx.x; t < P.n_tiles; t += gridDim.x) {
+        const SMixFlacTile tl = P.tiles[t];
+        const SMixFlacJob job = P.jobs[tl.job];
+        const SMixFlacClass K = P.classes[job.cls];
+        double *const win = fsm;
+        double *const xb = fsm + K.cap;
+        auto pos = [&](unsigned o) { const double nn = (double)o; return (K.exact ? div_rcp(nn, K.ratio, K.rcp) : nn / K.ratio) + 1.0; };  // x = (i - 1) / ratio + 1  :3175
+        const unsigned o0 = tl.o0;
+        if (o0 >= (unsigned)job.nout) continue;   // (block-uniform; the host cuts no such tile)
+        const int cnt = (int)min((unsigned)K.T, (unsigned)job.nout - o0);
+        const int wl = (int)min((unsigned)K.W, o0);
+        const unsigned of = o0 - (unsigned)wl;
+        const int total = wl + cnt;   // <= T + W: the host sized xbn for it
+        const int n = job.n;
+        int k_lo = (int)floor(pos(of)) - 1, k_hi = (int)floor(pos(o0 + (unsigned)cnt - 1)) + 2;
+        k_lo = max(k_lo, -1);
+        k_hi = min(k_hi, n);
+        const int nst = min(k_hi - k_lo + 1, K.cap);   // (the host sized cap for the window; never past it)
+        const int last = max(nst - 1, 0);
+        const double z0 = job.last_off != ~0ull ? (double)rows[job.last_off] * K.scale : 0.0;   // src[0] = last[2]  :3170
+        const double m1 = job.m1_off != ~0ull ? (double)rows[job.m1_off] * K.scale : 0.0;       // src[-1] = last[1]  :3171
+        __syncthreads();   // the tile before: its reads of both buffers are done
+        {   // (1) table indices max(k_lo, 1) .. k_hi from the row, 16 bytes a lane; indices 0 and -1 from `last`
+            const int k1 = max(k_lo, 1);
+            const unsigned long long g0 = job.src_off + (unsigned long long)(k1 - 1), ga = g0 & ~3ull;
+            const int head = (int)(g0 - ga), nrow = min(k_hi - k1 + 1, nst - (k1 - k_lo));
+            const int nvec = nrow > 0 ? (head + nrow + 3) >> 2 : 0;
+            double *const w1 = win + (k1 - k_lo) - head;   // slot of element ga
+            for (int v = tid; v < nvec; v += 256) {
+                const int4 u = *reinterpret_cast<const int4 *>(rows + ga + 4ull * (unsigned)v);
+                const int e = 4 * v - head;   // the vector's first element, counted from the window's first row element
+                if (e >= 0 && e < nrow) w1[4 * v] = (double)u.x * K.scale;
+                if (e + 1 >= 0 && e + 1 < nrow) w1[4 * v + 1] = (double)u.y * K.scale;
+                if (e + 2 >= 0 && e + 2 < nrow) w1[4 * v + 2] = (double)u.z * K.scale;
+                if (e + 3 >= 0 && e + 3 < nrow) w1[4 * v + 3] = (double)u.w * K.scale;
+            }
+            if (tid < k1 - k_lo && tid < nst) win[tid] = (k_lo + tid == 0) ? z0 : m1;
+        }
+        __syncthreads();
+        auto tab = [&](int k) { return win[min(max(k - k_lo, 0), last)]; };   // (the clamp is a no-op on a window the host sized)
+        for (int idx = tid; idx < total; idx += 256) {   // (2)
+            const double x = pos(of + (unsigned)idx);
+            const double ffx = floor(x);
+            const int k = (int)ffx;
+            double s;
+            if (x == ffx) s = tab(k);   // x % 1 == 0: src[x]  :3177
+            else {
+                const double fx = x - ffx;
+                if constexpr (INTERP == AUKIT_INTERP_NONE) s = tab(k);
+                else if constexpr (INTERP == AUKIT_INTERP_LINEAR) { const double a = tab(k), b = (k + 1 <= n) ? tab(k + 1) : a; s = linear_exact(a, b, fx); }
+                else {
+                    const double p1 = tab(k), p0 = (k - 1 >= -1) ? tab(k - 1) : p1, p2 = (k + 1 <= n) ? tab(k + 1) : p1, p3 = (k + 2 <= n) ? tab(k + 2) : p2;
+                    s = cubic_exact(p0, p1, p2, p3, fx);
+                }
+            }
+            xb[skew(idx)] = s;   // (no clamp: :3178)
+        }
+        __syncthreads();
+        const int e0 = tid * E;
+        double y[E];
+        if (e0 < cnt) {   // (3)
+            const int start = wl + e0;
+            const int ws = min(K.W, start), begin = start - ws;
+            double ls = 0;
+            if (of + (unsigned)begin == 0) ls = z0 / (z0 < 0 ? 128 : 127);   // the warm-up reaches the job's first output  :3172
+            for (int i = begin; i < start; i++) { const double s = ls + K.lp_alpha * (xb[skew(i)] - ls); ls = s; }
+#pragma unroll
+            for (int i = 0; i < E; i++) {
+                const double xv = e0 + i < cnt ? xb[skew(start + i)] : 0.0;
+                const double s = ls + K.lp_alpha * (xv - ls);   // :3179
+                ls = s;
+                y[i] = lua_clamp(s * (s < 0 ? 128 : 127), -128, 127);   // :3181
+            }
+        }
+        __syncthreads();   // every warm-up has read the interpolated samples: the results take their place
+        if (e0 < cnt) {
+#pragma unroll
+            for (int i = 0; i < E; i++)
+                if (e0 + i < cnt) xb[skew(wl + e0 + i)] = y[i];
+        }
+        __syncthreads();
+        OUT_T *const orow = out + job.out_off + o0;
+        for (int idx = tid; idx < cnt; idx += 256) orow[idx] = (OUT_T)xb[skew(wl + idx)];   // (4)
+    }
+}
+
+// the tail of a batch's FLAC jobs: tables to the context's buffers, one launch, timed under its name.  lds: the largest class's
+int smix_flac_tail_launch(aukit_ctx *ctx, const std::vector<SMixFlacClass> &classes, const std::vector<SMixFlacJob> &jobs, const std::vector<SMixFlacTile> &tiles, size_t lds,
+                          const int *rows, void *out, int interp, int dtype, uint64_t algorithmic_bytes) {
+    static const char *names[] = {"k_smix_flac_tail<none>", "k_smix_flac_tail<linear>", "k_smix_flac_tail<cubic>"};
+    int rc;
+    if ((rc = upload_table(ctx, ctx->misc_buf, classes.data(), classes.size() * sizeof(SMixFlacClass))) ||
+        (rc = upload_table(ctx, ctx->seg_buf, jobs.data(), jobs.size() * sizeof(SMixFlacJob))) ||
+        (rc = upload_table(ctx, ctx->tile_buf, tiles.data(), tiles.size() * sizeof(SMixFlacTile))))
+        return rc;
+    SMixFlacParams P;
+    P.tiles = reinterpret_cast<const SMixFlacTile *>(ctx->tile_buf.p);
+    P.jobs = reinterpret_cast<const SMixFlacJob *>(ctx->seg_buf.p);
+    P.classes = reinterpret_cast<const SMixFlacClass *>(ctx->misc_buf.p);
+    P.n_tiles = (unsigned)tiles.size();
+    P.rows = rows;
+    P.out = out;
+    // (a finer hand-out than the resident count, as k_smix_qoa_tail's: tiles of different classes and of short frames differ in cost)
+    const unsigned grid = (unsigned)std::min<uint64_t>(tiles.size(), (uint64_t)ctx->num_cus * 64);
+    if ((rc = ctx_begin_kernel(ctx))) return rc;
+    mixed_dispatch(interp, dtype, [&](auto ip_, auto t_) {
+        hipLaunchKernelGGL((k_smix_flac_tail<decltype(ip_)::value, decltype(t_)>), dim3(grid), dim3(256), lds, ctx->stream, P);
+    });
+    AUKIT_HIP_CHECK(hipGetLastError());
+    return ctx_end_kernel(ctx, names[interp], algorithmic_bytes);
+}
+
+}  // namespace aukit

@@ -22,7 +22,7 @@ typedef struct { int32_t codec, channels; double sample_rate; int32_t bit_depth,
 typedef struct { aukit_codec_desc desc; uint64_t payload_off, payload_len; int32_t wav_data_type, bit_depth; double length_seconds; } aukit_container;
 const char *aukit_last_error(void);
 int aukit_ctx_create(aukit_ctx **out, int device); void aukit_ctx_destroy(aukit_ctx *ctx);
-int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);  /* 9: AUKIT_OPT_STREAM_MIXED_FRAME_CODECS (stream.many's `qoa`) */
+int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);  /* 9: AUKIT_OPT_STREAM_MIXED_FRAME_CODECS (stream.many's `qoa`); 12: AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS (its `flac`) */
 int aukit_parse_container(const uint8_t *bytes, uint64_t n, int kind, int stream, aukit_container *out);
 int aukit_batch_upload(aukit_ctx *, aukit_batch **, const uint8_t *bytes, const uint64_t *offsets, uint32_t n);
 int aukit_batch_info(const aukit_batch *, uint32_t *n, uint64_t *total); int aukit_batch_download(aukit_ctx *, const aukit_batch *, uint8_t *dst); void aukit_batch_free(aukit_batch *);
@@ -877,16 +877,20 @@ end
 -- QOA files (magic "qoaf") are taken whole with the key `qoa` of the options table, {mono = ..., qoa = true}: the descriptor names the codec only, the
 -- pair is aukit.stream.qoa(file, mono)'s (length file_samples / rate), and for this one call the context is opted in under an option of its own
 -- (AUKIT_OPT_STREAM_MIXED_FRAME_CODECS, option 9, bit 1 << AUKIT_CODEC_QOA) and put back behind it, also where the call is refused.
+-- FLAC files (magic "fLaC") are taken whole with the key `flac`, {mono = ..., flac = true}: the descriptor names the codec only (channel count, depth
+-- and rate are the file's STREAMINFO's), the pair is aukit.stream.flac(file, mono)'s (length total samples / rate), and for this one call the context
+-- is opted in under a third option (AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS, option 12, bit 1 << AUKIT_CODEC_FLAC) and put back behind it, also where the
+-- call is refused.  aukit.stream.flac ignores `mono`: with it only one-channel FLAC files join the list.  Without the key such a file is refused by index.
 function aukit.stream.many(files, mono)
     expect(1, files, "table") expect(2, mono, "boolean", "table", "nil")
-    local adpcm, msadpcm, qoa = false, false, false
+    local adpcm, msadpcm, qoa, flac = false, false, false, false
     if type(mono) == "table" then
-        for k in pairs(mono) do if k ~= "mono" and k ~= "adpcm" and k ~= "msadpcm" and k ~= "qoa" then error("bad argument #2 (unknown option " .. tostring(k) .. ")", 2) end end
+        for k in pairs(mono) do if k ~= "mono" and k ~= "adpcm" and k ~= "msadpcm" and k ~= "qoa" and k ~= "flac" then error("bad argument #2 (unknown option " .. tostring(k) .. ")", 2) end end
         if (mono.mono ~= nil and type(mono.mono) ~= "boolean") or (mono.adpcm ~= nil and type(mono.adpcm) ~= "boolean") or (mono.msadpcm ~= nil and type(mono.msadpcm) ~= "boolean") or
-           (mono.qoa ~= nil and type(mono.qoa) ~= "boolean") then
+           (mono.qoa ~= nil and type(mono.qoa) ~= "boolean") or (mono.flac ~= nil and type(mono.flac) ~= "boolean") then
             error("bad argument #2 (expected boolean options)", 2)
         end
-        mono, adpcm, msadpcm, qoa = mono.mono, mono.adpcm or false, mono.msadpcm or false, mono.qoa or false
+        mono, adpcm, msadpcm, qoa, flac = mono.mono, mono.adpcm or false, mono.msadpcm or false, mono.qoa or false, mono.flac or false
     end
     local n = #files
     local descs = ffi.new("aukit_codec_desc[?]", math.max(n, 1))
@@ -906,6 +910,10 @@ function aukit.stream.many(files, mono)
             descs[i - 1] = desc {codec = "qoa"}   -- only the codec is read: channel count and rate are the file header's
             parts[i] = f
             lengths[i] = 0 / 0   -- NaN: aukit.stream.qoa's own figure stands (file_samples / sampleRate)
+        elseif flac and type(f) == "string" and f:sub(1, 4) == "fLaC" then
+            descs[i - 1] = desc {codec = "flac"}   -- only the codec is read: channel count, depth and rate are STREAMINFO's
+            parts[i] = f
+            lengths[i] = 0 / 0   -- NaN: aukit.stream.flac's own figure stands (total samples / sampleRate)
         else
             if type(f) ~= "string" then error("bad argument #1 (file " .. (i - 1) .. ": expected string)", 2) end
             local kind
@@ -936,10 +944,13 @@ function aukit.stream.many(files, mono)
     if msadpcm then check(C.aukit_ctx_set_option(ctx(), 6, 2 ^ CODEC.msadpcm)) end
     -- qoa: AUKIT_OPT_STREAM_MIXED_FRAME_CODECS (9) with bit 1 << AUKIT_CODEC_QOA, likewise
     if qoa then check(C.aukit_ctx_set_option(ctx(), 9, 2 ^ CODEC.qoa)) end
+    -- flac: AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS (12) with bit 1 << AUKIT_CODEC_FLAC, likewise
+    if flac then check(C.aukit_ctx_set_option(ctx(), 12, 2 ^ CODEC.flac)) end
     local rc = C.aukit_stream_decode_mixed(ctx(), batch, descs, n, INTERP[aukit.defaultInterpolation], mono and 1 or 0, F64, o, ck)
     local words = rc ~= 0 and ffi.string(C.aukit_last_error()) or nil
     if msadpcm then C.aukit_ctx_set_option(ctx(), 6, 0) end
     if qoa then C.aukit_ctx_set_option(ctx(), 9, 0) end
+    if flac then C.aukit_ctx_set_option(ctx(), 12, 0) end
     if words then error(words, 2) end
     local whole = ffi.gc(o[0], C.aukit_audio_free)
     local cnt, mx = ffi.new("uint32_t[1]"), ffi.new("uint32_t[1]")

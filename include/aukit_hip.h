@@ -192,12 +192,19 @@ typedef enum {
                                    named (or "bit N"), and the context keeps the mask it had.  Options 7 and 8 know their one bit each and refuse
                                    this one by name; options 5, 6 and 9 are not needed for a set and open it to nothing; this option opens neither
                                    mixed call.  With 0 every call answers exactly as before. */
-    AUKIT_OPT_MIXED_FRAME_CODECS = 11 /* a second mask of aukit_decode_resample_mixed's, the only call that reads it: a bit mask of 1 << codec, 0 by
+    AUKIT_OPT_MIXED_FRAME_CODECS = 11,/* a second mask of aukit_decode_resample_mixed's, the only call that reads it: a bit mask of 1 << codec, 0 by
                                    default, exactly one bit known, 1 << AUKIT_CODEC_FLAC (whole .flac files as streams of a mixed batch, see that
                                    call); any other bit is AUKIT_E_UNSUPPORTED, the codec named (or "bit N"), and the context keeps the mask it had.
                                    A second option and not a second bit of option 5, which knows its one bit and refuses this one by name.  It opens
                                    neither aukit_stream_decode_mixed nor aukit_streamset_open to anything.  With 0 every call answers exactly as
                                    before. */
+    AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS = 12 /* a third mask of aukit_stream_decode_mixed's, the only call that reads it (a stream set hands its engine 0 and
+                                   keeps refusing the codec): a bit mask of 1 << codec, 0 by default, exactly one bit known, 1 << AUKIT_CODEC_FLAC
+                                   (aukit.stream.flac's files, see that call); any other bit is AUKIT_E_UNSUPPORTED, the codec named (or "bit N"),
+                                   and the context keeps the mask it had.  An option of its own: options 6 and 9 know their one bit each and refuse
+                                   this one by name.  Options 5 to 11 do not open the stream call to FLAC; this option opens it to nothing else, and
+                                   opens neither aukit_decode_resample_mixed (option 11 does) nor aukit_streamset_open.  With 0 every call answers
+                                   exactly as before. */
 } aukit_option;
 int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);
 /* counters of the most recent call that produced them (AUKIT_OPT_COLLECT_STATS = 1) */
@@ -449,11 +456,32 @@ int aukit_stream_decode_table(aukit_ctx *ctx, const double *values, const uint64
  * aukit_stream_decode, which serves them: a frame of more than 8192 samples, a rate so low that the low-pass's warm-up (ceil(41.86 / (2 pi rate /
  * 96000)) outputs: 640 at 1000 Hz) exceeds one tile of 2048 outputs, and a rate so high that a tile's window exceeds 64 KiB of LDS.  Sinc is
  * refused as for the whole call.
+ * AUKIT_CODEC_FLAC is taken only on a context that asked for it, AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS with bit 1 << AUKIT_CODEC_FLAC (without it the
+ * codec is refused by name in the words of before, whatever options 5 to 11 say; with it the refusal of a further codec names AUKIT_CODEC_FLAC
+ * under its option, behind option 6's and option 9's clauses where those are set).  Stream s is aukit.stream.flac (data_s, mono) (:3124-3191), what
+ * aukit_stream_decode gives for a one-stream batch of its bytes: only `codec` of the descriptor is read; channel count (1 .. 8), depth and sample
+ * rate are the file's STREAMINFO's.  The reference ignores `mono` for FLAC, and so does this call: a FLAC member keeps its header's channel count
+ * whatever `mono` says, and the channel rule below reads that count — with `mono` a FLAC member of more than one channel is AUKIT_E_ARG, streams
+ * differ in channel count, with the stream's index, and a one-channel member joins the mixed-down batch unchanged.  An iterator call accumulates
+ * frames while #chunk[1] < sampleRate (:3161), a frame yielding floor(blocksize * 48000 / rate) outputs per channel; pos is summed from 0, whatever a
+ * stream handle on the context carries; length_seconds is STREAMINFO's sample count / rate.  A stream whose chain ends in a frame error or inside a
+ * frame delivers the chunks before it with status 0, as the iterator swallows the error.  The samples are not floored: AUKIT_F64 holds the
+ * reference's doubles to the bar of aukit_stream_decode's warm-up tail, AUKIT_F32 that value rounded once.  A batch with such a stream pays, before
+ * `*out` and `*chunks` are touched, a header pass over its FLAC members (one read-back; what the stream's own call refuses of a header — Invalid
+ * magic string, Stream info metadata block absent, Sample depth not supported, data string too short — is refused with its words and the stream's
+ * index) and, per (channels, depth) group, the frame-parallel decoder on the group's compacted bytes, whose int32 rows wait in a buffer of the
+ * context's own.  The tail — rows scaled by 2^-depth, table indices 0 and -1 the last two samples the reference's walk has seen (shared across
+ * channels and frames), interpolation without a clamp, the recursive low-pass seeded per (frame, channel) block, the 128 / 127 scaling and the
+ * clamp — is one more launch, k_smix_flac_tail, for every (rate, depth) class of the batch at once and the call's last (behind k_smix_qoa_tail
+ * where the batch has QOA members too); a batch of FLAC files alone launches only it behind the decoders.  AUKIT_E_UNSUPPORTED by stream index,
+ * pointing to aukit_stream_decode, which serves them: a stream whose rows would be doubles (a depth of 32, a value beyond int32), a rate so low that
+ * the low-pass's warm-up exceeds one tile of 2048 outputs (below about 320 Hz) and a rate so high that a tile's window exceeds 64 KiB of LDS (no
+ * rate a STREAMINFO block holds).  Of several offenders the lowest index is named.  Sinc is refused as for the whole call.
  * n_descs must be the batch's stream count; without
  * `mono` the descriptors must agree in channel count (AUKIT_E_ARG).  A stream whose own call would fail fails the whole call with that status
  * and message, the stream's index appended.  PCM data that ends inside a frame is served with the mix-down (the partial frame counts for
  * nothing) and refused without it whatever AUKIT_OPT_CHANNEL_LENS says: the uneven last chunk stays with aukit_stream_decode.  Every refusal
- * happens before anything is allocated or launched (the header scan, the MS-ADPCM pre-pass, the QOA walks and decoder and their scratch excepted) and leaves `*out` and
+ * happens before anything is allocated or launched (the header scan, the MS-ADPCM pre-pass, the QOA walks and decoder, the FLAC header pass and decoders and their scratch excepted) and leaves `*out` and
  * `*chunks` as they were. */
 int aukit_stream_decode_mixed(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs /* n */, uint32_t n_descs,
                               int interp, int mono, int dtype, aukit_audio **out, aukit_chunks **chunks);
