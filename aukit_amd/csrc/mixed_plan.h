@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "resample.h"
+#include "mixed_words.h"
 
 namespace aukit {
 
@@ -20,11 +21,11 @@ static inline int mixed_check_call(const aukit_ctx *ctx, const aukit_batch *in, 
     return AUKIT_OK;
 }
 
-// every codec must be one of `served`.  `words`: the call's refusal, a format of the stream's index (%u) and its codec (%d), which names what the
-// call serves
-static inline int mixed_check_codecs(const aukit_codec_desc *descs, uint32_t n, std::initializer_list<int> served, const char *words) {
+// every codec must be one the call serves under its options (`rule`: mixed_words.h, which also makes the refusal's sentence, a format of the
+// stream's index and its codec that names what the call serves)
+static inline int mixed_check_served(const aukit_codec_desc *descs, uint32_t n, const ServedRule &rule) {
     for (uint32_t s = 0; s < n; s++)
-        if (std::find(served.begin(), served.end(), descs[s].codec) == served.end()) return fail(AUKIT_E_UNSUPPORTED, words, s, descs[s].codec);
+        if (!served(rule, descs[s].codec)) return fail(AUKIT_E_UNSUPPORTED, served_words(rule).c_str(), s, descs[s].codec);
     return AUKIT_OK;
 }
 
@@ -157,6 +158,30 @@ static inline void mixed_dispatch(int interp, int dtype, F &&f) {
     };
     if (dtype == AUKIT_F64) typed(double()); else typed(float());
 }
+// The launch the stream call's two tails end in (k_smix_qoa_tail, k_smix_flac_tail): mixed_launch for their records — the class, job and tile
+// tables go to the context's buffers, P gets them, the rows and the output, launch(grid, P) enqueues the kernel and the timed region is closed under
+// `name`.  The grid is a finer hand-out than the resident count, as k_iir_tail's: tiles of different classes and of short frames differ in cost
+template <class Params, class Class, class Job, class Tile, class Row, class Launch>
+static inline int mixed_tail_launch(aukit_ctx *ctx, const std::vector<Class> &classes, const std::vector<Job> &jobs, const std::vector<Tile> &tiles, const Row *rows, void *out,
+                                    const char *name, uint64_t algorithmic_bytes, Launch launch) {
+    int rc;
+    if ((rc = upload_table(ctx, ctx->misc_buf, classes.data(), classes.size() * sizeof(Class))) || (rc = upload_table(ctx, ctx->seg_buf, jobs.data(), jobs.size() * sizeof(Job))) ||
+        (rc = upload_table(ctx, ctx->tile_buf, tiles.data(), tiles.size() * sizeof(Tile))))
+        return rc;
+    Params P;
+    P.tiles = reinterpret_cast<const Tile *>(ctx->tile_buf.p);
+    P.jobs = reinterpret_cast<const Job *>(ctx->seg_buf.p);
+    P.classes = reinterpret_cast<const Class *>(ctx->misc_buf.p);
+    P.n_tiles = (unsigned)tiles.size();
+    P.rows = rows;
+    P.out = out;
+    const unsigned grid = (unsigned)std::min<uint64_t>(tiles.size(), (uint64_t)ctx->num_cus * 64);
+    if ((rc = ctx_begin_kernel(ctx))) return rc;
+    launch(grid, P);
+    AUKIT_HIP_CHECK(hipGetLastError());
+    return ctx_end_kernel(ctx, name, algorithmic_bytes);
+}
+
 // launches KERNEL<INTERP, OUT_T, flags...> (256 threads) on ctx->stream; the flags are compile-time, so every flag combination is a statement of its own
 #define AUKIT_MIXED_LAUNCH(ctx, KERNEL, interp, dtype, grid, lds, P, ...)                                                                             \
     mixed_dispatch(interp, dtype, [&](auto ip_, auto t_) {                                                                                            \

@@ -297,25 +297,8 @@ static int mix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec
     const uint32_t n = in->n;
     // AUKIT_OPT_MIXED_CODECS: MS-ADPCM joins the list on a context that asked for it; without the bit the call answers in the words of before
     // AUKIT_OPT_MIXED_FRAME_CODECS: FLAC likewise, under an option of its own; its clause stands behind option 5's
-    const bool with_flac = (ctx->mixed_frame_codecs >> AUKIT_CODEC_FLAC) & 1u;
-    if (with_flac && ((ctx->mixed_codecs >> AUKIT_CODEC_MSADPCM) & 1u))
-        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_MSADPCM, AUKIT_CODEC_FLAC},
-                                "stream %u: codec %d has its own loader (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, "
-                                "AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_MIXED_CODECS, AUKIT_CODEC_MSADPCM and, under "
-                                "AUKIT_OPT_MIXED_FRAME_CODECS, AUKIT_CODEC_FLAC)");
-    else if (with_flac)
-        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_FLAC},
-                                "stream %u: codec %d has its own loader (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, "
-                                "AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_MIXED_FRAME_CODECS, AUKIT_CODEC_FLAC)");
-    else if ((ctx->mixed_codecs >> AUKIT_CODEC_MSADPCM) & 1u)
-        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_MSADPCM},
-                                "stream %u: codec %d has its own loader (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, "
-                                "AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_MIXED_CODECS, AUKIT_CODEC_MSADPCM)");
-    else
-        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, AUKIT_CODEC_QOA, AUKIT_CODEC_ADPCM_WAV},
-                                "stream %u: codec %d has its own loader (per-stream descriptors serve AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_DFPWM, "
-                                "AUKIT_CODEC_QOA and AUKIT_CODEC_ADPCM_WAV)");
-    if (rc) return rc;
+    // (the sentence and the served set: mixed_words.h)
+    if ((rc = mixed_check_served(descs, n, mix_served((ctx->mixed_codecs >> AUKIT_CODEC_MSADPCM) & 1u, (ctx->mixed_frame_codecs >> AUKIT_CODEC_FLAC) & 1u)))) return rc;
     S.ch.resize(n);
     S.rate.resize(n);
     for (uint32_t s = 0; s < n; s++) {

@@ -12,12 +12,12 @@
 #include <cmath>
 #include <cstdint>
 #include <vector>
+#include "stream_mixed_tail.h"
 
 namespace aukit {
 
-constexpr int SMIX_FLAC_E = 8;                     // consecutive outputs per thread of k_smix_flac_tail
-constexpr int SMIX_FLAC_TMAX = 256 * SMIX_FLAC_E;  // outputs per tile at the most
-constexpr size_t SMIX_FLAC_LDS = 64 * 1024;        // what a class's window and sample buffer may take together
+constexpr int SMIX_FLAC_E = SMIX_TAIL_E, SMIX_FLAC_TMAX = SMIX_TAIL_TMAX;   // k_smix_flac_tail's names for the shared constants
+constexpr size_t SMIX_FLAC_LDS = SMIX_TAIL_LDS;
 
 struct SMixFlacClass {
     double ratio, rcp;         // x = (i - 1) / ratio + 1  :3174
@@ -49,35 +49,19 @@ struct SMixFlacParams {
     void *out;
 };
 
-// The class of (rate, depth): stream_mixed_qoa.h's shape with the tile height the class's own.  A state W outputs back still shows as a^W of it,
-// a = exp(-decay): below 1e-16 of a sample of magnitude 128 after W = ceil((37 + ln 128) / decay) outputs (a FLAC state is below 1 in magnitude:
-// the same W leaves 1e-18 of it).
-// -> 0; 1: the warm-up does not fit one tile (very low rates); 2: the window exceeds the LDS budget (very high rates)
+// The class of (rate, depth): the window's shape is the rate's (smix_tail_shape, stream_mixed_tail.h: its return codes).  A FLAC state is below 1 in
+// magnitude: the warm-up sized for a sample of 128 leaves 1e-18 of it
 static inline int smix_flac_class_shape(double rate, int depth, SMixFlacClass *K, size_t *lds) {
+    SMixTailShape S;
+    const int why = smix_tail_shape(rate, &S);   // ratio :3154, lp_alpha :3155
     *K = SMixFlacClass{};
+    K->ratio = S.ratio; K->rcp = S.rcp; K->lp_alpha = S.lp_alpha;
+    K->W = S.W; K->T = S.T; K->cap = S.cap; K->xbn = S.xbn;
     K->depth = depth;
     K->full = std::ldexp(1.0, depth);
     K->scale = std::ldexp(1.0, -depth);
-    K->ratio = 48000 / rate;                                         // :3154
-    K->rcp = 1.0 / K->ratio;
-    K->lp_alpha = 1 - std::exp(-(rate / 96000) * 2 * M_PI);          // :3155
-    const double decay = (rate / 96000) * 2 * M_PI;
-    const double wd = std::ceil((37.0 + std::log(128.0)) / decay);
-    auto shape = [&](int T, double w, int *cap, int *xbn) {
-        const double capd = std::ceil(((double)T + w) / K->ratio) + 8;
-        const double tot = (double)T + w;
-        *cap = capd < 1e9 ? (((int)capd + 3) & ~3) : 0x40000000;
-        *xbn = ((int)tot + (int)tot / SMIX_FLAC_E + 2 + 3) & ~3;
-        return ((size_t)*cap + (size_t)*xbn) * 8;
-    };
-    int T = SMIX_FLAC_TMAX;
-    if (!(wd <= (double)T)) return 1;
-    while (T > 256 && (double)(T / 2) >= wd && shape(T, wd, &K->cap, &K->xbn) > SMIX_FLAC_LDS) T /= 2;
-    *lds = shape(T, wd, &K->cap, &K->xbn);
-    if (*lds > SMIX_FLAC_LDS) return 2;
-    K->W = (int)wd;
-    K->T = T;
-    return 0;
+    *lds = S.lds;
+    return why;
 }
 
 // what a frame of `bs` samples yields per channel: floor(blocksize * ratio)  (:3173)

@@ -118,26 +118,11 @@ __global__ __launch_bounds__(256) void k_smix_flac_tail(const SMixFlacParams P) 
 int smix_flac_tail_launch(aukit_ctx *ctx, const std::vector<SMixFlacClass> &classes, const std::vector<SMixFlacJob> &jobs, const std::vector<SMixFlacTile> &tiles, size_t lds,
                           const int *rows, void *out, int interp, int dtype, uint64_t algorithmic_bytes) {
     static const char *names[] = {"k_smix_flac_tail<none>", "k_smix_flac_tail<linear>", "k_smix_flac_tail<cubic>"};
-    int rc;
-    if ((rc = upload_table(ctx, ctx->misc_buf, classes.data(), classes.size() * sizeof(SMixFlacClass))) ||
-        (rc = upload_table(ctx, ctx->seg_buf, jobs.data(), jobs.size() * sizeof(SMixFlacJob))) ||
-        (rc = upload_table(ctx, ctx->tile_buf, tiles.data(), tiles.size() * sizeof(SMixFlacTile))))
-        return rc;
-    SMixFlacParams P;
-    P.tiles = reinterpret_cast<const SMixFlacTile *>(ctx->tile_buf.p);
-    P.jobs = reinterpret_cast<const SMixFlacJob *>(ctx->seg_buf.p);
-    P.classes = reinterpret_cast<const SMixFlacClass *>(ctx->misc_buf.p);
-    P.n_tiles = (unsigned)tiles.size();
-    P.rows = rows;
-    P.out = out;
-    // (a finer hand-out than the resident count, as k_smix_qoa_tail's: tiles of different classes and of short frames differ in cost)
-    const unsigned grid = (unsigned)std::min<uint64_t>(tiles.size(), (uint64_t)ctx->num_cus * 64);
-    if ((rc = ctx_begin_kernel(ctx))) return rc;
-    mixed_dispatch(interp, dtype, [&](auto ip_, auto t_) {
-        hipLaunchKernelGGL((k_smix_flac_tail<decltype(ip_)::value, decltype(t_)>), dim3(grid), dim3(256), lds, ctx->stream, P);
+    return mixed_tail_launch<SMixFlacParams>(ctx, classes, jobs, tiles, rows, out, names[interp], algorithmic_bytes, [&](unsigned grid, const SMixFlacParams &P) {
+        mixed_dispatch(interp, dtype, [&](auto ip_, auto t_) {
+            hipLaunchKernelGGL((k_smix_flac_tail<decltype(ip_)::value, decltype(t_)>), dim3(grid), dim3(256), lds, ctx->stream, P);
+        });
     });
-    AUKIT_HIP_CHECK(hipGetLastError());
-    return ctx_end_kernel(ctx, names[interp], algorithmic_bytes);
 }
 
 }  // namespace aukit

@@ -13,12 +13,12 @@
 #include <cmath>
 #include <cstdint>
 #include <vector>
+#include "stream_mixed_tail.h"
 
 namespace aukit {
 
-constexpr int SMIX_QOA_E = 8;                   // consecutive outputs per thread of k_smix_qoa_tail
-constexpr int SMIX_QOA_TMAX = 256 * SMIX_QOA_E; // outputs per tile at the most
-constexpr size_t SMIX_QOA_LDS = 64 * 1024;      // what a class's window and sample buffer may take together
+constexpr int SMIX_QOA_E = SMIX_TAIL_E, SMIX_QOA_TMAX = SMIX_TAIL_TMAX;   // k_smix_qoa_tail's names for the shared constants
+constexpr size_t SMIX_QOA_LDS = SMIX_TAIL_LDS;
 
 // one iterator call of a stream as the fill pass of the walk reports it (qoa.hip's QoaCallRec)
 struct QoaSMixCall {
@@ -91,32 +91,16 @@ static inline bool smix_qoa_drop(const uint32_t *end, const uint32_t *samples, u
     return true;
 }
 
-// The class of (channels, rate): stream_tail.hip's tail_shape for int8 rows, with the tile height the class's own.  A state W outputs back still shows
-// as a^W of it, a = exp(-decay): below 1e-16 of a sample of magnitude 128 after W = ceil((37 + ln 128) / decay) outputs.
-// -> 0; 1: the warm-up does not fit one tile (very low rates); 2: the window exceeds the LDS budget (very high rates)
+// The class of (channels, rate): the window's shape is the rate's (smix_tail_shape, stream_mixed_tail.h: its return codes), for int8 rows
 static inline int smix_qoa_class_shape(int channels, double rate, SMixQoaClass *K, size_t *lds) {
+    SMixTailShape S;
+    const int why = smix_tail_shape(rate, &S);   // ratio :3250, lp_alpha :3251
     *K = SMixQoaClass{};
+    K->ratio = S.ratio; K->rcp = S.rcp; K->lp_alpha = S.lp_alpha;
+    K->W = S.W; K->T = S.T; K->cap = S.cap; K->xbn = S.xbn;
     K->channels = channels;
-    K->ratio = 48000 / rate;                                         // :3250
-    K->rcp = 1.0 / K->ratio;
-    K->lp_alpha = 1 - std::exp(-(rate / 96000) * 2 * M_PI);          // :3251
-    const double decay = (rate / 96000) * 2 * M_PI;
-    const double wd = std::ceil((37.0 + std::log(128.0)) / decay);
-    auto shape = [&](int T, double w, int *cap, int *xbn) {
-        const double capd = std::ceil(((double)T + w) / K->ratio) + 8;
-        const double tot = (double)T + w;
-        *cap = capd < 1e9 ? (((int)capd + 3) & ~3) : 0x40000000;
-        *xbn = ((int)tot + (int)tot / SMIX_QOA_E + 2 + 3) & ~3;
-        return ((size_t)*cap + (size_t)*xbn) * 8;
-    };
-    int T = SMIX_QOA_TMAX;
-    if (!(wd <= (double)T)) return 1;
-    while (T > 256 && (double)(T / 2) >= wd && shape(T, wd, &K->cap, &K->xbn) > SMIX_QOA_LDS) T /= 2;
-    *lds = shape(T, wd, &K->cap, &K->xbn);
-    if (*lds > SMIX_QOA_LDS) return 2;
-    K->W = (int)wd;
-    K->T = T;
-    return 0;
+    *lds = S.lds;
+    return why;
 }
 
 // The chunk table of one stream from its call records, exactly as stream_qoa computes it: n_out = floor(n * ratio), 0 below 1 (:3312, :3317);

@@ -119,26 +119,11 @@ __global__ __launch_bounds__(256) void k_smix_qoa_tail(const SMixQoaParams P) {
 int smix_qoa_tail_launch(aukit_ctx *ctx, const std::vector<SMixQoaClass> &classes, const std::vector<SMixQoaJob> &jobs, const std::vector<SMixQoaTile> &tiles, size_t lds,
                          const signed char *rows, void *out, int interp, int dtype, uint64_t algorithmic_bytes) {
     static const char *names[] = {"k_smix_qoa_tail<none>", "k_smix_qoa_tail<linear>", "k_smix_qoa_tail<cubic>"};
-    int rc;
-    if ((rc = upload_table(ctx, ctx->misc_buf, classes.data(), classes.size() * sizeof(SMixQoaClass))) ||
-        (rc = upload_table(ctx, ctx->seg_buf, jobs.data(), jobs.size() * sizeof(SMixQoaJob))) ||
-        (rc = upload_table(ctx, ctx->tile_buf, tiles.data(), tiles.size() * sizeof(SMixQoaTile))))
-        return rc;
-    SMixQoaParams P;
-    P.tiles = reinterpret_cast<const SMixQoaTile *>(ctx->tile_buf.p);
-    P.jobs = reinterpret_cast<const SMixQoaJob *>(ctx->seg_buf.p);
-    P.classes = reinterpret_cast<const SMixQoaClass *>(ctx->misc_buf.p);
-    P.n_tiles = (unsigned)tiles.size();
-    P.rows = rows;
-    P.out = out;
-    // (the grid is a finer hand-out than the resident count, as k_iir_tail's: tiles of different classes differ in cost)
-    const unsigned grid = (unsigned)std::min<uint64_t>(tiles.size(), (uint64_t)ctx->num_cus * 64);
-    if ((rc = ctx_begin_kernel(ctx))) return rc;
-    mixed_dispatch(interp, dtype, [&](auto ip_, auto t_) {
-        hipLaunchKernelGGL((k_smix_qoa_tail<decltype(ip_)::value, decltype(t_)>), dim3(grid), dim3(256), lds, ctx->stream, P);
+    return mixed_tail_launch<SMixQoaParams>(ctx, classes, jobs, tiles, rows, out, names[interp], algorithmic_bytes, [&](unsigned grid, const SMixQoaParams &P) {
+        mixed_dispatch(interp, dtype, [&](auto ip_, auto t_) {
+            hipLaunchKernelGGL((k_smix_qoa_tail<decltype(ip_)::value, decltype(t_)>), dim3(grid), dim3(256), lds, ctx->stream, P);
+        });
     });
-    AUKIT_HIP_CHECK(hipGetLastError());
-    return ctx_end_kernel(ctx, names[interp], algorithmic_bytes);
 }
 
 // k_smix_qoa_last: for a stream set, behind a decode — pair i of `pairs` is what the call after a boundary reads as its table indices -1 and 0: the

@@ -629,33 +629,7 @@ int aukit_streamset_open(aukit_ctx *ctx, const aukit_codec_desc *descs, uint32_t
     const bool with_df = (ctx->streamset_codecs >> AUKIT_CODEC_DFPWM) & 1u, with_ms = (ctx->streamset_block_codecs >> AUKIT_CODEC_MSADPCM) & 1u;
     // AUKIT_OPT_STREAMSET_FRAME_CODECS: stream.qoa members, under a third option; its clause stands behind the others', which read as they do without it
     const bool with_qoa = (ctx->streamset_fcodecs >> AUKIT_CODEC_QOA) & 1u;
-    if (with_qoa) {
-        std::string words = "stream %u: codec %d keeps aukit_stream_open (a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV";
-        if (with_df) words += " and, under AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM";
-        if (with_ms) words += " and, under AUKIT_OPT_STREAMSET_BLOCK_CODECS, AUKIT_CODEC_MSADPCM";
-        words += " and, under AUKIT_OPT_STREAMSET_FRAME_CODECS, AUKIT_CODEC_QOA)";
-        rc = AUKIT_OK;
-        for (uint32_t s = 0; s < n && !rc; s++) {
-            const int c = descs[s].codec;
-            if (!(c == AUKIT_CODEC_PCM || c == AUKIT_CODEC_G711 || c == AUKIT_CODEC_ADPCM_WAV || c == AUKIT_CODEC_QOA || (with_df && c == AUKIT_CODEC_DFPWM) || (with_ms && c == AUKIT_CODEC_MSADPCM)))
-                rc = fail(AUKIT_E_UNSUPPORTED, words.c_str(), s, c);
-        }
-    } else if (with_df && with_ms)
-        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_DFPWM, AUKIT_CODEC_MSADPCM},
-                                "stream %u: codec %d keeps aukit_stream_open (a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV and, under "
-                                "AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM and, under AUKIT_OPT_STREAMSET_BLOCK_CODECS, AUKIT_CODEC_MSADPCM)");
-    else if (with_ms)
-        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_MSADPCM},
-                                "stream %u: codec %d keeps aukit_stream_open (a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV and, under "
-                                "AUKIT_OPT_STREAMSET_BLOCK_CODECS, AUKIT_CODEC_MSADPCM)");
-    else if (with_df)
-        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV, AUKIT_CODEC_DFPWM},
-                                "stream %u: codec %d keeps aukit_stream_open (a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV and, under "
-                                "AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM)");
-    else
-        rc = mixed_check_codecs(descs, n, {AUKIT_CODEC_PCM, AUKIT_CODEC_G711, AUKIT_CODEC_ADPCM_WAV},
-                                "stream %u: codec %d keeps aukit_stream_open (a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711 and AUKIT_CODEC_ADPCM_WAV)");
-    if (rc) return rc;
+    if ((rc = mixed_check_served(descs, n, sset_served(with_df, with_ms, with_qoa)))) return rc;   // (the sentence and the served set: mixed_words.h)
     if ((rc = mixed_check_channels(n, mono, [&](uint32_t s) { return descs[s].channels; }))) return rc;
     for (uint32_t s = 0; s < n; s++)
         if ((rc = check_smix_stream(&descs[s], 0, mono != 0))) return fail_for_stream(rc, s);

@@ -96,5 +96,6 @@ def test_header_comment_and_lua_shim_name_both_codecs():
     lua = open(os.path.join(ROOT, "aukit_amd", "lua", "aukit.lua")).read()
     body = lua[lua.index("function aukit.load_many("):lua.index("function aukit.load_many(") + 5000]
     assert '"qoaf"' in body and 'codec = "qoa"' in body and "the batch API takes IMA blocks" in body
-    src = open(os.path.join(ROOT, "aukit_amd", "csrc", "resample_mixed.hip")).read()
-    assert "stream %u: codec %d" in src and "AUKIT_CODEC_QOA and" in src and "AUKIT_CODEC_ADPCM_WAV)" in src
+    from tests.test_mixed_words_host import sentence, uses_the_shared_rule   # (where every sentence, as produced, is held against the words of before)
+    words = sentence("mix", "00")
+    assert uses_the_shared_rule("resample_mixed.hip", "mix_served") and words.startswith("stream %u: codec %d") and "AUKIT_CODEC_QOA and" in words and words.endswith("AUKIT_CODEC_ADPCM_WAV)")

@@ -137,8 +137,9 @@ def test_header_option_and_mirrors_name_the_codec():
     assert re.search(r"AUKIT_OPT_MIXED_CODECS\s*=\s*5\b", hdr) and N.OPT_MIXED_CODECS == 5
     assert re.search(r"#define\s+AUKIT_ABI_VERSION\s+2\b", hdr)
     assert "msadpcm_mixed.hip" in N.SOURCES
-    src = open(os.path.join(ROOT, "aukit_amd", "csrc", "resample_mixed.hip")).read()
-    assert "AUKIT_CODEC_QOA and AUKIT_CODEC_ADPCM_WAV)" in src and "under AUKIT_OPT_MIXED_CODECS, AUKIT_CODEC_MSADPCM)" in src
+    from tests.test_mixed_words_host import sentence, uses_the_shared_rule   # (where every sentence, as produced, is held against the words of before)
+    assert uses_the_shared_rule("resample_mixed.hip", "mix_served")
+    assert sentence("mix", "00").endswith("AUKIT_CODEC_QOA and AUKIT_CODEC_ADPCM_WAV)") and sentence("mix", "10").endswith("under AUKIT_OPT_MIXED_CODECS, AUKIT_CODEC_MSADPCM)")
     lua = open(os.path.join(ROOT, "aukit_amd", "lua", "aukit.lua")).read()
     assert re.search(r"aukit\.load_many = function\(files, sampleRate, interpolation, mono, adpcm\)", lua)
     body = lua[lua.index("function aukit.load_many("):]

@@ -126,8 +126,13 @@ def test_header_sources_mirrors_and_shim_name_the_codec_and_the_option():
                  "Invalid magic string", "streams differ in channel count"):
         assert word in comment, word
     src = _read("aukit_amd", "csrc", "stream_mixed.hip")
-    assert "AUKIT_CODEC_DFPWM and AUKIT_CODEC_ADPCM_WAV)" in src and "under AUKIT_OPT_STREAM_MIXED_CODECS, AUKIT_CODEC_MSADPCM)" in src   # the sentences of before
-    assert '" and, under AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS, AUKIT_CODEC_FLAC)"' in src
+    # the sentences of before, and this option's clause last in all four that have it: the call makes them by the shared rule
+    # (tests/test_mixed_words_host.py holds every one, as produced, against the words of before)
+    from tests.test_mixed_words_host import sentence, uses_the_shared_rule
+    assert uses_the_shared_rule("stream_mixed.hip", "smix_served")
+    assert sentence("smix", "000").endswith("AUKIT_CODEC_DFPWM and AUKIT_CODEC_ADPCM_WAV)") and sentence("smix", "100").endswith("under AUKIT_OPT_STREAM_MIXED_CODECS, AUKIT_CODEC_MSADPCM)")
+    for flags in ("001", "101", "011", "111"):
+        assert sentence("smix", flags).endswith(" and, under AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS, AUKIT_CODEC_FLAC)"), flags
     assert "ctx ? ctx->stream_mixed_chain_codecs : 0u" in src and src.count("ctx->stream_mixed_chain_codecs") == 1
     assert "if (carry) chain_codecs = 0;" in src   # a stream set keeps refusing the codec
     rt = _read("aukit_amd", "csrc", "runtime.hip")

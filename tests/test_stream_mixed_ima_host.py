@@ -134,5 +134,6 @@ def test_header_and_shim_name_the_codec():
     assert "AUKIT_CODEC_ADPCM_WAV" in body and "c.desc.codec ~= 3" in body and "descs[i - 1] = c.desc" in body   # the walk's descriptor, block_align included
     assert "stream.many takes PCM, G.711 and DFPWM payloads and IMA-ADPCM blocks (the other block codecs keep their own streams)" in body
     assert "mono.adpcm" in body and "(c.desc.codec ~= 3 or not adpcm)" in body   # on request only: {mono = ..., adpcm = true} in place of `mono`
-    src = open(os.path.join(ROOT, "aukit_amd", "csrc", "stream_mixed.hip")).read()
-    assert "AUKIT_CODEC_DFPWM and AUKIT_CODEC_ADPCM_WAV)" in src   # the "has its own stream" refusal names the codec among those served
+    # the "has its own stream" refusal names the codec among those served (tests/test_mixed_words_host.py holds the sentence, as produced, against the words of before)
+    from tests.test_mixed_words_host import sentence, uses_the_shared_rule
+    assert uses_the_shared_rule("stream_mixed.hip", "smix_served") and sentence("smix", "000").endswith("AUKIT_CODEC_DFPWM and AUKIT_CODEC_ADPCM_WAV)")

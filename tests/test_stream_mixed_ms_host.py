@@ -158,7 +158,9 @@ def test_header_mirrors_and_shim_name_the_codec_and_the_option():
                  "aukit.stream.msadpcm", "k_ms_mixed"):
         assert word in comment, word
     src = open(os.path.join(ROOT, "aukit_amd", "csrc", "stream_mixed.hip")).read()
-    assert "AUKIT_CODEC_DFPWM and AUKIT_CODEC_ADPCM_WAV)" in src and "under AUKIT_OPT_STREAM_MIXED_CODECS, AUKIT_CODEC_MSADPCM)" in src
+    from tests.test_mixed_words_host import sentence, uses_the_shared_rule   # (where every sentence, as produced, is held against the words of before)
+    assert uses_the_shared_rule("stream_mixed.hip", "smix_served")
+    assert sentence("smix", "000").endswith("AUKIT_CODEC_DFPWM and AUKIT_CODEC_ADPCM_WAV)") and sentence("smix", "100").endswith("under AUKIT_OPT_STREAM_MIXED_CODECS, AUKIT_CODEC_MSADPCM)")
     # one planner of the pre-pass's units, in the header both calls include
     plan = open(os.path.join(ROOT, "aukit_amd", "csrc", "mixed_plan.h")).read()
     dec = open(os.path.join(ROOT, "aukit_amd", "csrc", "resample_mixed.hip")).read()

@@ -39,9 +39,12 @@ def test_option_seven_in_header_native_and_shim():
     assert body.index("aukit_ctx_set_option(ctx(), 7, 2") < body.index("C.aukit_streamset_open(") < body.index("aukit_ctx_set_option(ctx(), 7, 0)") < body.index("if words then error(words, 2) end")
     rt = _read("aukit_amd", "csrc", "runtime.hip")
     assert '"AUKIT_OPT_STREAMSET_CODECS", "aukit_streamset_open takes", AUKIT_CODEC_DFPWM' in rt
-    src = _read("aukit_amd", "csrc", "streamset.hip")   # the words of before, and the words under the option
-    assert "(a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711 and AUKIT_CODEC_ADPCM_WAV)" in src
-    assert 'AUKIT_CODEC_ADPCM_WAV and, under "\n' in src and '"AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM)"' in src
+    # the words of before, and the words under the option: the open makes them by the shared rule (tests/test_mixed_words_host.py holds every
+    # sentence, as produced, against the words of before)
+    from tests.test_mixed_words_host import sentence, uses_the_shared_rule
+    assert uses_the_shared_rule("streamset.hip", "sset_served")
+    assert sentence("sset", "000").endswith("(a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711 and AUKIT_CODEC_ADPCM_WAV)")
+    assert sentence("sset", "100").endswith("AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM)")
 
 
 def test_sniff_set_with_the_request():

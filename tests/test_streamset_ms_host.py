@@ -43,11 +43,14 @@ def test_option_eight_in_header_native_and_shim():
     assert body.index("aukit_ctx_set_option(ctx(), 8, 2") < body.index("C.aukit_streamset_open(") < body.index("aukit_ctx_set_option(ctx(), 8, 0)") < body.index("if words then error(words, 2) end")
     rt = _read("aukit_amd", "csrc", "runtime.hip")
     assert '"AUKIT_OPT_STREAMSET_BLOCK_CODECS", "aukit_streamset_open takes")' in rt   # set_codec_mask's default `only`: AUKIT_CODEC_MSADPCM
-    src = _read("aukit_amd", "csrc", "streamset.hip")   # the two refusals of before, verbatim, and the words under the option
-    assert "(a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711 and AUKIT_CODEC_ADPCM_WAV)" in src
-    assert 'AUKIT_CODEC_ADPCM_WAV and, under "\n' in src and '"AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM)"' in src
-    assert '"AUKIT_OPT_STREAMSET_BLOCK_CODECS, AUKIT_CODEC_MSADPCM)"' in src
-    assert '"AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM and, under AUKIT_OPT_STREAMSET_BLOCK_CODECS, AUKIT_CODEC_MSADPCM)"' in src
+    # the two refusals of before and the words under the option: the open makes them by the shared rule (tests/test_mixed_words_host.py holds every
+    # sentence, as produced, against the words of before)
+    from tests.test_mixed_words_host import sentence, uses_the_shared_rule
+    assert uses_the_shared_rule("streamset.hip", "sset_served")
+    assert sentence("sset", "000").endswith("(a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711 and AUKIT_CODEC_ADPCM_WAV)")
+    assert sentence("sset", "100").endswith("AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM)")
+    assert sentence("sset", "010").endswith("AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_STREAMSET_BLOCK_CODECS, AUKIT_CODEC_MSADPCM)")
+    assert sentence("sset", "110").endswith("AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM and, under AUKIT_OPT_STREAMSET_BLOCK_CODECS, AUKIT_CODEC_MSADPCM)")
     # the engine takes the mask from its caller: the context's option 6 is read by the public call alone
     eng = _read("aukit_amd", "csrc", "stream_mixed.hip")
     assert eng.count("ctx->stream_mixed_codecs") == 1 and "ctx ? ctx->stream_mixed_codecs : 0u" in eng

@@ -50,12 +50,16 @@ def test_option_ten_in_header_native_and_shim():
     assert order == sorted(order), order
     rt = _read("aukit_amd", "csrc", "runtime.hip")
     assert '"AUKIT_OPT_STREAMSET_FRAME_CODECS", "aukit_streamset_open takes", AUKIT_CODEC_QOA)' in rt
-    src = _read("aukit_amd", "csrc", "streamset.hip")   # the four refusals of before, verbatim, and the clause under the option
-    assert "(a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711 and AUKIT_CODEC_ADPCM_WAV)" in src
-    assert 'AUKIT_CODEC_ADPCM_WAV and, under "\n' in src and '"AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM)"' in src
-    assert '"AUKIT_OPT_STREAMSET_BLOCK_CODECS, AUKIT_CODEC_MSADPCM)"' in src
-    assert '"AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM and, under AUKIT_OPT_STREAMSET_BLOCK_CODECS, AUKIT_CODEC_MSADPCM)"' in src
-    assert '" and, under AUKIT_OPT_STREAMSET_FRAME_CODECS, AUKIT_CODEC_QOA)"' in src
+    # the four refusals of before and the clause under the option, last in all four that have it: the open makes them by the shared rule
+    # (tests/test_mixed_words_host.py holds every sentence, as produced, against the words of before)
+    from tests.test_mixed_words_host import sentence, uses_the_shared_rule
+    assert uses_the_shared_rule("streamset.hip", "sset_served")
+    assert sentence("sset", "000").endswith("(a stream set serves AUKIT_CODEC_PCM, AUKIT_CODEC_G711 and AUKIT_CODEC_ADPCM_WAV)")
+    assert sentence("sset", "100").endswith("AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM)")
+    assert sentence("sset", "010").endswith("AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_STREAMSET_BLOCK_CODECS, AUKIT_CODEC_MSADPCM)")
+    assert sentence("sset", "110").endswith("AUKIT_CODEC_ADPCM_WAV and, under AUKIT_OPT_STREAMSET_CODECS, AUKIT_CODEC_DFPWM and, under AUKIT_OPT_STREAMSET_BLOCK_CODECS, AUKIT_CODEC_MSADPCM)")
+    for flags in ("001", "101", "011", "111"):
+        assert sentence("sset", flags).endswith(" and, under AUKIT_OPT_STREAMSET_FRAME_CODECS, AUKIT_CODEC_QOA)"), flags
     # the engine: the carry's refusal is gone, the walk has its set mode, the pairs go back through a kernel of plain loads and stores
     eng = _read("aukit_amd", "csrc", "stream_mixed.hip")
     assert "a stream set takes no AUKIT_CODEC_QOA member" not in eng and "samples_dropped" in eng
