@@ -573,6 +573,9 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     };
     int src = table ? SRC_PCM_GENERIC : pick_pcm_source(in, d, false, mono != 0);
     bool done = false;
+    // a float string can hold NaN and ±Inf: the exact-position f32 kernels raise a flag when they stage one, and the reference-order kernel queued
+    // behind them with the flag as its launch condition redoes the call (ResampleParams::wild)
+    const int *redo_if = nullptr;
     if (table) {   // the numbers of a table are not bytes: only the generic staging reads them (reference order, fp64)
         size_t lds;
         if ((rc = plan_tiles(ctx, segs, cp_ratio, interp, nd, P, &lds))) return rc;
@@ -602,8 +605,7 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
     if (!done && dtype == AUKIT_F32 && !ctx->exact_math && C <= 2 && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {
         // every other interleaved format of one or two channels: unpack + resample + the stream.pcm epilogue in one launch (fast_fmt.hip, round 3)
         int frc = AUKIT_OK;
-        const int *unused = nullptr;
-        done = fast_fmt_try(ctx, d, interp, 48000, segs, P, in_bytes + out_elems * 4, &frc, &unused, (mono && C > 1) ? 2 : 1, P.lp_alpha);
+        done = fast_fmt_try(ctx, d, interp, 48000, segs, P, in_bytes + out_elems * 4, &frc, &redo_if, (mono && C > 1) ? 2 : 1, P.lp_alpha);
         if (done && frc) return frc;
     }
     if (!done && dtype == AUKIT_F32 && !ctx->exact_math && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {
@@ -658,9 +660,16 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
             R.lp_alpha = P.lp_alpha;
             R.safe_lo = R.src;
             R.safe_hi = R.src + ctx->tmp_buf.cap;
+            if (is_float) {
+                if ((rc = ctx->fmt_flag.ensure(64))) return rc;
+                R.wild = reinterpret_cast<int *>(ctx->fmt_flag.p);
+                R.wild_above = 3.402823466e+38f;
+                AUKIT_HIP_CHECK(hipMemsetAsync(R.wild, 0, 4, ctx->stream));
+            }
             int frc = AUKIT_OK;
             done = fast_try(ctx, SRC_AUDIO_F32, interp, d->sample_rate, 48000, rsegs, R, in_bytes + out_elems * 4, &frc, 1, P.lp_alpha);
             if (done && frc) return frc;
+            if (done && R.n_tiles) redo_if = R.wild;
         } else if (rc) return rc;
     }
     if (!done && ctx->exact_math == 1 && dtype == AUKIT_F32 && src == SRC_PCM_S16LE_MONO && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {
@@ -678,6 +687,18 @@ static int stream_pcm(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_d
         size_t lds;
         if ((rc = plan_tiles(ctx, segs, cp_ratio, interp, nd, P, &lds))) return rc;
         rc = launch_resample(ctx, src, interp, EPI_STREAM_PCM, dtype, P, lds, in_bytes + out_elems * dtype_size(dtype), nullptr);
+        if (rc) return rc;
+    } else if (redo_if) {   // the conditional redo: the call keeps the name of the kernel that (normally) did the work
+        const std::string nm = ctx->last_kernel;
+        const float ms = ctx->last_ms;
+        const uint64_t bytes = ctx->last_bytes;
+        size_t lds;
+        if ((rc = plan_tiles(ctx, segs, cp_ratio, interp, nd, P, &lds, true))) return rc;
+        P.only_if = redo_if;
+        rc = launch_resample(ctx, src, interp, EPI_STREAM_PCM, dtype, P, lds, 0, nullptr);
+        ctx->last_kernel = nm;
+        ctx->last_ms += ms;
+        ctx->last_bytes = bytes;
         if (rc) return rc;
     }
     return finish();
@@ -1069,9 +1090,31 @@ int aukit_resample(aukit_ctx *ctx, const aukit_audio *in, double new_rate, int i
     P.out = a->dev;
     P.safe_lo = reinterpret_cast<const unsigned char *>(in->dev);
     P.safe_hi = P.safe_lo + in->cap_bytes;
-    if (in->dtype == AUKIT_F32) {
+    if (in->dtype == AUKIT_F32 && !ctx->exact_math && (interp == AUKIT_INTERP_LINEAR || interp == AUKIT_INTERP_CUBIC)) {
+        // f32 rows can hold samples beyond ±1 and NaN, which the exact-position kernels get wrong where the reference's rounded position misses an
+        // integer (fast.hip's header): they raise a flag, and the reference-order kernel queued behind them redoes the call if it is set
+        if ((rc = ctx->fmt_flag.ensure(64))) return rc;
+        int *const flag = reinterpret_cast<int *>(ctx->fmt_flag.p);
+        AUKIT_HIP_CHECK(hipMemsetAsync(flag, 0, 4, ctx->stream));
+        P.wild = flag;
+        P.wild_above = 1.0f;
         int frc = AUKIT_OK;
-        if (fast_try(ctx, SRC_AUDIO_F32, interp, in->rate, new_rate, segs, P, (in_elems + out_elems) * 4, &frc)) return frc;
+        if (fast_try(ctx, SRC_AUDIO_F32, interp, in->rate, new_rate, segs, P, (in_elems + out_elems) * 4, &frc)) {
+            if (frc || !P.n_tiles) return frc;
+            const std::string nm = ctx->last_kernel;   // the call keeps the name of the kernel that (normally) did the work
+            const float ms = ctx->last_ms;
+            const uint64_t bytes = ctx->last_bytes;
+            size_t rlds;
+            if ((rc = plan_tiles(ctx, segs, ratio, interp, 1, P, &rlds, true))) return rc;
+            P.wild = nullptr;
+            P.only_if = flag;
+            rc = launch_resample(ctx, SRC_AUDIO_F32, interp, EPI_AUDIO, AUKIT_F32, P, rlds, 0, nullptr);
+            ctx->last_kernel = nm;
+            ctx->last_ms += ms;
+            ctx->last_bytes = bytes;
+            return rc;
+        }
+        P.wild = nullptr;
     }
     if (in->dtype == AUKIT_F64) {  // reference-order fp64 on wave tiles (exact_wave.hip)
         int erc = AUKIT_OK;

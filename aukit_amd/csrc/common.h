@@ -136,6 +136,13 @@ struct aukit_ctx {
     std::vector<unsigned char> plan_segs;   // the segment descriptors of that plan, byte for byte
     int plan_tile_out = 0;
     unsigned plan_n_tiles = 0, plan_tiles_per_seg = 0;
+    // the same for the plan of a conditional redo (Audio:resample on f32 rows: the reference-order kernel behind the fast one): buffers nobody else
+    // writes, so that neither plan evicts the other from one call to the next
+    aukit::DevBuf redo_seg_buf, redo_tile_buf;
+    bool redo_plan_valid = false;
+    std::vector<unsigned char> redo_plan_segs;
+    int redo_plan_tile_out = 0;
+    unsigned redo_plan_n_tiles = 0, redo_plan_tiles_per_seg = 0;
     // verified range of the reciprocal-based exact division per ratio (see exact_div_verified)
     std::map<double, uint64_t> div_ok;
     // aukit.stream.pcm: the chunk plan of the last call (segments before their row offsets, per-stream lengths, the chunk table), reused when

@@ -3,7 +3,13 @@
 // Same segment/tile machinery as resample.hip, different arithmetic:
 //   * position: x - 1 = o·a/b exactly (a/b = old_rate/new_rate reduced), so floor and fraction come from
 //     32-bit integer arithmetic (magic-number division by b) instead of an fp64 divide + floor;
-//     the reference's double x differs from the rational value by a few ulps at most (≤ 1e-10 in the output);
+//     the reference's double x differs from the rational value by a few ulps at most: ≤ 1e-10 in the output WHILE THE SAMPLES LIE IN
+//     [-1, 1].  Where the rounded x misses an integer the rational position hits (44100 → 48000: outputs 480, 800, 960, ...) the reference
+//     interpolates with fx = 1 - 6e-14 and CLAMPS (:667-668) what these kernels copy unclamped (rem == 0): a sample of 2.7 comes out as 1.0
+//     there and as 2.7 here.  Lua's clamp also lets a NaN through where v_med3 / fminf(fmaxf()) return a rail.  The integer formats cannot
+//     hold such samples; f32 rows can.  On f32 rows the kernels therefore raise ResampleParams::wild when they stage a sample
+//     that is not inside [-1, 1], and Audio:resample queues the reference-order kernel behind them with that flag as its launch condition
+//     (ResampleParams::only_if, as fast_fmt.hip does for float strings): tame rows pay one compare per staged sample and an empty launch;
 //   * taps are staged in LDS as f32 (half the LDS bytes of the exact path) with the reference's nil
 //     fall-backs (`p0 or p1`, `p2 or p1`, `p3 or p2 or p1`, aukit.lua:264) materialised as replicated
 //     edge samples, so the inner loop has no selects;
@@ -115,13 +121,16 @@ AUKIT_DEV int fast_stage(const ResampleParams &P, const FastParams &F, const Seg
         const int nvec = (head + n_stage + 3) >> 2;
         const float *row_lo = reinterpret_cast<const float *>(P.src) + P.src_off[sg.stream] + sg.src_base + sg.w_lo;
         const float *row_hi = reinterpret_cast<const float *>(P.src) + P.src_off[sg.stream] + sg.src_base + sg.w_hi;
+        bool wild = false;   // a staged sample that fails |s| <= P.wild_above, as a NaN always does (every d[e] is a sample of the row: the edges are replicated)
         for (int v = tid; v < nvec; v += 256) {
             const float *p = al + 4 * (size_t)v;
             float d[4];
             if (p >= row_lo && p + 3 <= row_hi) { float4 u = *reinterpret_cast<const float4 *>(p); d[0] = u.x; d[1] = u.y; d[2] = u.z; d[3] = u.w; }
             else for (int e = 0; e < 4; e++) { const float *q = p + e; d[e] = q < row_lo ? *row_lo : (q > row_hi ? *row_hi : *q); }
+            wild = wild || !(fabsf(d[0]) <= P.wild_above) || !(fabsf(d[1]) <= P.wild_above) || !(fabsf(d[2]) <= P.wild_above) || !(fabsf(d[3]) <= P.wild_above);
             *reinterpret_cast<float4 *>(sm + 4 * v) = make_float4(d[0], d[1], d[2], d[3]);
         }
+        if (P.wild && __builtin_amdgcn_ballot_w64(wild) != 0 && (tid & 63) == 0) atomicOr(P.wild, 1);   // the header says why
         return head;
     }
 }
@@ -230,8 +239,6 @@ bool fast_eligible(int src_kind, int interp, double old_rate, double new_rate, F
     F.dq64 = F.dr64 = 0;
     return true;
 }
-
-int plan_tiles_sized(aukit_ctx *ctx, const std::vector<Seg> &segs, int tile_out, ResampleParams &P);
 
 template <int SRC, bool X4>
 static int launch_fast_interp(aukit_ctx *ctx, int interp, const ResampleParams &P, const FastParams &F, size_t lds, unsigned grid) {

@@ -29,6 +29,9 @@ __global__ __launch_bounds__(256) void k_fast_wave(const ResampleParams P, const
     issue_loads<NV>(P, cur, lane, pre);
     for (;;) {
         write_lds<SRC, NV>(P, F, cur, lane, pre, sm);
+        if constexpr (SRC == SRC_AUDIO_F32) {
+            if (P.wild) flag_wild_f32<NV>(P, cur, lane, pre);   // kernel-uniform
+        }
         const unsigned tn = t + nwaves;
         const bool more = tn < P.n_tiles;
         WaveTile nxt = cur;

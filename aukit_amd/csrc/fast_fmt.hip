@@ -13,7 +13,9 @@
 // Samples beyond [-1, 1] (float strings can hold anything): where the reference's ROUNDED position x misses an integer the exact rational
 // position hits (or the other way round) the reference clamps what this kernel copies — invisible inside [-1, 1], arbitrarily large outside.
 // The kernel therefore raises a flag when it stages such a sample, and the reference-order kernel, queued right behind with the flag as
-// its launch condition (ResampleParams::only_if), redoes the call; without the flag it returns at once.
+// its launch condition (ResampleParams::only_if), redoes the call; without the flag it returns at once.  stream.pcm does not clamp its
+// interpolated sample (Q2): there only NaN and ±Inf tell the two positions apart (Inf * 0, a NaN tap only one of them reads), and only they
+// raise the flag.
 #include <algorithm>
 #include "fast_stream_body.h"   // interp_qr_raw, prev_lane / last_lane: the stream.pcm epilogue
 
@@ -26,7 +28,8 @@ struct FmtParams {
     int kind, big_endian;
     float scale_pos, scale_neg;   // signed: 1 / (2^(bits-1) - 1), 1 / 2^(bits-1)   (:1133)
     float g711_scale;
-    int *flag;                    // FMT_FLOAT: set when a staged sample is not inside [-1, 1]
+    int *flag;                    // FMT_FLOAT: set when a staged sample fails |s| <= wild_above (a NaN always does)
+    float wild_above;             // 1 for Audio:resample; FLT_MAX for stream.pcm, which does not clamp its interpolated sample (ResampleParams::wild)
     // fp64 arithmetic (AUKIT_OPT_EXACT_MATH = 1): s / (2^(bits-1) - 1) as a correctly rounded double quotient (div_rcp), s * 2^-(bits-1) exact
     double dpos, drcp, dneg, dg711, dinv_b;
 };
@@ -62,7 +65,7 @@ AUKIT_DEV AT fmt_sample(unsigned raw, const FmtParams &M, bool &wild) {
         if constexpr (B == 4) {
             if (M.kind == FMT_FLOAT) {
                 const float f = __uint_as_float(u);
-                wild = wild || !(fabsf(f) <= 1.0f);
+                wild = wild || !(fabsf(f) <= M.wild_above);
                 return (AT)f;
             }
         }
@@ -414,7 +417,8 @@ bool fast_fmt_try(aukit_ctx *ctx, const aukit_codec_desc *d, int interp, double 
     M.dinv_b = 1.0 / (double)F.b;
     const size_t lds = 4 * ((size_t)(nv * 64 * 4 + 4) + (size_t)(epi == 2 ? 1 : C) * F.cap * (f64 ? 2 : 1)) * 4;
     if (lds > 64 * 1024) return false;
-    if (M.kind == FMT_FLOAT && !epi) {
+    if (M.kind == FMT_FLOAT) {
+        M.wild_above = epi ? 3.402823466e+38f : 1.0f;
         if ((*rc = ctx->fmt_flag.ensure(64))) return true;
         M.flag = reinterpret_cast<int *>(ctx->fmt_flag.p);
     }

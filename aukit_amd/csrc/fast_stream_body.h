@@ -48,6 +48,9 @@ __global__ __launch_bounds__(256) void k_fast_wave_stream(const ResampleParams P
     issue_loads<NV>(P, cur, lane, pre);
     for (;;) {
         write_lds<SRC, NV>(P, F, cur, lane, pre, sm);
+        if constexpr (SRC == SRC_AUDIO_F32) {
+            if (P.wild) flag_wild_f32<NV>(P, cur, lane, pre);   // kernel-uniform: rows unpacked from a float string (NaN, ±Inf: ResampleParams::wild)
+        }
         const bool first = (P.tiles_per_seg ? t % P.tiles_per_seg : t - as_const(P.seg_tile0)[as_const(P.tile_seg)[t]]) == 0;  // first tile of its iterator call
         const unsigned tn = t + nwaves;
         const bool more = tn < P.n_tiles;

@@ -13,7 +13,6 @@
 namespace aukit {
 
 bool fast_eligible(int src_kind, int interp, double old_rate, double new_rate, FastParams &F);
-int plan_tiles_sized(aukit_ctx *ctx, const std::vector<Seg> &segs, int tile_out, ResampleParams &P);
 
 template <int INTERP, int NV>
 __global__ __launch_bounds__(256) void k_fast_wave_dfpwm(const ResampleParams P, const FastParams F, const int rows_out, const int mono_div) {

@@ -231,6 +231,38 @@ AUKIT_DEV void write_lds(const ResampleParams &P, const FastParams &F, const Wav
     }
 }
 
+// f32 rows can hold anything (a float WAV, Q4's unsigned strings, a high-passed square, uploaded rows): raises P.wild when a sample of the row
+// among the tile's vectors fails |s| <= P.wild_above — a NaN always does — see ResampleParams::wild and fast.hip's header.  Elements in front
+// of the row or behind it (the row's padding, a neighbouring row) do not count: four compares per vector, and two more that find the vectors
+// lying wholly inside the row; the others — one or two per row — are looked at element by element.
+template <int NV>
+AUKIT_DEV void flag_wild_f32(const ResampleParams &P, const WaveTile &w, int lane, const uint4 (&pre)[NV]) {
+    bool wild = false;
+    const float lim = P.wild_above;
+    const int first = w.w_lo - (w.k_lo - w.head), last = w.w_hi - (w.k_lo - w.head);   // the row's first and last sample as elements of the tile's vectors
+#pragma unroll
+    for (int i = 0; i < NV; i++) {
+        const int e0 = 4 * (lane + 64 * i);
+        if (lane + 64 * i >= w.nvec) continue;
+        const float x = __uint_as_float(pre[i].x), y = __uint_as_float(pre[i].y), z = __uint_as_float(pre[i].z), u = __uint_as_float(pre[i].w);
+        const bool wx = !(fabsf(x) <= lim), wy = !(fabsf(y) <= lim), wz = !(fabsf(z) <= lim), wu = !(fabsf(u) <= lim);
+        if (e0 >= first && e0 + 3 <= last) wild = wild || wx || wy || wz || wu;
+        else wild = wild || (wx && e0 >= first && e0 <= last) || (wy && e0 + 1 >= first && e0 + 1 <= last) || (wz && e0 + 2 >= first && e0 + 2 <= last) || (wu && e0 + 3 >= first && e0 + 3 <= last);
+    }
+    // A vector that is not wholly inside the allocation was not loaded (issue_loads left zeros; write_lds patches it sample by sample): the cubic's
+    // left tap in front of the buffer's first row, every call.  Such a vector holds no sample of a row as long as the allocation's ends are
+    // 16-byte aligned; should it ever hold one, nothing is known about that sample: redo.
+    if (w.al < P.safe_lo || w.al + 16 * (size_t)w.nvec > P.safe_hi) {   // wave-uniform
+#pragma unroll
+        for (int i = 0; i < NV; i++) {
+            const int v = lane + 64 * i, e0 = 4 * v;
+            const unsigned char *p = w.al + 16 * (size_t)v;
+            if (v < w.nvec && !(p >= P.safe_lo && p + 16 <= P.safe_hi)) wild = wild || (e0 <= last && e0 + 3 >= first);
+        }
+    }
+    if (__builtin_amdgcn_ballot_w64(wild) != 0 && lane == 0) atomicOr(P.wild, 1);
+}
+
 // The full-tile path of k_fast_wave: the wave is VALU-issue-bound (profiles/: 32 VALU instructions per 64 outputs, two of them
 // quarter-rate integer multiplies), so the position arrives as (q, rem) kept by additions, fx is one multiply (|error| <= 6e-8,
 // the tolerance path allows 1e-6 RMS), the clamp is one v_med3, and for sources whose samples lie in [-1, 1] the `x % 1 == 0`

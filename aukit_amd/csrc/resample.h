@@ -70,6 +70,10 @@ struct ResampleParams {
     int table;         // SRC_PCM_GENERIC: the "string" is a Lua TABLE of numbers (doubles, 8 bytes each: aukit.lua:2255-2290), read as they are
                        // (last members: the offsets of everything the wave kernels read stay what they were)
     const int *only_if;// k_resample: non-null → the launch does nothing unless *only_if != 0 (fast_fmt.hip's flag: a float string with samples beyond ±1)
+    int *wild;         // the exact-position kernels on f32 rows (k_fast_wave, k_fast_resample, k_fast_wave_stream): non-null → set to 1 when a staged sample
+    float wild_above;  // of a row fails |s| <= wild_above (a NaN always does).  The caller queues the reference-order kernel behind with this flag as its
+                       // only_if: Audio:resample with 1 (fast.hip's header says why), stream.pcm with FLT_MAX (it does not clamp the interpolated sample,
+                       // Q2, so only NaN and ±Inf tell the rounded position from the exact one: Inf * 0, and a NaN tap the other position does not read)
 };
 
 // launches the right instantiation; `name` receives a static string naming the kernel
@@ -78,9 +82,11 @@ int launch_resample(aukit_ctx *ctx, int src_kind, int interp, int epi, int out_d
 
 // host-side tiling helper: fills the tile tables for a list of segments, uploads segs/tiles to ctx scratch
 // and completes P.{segs,tile_seg,seg_tile0,tiles_per_seg,n_tiles,tile_out,cap,halo_*,ratio,rcp,exact_rcp}.
-int plan_tiles(aukit_ctx *ctx, const std::vector<Seg> &segs, double ratio, int interp, int stage_channels, ResampleParams &P, size_t *lds_bytes);
+// `redo`: the tables go to a second pair of buffers with a cache of its own (aukit_ctx::redo_plan) — the plan of a conditional redo queued behind
+// a kernel that reads the first pair, which stays cached for the next call
+int plan_tiles(aukit_ctx *ctx, const std::vector<Seg> &segs, double ratio, int interp, int stage_channels, ResampleParams &P, size_t *lds_bytes, bool redo = false);
 
-int plan_tiles_sized(aukit_ctx *ctx, const std::vector<Seg> &segs, int tile_out, ResampleParams &P);
+int plan_tiles_sized(aukit_ctx *ctx, const std::vector<Seg> &segs, int tile_out, ResampleParams &P, bool redo = false);
 
 // fast.hip / fast2.hip: f32 tolerance path (exact rational positions, f32 FMA taps)
 struct FastParams {

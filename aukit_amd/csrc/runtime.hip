@@ -257,7 +257,7 @@ void aukit_ctx_destroy(aukit_ctx *c) {
     { std::lock_guard<std::mutex> lk(g_live_mu); g_live.erase(c); }
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    c->seg_buf.release(); c->tile_buf.release(); c->misc_buf.release(); c->tmp_buf.release(); c->tmp_buf2.release(); c->tmp_buf3.release(); c->wt_buf.release(); c->enc_state_buf.release(); c->dfx_lut.release(); c->dfx_gather.release(); if (c->dfx_sub_out) { aukit_batch_free(c->dfx_sub_out); c->dfx_sub_out = nullptr; }
+    c->seg_buf.release(); c->tile_buf.release(); c->redo_seg_buf.release(); c->redo_tile_buf.release(); c->misc_buf.release(); c->tmp_buf.release(); c->tmp_buf2.release(); c->tmp_buf3.release(); c->wt_buf.release(); c->enc_state_buf.release(); c->dfx_lut.release(); c->dfx_gather.release(); if (c->dfx_sub_out) { aukit_batch_free(c->dfx_sub_out); c->dfx_sub_out = nullptr; }
     if (c->aux_stream) {
         (void)hipStreamSynchronize(c->aux_stream);
         for (int i = 0; i < 9; i++) if (c->aux_ev[i]) (void)hipEventDestroy(c->aux_ev[i]);
