@@ -15,7 +15,7 @@ if os.environ.get("AUKIT_LIB"):  # A/B of library builds on one box (tools/build
     LIB_PATH = os.path.abspath(os.environ["AUKIT_LIB"])
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["runtime.hip", "resample.hip", "resample_mixed.hip", "stream_mixed.hip", "stream_mixed_qoa.hip", "stream_mixed_flac.hip", "fast.hip", "fast2.hip", "fast_stream.hip", "fast_stream_f32.hip", "fast_stream_u8.hip", "fast_stream_dfpwm.hip", "fast_stream_s16x2.hip", "fast_coef.hip", "fast_s16x2.hip", "fast_fmt.hip", "floor_wave.hip", "exact_wave.hip", "wave_f64.hip", "wave_coef_f64.hip", "container.hip", "stream_handle.hip", "streamset.hip", "api_resample.hip", "stream_pcm_sinc.hip", "stream_pcm_tail.hip", "codecs.hip", "codecs2.hip", "msadpcm.hip", "msadpcm_mixed.hip", "qoa_stream.hip", "qoa.hip", "stream_tail.hip", "effects.hip", "flac.hip", "flac_first.hip", "flac_stream.hip", "flac_pq.hip", "flac_gather.hip", "flac_tail.hip", "rs_periodic.hip", "ops.hip", "dfpwm_par.hip", "dfpwm_spec.hip", "group.hip"]
-HEADERS = ["common.h", "chunks.h", "resample.h", "fast_wave_dev.h", "fast_stream_body.h", "resample_dev.h", "resample_mixed_body.h", "mixed_plan.h", "mixed_words.h", "flac_mixed.h", "stream_mixed_dev.h", "stream_mixed_tail.h", "stream_mixed_qoa.h", "stream_mixed_flac.h", "ima_geom.h", "ms_geom.h", "dfpwm_dev.h", "dfpwm_par_dev.h", "stream_tail.h", "flac_dev.h", "flac_stream_dev.h", "rs_onepole_dev.h", "stream_pcm_sinc.h", os.path.join(_ROOT, "include", "aukit_hip.h")]
+HEADERS = ["common.h", "chunks.h", "resample.h", "fast_wave_dev.h", "fast_stream_body.h", "resample_dev.h", "resample_mixed_body.h", "mixed_plan.h", "mixed_words.h", "flac_mixed.h", "stream_mixed_dev.h", "stream_mixed_tail.h", "stream_mixed_qoa.h", "stream_mixed_flac.h", "sset_flac.h", "ima_geom.h", "ms_geom.h", "dfpwm_dev.h", "dfpwm_par_dev.h", "stream_tail.h", "flac_dev.h", "flac_stream_dev.h", "rs_onepole_dev.h", "stream_pcm_sinc.h", os.path.join(_ROOT, "include", "aukit_hip.h")]
 
 OK, E_ARG, E_LUA, E_NOMEM, E_UNSUPPORTED, E_HIP = 0, -1, -2, -3, -4, -5
 F64, F32, I8 = 0, 1, 2
@@ -33,6 +33,7 @@ OPT_STREAMSET_BLOCK_CODECS = 8   # aukit_streamset_open's second mask (only CODE
 OPT_STREAMSET_FRAME_CODECS = 10   # aukit_streamset_open's third mask (only CODEC_QOA is known), read when a set is opened; options 7 and 8 refuse the bit by name
 OPT_MIXED_FRAME_CODECS = 11   # aukit_decode_resample_mixed's second mask (only CODEC_FLAC is known); option 5 refuses the bit by name
 OPT_STREAM_MIXED_CHAIN_CODECS = 12   # aukit_stream_decode_mixed's third mask (only CODEC_FLAC is known); options 5 to 11 do not open that call to FLAC
+OPT_STREAMSET_CHAIN_CODECS = 13   # aukit_streamset_open's fourth mask (only CODEC_FLAC is known), read when a set is opened; options 7, 8 and 10 refuse the bit by name
 OPT_STREAM_MIXED_FRAME_CODECS = 9   # aukit_stream_decode_mixed's second mask (only CODEC_QOA is known); options 5 to 8 do not open that call to QOA
 COUNTER_DFPWM_CHUNKS, COUNTER_DFPWM_CHUNKS_REDONE, COUNTER_FLAC_FUSED, COUNTER_TIER1_ERR_NANO, COUNTER_TIER1_OUTPUTS = 0, 1, 2, 3, 4
 COUNTER_DFPWM_RESPECULATED, COUNTER_DFPWM_HARD, COUNTER_RECURRENCE_F32, COUNTER_QOA_WAVE = 5, 6, 7, 8

@@ -570,7 +570,7 @@ def _sniff_many(files, stream=False, stream_dfpwm=False, stream_ima=False, adpcm
     return descs, ranges, infos
 
 
-def _sniff_set(readers, dfpwm=False, msadpcm=False, qoa=False):
+def _sniff_set(readers, dfpwm=False, msadpcm=False, qoa=False, flac=False):
     """aukit.stream.set's host half, up to the device: every reader is called once; its first piece, which holds the whole header (:2918), is
     sniffed by magic and walked by aukit_parse_container in its first-piece mode
     -> ([descriptor per reader], [the payload bytes behind the header per reader], [the container's length in seconds, NaN where the stream
@@ -586,10 +586,15 @@ def _sniff_set(readers, dfpwm=False, msadpcm=False, qoa=False):
     `qoa`: stream.set's request for QOA members — a reader whose first piece starts with the magic "qoaf" is taken too.  That piece holds the twelve
     header bytes (the first-piece rule, :2918; :3241 peeks at bytes 8..11): the descriptor carries the channel count (byte 8) and the rate (bytes 9..11)
     — a set's QOA member is described, unlike a mixed call's stream —, the whole piece is payload (there is no container around it) and the length is
-    file_samples / rate (:3336).  Without it such a reader is refused by index in the words of before."""
+    file_samples / rate (:3336).  Without it such a reader is refused by index in the words of before.
+    `flac`: stream.set's request for FLAC members — a reader whose first piece starts with the magic "fLaC" is taken too.  That piece holds the
+    metadata blocks (the first-piece rule, :2918): they are walked as k_flac_header walks them (a STREAMINFO by its 34 bytes, the last one wins; a
+    VORBIS_COMMENT by its content; every other block by its declared length), the descriptor carries STREAMINFO's channel count, depth and rate —
+    a set's FLAC member is described —, the whole piece is payload and the length is STREAMINFO's sample count / rate (:3190).  Without it such a
+    reader is refused by index in the words of before."""
     _expect(1, readers, "table")
     takes = "stream.set takes " + ("PCM, G.711 and DFPWM" if dfpwm else "PCM and G.711") + " payloads and " + ("IMA-ADPCM and MS-ADPCM" if msadpcm else "IMA-ADPCM") + \
-        " blocks" + (" and QOA files" if qoa else "") + " (the other codecs keep their own streams)"
+        " blocks" + (" and QOA files" if qoa else "") + (" and FLAC files" if flac else "") + " (the other codecs keep their own streams)"
     served = (N.CODEC_PCM, N.CODEC_G711, N.CODEC_ADPCM_WAV) + ((N.CODEC_DFPWM,) if dfpwm else ()) + ((N.CODEC_MSADPCM,) if msadpcm else ())
     descs, firsts, lengths = [], [], []
     for i, fn in enumerate(readers):
@@ -626,6 +631,15 @@ def _sniff_set(readers, dfpwm=False, msadpcm=False, qoa=False):
             continue
         if kind == "qoa":
             raise LuaError(f"reader {i}: qoa payload: {takes}")
+        if first[:4] == b"fLaC" and flac:
+            info = _flac_streaminfo(first)
+            if info is None:
+                raise LuaError(f"reader {i}: the first piece of a FLAC stream holds its metadata blocks, a STREAMINFO among them")
+            ch, depth, rate, nsamples = info
+            descs.append(B.make_desc(N.CODEC_FLAC, ch, rate, depth))
+            firsts.append(first)
+            lengths.append(nsamples / rate if rate else math.nan)
+            continue
         if kind not in _MAGIC_KIND:
             raise LuaError(f"reader {i}: not a WAV, AIFF or AU stream")
         try:
@@ -640,6 +654,42 @@ def _sniff_set(readers, dfpwm=False, msadpcm=False, qoa=False):
         firsts.append(p)
         lengths.append(float(c.length_seconds))
     return descs, firsts, lengths
+
+
+def _flac_streaminfo(data):
+    """the metadata walk of k_flac_header (flac.hip; aukit.lua:569-606) on a string that starts with "fLaC" -> (channels, depth, rate, samples) of
+    the last STREAMINFO, or None where the blocks do not end inside the string or none is a STREAMINFO"""
+    pos, last, info, nb = 4, False, None, len(data)
+    while not last:
+        if pos + 4 > nb:
+            return None
+        last, kind, length = bool(data[pos] & 0x80), data[pos] & 0x7F, int.from_bytes(data[pos + 1:pos + 4], "big")
+        pos += 4
+        if kind == 0:
+            if pos + 34 > nb:
+                return None
+            q = data[pos:pos + 34]
+            info = (((q[12] >> 1) & 7) + 1, (q[12] & 1) * 16 + (q[13] >> 4) + 1, (q[10] << 8 | q[11]) * 16 + (q[12] >> 4),
+                    int.from_bytes(q[14:18], "big") + (q[13] & 15) * 4294967296)
+            pos += 34
+        elif kind == 4:   # walked by its content (:592-600)
+            comments, i = 0, 0
+            while i <= comments:
+                for field in range(2 if i == 0 else 1):
+                    if pos + 4 > nb:
+                        return None
+                    v = int.from_bytes(data[pos:pos + 4], "little")
+                    pos += 4
+                    if field == 1:
+                        comments = v
+                        break
+                    if v > nb - pos:
+                        return None
+                    pos += v
+                i += 1
+        else:
+            pos += length
+    return info if pos <= nb else None
 
 
 class _RowView(B.AudioBatch):
@@ -994,7 +1044,7 @@ class _StreamNS:
         rows = out.download()
         return [self._chunk_iter(out, ck, None if math.isnan(lengths[i]) else lengths[i], d.codec == N.CODEC_G711, i, rows) for i, d in enumerate(descs)]
 
-    def set(self, readers, mono=None, dfpwm=None, msadpcm=None, qoa=None):
+    def set(self, readers, mono=None, dfpwm=None, msadpcm=None, qoa=None, flac=None):
         """aukit.stream.wav / aiff / au (fn, mono) for a LIST of reader functions — live sources, each a WAV / AIFF / AU stream of PCM, G.711 or
         IMA-ADPCM blocks with its own rate, format and channel count — served by ONE aukit_streamset: a list of (iterator, length) pairs in
         input order, each iterator handing out what the reader's own factory hands out.  Every reader's first piece holds the whole header
@@ -1014,16 +1064,22 @@ class _StreamNS:
         QOA readers (a first piece that starts with "qoaf" and holds the twelve header bytes) are taken with `qoa=True`, or the key "qoa" of the
         options table: the pair is what aukit.stream.qoa(fn, mono) returns (length file_samples / sampleRate), and for the one open the context is
         opted in to QOA members (AUKIT_OPT_STREAMSET_FRAME_CODECS, a third option) and put back as it was behind it, also where the open is
-        refused.  Without it such a reader is refused by index, as before."""
+        refused.  Without it such a reader is refused by index, as before.
+        FLAC readers (a first piece that starts with "fLaC" and holds the metadata blocks) are taken with `flac=True`, or the key "flac" of the
+        options table: the pair is what aukit.stream.flac(fn, mono) returns (`mono` is not read for them, so a set with `mono` takes one-channel
+        FLAC readers only; length STREAMINFO's sample count / sampleRate), and for the one open the context is opted in to FLAC members
+        (AUKIT_OPT_STREAMSET_CHAIN_CODECS, a fourth option) and put back as it was behind it, also where the open is refused.  Without it such a
+        reader is refused by index, as before."""
         if isinstance(mono, dict):
-            if set(mono) - {"mono", "dfpwm", "msadpcm", "qoa"}:
-                raise LuaError("bad argument #2 (unknown option " + sorted(set(mono) - {"mono", "dfpwm", "msadpcm", "qoa"})[0] + ")")
-            mono, dfpwm, msadpcm, qoa = mono.get("mono"), mono.get("dfpwm", dfpwm), mono.get("msadpcm", msadpcm), mono.get("qoa", qoa)
+            if set(mono) - {"mono", "dfpwm", "msadpcm", "qoa", "flac"}:
+                raise LuaError("bad argument #2 (unknown option " + sorted(set(mono) - {"mono", "dfpwm", "msadpcm", "qoa", "flac"})[0] + ")")
+            mono, dfpwm, msadpcm, qoa, flac = mono.get("mono"), mono.get("dfpwm", dfpwm), mono.get("msadpcm", msadpcm), mono.get("qoa", qoa), mono.get("flac", flac)
         _expect(2, mono, "boolean", "nil")
         _expect(3, dfpwm, "boolean", "nil")
         _expect(4, msadpcm, "boolean", "nil")
         _expect(5, qoa, "boolean", "nil")
-        descs, firsts, lengths = _sniff_set(readers, dfpwm=bool(dfpwm), msadpcm=bool(msadpcm), qoa=bool(qoa))
+        _expect(6, flac, "boolean", "nil")
+        descs, firsts, lengths = _sniff_set(readers, dfpwm=bool(dfpwm), msadpcm=bool(msadpcm), qoa=bool(qoa), flac=bool(flac))
         ctx = context()
         was, was_block, was_frame = ctx.option(N.OPT_STREAMSET_CODECS), ctx.option(N.OPT_STREAMSET_BLOCK_CODECS), ctx.option(N.OPT_STREAMSET_FRAME_CODECS)
         try:
@@ -1033,6 +1089,9 @@ class _StreamNS:
                 _wrap(ctx.set_option, N.OPT_STREAMSET_BLOCK_CODECS, was_block | 1 << N.CODEC_MSADPCM)
             if qoa:
                 _wrap(ctx.set_option, N.OPT_STREAMSET_FRAME_CODECS, was_frame | 1 << N.CODEC_QOA)
+            if flac:
+                was_chain = ctx.option(N.OPT_STREAMSET_CHAIN_CODECS)
+                _wrap(ctx.set_option, N.OPT_STREAMSET_CHAIN_CODECS, was_chain | 1 << N.CODEC_FLAC)
             st = _wrap(B.StreamSet, ctx, descs, _interp(defaultInterpolation, 0), bool(mono), N.F64)
         finally:
             if dfpwm:
@@ -1041,6 +1100,8 @@ class _StreamNS:
                 ctx.set_option(N.OPT_STREAMSET_BLOCK_CODECS, was_block)
             if qoa:
                 ctx.set_option(N.OPT_STREAMSET_FRAME_CODECS, was_frame)
+            if flac:
+                ctx.set_option(N.OPT_STREAMSET_CHAIN_CODECS, was_chain)
         readers = [r[0] if isinstance(r, (list, tuple)) else r for r in readers]
         n = len(readers)
         done = [False] * n

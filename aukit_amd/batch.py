@@ -730,7 +730,15 @@ class StreamSet:
     header's channel count and rate: make_desc(N.CODEC_QOA, channels, sample_rate).  The member is fed the file from its first byte; the last
     two samples of a call and the position are carried across compactions, so the rest starts at the next call.  A member whose header is no
     QOA header or disagrees with the descriptor, one with a frame of more than 8192 samples and one finished inside a frame end alone.  A pump
-    that decodes such members waits two more times (the frame walk's read-backs).  A chunk of theirs may exceed `cap` (61440 at 8 kHz)."""
+    that decodes such members waits two more times (the frame walk's read-backs).  A chunk of theirs may exceed `cap` (61440 at 8 kHz).
+    CODEC_FLAC members (aukit.stream.flac) join under a fourth option, ctx.set_option(N.OPT_STREAMSET_CHAIN_CODECS, 1 << N.CODEC_FLAC) — option 13,
+    read by the open alone; OPT_STREAM_MIXED_CHAIN_CODECS is not needed.  A member's descriptor carries STREAMINFO's figures:
+    make_desc(N.CODEC_FLAC, channels, sample_rate, bit_depth) with a depth of 8, 16 or 24; `mono` is not read for FLAC, so a mono set takes
+    one-channel members only.  The member is fed the file from its first byte: `feed` walks the metadata on the host, nothing of it reaches the
+    device but a canonical 42-byte header, and the two `last` samples and the position are carried across compactions, so the rest starts at the
+    next call.  A member whose magic is wrong, that has no STREAMINFO or whose STREAMINFO disagrees with the descriptor, one finished inside its
+    metadata and one with a value beyond int32 end alone.  A chunk of theirs may exceed `cap` (a call stops at the first frame that brings it to
+    `rate` outputs)."""
 
     def __init__(self, ctx, descs, interp, mono=False, dtype=None, cap=48000):
         self.ctx = ctx

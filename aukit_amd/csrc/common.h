@@ -56,12 +56,14 @@ struct aukit_ctx {
     // int32 rows of all groups in fmix_rows — of their own, because the next group's decode, the other pre-passes and lazy_drop write or swap the
     // shared scratch; both stay at their high-water size.  fmix_ev: the look-ahead stream behind the compaction
     aukit::DevBuf fmix_src, fmix_rows;
+    aukit::DevBuf fmix_back;   // a stream set's FLAC members: where k_smix_flac_last finds the boundary pairs (offsets), and the pairs (stream_mixed.hip)
     hipEvent_t fmix_ev = nullptr;
     unsigned stream_mixed_codecs = 0;  // AUKIT_OPT_STREAM_MIXED_CODECS: the same for aukit_stream_decode_mixed, which reads this mask and no other
     unsigned stream_mixed_frame_codecs = 0;   // AUKIT_OPT_STREAM_MIXED_FRAME_CODECS: that call's second mask (1 << AUKIT_CODEC_QOA), read by the public call alone
     unsigned stream_mixed_chain_codecs = 0;   // AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS: that call's third mask (1 << AUKIT_CODEC_FLAC), read by the public call alone
     unsigned streamset_codecs = 0;     // AUKIT_OPT_STREAMSET_CODECS: bit 1 << codec lets aukit_streamset_open, which reads this mask and no other, take that codec
     unsigned streamset_fcodecs = 0;   // AUKIT_OPT_STREAMSET_FRAME_CODECS: the same call's third mask (1 << AUKIT_CODEC_QOA), read while a set opens
+    unsigned streamset_ccodecs = 0;   // AUKIT_OPT_STREAMSET_CHAIN_CODECS: the same call's fourth mask (1 << AUKIT_CODEC_FLAC), read while a set opens
     unsigned streamset_block_codecs = 0;   // AUKIT_OPT_STREAMSET_BLOCK_CODECS: the same call's second mask (1 << AUKIT_CODEC_MSADPCM), read while a set opens
     bool fast_store_x4 = true;  // AUKIT_OPT_STORE_X4: LDS-transposed 16-byte stores in the fast kernels
     std::string last_kernel;

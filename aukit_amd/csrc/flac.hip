@@ -714,13 +714,14 @@ static int flac_decode_rows(aukit_ctx *ctx, const aukit_batch *in, FlacDecoded &
 }
 
 // ================================================================= the FLAC members of aukit_decode_resample_mixed (flac_mixed.h)
-int flac_mixed_headers(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F, const char *single) {
+int flac_mixed_headers(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F, const char *single,
+                       const std::vector<FlacSetIn> *set) {
     int rc;
     const size_t m = list.size();
     F.assign(m, FlacMixedStream());
     if (!m) return AUKIT_OK;
     std::vector<u64> pairs(2 * m);
-    for (size_t k = 0; k < m; k++) { pairs[2 * k] = in->off[list[k]]; pairs[2 * k + 1] = in->off[list[k] + 1]; }
+    for (size_t k = 0; k < m; k++) { pairs[2 * k] = in->off[list[k]]; pairs[2 * k + 1] = set ? in->off[list[k]] + (*set)[k].nbytes : in->off[list[k] + 1]; }
     const size_t info_at = (size_t)round_up(2 * m * 8, 256);
     if ((rc = ctx->misc_buf.ensure(info_at + m * sizeof(FlacStreamInfo)))) return rc;
     char *B = reinterpret_cast<char *>(ctx->misc_buf.p);
@@ -767,7 +768,9 @@ static int fmix_rows_grow(aukit_ctx *ctx, size_t need, size_t keep) {
 static void frames_from_brief(FlacDecoded &D);
 // `frames` (flac_smix_decode, the stream call): the decoders keep the frame lists, a chain that ends in an error is the stream's own end, and the
 // refusals name aukit_stream_decode; null: aukit_decode_resample_mixed's decode, as it always was
-static int flac_mixed_decode_groups(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F, std::vector<FlacSMixFrames> *frames) {
+// `set` (with `frames`): a stream set's batch — byte counts and carried pairs per entry of `list` (FlacSetIn), a wide stream ends alone
+static int flac_mixed_decode_groups(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F, std::vector<FlacSMixFrames> *frames,
+                                    const std::vector<FlacSetIn> *set = nullptr) {
     int rc;
     const size_t m = list.size();
     if (frames) frames->assign(m, FlacSMixFrames());
@@ -789,7 +792,7 @@ static int flac_mixed_decode_groups(aukit_ctx *ctx, const aukit_batch *in, const
         P.at = (size_t)round_up(end, 256);
         P.off.push_back(0);
         for (size_t k : groups[g]) {
-            const uint64_t b = in->off[list[k]], nb = in->off[list[k] + 1] - b;
+            const uint64_t b = in->off[list[k]], nb = set ? (*set)[k].nbytes : in->off[list[k] + 1] - b;
             for (uint64_t at = 0; at < nb; at += 0x20000000ull) segments.push_back({b + at, P.at + P.off.back() + at, std::min<uint64_t>(nb - at, 0x20000000ull)});
             P.off.push_back(P.off.back() + nb);
         }
@@ -833,6 +836,36 @@ static int flac_mixed_decode_groups(aukit_ctx *ctx, const aukit_batch *in, const
     std::string bad_msg;
     auto offender = [&](unsigned s, int code, const std::string &msg) { if (s < bad) { bad = s; bad_code = code; bad_msg = msg; } };
     size_t rows_end = 0;
+    // the rows of a decode join ctx->fmix_rows behind those of the decodes before; G: the entries of `list` the decode's streams are, in its order
+    auto take = [&](FlacDecoded &D, const std::vector<size_t> &G) -> int {
+        if (frames) {   // stream.flac swallows the error: the frames in front of it are the stream (stream_flac)
+            frames_from_brief(D);
+            for (size_t i = 0; i < G.size(); i++) {
+                FlacSMixFrames &fs = (*frames)[G[i]];
+                fs.nsamples = D.info[i].nsamples;
+                fs.status = D.status[i];
+                for (const auto &fr : D.frames[i]) { fs.at.push_back(fr.first); fs.bs.push_back((uint32_t)fr.second); }
+                if (i < D.frame_end.size() && D.frame_end[i].size() == fs.bs.size()) fs.end = D.frame_end[i];
+                else fs.end.assign(fs.bs.size(), 0u);
+            }
+        }
+        const size_t at = (size_t)round_up(rows_end, 256), bytes = (size_t)D.tot_elems * 4;
+        if ((rc = fmix_rows_grow(ctx, at + bytes + 256, rows_end))) return rc;
+        int *const rows = reinterpret_cast<int *>(reinterpret_cast<char *>(ctx->fmix_rows.p) + at);
+        if (D.in_scratch) {
+            if (D.nfr) {
+                if ((rc = ctx_begin_kernel(ctx))) return rc;
+                if ((rc = flac_gather_launch(ctx, D.d_frames, D.nfr, D.channels, D.d_rowoff, reinterpret_cast<const int *>(ctx->tmp_buf3.p), rows, D.scratch16))) return rc;
+                if ((rc = ctx_end_kernel(ctx, "k_flac_gather", 2 * D.tot_elems * 4))) return rc;
+            }
+        } else if (bytes) AUKIT_HIP_CHECK(hipMemcpyAsync(rows, ctx->tmp_buf.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));   // the first design's rows
+        for (size_t i = 0; i < G.size(); i++) {
+            F[G[i]].frames = D.row_len[i * (size_t)D.channels];
+            F[G[i]].row = at + 4 * D.row_off[i * (size_t)D.channels];
+        }
+        rows_end = at + bytes + 64;
+        return AUKIT_OK;
+    };
     for (size_t g = 0; g < groups.size(); g++) {
         const Place &P = place[g];
         const std::vector<size_t> &G = groups[g];
@@ -841,6 +874,19 @@ static int flac_mixed_decode_groups(aukit_ctx *ctx, const aukit_batch *in, const
         FlacDecoded D;
         D.want16 = false;
         rc = flac_decode_rows(ctx, &tb, D, frames != nullptr, true);
+        if (rc == FLAC_ROWS_WIDE && set) {   // a stream set's batch: the offender ends alone — every member of the group on its own, each with its own verdict
+            for (size_t who = 0; who < G.size(); who++) {
+                aukit_batch one;
+                if ((rc = member_batch(P, who, one))) return rc;
+                FlacDecoded D1;
+                D1.want16 = false;
+                const int r1 = flac_decode_rows(ctx, &one, D1, true, true);
+                if (r1 == FLAC_ROWS_WIDE) { (*frames)[G[who]].wide = true; F[G[who]].frames = 0; F[G[who]].row = 0; continue; }
+                if (r1) return r1;
+                if ((rc = take(D1, std::vector<size_t>{G[who]}))) return rc;
+            }
+            continue;
+        }
         if (rc == FLAC_ROWS_WIDE) {   // a value beyond int32 somewhere in the group: which stream's, one at a time (the last one if no other)
             size_t who = 0;
             for (; who + 1 < G.size(); who++) {
@@ -858,33 +904,24 @@ static int flac_mixed_decode_groups(aukit_ctx *ctx, const aukit_batch *in, const
         if (rc) return rc;
         size_t raised = 0;
         while (raised < G.size() && !D.status[raised]) raised++;
-        if (frames) {   // stream.flac swallows the error: the frames in front of it are the stream (stream_flac)
-            frames_from_brief(D);
-            for (size_t i = 0; i < G.size(); i++) {
-                FlacSMixFrames &fs = (*frames)[G[i]];
-                fs.nsamples = D.info[i].nsamples;
-                fs.status = D.status[i];
-                for (const auto &fr : D.frames[i]) { fs.at.push_back(fr.first); fs.bs.push_back((uint32_t)fr.second); }
-            }
-        } else if (raised < G.size()) {   // decodeFLAC raises (the group's members are in library order: its first is its lowest)
+        if (!frames && raised < G.size()) {   // decodeFLAC raises (the group's members are in library order: its first is its lowest)
             offender(list[G[raised]], AUKIT_E_LUA, flac_err_msg(D.status[raised]));
             continue;
         }
-        const size_t at = (size_t)round_up(rows_end, 256), bytes = (size_t)D.tot_elems * 4;
-        if ((rc = fmix_rows_grow(ctx, at + bytes + 256, rows_end))) return rc;
-        int *const rows = reinterpret_cast<int *>(reinterpret_cast<char *>(ctx->fmix_rows.p) + at);
-        if (D.in_scratch) {
-            if (D.nfr) {
-                if ((rc = ctx_begin_kernel(ctx))) return rc;
-                if ((rc = flac_gather_launch(ctx, D.d_frames, D.nfr, D.channels, D.d_rowoff, reinterpret_cast<const int *>(ctx->tmp_buf3.p), rows, D.scratch16))) return rc;
-                if ((rc = ctx_end_kernel(ctx, "k_flac_gather", 2 * D.tot_elems * 4))) return rc;
+        if ((rc = take(D, G))) return rc;
+    }
+    if (set && frames) {   // the carried pairs, behind the last group's rows: two int32 per stream that carries one, uploaded in front of the tail's launch
+        std::vector<int32_t> pairs;
+        const size_t at = (size_t)round_up(rows_end, 256);
+        for (size_t k = 0; k < m; k++)
+            if ((*set)[k].last_on) {
+                (*frames)[k].last_at = at / 4 + pairs.size();
+                pairs.push_back((*set)[k].last[0]); pairs.push_back((*set)[k].last[1]);
             }
-        } else if (bytes) AUKIT_HIP_CHECK(hipMemcpyAsync(rows, ctx->tmp_buf.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));   // the first design's rows
-        for (size_t i = 0; i < G.size(); i++) {
-            F[G[i]].frames = D.row_len[i * (size_t)D.channels];
-            F[G[i]].row = at + 4 * D.row_off[i * (size_t)D.channels];
+        if (!pairs.empty()) {
+            if ((rc = fmix_rows_grow(ctx, at + pairs.size() * 4 + 256, rows_end))) return rc;
+            if ((rc = h2d_table(ctx, reinterpret_cast<char *>(ctx->fmix_rows.p) + at, pairs.data(), pairs.size() * 4))) return rc;
         }
-        rows_end = at + bytes + 64;
     }
     if (bad != ~0u) return fail(bad_code, "%s (stream %u)", bad_msg.c_str(), bad);
     return AUKIT_OK;
@@ -892,8 +929,9 @@ static int flac_mixed_decode_groups(aukit_ctx *ctx, const aukit_batch *in, const
 int flac_mixed_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F) {
     return flac_mixed_decode_groups(ctx, in, list, F, nullptr);
 }
-int flac_smix_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F, std::vector<FlacSMixFrames> &frames) {
-    return flac_mixed_decode_groups(ctx, in, list, F, &frames);
+int flac_smix_decode(aukit_ctx *ctx, const aukit_batch *in, const std::vector<uint32_t> &list, std::vector<FlacMixedStream> &F, std::vector<FlacSMixFrames> &frames,
+                     const std::vector<FlacSetIn> *set) {
+    return flac_mixed_decode_groups(ctx, in, list, F, &frames, set);
 }
 
 static void frames_from_brief(FlacDecoded &D) {

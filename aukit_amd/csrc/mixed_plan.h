@@ -61,6 +61,14 @@ struct SMixCarry {
     uint64_t samples_dropped;
     int qoa_back, qoa_last_on;
     signed char qoa_last[2 * AUKIT_MAX_PLANAR_CHANNELS];
+    // an AUKIT_CODEC_FLAC stream (zeros otherwise; the public call takes no carry): the rest is a canonical 42-byte header ("fLaC", one last-block
+    // STREAMINFO) and whole frames from some iterator call's start on.  flac_last_on — the rest's first (frame, channel) job reads flac_last[0] and
+    // flac_last[1] as its table indices -1 and 0 (`last`, :3157, :3183: two integers of the decoder's int32 rows, shared across channels and
+    // frames, so carrying them is exact); flac_pos — `pos` (:3188) as the dropped calls summed it: the plan starts from exactly that double, as
+    // aukit_ctx::sb_pos does for the handle; flac_back — the pair behind every call of this decode, the byte behind it and its `pos` come back
+    int flac_back, flac_last_on;
+    int32_t flac_last[2];
+    double flac_pos;
 };
 // where the pre-pass left the states of the streams that asked (df_back): entry first[s] + k of the device table `dev` (six ints each; scratch of the
 // call, valid until the context's next call) is stream s's decoder in front of call k of this decode — after the slices of calls 0 .. k - 1,
@@ -79,13 +87,23 @@ struct SMixDfBack {
     std::vector<uint64_t> qoa_first, qoa_call0;   // per stream of the batch (~0: none)
     std::vector<uint32_t> qoa_calls;
     std::vector<uint32_t> qoa_end, qoa_samples;
+    // the FLAC streams that asked (flac_back): pair flac_first[s] + k of the device table flac_dev (two int32 each, ctx->fmix_back: valid until the
+    // context's next call that decodes a set's FLAC members) holds `last` behind call k of this decode, k = 0 .. flac_calls[s] - 1 (k_smix_flac_last,
+    // stream_mixed_flac.hip).  flac_end / flac_pos, from flac_call0[s] on: per call the byte behind its last frame, counted from the rest's first
+    // (0: the decoder reports none, the rest is not cut there), and the `pos` it returns
+    const int32_t *flac_dev = nullptr;
+    size_t flac_pairs = 0;
+    std::vector<uint64_t> flac_first, flac_call0;   // per stream of the batch (~0: none)
+    std::vector<uint32_t> flac_calls;
+    std::vector<uint64_t> flac_end;
+    std::vector<double> flac_pos;
 };
 int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit_codec_desc *descs, uint32_t n_descs, int interp, int mono, int dtype, aukit_audio **out,
                               aukit_chunks **chunks, const SMixCarry *carry /* n_descs, or null */, SMixDfBack *back = nullptr /* where a carry sets df_back */,
                               unsigned block_codecs = 0 /* 1 << AUKIT_CODEC_MSADPCM: the caller takes such streams, whatever the context's masks say; with a carry (a stream
-                              set, which keeps ONE mask of what it was opened with) also 1 << AUKIT_CODEC_QOA, read as that bit of the next mask */,
+                              set, which keeps ONE mask of what it was opened with) also 1 << AUKIT_CODEC_QOA, read as that bit of the next mask, and 1 << AUKIT_CODEC_FLAC, read as that bit of the last */,
                               unsigned frame_codecs = 0 /* 1 << AUKIT_CODEC_QOA: the public call's AUKIT_OPT_STREAM_MIXED_FRAME_CODECS */,
-                              unsigned chain_codecs = 0 /* 1 << AUKIT_CODEC_FLAC: the public call's AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS; a stream set hands in 0 */);
+                              unsigned chain_codecs = 0 /* 1 << AUKIT_CODEC_FLAC: the public call's AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS; with a carry it is not read: a stream set's FLAC bit (AUKIT_OPT_STREAMSET_CHAIN_CODECS) travels in its one mask, as QOA's does */);
 // what the stream's own aukit_stream_decode call refuses of a descriptor and a byte count, and the uneven last chunk (stream_mixed.hip)
 int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono);
 

@@ -42,7 +42,7 @@ static inline bool served(const ServedRule &r, int codec) {
 }
 
 // aukit_stream_decode_mixed: MS-ADPCM under option 6, QOA under option 9, FLAC under option 12 (the masks are the caller's: a stream set hands in
-// the one it was opened with, and never FLAC's)
+// the one it was opened with; FLAC's bit only where the set was opened under option 13)
 static inline ServedRule smix_served(bool with_ms, bool with_qoa, bool with_flac) {
     return {"stream %u: codec %d has its own stream (per-stream descriptors serve ",
             {AUKIT_SERVED(AUKIT_CODEC_PCM), AUKIT_SERVED(AUKIT_CODEC_G711), AUKIT_SERVED(AUKIT_CODEC_DFPWM), AUKIT_SERVED(AUKIT_CODEC_ADPCM_WAV)},
@@ -51,13 +51,14 @@ static inline ServedRule smix_served(bool with_ms, bool with_qoa, bool with_flac
              {with_flac, "AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS", AUKIT_SERVED(AUKIT_CODEC_FLAC)}}};
 }
 
-// aukit_streamset_open: DFPWM under option 7, MS-ADPCM under option 8, QOA under option 10
-static inline ServedRule sset_served(bool with_df, bool with_ms, bool with_qoa) {
+// aukit_streamset_open: DFPWM under option 7, MS-ADPCM under option 8, QOA under option 10, FLAC under option 13
+static inline ServedRule sset_served(bool with_df, bool with_ms, bool with_qoa, bool with_flac = false) {
     return {"stream %u: codec %d keeps aukit_stream_open (a stream set serves ",
             {AUKIT_SERVED(AUKIT_CODEC_PCM), AUKIT_SERVED(AUKIT_CODEC_G711), AUKIT_SERVED(AUKIT_CODEC_ADPCM_WAV)},
             {{with_df, "AUKIT_OPT_STREAMSET_CODECS", AUKIT_SERVED(AUKIT_CODEC_DFPWM)},
              {with_ms, "AUKIT_OPT_STREAMSET_BLOCK_CODECS", AUKIT_SERVED(AUKIT_CODEC_MSADPCM)},
-             {with_qoa, "AUKIT_OPT_STREAMSET_FRAME_CODECS", AUKIT_SERVED(AUKIT_CODEC_QOA)}}};
+             {with_qoa, "AUKIT_OPT_STREAMSET_FRAME_CODECS", AUKIT_SERVED(AUKIT_CODEC_QOA)},
+             {with_flac, "AUKIT_OPT_STREAMSET_CHAIN_CODECS", AUKIT_SERVED(AUKIT_CODEC_FLAC)}}};
 }
 
 // aukit_decode_resample_mixed: MS-ADPCM under option 5, FLAC under option 11

@@ -267,7 +267,7 @@ void aukit_ctx_destroy(aukit_ctx *c) {
     if (c->host_stage) (void)hipHostFree(c->host_stage);
     if (c->pre_stream) { (void)hipStreamSynchronize(c->pre_stream); (void)hipStreamDestroy(c->pre_stream); c->pre_stream = nullptr; }
     for (hipEvent_t *e : {&c->pre_ev, &c->entry_ev[0], &c->entry_ev[1], &c->scratch_ev}) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
-    c->fmix_src.release(); c->fmix_rows.release(); if (c->fmix_ev) { (void)hipEventDestroy(c->fmix_ev); c->fmix_ev = nullptr; }
+    c->fmix_src.release(); c->fmix_rows.release(); c->fmix_back.release(); if (c->fmix_ev) { (void)hipEventDestroy(c->fmix_ev); c->fmix_ev = nullptr; }
     c->flac_set[0].release(); c->flac_set[1].release(); c->scan_buf.release(); for (int i = 0; i < 2; i++) for (int j = 0; j < 3; j++) c->qoa_set[i][j].release();
     if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); (void)hipEventDestroy(c->side_ev[0]); (void)hipEventDestroy(c->side_ev[1]); }
     if (c->tab_ring) (void)hipHostFree(c->tab_ring);
@@ -308,7 +308,7 @@ int aukit_ctx_set_sinc_window(aukit_ctx *c, int w) {
     c->sinc_w = w;
     return AUKIT_OK;
 }
-// AUKIT_OPT_MIXED_CODECS / AUKIT_OPT_MIXED_FRAME_CODECS / AUKIT_OPT_STREAM_MIXED_CODECS / AUKIT_OPT_STREAMSET_CODECS / AUKIT_OPT_STREAMSET_BLOCK_CODECS / AUKIT_OPT_STREAM_MIXED_FRAME_CODECS / AUKIT_OPT_STREAMSET_FRAME_CODECS / AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS: a mask of 1 << codec; refused as a whole, the mask as it was,
+// AUKIT_OPT_MIXED_CODECS / AUKIT_OPT_MIXED_FRAME_CODECS / AUKIT_OPT_STREAM_MIXED_CODECS / AUKIT_OPT_STREAMSET_CODECS / AUKIT_OPT_STREAMSET_BLOCK_CODECS / AUKIT_OPT_STREAM_MIXED_FRAME_CODECS / AUKIT_OPT_STREAMSET_FRAME_CODECS / AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS / AUKIT_OPT_STREAMSET_CHAIN_CODECS: a mask of 1 << codec; refused as a whole, the mask as it was,
 // where a bit names a codec the option's calls (`who`) do not take on request.  `only`: the one codec the option knows
 static int set_codec_mask(unsigned *mask, int value, const char *opt, const char *who, int only = AUKIT_CODEC_MSADPCM) {
     const unsigned known = 1u << only, extra = (unsigned)value & ~known;
@@ -341,6 +341,8 @@ int aukit_ctx_set_option(aukit_ctx *c, int option, int value) {
         return set_codec_mask(&c->mixed_frame_codecs, value, "AUKIT_OPT_MIXED_FRAME_CODECS", "aukit_decode_resample_mixed takes", AUKIT_CODEC_FLAC);
     else if (option == AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS)
         return set_codec_mask(&c->stream_mixed_chain_codecs, value, "AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS", "aukit_stream_decode_mixed takes", AUKIT_CODEC_FLAC);
+    else if (option == AUKIT_OPT_STREAMSET_CHAIN_CODECS)
+        return set_codec_mask(&c->streamset_ccodecs, value, "AUKIT_OPT_STREAMSET_CHAIN_CODECS", "aukit_streamset_open takes", AUKIT_CODEC_FLAC);
     else return fail(AUKIT_E_ARG, "unknown option %d", option);
     return AUKIT_OK;
 }

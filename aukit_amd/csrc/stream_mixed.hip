@@ -14,7 +14,7 @@
 //   7  smix_tiles, 8 smix_launch — k_stream_mixed; 9 smix_qoa_tail, 10 smix_flac_tail — the call's last kernels.
 // A stream may be the REST of a longer one — a stream set's member (streamset.hip; stream_decode_mixed_carry, never the public call): DFPWM under
 // AUKIT_OPT_STREAMSET_CODECS with the decoder's state carried in and the states at every call boundary handed back, MS-ADPCM under
-// AUKIT_OPT_STREAMSET_BLOCK_CODECS, QOA under AUKIT_OPT_STREAMSET_FRAME_CODECS; each planner says what its carry holds.  A batch without a carry
+// AUKIT_OPT_STREAMSET_BLOCK_CODECS, QOA under AUKIT_OPT_STREAMSET_FRAME_CODECS, FLAC under AUKIT_OPT_STREAMSET_CHAIN_CODECS; each planner says what its carry holds.  A batch without a carry
 // launches what it always did.  What the call shares with aukit_decode_resample_mixed is in mixed_plan.h, stream.adpcm's arithmetic in ima_geom.h;
 // stream.msadpcm's is in ms_geom.h.
 #include <algorithm>
@@ -43,6 +43,7 @@ int smix_qoa_tail_launch(aukit_ctx *ctx, const std::vector<SMixQoaClass> &classe
 // stream_mixed_flac.hip's launch (flac.hip's header pass and group decode: flac_mixed.h)
 int smix_flac_tail_launch(aukit_ctx *ctx, const std::vector<SMixFlacClass> &classes, const std::vector<SMixFlacJob> &jobs, const std::vector<SMixFlacTile> &tiles, size_t lds,
                           const int *rows, void *out, int interp, int dtype, uint64_t algorithmic_bytes);
+int smix_flac_last_launch(aukit_ctx *ctx, const int *rows, const unsigned long long *d_at, unsigned n, int *d_pairs);
 
 // ------------------------------------------------------------------ host
 // what smix_tail_shape refuses of a rate (why: its return code), in words: the codec's name, who takes the stream instead and — where the batch's
@@ -100,6 +101,17 @@ int check_smix_stream(const aukit_codec_desc *d, uint64_t nb, bool mono) {
         size_t lds = 0;
         // what smix_qoa_classes refuses of a file, in its words
         return smix_tail_refusal(smix_qoa_class_shape(d->channels, d->sample_rate, &K, &lds), "QOA", d->sample_rate, "aukit_stream_open takes this stream");
+    }
+    if (d->codec == AUKIT_CODEC_FLAC) {  // a stream set's member (the mixed call reads a file's STREAMINFO instead): the descriptor carries its figures
+        if (d->channels < 1 || d->channels > 8) return fail(AUKIT_E_UNSUPPORTED, "FLAC channel count %d", d->channels);
+        if (d->bit_depth == 32) return fail(AUKIT_E_UNSUPPORTED, "FLAC stream of 32 bits whose rows are doubles: aukit_stream_open takes this stream");
+        if (d->bit_depth != 8 && d->bit_depth != 16 && d->bit_depth != 24) return fail(AUKIT_E_UNSUPPORTED, "FLAC sample depth %d: a stream set takes 8, 16 and 24 bits: aukit_stream_open takes this stream", d->bit_depth);
+        if (!(d->sample_rate >= 1 && d->sample_rate <= 1048575) || d->sample_rate != std::floor(d->sample_rate))
+            return fail(AUKIT_E_ARG, "FLAC sample rate %g: a STREAMINFO block holds 1 to 1048575 Hz", d->sample_rate);
+        SMixFlacClass K;
+        size_t lds = 0;
+        // what smix_flac_classes refuses of a file, in its words
+        return smix_tail_refusal(smix_flac_class_shape(d->sample_rate, d->bit_depth, &K, &lds), "FLAC", d->sample_rate, "aukit_stream_open takes this stream");
     }
     if (d->codec == AUKIT_CODEC_PCM) {
         int rc;
@@ -175,6 +187,11 @@ struct SMixQoa {
 // of `*out`; it is the call's last kernel — behind the QOA tail where the batch has QOA members too: the two tails write disjoint rows and either
 // order gives the same audio, this one keeps the QOA tail's launch where it was.  Their calls are marked SMIX_CLS_FLAC: k_stream_mixed gets no tile for
 // them, and a batch of FLAC streams alone launches no k_stream_mixed.
+// A stream set's member is the REST of a longer stream: a canonical 42-byte header, then whole frames from some iterator call's start on.  Its byte
+// count is the carry's; `pos` starts at the carry's flac_pos; its first job reads the carry's pair as table indices -1 and 0 — uploaded into the
+// int32 rows buffer behind the rows, where the job's offsets point (k_smix_flac_tail's arithmetic is the same).  For a stream that asks
+// (flac_back) `last` behind every call is copied into a device table (k_smix_flac_last, smix_flac_hand_back) and handed back with the byte behind
+// every call's last frame and its `pos`.  A value beyond int32 is then the stream's own verdict: no chunk, AUKIT_E_UNSUPPORTED as its status.
 //
 // the FLAC streams of the batch, in batch order, as the header pass found them (smix_validate), their decode (flac_smix_decode) and what is planned from that
 struct SMixFlac {
@@ -187,6 +204,10 @@ struct SMixFlac {
     size_t lds = 0;                       // the largest class's
     std::vector<std::vector<SMixFlacChunk>> plan;   // per entry of `list`
     uint64_t row_bytes = 0;               // of the decoded rows
+    // a stream set's batch (a carry): the decode's table of byte counts and carried pairs, per entry of `list`; where `last` lives behind every
+    // frame of the streams that asked for their boundaries (smix_flac_jobs' `after`)
+    std::vector<FlacSetIn> set;
+    std::vector<std::vector<SMixFlacLast>> after;
 };
 
 // a stream set's member: its slot holds at least the bytes its carry names
@@ -219,14 +240,19 @@ static int smix_validate(aukit_ctx *ctx, const aukit_batch *in, const aukit_code
     // the decoders' tables, ctx->tmp_buf and ctx->tmp_buf3 among them — hence in front of the QOA count pass, whose words in tmp_buf3 its fill pass
     // reads again, and of the other pre-passes' scratch) and can still refuse, by stream index
     if (!FS.list.empty()) {
+        if (carry)
+            for (uint32_t s : FS.list) {
+                if ((rc = smix_check_carry(in, carry, s))) return rc;
+                FS.set.push_back(FlacSetIn{carry[s].nbytes, carry[s].flac_last_on, {carry[s].flac_last[0], carry[s].flac_last[1]}});
+            }
         AUKIT_HIP_CHECK(hipSetDevice(ctx->device));
-        if ((rc = flac_mixed_headers(ctx, in, FS.list, FS.F, "aukit_stream_decode"))) return rc;
+        if ((rc = flac_mixed_headers(ctx, in, FS.list, FS.F, "aukit_stream_decode", carry ? &FS.set : nullptr))) return rc;
         for (size_t i = 0; i < FS.list.size(); i++) ch_of[FS.list[i]] = FS.F[i].channels;
         if (mono)
             for (size_t i = 0; i < FS.list.size(); i++)
                 if (FS.F[i].channels != 1)
                     return fail(AUKIT_E_ARG, "streams differ in channel count: stream.flac ignores `mono` and stream %u has %d channels: split the batch", FS.list[i], FS.F[i].channels);
-        if ((rc = flac_smix_decode(ctx, in, FS.list, FS.F, FS.frames))) return rc;
+        if ((rc = flac_smix_decode(ctx, in, FS.list, FS.F, FS.frames, carry ? &FS.set : nullptr))) return rc;
         for (const FlacMixedStream &f : FS.F) FS.row_bytes += f.frames * (uint64_t)f.channels * 4;
     }
     // QOA: only `codec` of the descriptor is read.  The count pass of the device walk on these streams, and the header read-back: what stream_qoa
@@ -380,6 +406,7 @@ static int smix_flac_classes(SMixFlac &FS) {
     for (size_t i = 0; i < FS.list.size(); i++) {
         const FlacMixedStream &f = FS.F[i];
         const unsigned s = FS.list[i];
+        if (FS.frames[i].wide) { FS.cls_of[i] = 0; continue; }   // (a stream set's member: its own verdict, no call, no class)
         bool fresh;
         FS.cls_of[i] = index.of({f.rate, f.depth}, &fresh);
         if (!fresh) continue;
@@ -643,7 +670,7 @@ static void smix_plan(const aukit_batch *in, const aukit_codec_desc *descs, cons
     for (uint32_t s = 0; s < in->n; s++) {
         const aukit_codec_desc &d = descs[s];
         const uint64_t nb = smix_nbytes(in, carry, s);
-        const SMixCarry cy = carry ? carry[s] : SMixCarry{0, 0, nb, 0, 0, {0, 0, 0, 0, 0, 0}, 0, 0, 0, {0}};
+        const SMixCarry cy = carry ? carry[s] : SMixCarry{0, 0, nb, 0, 0, {0, 0, 0, 0, 0, 0}, 0, 0, 0, {0}, 0, 0, {0, 0}, 0};
         pl.in_bytes += nb;
         SMixSeg g;
         memset(&g, 0, sizeof g);
@@ -689,13 +716,15 @@ static int plan_qoa(SMixPlan &pl, SMixQoa &QS, const SMixCarry *carry) {
 // stream_flac's plan (flac.hip) for every FLAC stream, from the frame lists: the chunk table by its loop (smix_flac_plan_stream), the length
 // nsamples / rate (:3190), status 0 whatever ended the chain — the iterator swallows the error —, and the class's longest job.  The calls join the
 // plan as segments in the stream's place (a QOA stream has none yet: plan_qoa comes behind)
-static int plan_flac(SMixPlan &pl, SMixFlac &FS) {
+// `carry`: a stream set's member starts `pos` from what its dropped calls summed up; one the decoder found wide has no call and its verdict as status
+static int plan_flac(SMixPlan &pl, SMixFlac &FS, const SMixCarry *carry) {
     FS.plan.resize(FS.list.size());
     for (size_t fi = 0; fi < FS.list.size(); fi++) {
         const uint32_t s = FS.list[fi];
         const FlacMixedStream &f = FS.F[fi];
         const FlacSMixFrames &fr = FS.frames[fi];
-        if (!smix_flac_plan_stream(f.rate, fr.bs.data(), fr.bs.size(), FS.plan[fi])) return fail_for_stream(fail(AUKIT_E_UNSUPPORTED, "stream too long"), s);
+        if (fr.wide) { pl.ck->status[s] = AUKIT_E_UNSUPPORTED; continue; }   // (a stream set's member only: the public call was refused by the decode)
+        if (!smix_flac_plan_stream(f.rate, fr.bs.data(), fr.bs.size(), FS.plan[fi], carry ? carry[s].flac_pos : 0)) return fail_for_stream(fail(AUKIT_E_UNSUPPORTED, "stream too long"), s);
         pl.ck->length_seconds[s] = fr.nsamples / f.rate;
         for (const SMixFlacChunk &c : FS.plan[fi]) {
             SMixSeg g;
@@ -924,16 +953,19 @@ static int smix_qoa_tail(aukit_ctx *ctx, SMixQoa &QS, const SMixScratch &L, cons
 
 // ---- phase 10: the FLAC streams' tail, the call's last kernel: a job per (frame, channel) with `last` chained and its place in the audio's rows, tiles,
 // the exact_div_verified verdict of every class over its longest job, one launch.  (Behind the QOA tail: the two write disjoint rows)
-static int smix_flac_tail(aukit_ctx *ctx, SMixFlac &FS, const aukit_audio *a, int interp, int dtype) {
+static int smix_flac_tail(aukit_ctx *ctx, SMixFlac &FS, const aukit_audio *a, int interp, int dtype, const SMixCarry *carry) {
     std::vector<SMixFlacJob> jobs;
     std::vector<SMixFlacTile> tiles;
     uint64_t out_elems = 0;
+    FS.after.assign(FS.list.size(), {});
     for (size_t i = 0; i < FS.list.size(); i++) {
         const uint32_t s = FS.list[i];
         const FlacMixedStream &f = FS.F[i];
         const FlacSMixFrames &fr = FS.frames[i];
+        if (fr.wide) continue;
         const uint64_t stride = round_up(std::max<uint64_t>(f.frames, 1), 4);
-        if (!smix_flac_jobs(FS.classes[FS.cls_of[i]], FS.cls_of[i], f.channels, fr.bs.data(), fr.at.data(), fr.bs.size(), f.row / 4, stride, a->row_off[s], a->row_stride[s], jobs, tiles))
+        if (!smix_flac_jobs(FS.classes[FS.cls_of[i]], FS.cls_of[i], f.channels, fr.bs.data(), fr.at.data(), fr.bs.size(), f.row / 4, stride, a->row_off[s], a->row_stride[s], jobs, tiles,
+                            fr.last_at, carry && carry[s].flac_back ? &FS.after[i] : nullptr))
             return fail(AUKIT_E_HIP, "internal: a FLAC frame leaves its row (stream %u)", s);
         for (const SMixFlacChunk &c : FS.plan[i]) out_elems += c.nout * (uint64_t)f.channels;
     }
@@ -990,6 +1022,47 @@ static int smix_qoa_hand_back(aukit_ctx *ctx, const SMixQoa &QS, const SMixScrat
     return AUKIT_OK;
 }
 
+// a stream set's batch, behind the FLAC tail's planning (FS.after) and the decode (the rows are complete in stream order): `last` behind every call
+// of the streams that asked, the byte behind every call's last frame and its `pos`, handed back.  One small launch for all members, nothing is
+// awaited: the set copies the table out in front of its pump's wait.  Offsets and pairs live in ctx->fmix_back
+static int smix_flac_hand_back(aukit_ctx *ctx, const SMixFlac &FS, const SMixCarry *carry, uint32_t n, SMixDfBack *back) {
+    back->flac_first.assign(n, ~0ull); back->flac_call0.assign(n, ~0ull); back->flac_calls.assign(n, 0);
+    back->flac_end.clear(); back->flac_pos.clear();
+    back->flac_dev = nullptr; back->flac_pairs = 0;
+    std::vector<unsigned long long> at;
+    const uint64_t rows_elems = ctx->fmix_rows.cap / 4;
+    for (size_t i = 0; i < FS.list.size(); i++) {
+        const uint32_t s = FS.list[i];
+        const FlacSMixFrames &fr = FS.frames[i];
+        if (!carry[s].flac_back || fr.wide) continue;
+        back->flac_first[s] = at.size() / 2; back->flac_call0[s] = back->flac_end.size(); back->flac_calls[s] = (uint32_t)FS.plan[i].size();
+        uint64_t cum = 0;
+        for (const SMixFlacChunk &c : FS.plan[i]) {
+            const bool took = c.frames != 0;
+            cum += c.frames;
+            SMixFlacLast L{fr.last_at, fr.last_at == ~0ull ? ~0ull : fr.last_at + 1};   // (no frame so far: what the stream started from)
+            if (cum && cum - 1 < FS.after[i].size()) L = FS.after[i][cum - 1];
+            if ((L.l1 != ~0ull && L.l1 >= rows_elems) || (L.l2 != ~0ull && L.l2 >= rows_elems)) return fail(AUKIT_E_HIP, "internal: a FLAC boundary pair leaves the rows (stream %u)", s);
+            at.push_back(L.l1); at.push_back(L.l2);
+            back->flac_end.push_back(took && cum - 1 < fr.end.size() ? (uint64_t)fr.end[cum - 1] : 0ull);
+            back->flac_pos.push_back(c.pos);
+        }
+    }
+    if (at.empty()) return AUKIT_OK;
+    if (at.size() / 2 > 0x7FFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
+    const size_t pairs_at = (size_t)round_up(at.size() * 8, 256);
+    int rc;
+    if ((rc = ctx->fmix_back.ensure(pairs_at + at.size() * 4 + 64))) return rc;
+    char *const B = reinterpret_cast<char *>(ctx->fmix_back.p);
+    if ((rc = h2d_table(ctx, B, at.data(), at.size() * 8))) return rc;
+    if ((rc = smix_flac_last_launch(ctx, reinterpret_cast<const int *>(ctx->fmix_rows.p), reinterpret_cast<const unsigned long long *>(B), (unsigned)(at.size() / 2),
+                                    reinterpret_cast<int *>(B + pairs_at))))
+        return rc;
+    back->flac_dev = reinterpret_cast<const int32_t *>(B + pairs_at);
+    back->flac_pairs = at.size() / 2;
+    return AUKIT_OK;
+}
+
 // the call itself.  `carry` (null: the public call, every stream counted from byte 0): per stream, what a stream set has dropped in front of the
 // bytes and how many of the slot's bytes are the stream's (mixed_plan.h); a DFPWM stream's carry may hold the decoder's state in front of the bytes
 // and ask for the states at this decode's call boundaries, which `back` then names (the set's next carry comes from there).  A batch in which no
@@ -1002,11 +1075,12 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
     SMixQoa QS;
     SMixFlac FS;
     std::vector<int> ch_of;
-    if (carry) {   // a stream set's one mask: the QOA bit is the frame mask's
+    if (carry) chain_codecs = 0;   // (a stream set keeps refusing the codec, unless it was opened under AUKIT_OPT_STREAMSET_CHAIN_CODECS: the bit is its one mask's, below)
+    if (carry) {   // a stream set's one mask: the QOA bit is the frame mask's, the FLAC bit the chain mask's
         frame_codecs |= block_codecs & (1u << AUKIT_CODEC_QOA);
-        block_codecs &= ~(1u << AUKIT_CODEC_QOA);
+        chain_codecs = block_codecs & (1u << AUKIT_CODEC_FLAC);
+        block_codecs &= ~((1u << AUKIT_CODEC_QOA) | (1u << AUKIT_CODEC_FLAC));
     }
-    if (carry) chain_codecs = 0;   // (a stream set keeps refusing the codec)
     if ((rc = smix_validate(ctx, in, descs, n_descs, interp, mono, dtype, out, carry, block_codecs, frame_codecs, chain_codecs, QS, FS, ch_of))) return rc;
     const uint32_t n = in->n;
     const bool qoa = !QS.list.empty(), flac = !FS.list.empty();
@@ -1025,7 +1099,7 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
     const int C_out = mono ? 1 : (n ? ch_of[0] : 1);
     SMixPlan pl(n);
     smix_plan(in, descs, carry, T.cls_of, interp, mono != 0, ima_bad, pl);
-    if (flac && (rc = plan_flac(pl, FS))) return rc;   // the FLAC streams' calls join the plan
+    if (flac && (rc = plan_flac(pl, FS, carry))) return rc;   // the FLAC streams' calls join the plan
     uint64_t nt = smix_count_tiles(T, pl);
     if (nt > 0xFFFFFFF0ull || pl.ima_jobs > 0x7FFFFFF0ull * 64 || pl.ms.units.size() > 0x7FFFFFF0ull || pl.df_states > 0x7FFFFFF0ull) return fail(AUKIT_E_UNSUPPORTED, "too many tiles");
     if (pl.df_states && !back) return fail(AUKIT_E_ARG, "null argument");
@@ -1063,7 +1137,8 @@ int stream_decode_mixed_carry(aukit_ctx *ctx, const aukit_batch *in, const aukit
         if ((rc = smix_launch(ctx, in, T, pl, tiles, L, a, interp, dtype))) return rc;
     }
     if (qoa && (rc = smix_qoa_tail(ctx, QS, L, a, mono != 0, interp, dtype))) return rc;
-    if (flac && (rc = smix_flac_tail(ctx, FS, a, interp, dtype))) return rc;
+    if (flac && (rc = smix_flac_tail(ctx, FS, a, interp, dtype, carry))) return rc;
+    if (flac && carry && back && (rc = smix_flac_hand_back(ctx, FS, carry, n, back))) return rc;
     chunks_deliver(pl.ck, chunks);   // the caller's table is replaced
     return AUKIT_OK;
 }

@@ -71,15 +71,18 @@ static inline uint64_t smix_flac_frame_out(uint32_t bs, double ratio) { return (
 // #chunk[1] < sampleRate (:3161); the end of the frames kills the coroutine, and that last call returns what it has (possibly nothing);
 // pos is summed from 0 and delivered behind the call's own outputs (:3188).
 // -> false: a call of more than 0x7FFFFFF0 outputs ("stream too long")
-struct SMixFlacChunk { uint64_t nout; double pos; };
-static inline bool smix_flac_plan_stream(double rate, const uint32_t *bs, size_t nframes, std::vector<SMixFlacChunk> &plan) {
+// pos0: a stream set's member is the rest of a longer stream — `pos` carries on from the double the dropped calls summed up (0 otherwise).
+// `frames`: how many frames the call took
+struct SMixFlacChunk { uint64_t nout; double pos; uint64_t frames; };
+static inline bool smix_flac_plan_stream(double rate, const uint32_t *bs, size_t nframes, std::vector<SMixFlacChunk> &plan, double pos0 = 0) {
     const double ratio = 48000 / rate;
     plan.clear();
     size_t f = 0;
     bool dead = false;
-    double pos = 0;
+    double pos = pos0;
     while (!dead) {
         uint64_t got = 0;
+        const size_t f0 = f;
         while ((double)got < rate) {
             if (f >= nframes) { dead = true; break; }
             got += smix_flac_frame_out(bs[f], ratio);
@@ -87,7 +90,7 @@ static inline bool smix_flac_plan_stream(double rate, const uint32_t *bs, size_t
             if (got > 0x7FFFFFF0ull) return false;
         }
         pos = pos + (double)got / 48000;
-        plan.push_back(SMixFlacChunk{got, pos});
+        plan.push_back(SMixFlacChunk{got, pos, (uint64_t)(f - f0)});
     }
     return true;
 }
@@ -96,9 +99,14 @@ static inline bool smix_flac_plan_stream(double rate, const uint32_t *bs, size_t
 // frame f's sample offset within a row.  out0: element of the stream's output 0, channel 0; out_stride: elements between its output channels.
 // A job without an output (a one-sample frame above 48 kHz) gets no tile and still moves `last`.
 // -> false: a frame that leaves its row (the decoder's lists disagree: nothing is appended for it)
+// first_last: where the rest of a stream set's member finds the `last` it starts from — int32 element first_last of the rows holds last[1], the next
+// last[2] — in place of the initial 0, 0 (~0: a stream from its start).  after (optional): per frame, where last[1] and last[2] live behind its last
+// channel (~0: still the initial 0) — a set's call boundaries are read from there (k_smix_flac_last)
+struct SMixFlacLast { uint64_t l1, l2; };
 static inline bool smix_flac_jobs(const SMixFlacClass &K, unsigned cls, int channels, const uint32_t *bs, const uint64_t *at, size_t nframes, uint64_t row0, uint64_t row_stride,
-                                  uint64_t out0, uint64_t out_stride, std::vector<SMixFlacJob> &jobs, std::vector<SMixFlacTile> &tiles) {
-    uint64_t op = 0, l1 = ~0ull, l2 = ~0ull;   // where last[1], last[2] live in the rows (~0: the initial 0)
+                                  uint64_t out0, uint64_t out_stride, std::vector<SMixFlacJob> &jobs, std::vector<SMixFlacTile> &tiles, uint64_t first_last = ~0ull,
+                                  std::vector<SMixFlacLast> *after = nullptr) {
+    uint64_t op = 0, l1 = first_last, l2 = first_last == ~0ull ? ~0ull : first_last + 1;   // where last[1], last[2] live in the rows (~0: the initial 0)
     for (size_t f = 0; f < nframes; f++) {
         if (at[f] + bs[f] > row_stride) return false;
         const uint64_t nout = smix_flac_frame_out(bs[f], K.ratio);
@@ -116,6 +124,7 @@ static inline bool smix_flac_jobs(const SMixFlacClass &K, unsigned cls, int chan
             else if (bs[f] == 1) { l1 = l2; l2 = j.src_off; }
         }
         op += nout;
+        if (after) after->push_back(SMixFlacLast{l1, l2});
     }
     return true;
 }

@@ -125,4 +125,24 @@ int smix_flac_tail_launch(aukit_ctx *ctx, const std::vector<SMixFlacClass> &clas
     });
 }
 
+// k_smix_flac_last: for a stream set, behind a decode — pair i of `pairs` is `last` (:3183) behind an iterator call: the rows' elements at[2 i] and
+// at[2 i + 1], which the host planned from smix_flac_jobs' l1, l2 behind that call's last job (the one-sample-block shift included; inside the
+// rows, or the carried pair behind them; ~0: still the initial 0).  One lane per (member, call boundary).  Plain vector loads and stores only
+__global__ __launch_bounds__(256) void k_smix_flac_last(const int *__restrict__ rows, const unsigned long long *__restrict__ at, unsigned n, int *__restrict__ pairs) {
+    const unsigned i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long a = at[2 * (size_t)i], b = at[2 * (size_t)i + 1];
+    pairs[2 * (size_t)i] = a != ~0ull ? rows[a] : 0;
+    pairs[2 * (size_t)i + 1] = b != ~0ull ? rows[b] : 0;
+}
+
+int smix_flac_last_launch(aukit_ctx *ctx, const int *rows, const unsigned long long *d_at, unsigned n, int *d_pairs) {
+    int rc;
+    if (!n) return AUKIT_OK;
+    if ((rc = ctx_begin_kernel(ctx))) return rc;
+    hipLaunchKernelGGL(k_smix_flac_last, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, rows, d_at, n, d_pairs);
+    AUKIT_HIP_CHECK(hipGetLastError());
+    return ctx_end_kernel(ctx, "k_smix_flac_last", (uint64_t)n * 32);
+}
+
 }  // namespace aukit

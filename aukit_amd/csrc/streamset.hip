@@ -54,12 +54,29 @@
 // that ends inside a frame just yields the calls before it — and a frame of more than 8192 samples is the member's own verdict from the walk.
 // The walk's two read-backs (count, call records) are two more waits in a pump that decodes such members, as the header scan is one for
 // stream.adpcm members and the flag read-back one for stream.msadpcm members.
+//
+// stream.flac members (AUKIT_CODEC_FLAC; only a set opened on a context that set AUKIT_OPT_STREAMSET_CHAIN_CODECS has them — the set keeps that bit in its
+// one mask and hands it to the engine, so AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS is not needed): the descriptor carries STREAMINFO's channel count, depth and
+// rate.  aukit_streamset_feed walks the metadata blocks on the host as the bytes arrive (sset_flac.h: k_flac_header's walk, resumable); none of them
+// is staged, and until the walk has passed the last block the member enters no pump.  Then the member is checked — magic, STREAMINFO present, its
+// figures against the descriptor's: a member that fails ends alone — and its slot starts with a canonical 42-byte header ("fLaC", one last-block
+// STREAMINFO header, the file's winning 34 bytes), staged once and written again by every repack that drops bytes (a 42-byte staging segment, the
+// rest's own segment starting 42 bytes in, as head7): a file with megabytes of cover art costs the set 42 bytes.  All that crosses an iterator call
+// are `last` — two integers of the decoder's int32 rows, shared across channels and frames (:3183) — and `pos`, summed as a double (:3188).  The
+// member carries both (restart lead 0, where the handle restarts a call early): the engine reports `last` behind every call of a decode
+// (k_smix_flac_last into a device table, copied to pinned memory in front of the pump's wait, as the QOA pairs are), the byte behind every call's
+// last frame and its `pos`; the compaction plan (smix_flac_drop) drops the decided calls up to the last such byte that is known — where the decoder
+// reports none the rest is not cut there.  An unfinished member is decoded with all its resident bytes; a chain that ends inside a frame or in a
+// frame error just ends the prefix, and a finished member delivers what the string call delivers, status 0 (stream.flac swallows the error).  A
+// value beyond int32 is the member's own verdict from the decode.  The set adds no wait of its own: a pump that decodes such members waits where
+// the engine waits for them — the header pass's read-back and the decoders' read-backs.
 #include <algorithm>
 #include <deque>
 #include "mixed_plan.h"
 #include "ms_geom.h"
 #include "stream_mixed_qoa.h"
 #include "flac_mixed.h"
+#include "sset_flac.h"
 
 namespace aukit {
 
@@ -186,12 +203,21 @@ struct SSetMember {
     bool qoa_checked = false, qoa_last_on = false;
     uint64_t samples_dropped = 0;
     signed char qoa_last[2 * AUKIT_MAX_PLANAR_CHANNELS] = {0};
+    // stream.flac: the metadata walk; once it is through and the member checked (flac_ready), the canonical header every rest starts with; `pos` as the
+    // dropped calls summed it; `last` in front of the rest, valid once calls were dropped
+    SSetFlacWalk flac_walk;
+    bool flac_ready = false, flac_last_on = false;
+    unsigned char flac_head[SSET_FLAC_HEAD] = {0};
+    double flac_pos = 0;
+    int32_t flac_last[2] = {0, 0};
     std::deque<SSetChunk> q;
 };
 // a compaction planned in front of the pump's wait: member s's next state is entry `entry` of the states the pump downloads
 struct SSetDfFix { uint32_t s; size_t entry; };
 // ... and a stream.qoa member's next two samples per channel are pairs `pair` .. `pair` + channels - 1 of the pairs the pump downloads
 struct SSetQoaFix { uint32_t s; size_t pair; };
+// ... and a stream.flac member's next `last` is pair `pair` of the pairs the pump downloads
+struct SSetFlacFix { uint32_t s; size_t pair; };
 
 }  // namespace aukit
 
@@ -199,7 +225,8 @@ struct aukit_streamset {
     aukit_ctx *ctx = nullptr;
     int interp = 0, mono = 0, dtype = AUKIT_F64;
     // the codecs the set takes on request, as the context's masks were when it was opened: AUKIT_OPT_STREAMSET_BLOCK_CODECS's bit (1 << AUKIT_CODEC_MSADPCM)
-    // and AUKIT_OPT_STREAMSET_FRAME_CODECS's (1 << AUKIT_CODEC_QOA) — distinct bits, so one mask holds both, and the engine gets this one mask
+    // and AUKIT_OPT_STREAMSET_FRAME_CODECS's (1 << AUKIT_CODEC_QOA) — distinct bits, so one mask holds both, and the engine gets this one mask;
+    // AUKIT_OPT_STREAMSET_CHAIN_CODECS's (1 << AUKIT_CODEC_FLAC) is a third bit of it
     unsigned block_codecs = 0;
     std::vector<aukit::SSetMember> m;
     // pinned host staging of what was fed since the last pump, and its device copy
@@ -226,6 +253,10 @@ struct aukit_streamset {
     signed char *qoa_host = nullptr;
     size_t qoa_host_cap = 0;
     std::vector<aukit::SSetQoaFix> qoa_fix;
+    // the same for the FLAC boundary pairs (two int32 each)
+    int32_t *flac_host = nullptr;
+    size_t flac_host_cap = 0;
+    std::vector<aukit::SSetFlacFix> flac_fix;
 };
 
 namespace aukit {
@@ -256,6 +287,12 @@ static void sset_apply_states(aukit_streamset *S) {
         M.qoa_last_on = true;
     }
     S->qoa_fix.clear();
+    for (const SSetFlacFix &f : S->flac_fix) {
+        SSetMember &M = S->m[f.s];
+        M.flac_last[0] = S->flac_host[f.pair * 2]; M.flac_last[1] = S->flac_host[f.pair * 2 + 1];
+        M.flac_last_on = true;
+    }
+    S->flac_fix.clear();
 }
 
 // restart_rule's PCM / G.711 / IMA / DFPWM / MS-ADPCM cases (stream_handle.hip): the bytes of a whole iterator call, and whether the rest starts one call early
@@ -269,8 +306,8 @@ static void sset_restart(SSetMember &M, int interp) {
         M.call_bytes = (uint64_t)d.sample_rate * C;
     } else if (d.codec == AUKIT_CODEC_DFPWM) {
         M.call_bytes = 6000 * C;   // lead 0: the rest starts at the next call, with the decoder's state and its last output carried (df_state)
-    } else if (d.codec == AUKIT_CODEC_QOA) {
-        M.call_bytes = 0;   // lead 0, and no constant: the walk reports where every call ends
+    } else if (d.codec == AUKIT_CODEC_QOA || d.codec == AUKIT_CODEC_FLAC) {
+        M.call_bytes = 0;   // lead 0, and no constant: the walk (the decoder) reports where every call ends
     } else if (d.codec == AUKIT_CODEC_MSADPCM) {
         const double spb = C == 2 ? (double)(d.block_align - 14) : (double)(d.block_align - 7) * 2;   // :2617 / :2682 (MsGeom's)
         M.call_bytes = (uint64_t)std::ceil(d.sample_rate / spb) * (uint64_t)d.block_align;            // lead 0: every block decodes alone
@@ -322,6 +359,30 @@ static int sset_qoa_header(const SSetMember &M) {
     return AUKIT_OK;
 }
 
+// A stream.flac member whose metadata walk is through (or whose bytes end where the walk counts as through): magic, STREAMINFO and its figures against
+// the descriptor's.  The member either ends here, alone — its status and words set, nothing staged — or is ready: the canonical header is made and the
+// length known.  No device call, and the thread's last error is left alone (this runs inside aukit_streamset_feed, which succeeds either way)
+static void sset_flac_checked(SSetMember &M, int status) {
+    auto end = [&](int rc, const std::string &msg) { M.over = true; M.end_status = rc; M.end_msg = msg; };
+    switch (status) {
+    case 0: break;
+    case 2: return end(AUKIT_E_LUA, "Invalid magic string");
+    case 3: return end(AUKIT_E_LUA, "Stream info metadata block absent");
+    case 5: return end(AUKIT_E_LUA, "data string too short");
+    default: return end(AUKIT_E_LUA, "attempt to perform arithmetic on a nil value");
+    }
+    const SSetFlacInfo I = sset_flac_info(M.flac_walk.info);
+    if (I.channels != M.desc.channels || I.depth != M.desc.bit_depth || I.rate != M.desc.sample_rate) {
+        char words[256];
+        snprintf(words, sizeof words, "the FLAC STREAMINFO names %d channels of %d bits at %g Hz, the member's descriptor %d channels of %d bits at %g Hz", I.channels, I.depth, I.rate,
+                 M.desc.channels, M.desc.bit_depth, M.desc.sample_rate);
+        return end(AUKIT_E_ARG, words);
+    }
+    sset_flac_canon(M.flac_walk.info, M.flac_head);
+    M.length = I.nsamples / I.rate;   // :3190
+    M.flac_ready = true;
+}
+
 struct SSetJob { uint32_t s; uint64_t usable; bool all_decided, ends; int end_status; std::string end_msg; };
 
 static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
@@ -351,6 +412,8 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
             size_t hn = 0;
             if (M.drop && M.desc.codec == AUKIT_CODEC_MSADPCM && M.desc.channels == 1 && M.head7_n == 7) { hsrc = M.head7; hn = 7; }
             if (M.drop && M.desc.codec == AUKIT_CODEC_QOA && M.head12_n >= 8) { hsrc = M.head12; hn = 8; }
+            // a stream.flac member: the canonical header over the last 42 bytes of the dropped frames
+            if (M.drop && M.desc.codec == AUKIT_CODEC_FLAC && M.flac_ready) { hsrc = M.flac_head; hn = SSET_FLAC_HEAD; }
             if (hsrc) {
                 head = std::min<uint64_t>(M.resident, hn);
                 void *p = S->stage;
@@ -418,6 +481,7 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
     for (uint32_t s = 0; s < n; s++) {
         SSetMember &M = S->m[s];
         if (M.over || !(fed[s] || M.finished)) continue;
+        if (M.desc.codec == AUKIT_CODEC_FLAC && !M.flac_ready) continue;   // (still inside its metadata: nothing of it is in the arena)
         if (M.desc.codec == AUKIT_CODEC_QOA && !M.qoa_checked) {
             // the file header, once twelve bytes are in (nothing was dropped yet: the rest is the stream): a member that fails it ends here, alone
             if (M.resident < 12 && !M.finished) continue;
@@ -449,6 +513,7 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
     uint64_t gather_elems = 0;
     S->df_fix.clear();
     S->qoa_fix.clear();
+    S->flac_fix.clear();
     if (!jobs.empty()) {
         const uint32_t nj = (uint32_t)jobs.size();
         std::vector<aukit_codec_desc> descs(nj);
@@ -470,6 +535,11 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
                     memcpy(carry[i].qoa_last, M.qoa_last, sizeof M.qoa_last);
                 }
             }
+            if (M.desc.codec == AUKIT_CODEC_FLAC) {   // `pos` carries on; an unfinished member gets `last` behind every call back, and where the calls end
+                carry[i].flac_pos = M.flac_pos;
+                carry[i].flac_back = jobs[i].ends ? 0 : 1;
+                if (M.flac_last_on) { carry[i].flac_last_on = 1; carry[i].flac_last[0] = M.flac_last[0]; carry[i].flac_last[1] = M.flac_last[1]; }
+            }
             if (M.desc.codec == AUKIT_CODEC_DFPWM && !jobs[i].ends) {   // an unfinished stream.dfpwm member: the states at this decode's call boundaries come back
                 carry[i].df_back = 1;
             }
@@ -488,6 +558,12 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
             S->qoa_host = reinterpret_cast<signed char *>(hp);
             AUKIT_HIP_CHECK(hipMemcpyAsync(S->qoa_host, back.qoa_dev, back.qoa_pairs * 2, hipMemcpyDeviceToHost, ctx->stream));
         }
+        if (back.flac_pairs) {   // ... and the FLAC members' `last`
+            void *hp = S->flac_host;
+            if ((rc = pinned_grow(&hp, &S->flac_host_cap, 0, back.flac_pairs * 2, sizeof(int32_t)))) return rc;
+            S->flac_host = reinterpret_cast<int32_t *>(hp);
+            AUKIT_HIP_CHECK(hipMemcpyAsync(S->flac_host, back.flac_dev, back.flac_pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
+        }
         if (back.entries) {   // the states travel with the pump's one download: queued here, on the set's stream, awaited with the chunks below
             void *hp = S->df_host;
             if ((rc = pinned_grow(&hp, &S->df_host_cap, 0, back.entries * 6, sizeof(int)))) return rc;
@@ -502,7 +578,7 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
             SSetMember &M = S->m[J.s];
             const uint32_t nch = ck.nchunks[i];
             const uint32_t decided = J.all_decided ? nch : (nch ? nch - 1 : 0);
-            M.length = ck.length_seconds[i];
+            if (!(M.desc.codec == AUKIT_CODEC_FLAC && ck.status[i] == AUKIT_E_UNSUPPORTED)) M.length = ck.length_seconds[i];   // (a FLAC member with the decoder's verdict has no plan: its length stays STREAMINFO's)
             M.decoded_total += J.usable;
             M.decoded_usable = J.usable;
             uint64_t before = 0;
@@ -534,6 +610,13 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
                 M.sb_bytes += M.resident; M.resident = 0;
                 continue;
             }
+            if (M.desc.codec == AUKIT_CODEC_FLAC && ck.status[i] == AUKIT_E_UNSUPPORTED) {   // the decoder's verdict on this member (no chunk came back): it ends here, alone
+                M.over = true;
+                M.end_status = ck.status[i];
+                M.end_msg = "FLAC stream with a value beyond int32, whose rows are doubles: aukit_stream_open takes this stream";
+                M.sb_bytes += M.resident; M.resident = 0;
+                continue;
+            }
             if (J.ends) {   // what follows the queued chunks is settled: the member leaves the arena
                 M.over = true;
                 M.end_status = J.end_status ? J.end_status : ck.status[i];
@@ -561,6 +644,23 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
                 M.drop += drop; M.resident -= drop;
                 M.decoded_usable -= drop;
                 M.skip -= (uint32_t)shift;
+                continue;
+            }
+            if (M.desc.codec == AUKIT_CODEC_FLAC) {
+                // stream.flac: the rest starts at the byte behind the last dropped call's last frame, 42 bytes early (the canonical header's place);
+                // `last` behind that call comes from the downloaded pairs behind the wait, `pos` is the double that call returned.  (A prefix whose
+                // chain ended inside a frame or in a frame error came back with the calls before it: not a verdict while more bytes may come)
+                if (back.flac_first.empty() || back.flac_first[i] == ~0ull) continue;   // (no table for this member: it keeps its prefix)
+                const uint64_t c0 = back.flac_call0[i];
+                SMixFlacDrop D;
+                if (!smix_flac_drop(back.flac_end.data() + c0, back.flac_calls[i], shift, M.resident, &D)) continue;
+                for (uint64_t k = 0; k < D.calls; k++) M.sb_outputs += ck.lens[(size_t)i * mc + k];
+                M.flac_pos = back.flac_pos[c0 + D.calls - 1];
+                S->flac_fix.push_back(SSetFlacFix{J.s, (size_t)(back.flac_first[i] + D.calls - 1)});
+                M.sb_bytes += D.bytes;
+                M.drop += D.bytes; M.resident -= D.bytes;
+                M.decoded_usable -= D.bytes;
+                M.skip -= (uint32_t)D.calls;
                 continue;
             }
             if (shift && M.call_bytes && shift * M.call_bytes <= M.resident) {
@@ -611,6 +711,28 @@ static int sset_pump(aukit_streamset *S, uint32_t *n_ready) {
     return AUKIT_OK;
 }
 
+// nbytes (not 0) of member s to the pinned staging buffer: no device call, no wait
+static int sset_stage(aukit_streamset *S, uint32_t s, const uint8_t *bytes, uint64_t nbytes) {
+    SSetMember &M = S->m[s];
+    // the piece starts at the residue modulo 16 it will have in the arena: slots start at multiples of 16, the rest and what is pending lie in front
+    const size_t want = (size_t)((M.resident + M.pending) & 15);
+    size_t at = S->stage_used;
+    at += (want + 16 - (at & 15)) & 15;
+    void *p = S->stage;
+    if (at + nbytes > S->stage_cap) {
+        if (hipSetDevice(S->ctx->device) != hipSuccess) { (void)hipGetLastError(); return fail(AUKIT_E_HIP, "hipSetDevice failed"); }
+        int rc = pinned_grow(&p, &S->stage_cap, S->stage_used, at + (size_t)nbytes, 1);
+        if (rc) return rc;
+        S->stage = reinterpret_cast<unsigned char *>(p);
+    }
+    memcpy(S->stage + at, bytes, (size_t)nbytes);
+    S->stage_used = at + (size_t)nbytes;
+    S->feeds.push_back(SSetFeed{s, (uint64_t)at, nbytes});
+    M.pending += nbytes;
+    M.fed_any = true;
+    return AUKIT_OK;
+}
+
 }  // namespace aukit
 
 using namespace aukit;
@@ -629,13 +751,19 @@ int aukit_streamset_open(aukit_ctx *ctx, const aukit_codec_desc *descs, uint32_t
     const bool with_df = (ctx->streamset_codecs >> AUKIT_CODEC_DFPWM) & 1u, with_ms = (ctx->streamset_block_codecs >> AUKIT_CODEC_MSADPCM) & 1u;
     // AUKIT_OPT_STREAMSET_FRAME_CODECS: stream.qoa members, under a third option; its clause stands behind the others', which read as they do without it
     const bool with_qoa = (ctx->streamset_fcodecs >> AUKIT_CODEC_QOA) & 1u;
-    if ((rc = mixed_check_served(descs, n, sset_served(with_df, with_ms, with_qoa)))) return rc;   // (the sentence and the served set: mixed_words.h)
+    // AUKIT_OPT_STREAMSET_CHAIN_CODECS: stream.flac members, under a fourth option; its clause stands last
+    const bool with_flac = (ctx->streamset_ccodecs >> AUKIT_CODEC_FLAC) & 1u;
+    if ((rc = mixed_check_served(descs, n, sset_served(with_df, with_ms, with_qoa, with_flac)))) return rc;   // (the sentence and the served set: mixed_words.h)
     if ((rc = mixed_check_channels(n, mono, [&](uint32_t s) { return descs[s].channels; }))) return rc;
     for (uint32_t s = 0; s < n; s++)
         if ((rc = check_smix_stream(&descs[s], 0, mono != 0))) return fail_for_stream(rc, s);
+    if (mono)   // the reference ignores `mono` for FLAC (:3124-3191 never reads it): a mono set — one output row per member — takes one-channel FLAC members only
+        for (uint32_t s = 0; s < n; s++)
+            if (descs[s].codec == AUKIT_CODEC_FLAC && descs[s].channels != 1)
+                return fail(AUKIT_E_ARG, "streams differ in channel count: stream.flac ignores `mono` and stream %u has %d channels: split the batch", s, descs[s].channels);
     aukit_streamset *S = new aukit_streamset();
     S->ctx = ctx; S->interp = interp; S->mono = mono ? 1 : 0; S->dtype = dtype;
-    S->block_codecs = (with_ms ? 1u << AUKIT_CODEC_MSADPCM : 0u) | (with_qoa ? 1u << AUKIT_CODEC_QOA : 0u);
+    S->block_codecs = (with_ms ? 1u << AUKIT_CODEC_MSADPCM : 0u) | (with_qoa ? 1u << AUKIT_CODEC_QOA : 0u) | (with_flac ? 1u << AUKIT_CODEC_FLAC : 0u);
     S->m.resize(n);
     for (uint32_t s = 0; s < n; s++) {
         S->m[s].desc = descs[s];
@@ -652,28 +780,29 @@ int aukit_streamset_feed(aukit_streamset *S, uint32_t s, const uint8_t *bytes, u
     if (M.finished) return fail(AUKIT_E_ARG, "aukit_streamset_feed after aukit_streamset_finish");
     if (!nbytes) return AUKIT_OK;
     if (M.over) return AUKIT_OK;   // (a member that has ended on its own words: the bytes have nowhere to go)
-    // the piece starts at the residue modulo 16 it will have in the arena: slots start at multiples of 16, the rest and what is pending lie in front
-    const size_t want = (size_t)((M.resident + M.pending) & 15);
-    size_t at = S->stage_used;
-    at += (want + 16 - (at & 15)) & 15;
-    void *p = S->stage;
-    if (at + nbytes > S->stage_cap) {
-        if (hipSetDevice(S->ctx->device) != hipSuccess) { (void)hipGetLastError(); return fail(AUKIT_E_HIP, "hipSetDevice failed"); }
-        int rc = pinned_grow(&p, &S->stage_cap, S->stage_used, at + (size_t)nbytes, 1);
+    if (M.desc.codec == AUKIT_CODEC_FLAC && !M.flac_ready) {
+        // the metadata is walked, not staged; the piece in which the walk gets through the last block is checked, and what it holds behind the
+        // metadata — frame bytes — is staged behind the canonical header
+        const size_t took = sset_flac_walk(M.flac_walk, bytes, (size_t)nbytes);
+        M.fed_any = true;
+        if (M.flac_walk.bad_magic) { sset_flac_checked(M, 2); return AUKIT_OK; }
+        if (!M.flac_walk.done()) return AUKIT_OK;
+        sset_flac_checked(M, sset_flac_walk_finish(M.flac_walk));
+        if (M.over) return AUKIT_OK;
+        int rc = sset_stage(S, s, M.flac_head, SSET_FLAC_HEAD);
         if (rc) return rc;
-        S->stage = reinterpret_cast<unsigned char *>(p);
+        bytes += took; nbytes -= took;
+        if (!nbytes) return AUKIT_OK;
     }
-    memcpy(S->stage + at, bytes, (size_t)nbytes);
+    int rc = sset_stage(S, s, bytes, nbytes);
+    if (rc) return rc;
     if (M.head7_n < 7 && M.desc.codec == AUKIT_CODEC_MSADPCM && M.desc.channels == 1)   // (nothing is dropped before the first call is whole: these are the stream's first bytes)
         for (uint64_t i = 0; i < nbytes && M.head7_n < 7; i++) M.head7[M.head7_n++] = bytes[i];
     if (M.head12_n < 12 && M.desc.codec == AUKIT_CODEC_QOA)   // (likewise: the file header)
         for (uint64_t i = 0; i < nbytes && M.head12_n < 12; i++) M.head12[M.head12_n++] = bytes[i];
-    S->stage_used = at + (size_t)nbytes;
-    S->feeds.push_back(SSetFeed{s, (uint64_t)at, nbytes});
-    M.pending += nbytes;
-    M.fed_any = true;
     return AUKIT_OK;
 }
+
 
 int aukit_streamset_finish(aukit_streamset *S, uint32_t s) {
     if (!S) return fail(AUKIT_E_ARG, "null argument");
@@ -681,6 +810,12 @@ int aukit_streamset_finish(aukit_streamset *S, uint32_t s) {
     SSetMember &M = S->m[s];
     M.finished = true;
     if (!M.fed_any) M.over = true;   // finished while empty: the iterator's first call returns nil
+    if (M.desc.codec == AUKIT_CODEC_FLAC && !M.flac_ready && !M.over) {
+        // finished inside its metadata: aukit_stream_decode's status and words for those bytes (sset_flac_walk_finish: what k_flac_header says of
+        // them); where the walk counts as through — the last block declares more bytes than came — the member is a header and no frame
+        sset_flac_checked(M, sset_flac_walk_finish(M.flac_walk));
+        if (M.flac_ready) return sset_stage(S, s, M.flac_head, SSET_FLAC_HEAD);
+    }
     return AUKIT_OK;
 }
 
@@ -691,7 +826,7 @@ int aukit_streamset_pump(aukit_streamset *S, uint32_t *n_ready) {
         const std::string msg = aukit_last_error();
         const bool waited = hipStreamSynchronize(S->ctx->stream) == hipSuccess;
         (void)hipGetLastError();
-        if (waited) sset_apply_states(S); else { S->df_fix.clear(); S->qoa_fix.clear(); }
+        if (waited) sset_apply_states(S); else { S->df_fix.clear(); S->qoa_fix.clear(); S->flac_fix.clear(); }
         return fail(rc, "%s", msg.c_str());
     }
     return AUKIT_OK;
@@ -755,6 +890,7 @@ void aukit_streamset_close(aukit_streamset *S) {
     if (S->cache) (void)hipHostFree(S->cache);
     if (S->df_host) (void)hipHostFree(S->df_host);
     if (S->qoa_host) (void)hipHostFree(S->qoa_host);
+    if (S->flac_host) (void)hipHostFree(S->flac_host);
     S->d_stage.release(); S->d_tab.release(); S->d_gather.release();
     delete S;
 }

@@ -22,7 +22,7 @@ typedef struct { int32_t codec, channels; double sample_rate; int32_t bit_depth,
 typedef struct { aukit_codec_desc desc; uint64_t payload_off, payload_len; int32_t wav_data_type, bit_depth; double length_seconds; } aukit_container;
 const char *aukit_last_error(void);
 int aukit_ctx_create(aukit_ctx **out, int device); void aukit_ctx_destroy(aukit_ctx *ctx);
-int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);  /* 9: AUKIT_OPT_STREAM_MIXED_FRAME_CODECS (stream.many's `qoa`); 12: AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS (its `flac`) */
+int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);  /* 9: AUKIT_OPT_STREAM_MIXED_FRAME_CODECS (stream.many's `qoa`); 12: AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS (its `flac`); 13: AUKIT_OPT_STREAMSET_CHAIN_CODECS (stream.set's `flac`) */
 int aukit_parse_container(const uint8_t *bytes, uint64_t n, int kind, int stream, aukit_container *out);
 int aukit_batch_upload(aukit_ctx *, aukit_batch **, const uint8_t *bytes, const uint64_t *offsets, uint32_t n);
 int aukit_batch_info(const aukit_batch *, uint32_t *n, uint64_t *total); int aukit_batch_download(aukit_ctx *, const aukit_batch *, uint8_t *dst); void aukit_batch_free(aukit_batch *);
@@ -1007,16 +1007,58 @@ end
 -- descriptor carries the header's channel count and rate, the whole piece is payload, the pair is aukit.stream.qoa(fn, mono)'s (length file_samples /
 -- sampleRate); for the one open the context is opted in under a third option (AUKIT_OPT_STREAMSET_FRAME_CODECS, option 10, bit 1 << AUKIT_CODEC_QOA)
 -- and put back behind it, also where the open is refused.
+-- FLAC readers (a first piece that starts with "fLaC" and holds the metadata blocks) are taken with the key `flac`, {mono = ..., flac = true}: the
+-- descriptor carries STREAMINFO's channel count, depth and rate (the blocks are walked as the library walks them: a STREAMINFO by its 34 bytes, the last
+-- one wins; a VORBIS_COMMENT by its content; every other block by its declared length), the whole piece is payload, the pair is aukit.stream.flac(fn,
+-- mono)'s (`mono` is not read for FLAC: a set with `mono` takes one-channel FLAC readers only; length samples / sampleRate); for the one open the context
+-- is opted in under a fourth option (AUKIT_OPT_STREAMSET_CHAIN_CODECS, option 13, bit 1 << AUKIT_CODEC_FLAC) and put back behind it, also where the open
+-- is refused.
+local function flac_streaminfo(f)   -- -> channels, depth, rate, samples of the last STREAMINFO; nil where the blocks do not end inside f or none is one
+    local pos, last, nb = 4, false, #f
+    local ch, depth, rate, samples
+    while not last do
+        if pos + 4 > nb then return nil end
+        local t = f:byte(pos + 1)
+        last = t >= 128
+        local kind = t % 128
+        local length = f:byte(pos + 2) * 65536 + f:byte(pos + 3) * 256 + f:byte(pos + 4)
+        pos = pos + 4
+        if kind == 0 then
+            if pos + 34 > nb then return nil end
+            local q10, q11, q12, q13 = f:byte(pos + 11), f:byte(pos + 12), f:byte(pos + 13), f:byte(pos + 14)
+            rate = (q10 * 256 + q11) * 16 + math.floor(q12 / 16)
+            ch = math.floor(q12 / 2) % 8 + 1
+            depth = (q12 % 2) * 16 + math.floor(q13 / 16) + 1
+            samples = f:byte(pos + 15) * 16777216 + f:byte(pos + 16) * 65536 + f:byte(pos + 17) * 256 + f:byte(pos + 18) + (q13 % 16) * 4294967296
+            pos = pos + 34
+        elseif kind == 4 then
+            local comments, i = 0, 0
+            while i <= comments do
+                for field = 0, (i == 0 and 1 or 0) do
+                    if pos + 4 > nb then return nil end
+                    local v = f:byte(pos + 1) + f:byte(pos + 2) * 256 + f:byte(pos + 3) * 65536 + f:byte(pos + 4) * 16777216
+                    pos = pos + 4
+                    if field == 1 then comments = v break end
+                    if v > nb - pos then return nil end
+                    pos = pos + v
+                end
+                i = i + 1
+            end
+        else pos = pos + length end
+    end
+    if pos > nb or not ch then return nil end
+    return ch, depth, rate, samples
+end
 function aukit.stream.set(readers, mono)
     expect(1, readers, "table") expect(2, mono, "boolean", "table", "nil")
-    local dfpwm, msadpcm, qoa = false, false, false
+    local dfpwm, msadpcm, qoa, flac = false, false, false, false
     if type(mono) == "table" then
-        for k in pairs(mono) do if k ~= "mono" and k ~= "dfpwm" and k ~= "msadpcm" and k ~= "qoa" then error("bad argument #2 (unknown option " .. tostring(k) .. ")", 2) end end
+        for k in pairs(mono) do if k ~= "mono" and k ~= "dfpwm" and k ~= "msadpcm" and k ~= "qoa" and k ~= "flac" then error("bad argument #2 (unknown option " .. tostring(k) .. ")", 2) end end
         if (mono.mono ~= nil and type(mono.mono) ~= "boolean") or (mono.dfpwm ~= nil and type(mono.dfpwm) ~= "boolean") or (mono.msadpcm ~= nil and type(mono.msadpcm) ~= "boolean") or
-           (mono.qoa ~= nil and type(mono.qoa) ~= "boolean") then
+           (mono.qoa ~= nil and type(mono.qoa) ~= "boolean") or (mono.flac ~= nil and type(mono.flac) ~= "boolean") then
             error("bad argument #2 (expected boolean options)", 2)
         end
-        mono, dfpwm, msadpcm, qoa = mono.mono, mono.dfpwm or false, mono.msadpcm or false, mono.qoa or false
+        mono, dfpwm, msadpcm, qoa, flac = mono.mono, mono.dfpwm or false, mono.msadpcm or false, mono.qoa or false, mono.flac or false
     end
     local n = #readers
     local descs = ffi.new("aukit_codec_desc[?]", math.max(n, 1))
@@ -1025,6 +1067,7 @@ function aukit.stream.set(readers, mono)
                   or "stream.set takes PCM and G.711 payloads and IMA-ADPCM blocks (the other codecs keep their own streams)"
     if msadpcm then takes = takes:gsub("IMA%-ADPCM blocks", "IMA-ADPCM and MS-ADPCM blocks") end
     if qoa then takes = takes:gsub(" blocks %(", " blocks and QOA files (") end
+    if flac then takes = takes:gsub(" %(the other", " and FLAC files (the other") end
     local fns = {}
     for i = 1, n do
         local e = readers[i]
@@ -1051,6 +1094,12 @@ function aukit.stream.set(readers, mono)
                 descs[i - 1] = desc {codec = "qoa", channels = f:byte(9), sampleRate = rate}
                 firsts[i], done[i] = f, false
                 lengths[i] = (f:byte(5) * 16777216 + f:byte(6) * 65536 + f:byte(7) * 256 + f:byte(8)) / rate
+            elseif flac and f:sub(1, 4) == "fLaC" then   -- the metadata blocks; the whole piece is payload (the set walks the blocks itself)
+                local fch, fdepth, frate, fsamples = flac_streaminfo(f)
+                if not fch then error("reader " .. (i - 1) .. ": the first piece of a FLAC stream holds its metadata blocks, a STREAMINFO among them", 2) end
+                descs[i - 1] = desc {codec = "flac", channels = fch, sampleRate = frate, bitDepth = fdepth}
+                firsts[i], done[i] = f, false
+                lengths[i] = fsamples / frate
             else
             for _, m in ipairs(MAGIC) do if f:find(m[1]) then kind = m[2] break end end
             if not kind then error("reader " .. (i - 1) .. ": not a WAV, AIFF or AU stream", 2) end
@@ -1073,11 +1122,14 @@ function aukit.stream.set(readers, mono)
     if msadpcm then check(C.aukit_ctx_set_option(ctx(), 8, 2 ^ CODEC.msadpcm)) end
     -- qoa: AUKIT_OPT_STREAMSET_FRAME_CODECS (10) with bit 1 << AUKIT_CODEC_QOA, likewise
     if qoa then check(C.aukit_ctx_set_option(ctx(), 10, 2 ^ CODEC.qoa)) end
+    -- flac: AUKIT_OPT_STREAMSET_CHAIN_CODECS (13) with bit 1 << AUKIT_CODEC_FLAC, likewise
+    if flac then check(C.aukit_ctx_set_option(ctx(), 13, 2 ^ CODEC.flac)) end
     local rc = C.aukit_streamset_open(ctx(), descs, n, INTERP[aukit.defaultInterpolation], mono and 1 or 0, F64, sp)
     local words = rc ~= 0 and ffi.string(C.aukit_last_error()) or nil
     if dfpwm then C.aukit_ctx_set_option(ctx(), 7, 0) end
     if msadpcm then C.aukit_ctx_set_option(ctx(), 8, 0) end
     if qoa then C.aukit_ctx_set_option(ctx(), 10, 0) end
+    if flac then C.aukit_ctx_set_option(ctx(), 13, 0) end
     if words then error(words, 2) end
     local set = ffi.gc(sp[0], C.aukit_streamset_close)
     local ready = ffi.new("uint32_t[1]")

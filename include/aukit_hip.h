@@ -198,13 +198,21 @@ typedef enum {
                                    A second option and not a second bit of option 5, which knows its one bit and refuses this one by name.  It opens
                                    neither aukit_stream_decode_mixed nor aukit_streamset_open to anything.  With 0 every call answers exactly as
                                    before. */
-    AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS = 12 /* a third mask of aukit_stream_decode_mixed's, the only call that reads it (a stream set hands its engine 0 and
-                                   keeps refusing the codec): a bit mask of 1 << codec, 0 by default, exactly one bit known, 1 << AUKIT_CODEC_FLAC
+    AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS = 12,/* a third mask of aukit_stream_decode_mixed's, the only call that reads it (a stream set hands its engine 0 and
+                                   keeps refusing the codec, unless it was opened under option 13): a bit mask of 1 << codec, 0 by default, exactly one bit
+                                   known, 1 << AUKIT_CODEC_FLAC
                                    (aukit.stream.flac's files, see that call); any other bit is AUKIT_E_UNSUPPORTED, the codec named (or "bit N"),
                                    and the context keeps the mask it had.  An option of its own: options 6 and 9 know their one bit each and refuse
                                    this one by name.  Options 5 to 11 do not open the stream call to FLAC; this option opens it to nothing else, and
                                    opens neither aukit_decode_resample_mixed (option 11 does) nor aukit_streamset_open.  With 0 every call answers
                                    exactly as before. */
+    AUKIT_OPT_STREAMSET_CHAIN_CODECS = 13 /* a fourth mask of aukit_streamset_open's, read by that call alone and only while it opens (an open set keeps
+                                   what it was opened with and hands its engine that bit; option 12's sentence about a set holds for a set opened
+                                   without this option): a bit mask of 1 << codec, 0 by default, exactly one bit known, 1 << AUKIT_CODEC_FLAC
+                                   (aukit.stream.flac's streams as members of a set, see that call); any other bit is AUKIT_E_UNSUPPORTED, the codec
+                                   named (or "bit N"), and the context keeps the mask it had.  Options 7, 8 and 10 know their one bit each and refuse
+                                   this one by name; options 5 to 12 do not open a set to FLAC; this option opens neither mixed call.  With 0 every
+                                   call answers exactly as before. */
 } aukit_option;
 int aukit_ctx_set_option(aukit_ctx *ctx, int option, int value);
 /* counters of the most recent call that produced them (AUKIT_OPT_COLLECT_STATS = 1) */
@@ -649,6 +657,34 @@ typedef struct aukit_streamset aukit_streamset;
  * arithmetic on a nil value (field '?')".  A frame of more than 8192 samples ends the member alone at the pump that meets it, behind the chunks of
  * earlier pumps, with AUKIT_E_UNSUPPORTED "QOA frame of more than 8192 samples: aukit_stream_open takes this stream".  A pump that decodes such
  * members waits two more times, the walk's two read-backs (count, call records). */
+/* AUKIT_CODEC_FLAC members of a set.
+ * On request, AUKIT_OPT_STREAMSET_CHAIN_CODECS with bit 1 << AUKIT_CODEC_FLAC set on the context when the set is opened, AUKIT_CODEC_FLAC members join
+ * (without the bit every refusal above stands, word for word, whatever options 5 to 12 say; with it a refusal of a further codec names
+ * AUKIT_CODEC_FLAC in its list, behind the clauses of options 7, 8 and 10; sinc stays refused).  AUKIT_OPT_STREAM_MIXED_CHAIN_CODECS is not needed.
+ * Such a member is aukit.stream.flac (aukit.lua:3124-3191).  As for a QOA member the descriptor is described: `channels` (1 .. 8), `sample_rate`
+ * and `bit_depth` are STREAMINFO's.  The open refuses by index a depth that is not 8, 16 or 24 (a depth of 32 means rows of doubles:
+ * "aukit_stream_open takes this stream"), what the mixed call refuses of a file's rate (a warm-up beyond one tile: rates below about 320 Hz), and
+ * — the reference ignores `mono` for FLAC — with `mono` a member of more than one channel (AUKIT_E_ARG, streams differ in channel count); without
+ * `mono` the members agree in channel count.  aukit_streamset_feed walks the metadata blocks on the host as the bytes arrive, in however many
+ * pieces (sset_flac.h: k_flac_header's walk restated, resumable, O(1) state and the 34 STREAMINFO bytes — the last STREAMINFO wins, a
+ * VORBIS_COMMENT is walked by its content, every other block by its declared length); until the walk has passed the last block the member enters
+ * no pump.  Then, before its first batch: a wrong magic ends the member alone with AUKIT_E_LUA "Invalid magic string", an absent STREAMINFO with
+ * AUKIT_E_LUA "Stream info metadata block absent", a channel count, depth or rate that differs from the descriptor's with AUKIT_E_ARG (both
+ * named); a member finished inside its metadata ends with aukit_stream_decode's status and words for those bytes.  The metadata never lives in the
+ * arena: a member's slot starts with a canonical 42-byte header — "fLaC", one last-block STREAMINFO header, the file's winning 34 bytes — written
+ * once to the staging buffer and again, as a 42-byte segment of the one k_sset_repack launch, in front of every rest.  aukit_streamset_length is
+ * STREAMINFO's sample count / rate.  All that crosses an iterator call are `last` — two integers of the decoder's int32 rows, shared by channels
+ * and frames — and the position, summed as a double: the member carries both, the rest starts at the byte behind the last dropped call's last frame
+ * (no call is kept in front of it, where the handle keeps one), which the fused decoders report; where they report none that call is not cut.
+ * The pair of every call boundary is copied out by one launch for all members (k_smix_flac_last) into a table that rides in the pump's one
+ * download.  An unfinished member is decoded with all its resident bytes; a chain that ends inside a frame or in a frame error just ends the
+ * prefix there, and at the finish the member delivers what the string call delivers, with status 0.  A value beyond int32 ends the member alone at
+ * that pump, behind the chunks of earlier pumps, with AUKIT_E_UNSUPPORTED "FLAC stream with a value beyond int32, whose rows are doubles:
+ * aukit_stream_open takes this stream" — no chunk of that pump's decode goes out, not even whole calls in front of the frame that arrived in the same
+ * pump: in this one case how the bytes were cut decides what is delivered, not only when (as for a QOA member's frame of more than 8192 samples).
+ * A pump that decodes such members adds no wait of its own beyond the engine's FLAC header-pass read-back
+ * and the decoders' read-backs.  A chunk may be longer than 48000 samples (a call stops at the first frame that brings it to `rate` outputs):
+ * size `cap` for it, or read `*len` from the AUKIT_E_ARG refusal and call again. */
 int aukit_streamset_open(aukit_ctx *ctx, const aukit_codec_desc *descs /* n */, uint32_t n, int interp, int mono, int dtype, aukit_streamset **out);
 /* host copy only: no device call, no wait (the pinned buffer grows, rarely, outside the steady state).  After aukit_streamset_finish: AUKIT_E_ARG */
 int aukit_streamset_feed(aukit_streamset *set, uint32_t s, const uint8_t *bytes, uint64_t nbytes);
